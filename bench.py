@@ -6,10 +6,15 @@ tail] -> int16 PCM, reference src/rtl_fm.c:1326-1338 + 1179-1272; for `--workloa
 scanner(), src/rtl_power.c:642-720) over one batch of synthetic input that is already resident
 in HBM.
 
-    python bench.py [--workload c2] --gpus N --steps K --warmup W
+    python bench.py [--workload c2] --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Workloads (BASELINE.json `configs`; the default line is north_star's own shape of configs[1]'s chain, and every
+A plain run builds (a no-op when nothing is stale), sets up, warms up, times the K steps and prints the line: `value`,
+`ms_per_step` and the roofline fields that come from the timed launches themselves.  --full adds every leg below.
+--dump-outputs DIR writes what the last timed step computed (FmJob.outputs / PowerJob.outputs) for output-for-output
+comparisons of two builds: the inputs are generated from a fixed seed.
+
+Workloads (BASELINE.json `configs`; the default line is north_star's own shape of configs[1]'s chain, and with --full every
 other BASELINE configuration is timed by the same invocation as a short `also` leg):
 
     ns4096  north_star's target shape: 4096 batched 2.4 MS/s streams x 4 buffers x 262144 B, -F 0 (4x fifth_order,
@@ -24,7 +29,7 @@ Streams are independent: rank r owns its own streams (weak scaling), there is no
 collective; RCCL is used only for the barrier and the max-over-ranks of the elapsed time.
 `python bench.py --gpus N` outside torchrun starts the N ranks itself.
 
-Besides the contract fields the line carries
+Besides the contract fields the line of a --full run carries
   roofline.sustained   the same step repeated for >= --sustain seconds (the short K-step figure is
                        taken right after the warm-up; the GPU sits at its 1.4 kW cap on this path
                        and the clock settles over seconds)
@@ -98,20 +103,39 @@ def parse():
     ap.add_argument("--squelch", type=int, default=None, help="-l N: the power squelch behind the decimator (the front end's emit mode + squelch kernels)")
     ap.add_argument("--atan", choices=["std", "fast", "lut"], default=None)
     ap.add_argument("--path", type=int, default=0, help="0 auto, 1 staged, 2 fused")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    # A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure is a leg of its own,
+    # on by default only under --full (a leg's own option, given explicitly, wins either way)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every optional leg: cpu_baseline with its parity gate, the rocprofv3 PMC passes, the cold and "
+                         "sustained figures, the in-kernel clock and VALU-issue figures, the box's ceilings, the other BASELINE shapes "
+                         "(also) and the PCIe-inclusive e2e leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / float64, rank 0, "
+                         "at most 48 MiB: a fixed, seeded sample of the streams where the whole output is larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--check", type=int, default=1, help="have the cpu_baseline leg compare a slice of the GPU output with the CPU path")
-    ap.add_argument("--sustain", type=float, default=2.0, help="seconds of the sustained leg after the K timed steps (0: skip)")
-    ap.add_argument("--pmc", type=int, default=-1, help="rocprofv3 PMC passes for roofline.traffic: 1 on, 0 off, -1 on for N = 1 when rocprofv3 exists")
-    ap.add_argument("--e2e", type=int, default=1, help="1: also time the PCIe-inclusive push / run / fetch path (N = 1)")
-    ap.add_argument("--ceiling", type=int, default=1, help="1: measure this box's streaming ceilings (roofline.ceiling)")
+    ap.add_argument("--sustain", type=float, default=None,
+                    help="seconds of the sustained leg after the K timed steps (0: skip; default 2 with --full, else 0)")
+    ap.add_argument("--pmc", type=int, default=None,
+                    help="rocprofv3 PMC passes for roofline.traffic: 1 on, 0 off, -1 on for N = 1 when rocprofv3 exists "
+                         "(default -1 with --full, else 0)")
+    ap.add_argument("--e2e", type=int, default=None,
+                    help="1: also time the PCIe-inclusive push / run / fetch path (default 1 with --full, else 0)")
+    ap.add_argument("--ceiling", type=int, default=None,
+                    help="1: measure this box's streaming ceilings, roofline.ceiling (default 1 with --full, else 0)")
     ap.add_argument("--colocate", type=int, default=0, help="1: leave the output wherever the allocator puts it (normally the input's HBM quarter)")
-    ap.add_argument("--also", type=int, default=1, help="1: the default workload also times the other BASELINE shapes (short legs)")
+    ap.add_argument("--also", type=int, default=None,
+                    help="1: the default workload also times the other BASELINE shapes in short legs (default 1 with --full, else 0)")
     ap.add_argument("--also-steps", type=int, default=200, help="timed launches per `also` leg (after 100 untimed)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--scatter", action="store_true",
                     help="N > 1: also time shard.scatter_streams (root GPU -> its owner GPUs) of one step's IQ over RCCL")
     a = ap.parse_args()
+    for k, on in (("sustain", 2.0), ("pmc", -1), ("e2e", 1), ("ceiling", 1), ("also", 1)):
+        if getattr(a, k) is None:
+            setattr(a, k, on if a.full else 0)
+    a.cpu_baseline = a.full and not a.no_cpu_baseline
     if a.boxcar is not None and a.boxcar > 0 and a.passes is None:
         a.passes = 0
     if a.passes is not None and a.passes > 0 and a.boxcar is None:
@@ -800,6 +824,19 @@ def time_scatter(dist, rank, world, dev, streams_per_rank, bytes_per_stream, rep
 
 # ------------------------------------------------------------------- workloads ----
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: the most one job writes
+
+
+def dump_streams(S, row_bytes):
+    """The streams --dump-outputs writes out in full: all of them if they fit DUMP_BYTES, else a sample of as many as fit,
+    drawn with a fixed seed (the same for every run with the same shape), in ascending order."""
+    import numpy as np
+    k = min(S, max(1, DUMP_BYTES // max(row_bytes, 1)))
+    if k == S:
+        return np.arange(S)
+    return np.sort(np.random.default_rng(0).choice(S, k, replace=False))
+
+
 class FmJob:
     """rtl_fm's chain on S streams x NB buffers per step."""
 
@@ -876,6 +913,23 @@ class FmJob:
     def sync(self):
         self.g.sync()
 
+    def outputs(self):
+        """What a caller of run_device holds after the last step: every stream's sample count (pcm_len) and the int16 PCM of
+        the streams dump_streams picks (pcm, row i = stream pcm_streams[i], zero behind that stream's count)."""
+        import numpy as np
+        torch = self.torch
+        S = self.a.streams
+        n = self.out_len.cpu().numpy()
+        if isinstance(self.out, torch.Tensor):
+            pcm, cols = self.out, self.out.shape[1]
+        else:
+            pcm, cols = torch.as_tensor(_DevMem(self.out.ptr, (S, self.out.cols), "<i2"), device=self.out_len.device), self.out.cols
+        m = min(int(n.max()) if S else 0, cols, DUMP_BYTES // 4)
+        rows = dump_streams(S, 4 * m)
+        got = pcm[torch.as_tensor(rows, device=self.out_len.device), :m].cpu().numpy().astype(np.float32)
+        got[np.arange(m)[None, :] >= n[rows][:, None]] = 0
+        return {"pcm": got, "pcm_len": n.astype(np.float64), "pcm_streams": rows.astype(np.float64)}
+
     def gate(self):
         from rtlsdr_amd.capi import RtlfmCfg
         from rtlsdr_amd.demod import GpuDemod
@@ -946,6 +1000,16 @@ class PowerJob:
 
     def sync(self):
         self.g.sync()
+
+    def outputs(self):
+        """What a caller of rtlpower_gpu_fetch receives after the last step, for the streams dump_streams picks: avg[] (row i =
+        stream avg_streams[i]) and samples.  The handle accumulates from scan to scan as scanner() does until csv_dbm()
+        reads and clears, so these are the sums over every step this run made."""
+        import numpy as np
+        rows = dump_streams(self.a.streams, 8 << self.bin_e)
+        got = [self.g.fetch(int(s)) for s in rows]
+        return {"avg": np.stack([g[0] for g in got]).astype(np.float64),
+                "avg_samples": np.array([g[1] for g in got], dtype=np.float64), "avg_streams": rows.astype(np.float64)}
 
     def gate(self):
         import numpy as np
@@ -1078,7 +1142,7 @@ def main():
     # a slice through the product before any timing (rank 0): the same handle type, same kernels;
     # the cpu_baseline leg below compares it with the CPU path's output for the same bytes
     gate = None
-    if a.check and rank == 0 and not a.no_cpu_baseline and world == 1:
+    if a.check and rank == 0 and a.cpu_baseline and world == 1:
         gate = job.gate()
 
     # Untimed: after idle the GPU needs ~50 launches (~50 ms) to reach its steady clock - on most boxes; round 5's last
@@ -1089,7 +1153,7 @@ def main():
     # ... and what the K steps measure behind EXACTLY --warmup untimed ones (`cold`), first: the figure a caller who warms up
     # as the command line says would see; the steady-state figure below stays `value` (say both)
     cold = None
-    if prewarm and not a.pmc_child:
+    if prewarm and a.full and not a.pmc_child:
         for _ in range(a.warmup):
             step()
         fence()
@@ -1115,6 +1179,11 @@ def main():
     elapsed = time.perf_counter() - t0
     front_ms, launches = job.g.timing_read()
     path_used = getattr(job.g, "last_path", 2)
+    if a.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in job.outputs().items():
+            np.save(os.path.join(a.dump_outputs, f"{name}.npy"), arr)
 
     # the sustained leg: the same step for >= a.sustain seconds (HIP events per launch, wall clock over all)
     sustained = None
@@ -1133,7 +1202,7 @@ def main():
 
     # the in-kernel clock stamps of one more launch, right behind the sustained leg (fused fifth_order path)
     clock = None
-    if hasattr(job.g, "clock_probe") and not a.pmc_child:
+    if hasattr(job.g, "clock_probe") and a.full and not a.pmc_child:
         job.g.clock_probe(True)
         for _ in range(3):
             step()
@@ -1228,7 +1297,8 @@ def main():
         if a.tail == "power":
             roof["note"] = ("not HBM-bound: integer VALU issue in LDS-resident radix-2 stages; valu_issue = the launch time "
                             "the instruction count alone takes at the clock the launch ran at (DESIGN.md section 4.5)")
-            roof["valu_issue"] = job.valu_issue(front_ms / max(launches, 1), c4_valu)
+            if a.full:
+                roof["valu_issue"] = job.valu_issue(front_ms / max(launches, 1), c4_valu)
         if sustained:
             n_s, dt, s_launch = sustained
             roof["sustained"] = {
@@ -1295,7 +1365,7 @@ def main():
             res["also"] = also
         if e2e:
             res["e2e"] = e2e
-        if not a.no_cpu_baseline and world == 1:
+        if a.cpu_baseline and world == 1:
             res["cpu_baseline"] = job.cpu_baseline(a.cpu_seconds, gate)
             res["cpu_baseline"]["parity_checked"] = gate is not None
         else:

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import reference_record as rr
 from rtlsdr_amd import build as hipbuild
 
 SYMS = """rtlsdr_cancel_async rtlsdr_close rtlsdr_get_center_freq rtlsdr_get_device_count rtlsdr_get_device_name
@@ -211,22 +212,24 @@ def test_wave_header_matches_reference_writer(shim, tmp_path, oracle_lib):
     assert int.from_bytes(a[116:120], "little") == len(payload)
     assert int.from_bytes(a[76:80], "little") == 99400000 and int.from_bytes(a[32:34], "little") == 1
     assert 2024 <= int.from_bytes(a[44:46], "little") <= 2100
-    if not oracle_lib.have_reference():
-        return
-    ref = oracle_lib.Reference()
-    try:
-        ref.lib.waveWriteHeader.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_void_p]
-        ref.lib.waveFinalizeHeader.argtypes = [C.c_void_p]
-        theirs = tmp_path / "ref.wav"
-        f = libc.fopen(str(theirs).encode(), b"wb")
-        ref.lib.waveWriteHeader(32000, 99400000, 16, 1, f)
-        libc.fwrite(payload, 1, len(payload), f)
-        C.c_uint32.in_dll(ref.lib, "waveDataSize").value = len(payload)
-        ref.lib.waveFinalizeHeader(f)
-        libc.fclose(f)
-        b = theirs.read_bytes()
-    finally:
-        ref.close()
+
+    def live():
+        ref = oracle_lib.Reference()
+        try:
+            ref.lib.waveWriteHeader.argtypes = [C.c_uint, C.c_uint, C.c_int, C.c_int, C.c_void_p]
+            ref.lib.waveFinalizeHeader.argtypes = [C.c_void_p]
+            theirs = tmp_path / "ref.wav"
+            f = libc.fopen(str(theirs).encode(), b"wb")
+            ref.lib.waveWriteHeader(32000, 99400000, 16, 1, f)
+            libc.fwrite(payload, 1, len(payload), f)
+            C.c_uint32.in_dll(ref.lib, "waveDataSize").value = len(payload)
+            ref.lib.waveFinalizeHeader(f)
+            libc.fclose(f)
+            return {"wav": np.frombuffer(theirs.read_bytes(), dtype=np.uint8)}
+        finally:
+            ref.close()
+    # the reference's file: written live where oracle/_ref is built, recorded from it otherwise (tests/reference_record.py)
+    b = rr.result(oracle_lib.have_reference(), "device_shim/wave_header", live, (payload,))["wav"].tobytes()
     assert len(a) == len(b)
     assert a[:44] == b[:44] and a[76:] == b[76:]  # everything but the two time stamps
 

@@ -50,7 +50,7 @@ def test_bench_gpus_2_starts_two_ranks():
         env["RTLFM_BENCH_BACKEND"] = "gloo"  # both ranks on the one device
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--streams", "32", "--blocks", "4", "--no-cpu-baseline", "--scatter"]
+           "--streams", "32", "--blocks", "4", "--full", "--no-cpu-baseline", "--scatter"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -108,7 +108,7 @@ def test_bench_workloads_emit_the_contract_line(args):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--pmc", "0", "--sustain", "0.2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--pmc", "0", "--sustain", "0.2",
            "--cpu-seconds", "0.5"] + args
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -124,3 +124,43 @@ def test_bench_workloads_emit_the_contract_line(args):
     assert args[1] in d["config"]["workload"]
     if args[1] != "c4":
         assert d["e2e"]["value"] > 0
+
+
+@pytest.mark.parametrize("args", [
+    ["--workload", "c2", "--streams", "16", "--blocks", "4"],
+    ["--workload", "c4", "--streams", "8", "--blocks", "4"],
+])
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path, args):
+    """A plain run (no --full) times exactly --steps steps and prints the contract line without the optional legs;
+    --dump-outputs writes float32 / float64 arrays within the size bound, and two runs with the same arguments write
+    the same values (the inputs come from a fixed seed, the outputs are integers)."""
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d_out = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+               "--dump-outputs", str(d_out)] + args
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 5 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["cpu_baseline"] is None and "also" not in d and "e2e" not in d
+        assert "sustained" not in d["roofline"] and "cold" not in d["roofline"] and d["roofline"]["traffic"] is None
+        files = sorted(d_out.glob("*.npy"))
+        assert files and sum(f.stat().st_size for f in files) <= 64 << 20
+        arrs = {f.stem: np.load(f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    if args[1] == "c4":
+        assert dumps[0]["avg"].shape == (8, 1 << 14) and (dumps[0]["avg_samples"] > 0).all()
+    else:
+        per_stream = 4 * 262144 // 2 // 16  # 4 buffers through /16
+        assert dumps[0]["pcm"].shape == (16, per_stream) and (dumps[0]["pcm_len"] == per_stream).all()
+        assert np.abs(dumps[0]["pcm"]).max() > 0

@@ -1,11 +1,27 @@
 """The CPU oracle against the golden vectors the reference itself produced,
-and (where oracle/_ref exists) against the live reference."""
+and against the reference's own results for seeded cases: live where oracle/_ref exists,
+recorded from it otherwise (tests/reference_record.py)."""
 import numpy as np
 import pytest
 
 import golden_util as gu
+import reference_record as rr
 from cases import CASES, make_cfg
 from rtlsdr_amd import capi, synth
+
+
+def _reference_stream(po, key, cfg, iq):
+    """The reference's own rtlsdr_callback() + full_demod() over every block of one stream, from a fresh state:
+    (int16 output, carried state)."""
+    def live():
+        ref = po.Reference()
+        try:
+            want, rst = ref.run_stream(cfg, iq)
+        finally:
+            ref.close()
+        return {"out": want, "state": np.frombuffer(bytes(rst), dtype=np.uint8)}
+    r = rr.result(po.have_reference(), key, live, (int(cfg.block_len), iq))
+    return r["out"], capi.RtlfmStreamState.from_buffer_copy(r["state"].tobytes())
 
 
 @pytest.mark.parametrize("name", gu.fixture_names())
@@ -78,15 +94,11 @@ def test_polar_disc_lut_quirk(oracle_lib):
 
 @pytest.mark.parametrize("name,ov,sig", CASES[:12])
 def test_oracle_matches_live_reference(oracle_lib, name, ov, sig):
-    if not oracle_lib.have_reference():
-        pytest.skip("oracle/_ref not built here")
     L, nb = 1024, 7
     cfg = make_cfg(ov, L)
     iq = synth.fm_iq_u8(1, L // 2 * nb, seed=99, **sig)[0]
     got, st = oracle_lib.run_stream(cfg, iq)
-    ref = oracle_lib.Reference()
-    want, rst = ref.run_stream(cfg, iq)
-    ref.close()
+    want, rst = _reference_stream(oracle_lib, f"oracle_golden/case/{name}", cfg, iq)
     assert np.array_equal(got, want)
     assert gu.state_dict(st) == gu.state_dict(rst)
 
@@ -127,8 +139,6 @@ def _random_ref_cfg(rng):
 def test_oracle_random_configurations_vs_live_reference(oracle_lib, seed):
     """The restatement against the reference's own full_demod() (compiled in place) on seeded
     random configurations: every sample and the complete carried state."""
-    if not oracle_lib.have_reference():
-        pytest.skip("oracle/_ref not built here")
     rng = np.random.default_rng(31000 + seed)
     ov = _random_ref_cfg(rng)
     L = int(rng.choice([1024, 2048, 4096, 8192, 16384]))
@@ -153,11 +163,7 @@ def test_oracle_random_configurations_vs_live_reference(oracle_lib, seed):
         got, st = oracle_lib.run_stream(cfg, iq)
     except RuntimeError:
         pytest.skip("configuration rejected by the oracle")
-    ref = oracle_lib.Reference()
-    try:
-        want, rst = ref.run_stream(cfg, iq)
-    finally:
-        ref.close()
+    want, rst = _reference_stream(oracle_lib, f"oracle_golden/random/{seed}", cfg, iq)
     assert np.array_equal(got, want), (ov, L, nb)
     assert gu.state_dict(st) == gu.state_dict(rst), (ov, L, nb)
 
@@ -169,8 +175,6 @@ def test_oracle_vs_live_reference_on_buffers_the_passes_do_not_divide(oracle_lib
     (src/rtl_fm.c:1188-1191): the last passes see lengths that are not multiples of four elements.  The oracle's
     loops against the reference's own, compiled in place: every sample and the carried state.  (Buffers that come down
     to fewer than two elements make the reference read lowpassed[-1]: not compared here.)"""
-    if not oracle_lib.have_reference():
-        pytest.skip("oracle/_ref not built here")
     assert (L >> passes) >= 2
     ov = dict(downsample=1 << passes, downsample_passes=passes, comp_fir_size=9 if "fir" in kind else 0, rate_out=2000)
     if "fast" in kind: ov["custom_atan"] = 1
@@ -183,11 +187,7 @@ def test_oracle_vs_live_reference_on_buffers_the_passes_do_not_divide(oracle_lib
     nb = 9
     iq = synth.fm_iq_u8(1, L // 2 * nb, seed=900 + passes + L, fs=1.024e6, dev_hz=300.0, amplitude=20.0 if "fast" in kind else 50.0)[0]
     got, st = oracle_lib.run_stream(cfg, iq)
-    ref = oracle_lib.Reference()
-    try:
-        want, rst = ref.run_stream(cfg, iq)
-    finally:
-        ref.close()
+    want, rst = _reference_stream(oracle_lib, f"oracle_golden/undivided/{kind}/{passes}/{L}", cfg, iq)
     assert np.array_equal(got, want), (kind, passes, L)
     assert gu.state_dict(st) == gu.state_dict(rst), (kind, passes, L)
 
@@ -206,7 +206,7 @@ def test_batch_threads_equal_serial(oracle_lib):
 
 def test_rotate_90_u8_oracle_vs_reference_and_known_answer(oracle_lib):
     """rotate_90 on raw bytes (src/rtl_fm.c:437-447, dead code in the reference): the
-    restatement against the reference's own function (when built here) and a known answer."""
+    restatement against the reference's own function and a known answer."""
     po = oracle_lib
     lib = po.oracle()
     rng = np.random.default_rng(90)
@@ -221,9 +221,13 @@ def test_rotate_90_u8_oracle_vs_reference_and_known_answer(oracle_lib):
         want[:, 4] = 255 - src[:, 4]; want[:, 5] = 255 - src[:, 5]
         want[:, 6] = src[:, 7]; want[:, 7] = 255 - src[:, 6]
         assert np.array_equal(got, want.ravel())
-        if po.have_reference():
+
+        def live():
             ref = po.Reference()
-            r = x.copy()
-            ref.lib.ref_rotate_90_u8(r.ctypes.data, n)
-            assert np.array_equal(r, got)
-            ref.close()
+            try:
+                r = x.copy()
+                ref.lib.ref_rotate_90_u8(r.ctypes.data, n)
+            finally:
+                ref.close()
+            return {"out": r}
+        assert np.array_equal(rr.result(po.have_reference(), f"oracle_golden/rotate_90_u8/{n}", live, (x,))["out"], got)

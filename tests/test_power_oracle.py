@@ -1,6 +1,6 @@
 """rtl_power: the CPU oracle against the reference's own golden output and
-(where oracle/_ref exists) against the live compiled reference, function by
-function."""
+against the compiled reference, function by function: live where oracle/_ref
+exists, recorded from it otherwise (tests/reference_record.py)."""
 import ctypes as C
 import glob
 import os
@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import reference_record as rr
 from rtlsdr_amd.capi import RtlpowerCfg
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -31,38 +32,52 @@ def test_power_oracle_matches_golden(oracle_lib, name):
 
 
 def test_power_functions_against_live_reference(oracle_lib):
-    if not oracle_lib.have_power_reference():
-        pytest.skip("oracle/_ref not built here")
     lib = oracle_lib._power_lib()
-    ref = oracle_lib.PowerReference()
     rng = np.random.default_rng(9)
-    try:
-        for be in (3, 8, 12):
-            cfg = RtlpowerCfg.default(bin_e=be, window=1, buf_len=max(16384, 2 << be))
-            ref.lib.ref_power_setup(C.byref(cfg))
-            n = 1 << be
-            # sine table and window coefficients
-            sw = np.ctypeslib.as_array(ref.lib.ref_sinewave(), shape=(n * 3 // 4,)).copy()
-            mine = np.ctypeslib.as_array(C.cast(lib.orcp_sine_table(be), C.POINTER(C.c_int16)), shape=(n * 3 // 4,))
-            assert np.array_equal(sw, mine)
-            wc = np.ctypeslib.as_array(ref.lib.ref_window_coefs(), shape=(n,)).copy()
-            assert np.array_equal(wc, oracle_lib.power_window_coefs(1, n))
-            # fix_fft on full-scale data
-            x = rng.integers(-32768, 32768, size=2 * n).astype(np.int16)
-            a, b = x.copy(), x.copy()
-            ref.lib.fix_fft(a.ctypes.data, be)
-            lib.orcp_fix_fft(b.ctypes.data, be, mine.ctypes.data, be)
-            assert np.array_equal(a, b)
-        for length in (64, 1024, 4096):
-            x = rng.integers(-3000, 3000, size=length).astype(np.int16)
-            a, b = x.copy(), x.copy()
-            ref.lib.fifth_order(a.ctypes.data, length); lib.orcp_fifth_order(b.ctypes.data, length)
-            assert np.array_equal(a, b)
-            a, b = x.copy(), x.copy()
-            ref.lib.remove_dc(a.ctypes.data, length); lib.orcp_remove_dc(b.ctypes.data, length)
-            assert np.array_equal(a, b)
-    finally:
-        ref.close()
+    bes, lengths = (3, 8, 12), (64, 1024, 4096)
+    fft_in = [rng.integers(-32768, 32768, size=2 << be).astype(np.int16) for be in bes]  # fix_fft on full-scale data
+    dsp_in = [rng.integers(-3000, 3000, size=length).astype(np.int16) for length in lengths]
+
+    def live():
+        ref = oracle_lib.PowerReference()
+        out = {}
+        try:
+            for be, x in zip(bes, fft_in):
+                cfg = RtlpowerCfg.default(bin_e=be, window=1, buf_len=max(16384, 2 << be))
+                ref.lib.ref_power_setup(C.byref(cfg))
+                n = 1 << be
+                out[f"sine{be}"] = np.ctypeslib.as_array(ref.lib.ref_sinewave(), shape=(n * 3 // 4,)).copy()
+                out[f"window{be}"] = np.ctypeslib.as_array(ref.lib.ref_window_coefs(), shape=(n,)).copy()
+                a = x.copy()
+                ref.lib.fix_fft(a.ctypes.data, be)
+                out[f"fft{be}"] = a
+            for length, x in zip(lengths, dsp_in):
+                a = x.copy()
+                ref.lib.fifth_order(a.ctypes.data, length)
+                out[f"fifth{length}"] = a
+                a = x.copy()
+                ref.lib.remove_dc(a.ctypes.data, length)
+                out[f"remove_dc{length}"] = a
+        finally:
+            ref.close()
+        return out
+    want = rr.result(oracle_lib.have_power_reference(), "power_oracle/functions", live, (*fft_in, *dsp_in))
+    for be, x in zip(bes, fft_in):
+        n = 1 << be
+        # sine table and window coefficients
+        mine = np.ctypeslib.as_array(C.cast(lib.orcp_sine_table(be), C.POINTER(C.c_int16)), shape=(n * 3 // 4,))
+        assert np.array_equal(want[f"sine{be}"], mine)
+        assert np.array_equal(want[f"window{be}"], oracle_lib.power_window_coefs(1, n))
+        b = x.copy()
+        lib.orcp_fix_fft(b.ctypes.data, be, mine.ctypes.data, be)
+        assert np.array_equal(want[f"fft{be}"], b)
+    for length, x in zip(lengths, dsp_in):
+        b = x.copy()
+        lib.orcp_fifth_order(b.ctypes.data, length)
+        assert np.array_equal(want[f"fifth{length}"], b)
+        b = x.copy()
+        lib.orcp_remove_dc(b.ctypes.data, length)
+        assert np.array_equal(want[f"remove_dc{length}"], b)
 
 
 def _random_power_cfg(rng):
@@ -85,8 +100,6 @@ def test_oracle_scan_against_live_scanner(oracle_lib, seed):
     full-scale random bytes, 2..4 reads, avg[] (int64) and samples identical.  Configurations outside
     scanner()'s own domain (rtlpower_cfg_validate: a trailing frame past the read, where the reference
     transforms what its static buffer still holds) are skipped and counted."""
-    if not oracle_lib.have_power_reference():
-        pytest.skip("oracle/_ref not built here")
     from rtlsdr_amd import build as hipbuild
     from rtlsdr_amd import capi, synth
     hipbuild.build()
@@ -100,14 +113,18 @@ def test_oracle_scan_against_live_scanner(oracle_lib, seed):
     iq = np.concatenate([synth.fm_iq_u8(1, L // 2 * nr, fs=2.048e6, dev_hz=40e3, seed=100 + seed),
                          synth.random_u8(1, L * nr, seed=200 + seed)])
     avg, n = oracle_lib.power_scan_batch(cfg, iq)
-    ref = oracle_lib.PowerReference()
-    try:
-        for s in range(2):
-            ravg, rn = ref.scan_stream(cfg, iq[s])
-            assert rn == n[s], (kw, s)
-            assert np.array_equal(ravg, avg[s]), (kw, s)
-    finally:
-        ref.close()
+
+    def live():
+        ref = oracle_lib.PowerReference()
+        try:
+            got = [ref.scan_stream(cfg, iq[s]) for s in range(2)]
+        finally:
+            ref.close()
+        return {"avg": np.stack([g[0] for g in got]), "samples": np.array([g[1] for g in got])}
+    want = rr.result(oracle_lib.have_power_reference(), f"power_oracle/scan/{seed}", live, (L, iq))
+    for s in range(2):
+        assert want["samples"][s] == n[s], (kw, s)
+        assert np.array_equal(want["avg"][s], avg[s]), (kw, s)
 
 
 def test_remove_dc_removes_only_half(oracle_lib):
@@ -144,8 +161,6 @@ def _atofs(t):
 def test_planner_and_csv_match_reference(oracle_lib, arg, crop, boxcar):
     """§8f-3: rtlpower_frequency_range / rtlpower_csv_dbm (host side of the product library)
     against the reference's frequency_range() and csv_dbm() compiled in place."""
-    if not oracle_lib.have_power_reference():
-        pytest.skip("oracle/_ref not built here")
     from rtlsdr_amd import capi
     from rtlsdr_amd import build as hipbuild
     hipbuild.build()
@@ -153,72 +168,88 @@ def test_planner_and_csv_match_reference(oracle_lib, arg, crop, boxcar):
     lo, hi, step = (int(_atofs(x)) for x in arg.split(":"))
     plan = capi.RtlpowerPlan()
     assert lib.rtlpower_frequency_range(lo, hi, step, crop, boxcar, C.byref(plan)) == 0
-    ref = oracle_lib.PowerReference()
-    try:
-        ref.lib.ref_frequency_range.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
-        ref.lib.ref_csv_dbm.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_char_p, C.c_size_t]
-        o = np.zeros(10, dtype=np.int32); rc = C.c_double()
-        ref.lib.ref_frequency_range(arg.encode(), crop, boxcar, o.ctypes.data, C.byref(rc))
-        last = plan.tune_count - 1
-        assert (plan.tune_count, plan.rate, plan.bin_e, plan.downsample, plan.downsample_passes, plan.buf_len,
-                lib.rtlpower_tune_freq(C.byref(plan), 0), lib.rtlpower_tune_freq(C.byref(plan), last), plan.crop) == \
-               (o[0], o[2], o[3], o[4], o[5], o[6], o[7], o[8], rc.value)
-        if plan.tune_count > 1:
-            assert plan.bw_seen == o[1]
-        if plan.bin_e > 14:
-            return
-        # csv line for hop 0 and the last hop, from the same accumulators
-        rng = np.random.default_rng(3)
-        avg = rng.integers(1, 1 << 40, size=1 << plan.bin_e).astype(np.int64)
-        for tune in {0, last}:
-            mine_avg = avg.copy()
-            buf = C.create_string_buffer(1 << 20)
-            n = lib.rtlpower_csv_dbm(C.byref(plan), tune, mine_avg.ctypes.data, 77, buf, len(buf))
-            rbuf = C.create_string_buffer(1 << 20)
-            rn = ref.lib.ref_csv_dbm(tune, avg.ctypes.data, 77, rbuf, len(rbuf))
-            assert n == rn and buf.value == rbuf.value
-    finally:
-        ref.close()
+    last = plan.tune_count - 1
+    # csv line for hop 0 and the last hop, from the same accumulators
+    rng = np.random.default_rng(3)
+    avg = rng.integers(1, 1 << 40, size=1 << plan.bin_e).astype(np.int64) if plan.bin_e <= 14 else None
+    tunes = sorted({0, last}) if avg is not None else []
+
+    def live():
+        ref = oracle_lib.PowerReference()
+        try:
+            ref.lib.ref_frequency_range.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+            ref.lib.ref_csv_dbm.argtypes = [C.c_int, C.c_void_p, C.c_int32, C.c_char_p, C.c_size_t]
+            o = np.zeros(10, dtype=np.int32); rc = C.c_double()
+            ref.lib.ref_frequency_range(arg.encode(), crop, boxcar, o.ctypes.data, C.byref(rc))
+            out = {"range": o, "crop": np.float64(rc.value)}
+            for tune in tunes:
+                rbuf = C.create_string_buffer(1 << 20)
+                out[f"csv_n{tune}"] = np.int64(ref.lib.ref_csv_dbm(tune, avg.ctypes.data, 77, rbuf, len(rbuf)))
+                out[f"csv{tune}"] = np.frombuffer(rbuf.value, dtype=np.uint8)
+        finally:
+            ref.close()
+        return out
+    want = rr.result(oracle_lib.have_power_reference(), f"power_oracle/plan/{arg}/{crop}/{boxcar}", live,
+                     (arg, crop, boxcar, tunes, avg))
+    o, rc = want["range"], float(want["crop"])
+    assert (plan.tune_count, plan.rate, plan.bin_e, plan.downsample, plan.downsample_passes, plan.buf_len,
+            lib.rtlpower_tune_freq(C.byref(plan), 0), lib.rtlpower_tune_freq(C.byref(plan), last), plan.crop) == \
+           (o[0], o[2], o[3], o[4], o[5], o[6], o[7], o[8], rc)
+    if plan.tune_count > 1:
+        assert plan.bw_seen == o[1]
+    for tune in tunes:
+        mine_avg = avg.copy()
+        buf = C.create_string_buffer(1 << 20)
+        n = lib.rtlpower_csv_dbm(C.byref(plan), tune, mine_avg.ctypes.data, 77, buf, len(buf))
+        assert n == int(want[f"csv_n{tune}"]) and buf.value == want[f"csv{tune}"].tobytes()
 
 
 def test_planner_random_against_live_reference(oracle_lib):
     """rtlpower_frequency_range against the reference's frequency_range() (compiled in place) on a
     seeded random sweep of ranges, bin sizes, crop factors and both decimator kinds."""
-    if not oracle_lib.have_power_reference():
-        pytest.skip("oracle/_ref not built here")
     from rtlsdr_amd import capi
     from rtlsdr_amd import build as hipbuild
     hipbuild.build()
     lib = capi.load()
     rng = np.random.default_rng(77)
-    ref = oracle_lib.PowerReference()
-    try:
-        ref.lib.ref_frequency_range.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
-        for _ in range(250):
-            lo = int(rng.integers(24_000_000, 1_600_000_000))
-            width = int(rng.choice([rng.integers(20_000, 900_000), rng.integers(900_000, 3_000_000),
-                                    rng.integers(3_000_000, 400_000_000)]))
-            step = int(rng.choice([rng.integers(500, 20_000), rng.integers(20_000, 900_000),
-                                   rng.integers(1_000_000, 2_500_000)]))
-            crop = float(rng.choice([0.0, 0.0, 0.1, 0.25, 0.5]))
-            boxcar = int(rng.integers(0, 2))
-            arg = f"{lo}:{lo + width}:{step}"
-            plan = capi.RtlpowerPlan()
-            r = lib.rtlpower_frequency_range(lo, lo + width, step, crop, boxcar, C.byref(plan))
-            if r != 0:
-                continue  # rejected (the reference would exit or misbehave); covered by the fixed cases
-            o = np.zeros(10, dtype=np.int32); rc = C.c_double()
-            ref.lib.ref_frequency_range(arg.encode(), crop, boxcar, o.ctypes.data, C.byref(rc))
-            assert plan.tune_count == o[0], (arg, crop, boxcar)
-            if plan.tune_count == 0:
-                continue  # an empty plan (giant bins wider than the range): nothing else is defined
-            last = plan.tune_count - 1
-            got = (plan.rate, plan.bin_e, plan.downsample, plan.downsample_passes, plan.buf_len,
-                   lib.rtlpower_tune_freq(C.byref(plan), 0), lib.rtlpower_tune_freq(C.byref(plan), last), plan.crop)
-            want = (o[2], o[3], o[4], o[5], o[6], o[7], o[8], rc.value)
-            assert got == want, (arg, crop, boxcar)
-    finally:
-        ref.close()
+    cases = []
+    for _ in range(250):
+        lo = int(rng.integers(24_000_000, 1_600_000_000))
+        width = int(rng.choice([rng.integers(20_000, 900_000), rng.integers(900_000, 3_000_000),
+                                rng.integers(3_000_000, 400_000_000)]))
+        step = int(rng.choice([rng.integers(500, 20_000), rng.integers(20_000, 900_000),
+                               rng.integers(1_000_000, 2_500_000)]))
+        crop = float(rng.choice([0.0, 0.0, 0.1, 0.25, 0.5]))
+        boxcar = int(rng.integers(0, 2))
+        plan = capi.RtlpowerPlan()
+        r = lib.rtlpower_frequency_range(lo, lo + width, step, crop, boxcar, C.byref(plan))
+        if r != 0:
+            continue  # rejected (the reference would exit or misbehave); covered by the fixed cases
+        cases.append((f"{lo}:{lo + width}:{step}", crop, boxcar, plan))
+
+    def live():
+        ref = oracle_lib.PowerReference()
+        try:
+            ref.lib.ref_frequency_range.argtypes = [C.c_char_p, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+            ranges, crops = [], []
+            for arg, crop, boxcar, _ in cases:
+                o = np.zeros(10, dtype=np.int32); rc = C.c_double()
+                ref.lib.ref_frequency_range(arg.encode(), crop, boxcar, o.ctypes.data, C.byref(rc))
+                ranges.append(o); crops.append(rc.value)
+        finally:
+            ref.close()
+        return {"range": np.array(ranges), "crop": np.array(crops, dtype=np.float64)}
+    want_all = rr.result(oracle_lib.have_power_reference(), "power_oracle/plan_random", live,
+                         ([c[:3] for c in cases],))
+    for (arg, crop, boxcar, plan), o, rc in zip(cases, want_all["range"], want_all["crop"], strict=True):
+        assert plan.tune_count == o[0], (arg, crop, boxcar)
+        if plan.tune_count == 0:
+            continue  # an empty plan (giant bins wider than the range): nothing else is defined
+        last = plan.tune_count - 1
+        got = (plan.rate, plan.bin_e, plan.downsample, plan.downsample_passes, plan.buf_len,
+               lib.rtlpower_tune_freq(C.byref(plan), 0), lib.rtlpower_tune_freq(C.byref(plan), last), plan.crop)
+        want = (o[2], o[3], o[4], o[5], o[6], o[7], o[8], float(rc))
+        assert got == want, (arg, crop, boxcar)
 
 
 def test_every_plan_of_the_planner_is_accepted():

@@ -30,9 +30,9 @@ for spec in "ns4096:" "c2:--workload c2" "c1:--workload c1" "box10_std:--boxcar 
   if [ -n "${ONLY:-}" ] && ! echo " $ONLY " | grep -q " $tag "; then continue; fi
   cd $ROOT
   case $tag in
-    ns4096) timeout 600 python bench.py > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err ;;
-    box*) timeout 300 python bench.py $args --steps 100 --warmup 50 --no-cpu-baseline --e2e 0 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err ;;
-    *) timeout 400 python bench.py $args --steps 100 --warmup 50 --cpu-seconds 6 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err ;;
+    ns4096) timeout 600 python bench.py --full > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err ;;
+    box*) timeout 300 python bench.py --full $args --steps 100 --warmup 50 --no-cpu-baseline --e2e 0 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err ;;
+    *) timeout 400 python bench.py --full $args --steps 100 --warmup 50 --cpu-seconds 6 > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err ;;
   esac
   cd /tmp && export TMPDIR=/tmp
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$tag -- python3 $ROOT/bench.py $COMMON $args > $OUT/trace_$tag.log 2>&1
