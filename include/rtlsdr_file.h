@@ -12,9 +12,14 @@
  * unchanged.  The input is what rtl_sdr writes (src/rtl_sdr.c:97-121): raw
  * interleaved u8 I,Q, optionally behind a RIFF/WAVE header, which is skipped.
  *
- * The file comes from the environment: RTLSDR_FILE=<path> (required),
- * RTLSDR_FILE_LOOP=1 to wrap around at end of file instead of ending the
- * asynchronous read.
+ * The file comes from the environment: RTLSDR_FILE=<path> (one device, serial
+ * 00000001), or, when RTLSDR_FILE is unset or empty, RTLSDR_FILE_LIST=<list file>:
+ * one source per line (a raw IQ file, an rtl_sdr -H WAV file or tcp://host:port;
+ * blank lines and lines starting with '#' are skipped), device i = the i-th
+ * source, serial = %08u of i + 1.  Devices are independent: each has its own
+ * file or socket, async read and cancel flag, so one thread per device may sit
+ * in rtlsdr_read_async at the same time.  RTLSDR_FILE_LOOP=1 wraps around at end
+ * of file (every file device) instead of ending the asynchronous read.
  */
 #ifndef RTLSDR_FILE_H
 #define RTLSDR_FILE_H

@@ -12,12 +12,20 @@
 // (:1339-1343) nothing is ever dropped: the callback waits while the queue is
 // full, so the output is a deterministic function of the input file.
 //
+// -N n (not a reference option) demodulates devices d .. d+n-1 as streams 0 .. n-1 of ONE handle, one run
+// per step for all of them (see run_multi below): one dongle thread per device, as the reference has for its
+// one dongle, each filling a host queue of its own; the demod thread takes the same number of buffers from
+// every queue, so the library's equal-count rule holds, and the slowest source sets the pace.  A source that
+// ends leaves the batch and the others go on, their carried state moved to a handle with fewer streams.
+// With RTLSDR_FILE_LIST=<list of sources> the device layer has one device per line.
+//
 // Not restated (out of scope): frequency scanning / hopping,
 // the CSV command file, squelch-driven retuning.  -l / -t hold the output back as
 // demod_thread_fn does, -L prints full_demod()'s level lines.
 #include <getopt.h>
 #include <pthread.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <chrono>
 #include <cmath>
@@ -260,12 +268,395 @@ void output_thread(App *a)
 	fflush(a->file);
 }
 
+// ---- -N n: devices d .. d+n-1 as streams 0 .. n-1 of one handle ----------------------------------------
+//
+// rtlfm_gpu_run() takes every stream's queued buffers and wants the same number from each (-EAGAIN otherwise), so
+// the callbacks do not push into the ring themselves: each copies its buffer into a host queue of its own stream
+// (at most `depth` buffers; a full queue makes the callback wait, nothing is dropped), and the demod thread, once
+// every live stream has a buffer, takes b = min(what every queue holds, max_blocks) from each, pushes them and runs.
+// The slowest source sets the pace of all.  A stream whose source has ended and whose queue is empty leaves the
+// batch: the others move, carried state and all, to a handle with one stream fewer for each that left.  Between runs
+// nothing is left in the ring (every push is taken by the run right behind it, whose results are fetched before the
+// next push), so the state is all there is to move, and no stream loses a sample or sees one twice.
+
+struct Multi;
+
+struct Source {
+	int index = 0;                            // stream index: output file, %d, "stream i:"
+	rtlsdr_dev_t *dev = nullptr;
+	uint32_t user_freq = 0, capture_freq = 0;
+	FILE *file = nullptr;
+	rtlamd_wave wave{};
+	Multi *m = nullptr;
+	std::deque<std::vector<uint8_t>> q;       // buffers copied by the callback, not yet taken by a run
+	std::vector<std::vector<uint8_t>> spare;  // taken buffers come back here, so a callback hardly ever allocates
+	std::vector<std::vector<uint8_t>> taken;  // what the current run pushes
+	int copying = 0;                          // callbacks copying into a reserved place of the queue
+	bool eof = false;
+	std::condition_variable cv_room;
+	// -L (src/rtl_fm.c:109-113, 1217-1237), per stream
+	int print_level_no = 1, level_max = 0, level_max_max = 0;
+	double level_sum = 0.0;
+	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
+};
+
+struct RunOut {
+	std::vector<int16_t> pcm;  // handle stream k at k * stride
+	std::vector<int32_t> lens;
+	std::vector<int> who;      // handle stream k -> source
+	size_t stride = 0;
+};
+
+struct Multi {
+	rtlfm_cfg cfg;
+	rtlfm_gpu *gpu = nullptr;
+	std::vector<Source> src;
+	int depth = 0;
+	int verbosity = 0, conseq_squelch = 10, print_levels = 0;
+	std::mutex m;
+	std::condition_variable cv_work, cv_out;
+	bool failed = false, out_done = false;
+	std::deque<RunOut> out_q;
+};
+
+// with m->m held
+void fail_multi(Multi *m, const char *what, int r)
+{
+	fprintf(stderr, "%s: %s\n", what, rtlfm_gpu_strerror(r));
+	m->failed = true;
+	for (Source &s : m->src) {
+		rtlsdr_cancel_async(s.dev);
+		s.cv_room.notify_all();
+	}
+	m->cv_work.notify_all();
+}
+
+void on_buffer_multi(unsigned char *buf, uint32_t len, void *ctx)
+{
+	Source *s = static_cast<Source *>(ctx);
+	Multi *m = s->m;
+	len -= len % 512;  // as on_buffer
+	if (len == 0) return;
+	std::vector<uint8_t> b;
+	{
+		std::unique_lock<std::mutex> g(m->m);
+		s->cv_room.wait(g, [&] { return (int)s->q.size() + s->copying < m->depth || m->failed; });
+		if (m->failed) return;
+		s->copying++;
+		if (!s->spare.empty()) {
+			b = std::move(s->spare.back());
+			s->spare.pop_back();
+		}
+	}
+	b.assign(buf, buf + len);  // outside the lock: the other devices' callbacks copy at the same time
+	std::lock_guard<std::mutex> g(m->m);
+	s->copying--;
+	s->q.push_back(std::move(b));
+	s->blocks_in++;
+	m->cv_work.notify_one();
+}
+
+void dongle_thread_multi(Source *s)
+{
+	rtlsdr_read_async(s->dev, on_buffer_multi, s, 0, s->m->cfg.block_len);
+	std::lock_guard<std::mutex> g(s->m->m);
+	s->eof = true;  // after the last callback: the queue holds everything the source gave
+	s->m->cv_work.notify_one();
+}
+
+// the streams in `stay` (a subsequence of `live`) go on, on a new handle with stay.size() streams
+int shrink(Multi *m, const std::vector<int> &live, const std::vector<int> &stay)
+{
+	rtlfm_gpu *nh = nullptr;
+	int r = rtlfm_gpu_create(&m->cfg, (int)stay.size(), 0, &nh);
+	if (r < 0) return r;
+	for (size_t i = 0, k = 0; i < live.size() && k < stay.size() && r == 0; i++) {
+		if (live[i] != stay[k]) continue;
+		rtlfm_stream_state st;
+		r = rtlfm_gpu_state_get(m->gpu, (int)i, &st);
+		if (r == 0) r = rtlfm_gpu_state_set(nh, (int)k, &st);
+		k++;
+	}
+	if (r < 0) {
+		rtlfm_gpu_destroy(nh);
+		return r;
+	}
+	rtlfm_gpu_destroy(m->gpu);
+	m->gpu = nh;
+	return 0;
+}
+
+void levels_multi(Multi *m, Source &s, int k)
+{
+	// as demod_thread's -L block, per stream
+	int32_t sr = 0;
+	int nl = 0;
+	if (rtlfm_gpu_levels(m->gpu, k, &sr, 1, &nl) != 0 || nl != 1) return;
+	--s.print_level_no;
+	if (sr < 0) return;
+	s.level_sum += sr;
+	if (s.level_max < sr) s.level_max = sr;
+	if (s.level_max_max < sr) s.level_max_max = sr;
+	if (s.print_level_no) return;
+	s.print_level_no = m->print_levels;
+	const double avg_rms = s.level_sum / m->print_levels;
+	fprintf(stderr, "stream %d: %.3f kHz, %.1f avg rms, %d max rms, %d max max rms, %d squelch rms, %d rms, %.1f dB rms level, %.2f dB avg rms level\n",
+	        s.index, s.user_freq / 1000.0, avg_rms, s.level_max, s.level_max_max, m->cfg.squelch_level, (int)sr,
+	        20.0 * log10(1E-10 + sr), 20.0 * log10(1E-10 + avg_rms));
+	s.level_max = 0;
+	s.level_sum = 0;
+}
+
+void demod_thread_multi(Multi *m)
+{
+	const size_t stride = ((size_t)rtlfm_result_cap(&m->cfg) * m->cfg.max_blocks + 16 + 63) / 64 * 64;
+	std::vector<int> live;
+	for (size_t i = 0; i < m->src.size(); i++) live.push_back((int)i);
+	// -vv: where this thread's time goes (waiting for the slowest source, the copy into the ring, run + fetch, the
+	// per-stream -l / -L calls)
+	using clk = std::chrono::steady_clock;
+	double t_wait = 0, t_push = 0, t_run = 0, t_per_stream = 0;
+	uint64_t runs = 0;
+	auto since = [](clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); };
+	for (;;) {
+		std::vector<int> stay;
+		int b = m->cfg.max_blocks;
+		clk::time_point t0 = clk::now();
+		{
+			std::unique_lock<std::mutex> g(m->m);
+			m->cv_work.wait(g, [&] {
+				if (m->failed) return true;
+				for (int i : live)
+					if (m->src[i].q.empty() && !m->src[i].eof) return false;
+				return true;
+			});
+			if (m->failed) break;
+			for (int i : live)
+				if (!m->src[i].q.empty()) stay.push_back(i);  // an empty queue here means the source has ended
+			for (int i : stay) b = std::min(b, (int)m->src[i].q.size());
+			for (int i : stay) {
+				Source &s = m->src[i];
+				for (int j = 0; j < b; j++) {
+					s.taken.push_back(std::move(s.q.front()));
+					s.q.pop_front();
+				}
+				s.cv_room.notify_all();
+			}
+		}
+		if (stay.empty()) break;
+		if (stay.size() != live.size()) {
+			int r = shrink(m, live, stay);
+			if (r < 0) {
+				std::lock_guard<std::mutex> g(m->m);
+				fail_multi(m, "rtlfm_gpu_create / state_get / state_set", r);
+				break;
+			}
+			if (m->verbosity)
+				fprintf(stderr, "%zu of %zu streams go on (the others' sources have ended)\n", stay.size(), m->src.size());
+			live = stay;
+		}
+		// the pushes of different streams may run concurrently (rtlfm_hip.h): a few threads share the copy into the ring
+		t_wait += since(t0);
+		t0 = clk::now();
+		const size_t ns = live.size();
+		const size_t nt = std::min<size_t>(16, (ns + 15) / 16);
+		std::vector<int> err(nt, 0);
+		auto push_some = [&](size_t t) {
+			for (size_t k = t * ns / nt; k < (t + 1) * ns / nt && !err[t]; k++)
+				for (const std::vector<uint8_t> &buf : m->src[live[k]].taken) {
+					int r = rtlfm_gpu_push(m->gpu, (int)k, buf.data(), (uint32_t)buf.size());
+					if (r < 0) { err[t] = r; break; }
+				}
+		};
+		if (nt == 1) {
+			push_some(0);
+		} else {
+			std::vector<std::thread> th;
+			for (size_t t = 0; t < nt; t++) th.emplace_back(push_some, t);
+			for (std::thread &t : th) t.join();
+		}
+		int r = 0;
+		for (int e : err) if (e < 0 && r == 0) r = e;
+		t_push += since(t0);
+		t0 = clk::now();
+		int ran = 0;
+		if (r == 0) r = rtlfm_gpu_run_begin(m->gpu, &ran);
+		if (r == 0 && ran != b) r = -EPROTO;
+		if (r == 0) r = rtlfm_gpu_run_end(m->gpu);
+		RunOut o;
+		o.stride = stride;
+		o.pcm.resize(ns * stride);
+		o.lens.resize(ns);
+		o.who = live;
+		if (r == 0) r = rtlfm_gpu_fetch_all(m->gpu, o.pcm.data(), stride, o.lens.data());
+		if (r < 0) {
+			std::lock_guard<std::mutex> g(m->m);
+			fail_multi(m, "rtlfm_gpu_push/run/fetch_all", r);
+			break;
+		}
+		t_run += since(t0);
+		t0 = clk::now();
+		runs++;
+		for (size_t k = 0; k < ns; k++) {
+			Source &s = m->src[live[k]];
+			if (m->print_levels) levels_multi(m, s, (int)k);
+			if (m->cfg.squelch_level) {
+				// demod_thread's squelch rule (src/rtl_fm.c:1366-1370), per stream; max_blocks is 1 here
+				rtlfm_stream_state st;
+				if (rtlfm_gpu_state_get(m->gpu, (int)k, &st) == 0 && st.squelch_hits > m->conseq_squelch) {
+					st.squelch_hits = m->conseq_squelch + 1;
+					rtlfm_gpu_state_set(m->gpu, (int)k, &st);
+					s.blocks_squelched++;
+					o.lens[k] = 0;
+				}
+			}
+		}
+		t_per_stream += since(t0);
+		std::lock_guard<std::mutex> g(m->m);
+		for (int i : live) {
+			Source &s = m->src[i];
+			for (std::vector<uint8_t> &buf : s.taken) s.spare.push_back(std::move(buf));
+			s.taken.clear();
+		}
+		m->out_q.push_back(std::move(o));
+		m->cv_out.notify_one();
+	}
+	if (m->verbosity >= 2)
+		fprintf(stderr, "demod thread: %llu runs; %.3f s waiting for buffers, %.3f s pushing, %.3f s run + fetch_all, %.3f s -l / -L\n",
+		        (unsigned long long)runs, t_wait, t_push, t_run, t_per_stream);
+	std::lock_guard<std::mutex> g(m->m);
+	m->out_done = true;
+	m->cv_out.notify_all();
+}
+
+void output_thread_multi(Multi *m)
+{
+	for (;;) {
+		RunOut o;
+		{
+			std::unique_lock<std::mutex> g(m->m);
+			m->cv_out.wait(g, [&] { return !m->out_q.empty() || m->out_done; });
+			if (m->out_q.empty()) break;
+			o = std::move(m->out_q.front());
+			m->out_q.pop_front();
+		}
+		for (size_t k = 0; k < o.who.size(); k++) {
+			Source &s = m->src[o.who[k]];
+			const size_t n = (size_t)o.lens[k];
+			if (!n) continue;
+			fwrite(o.pcm.data() + k * o.stride, 2, n, s.file);
+			s.wave.data_size += 2 * (uint32_t)n;
+			s.samples_out += n;
+		}
+	}
+	for (Source &s : m->src) fflush(s.file);
+}
+
+// everything after option parsing for n > 1 (main has refused what -N does not allow)
+int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<uint32_t> &freqs,
+              const std::vector<uint32_t> &capture_freqs, uint32_t capture_rate, int gain, int ppm, const std::string &pattern,
+              bool write_wav, int verbosity, int conseq_squelch, int print_levels)
+{
+	Multi m;
+	m.cfg = planned;
+	rtlfm_cfg &c = m.cfg;
+	m.depth = 2 * c.max_blocks;
+	m.verbosity = verbosity;
+	m.conseq_squelch = conseq_squelch;
+	m.print_levels = print_levels;
+	m.src = std::vector<Source>((size_t)n);
+	const uint32_t count = rtlsdr_get_device_count();
+	if (count == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE or RTLSDR_FILE_LIST).\n"); return 1; }
+	if ((uint64_t)dev_index + (uint64_t)n > count) {
+		fprintf(stderr, "-d %d -N %d needs devices %d .. %d, and there are %u.\n", dev_index, n, dev_index, dev_index + n - 1, count);
+		return 1;
+	}
+	int ret = 0;
+	for (int i = 0; i < n && !ret; i++) {
+		Source &s = m.src[i];
+		s.index = i;
+		s.m = &m;
+		s.user_freq = freqs[i];
+		s.capture_freq = capture_freqs[i];
+		if (rtlsdr_open(&s.dev, (uint32_t)(dev_index + i)) < 0) {
+			fprintf(stderr, "Failed to open rtlsdr device #%d.\n", dev_index + i);
+			ret = 1;
+			break;
+		}
+		if (gain == -100) rtlsdr_set_tuner_gain_mode(s.dev, 0);
+		else { rtlsdr_set_tuner_gain_mode(s.dev, 1); rtlsdr_set_tuner_gain(s.dev, gain); }
+		rtlsdr_set_freq_correction_ppb(s.dev, ppm * 1000);
+		rtlsdr_set_offset_tuning(s.dev, c.offset_tuning);
+		rtlsdr_set_center_freq(s.dev, s.capture_freq);
+		if (rtlsdr_set_sample_rate(s.dev, capture_rate) < 0 && i == 0)
+			fprintf(stderr, "WARNING: capture rate %u Hz is outside what an RTL2832 can do.\n", capture_rate);
+		if (verbosity || i == 0 || capture_freqs[i] != capture_freqs[0])
+			fprintf(stderr, "stream %d: device #%d, tuned to %u Hz.\n", i, dev_index + i, s.capture_freq);
+	}
+	if (!ret) {
+		fprintf(stderr, "%d streams.\nOversampling input by: %ix.\nSampling at %u S/s.\nOutput at %u Hz.\n", n, c.downsample,
+		        capture_rate, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out));
+		if (verbosity)
+			fprintf(stderr, "downsample_passes = %d, downsample = %d, deemph_a = %d, buffer = %u B, host queue = %d buffers per stream\n",
+			        c.downsample_passes, c.downsample, c.deemph_a, c.block_len, m.depth);
+		int r = rtlfm_gpu_create(&c, n, 0, &m.gpu);
+		if (r < 0) {
+			fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r));
+			ret = 2;
+		}
+	}
+	const size_t at = pattern.find("%d");
+	for (int i = 0; i < n && !ret; i++) {
+		Source &s = m.src[i];
+		const std::string name = pattern.substr(0, at) + std::to_string(i) + pattern.substr(at + 2);
+		s.file = fopen(name.c_str(), "wb");
+		if (!s.file) { fprintf(stderr, "Failed to open %s\n", name.c_str()); ret = 1; break; }
+		if (write_wav)
+			rtlamd_wave_write_header(&s.wave, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out), s.user_freq, 16,
+			                         c.mode == RTLFM_MODE_RAW ? 2 : 1, s.file);
+		rtlsdr_reset_buffer(s.dev);
+	}
+	if (!ret) {
+		std::thread t_out(output_thread_multi, &m), t_demod(demod_thread_multi, &m);
+		std::vector<std::thread> t_dongle;
+		for (Source &s : m.src) t_dongle.emplace_back(dongle_thread_multi, &s);
+		for (std::thread &t : t_dongle) t.join();
+		t_demod.join();
+		t_out.join();
+		uint64_t in = 0, out = 0, sq = 0;
+		for (Source &s : m.src) {
+			in += s.blocks_in;
+			out += s.samples_out;
+			sq += s.blocks_squelched;
+		}
+		fprintf(stderr, "%llu buffers in, %llu samples out, %llu buffers held back by the squelch%s\n", (unsigned long long)in,
+		        (unsigned long long)out, (unsigned long long)sq, m.failed ? " (FAILED)" : "");
+		if (verbosity)
+			for (Source &s : m.src)
+				fprintf(stderr, "stream %d: %llu buffers in, %llu samples out, %llu buffers held back by the squelch\n", s.index,
+				        (unsigned long long)s.blocks_in, (unsigned long long)s.samples_out, (unsigned long long)s.blocks_squelched);
+		if (m.failed) ret = 3;
+	}
+	for (Source &s : m.src) {
+		if (s.file) {
+			if (write_wav) rtlamd_wave_finalize(&s.wave, s.file);
+			fclose(s.file);
+		}
+		if (s.dev) rtlsdr_close(s.dev);
+	}
+	if (m.gpu) rtlfm_gpu_destroy(m.gpu);
+	return ret;
+}
+
 void usage()
 {
 	fprintf(stderr,
-	        "rtl_fm_hip, rtl_fm's demodulator on an AMD GPU (one stream; see rtlfm_hip.h for batches)\n"
-	        "Use:\trtl_fm_hip -f freq [-options] [filename]   (input: RTLSDR_FILE=<raw u8 IQ file>)\n"
-	        "\t-f frequency_to_tune_to [Hz]\n"
+	        "rtl_fm_hip, rtl_fm's demodulator on an AMD GPU (one stream, or -N streams in one batch)\n"
+	        "Use:\trtl_fm_hip -f freq [-options] [filename]   (input: RTLSDR_FILE=<raw u8 IQ file>\n"
+	        "\t                                                or RTLSDR_FILE_LIST=<file with one source per line>)\n"
+	        "\t-f frequency_to_tune_to [Hz]  (with -N n: once for every device, or n times, one per device)\n"
+	        "\t[-N n  demodulate devices d .. d+n-1 (d = -d) in one batch; filename must hold one %%d (stream index),\n"
+	        "\t       not '-'; a source that ends leaves the batch, the slowest source sets the pace; not with -Z]\n"
 	        "\t[-M modulation (default: fm)]  fm, wbfm, raw, am, usb, lsb\n"
 	        "\t[-s sample_rate (default: 24k)]  [-r resample_rate (default: none / same as -s)]\n"
 	        "\t[-m minimum_capture_rate Hz (default: 1m)]\n"
@@ -274,9 +665,9 @@ void usage()
 	        "\t[-E enable_option]  edge, dc, rdc, deemp, offset\n"
 	        "\t[-c de-emphasis_time_constant in us: us (75), eu (50) or a number]\n"
 	        "\t[-o oversampling (default: 1)]  [-l squelch_level]  [-t squelch_delay (default: 10)]  [-q rdc_block_const]\n"
-	        "\t[-L N  prints levels every N calculations]\n"
+	        "\t[-L N  prints levels every N calculations (with -N: per stream, as 'stream i: ...')]\n"
 	        "\t[-W length of one buffer in units of 512 bytes (default: 32 = 16384 B)]\n"
-	        "\t[-H write a wave header with the auxi chunk SDR programs read the frequency from]\n"
+	        "\t[-H write a wave header with the auxi chunk SDR programs read the frequency from]  [-v verbose]\n"
 	        "\t[-Z zero-copy: the device layer reads straight into the GPU layer's pinned staging ring]\n"
 	        "\t[-d device_index] [-g gain] [-p ppm]  accepted and passed to the device layer\n"
 	        "\tfilename ('-' means stdout)\n");
@@ -293,15 +684,18 @@ int main(int argc, char **argv)
 	int rate_in = 24000, min_capture = 1000000, time_constant = 75;
 	int fifth = 0, edge = 0, dev_index = 0, gain = -100, ppm = 0;
 	uint32_t freq = 0;
+	std::vector<uint32_t> freqs;  // every -f, in order (-N)
+	int nstreams = 1;
 	bool have_freq = false, write_wav = false, wb_mode = false;
 	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
-	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZ")) != -1) {
+	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:")) != -1) {
 		switch (opt) {
 		case 'd': dev_index = atoi(optarg); break;
-		case 'f': freq = (uint32_t)atofs(optarg); have_freq = true; break;
+		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
+		case 'N': nstreams = atoi(optarg); break;
 		case 'g': gain = (int)(atof(optarg) * 10); break;
 		case 'p': ppm = (int)atof(optarg); break;
 		case 'm': min_capture = (int)atofs(optarg); break;
@@ -369,6 +763,52 @@ int main(int argc, char **argv)
 	a.user_freq = freq;  // dongle.userFreq, src/rtl_fm.c:1440
 	rate_in *= c.post_downsample;  // src/rtl_fm.c:1886
 	const char *filename = optind < argc ? argv[optind] : "-";
+
+	if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
+	if (nstreams > 1) {
+		// everything -N refuses is refused here, before a device is opened or a GPU handle created
+		const std::string pattern(filename);
+		const size_t at = pattern.find("%d");
+		if (freqs.size() != 1 && freqs.size() != (size_t)nstreams) {
+			fprintf(stderr, "-N %d: give -f once (every device) or %d times (one per device), not %zu times.\n", nstreams,
+			        nstreams, freqs.size());
+			usage();
+		}
+		if (pattern == "-") { fprintf(stderr, "-N %d: no stdout; name the files, e.g. out_%%d.raw.\n", nstreams); usage(); }
+		if (at == std::string::npos || pattern.find("%d", at + 2) != std::string::npos) {
+			fprintf(stderr, "-N %d: the filename must hold exactly one %%d (the stream index), e.g. out_%%d.raw.\n", nstreams);
+			usage();
+		}
+		if (a.zero_copy) {
+			// -Z writes a device's buffer straight into the ring, but with -N the ring is filled from the host
+			// queues (run_multi): there is no slot a device could own
+			fprintf(stderr, "-Z (zero-copy) works with one stream only, not with -N %d.\n", nstreams);
+			usage();
+		}
+		if (freqs.size() == 1) freqs.assign((size_t)nstreams, freqs[0]);
+		if (wb_mode)
+			for (uint32_t &f : freqs) f += 16000;  // the -M wbfm rule above, for every device
+		if (c.deemph) c.deemph_a = rtlfm_deemph_a(c.rate_out, time_constant);
+		// one plan for all streams: optimal_settings() must not depend on the frequency for what this CLI accepts
+		rtlfm_cfg planned = c;
+		std::vector<uint32_t> capture_freqs((size_t)nstreams);
+		uint32_t capture_rate = 0;
+		for (int i = 0; i < nstreams; i++) {
+			rtlfm_cfg ci = c;
+			uint32_t cr = 0;
+			rtlfm_optimal_settings(&ci, freqs[i], rate_in, min_capture, fifth, edge, &capture_freqs[i], &cr);
+			if (i == 0) {
+				planned = ci;
+				capture_rate = cr;
+			} else if (memcmp(&ci, &planned, sizeof(ci)) != 0 || cr != capture_rate) {
+				fprintf(stderr, "-N: the rate plan for %u Hz differs from the one for %u Hz; one handle needs one plan.\n",
+				        freqs[i], freqs[0]);
+				return 1;
+			}
+		}
+		return run_multi(planned, nstreams, dev_index, freqs, capture_freqs, capture_rate, gain, ppm, pattern, write_wav,
+		                 a.verbosity, conseq_squelch, a.print_levels);
+	}
 
 	if (rtlsdr_get_device_count() == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE).\n"); return 1; }
 	if (rtlsdr_open(&a.dev, (uint32_t)dev_index) < 0) { fprintf(stderr, "Failed to open rtlsdr device #%d.\n", dev_index); return 1; }

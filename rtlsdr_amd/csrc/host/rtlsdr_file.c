@@ -40,25 +40,87 @@ struct rtlsdr_dev {
 	void *source_ctx;
 };
 
+/*
+ * Where the devices come from.  RTLSDR_FILE=<source> is one device, as it always was.  Without it,
+ * RTLSDR_FILE_LIST=<text file> names one source per line (a raw u8 IQ file, an rtl_sdr -H WAV file or
+ * tcp://host:port; blank lines and lines that start with '#' are skipped): device i is the i-th source.
+ * The list is read afresh on every call, so nothing about it is kept between calls or shared between devices.
+ */
 static const char *env_path(void)
 {
 	const char *p = getenv("RTLSDR_FILE");
 	return (p && *p) ? p : NULL;
 }
 
-uint32_t rtlsdr_get_device_count(void) { return env_path() ? 1u : 0u; }
+static const char *env_list(void)
+{
+	const char *p = getenv("RTLSDR_FILE_LIST");
+	return (p && *p) ? p : NULL;
+}
+
+/* Source `index` into buf (NULL = only count): 0 when it exists.  *count = entries seen (all of them if NULL buf). */
+static int list_entry(uint32_t index, char *buf, size_t cap, uint32_t *count)
+{
+	uint32_t n = 0;
+	int found = -1;
+	FILE *f = fopen(env_list(), "r");
+	if (!f) { if (count) *count = 0; return -1; }
+	char line[4096];
+	while (fgets(line, sizeof(line), f)) {
+		size_t len = strlen(line);
+		while (len && (line[len - 1] == '\n' || line[len - 1] == '\r' || line[len - 1] == ' ' || line[len - 1] == '\t'))
+			line[--len] = 0;
+		const char *p = line;
+		while (*p == ' ' || *p == '\t') p++;
+		if (!*p || *p == '#') continue;
+		if (buf && n == index) {
+			if (strlen(p) >= cap) break;
+			strcpy(buf, p);
+			found = 0;
+			break;
+		}
+		n++;
+	}
+	fclose(f);
+	if (count) *count = n;
+	return found;
+}
+
+/* Device `index`'s source into buf: 0, or -1 if there is no such device. */
+static int device_path(uint32_t index, char *buf, size_t cap)
+{
+	const char *p = env_path();
+	if (p) {
+		if (index != 0 || strlen(p) >= cap) return -1;
+		strcpy(buf, p);
+		return 0;
+	}
+	if (!env_list()) return -1;
+	return list_entry(index, buf, cap, NULL);
+}
+
+uint32_t rtlsdr_get_device_count(void)
+{
+	if (env_path()) return 1u;
+	if (!env_list()) return 0u;
+	uint32_t n = 0;
+	list_entry(0, NULL, 0, &n);
+	return n;
+}
 
 const char *rtlsdr_get_device_name(uint32_t index)
 {
-	return (index == 0 && env_path()) ? "IQ file (rtlsdr_amd file device)" : "";
+	char path[4096];
+	return device_path(index, path, sizeof(path)) == 0 ? "IQ file (rtlsdr_amd file device)" : "";
 }
 
 int rtlsdr_get_device_usb_strings(uint32_t index, char *manufact, char *product, char *serial)
 {
-	if (index != 0 || !env_path()) return -2;
+	char path[4096];
+	if (device_path(index, path, sizeof(path)) != 0) return -2;
 	if (manufact) strcpy(manufact, "rtlsdr_amd");
-	if (product) strcpy(product, !strncmp(env_path(), "tcp://", 6) ? "rtl_tcp" : "file");
-	if (serial) strcpy(serial, "00000001");
+	if (product) strcpy(product, !strncmp(path, "tcp://", 6) ? "rtl_tcp" : "file");
+	if (serial) snprintf(serial, 9, "%08u", (unsigned)(index + 1) % 100000000u);
 	return 0;
 }
 
@@ -109,8 +171,8 @@ static int tcp_open(rtlsdr_dev_t **out, const char *url)
 
 int rtlsdr_open(rtlsdr_dev_t **out, uint32_t index)
 {
-	const char *path = env_path();
-	if (!out || index != 0 || !path) return -1;
+	char path[4096];
+	if (!out || device_path(index, path, sizeof(path)) != 0) return -1;
 	if (!strncmp(path, "tcp://", 6)) return tcp_open(out, path + 6);
 	FILE *f = fopen(path, "rb");
 	if (!f) { perror(path); return -1; }
@@ -275,7 +337,9 @@ int rtlsdr_cancel_async(rtlsdr_dev_t *d)
 const char *rtlsdr_get_ver_id(void) { return "rtlsdr_amd file device"; }
 uint32_t rtlsdr_get_version(void) { return (0u << 24) | (1u << 16) | (0u << 8) | 0u; }
 
-/* ---- the WAV container helpers, exported for tools and tests (not part of the 26) ---- */
+/* ---- the WAV container helpers, exported for tools and tests (not part of the 26) ----
+ * g_wave is the library's only file-scope object, and no device touches it: everything a device reads with
+ * lives in its struct rtlsdr_dev (and rtlsdr_read_async's own buffers), so devices on different threads share nothing. */
 #include "wavhdr.h"
 static struct rtlamd_wave g_wave;
 void rtlamd_wave_write_header_file(unsigned samplerate, unsigned freq, int bits, int channels, FILE *f)
