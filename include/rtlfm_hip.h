@@ -244,6 +244,31 @@ int rtlfm_gpu_fetch_all_prev(rtlfm_gpu *h, int16_t *out, size_t out_stride, int3
  * of squares, see rms()) reads INT32_MIN as in the reference.  *n = buffers in the last run.
  */
 int rtlfm_gpu_levels(rtlfm_gpu *h, int stream, int32_t *rms, int cap, int *n);
+/* The same for every stream in one copy: stream s gets its *n levels at rms + s * cap (cap = room per stream). */
+int rtlfm_gpu_levels_all(rtlfm_gpu *h, int32_t *rms, int cap, int *n);
+
+/*
+ * The ADC statistics rtlsdr_callback keeps on the raw bytes of a buffer BEFORE the byte-to-int16 conversion
+ * (src/rtl_fm.c:1302-1324), one record per buffer:
+ *   max        largest byte of the buffer (sampleMax, the overload check, :1305-1312)
+ *   step       2; while (len >= 16384 * step) step += 2;                                   (:1314-1315)
+ *   pow_sum    sum over i = 0, step, 2 step, ... < len of (buf[i]-127)^2 + (buf[i+1]-127)^2 (:1316-1321)
+ *   pow_count  number of those i.  The reference adds (double)pow_sum / pow_count to samplePowSum per buffer;
+ *              that and everything behind it is host work: include/rtlfm_monitor.h
+ * Taken on the GPU over the full-rate input (k_input_stats, csrc/input_stats_kernel.h) by every run while the
+ * option "input_stats" is 1 (default 0: nothing is launched, nothing allocated), whatever path the run takes;
+ * integer and bit-identical to the reference.  rtlfm_gpu_input_stats: the last run's records of `stream`, the
+ * contract of rtlfm_gpu_levels (-ENODATA while the option is off, -ENOBUFS when cap is too small, *n = buffers
+ * of the last run that have records); _all: every stream in one copy, stream s at out + s * cap.
+ */
+typedef struct { uint32_t pow_sum; int32_t pow_count; int32_t max; int32_t step; } rtlfm_input_stat;
+int rtlfm_gpu_input_stats(rtlfm_gpu *h, int stream, rtlfm_input_stat *out, int cap, int *n);
+int rtlfm_gpu_input_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int *n);
+/* The same kernel as a standalone operator (no handle), asynchronous on hip_stream (NULL = the default stream): nstreams
+ * rows of nblocks buffers of block_len bytes (a multiple of 512) at d_iq + s * stream_stride (16-byte aligned, a multiple of
+ * 16), records [nstreams][nblocks] to device memory d_out (16-byte aligned).  nontemporal: 1 / 0 as input_stats_nt. */
+int rtlfm_gpu_input_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                 int nstreams, rtlfm_input_stat *d_out, int nontemporal, void *hip_stream);
 
 int rtlfm_gpu_state_get(rtlfm_gpu *h, int stream, rtlfm_stream_state *st);
 int rtlfm_gpu_state_set(rtlfm_gpu *h, int stream, const rtlfm_stream_state *st);
@@ -335,8 +360,11 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        the state records on the device; a difference is reported on stderr and counted.  Separates a transient
  *                        fault of the device code from a deterministic one (tests/test_soak_gpu.py).  Twice the time and a
  *                        second set of output rows; ragged runs (short callback buffers) are not verified
+ *   input_stats          1: every run also takes the ADC statistics of its raw input bytes (rtlfm_gpu_input_stats; one more
+ *                        kernel, k_input_stats, in front of the front end; default 0; anything but 0 / 1 -EINVAL)
+ *   input_stats_nt       that kernel's loads non-temporal (1, default) or plain (0): an A/B switch, LAB.md
  * Read-only (rtlfm_gpu_get_option):
- *   verify_runs          runs executed under verify_twice so far, and
+ *   verify_runs         runs executed under verify_twice so far, and
  *   verify_mismatches    ... how many of them differed between their two executions
  *   ring_apart           1 / 0: the result buffers behind rtlfm_gpu_push() / _run() are / are not a quarter of the HBM
  *                        away from the ring's device input; -1 before the ring exists (it is built by the first push)

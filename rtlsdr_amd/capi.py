@@ -125,6 +125,72 @@ class RtlfmStreamState(C.Structure):
         return d
 
 
+class RtlfmInputStat(C.Structure):
+    """``rtlfm_input_stat`` — the ADC statistics of one raw buffer (reference: src/rtl_fm.c:1302-1324)."""
+
+    _fields_ = [("pow_sum", C.c_uint32), ("pow_count", C.c_int32), ("max", C.c_int32), ("step", C.c_int32)]
+
+
+# the same record as a numpy dtype (GpuDemod.input_stats / .input_stats_all return arrays of it)
+INPUT_STAT_DTYPE = [("pow_sum", "<u4"), ("pow_count", "<i4"), ("max", "<i4"), ("step", "<i4")]
+
+MONITOR_AUTO_GAIN = -100
+CRIT_IN, CRIT_OUT, CRIT_LT, CRIT_GT = range(4)
+CRIT_NAMES = ("in", "out", "<", ">")  # aCritStr, src/rtl_fm.c:116
+MONITOR_COMMAND_MAX, MONITOR_ARGS_MAX = 256, 1024
+
+
+class RtlfmMonitorRule(C.Structure):
+    """``rtlfm_monitor_rule`` — one measurement line of the command file (include/rtlfm_monitor.h)."""
+
+    _fields_ = [
+        ("freq", C.c_uint32),
+        ("gain", C.c_int32),
+        ("crit", C.c_int32),
+        ("num_meas", C.c_int32),
+        ("ref_level", C.c_double),
+        ("ref_tol", C.c_double),
+        ("num_block_trigger", C.c_int32),
+        ("check_adc_max", C.c_int32),
+        ("check_adc_rms", C.c_int32),
+        ("omit_first", C.c_int32),
+        ("command", C.c_char * MONITOR_COMMAND_MAX),
+        ("args", C.c_char * MONITOR_ARGS_MAX),
+    ]
+
+    @classmethod
+    def default(cls, **kw) -> "RtlfmMonitorRule":
+        """cmd_init()'s values (rtlfm_monitor_rule_default) plus overrides."""
+        r = cls(crit=CRIT_IN, num_meas=10, omit_first=3)
+        for k, v in kw.items():
+            if not hasattr(r, k):
+                raise AttributeError(k)
+            setattr(r, k, v.encode() if isinstance(v, str) else v)
+        return r
+
+    def as_dict(self) -> dict:
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["command"] = d["command"].decode()
+        d["args"] = d["args"].decode()
+        return d
+
+
+class RtlfmMonitorEvent(C.Structure):
+    """``rtlfm_monitor_event`` — what one finished cycle of one stream reports."""
+
+    _fields_ = [("stream", C.c_int32), ("cycle", C.c_int32), ("crit_met", C.c_int32), ("fired", C.c_int32),
+                ("blocked_for", C.c_int32), ("adc_max", C.c_int32), ("level_db", C.c_double), ("adc_rms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class RtlfmMonitorStat(C.Structure):
+    """``rtlfm_monitor_stat`` — the exit statistics of one line (src/rtl_fm.c:2033-2040)."""
+
+    _fields_ = [("count", C.c_int32), ("min_level", C.c_float), ("max_level", C.c_float), ("sum_levels", C.c_double)]
+
+
 WIN_RECTANGLE, WIN_HAMMING, WIN_BLACKMAN, WIN_BLACKMAN_HARRIS, WIN_HANN_POISSON, WIN_YOUSSEF, WIN_KAISER, \
     WIN_BARTLETT = range(8)
 
@@ -182,6 +248,10 @@ _SIGNATURES = [
     ("rtlfm_gpu_fetch_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtlfm_gpu_fetch_all_prev", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtlfm_gpu_levels", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_levels_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_input_stats", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_input_stats_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_input_stats_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     ("rtlfm_gpu_state_get", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_state_set", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_reset", C.c_int, [C.c_void_p]),
@@ -258,6 +328,21 @@ _POWER_SIGNATURES = [
 ]
 _SIGNATURES = _SIGNATURES + _POWER_SIGNATURES
 
+# ... and include/rtlfm_monitor.h (the level monitor: host code inside the same library)
+_MONITOR_SIGNATURES = [
+    ("rtlfm_monitor_rule_default", None, [_P(RtlfmMonitorRule)]),
+    ("rtlfm_monitor_create", C.c_int, [C.c_int, _P(RtlfmMonitorRule), _P(C.c_void_p)]),
+    ("rtlfm_monitor_destroy", C.c_int, [C.c_void_p]),
+    ("rtlfm_monitor_feed", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    ("rtlfm_monitor_update", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_monitor_poll", C.c_int, [C.c_void_p, _P(RtlfmMonitorEvent), C.c_int, _P(C.c_int)]),
+    ("rtlfm_monitor_stats", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmMonitorStat)]),
+    ("rtlfm_monitor_rule_get", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmMonitorRule)]),
+    ("rtlfm_monitor_parse_file", C.c_int, [C.c_char_p, _P(RtlfmMonitorRule), C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int)]),
+    ("rtlfm_monitor_format_event", C.c_int, [_P(RtlfmMonitorRule), _P(RtlfmMonitorEvent), C.c_char_p, C.c_size_t]),
+]
+DECLARED_MONITOR_SYMBOLS = [s[0] for s in _MONITOR_SIGNATURES]
+
 DECLARED_SYMBOLS = [s[0] for s in _SIGNATURES]
 DECLARED_FM_SYMBOLS = [s[0] for s in _SIGNATURES if s[0].startswith("rtlfm_")]
 DECLARED_POWER_SYMBOLS = [s[0] for s in _POWER_SIGNATURES]
@@ -291,7 +376,9 @@ def load(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, res, args in _SIGNATURES:
+    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES:
+        if path is not None and not hasattr(lib, name):
+            continue  # an explicitly named other build (A/B against an earlier revision) may predate a symbol
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -19,11 +19,23 @@
 // ends leaves the batch and the others go on, their carried state moved to a handle with fewer streams.
 // With RTLSDR_FILE_LIST=<list of sources> the device layer has one device per line.
 //
-// Not restated (out of scope): frequency scanning / hopping,
-// the CSV command file, squelch-driven retuning.  -l / -t hold the output back as
-// demod_thread_fn does, -L prints full_demod()'s level lines.
+// -C file (the reference's command file, src/rtl_fm.c:527-736, README.rtlfm_cmdfile) is restated for -N n sources
+// WITHOUT the hop: measurement line i of the file is watched permanently by source i (include/rtlfm_monitor.h).  As
+// in the reference -C sets -M raw and takes each source's frequency and gain from its line; it switches report_levels
+// and the library's option input_stats on, the demod thread feeds the monitor after every run, -v prints each event
+// in the reference's wording (:716-718, :731-733, behind "stream i: "), a fired event with a command starts it in
+// the background (posix_spawnp, no shell; !freq! !gain! !mlevel! !crit! !reflevel! !reftol! replaced as at :722-727;
+// the children are waited for at exit), and the statistics per line are printed at exit (:2033-2040).  Every buffer
+// of every source is still written (the reference's demod thread drops the buffer a cycle ends on, :1375-1380) and
+// the lines are not limited to FREQUENCIES_LIMIT.
+//
+// Not restated (out of scope): frequency scanning / hopping - also through the command file's
+// lines: no retune, hence no mute / -B buffer dump and no DC-filter reset between cycles -, squelch-driven
+// retuning.  -l / -t hold the output back as demod_thread_fn does, -L prints full_demod()'s level lines.
 #include <getopt.h>
 #include <pthread.h>
+#include <spawn.h>
+#include <sys/wait.h>
 
 #include <algorithm>
 #include <cerrno>
@@ -40,6 +52,7 @@
 #include <vector>
 
 #include "../../../include/rtlfm_hip.h"
+#include "../../../include/rtlfm_monitor.h"
 #include "../../../include/rtlsdr_file.h"
 #include "wavhdr.h"
 
@@ -317,6 +330,11 @@ struct Multi {
 	std::condition_variable cv_work, cv_out;
 	bool failed = false, out_done = false;
 	std::deque<RunOut> out_q;
+	// -C: the level monitor, rule i = source i
+	rtlfm_monitor *mon = nullptr;
+	std::vector<rtlfm_monitor_rule> rules;
+	std::vector<pid_t> children;
+	uint64_t events = 0, fired = 0;
 };
 
 // with m->m held
@@ -377,6 +395,7 @@ int shrink(Multi *m, const std::vector<int> &live, const std::vector<int> &stay)
 		if (r == 0) r = rtlfm_gpu_state_set(nh, (int)k, &st);
 		k++;
 	}
+	if (r == 0 && m->mon) r = rtlfm_gpu_set_option(nh, "input_stats", 1);
 	if (r < 0) {
 		rtlfm_gpu_destroy(nh);
 		return r;
@@ -405,6 +424,81 @@ void levels_multi(Multi *m, Source &s, int k)
 	        20.0 * log10(1E-10 + sr), 20.0 * log10(1E-10 + avg_rms));
 	s.level_max = 0;
 	s.level_sum = 0;
+}
+
+// -C: a fired event's command, in the background and without a shell: argv[0] = the command, the arguments split at
+// blanks, an argument that IS one of the placeholders replaced (src/rtl_fm.c:722-727, executeInBackground)
+void start_command(Multi *m, const rtlfm_monitor_rule &r, const rtlfm_monitor_event &ev)
+{
+	static const char *crit_names[] = {"in", "out", "<", ">"};  // aCritStr, :116
+	fprintf(stderr, "command to trigger is '%s %s'\n", r.command, r.args);
+	char v_freq[32], v_gain[32], v_level[32], v_ref[32], v_tol[32];
+	snprintf(v_freq, sizeof(v_freq), "%u", r.freq);
+	snprintf(v_gain, sizeof(v_gain), "%d", r.gain);
+	snprintf(v_level, sizeof(v_level), "%d", (int)(0.5 + ev.level_db * 10.0));
+	snprintf(v_ref, sizeof(v_ref), "%d", (int)(0.5 + r.ref_level * 10.0));
+	snprintf(v_tol, sizeof(v_tol), "%d", (int)(0.5 + r.ref_tol * 10.0));
+	const char *names[] = {"!freq!", "!gain!", "!mlevel!", "!crit!", "!reflevel!", "!reftol!"};
+	const char *values[] = {v_freq, v_gain, v_level, crit_names[r.crit & 3], v_ref, v_tol};
+	std::vector<std::string> words{r.command};
+	std::string cur;
+	for (const char *p = r.args;; p++) {
+		if (*p && *p != ' ' && *p != '\t') { cur += *p; continue; }
+		if (!cur.empty()) {
+			for (int k = 0; k < 6; k++)
+				if (cur == names[k]) { cur = values[k]; break; }
+			words.push_back(cur);
+			cur.clear();
+		}
+		if (!*p) break;
+	}
+	std::vector<char *> argv;
+	for (std::string &w : words) argv.push_back(&w[0]);
+	argv.push_back(nullptr);
+	pid_t pid = 0;
+	const int e = posix_spawnp(&pid, r.command, nullptr, nullptr, argv.data(), environ);
+	if (e) fprintf(stderr, "cannot start '%s': %s\n", r.command, strerror(e));
+	else m->children.push_back(pid);
+}
+
+// -C: after a run, feed the monitor and act on what it reports.  While every source is alive the handle's streams ARE
+// the file's lines (rtlfm_monitor_update: one copy of the levels, one of the records); once sources have left, stream k
+// of the handle is line live[k].
+int monitor_step(Multi *m, const std::vector<int> &live)
+{
+	int r = 0;
+	if (live.size() == m->src.size()) {
+		r = rtlfm_monitor_update(m->mon, m->gpu);
+	} else {
+		const int cap = m->cfg.max_blocks;
+		std::vector<int32_t> lv(live.size() * (size_t)cap);
+		std::vector<rtlfm_input_stat> st(live.size() * (size_t)cap);
+		int n = 0, ns = 0;
+		r = rtlfm_gpu_levels_all(m->gpu, lv.data(), cap, &n);
+		if (r == 0) r = rtlfm_gpu_input_stats_all(m->gpu, st.data(), cap, &ns);
+		for (size_t k = 0; k < live.size() && r == 0; k++)
+			r = rtlfm_monitor_feed(m->mon, live[k], lv.data() + k * cap, ns == n ? st.data() + k * cap : nullptr, n);
+	}
+	if (r < 0) return r;
+	rtlfm_monitor_event ev[64];
+	for (;;) {
+		int n = 0;
+		if ((r = rtlfm_monitor_poll(m->mon, ev, 64, &n)) < 0) return r;
+		for (int i = 0; i < n; i++) {
+			const rtlfm_monitor_rule &rule = m->rules[(size_t)ev[i].stream];
+			m->events++;
+			if (m->verbosity) {
+				char line[512];
+				rtlfm_monitor_format_event(&rule, &ev[i], line, sizeof(line));
+				fprintf(stderr, "stream %d: %s\n", ev[i].stream, line);
+			}
+			if (ev[i].fired) {
+				m->fired++;
+				if (rule.command[0]) start_command(m, rule, ev[i]);
+			}
+		}
+		if (n < 64) return 0;
+	}
 }
 
 void demod_thread_multi(Multi *m)
@@ -494,6 +588,11 @@ void demod_thread_multi(Multi *m)
 			fail_multi(m, "rtlfm_gpu_push/run/fetch_all", r);
 			break;
 		}
+		if (m->mon && (r = monitor_step(m, live)) < 0) {
+			std::lock_guard<std::mutex> g(m->m);
+			fail_multi(m, "rtlfm_monitor_update / feed", r);
+			break;
+		}
 		t_run += since(t0);
 		t0 = clk::now();
 		runs++;
@@ -555,9 +654,10 @@ void output_thread_multi(Multi *m)
 // everything after option parsing for n > 1 (main has refused what -N does not allow)
 int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<uint32_t> &freqs,
               const std::vector<uint32_t> &capture_freqs, uint32_t capture_rate, int gain, int ppm, const std::string &pattern,
-              bool write_wav, int verbosity, int conseq_squelch, int print_levels)
+              bool write_wav, int verbosity, int conseq_squelch, int print_levels, const std::vector<rtlfm_monitor_rule> &rules)
 {
 	Multi m;
+	m.rules = rules;
 	m.cfg = planned;
 	rtlfm_cfg &c = m.cfg;
 	m.depth = 2 * c.max_blocks;
@@ -583,8 +683,9 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 			ret = 1;
 			break;
 		}
-		if (gain == -100) rtlsdr_set_tuner_gain_mode(s.dev, 0);
-		else { rtlsdr_set_tuner_gain_mode(s.dev, 1); rtlsdr_set_tuner_gain(s.dev, gain); }
+		const int g_i = rules.empty() ? gain : rules[(size_t)i].gain;  // -C: each source's gain from its line
+		if (g_i == -100) rtlsdr_set_tuner_gain_mode(s.dev, 0);
+		else { rtlsdr_set_tuner_gain_mode(s.dev, 1); rtlsdr_set_tuner_gain(s.dev, g_i); }
 		rtlsdr_set_freq_correction_ppb(s.dev, ppm * 1000);
 		rtlsdr_set_offset_tuning(s.dev, c.offset_tuning);
 		rtlsdr_set_center_freq(s.dev, s.capture_freq);
@@ -603,6 +704,14 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 		if (r < 0) {
 			fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r));
 			ret = 2;
+		}
+		if (!ret && !rules.empty()) {
+			r = rtlfm_gpu_set_option(m.gpu, "input_stats", 1);
+			if (r == 0) r = rtlfm_monitor_create(n, rules.data(), &m.mon);
+			if (r < 0) {
+				fprintf(stderr, "rtlfm_monitor_create: %s\n", rtlfm_gpu_strerror(r));
+				ret = 2;
+			}
 		}
 	}
 	const size_t at = pattern.find("%d");
@@ -635,8 +744,19 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 			for (Source &s : m.src)
 				fprintf(stderr, "stream %d: %llu buffers in, %llu samples out, %llu buffers held back by the squelch\n", s.index,
 				        (unsigned long long)s.blocks_in, (unsigned long long)s.samples_out, (unsigned long long)s.blocks_squelched);
+		if (m.mon) {
+			fprintf(stderr, "%llu monitor events, %llu fired\n", (unsigned long long)m.events, (unsigned long long)m.fired);
+			// the scan statistics of src/rtl_fm.c:2033-2040, one line per command-file line that reported a level
+			for (int i = 0; i < n; i++) {
+				rtlfm_monitor_stat st;
+				if (rtlfm_monitor_stats(m.mon, i, &st) == 0 && st.count > 0)
+					fprintf(stderr, "%u, %.1f, %.2f, %.1f\n", rules[(size_t)i].freq, st.min_level, st.sum_levels / st.count, st.max_level);
+			}
+		}
 		if (m.failed) ret = 3;
 	}
+	for (pid_t pid : m.children) waitpid(pid, nullptr, 0);  // the triggered commands run in the background; none outlives the tool
+	if (m.mon) rtlfm_monitor_destroy(m.mon);
 	for (Source &s : m.src) {
 		if (s.file) {
 			if (write_wav) rtlamd_wave_finalize(&s.wave, s.file);
@@ -657,6 +777,9 @@ void usage()
 	        "\t-f frequency_to_tune_to [Hz]  (with -N n: once for every device, or n times, one per device)\n"
 	        "\t[-N n  demodulate devices d .. d+n-1 (d = -d) in one batch; filename must hold one %%d (stream index),\n"
 	        "\t       not '-'; a source that ends leaves the batch, the slowest source sets the pace; not with -Z]\n"
+	        "\t[-C command_file  with -N n: measurement line i of the file (freq, gain, in|out|lt|gt, level dB, tolerance dB,\n"
+	        "\t       #meas, #blocks, command, args) is watched by source i - the file must hold n such lines; adc / adcmax /\n"
+	        "\t       adcrms lines add the ADC statistics of the raw bytes; sets -M raw; -v prints every event]\n"
 	        "\t[-M modulation (default: fm)]  fm, wbfm, raw, am, usb, lsb\n"
 	        "\t[-s sample_rate (default: 24k)]  [-r resample_rate (default: none / same as -s)]\n"
 	        "\t[-m minimum_capture_rate Hz (default: 1m)]\n"
@@ -688,14 +811,16 @@ int main(int argc, char **argv)
 	int nstreams = 1;
 	bool have_freq = false, write_wav = false, wb_mode = false;
 	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
+	const char *cmd_file = nullptr;
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
-	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:")) != -1) {
+	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:")) != -1) {
 		switch (opt) {
 		case 'd': dev_index = atoi(optarg); break;
 		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
 		case 'N': nstreams = atoi(optarg); break;
+		case 'C': cmd_file = optarg; break;
 		case 'g': gain = (int)(atof(optarg) * 10); break;
 		case 'p': ppm = (int)atof(optarg); break;
 		case 'm': min_capture = (int)atofs(optarg); break;
@@ -755,6 +880,31 @@ int main(int argc, char **argv)
 		default: usage();
 		}
 	}
+	std::vector<rtlfm_monitor_rule> rules;
+	if (cmd_file) {
+		// src/rtl_fm.c:1738-1741: the command file implies -M raw; here its lines are the -N sources, in order
+		if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
+		rules.resize((size_t)nstreams);
+		int found = 0;
+		const int pr = rtlfm_monitor_parse_file(cmd_file, rules.data(), nstreams, &found, nullptr, nullptr);
+		if (pr < 0 && pr != -ENOBUFS) {
+			fprintf(stderr, "-C %s: %s\n", cmd_file, pr == -ENOENT ? "cannot open the command file" : "no valid measurement line");
+			usage();
+		}
+		if (found != nstreams) {
+			fprintf(stderr, "-C %s holds %d measurement lines, -N %d needs exactly %d: line i of the file is watched by source i.\n",
+			        cmd_file, found, nstreams, nstreams);
+			usage();
+		}
+		c.mode = RTLFM_MODE_RAW;
+		c.report_levels = 1;
+		c.max_blocks = 1;  // as -L: one buffer per run, so that a source's short last buffer keeps its place among the levels
+		freqs.clear();
+		for (const rtlfm_monitor_rule &r : rules) freqs.push_back(r.freq);
+		freq = freqs[0];
+		have_freq = true;
+		wb_mode = false;
+	}
 	if (!have_freq) { fprintf(stderr, "Please specify a frequency.\n"); return 1; }
 	if (wb_mode) freq += 16000;  // controller_thread_fn(), src/rtl_fm.c:1455-1460: "wbfm: adding 16000 Hz to every input frequency"
 	a.conseq_squelch = conseq_squelch;
@@ -765,7 +915,7 @@ int main(int argc, char **argv)
 	const char *filename = optind < argc ? argv[optind] : "-";
 
 	if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
-	if (nstreams > 1) {
+	if (nstreams > 1 || cmd_file) {
 		// everything -N refuses is refused here, before a device is opened or a GPU handle created
 		const std::string pattern(filename);
 		const size_t at = pattern.find("%d");
@@ -807,7 +957,7 @@ int main(int argc, char **argv)
 			}
 		}
 		return run_multi(planned, nstreams, dev_index, freqs, capture_freqs, capture_rate, gain, ppm, pattern, write_wav,
-		                 a.verbosity, conseq_squelch, a.print_levels);
+		                 a.verbosity, conseq_squelch, a.print_levels, rules);
 	}
 
 	if (rtlsdr_get_device_count() == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE).\n"); return 1; }

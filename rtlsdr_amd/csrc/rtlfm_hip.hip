@@ -26,6 +26,7 @@
 #include "staged_kernels.h"
 #include "fused_kernel.h"
 #include "boxcar_kernel.h"
+#include "input_stats_kernel.h"
 
 using namespace rtlfm;
 
@@ -93,6 +94,8 @@ struct rtlfm_gpu {
 	int32_t *d_mute = nullptr;        // [nstreams*cap_blocks]
 	int32_t *d_levels = nullptr;      // [nstreams*cap_blocks] rms() per buffer of the last run
 	int last_nblocks = 0;
+	rtlfm_input_stat *d_istats = nullptr;  // [nstreams*cap_blocks] ADC statistics of the raw bytes (option input_stats), allocated on first use
+	int stats_nblocks = 0;                 // buffers of the last run that have records ([stream][stats_nblocks])
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -129,6 +132,8 @@ struct rtlfm_gpu {
 		int lpr_slim_prio = 3;      // s_setprio of that kernel's waves (0 .. 3)
 		int lpr_slim_chunk = 6120;  // samples per lane of that kernel: 16 chunks per stream at the wbfm shape = 1024 waves, one per SIMD
 		int verify_inject = 0; // tests: the shadow execution's first sample of stream 0 is overwritten before the comparison (it must be noticed)
+		int input_stats = 0;   // 1: k_input_stats in front of every run's front end (rtlfm_gpu_input_stats)
+		int input_stats_nt = 1; // its loads non-temporal (the A/B of LAB.md)
 		int verify_twice = 0;  // debug: every run_device runs twice - into a shadow output, then into the caller's - and the two are compared on the device
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
@@ -496,7 +501,7 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	void *ptrs[] = {h->d_arb_i, h->d_arb_frac, h->d_arb_tab, h->d_deemph_tab, h->d_deemph_inc, h->d_lpr_chunks, h->deepA, h->deepB, h->bufA, h->bufB, h->res[0][0], h->res[0][1], h->res_one_block ? nullptr : (void *)h->res[1][0], h->res[1][1],
 	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
-	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan};
+	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	h->fws.release();
@@ -615,6 +620,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"tail_sync", &h->opt.tail_sync}, {"apart_budget_gb", &h->place.budget_gb}, {"ring_force_retry", &h->place.force_retry},
 		{"arb_span", &h->opt.arb_span}, {"arb_chunk", &h->opt.arb_chunk}, {"arb_waves", &h->opt.arb_waves}, {"lpr_threads", &h->opt.lpr_threads}, {"arb_serial", &h->opt.arb_serial}, {"lpr_ring", &h->opt.lpr_ring}, {"squelch_fused", &h->opt.squelch_fused}, {"adc_separate", &h->opt.adc_separate}, {"deep_rest", &h->opt.deep_rest}, {"box_store", &h->fws.box_store}, {"fused_store", &h->fws.fused_store},
 		{"verify_twice", &h->opt.verify_twice}, {"verify_inject", &h->opt.verify_inject}, {"lpr_slim", &h->opt.lpr_slim}, {"lpr_slim_chunk", &h->opt.lpr_slim_chunk}, {"lpr_slim_prio", &h->opt.lpr_slim_prio},
+		{"input_stats", &h->opt.input_stats}, {"input_stats_nt", &h->opt.input_stats_nt},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -657,6 +663,7 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 	if ((!strcmp(name, "box_store") || !strcmp(name, "fused_store")) && (value < -1 || value > 1)) return -EINVAL;
 	// the chunk tables of the one-pass deemph + low_pass_real kernel are sized from it: keep it in a sane range
 	if ((!strcmp(name, "lpr_chunk") || !strcmp(name, "lpr_slim_chunk")) && (value < 256 || value > (1 << 20))) return -EINVAL;
+	if ((!strcmp(name, "input_stats") || !strcmp(name, "input_stats_nt")) && value != 0 && value != 1) return -EINVAL;
 	if (!strcmp(name, "arb_chunk") && value != 32 && value != 64) return -EINVAL;
 	if (!strcmp(name, "arb_waves") && (value < 0 || value > kSpecArbMaxWaves)) return -EINVAL;
 	if (!strcmp(name, "lpr_threads") && (value < 64 || value > kSpecLprThreads || value % 64)) return -EINVAL;
@@ -1767,6 +1774,13 @@ static int run_boxfused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_st
 	return run_tail(h, tp, dd, dds, T, varcnt, nblocks, N0, D, d_out, out_stride, d_out_len);
 }
 
+static int ensure_input_stats(rtlfm_gpu *h)
+{
+	if (!h->d_istats)
+		HIP_TRY(hipMalloc(&h->d_istats, (size_t)h->nstreams * h->cap_blocks * sizeof(rtlfm_input_stat)));
+	return 0;
+}
+
 // one execution of a run: everything rtlfm_gpu_run_device does except moving on to the next state copy / step
 static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
                            int16_t *d_out, size_t out_stride, int32_t *d_out_len)
@@ -1795,6 +1809,13 @@ static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		}
 	}
 	if (h->path == 2 && !can_fuse && !can_box && !can_box_emit && !can_deep) return -ENOTSUP;
+	// the callback's ADC statistics (src/rtl_fm.c:1302-1324) come before the conversion: in front of whichever front end runs
+	if (h->opt.input_stats) {
+		if ((r = ensure_input_stats(h)) < 0) return r;
+		if ((r = istats::launch(d_iq, stream_stride, h->cfg.block_len, nblocks, (int)S, h->d_istats, nblocks, h->opt.input_stats_nt != 0,
+		                        h->stream)) < 0)
+			return r;
+	}
 	// state is double-buffered: kernels read st[cur], write st[cur^1].  The staged kernels each
 	// update their own fields, so the record is copied first; the fused kernels copy it themselves.
 	if (!(h->path != 1 && (can_fuse || can_box || can_box_emit || can_deep)))
@@ -1917,6 +1938,7 @@ extern "C" int rtlfm_gpu_run_device(rtlfm_gpu *h, const uint8_t *d_iq, size_t st
 	h->st_cur = (h->st_cur + 1) % 3;
 	h->step++;
 	h->last_nblocks = nblocks;
+	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
 	return 0;
 }
 
@@ -1932,6 +1954,65 @@ extern "C" int rtlfm_gpu_levels(rtlfm_gpu *h, int stream, int32_t *rms, int cap,
 	if (h->last_nblocks > 0)
 		HIP_TRY(hipMemcpy(rms, h->d_levels + (size_t)stream * h->last_nblocks, (size_t)h->last_nblocks * sizeof(int32_t),
 		                  hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_levels_all(rtlfm_gpu *h, int32_t *rms, int cap, int *n)
+{
+	if (!h || !rms || !n) return -EINVAL;
+	if (!h->cfg.squelch_level && !h->cfg.report_levels) return -ENODATA;
+	*n = h->last_nblocks;
+	if (h->last_nblocks > cap) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (h->last_nblocks > 0)
+		HIP_TRY(hipMemcpy2D(rms, (size_t)cap * sizeof(int32_t), h->d_levels, (size_t)h->last_nblocks * sizeof(int32_t),
+		                    (size_t)h->last_nblocks * sizeof(int32_t), (size_t)h->nstreams, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+// The last run's ADC statistics (k_input_stats, option input_stats): the contract of rtlfm_gpu_levels.
+extern "C" int rtlfm_gpu_input_stats(rtlfm_gpu *h, int stream, rtlfm_input_stat *out, int cap, int *n)
+{
+	if (!h || !out || !n || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (!h->opt.input_stats) return -ENODATA;
+	*n = h->stats_nblocks;
+	if (h->stats_nblocks > cap) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	// the kernel indexes the records of a run [stream][nblocks]
+	if (h->stats_nblocks > 0)
+		HIP_TRY(hipMemcpy(out, h->d_istats + (size_t)stream * h->stats_nblocks, (size_t)h->stats_nblocks * sizeof(rtlfm_input_stat),
+		                  hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_input_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int *n)
+{
+	if (!h || !out || !n) return -EINVAL;
+	if (!h->opt.input_stats) return -ENODATA;
+	*n = h->stats_nblocks;
+	if (h->stats_nblocks > cap) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (h->stats_nblocks > 0)
+		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(rtlfm_input_stat), h->d_istats, (size_t)h->stats_nblocks * sizeof(rtlfm_input_stat),
+		                    (size_t)h->stats_nblocks * sizeof(rtlfm_input_stat), (size_t)h->nstreams, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+// The same statistics as a standalone operator on device memory (no handle): tools/input_stats_bench.py times it, and a
+// caller that only wants to know which front ends clip needs no demodulator.
+extern "C" int rtlfm_gpu_input_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                            int nstreams, rtlfm_input_stat *d_out, int nontemporal, void *hip_stream)
+{
+	if (!d_iq || !d_out || ((uintptr_t)d_out & 15)) return -EINVAL;
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
+	HIP_TRY(hipSetDevice(device));
+	const int r = istats::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream);
+	if (r < 0) return r;
+	HIP_TRY(hipGetLastError());
 	return 0;
 }
 
@@ -2246,6 +2327,7 @@ static rtlfm_gpu make_view(rtlfm_gpu *h, int s0, int ns, uint32_t block_len)
 	v.tail_overlap = false;
 	v.timing = false;
 	v.no_deemph_scan = true;
+	v.opt.input_stats = 0;   // run_ragged takes the statistics itself, into the run's own rows
 	v.opt.verify_twice = 0;  // views must not allocate (the shadow rows): ragged runs are not verified
 	v.ev_pending.clear(); v.ev_free.clear();
 	const size_t cb = (size_t)h->cap_blocks;
@@ -2277,6 +2359,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	// views must not allocate: everything any path may need exists before the first one is made
 	if ((r = ensure_work_buffers(h)) < 0 || (r = ensure_res_buffers(h)) < 0 || (r = ensure_deep_buffers(h)) < 0) return r;
 	if (fused::ensure_dummy_tile(h->fws)) return -ENOMEM;
+	if (h->opt.input_stats && (r = ensure_input_stats(h)) < 0) return r;
 	if (!in->d_tmp) {
 		HIP_TRY(hipMalloc(&in->d_tmp, (size_t)S * in->ostride * sizeof(int16_t)));
 		HIP_TRY(hipMalloc(&in->d_tmp_len, (size_t)S * sizeof(int32_t)));
@@ -2302,6 +2385,11 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 			c.block_len = len;
 			c.max_blocks = 1;
 			if ((r = validate_cfg(&c)) < 0) return r;
+			// each buffer's statistics over its own length, filed as [stream][nb] like a batched run's
+			if (h->opt.input_stats &&
+			    (r = istats::launch(in->d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, len, 1, s1 - s0,
+			                        h->d_istats + (size_t)s0 * nb + j, nb, h->opt.input_stats_nt != 0, h->stream)) < 0)
+				return r;
 			rtlfm_gpu v = make_view(h, s0, s1 - s0, len);
 			v.st_cur = cur;
 			v.step = step;
@@ -2317,6 +2405,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 		k_append_results<<<S, 256, 0, h->stream>>>(in->d_result[f], in->ostride, in->d_result_len[f], in->d_tmp, in->ostride,
 		                                          in->d_tmp_len, 0, S, (int)in->ostride);
 	}
+	h->stats_nblocks = h->opt.input_stats ? nb : 0;
 	HIP_TRY(hipGetLastError());
 	return 0;
 }

@@ -137,6 +137,30 @@ class GpuDemod:
         check(self.lib.rtlfm_gpu_levels(self._h, stream, out.ctypes.data, out.size, C.byref(n)), "rtlfm_gpu_levels")
         return out[:n.value].copy()
 
+    def levels_all(self) -> np.ndarray:
+        """int32 [nstreams, buffers of the last run]: every stream's levels in one copy."""
+        cap = max(1, self.cfg.max_blocks)
+        out = np.zeros((self.nstreams, cap), dtype=np.int32)
+        n = C.c_int()
+        check(self.lib.rtlfm_gpu_levels_all(self._h, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_levels_all")
+        return out[:, :n.value].copy()
+
+    def input_stats(self, stream: int = 0) -> np.ndarray:
+        """The ADC statistics of the raw bytes (src/rtl_fm.c:1302-1324) of every buffer of the last run for ``stream``:
+        a record array with pow_sum, pow_count, max, step.  Needs ``set_option("input_stats", 1)`` before the run."""
+        out = np.zeros(max(1, self.cfg.max_blocks), dtype=capi.INPUT_STAT_DTYPE)
+        n = C.c_int()
+        check(self.lib.rtlfm_gpu_input_stats(self._h, stream, out.ctypes.data, out.size, C.byref(n)), "rtlfm_gpu_input_stats")
+        return out[:n.value].copy()
+
+    def input_stats_all(self) -> np.ndarray:
+        """The same for every stream in one copy: records [nstreams, buffers of the last run]."""
+        cap = max(1, self.cfg.max_blocks)
+        out = np.zeros((self.nstreams, cap), dtype=capi.INPUT_STAT_DTYPE)
+        n = C.c_int()
+        check(self.lib.rtlfm_gpu_input_stats_all(self._h, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_input_stats_all")
+        return out[:, :n.value].copy()
+
     # -- state & plumbing ------------------------------------------------------
     def state_get(self, stream: int = 0) -> RtlfmStreamState:
         st = RtlfmStreamState()
