@@ -88,6 +88,28 @@ void rtlpower_plan_cfg(const rtlpower_plan *plan, int window, int boxcar, int co
  */
 int rtlpower_csv_dbm(const rtlpower_plan *plan, int tune, int64_t *avg, int32_t samples, char *out, size_t cap);
 
+/*
+ * The value part of csv_dbm() (src/rtl_power.c:729-760) without a GPU and without touching avg[]: output j
+ * (0 <= j <= i2 - i1, the bounds of :746-747) reads bin (j + i1 + len/2) mod len of the unswapped array (the swap of
+ * :734-738), bin 0 as bin 1 (:732, bin_e > 0 only), and is reduced to what "%.2f" prints of
+ * 10 * log10(((double)avg / rate) / samples) (:749-753) - derived from glibc's own "%.2f", so right by construction.
+ * One more value follows them: the line's trailing one (:755-760), the last kept bin again but formed as the reference
+ * forms it there, avg / (rate * samples) - where a rounding boundary lies within an ulp the two print differently.
+ * centi[] therefore needs room for 2^bin_e + 1 values; *n = i2 - i1 + 2, or 0 when samples == 0 (rtl_power_hip prints
+ * no line for a hop that was never scanned).
+ * centi[j]: bit 31 = the printed sign ("-0.00" keeps it), bits 0 .. 30 = hundredths of a dB; the magnitudes
+ * RTLPOWER_CENTI_INF / RTLPOWER_CENTI_NAN stand for "inf" / "nan" ("-inf", an empty bin, is the int32 -1).
+ * This is the definition rtlpower_gpu_report() is held to, and what decides the bins its kernel leaves to the host.
+ */
+#define RTLPOWER_CENTI_SIGN 0x80000000u
+#define RTLPOWER_CENTI_INF 0x7fffffffu
+#define RTLPOWER_CENTI_NAN 0x7ffffffeu
+int rtlpower_report_host(const int64_t *avg, int32_t samples, double rate, int bin_e, double crop, int32_t *centi, int *n);
+/* The line rtlpower_csv_dbm() writes (src/rtl_power.c:740-760), from the n values of such a report: the header
+ * fields, each of the first n - 1 values followed by ", ", then the trailing value with "\n".  Integer formatting
+ * only.  Returns the string length (0 and an empty string for n == 0), or -ENOBUFS. */
+int rtlpower_csv_report(const rtlpower_plan *plan, int tune, const int32_t *centi, int n, int32_t samples, char *out, size_t cap);
+
 /* window_coefs[i] = (int)(256 * window_fn(i, length)) (src/rtl_power.c:985-988); host only */
 int rtlpower_window_coefs(int window, int length, int32_t *out);
 
@@ -114,6 +136,30 @@ int rtlpower_gpu_scan(rtlpower_gpu *h, int stream, const uint8_t *buf, uint32_t 
 int rtlpower_gpu_fetch(rtlpower_gpu *h, int stream, int64_t *avg, int32_t *samples);
 /* csv_dbm() zeroes avg[] and samples after reporting (:761-764). */
 int rtlpower_gpu_clear(rtlpower_gpu *h);
+/* The inverse of rtlpower_gpu_fetch (the counterpart of rtlfm_gpu_state_set): tuning_state.avg[0 .. 2^bin_e) and
+ * .samples (src/rtl_power.c:86-108) of one stream are replaced, behind whatever is queued.  With fetch it makes a
+ * handle checkpointable. */
+int rtlpower_gpu_store(rtlpower_gpu *h, int stream, const int64_t *avg, int32_t samples);
+/* scanner()'s reads (src/rtl_power.c:650-719) of every stream from HOST memory, laid out as for
+ * rtlpower_gpu_scan_device: one copy into a device buffer the handle owns, then one scan - n sources x hops enter as
+ * one call instead of n x hops calls of rtlpower_gpu_scan.  The caller's memory is free again on return; the scan
+ * itself is asynchronous. */
+int rtlpower_gpu_scan_host(rtlpower_gpu *h, const uint8_t *iq, size_t stream_stride, int nreads);
+/*
+ * csv_dbm()'s arithmetic (src/rtl_power.c:729-753) and its reset (:761-764) for EVERY stream of the handle in one
+ * kernel launch, enqueued on the handle's stream behind any scans, followed by one copy of all values, all samples
+ * and the list of undecided bins into pinned host memory the handle owns (allocated by the first report).
+ * Asynchronous.  `rate` is tuning_state.rate, `crop` the plan's; clear != 0 leaves avg[] and samples of every stream
+ * zero, as csv_dbm() does.  Values are those of rtlpower_report_host(), every one: where the device's log10 cannot
+ * decide the rounding of "%.2f" the bin goes to the host, which decides it with that definition before a fetch
+ * returns anything.  A new report waits for the copy of the one before.
+ */
+int rtlpower_gpu_report(rtlpower_gpu *h, double rate, double crop, int clear);
+/* Waits for the last report and copies one stream's values out: *n of them (as rtlpower_report_host counts them; 0 for a stream whose samples were 0), *samples as they were before the reset.  -ENODATA without a report, -ENOBUFS when cap < *n, -EOVERFLOW
+ * when more bins were left to the host than the list holds (the report then has no values). */
+int rtlpower_gpu_report_fetch(rtlpower_gpu *h, int stream, int32_t *centi, int cap, int *n, int32_t *samples);
+/* The same for every stream: stream s at centi + s * stream_stride (in values), n[s] and samples[s] (either may be NULL). */
+int rtlpower_gpu_report_fetch_all(rtlpower_gpu *h, int32_t *centi, size_t stream_stride, int32_t *n, int32_t *samples);
 int rtlpower_gpu_sync(rtlpower_gpu *h);
 int rtlpower_gpu_set_stream(rtlpower_gpu *h, void *hip_stream);
 /* Cross-stream ordering as rtlfm_gpu_wait_for / rtlfm_gpu_release_to (include/rtlfm_hip.h). */
@@ -131,7 +177,9 @@ int rtlpower_gpu_release_to(rtlpower_gpu *h, void *consumer_stream);
  * other; 1: from 2^18 bins on and for scans of several batches; 2: wherever it applies.  (Measured: the kernels overlap, the
  * scan gains 4-5 % at 2^19 .. 2^21 bins in two sessions of three and loses 1-3 % at 2^15 .. 2^17.)  "staged_batch" = n > 0: at most n reads per batch (tests).
  * -ENOENT for an unknown name.  get_option reads them back, and "last_kernel" (read-only): which transform the last
- * scan took, one of RTLPOWER_KERNEL_*. */
+ * scan took, one of RTLPOWER_KERNEL_*; "report_doubts" (read-only, waits for the report): how many bins the last
+ * rtlpower_gpu_report left to the host.  "report_guard_ppm" (1 .. 500000, default 1; tests): the distance from a
+ * rounding boundary, in millionths of a hundredth of a dB, below which the report kernel does not decide. */
 int rtlpower_gpu_set_option(rtlpower_gpu *h, const char *name, long value);
 int rtlpower_gpu_get_option(rtlpower_gpu *h, const char *name, long *value);
 enum rtlpower_kernel {

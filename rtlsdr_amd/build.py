@@ -30,7 +30,7 @@ UNIT_HEADERS = {
                       "input_stats_kernel.h", os.path.join("..", "..", "include", "rtlfm_hip.h")],
     "rtlfm_place.hip": ["debug_poison.h", "bw_probe_kernel.h", os.path.join("..", "..", "include", "rtlfm_hip.h")],
     "monitor.cpp": [os.path.join("..", "..", "include", "rtlfm_monitor.h"), os.path.join("..", "..", "include", "rtlfm_hip.h")],  # host only
-    "rtlpower_hip.hip": ["debug_poison.h", "stream_pool.h", "dsp_device.h", "power_kernels.h", os.path.join("..", "..", "include", "rtlpower_hip.h"),
+    "rtlpower_hip.hip": ["debug_poison.h", "stream_pool.h", "dsp_device.h", "power_kernels.h", "power_report_kernel.h", os.path.join("..", "..", "include", "rtlpower_hip.h"),
                          os.path.join("..", "..", "include", "rtlfm_hip.h")],
 }
 # -ffile-prefix-map: __FILE__ (HIP_TRY's messages) and every other path the compiler embeds are written relative to the
@@ -159,7 +159,7 @@ def build_host(force: bool = False, verbose: bool = False) -> tuple[str, str]:
     pw_src = os.path.join(HOST, "rtl_power_hip.cpp")
     if stale(POWER_CLI_OUT, [pw_src, SHIM_OUT, OUT, os.path.join(inc, "rtlpower_hip.h")]):
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", POWER_CLI_OUT, pw_src,
-               "-L" + HOST, "-L" + CSRC, "-lrtlsdr_file", "-lrtlfm_hip", "-lm",
+               "-L" + HOST, "-L" + CSRC, "-lrtlsdr_file", "-lrtlfm_hip", "-lm", "-lpthread",
                "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib",
                "-Wl,--allow-shlib-undefined"]
         if verbose:

@@ -325,7 +325,15 @@ _POWER_SIGNATURES = [
     ("rtlpower_gpu_timing_read", C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_int)]),
     ("rtlpower_gpu_clock_probe", C.c_int, [C.c_void_p, C.c_int]),
     ("rtlpower_gpu_clock_read", C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double)]),
+    ("rtlpower_report_host", C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_int, C.c_double, C.c_void_p, _P(C.c_int)]),
+    ("rtlpower_csv_report", C.c_int, [_P(RtlpowerPlan), C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_char_p, C.c_size_t]),
+    ("rtlpower_gpu_store", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int32]),
+    ("rtlpower_gpu_scan_host", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
+    ("rtlpower_gpu_report", C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    ("rtlpower_gpu_report_fetch", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int), _P(C.c_int32)]),
+    ("rtlpower_gpu_report_fetch_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 ]
+CENTI_SIGN, CENTI_INF, CENTI_NAN = 0x80000000, 0x7FFFFFFF, 0x7FFFFFFE  # RTLPOWER_CENTI_* (include/rtlpower_hip.h)
 _SIGNATURES = _SIGNATURES + _POWER_SIGNATURES
 
 # ... and include/rtlfm_monitor.h (the level monitor: host code inside the same library)

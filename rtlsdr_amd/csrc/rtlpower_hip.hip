@@ -15,6 +15,7 @@
 #include "debug_poison.h"
 #include "stream_pool.h"
 #include "power_kernels.h"
+#include "power_report_kernel.h"
 
 using namespace rtlpower;
 
@@ -77,6 +78,19 @@ struct rtlpower_gpu {
 	int stamp_cap = 0, stamp_last = 0;     // workgroups the buffer holds / of the last stamped launch
 	bool attr_set = false, attr_big = false;  // the kernels' dynamic-LDS limits are raised on this handle's device
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending, ev_free;
+	// rtlpower_gpu_report (power_report_kernel.h): one device block - doubt counter, doubt list, samples, values - and its
+	// pinned mirror, both allocated by the first report; `arrived` is the kernel's per-stream counter
+	uint8_t *d_rep = nullptr, *h_rep = nullptr;
+	uint32_t *d_arrived = nullptr;
+	hipEvent_t ev_rep = nullptr;
+	int rep_outn = 0;            // values per stream of the last report (the kept bins and the trailing value)
+	double rep_rate = 0;
+	bool rep_issued = false, rep_resolved = false;
+	int rep_status = 0;          // what resolving found (0, -EOVERFLOW, -EIO)
+	long rep_doubts = 0;         // option "report_doubts" (read-only)
+	long rep_guard_ppm = 1;      // option "report_guard_ppm": the guard in millionths of a hundredth of a dB (tests widen it)
+	uint8_t *d_in = nullptr; size_t in_cap = 0;  // landing zone of rtlpower_gpu_scan_host()
+	hipEvent_t ev_in = nullptr;
 };
 
 // the window functions, src/rtl_power.c:329-408
@@ -219,6 +233,109 @@ extern "C" int rtlpower_csv_dbm(const rtlpower_plan *p, int tune, int64_t *avg, 
 	return (int)sres.size();
 }
 
+// ---- the report: host definition and formatter (no GPU needed) ---------------------
+
+// One value as glibc's own "%.2f" prints the reference's expression (src/rtl_power.c:749-753), read back into
+// sign + hundredths: right by construction, and what the doubt list of k_power_report is resolved with.
+static uint32_t report_centi_one(int64_t avg, int32_t samples, double rate, bool trailing)
+{
+	double dbm = (double)avg;
+	if (trailing) {
+		dbm = (double)avg / (rate * (double)samples);  // the line's last value, :755-758: one division
+	} else {
+		dbm /= rate;
+		dbm /= (double)samples;
+	}
+	dbm = 10 * log10(dbm);
+	char tmp[400];
+	snprintf(tmp, sizeof(tmp), "%.2f", dbm);
+	const char *t = tmp;
+	uint32_t sign = 0;
+	if (*t == '-') { sign = kCentiSign; t++; }
+	if (*t == 'i') return sign | kCentiInf;
+	if (*t == 'n') return sign | kCentiNan;
+	uint64_t v = 0;
+	for (; *t; t++)
+		if (*t != '.') v = v * 10 + (uint64_t)(*t - '0');
+	return sign | (uint32_t)(v < kCentiDoubt ? v : kCentiDoubt - 1);
+}
+
+// i1 and the number of kept bins, in doubles as csv_dbm() writes them (:746-747)
+static int report_range(int bin_e, double crop, int *i1, int *outn)
+{
+	if (bin_e < 0 || bin_e > 21 || !(crop >= 0.0) || !(crop < 1.0)) return -EINVAL;
+	const int len = 1 << bin_e;
+	*i1 = 0 + (int)((double)len * crop * 0.5);
+	const int i2 = (len - 1) - (int)((double)len * crop * 0.5);
+	*outn = i2 - *i1 + 1;
+	return *outn >= 1 ? 0 : -EINVAL;
+}
+
+extern "C" int rtlpower_report_host(const int64_t *avg, int32_t samples, double rate, int bin_e, double crop, int32_t *centi,
+                                    int *n)
+{
+	int i1 = 0, outn = 0;
+	if (!avg || !centi || !n || !(rate > 0.0)) return -EINVAL;
+	const int r = report_range(bin_e, crop, &i1, &outn);
+	if (r < 0) return r;
+	*n = 0;
+	if (samples == 0) return 0;  // no line for a hop that was never scanned
+	const int len = 1 << bin_e;
+	for (int j = 0; j < outn; j++) {
+		int b = (j + i1 + len / 2) & (len - 1);
+		if (bin_e > 0 && b == 0) b = 1;
+		centi[j] = (int32_t)report_centi_one(avg[b], samples, rate, false);
+		if (j == outn - 1) centi[outn] = (int32_t)report_centi_one(avg[b], samples, rate, true);
+	}
+	*n = outn + 1;
+	return 0;
+}
+
+static inline char *put_centi(char *o, uint32_t w)
+{
+	if (w & kCentiSign) *o++ = '-';
+	w &= ~kCentiSign;
+	if (w == kCentiInf) { memcpy(o, "inf", 3); return o + 3; }
+	if (w >= kCentiDoubt) { memcpy(o, "nan", 3); return o + 3; }
+	char d[12];
+	int k = 0;
+	uint32_t whole = w / 100, frac = w % 100;
+	do { d[k++] = (char)('0' + whole % 10); whole /= 10; } while (whole);
+	while (k) *o++ = d[--k];
+	*o++ = '.';
+	*o++ = (char)('0' + frac / 10);
+	*o++ = (char)('0' + frac % 10);
+	return o;
+}
+
+extern "C" int rtlpower_csv_report(const rtlpower_plan *p, int tune, const int32_t *centi, int n, int32_t samples, char *out,
+                                   size_t cap)
+{
+	// the line of csv_dbm(), src/rtl_power.c:740-760, from values already reduced to hundredths
+	if (!p || !centi || !out || n < 0 || n == 1 || cap < 1) return -EINVAL;
+	out[0] = 0;
+	if (n == 0) return 0;
+	const int len = 1 << p->bin_e, ds = p->downsample;
+	const int freq = rtlpower_tune_freq(p, tune);
+	const int bin_count = (int)((double)len * (1.0 - p->crop));
+	const int bw2 = (int)(((double)p->rate * (double)bin_count) / (len * 2 * ds));
+	char head[128];
+	const int hn = snprintf(head, sizeof(head), "%i, %i, %.2f, %i, ", freq - bw2, freq + bw2, (double)p->rate / (double)(len * ds), samples);
+	if ((size_t)hn + (size_t)(n + 1) * 16 + 2 > cap) return -ENOBUFS;  // (a value and its separator: at most 15 bytes)
+	memcpy(out, head, (size_t)hn);
+	char *o = out + hn;
+	for (int j = 0; j < n - 1; j++) {
+		o = put_centi(o, (uint32_t)centi[j]);
+		*o++ = ','; *o++ = ' ';
+	}
+	o = put_centi(o, (uint32_t)centi[n - 1]);  // the last bin once more, as the reference forms it there (:755-760)
+	*o++ = '\n';
+	*o = 0;
+	return (int)(o - out);
+}
+
+static int report_wait(rtlpower_gpu *h);
+
 static int validate(const rtlpower_cfg *c)
 {
 	if (c->bin_e < 0 || c->bin_e > 21) return -EINVAL;  // frequency_range() plans 2^1 .. 2^21 bins (src/rtl_power.c:483-486)
@@ -349,7 +466,10 @@ extern "C" int rtlpower_gpu_destroy(rtlpower_gpu *h)
 		if (e) (void)hipEventDestroy(e);
 	for (auto &p : h->ev_pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
 	for (auto &p : h->ev_free) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-	void *ptrs[] = {h->d_window, h->d_window16, h->d_tw, h->d_avg, h->d_samples, h->d_decA, h->d_decB, h->d_one, h->d_stamps, h->d_work, h->d_ave, h->d_window16T, h->d_tbuf, h->d_part, h->d_dec32};
+	if (h->h_rep) (void)hipHostFree(h->h_rep);
+	for (hipEvent_t e : {h->ev_rep, h->ev_in})
+		if (e) (void)hipEventDestroy(e);
+	void *ptrs[] = {h->d_rep, h->d_arrived, h->d_in, h->d_window, h->d_window16, h->d_tw, h->d_avg, h->d_samples, h->d_decA, h->d_decB, h->d_one, h->d_stamps, h->d_work, h->d_ave, h->d_window16T, h->d_tbuf, h->d_part, h->d_dec32};
 	for (void *p : ptrs)
 		if (p) (void)hipFree(p);
 	if (h->pipe.aux) (void)hipStreamSynchronize(h->pipe.aux);
@@ -440,6 +560,11 @@ extern "C" int rtlpower_gpu_set_option(rtlpower_gpu *h, const char *name, long v
 		h->scan_frames = value != 0;
 		return 0;
 	}
+	if (!strcmp(name, "report_guard_ppm")) {
+		if (value < 1 || value > 500000) return -EINVAL;
+		h->rep_guard_ppm = value;
+		return 0;
+	}
 	return -ENOENT;
 }
 
@@ -453,6 +578,13 @@ extern "C" int rtlpower_gpu_get_option(rtlpower_gpu *h, const char *name, long *
 	if (!strcmp(name, "staged_batch")) { *value = h->staged_batch; return 0; }
 	if (!strcmp(name, "scan_frames")) { *value = h->scan_frames; return 0; }
 	if (!strcmp(name, "last_kernel")) { *value = h->last_kernel; return 0; }
+	if (!strcmp(name, "report_guard_ppm")) { *value = h->rep_guard_ppm; return 0; }
+	if (!strcmp(name, "report_doubts")) {
+		if (!h->rep_issued) { *value = 0; return 0; }
+		const int r = report_wait(h);
+		*value = h->rep_doubts;
+		return r == -EOVERFLOW ? 0 : r;  // (an overflowing report still says how many bins it was handed)
+	}
 	return -ENOENT;
 }
 
@@ -908,5 +1040,156 @@ extern "C" int rtlpower_gpu_fetch(rtlpower_gpu *h, int stream, int64_t *avg, int
 	HIP_TRY(hipStreamSynchronize(h->stream));
 	if (avg) HIP_TRY(hipMemcpy(avg, h->d_avg + (size_t)stream * h->N, (size_t)h->N * sizeof(long long), hipMemcpyDeviceToHost));
 	if (samples) HIP_TRY(hipMemcpy(samples, h->d_samples + stream, sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlpower_gpu_store(rtlpower_gpu *h, int stream, const int64_t *avg, int32_t samples)
+{
+	// the inverse of rtlpower_gpu_fetch: tuning_state.avg[] / .samples of one stream, behind what is queued
+	if (!h || !avg || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(hipMemcpyAsync(h->d_avg + (size_t)stream * h->N, avg, (size_t)h->N * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(hipMemcpyAsync(h->d_samples + stream, &samples, sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(hipStreamSynchronize(h->stream));  // the caller's memory is free again
+	return 0;
+}
+
+extern "C" int rtlpower_gpu_scan_host(rtlpower_gpu *h, const uint8_t *iq, size_t stream_stride, int nreads)
+{
+	// scanner()'s reads of every stream from host memory (stream s, read r at iq + s*stream_stride + r*buf_len):
+	// one copy into a buffer the handle owns, one rtlpower_gpu_scan_device
+	if (!h || !iq || nreads < 1) return -EINVAL;
+	const size_t row = (size_t)nreads * h->cfg.buf_len;
+	if (stream_stride < row) return -EINVAL;
+	HIP_TRY(hipSetDevice(h->device));
+	const size_t pitch = (row + 15) & ~(size_t)15;
+	const size_t need = pitch * (size_t)h->nstreams;
+	if (h->in_cap < need) {
+		HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier scan may still read the old buffer
+		if (h->d_in) (void)hipFree(h->d_in);
+		h->d_in = nullptr; h->in_cap = 0;
+		HIP_TRY(hipMalloc(&h->d_in, need));
+		h->in_cap = need;
+	}
+	if (!h->ev_in) HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+	HIP_TRY(hipMemcpy2DAsync(h->d_in, pitch, iq, stream_stride, row, (size_t)h->nstreams, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(hipEventRecord(h->ev_in, h->stream));
+	const int r = rtlpower_gpu_scan_device(h, h->d_in, pitch, nreads);
+	HIP_TRY(hipEventSynchronize(h->ev_in));  // the copy has left the caller's memory; the scan itself stays asynchronous
+	return r;
+}
+
+// ---- the report on the device (power_report_kernel.h) ------------------------------
+
+static constexpr uint32_t kDoubtCap = 65536;
+static constexpr size_t kRepDoubtsAt = 16, kRepSamplesAt = kRepDoubtsAt + (size_t)kDoubtCap * sizeof(ReportDoubt);
+static inline size_t rep_values_at(int nstreams) { return kRepSamplesAt + (((size_t)nstreams * 4 + 15) & ~(size_t)15); }
+
+extern "C" int rtlpower_gpu_report(rtlpower_gpu *h, double rate, double crop, int clear)
+{
+	// csv_dbm() (src/rtl_power.c:722-765) for every stream: enqueued behind the scans, results into pinned memory
+	if (!h || !(rate > 0.0)) return -EINVAL;
+	int i1 = 0, outn = 0;
+	const int rr = report_range(h->cfg.bin_e, crop, &i1, &outn);
+	if (rr < 0) return rr;
+	HIP_TRY(hipSetDevice(h->device));
+	const int S = h->nstreams;
+	const size_t vals_at = rep_values_at(S);
+	if (!h->ev_rep) {  // first use: sized for crop 0.  ev_rep is created last; a first use that failed half way starts over
+		const size_t bytes = vals_at + (size_t)S * ((size_t)h->N + 1) * sizeof(uint32_t);
+		if (h->h_rep) (void)hipHostFree(h->h_rep);
+		if (h->d_arrived) (void)hipFree(h->d_arrived);
+		if (h->d_rep) (void)hipFree(h->d_rep);
+		h->h_rep = nullptr; h->d_arrived = nullptr; h->d_rep = nullptr;
+		HIP_TRY(hipMalloc(&h->d_rep, bytes));
+		HIP_TRY(hipMalloc(&h->d_arrived, (size_t)S * sizeof(uint32_t)));
+		HIP_TRY(hipMemset(h->d_arrived, 0, (size_t)S * sizeof(uint32_t)));
+		HIP_TRY(hipHostMalloc(&h->h_rep, bytes, hipHostMallocDefault));
+		HIP_TRY(hipEventCreateWithFlags(&h->ev_rep, hipEventDisableTiming));
+	}
+	if (h->rep_issued) HIP_TRY(hipEventSynchronize(h->ev_rep));  // the last report's copy has left the pinned block
+	hipStream_t q = h->stream;
+	ReportParams p{};
+	p.avg = h->d_avg; p.samples = h->d_samples; p.len = h->N; p.i1 = i1; p.outn = outn;
+	p.patch = h->cfg.bin_e > 0; p.clear = clear != 0;
+	// one workgroup per stream where the streams alone fill the device, else segments of a row
+	int groups = 1;
+	if (S < 1024) {
+		groups = (2048 + S - 1) / S;
+		const int most = (h->N + 4 * kReportThreads - 1) / (4 * kReportThreads);
+		if (groups > most) groups = most;
+	}
+	p.seg = ((h->N + groups - 1) / groups + kReportThreads - 1) / kReportThreads * kReportThreads;
+	p.groups = (h->N + p.seg - 1) / p.seg;
+	p.rate = rate; p.guard = (double)h->rep_guard_ppm * 1e-6;
+	p.doubt_count = reinterpret_cast<uint32_t *>(h->d_rep);
+	p.doubts = reinterpret_cast<ReportDoubt *>(h->d_rep + kRepDoubtsAt); p.doubt_cap = kDoubtCap;
+	p.out_samples = reinterpret_cast<int32_t *>(h->d_rep + kRepSamplesAt);
+	p.out = reinterpret_cast<uint32_t *>(h->d_rep + vals_at);
+	p.arrived = h->d_arrived;
+	HIP_TRY(hipMemsetAsync(h->d_rep, 0, kRepDoubtsAt, q));
+	hipLaunchKernelGGL(k_power_report, dim3((unsigned)S * (unsigned)p.groups), dim3(kReportThreads), 0, q, p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(h->h_rep, h->d_rep, vals_at + (size_t)S * ((size_t)outn + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, q));
+	HIP_TRY(hipEventRecord(h->ev_rep, q));
+	h->rep_outn = outn + 1; h->rep_rate = rate;
+	h->rep_issued = true; h->rep_resolved = false; h->rep_status = 0; h->rep_doubts = 0;
+	return 0;
+}
+
+// waits for the last report's copy and decides, once, the bins the kernel left to the host
+static int report_wait(rtlpower_gpu *h)
+{
+	if (!h->rep_issued) return -ENODATA;
+	if (h->rep_resolved) return h->rep_status;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(hipEventSynchronize(h->ev_rep));
+	const uint32_t count = *reinterpret_cast<const uint32_t *>(h->h_rep);
+	h->rep_doubts = (long)count;
+	h->rep_resolved = true;
+	if (count > kDoubtCap) {
+		fprintf(stderr, "rtlpower_hip: the report left %u bins to the host, the list holds %u; nothing is guessed\n", count, kDoubtCap);
+		return h->rep_status = -EOVERFLOW;
+	}
+	const ReportDoubt *d = reinterpret_cast<const ReportDoubt *>(h->h_rep + kRepDoubtsAt);
+	const int32_t *samples = reinterpret_cast<const int32_t *>(h->h_rep + kRepSamplesAt);
+	uint32_t *vals = reinterpret_cast<uint32_t *>(h->h_rep + rep_values_at(h->nstreams));
+	for (uint32_t k = 0; k < count; k++) {
+		if (d[k].stream < 0 || d[k].stream >= h->nstreams || d[k].j < 0 || d[k].j >= h->rep_outn) return h->rep_status = -EIO;
+		vals[(size_t)d[k].stream * h->rep_outn + d[k].j] =
+		    report_centi_one(d[k].avg, samples[d[k].stream], h->rep_rate, d[k].j == h->rep_outn - 1);
+	}
+	return h->rep_status = 0;
+}
+
+extern "C" int rtlpower_gpu_report_fetch(rtlpower_gpu *h, int stream, int32_t *centi, int cap, int *n, int32_t *samples)
+{
+	if (!h || stream < 0 || stream >= h->nstreams || cap < 0) return -EINVAL;
+	const int r = report_wait(h);
+	if (r < 0) return r;
+	const int32_t ns = reinterpret_cast<const int32_t *>(h->h_rep + kRepSamplesAt)[stream];
+	const int len = ns == 0 ? 0 : h->rep_outn;
+	if (n) *n = len;
+	if (samples) *samples = ns;
+	if (len > cap || (len && !centi)) return -ENOBUFS;
+	if (len) memcpy(centi, h->h_rep + rep_values_at(h->nstreams) + (size_t)stream * h->rep_outn * 4, (size_t)len * 4);
+	return 0;
+}
+
+extern "C" int rtlpower_gpu_report_fetch_all(rtlpower_gpu *h, int32_t *centi, size_t stream_stride, int32_t *n, int32_t *samples)
+{
+	// every stream: values of stream s at centi + s*stream_stride (int32 elements), n[s] of them (0 where samples[s] == 0)
+	if (!h || !centi) return -EINVAL;
+	const int r = report_wait(h);
+	if (r < 0) return r;
+	if (stream_stride < (size_t)h->rep_outn) return -ENOBUFS;
+	const int32_t *ns = reinterpret_cast<const int32_t *>(h->h_rep + kRepSamplesAt);
+	const uint8_t *vals = h->h_rep + rep_values_at(h->nstreams);
+	for (int s = 0; s < h->nstreams; s++) {
+		const int len = ns[s] == 0 ? 0 : h->rep_outn;
+		if (n) n[s] = len;
+		if (samples) samples[s] = ns[s];
+		if (len) memcpy(centi + (size_t)s * stream_stride, vals + (size_t)s * h->rep_outn * 4, (size_t)len * 4);
+	}
 	return 0;
 }

@@ -69,6 +69,54 @@ class GpuPower:
     def clear(self):
         check(self.lib.rtlpower_gpu_clear(self._h), "rtlpower_gpu_clear")
 
+    def store(self, avg, samples: int, stream: int = 0):
+        """The inverse of ``fetch``: replaces avg[] / samples of one tuning state."""
+        a = np.ascontiguousarray(avg, dtype=np.int64)
+        if a.size != 1 << self.cfg.bin_e:
+            raise ValueError("avg must hold 2^bin_e values")
+        check(self.lib.rtlpower_gpu_store(self._h, stream, a.ctypes.data, int(samples)), "rtlpower_gpu_store")
+
+    def scan_host(self, iq, nreads: int | None = None):
+        """iq: uint8 [nstreams, nreads*buf_len] in host memory: one copy, one scan of every tuning state."""
+        a = np.ascontiguousarray(iq, dtype=np.uint8)
+        if a.ndim != 2 or a.shape[0] != self.nstreams:
+            raise ValueError("iq must be [nstreams, nreads*buf_len]")
+        if nreads is None:
+            nreads = a.shape[1] // int(self.cfg.buf_len)
+        check(self.lib.rtlpower_gpu_scan_host(self._h, a.ctypes.data, a.strides[0], nreads), "rtlpower_gpu_scan_host")
+
+    def report(self, rate: float, crop: float = 0.0, clear: bool = True):
+        """csv_dbm()'s values (src/rtl_power.c:722-765) of every tuning state, computed on the device behind the queued
+        scans.  Returns (centi int32 [nstreams, n_max], n int32 [nstreams], samples int32 [nstreams]): row s holds n[s]
+        values as ``rtlpower_report_host`` defines them - the kept bins, then the line's trailing value - (n[s] == 0 where the state had no samples)."""
+        check(self.lib.rtlpower_gpu_report(self._h, float(rate), float(crop), int(bool(clear))), "rtlpower_gpu_report")
+        return self.report_fetch_all()
+
+    def report_async(self, rate: float, crop: float = 0.0, clear: bool = True):
+        check(self.lib.rtlpower_gpu_report(self._h, float(rate), float(crop), int(bool(clear))), "rtlpower_gpu_report")
+
+    def report_fetch(self, stream: int = 0):
+        """(values int32 [n], samples) of one tuning state of the last report."""
+        out = np.zeros((1 << self.cfg.bin_e) + 1, dtype=np.int32)
+        n, samples = C.c_int(), C.c_int32()
+        check(self.lib.rtlpower_gpu_report_fetch(self._h, stream, out.ctypes.data, out.size, C.byref(n), C.byref(samples)),
+              "rtlpower_gpu_report_fetch")
+        return out[:n.value], samples.value
+
+    def report_fetch_all(self):
+        width = (1 << self.cfg.bin_e) + 1
+        out = np.zeros((self.nstreams, width), dtype=np.int32)
+        n = np.zeros(self.nstreams, dtype=np.int32)
+        samples = np.zeros(self.nstreams, dtype=np.int32)
+        check(self.lib.rtlpower_gpu_report_fetch_all(self._h, out.ctypes.data, width, n.ctypes.data, samples.ctypes.data),
+              "rtlpower_gpu_report_fetch_all")
+        return out[:, :int(n.max(initial=0))], n, samples
+
+    @property
+    def report_doubts(self) -> int:
+        """How many bins the last report left to the host."""
+        return self.get_option("report_doubts")
+
     def set_option(self, name: str, value: int):
         """Tunables by name (include/rtlpower_hip.h): "groups", "staged_fast", "scan_frames", "dec_fast"."""
         check(self.lib.rtlpower_gpu_set_option(self._h, name.encode(), int(value)), f"rtlpower_gpu_set_option({name})")
@@ -103,6 +151,25 @@ class GpuPower:
         mhz, span = C.c_double(), C.c_double()
         r = self.lib.rtlpower_gpu_clock_read(self._h, C.byref(mhz), C.byref(span))
         return (mhz.value, span.value) if r == 0 else None
+
+
+def report_host(avg, samples: int, rate: float, bin_e: int, crop: float = 0.0) -> np.ndarray:
+    """``rtlpower_report_host``: the values csv_dbm() prints, as sign + hundredths (no GPU; avg is left as it is)."""
+    a = np.ascontiguousarray(avg, dtype=np.int64)
+    out = np.zeros((1 << bin_e) + 1, dtype=np.int32)
+    n = C.c_int()
+    check(capi.load().rtlpower_report_host(a.ctypes.data, int(samples), float(rate), bin_e, float(crop), out.ctypes.data,
+                                           C.byref(n)), "rtlpower_report_host")
+    return out[:n.value]
+
+
+def csv_report(plan, tune: int, centi, samples: int) -> bytes:
+    """``rtlpower_csv_report``: csv_dbm()'s line from such values."""
+    c = np.ascontiguousarray(centi, dtype=np.int32)
+    buf = C.create_string_buffer(c.size * 16 + 256)
+    n = check(capi.load().rtlpower_csv_report(C.byref(plan), tune, c.ctypes.data, c.size, int(samples), buf, len(buf)),
+              "rtlpower_csv_report")
+    return buf.raw[:n]
 
 
 def window_coefs(window: int, length: int) -> np.ndarray:
