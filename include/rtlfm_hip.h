@@ -270,6 +270,30 @@ int rtlfm_gpu_input_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int 
 int rtlfm_gpu_input_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
                                  int nstreams, rtlfm_input_stat *d_out, int nontemporal, void *hip_stream);
 
+/* Input health: what the reference's other three passes over the raw bytes of a transfer count, one record per buffer:
+ *   overload   bytes equal to 0 or 255: softagc()'s `overload` (src/librtlsdr.c:3288-3327) and detect_overload()'s
+ *              overload_count (src/rtl_tcp.c:235-244)
+ *   high       bytes < 64 or > 191: softagc()'s high_level
+ *   lost       what underrun_test() (src/rtl_test.c:121-151) adds to `lost` at positions 1 .. len-1 of this buffer; the
+ *              term at position 0 needs the previous buffer's last byte and is added by the host engine
+ *              (include/rtlfm_agc.h) from `first` and its own carried counter
+ *   first,last buf[0] and buf[len-1];  pad_ is always 0
+ * Taken on the GPU (k_input_health, csrc/input_health_kernel.h) by every run while the option "input_health" is 1
+ * (default 0: nothing is launched, nothing allocated), whatever path the run takes, ragged runs per buffer over its own
+ * length; integer and bit-identical to the reference.  With "input_stats" on as well ONE launch reads the input and
+ * writes both record arrays.  The functions follow rtlfm_gpu_input_stats / _all / _device.
+ */
+typedef struct { uint32_t overload, high, lost; uint8_t first, last; uint16_t pad_; } rtlfm_input_health;
+int rtlfm_gpu_input_health(rtlfm_gpu *h, int stream, rtlfm_input_health *out, int cap, int *n);
+int rtlfm_gpu_input_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n);
+int rtlfm_gpu_input_health_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                  int nstreams, rtlfm_input_health *d_out, int nontemporal, void *hip_stream);
+/* The launch a handle with both options on makes, without a handle: d_out as above and d_stats as
+ * rtlfm_gpu_input_stats_device's d_out, from one read of the input. */
+int rtlfm_gpu_input_health_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                        int nstreams, rtlfm_input_health *d_out, rtlfm_input_stat *d_stats, int nontemporal,
+                                        void *hip_stream);
+
 int rtlfm_gpu_state_get(rtlfm_gpu *h, int stream, rtlfm_stream_state *st);
 int rtlfm_gpu_state_set(rtlfm_gpu *h, int stream, const rtlfm_stream_state *st);
 /* demod_init() values for every stream. */
@@ -363,9 +387,13 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *   input_stats          1: every run also takes the ADC statistics of its raw input bytes (rtlfm_gpu_input_stats; one more
  *                        kernel, k_input_stats, in front of the front end; default 0; anything but 0 / 1 -EINVAL)
  *   input_stats_nt       that kernel's loads non-temporal (1, default) or plain (0): an A/B switch, LAB.md
+ *   input_health         1: every run also takes the overload / high-level / continuity records of its raw input bytes
+ *                        (rtlfm_gpu_input_health; k_input_health in front of the front end, which with input_stats on takes
+ *                        the statistics in the same launch; default 0; anything but 0 / 1 -EINVAL); loads as input_stats_nt
  * Read-only (rtlfm_gpu_get_option):
  *   verify_runs         runs executed under verify_twice so far, and
  *   verify_mismatches    ... how many of them differed between their two executions
+ *   block_len            the buffer length the handle was created with
  *   ring_apart           1 / 0: the result buffers behind rtlfm_gpu_push() / _run() are / are not a quarter of the HBM
  *                        away from the ring's device input; -1 before the ring exists (it is built by the first push)
  *   ring_tries           searches the ring's placement took: 2 = the first found every candidate in the input's class and the

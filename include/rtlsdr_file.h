@@ -74,6 +74,14 @@ int rtlsdr_cancel_async(rtlsdr_dev_t *dev);
  */
 typedef int (*rtlamd_file_buffer_source_t)(void *ctx, unsigned char **buf, uint32_t *cap);
 int rtlamd_file_set_buffer_source(rtlsdr_dev_t *dev, rtlamd_file_buffer_source_t source, void *ctx);
+/*
+ * Extension (not one of the 26): the tuner gain by index into rtlsdr_get_tuner_gains()'s table, for a software AGC
+ * that runs on the consumer's side (include/rtlfm_agc.h; the reference's own is rtlsdr_set_tuner_gain_index(),
+ * src/librtlsdr.c:1465-1485).  A file source records the index (_get_ returns it); a tcp:// source also sends the
+ * rtl_tcp command 0x0d.  0, -1 for a NULL device, -22 for an index outside the table.
+ */
+int rtlamd_file_set_gain_index(rtlsdr_dev_t *dev, int idx);
+int rtlamd_file_get_gain_index(rtlsdr_dev_t *dev);
 int rtlsdr_set_bias_tee(rtlsdr_dev_t *dev, int on);
 int rtlsdr_set_opt_string(rtlsdr_dev_t *dev, const char *opts, int verbose);
 const char *rtlsdr_get_ver_id(void);

@@ -134,6 +134,28 @@ class RtlfmInputStat(C.Structure):
 # the same record as a numpy dtype (GpuDemod.input_stats / .input_stats_all return arrays of it)
 INPUT_STAT_DTYPE = [("pow_sum", "<u4"), ("pow_count", "<i4"), ("max", "<i4"), ("step", "<i4")]
 
+
+class RtlfmInputHealth(C.Structure):
+    """``rtlfm_input_health`` — overload / high-level / continuity counts of one raw buffer (include/rtlfm_hip.h)."""
+
+    _fields_ = [("overload", C.c_uint32), ("high", C.c_uint32), ("lost", C.c_uint32), ("first", C.c_uint8), ("last", C.c_uint8),
+                ("pad_", C.c_uint16)]
+
+
+# ... as a numpy dtype (GpuDemod.input_health / .input_health_all return arrays of it)
+INPUT_HEALTH_DTYPE = [("overload", "<u4"), ("high", "<u4"), ("lost", "<u4"), ("first", "u1"), ("last", "u1"), ("pad_", "<u2")]
+
+
+class RtlfmAgcEvent(C.Structure):
+    """``rtlfm_agc_event`` — one change of a stream's gain index (include/rtlfm_agc.h)."""
+
+    _fields_ = [("stream", C.c_int32), ("old_index", C.c_int32), ("new_index", C.c_int32), ("overloaded", C.c_int32),
+                ("buffer_serial", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 MONITOR_AUTO_GAIN = -100
 CRIT_IN, CRIT_OUT, CRIT_LT, CRIT_GT = range(4)
 CRIT_NAMES = ("in", "out", "<", ">")  # aCritStr, src/rtl_fm.c:116
@@ -252,6 +274,11 @@ _SIGNATURES = [
     ("rtlfm_gpu_input_stats", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_input_stats_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_input_stats_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    ("rtlfm_gpu_input_health", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_input_health_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_input_health_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    ("rtlfm_gpu_input_health_stats_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                      C.c_void_p]),
     ("rtlfm_gpu_state_get", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_state_set", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_reset", C.c_int, [C.c_void_p]),
@@ -351,6 +378,19 @@ _MONITOR_SIGNATURES = [
 ]
 DECLARED_MONITOR_SYMBOLS = [s[0] for s in _MONITOR_SIGNATURES]
 
+# ... and include/rtlfm_agc.h (input health: soft AGC, overload, continuity; host code inside the same library)
+_AGC_SIGNATURES = [
+    ("rtlfm_agc_create", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, _P(C.c_void_p)]),
+    ("rtlfm_agc_destroy", C.c_int, [C.c_void_p]),
+    ("rtlfm_agc_feed", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    ("rtlfm_agc_update", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_agc_poll", C.c_int, [C.c_void_p, _P(RtlfmAgcEvent), C.c_int, _P(C.c_int)]),
+    ("rtlfm_agc_state", C.c_int, [C.c_void_p, C.c_int, _P(C.c_int32), _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64)]),
+    ("rtlfm_agc_set_index", C.c_int, [C.c_void_p, C.c_int, C.c_int32]),
+    ("rtlfm_agc_set_settle", C.c_int, [C.c_void_p, C.c_int32]),
+]
+DECLARED_AGC_SYMBOLS = [s[0] for s in _AGC_SIGNATURES]
+
 DECLARED_SYMBOLS = [s[0] for s in _SIGNATURES]
 DECLARED_FM_SYMBOLS = [s[0] for s in _SIGNATURES if s[0].startswith("rtlfm_")]
 DECLARED_POWER_SYMBOLS = [s[0] for s in _POWER_SIGNATURES]
@@ -384,7 +424,7 @@ def load(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES:
+    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES:
         if path is not None and not hasattr(lib, name):
             continue  # an explicitly named other build (A/B against an earlier revision) may predate a symbol
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported

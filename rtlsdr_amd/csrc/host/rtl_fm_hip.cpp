@@ -29,6 +29,15 @@
 // of every source is still written (the reference's demod thread drops the buffer a cycle ends on, :1375-1380) and
 // the lines are not limited to FREQUENCIES_LIMIT.
 //
+// -O string (the reference's driver options, src/librtlsdr.c:3114-3200) goes to rtlsdr_set_opt_string() whole, as in the
+// reference; its parts agc=0|1|2 are also read here (anything else after agc= is refused before a device is opened).
+// agc=2 is the reference's SOFTWARE AGC (gain mode 2, softagc(), src/librtlsdr.c:3288-3327), run here for every source
+// at once: the library's option input_health is switched on, the records of every run's raw bytes (taken on the GPU)
+// are fed to the engine of include/rtlfm_agc.h with each buffer's own length, and after every run each source's last
+// index is applied to its device (rtlamd_file_set_gain_index).  settle = the buffers one run may take: they were
+// captured before a change could act.  -v prints every change and every flip of rtl_tcp's overload verdict
+// (detect_overload(), src/rtl_tcp.c:235-244); the final indices are printed at exit.
+//
 // Not restated (out of scope): frequency scanning / hopping - also through the command file's
 // lines: no retune, hence no mute / -B buffer dump and no DC-filter reset between cycles -, squelch-driven
 // retuning.  -l / -t hold the output back as demod_thread_fn does, -L prints full_demod()'s level lines.
@@ -52,6 +61,7 @@
 #include <vector>
 
 #include "../../../include/rtlfm_hip.h"
+#include "../../../include/rtlfm_agc.h"
 #include "../../../include/rtlfm_monitor.h"
 #include "../../../include/rtlsdr_file.h"
 #include "wavhdr.h"
@@ -85,6 +95,108 @@ struct Plumbing {
 	bool out_done = false;
 };
 
+// -O agc=2: the software AGC and the overload report for every source (include/rtlfm_agc.h)
+struct Health {
+	rtlfm_agc *agc = nullptr;
+	std::vector<rtlsdr_dev_t *> devs;
+	std::vector<std::vector<int>> gains;  // each source's gain table, tenths of a dB
+	std::vector<int> applied;             // the index each device has
+	std::vector<int> overloaded;          // detect_overload's verdict on each source's last buffer
+	std::vector<long long> serial;        // buffers of each source so far
+	std::vector<rtlfm_input_health> recs;
+	int verbosity = 0;
+};
+
+int health_create(Health *hl, const std::vector<rtlsdr_dev_t *> &devs, int settle, int verbosity)
+{
+	hl->devs = devs;
+	hl->verbosity = verbosity;
+	std::vector<int32_t> counts;
+	for (rtlsdr_dev_t *d : devs) {
+		const int n = rtlsdr_get_tuner_gains(d, nullptr);
+		std::vector<int> g((size_t)(n > 0 ? n : 1), 0);
+		if (n > 0) rtlsdr_get_tuner_gains(d, g.data());
+		counts.push_back((int32_t)g.size());
+		hl->gains.push_back(std::move(g));
+	}
+	hl->applied.assign(devs.size(), 0);  // mode 2 starts at index 0 (src/librtlsdr.c:1547)
+	hl->overloaded.assign(devs.size(), 0);
+	hl->serial.assign(devs.size(), 0);
+	int r = rtlfm_agc_create((int)devs.size(), counts.data(), nullptr, &hl->agc);
+	if (r == 0) r = rtlfm_agc_set_settle(hl->agc, settle);
+	return r;
+}
+
+// after a run: stream k of the handle is source live[k], whose buffers of this run were lens[k] bytes long
+int health_step(Health *hl, rtlfm_gpu *gpu, int cap, const std::vector<int> &live, const std::vector<std::vector<uint32_t>> &lens)
+{
+	hl->recs.resize(live.size() * (size_t)cap);
+	int n = 0;
+	int r = rtlfm_gpu_input_health_all(gpu, hl->recs.data(), cap, &n);
+	if (r < 0) return r;
+	for (size_t k = 0; k < live.size(); k++) {
+		const int i = live[k];
+		if ((int)lens[k].size() != n) return -EPROTO;
+		const rtlfm_input_health *rec = hl->recs.data() + k * (size_t)cap;
+		if ((r = rtlfm_agc_feed(hl->agc, i, rec, lens[k].data(), n)) < 0) return r;
+		for (int b = 0; b < n; b++) {
+			const int ov = 8000ll * rec[b].overload >= (long long)lens[k][(size_t)b] ? 1 : 0;  // src/rtl_tcp.c:243
+			if (ov != hl->overloaded[(size_t)i] && hl->verbosity)
+				fprintf(stderr, "stream %d: buffer %lld: overload %s\n", i, hl->serial[(size_t)i], ov ? "begins" : "ends");
+			hl->overloaded[(size_t)i] = ov;
+			hl->serial[(size_t)i]++;
+		}
+	}
+	rtlfm_agc_event ev[64];
+	for (;;) {
+		int ne = 0;
+		if ((r = rtlfm_agc_poll(hl->agc, ev, 64, &ne)) < 0) return r;
+		if (hl->verbosity)
+			for (int e = 0; e < ne; e++)
+				fprintf(stderr, "stream %d: buffer %lld: gain index %d -> %d, gain %d (%s)\n", ev[e].stream, (long long)ev[e].buffer_serial,
+				        ev[e].old_index, ev[e].new_index, hl->gains[(size_t)ev[e].stream][(size_t)ev[e].new_index],
+				        ev[e].overloaded ? "overload" : "low level");
+		if (ne < 64) break;
+	}
+	for (int i : live) {
+		int32_t idx = 0;
+		if ((r = rtlfm_agc_state(hl->agc, i, &idx, nullptr, nullptr, nullptr)) < 0) return r;
+		if (idx != hl->applied[(size_t)i]) {
+			rtlamd_file_set_gain_index(hl->devs[(size_t)i], idx);
+			hl->applied[(size_t)i] = idx;
+		}
+	}
+	return 0;
+}
+
+void health_report(Health *hl)
+{
+	for (size_t i = 0; i < hl->devs.size(); i++) {
+		int32_t idx = 0;
+		uint64_t total = 0, dropped = 0;
+		rtlfm_agc_state(hl->agc, (int)i, &idx, nullptr, &total, &dropped);
+		fprintf(stderr, "stream %zu: final gain index %d, gain %d\n", i, idx, hl->gains[i][(size_t)idx]);
+	}
+}
+
+// the parts agc=<n> of a -O string: the last one's value, -1 when there is none, -2 for anything but 0, 1, 2
+int opt_string_agc(const char *opts)
+{
+	int agc = -1;
+	const std::string t(opts);
+	for (size_t at = 0; at <= t.size();) {
+		size_t end = t.find(':', at);
+		if (end == std::string::npos) end = t.size();
+		const std::string part = t.substr(at, end - at);
+		if (part.compare(0, 4, "agc=") == 0) {
+			if (part.size() != 5 || part[4] < '0' || part[4] > '2') return -2;
+			agc = part[4] - '0';
+		}
+		at = end + 1;
+	}
+	return agc;
+}
+
 struct App {
 	rtlfm_cfg cfg;
 	rtlfm_gpu *gpu = nullptr;
@@ -101,6 +213,8 @@ struct App {
 	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
 	bool zero_copy = false;            // -Z: the device layer reads straight into the pinned staging ring
 	unsigned char *open_slot = nullptr;  // the slot the device layer is filling (rtlfm_gpu_acquire)
+	Health hl;                         // -O agc=2
+	std::deque<uint32_t> in_lens;      // ... the lengths of the buffers in the ring, oldest first (under p.m)
 };
 
 // -Z: where the device layer reads its next buffer to (rtlamd_file_set_buffer_source): a slot of the GPU
@@ -144,6 +258,7 @@ void on_buffer(unsigned char *buf, uint32_t len, void *ctx)
 		} else if (len) {
 			a->p.queued++;
 			a->blocks_in++;
+			if (a->hl.agc) a->in_lens.push_back(len);
 		}
 		a->p.cv_work.notify_all();
 		return;
@@ -168,6 +283,7 @@ void on_buffer(unsigned char *buf, uint32_t len, void *ctx)
 	}
 	a->p.queued++;
 	a->blocks_in++;
+	if (a->hl.agc) a->in_lens.push_back(len);
 	a->p.cv_work.notify_all();
 }
 
@@ -198,12 +314,17 @@ void demod_thread(App *a)
 		// The gate is held around the FLIP of the ring's halves only (rtlfm_gpu_run_begin): the transfer, a first run's
 		// allocations and the kernel launches (rtlfm_gpu_run_end) happen with the device thread already filling the other
 		// half - a callback never waits for a transfer or a kernel, as include/rtlfm_hip.h promises.
+		std::vector<std::vector<uint32_t>> run_lens;
 		int r = rtlfm_gpu_run_begin(a->gpu, &taken);
 		{
 			std::lock_guard<std::mutex> g(a->p.m);
 			a->p.want_run = false;
 			// the count goes down only for a run that has started: on -EAGAIN the buffers are still in the ring
 			if (r == 0) a->p.queued -= taken;
+			if (r == 0 && a->hl.agc) {
+				run_lens.assign(1, std::vector<uint32_t>(a->in_lens.begin(), a->in_lens.begin() + taken));
+				a->in_lens.erase(a->in_lens.begin(), a->in_lens.begin() + taken);
+			}
 			a->p.cv_room.notify_all();
 		}
 		if (r == -EAGAIN) { std::this_thread::yield(); continue; }
@@ -211,6 +332,7 @@ void demod_thread(App *a)
 		std::vector<int16_t> pcm((size_t)cap);
 		int n = 0;
 		if (r == 0) r = rtlfm_gpu_fetch(a->gpu, 0, pcm.data(), cap, &n);
+		if (r == 0 && a->hl.agc) r = health_step(&a->hl, a->gpu, a->cfg.max_blocks, {0}, run_lens);
 		if (r < 0) {
 			fprintf(stderr, "rtlfm_gpu_run/fetch: %s\n", rtlfm_gpu_strerror(r));
 			std::lock_guard<std::mutex> g(a->p.m);
@@ -335,6 +457,7 @@ struct Multi {
 	std::vector<rtlfm_monitor_rule> rules;
 	std::vector<pid_t> children;
 	uint64_t events = 0, fired = 0;
+	Health hl;  // -O agc=2
 };
 
 // with m->m held
@@ -396,6 +519,7 @@ int shrink(Multi *m, const std::vector<int> &live, const std::vector<int> &stay)
 		k++;
 	}
 	if (r == 0 && m->mon) r = rtlfm_gpu_set_option(nh, "input_stats", 1);
+	if (r == 0 && m->hl.agc) r = rtlfm_gpu_set_option(nh, "input_health", 1);
 	if (r < 0) {
 		rtlfm_gpu_destroy(nh);
 		return r;
@@ -588,6 +712,16 @@ void demod_thread_multi(Multi *m)
 			fail_multi(m, "rtlfm_gpu_push/run/fetch_all", r);
 			break;
 		}
+		if (m->hl.agc) {
+			std::vector<std::vector<uint32_t>> lens(ns);
+			for (size_t k = 0; k < ns; k++)
+				for (const std::vector<uint8_t> &buf : m->src[live[k]].taken) lens[k].push_back((uint32_t)buf.size());
+			if ((r = health_step(&m->hl, m->gpu, m->cfg.max_blocks, live, lens)) < 0) {
+				std::lock_guard<std::mutex> g(m->m);
+				fail_multi(m, "rtlfm_gpu_input_health_all / rtlfm_agc_feed", r);
+				break;
+			}
+		}
 		if (m->mon && (r = monitor_step(m, live)) < 0) {
 			std::lock_guard<std::mutex> g(m->m);
 			fail_multi(m, "rtlfm_monitor_update / feed", r);
@@ -654,7 +788,8 @@ void output_thread_multi(Multi *m)
 // everything after option parsing for n > 1 (main has refused what -N does not allow)
 int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<uint32_t> &freqs,
               const std::vector<uint32_t> &capture_freqs, uint32_t capture_rate, int gain, int ppm, const std::string &pattern,
-              bool write_wav, int verbosity, int conseq_squelch, int print_levels, const std::vector<rtlfm_monitor_rule> &rules)
+              bool write_wav, int verbosity, int conseq_squelch, int print_levels, const std::vector<rtlfm_monitor_rule> &rules,
+              const char *opt_string, int agc)
 {
 	Multi m;
 	m.rules = rules;
@@ -686,6 +821,8 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 		const int g_i = rules.empty() ? gain : rules[(size_t)i].gain;  // -C: each source's gain from its line
 		if (g_i == -100) rtlsdr_set_tuner_gain_mode(s.dev, 0);
 		else { rtlsdr_set_tuner_gain_mode(s.dev, 1); rtlsdr_set_tuner_gain(s.dev, g_i); }
+		if (opt_string) rtlsdr_set_opt_string(s.dev, opt_string, verbosity);
+		if (agc >= 0) rtlsdr_set_tuner_gain_mode(s.dev, agc);  // the string's agc=<tuner_gain_mode>, src/librtlsdr.c:3166-3171
 		rtlsdr_set_freq_correction_ppb(s.dev, ppm * 1000);
 		rtlsdr_set_offset_tuning(s.dev, c.offset_tuning);
 		rtlsdr_set_center_freq(s.dev, s.capture_freq);
@@ -704,6 +841,16 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 		if (r < 0) {
 			fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r));
 			ret = 2;
+		}
+		if (!ret && agc == 2) {
+			std::vector<rtlsdr_dev_t *> devs;
+			for (Source &s : m.src) devs.push_back(s.dev);
+			r = rtlfm_gpu_set_option(m.gpu, "input_health", 1);
+			if (r == 0) r = health_create(&m.hl, devs, c.max_blocks, verbosity);
+			if (r < 0) {
+				fprintf(stderr, "rtlfm_agc_create: %s\n", rtlfm_gpu_strerror(r));
+				ret = 2;
+			}
 		}
 		if (!ret && !rules.empty()) {
 			r = rtlfm_gpu_set_option(m.gpu, "input_stats", 1);
@@ -753,8 +900,10 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 					fprintf(stderr, "%u, %.1f, %.2f, %.1f\n", rules[(size_t)i].freq, st.min_level, st.sum_levels / st.count, st.max_level);
 			}
 		}
+		if (m.hl.agc) health_report(&m.hl);
 		if (m.failed) ret = 3;
 	}
+	if (m.hl.agc) rtlfm_agc_destroy(m.hl.agc);
 	for (pid_t pid : m.children) waitpid(pid, nullptr, 0);  // the triggered commands run in the background; none outlives the tool
 	if (m.mon) rtlfm_monitor_destroy(m.mon);
 	for (Source &s : m.src) {
@@ -793,6 +942,8 @@ void usage()
 	        "\t[-H write a wave header with the auxi chunk SDR programs read the frequency from]  [-v verbose]\n"
 	        "\t[-Z zero-copy: the device layer reads straight into the GPU layer's pinned staging ring]\n"
 	        "\t[-d device_index] [-g gain] [-p ppm]  accepted and passed to the device layer\n"
+	        "\t[-O driver options separated with ':', passed to the device layer; agc=0|1|2 is read here as well:\n"
+	        "\t       agc=2 = software AGC for every source from the GPU's records of the raw bytes; -v prints every change]\n"
 	        "\tfilename ('-' means stdout)\n");
 	exit(1);
 }
@@ -811,16 +962,25 @@ int main(int argc, char **argv)
 	int nstreams = 1;
 	bool have_freq = false, write_wav = false, wb_mode = false;
 	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
-	const char *cmd_file = nullptr;
+	const char *cmd_file = nullptr, *opt_string = nullptr;
+	int agc = -1;  // -O agc=<n>; -1: not given
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
-	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:")) != -1) {
+	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:")) != -1) {
 		switch (opt) {
 		case 'd': dev_index = atoi(optarg); break;
 		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
 		case 'N': nstreams = atoi(optarg); break;
 		case 'C': cmd_file = optarg; break;
+		case 'O':
+			opt_string = optarg;
+			agc = opt_string_agc(optarg);
+			if (agc == -2) {
+				fprintf(stderr, "-O %s: agc= takes 0 (hardware AGC), 1 (manual) or 2 (software AGC).\n", optarg);
+				return 1;
+			}
+			break;
 		case 'g': gain = (int)(atof(optarg) * 10); break;
 		case 'p': ppm = (int)atof(optarg); break;
 		case 'm': min_capture = (int)atofs(optarg); break;
@@ -957,7 +1117,7 @@ int main(int argc, char **argv)
 			}
 		}
 		return run_multi(planned, nstreams, dev_index, freqs, capture_freqs, capture_rate, gain, ppm, pattern, write_wav,
-		                 a.verbosity, conseq_squelch, a.print_levels, rules);
+		                 a.verbosity, conseq_squelch, a.print_levels, rules, opt_string, agc);
 	}
 
 	if (rtlsdr_get_device_count() == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE).\n"); return 1; }
@@ -967,6 +1127,8 @@ int main(int argc, char **argv)
 	rtlfm_optimal_settings(&c, freq, rate_in, min_capture, fifth, edge, &capture_freq, &capture_rate);
 	if (gain == -100) rtlsdr_set_tuner_gain_mode(a.dev, 0);
 	else { rtlsdr_set_tuner_gain_mode(a.dev, 1); rtlsdr_set_tuner_gain(a.dev, gain); }
+	if (opt_string) rtlsdr_set_opt_string(a.dev, opt_string, a.verbosity);
+	if (agc >= 0) rtlsdr_set_tuner_gain_mode(a.dev, agc);  // the string's agc=<tuner_gain_mode>, src/librtlsdr.c:3166-3171
 	rtlsdr_set_freq_correction_ppb(a.dev, ppm * 1000);
 	rtlsdr_set_offset_tuning(a.dev, c.offset_tuning);
 	rtlsdr_set_center_freq(a.dev, capture_freq);
@@ -980,6 +1142,11 @@ int main(int argc, char **argv)
 
 	int r = rtlfm_gpu_create(&c, 1, 0, &a.gpu);
 	if (r < 0) { fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r)); return 2; }
+	if (agc == 2) {
+		r = rtlfm_gpu_set_option(a.gpu, "input_health", 1);
+		if (r == 0) r = health_create(&a.hl, {a.dev}, c.max_blocks, a.verbosity);
+		if (r < 0) { fprintf(stderr, "rtlfm_agc_create: %s\n", rtlfm_gpu_strerror(r)); return 2; }
+	}
 	a.file = !strcmp(filename, "-") ? stdout : fopen(filename, "wb");
 	if (!a.file) { fprintf(stderr, "Failed to open %s\n", filename); return 1; }
 	if (write_wav && a.file != stdout)  // src/rtl_fm.c:1990-1995
@@ -997,6 +1164,10 @@ int main(int argc, char **argv)
 	}
 	fprintf(stderr, "%llu buffers in, %llu samples out, %llu buffers held back by the squelch%s\n", (unsigned long long)a.blocks_in,
 	        (unsigned long long)a.samples_out, (unsigned long long)a.blocks_squelched, a.p.failed ? " (FAILED)" : "");
+	if (a.hl.agc) {
+		health_report(&a.hl);
+		rtlfm_agc_destroy(a.hl.agc);
+	}
 	rtlfm_gpu_destroy(a.gpu);
 	rtlsdr_close(a.dev);
 	return a.p.failed ? 3 : 0;

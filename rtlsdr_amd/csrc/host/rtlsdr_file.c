@@ -34,6 +34,7 @@ struct rtlsdr_dev {
 	long data_start;
 	uint32_t freq, rate, bw;
 	int gain, ppb, agc, direct, offset, bias, gain_mode;
+	int gain_index;         /* rtlamd_file_set_gain_index: where a software AGC on the consumer's side has put the tuner */
 	volatile int async_running, cancel;
 	int loop;
 	rtlamd_file_buffer_source_t source;  /* zero-copy extension: where the next async buffer is read to */
@@ -235,7 +236,20 @@ int rtlsdr_set_and_get_tuner_bandwidth(rtlsdr_dev_t *d, uint32_t bw, uint32_t *a
 }
 
 int rtlsdr_set_tuner_bandwidth(rtlsdr_dev_t *d, uint32_t bw) { return rtlsdr_set_and_get_tuner_bandwidth(d, bw, NULL, 1); }
-int rtlsdr_set_tuner_gain_mode(rtlsdr_dev_t *d, int manual) { if (!d) return -1; d->gain_mode = manual; return tcp_command(d, 0x03, (uint32_t)manual); }
+
+/* Mode 2 is the reference's software AGC (src/librtlsdr.c:1545-1548: index 0, softagc() on).  Here the CONSUMER runs
+ * that AGC (include/rtlfm_agc.h) and drives the index through rtlamd_file_set_gain_index(), so an rtl_tcp server is
+ * NOT asked for mode 2 - its own soft AGC would fight the client's - but for mode 1, the only mode in which it honours
+ * index commands (src/rtl_tcp.c:472-476), once; the index starts at 0 as mode 2 sets it. */
+int rtlsdr_set_tuner_gain_mode(rtlsdr_dev_t *d, int manual)
+{
+	if (!d) return -1;
+	d->gain_mode = manual;
+	if (manual != 2) return tcp_command(d, 0x03, (uint32_t)manual);
+	d->gain_index = 0;
+	if (tcp_command(d, 0x03, 1u) != 0) return -1;
+	return tcp_command(d, 0x0d, 0u);
+}
 
 int rtlsdr_set_sample_rate(rtlsdr_dev_t *d, uint32_t rate)
 {
@@ -326,6 +340,21 @@ int rtlamd_file_set_buffer_source(rtlsdr_dev_t *d, rtlamd_file_buffer_source_t s
 	d->source_ctx = ctx;
 	return 0;
 }
+
+/*
+ * Extension (not one of the 26): the tuner's gain by index into rtlsdr_get_tuner_gains()'s table, what the reference's
+ * rtlsdr_set_tuner_gain_index() does for its own soft AGC (src/librtlsdr.c:1465-1485).  A file source records the
+ * index; an rtl_tcp source also sends SET_TUNER_GAIN_BY_INDEX (0x0d, src/rtl_tcp.c:472-476).
+ */
+int rtlamd_file_set_gain_index(rtlsdr_dev_t *d, int idx)
+{
+	if (!d) return -1;
+	if (idx < 0 || idx >= rtlsdr_get_tuner_gains(d, NULL)) return -22;
+	d->gain_index = idx;
+	return tcp_command(d, 0x0d, (uint32_t)idx);
+}
+
+int rtlamd_file_get_gain_index(rtlsdr_dev_t *d) { return d ? d->gain_index : -1; }
 
 int rtlsdr_cancel_async(rtlsdr_dev_t *d)
 {

@@ -27,6 +27,7 @@
 #include "fused_kernel.h"
 #include "boxcar_kernel.h"
 #include "input_stats_kernel.h"
+#include "input_health_kernel.h"
 
 using namespace rtlfm;
 
@@ -96,6 +97,8 @@ struct rtlfm_gpu {
 	int last_nblocks = 0;
 	rtlfm_input_stat *d_istats = nullptr;  // [nstreams*cap_blocks] ADC statistics of the raw bytes (option input_stats), allocated on first use
 	int stats_nblocks = 0;                 // buffers of the last run that have records ([stream][stats_nblocks])
+	rtlfm_input_health *d_ihealth = nullptr;  // the same for option input_health
+	int health_nblocks = 0;
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -134,6 +137,7 @@ struct rtlfm_gpu {
 		int verify_inject = 0; // tests: the shadow execution's first sample of stream 0 is overwritten before the comparison (it must be noticed)
 		int input_stats = 0;   // 1: k_input_stats in front of every run's front end (rtlfm_gpu_input_stats)
 		int input_stats_nt = 1; // its loads non-temporal (the A/B of LAB.md)
+		int input_health = 0;  // 1: k_input_health in front of every run's front end (rtlfm_gpu_input_health)
 		int verify_twice = 0;  // debug: every run_device runs twice - into a shadow output, then into the caller's - and the two are compared on the device
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
@@ -501,7 +505,7 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	void *ptrs[] = {h->d_arb_i, h->d_arb_frac, h->d_arb_tab, h->d_deemph_tab, h->d_deemph_inc, h->d_lpr_chunks, h->deepA, h->deepB, h->bufA, h->bufB, h->res[0][0], h->res[0][1], h->res_one_block ? nullptr : (void *)h->res[1][0], h->res[1][1],
 	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
-	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats};
+	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	h->fws.release();
@@ -621,6 +625,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"arb_span", &h->opt.arb_span}, {"arb_chunk", &h->opt.arb_chunk}, {"arb_waves", &h->opt.arb_waves}, {"lpr_threads", &h->opt.lpr_threads}, {"arb_serial", &h->opt.arb_serial}, {"lpr_ring", &h->opt.lpr_ring}, {"squelch_fused", &h->opt.squelch_fused}, {"adc_separate", &h->opt.adc_separate}, {"deep_rest", &h->opt.deep_rest}, {"box_store", &h->fws.box_store}, {"fused_store", &h->fws.fused_store},
 		{"verify_twice", &h->opt.verify_twice}, {"verify_inject", &h->opt.verify_inject}, {"lpr_slim", &h->opt.lpr_slim}, {"lpr_slim_chunk", &h->opt.lpr_slim_chunk}, {"lpr_slim_prio", &h->opt.lpr_slim_prio},
 		{"input_stats", &h->opt.input_stats}, {"input_stats_nt", &h->opt.input_stats_nt},
+		{"input_health", &h->opt.input_health},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -663,7 +668,8 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 	if ((!strcmp(name, "box_store") || !strcmp(name, "fused_store")) && (value < -1 || value > 1)) return -EINVAL;
 	// the chunk tables of the one-pass deemph + low_pass_real kernel are sized from it: keep it in a sane range
 	if ((!strcmp(name, "lpr_chunk") || !strcmp(name, "lpr_slim_chunk")) && (value < 256 || value > (1 << 20))) return -EINVAL;
-	if ((!strcmp(name, "input_stats") || !strcmp(name, "input_stats_nt")) && value != 0 && value != 1) return -EINVAL;
+	if ((!strcmp(name, "input_stats") || !strcmp(name, "input_stats_nt") || !strcmp(name, "input_health")) && value != 0 && value != 1)
+		return -EINVAL;
 	if (!strcmp(name, "arb_chunk") && value != 32 && value != 64) return -EINVAL;
 	if (!strcmp(name, "arb_waves") && (value < 0 || value > kSpecArbMaxWaves)) return -EINVAL;
 	if (!strcmp(name, "lpr_threads") && (value < 64 || value > kSpecLprThreads || value % 64)) return -EINVAL;
@@ -695,6 +701,7 @@ extern "C" int rtlfm_gpu_get_option(rtlfm_gpu *h, const char *name, long *value)
 	if (!strcmp(name, "placement_held_mb")) { *value = placement_held_mb(h); return 0; }
 	if (!strcmp(name, "verify_mismatches")) { *value = h->vt_mismatches; return 0; }  // verify_twice: runs whose two executions differed
 	if (!strcmp(name, "verify_runs")) { *value = h->vt_runs; return 0; }
+	if (!strcmp(name, "block_len")) { *value = (long)h->cfg.block_len; return 0; }  // what the handle was created with
 	// debugging (tests/test_soak_gpu.py): the host addresses of the runtime objects the handle owns - a hipStream_t / hipEvent_t
 	// IS the address of the runtime's object, which the runtime frees when the handle is destroyed
 	if (!strcmp(name, "dbg_own_stream")) { *value = (long)(uintptr_t)h->own_stream; return 0; }
@@ -1781,6 +1788,28 @@ static int ensure_input_stats(rtlfm_gpu *h)
 	return 0;
 }
 
+static int ensure_input_health(rtlfm_gpu *h)
+{
+	if (!h->d_ihealth)
+		HIP_TRY(hipMalloc(&h->d_ihealth, (size_t)h->nstreams * h->cap_blocks * sizeof(rtlfm_input_health)));
+	return 0;
+}
+
+// The raw-byte readers in front of a run's front end: with input_health on, k_input_health, which takes the statistics
+// along when input_stats is on as well (the input is read once); with input_stats alone, k_input_stats as ever.
+// Records of buffer j of stream s at [(s0 + s) * rec_stride + j0 + j].
+static int launch_input_readers(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, uint32_t len, int nblocks, int S,
+                                size_t rec_off, int rec_stride)
+{
+	const bool nt = h->opt.input_stats_nt != 0;
+	if (h->opt.input_health)
+		return ihealth::launch(d_iq, stream_stride, len, nblocks, S, h->d_ihealth + rec_off, rec_stride, nt, h->stream,
+		                       h->opt.input_stats ? h->d_istats + rec_off : nullptr);
+	if (h->opt.input_stats)
+		return istats::launch(d_iq, stream_stride, len, nblocks, S, h->d_istats + rec_off, rec_stride, nt, h->stream);
+	return 0;
+}
+
 // one execution of a run: everything rtlfm_gpu_run_device does except moving on to the next state copy / step
 static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
                            int16_t *d_out, size_t out_stride, int32_t *d_out_len)
@@ -1810,12 +1839,9 @@ static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	}
 	if (h->path == 2 && !can_fuse && !can_box && !can_box_emit && !can_deep) return -ENOTSUP;
 	// the callback's ADC statistics (src/rtl_fm.c:1302-1324) come before the conversion: in front of whichever front end runs
-	if (h->opt.input_stats) {
-		if ((r = ensure_input_stats(h)) < 0) return r;
-		if ((r = istats::launch(d_iq, stream_stride, h->cfg.block_len, nblocks, (int)S, h->d_istats, nblocks, h->opt.input_stats_nt != 0,
-		                        h->stream)) < 0)
-			return r;
-	}
+	if (h->opt.input_stats && (r = ensure_input_stats(h)) < 0) return r;
+	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
+	if ((r = launch_input_readers(h, d_iq, stream_stride, h->cfg.block_len, nblocks, (int)S, 0, nblocks)) < 0) return r;
 	// state is double-buffered: kernels read st[cur], write st[cur^1].  The staged kernels each
 	// update their own fields, so the record is copied first; the fused kernels copy it themselves.
 	if (!(h->path != 1 && (can_fuse || can_box || can_box_emit || can_deep)))
@@ -1939,6 +1965,7 @@ extern "C" int rtlfm_gpu_run_device(rtlfm_gpu *h, const uint8_t *d_iq, size_t st
 	h->step++;
 	h->last_nblocks = nblocks;
 	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
+	h->health_nblocks = h->opt.input_health ? nblocks : 0;
 	return 0;
 }
 
@@ -2011,6 +2038,64 @@ extern "C" int rtlfm_gpu_input_stats_device(int device, const uint8_t *d_iq, siz
 	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
 	HIP_TRY(hipSetDevice(device));
 	const int r = istats::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream);
+	if (r < 0) return r;
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// The last run's input health records (k_input_health, option input_health): the contract of rtlfm_gpu_input_stats.
+extern "C" int rtlfm_gpu_input_health(rtlfm_gpu *h, int stream, rtlfm_input_health *out, int cap, int *n)
+{
+	if (!h || !out || !n || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (!h->opt.input_health) return -ENODATA;
+	*n = h->health_nblocks;
+	if (h->health_nblocks > cap) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (h->health_nblocks > 0)
+		HIP_TRY(hipMemcpy(out, h->d_ihealth + (size_t)stream * h->health_nblocks, (size_t)h->health_nblocks * sizeof(rtlfm_input_health),
+		                  hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_input_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n)
+{
+	if (!h || !out || !n) return -EINVAL;
+	if (!h->opt.input_health) return -ENODATA;
+	*n = h->health_nblocks;
+	if (h->health_nblocks > cap) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (h->health_nblocks > 0)
+		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(rtlfm_input_health), h->d_ihealth, (size_t)h->health_nblocks * sizeof(rtlfm_input_health),
+		                    (size_t)h->health_nblocks * sizeof(rtlfm_input_health), (size_t)h->nstreams, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_input_health_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                             int nstreams, rtlfm_input_health *d_out, int nontemporal, void *hip_stream)
+{
+	if (!d_iq || !d_out || ((uintptr_t)d_out & 15)) return -EINVAL;
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
+	HIP_TRY(hipSetDevice(device));
+	const int r = ihealth::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream);
+	if (r < 0) return r;
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// ... and the launch a handle with both options on makes: both record arrays from one read of the input
+extern "C" int rtlfm_gpu_input_health_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                                   int nstreams, rtlfm_input_health *d_out, rtlfm_input_stat *d_stats, int nontemporal,
+                                                   void *hip_stream)
+{
+	if (!d_iq || !d_out || !d_stats || ((uintptr_t)d_out & 15) || ((uintptr_t)d_stats & 15)) return -EINVAL;
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
+	HIP_TRY(hipSetDevice(device));
+	const int r = ihealth::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream,
+	                              d_stats);
 	if (r < 0) return r;
 	HIP_TRY(hipGetLastError());
 	return 0;
@@ -2328,6 +2413,7 @@ static rtlfm_gpu make_view(rtlfm_gpu *h, int s0, int ns, uint32_t block_len)
 	v.timing = false;
 	v.no_deemph_scan = true;
 	v.opt.input_stats = 0;   // run_ragged takes the statistics itself, into the run's own rows
+	v.opt.input_health = 0;  // ... and the health records
 	v.opt.verify_twice = 0;  // views must not allocate (the shadow rows): ragged runs are not verified
 	v.ev_pending.clear(); v.ev_free.clear();
 	const size_t cb = (size_t)h->cap_blocks;
@@ -2360,6 +2446,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	if ((r = ensure_work_buffers(h)) < 0 || (r = ensure_res_buffers(h)) < 0 || (r = ensure_deep_buffers(h)) < 0) return r;
 	if (fused::ensure_dummy_tile(h->fws)) return -ENOMEM;
 	if (h->opt.input_stats && (r = ensure_input_stats(h)) < 0) return r;
+	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
 	if (!in->d_tmp) {
 		HIP_TRY(hipMalloc(&in->d_tmp, (size_t)S * in->ostride * sizeof(int16_t)));
 		HIP_TRY(hipMalloc(&in->d_tmp_len, (size_t)S * sizeof(int32_t)));
@@ -2386,9 +2473,8 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 			c.max_blocks = 1;
 			if ((r = validate_cfg(&c)) < 0) return r;
 			// each buffer's statistics over its own length, filed as [stream][nb] like a batched run's
-			if (h->opt.input_stats &&
-			    (r = istats::launch(in->d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, len, 1, s1 - s0,
-			                        h->d_istats + (size_t)s0 * nb + j, nb, h->opt.input_stats_nt != 0, h->stream)) < 0)
+			if ((r = launch_input_readers(h, in->d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, len, 1, s1 - s0,
+			                              (size_t)s0 * nb + j, nb)) < 0)
 				return r;
 			rtlfm_gpu v = make_view(h, s0, s1 - s0, len);
 			v.st_cur = cur;
@@ -2406,6 +2492,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 		                                          in->d_tmp_len, 0, S, (int)in->ostride);
 	}
 	h->stats_nblocks = h->opt.input_stats ? nb : 0;
+	h->health_nblocks = h->opt.input_health ? nb : 0;
 	HIP_TRY(hipGetLastError());
 	return 0;
 }

@@ -161,6 +161,23 @@ class GpuDemod:
         check(self.lib.rtlfm_gpu_input_stats_all(self._h, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_input_stats_all")
         return out[:, :n.value].copy()
 
+    def input_health(self, stream: int = 0) -> np.ndarray:
+        """The overload / high-level / continuity records (include/rtlfm_hip.h) of every buffer of the last run for
+        ``stream``: a record array with overload, high, lost, first, last.  Needs ``set_option("input_health", 1)``
+        before the run."""
+        out = np.zeros(max(1, self.cfg.max_blocks), dtype=capi.INPUT_HEALTH_DTYPE)
+        n = C.c_int()
+        check(self.lib.rtlfm_gpu_input_health(self._h, stream, out.ctypes.data, out.size, C.byref(n)), "rtlfm_gpu_input_health")
+        return out[:n.value].copy()
+
+    def input_health_all(self) -> np.ndarray:
+        """The same for every stream in one copy: records [nstreams, buffers of the last run]."""
+        cap = max(1, self.cfg.max_blocks)
+        out = np.zeros((self.nstreams, cap), dtype=capi.INPUT_HEALTH_DTYPE)
+        n = C.c_int()
+        check(self.lib.rtlfm_gpu_input_health_all(self._h, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_input_health_all")
+        return out[:, :n.value].copy()
+
     # -- state & plumbing ------------------------------------------------------
     def state_get(self, stream: int = 0) -> RtlfmStreamState:
         st = RtlfmStreamState()
