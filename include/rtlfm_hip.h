@@ -294,6 +294,41 @@ int rtlfm_gpu_input_health_stats_device(int device, const uint8_t *d_iq, size_t 
                                         int nstreams, rtlfm_input_health *d_out, rtlfm_input_stat *d_stats, int nontemporal,
                                         void *hip_stream);
 
+/*
+ * Scanning, the device side (csrc/scan_kernel.h; the host engine is include/rtlfm_scan.h).
+ *
+ * The squelch gate: the rule of the reference's demod thread (demod_thread_fn, src/rtl_fm.c:1366-1370) - while
+ * squelch_hits > conseq_squelch a buffer is not handed to the output thread and the counter is held at
+ * conseq_squelch + 1 - applied to every buffer of a run, for any max_blocks.  With the option "squelch_gate" on, one
+ * more kernel (k_scan_gate) runs at the end of every run, whatever path the run takes, ragged runs included: it walks
+ * the run's per-buffer rms() (what rtlfm_gpu_levels reads) from the carried squelch_hits, removes the held buffers'
+ * results from each stream's PCM row (the emitted ones move down, in order) and writes the CLAMPED counter to the state:
+ * rtlfm_gpu_fetch / _fetch_all / _fetch_all_prev and run_device's d_out_len then return exactly the bytes the reference
+ * fwrite()s, and rtlfm_gpu_state_get reads what the reference's d->squelch_hits reads.  A held buffer still passes
+ * through every filter (its state counts), as in the reference.
+ * One record per (stream, buffer) of the last run: rtlfm_gpu_gate / _gate_all, the contract of rtlfm_gpu_levels / _all
+ * (-ENODATA while the option is off, -ENOBUFS when cap is too small).
+ */
+typedef struct { int32_t hits_after; uint8_t emit; uint8_t pad[3]; } rtlfm_gate_rec;
+int rtlfm_gpu_gate(rtlfm_gpu *h, int stream, rtlfm_gate_rec *out, int cap, int *n);
+int rtlfm_gpu_gate_all(rtlfm_gpu *h, rtlfm_gate_rec *out, int cap, int *n);
+/*
+ * The hop mute (rtlsdr_callback, src/rtl_fm.c:1289-1296): the next nbytes that `stream` hands over through
+ * rtlfm_gpu_push / _acquire + _commit read as 127, across buffers and across runs (the handle keeps what is left per
+ * stream; calling again REPLACES the pending count, as `dongle.mute = ...` does).  Applied by the next run(s) to the
+ * handle's own device copy of the input behind the transfer (k_scan_mute: one launch, only in runs where a count is
+ * pending), in front of the input statistics / health readers and the front end, which see the muted bytes as the
+ * reference's callback does.  The caller's buffers and the pinned ring are not written.  Call it from the thread that
+ * runs the handle (rtlfm_gpu_run*), not from a producer.
+ * rtlfm_gpu_run_device takes const input and never mutes: -EBUSY while a count is pending.
+ */
+int rtlfm_gpu_mute(rtlfm_gpu *h, int stream, uint32_t nbytes);
+/* The same kernel on input that already lives on the device (the caller's own buffer, as rtlfm_gpu_rotate_90_u8): of
+ * every row s at d_iq + s * stream_stride (any alignment) the first min(mute_bytes[s], row_bytes) bytes become 127.
+ * mute_bytes is HOST memory.  Ordered on hip_stream (NULL = the default stream) and waits for it before it returns. */
+int rtlfm_gpu_mute_device(int device, uint8_t *d_iq, size_t stream_stride, int nstreams, size_t row_bytes,
+                          const uint32_t *mute_bytes, void *hip_stream);
+
 int rtlfm_gpu_state_get(rtlfm_gpu *h, int stream, rtlfm_stream_state *st);
 int rtlfm_gpu_state_set(rtlfm_gpu *h, int stream, const rtlfm_stream_state *st);
 /* demod_init() values for every stream. */
@@ -390,6 +425,10 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *   input_health         1: every run also takes the overload / high-level / continuity records of its raw input bytes
  *                        (rtlfm_gpu_input_health; k_input_health in front of the front end, which with input_stats on takes
  *                        the statistics in the same launch; default 0; anything but 0 / 1 -EINVAL); loads as input_stats_nt
+ *   squelch_gate         1: k_scan_gate at the end of every run (see rtlfm_gpu_gate; default 0: nothing is launched, nothing
+ *                        allocated; anything but 0 / 1 -EINVAL).  Needs cfg.squelch_level != 0 (-EINVAL); -ENOTSUP with a
+ *                        resampler (rate_out2 > 0), post_downsample > 1, or a buffer the fifth_order passes do not divide
+ *   conseq_squelch       the demod thread's limit (default 10, demod_init, src/rtl_fm.c:1613; < 0 -EINVAL)
  * Read-only (rtlfm_gpu_get_option):
  *   verify_runs         runs executed under verify_twice so far, and
  *   verify_mismatches    ... how many of them differed between their two executions

@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(CSRC, "librtlfm_hip.so")
-SOURCES = ["rtlfm_hip.hip", "rtlpower_hip.hip", "rtlfm_place.hip", "monitor.cpp", "agc.cpp"]
+SOURCES = ["rtlfm_hip.hip", "rtlpower_hip.hip", "rtlfm_place.hip", "monitor.cpp", "agc.cpp", "scan.cpp"]
 HEADERS = ["dsp_device.h", "staged_kernels.h", "fused_kernel.h",
            os.path.join("..", "..", "include", "rtlfm_hip.h")]
 ARCH = "gfx950"
@@ -27,10 +27,11 @@ OBJDIR = os.path.join(CSRC, "build")
 # which headers a translation unit sees (a header change recompiles only the units that include it)
 UNIT_HEADERS = {
     "rtlfm_hip.hip": ["debug_poison.h", "stream_pool.h", "dsp_device.h", "staged_kernels.h", "fused_kernel.h", "boxcar_kernel.h",
-                      "input_stats_kernel.h", "input_health_kernel.h", os.path.join("..", "..", "include", "rtlfm_hip.h")],
+                      "input_stats_kernel.h", "input_health_kernel.h", "scan_kernel.h", os.path.join("..", "..", "include", "rtlfm_hip.h")],
     "rtlfm_place.hip": ["debug_poison.h", "bw_probe_kernel.h", os.path.join("..", "..", "include", "rtlfm_hip.h")],
     "monitor.cpp": [os.path.join("..", "..", "include", "rtlfm_monitor.h"), os.path.join("..", "..", "include", "rtlfm_hip.h")],  # host only
     "agc.cpp": [os.path.join("..", "..", "include", "rtlfm_agc.h"), os.path.join("..", "..", "include", "rtlfm_hip.h")],  # host only
+    "scan.cpp": [os.path.join("..", "..", "include", "rtlfm_scan.h"), os.path.join("..", "..", "include", "rtlfm_hip.h")],  # host only
     "rtlpower_hip.hip": ["debug_poison.h", "stream_pool.h", "dsp_device.h", "power_kernels.h", "power_report_kernel.h", os.path.join("..", "..", "include", "rtlpower_hip.h"),
                          os.path.join("..", "..", "include", "rtlfm_hip.h")],
 }
@@ -76,6 +77,7 @@ def needs_build() -> bool:
     deps += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".cpp"))]
     deps.append(os.path.join(CSRC, "..", "..", "include", "rtlfm_monitor.h"))
     deps.append(os.path.join(CSRC, "..", "..", "include", "rtlfm_agc.h"))
+    deps.append(os.path.join(CSRC, "..", "..", "include", "rtlfm_scan.h"))
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
 
@@ -151,7 +153,7 @@ def build_host(force: bool = False, verbose: bool = False) -> tuple[str, str]:
         subprocess.check_call(cmd)
     cli_src = os.path.join(HOST, "rtl_fm_hip.cpp")
     if stale(CLI_OUT, [cli_src, SHIM_OUT, OUT, os.path.join(inc, "rtlfm_hip.h"), os.path.join(inc, "rtlfm_monitor.h"),
-                       os.path.join(inc, "rtlfm_agc.h"), os.path.join(inc, "rtlsdr_file.h")]):
+                       os.path.join(inc, "rtlfm_agc.h"), os.path.join(inc, "rtlfm_scan.h"), os.path.join(inc, "rtlsdr_file.h")]):
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", CLI_OUT, cli_src,
                "-L" + HOST, "-L" + CSRC, "-lrtlsdr_file", "-lrtlfm_hip", "-lpthread",
                "-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/..", "-Wl,-rpath,/opt/rocm/lib",

@@ -146,6 +146,26 @@ class RtlfmInputHealth(C.Structure):
 INPUT_HEALTH_DTYPE = [("overload", "<u4"), ("high", "<u4"), ("lost", "<u4"), ("first", "u1"), ("last", "u1"), ("pad_", "<u2")]
 
 
+class RtlfmGateRec(C.Structure):
+    """``rtlfm_gate_rec`` — what the squelch gate decided for one buffer (include/rtlfm_hip.h)."""
+
+    _fields_ = [("hits_after", C.c_int32), ("emit", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+# ... as a numpy dtype (GpuDemod.gate / .gate_all return arrays of it)
+GATE_REC_DTYPE = [("hits_after", "<i4"), ("emit", "u1"), ("pad", "u1", (3,))]
+
+
+class RtlfmScanEvent(C.Structure):
+    """``rtlfm_scan_event`` — one hop of a stream (include/rtlfm_scan.h)."""
+
+    _fields_ = [("stream", C.c_int32), ("from_index", C.c_int32), ("to_index", C.c_int32), ("freq", C.c_uint32),
+                ("pad_", C.c_uint32), ("buffer_serial", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad_"}
+
+
 class RtlfmAgcEvent(C.Structure):
     """``rtlfm_agc_event`` — one change of a stream's gain index (include/rtlfm_agc.h)."""
 
@@ -279,6 +299,10 @@ _SIGNATURES = [
     ("rtlfm_gpu_input_health_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     ("rtlfm_gpu_input_health_stats_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                       C.c_void_p]),
+    ("rtlfm_gpu_gate", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_gate_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_mute", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
+    ("rtlfm_gpu_mute_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("rtlfm_gpu_state_get", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_state_set", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_reset", C.c_int, [C.c_void_p]),
@@ -391,6 +415,21 @@ _AGC_SIGNATURES = [
 ]
 DECLARED_AGC_SYMBOLS = [s[0] for s in _AGC_SIGNATURES]
 
+# ... and include/rtlfm_scan.h (the scanner's hop engine; host code inside the same library)
+_SCAN_SIGNATURES = [
+    ("rtlfm_scan_create", C.c_int, [C.c_int, C.c_uint32, C.c_int32, _P(C.c_void_p)]),
+    ("rtlfm_scan_destroy", C.c_int, [C.c_void_p]),
+    ("rtlfm_scan_set_list", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    ("rtlfm_scan_parse_list", C.c_int, [C.c_char_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_scan_feed", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    ("rtlfm_scan_update", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_scan_events", C.c_int, [C.c_void_p, _P(RtlfmScanEvent), C.c_int, _P(C.c_int)]),
+    ("rtlfm_scan_apply", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_scan_take_hopped", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_scan_freq", C.c_int, [C.c_void_p, C.c_int, _P(C.c_uint32), _P(C.c_int32), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+]
+DECLARED_SCAN_SYMBOLS = [s[0] for s in _SCAN_SIGNATURES]
+
 DECLARED_SYMBOLS = [s[0] for s in _SIGNATURES]
 DECLARED_FM_SYMBOLS = [s[0] for s in _SIGNATURES if s[0].startswith("rtlfm_")]
 DECLARED_POWER_SYMBOLS = [s[0] for s in _POWER_SIGNATURES]
@@ -424,7 +463,7 @@ def load(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES:
+    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES:
         if path is not None and not hasattr(lib, name):
             continue  # an explicitly named other build (A/B against an earlier revision) may predate a symbol
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported

@@ -38,9 +38,21 @@
 // captured before a change could act.  -v prints every change and every flip of rtl_tcp's overload verdict
 // (detect_overload(), src/rtl_tcp.c:235-244); the final indices are printed at exit.
 //
-// Not restated (out of scope): frequency scanning / hopping - also through the command file's
-// lines: no retune, hence no mute / -B buffer dump and no DC-filter reset between cycles -, squelch-driven
-// retuning.  -l / -t hold the output back as demod_thread_fn does, -L prints full_demod()'s level lines.
+// -S file (not a reference letter) is the reference's scanning ("use multiple -f for scanning (requires squelch)",
+// controller_thread_fn, src/rtl_fm.c:1495-1507) for -N n sources (n = 1 without -N): line i of the file is source i's
+// frequency list (single frequencies and a:b:step ranges, rtlfm_scan_parse_list; blank lines and lines that start with
+// '#' are skipped).  -f keeps its meaning (where a source is tuned first; without -f that is its list's first entry).
+// The squelch gate runs on the device (option squelch_gate), after every run the gate's records go to the engine of
+// include/rtlfm_scan.h, a source whose run held a buffer hops to its list's next entry: rtlsdr_set_center_freq() with
+// the capture frequency optimal_settings() gives for it, and the first DEFAULT_BUFFER_DUMP = 4096 bytes of its next
+// buffer read 127 (rtlfm_gpu_mute).  At most one hop per source and run, settle = the buffers one run may take: the
+// output is a deterministic function of the input files.  -v prints every hop, the hop counts are printed at exit.
+//
+// -l / -t hold the output back as demod_thread_fn does (:1366-1370): on the device (squelch_gate / conseq_squelch) where
+// the configuration has a gate, else per stream through the carried state.  -L prints full_demod()'s level lines.
+//
+// Not restated (out of scope): the command file's own hop (its 2 x 3 200 000 byte mute, the DC-filter reset, -B), and
+// -t negative (terminate on squelch).
 #include <getopt.h>
 #include <pthread.h>
 #include <spawn.h>
@@ -63,6 +75,7 @@
 #include "../../../include/rtlfm_hip.h"
 #include "../../../include/rtlfm_agc.h"
 #include "../../../include/rtlfm_monitor.h"
+#include "../../../include/rtlfm_scan.h"
 #include "../../../include/rtlsdr_file.h"
 #include "wavhdr.h"
 
@@ -211,6 +224,7 @@ struct App {
 	double level_sum = 0.0;
 	uint32_t user_freq = 0;
 	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
+	bool use_gate = false;             // -l through the device's squelch gate (rtlfm_gpu_gate)
 	bool zero_copy = false;            // -Z: the device layer reads straight into the pinned staging ring
 	unsigned char *open_slot = nullptr;  // the slot the device layer is filling (rtlfm_gpu_acquire)
 	Health hl;                         // -O agc=2
@@ -364,7 +378,15 @@ void demod_thread(App *a)
 				}
 			}
 		}
-		if (a->cfg.squelch_level) {
+		if (a->use_gate) {
+			// the same rule, applied on the device: a held buffer comes back with no samples and its record says so
+			rtlfm_gate_rec g1;
+			int ng = 0;
+			if (rtlfm_gpu_gate(a->gpu, 0, &g1, 1, &ng) == 0 && ng == 1 && !g1.emit) {
+				a->blocks_squelched++;
+				continue;
+			}
+		} else if (a->cfg.squelch_level) {
 			// demod_thread_fn(), src/rtl_fm.c:1366-1370: while the squelch has been closed for more than
 			// conseq_squelch buffers nothing goes to the output thread, and the counter is held one above
 			// the limit ("hair trigger").  squelch_hits starts at 11 (:1615): silence until it first opens.
@@ -433,6 +455,7 @@ struct Source {
 	int print_level_no = 1, level_max = 0, level_max_max = 0;
 	double level_sum = 0.0;
 	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
+	uint32_t mute_owed = 0;                   // -S: bytes of the hop mute the handle still owes this source
 };
 
 struct RunOut {
@@ -458,7 +481,24 @@ struct Multi {
 	std::vector<pid_t> children;
 	uint64_t events = 0, fired = 0;
 	Health hl;  // -O agc=2
+	bool use_gate = false;  // -l through the device's squelch gate
+	// -S: the hop engine, list i = source i
+	rtlfm_scan *scan = nullptr;
+	std::vector<rtlfm_gate_rec> gate_recs;
+	bool wb_mode = false;
+	int rate_in = 0, min_capture = 0, fifth = 0, edge = 0;  // what optimal_settings() is asked with for a hop
 };
+
+// the options a handle of this tool runs with besides its configuration
+int handle_options(Multi *m, rtlfm_gpu *h)
+{
+	int r = 0;
+	if (m->mon) r = rtlfm_gpu_set_option(h, "input_stats", 1);
+	if (r == 0 && m->hl.agc) r = rtlfm_gpu_set_option(h, "input_health", 1);
+	if (r == 0 && m->use_gate) r = rtlfm_gpu_set_option(h, "conseq_squelch", m->conseq_squelch);
+	if (r == 0 && m->use_gate) r = rtlfm_gpu_set_option(h, "squelch_gate", 1);
+	return r;
+}
 
 // with m->m held
 void fail_multi(Multi *m, const char *what, int r)
@@ -518,8 +558,9 @@ int shrink(Multi *m, const std::vector<int> &live, const std::vector<int> &stay)
 		if (r == 0) r = rtlfm_gpu_state_set(nh, (int)k, &st);
 		k++;
 	}
-	if (r == 0 && m->mon) r = rtlfm_gpu_set_option(nh, "input_stats", 1);
-	if (r == 0 && m->hl.agc) r = rtlfm_gpu_set_option(nh, "input_health", 1);
+	if (r == 0) r = handle_options(m, nh);
+	for (size_t k = 0; k < stay.size() && r == 0; k++)  // a hop mute the old handle had not applied yet
+		if (m->src[(size_t)stay[k]].mute_owed) r = rtlfm_gpu_mute(nh, (int)k, m->src[(size_t)stay[k]].mute_owed);
 	if (r < 0) {
 		rtlfm_gpu_destroy(nh);
 		return r;
@@ -625,6 +666,56 @@ int monitor_step(Multi *m, const std::vector<int> &live)
 	}
 }
 
+// -l on the device, and -S: after a run, the gate's records of every stream in one copy - what was held is counted, and
+// with -S the records go to the hop engine: every hop retunes its source (controller_thread_fn, src/rtl_fm.c:1504-1507)
+// and leaves a mute for the source's next buffer.  Stream k of the handle is source live[k].
+int gate_step(Multi *m, const std::vector<int> &live)
+{
+	const int cap = m->cfg.max_blocks;
+	m->gate_recs.resize(live.size() * (size_t)cap);
+	int n = 0;
+	int r = rtlfm_gpu_gate_all(m->gpu, m->gate_recs.data(), cap, &n);
+	if (r < 0) return r;
+	for (size_t k = 0; k < live.size(); k++) {
+		Source &s = m->src[(size_t)live[k]];
+		uint64_t bytes = 0;
+		for (const std::vector<uint8_t> &buf : s.taken) bytes += buf.size();
+		s.mute_owed = bytes >= s.mute_owed ? 0 : (uint32_t)(s.mute_owed - bytes);  // this run's input was muted so far
+		for (int b = 0; b < n; b++)
+			if (!m->gate_recs[k * (size_t)cap + b].emit) s.blocks_squelched++;
+		if (m->scan && (r = rtlfm_scan_feed(m->scan, live[k], m->gate_recs.data() + k * (size_t)cap, n)) < 0) return r;
+	}
+	if (!m->scan) return 0;
+	rtlfm_scan_event ev[64];
+	for (;;) {
+		int ne = 0;
+		if ((r = rtlfm_scan_events(m->scan, ev, 64, &ne)) < 0) return r;
+		for (int e = 0; e < ne; e++) {
+			Source &s = m->src[(size_t)ev[e].stream];
+			const uint32_t f_new = ev[e].freq + (m->wb_mode ? 16000u : 0u);  // src/rtl_fm.c:1455-1460
+			rtlfm_cfg ci = m->cfg;
+			uint32_t cf = 0;
+			rtlfm_optimal_settings(&ci, f_new, m->rate_in, m->min_capture, m->fifth, m->edge, &cf, nullptr);
+			rtlsdr_set_center_freq(s.dev, cf);  // :1506
+			if (m->verbosity)
+				fprintf(stderr, "stream %d: hop %u -> %u at buffer %lld\n", ev[e].stream, s.user_freq, f_new, (long long)ev[e].buffer_serial);
+			s.user_freq = f_new;
+			s.capture_freq = cf;
+		}
+		if (ne < 64) break;
+	}
+	std::vector<int32_t> hopped(m->src.size());
+	int nh = 0;
+	if ((r = rtlfm_scan_take_hopped(m->scan, hopped.data(), (int)hopped.size(), &nh)) < 0) return r;
+	for (int i = 0; i < nh; i++) {
+		const size_t k = (size_t)(std::find(live.begin(), live.end(), (int)hopped[(size_t)i]) - live.begin());
+		if (k == live.size()) continue;
+		m->src[(size_t)hopped[(size_t)i]].mute_owed = RTLFM_SCAN_DEFAULT_DUMP;  // dongle.mute = DEFAULT_BUFFER_DUMP, :1507
+		if ((r = rtlfm_gpu_mute(m->gpu, (int)k, RTLFM_SCAN_DEFAULT_DUMP)) < 0) return r;
+	}
+	return 0;
+}
+
 void demod_thread_multi(Multi *m)
 {
 	const size_t stride = ((size_t)rtlfm_result_cap(&m->cfg) * m->cfg.max_blocks + 16 + 63) / 64 * 64;
@@ -727,13 +818,18 @@ void demod_thread_multi(Multi *m)
 			fail_multi(m, "rtlfm_monitor_update / feed", r);
 			break;
 		}
+		if (m->use_gate && (r = gate_step(m, live)) < 0) {
+			std::lock_guard<std::mutex> g(m->m);
+			fail_multi(m, "rtlfm_gpu_gate_all / rtlfm_scan_feed / rtlfm_gpu_mute", r);
+			break;
+		}
 		t_run += since(t0);
 		t0 = clk::now();
 		runs++;
 		for (size_t k = 0; k < ns; k++) {
 			Source &s = m->src[live[k]];
 			if (m->print_levels) levels_multi(m, s, (int)k);
-			if (m->cfg.squelch_level) {
+			if (m->cfg.squelch_level && !m->use_gate) {
 				// demod_thread's squelch rule (src/rtl_fm.c:1366-1370), per stream; max_blocks is 1 here
 				rtlfm_stream_state st;
 				if (rtlfm_gpu_state_get(m->gpu, (int)k, &st) == 0 && st.squelch_hits > m->conseq_squelch) {
@@ -789,9 +885,11 @@ void output_thread_multi(Multi *m)
 int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<uint32_t> &freqs,
               const std::vector<uint32_t> &capture_freqs, uint32_t capture_rate, int gain, int ppm, const std::string &pattern,
               bool write_wav, int verbosity, int conseq_squelch, int print_levels, const std::vector<rtlfm_monitor_rule> &rules,
-              const char *opt_string, int agc)
+              const char *opt_string, int agc, const std::vector<std::vector<uint32_t>> &scan_lists, bool wb_mode, int rate_in,
+              int min_capture, int fifth, int edge)
 {
 	Multi m;
+	m.wb_mode = wb_mode; m.rate_in = rate_in; m.min_capture = min_capture; m.fifth = fifth; m.edge = edge;
 	m.rules = rules;
 	m.cfg = planned;
 	rtlfm_cfg &c = m.cfg;
@@ -860,11 +958,30 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 				ret = 2;
 			}
 		}
+		if (!ret && c.squelch_level) {
+			// -l: demod_thread_fn's rule on the device where the configuration has a gate (not behind a resampler)
+			r = rtlfm_gpu_set_option(m.gpu, "conseq_squelch", conseq_squelch);
+			if (r == 0) r = rtlfm_gpu_set_option(m.gpu, "squelch_gate", 1);
+			m.use_gate = r == 0;
+			if (r < 0 && (r != -ENOTSUP || !scan_lists.empty())) {
+				fprintf(stderr, "squelch_gate: %s\n", rtlfm_gpu_strerror(r));
+				ret = 2;
+			}
+		}
+		if (!ret && !scan_lists.empty()) {
+			r = rtlfm_scan_create(n, RTLFM_SCAN_DEFAULT_DUMP, c.max_blocks, &m.scan);
+			for (int i = 0; i < n && r == 0; i++)
+				r = rtlfm_scan_set_list(m.scan, i, scan_lists[(size_t)i].data(), (int)scan_lists[(size_t)i].size());
+			if (r < 0) {
+				fprintf(stderr, "rtlfm_scan_create: %s\n", rtlfm_gpu_strerror(r));
+				ret = 2;
+			}
+		}
 	}
 	const size_t at = pattern.find("%d");
 	for (int i = 0; i < n && !ret; i++) {
 		Source &s = m.src[i];
-		const std::string name = pattern.substr(0, at) + std::to_string(i) + pattern.substr(at + 2);
+		const std::string name = at == std::string::npos ? pattern : pattern.substr(0, at) + std::to_string(i) + pattern.substr(at + 2);
 		s.file = fopen(name.c_str(), "wb");
 		if (!s.file) { fprintf(stderr, "Failed to open %s\n", name.c_str()); ret = 1; break; }
 		if (write_wav)
@@ -901,8 +1018,17 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 			}
 		}
 		if (m.hl.agc) health_report(&m.hl);
+		if (m.scan)
+			for (int i = 0; i < n; i++) {
+				uint32_t f = 0;
+				uint64_t hops = 0, held = 0;
+				rtlfm_scan_freq(m.scan, i, &f, nullptr, &hops, nullptr, &held);
+				fprintf(stderr, "stream %d: %llu hops, %llu buffers held, last on %u Hz\n", i, (unsigned long long)hops,
+				        (unsigned long long)held, f + (wb_mode ? 16000u : 0u));
+			}
 		if (m.failed) ret = 3;
 	}
+	if (m.scan) rtlfm_scan_destroy(m.scan);
 	if (m.hl.agc) rtlfm_agc_destroy(m.hl.agc);
 	for (pid_t pid : m.children) waitpid(pid, nullptr, 0);  // the triggered commands run in the background; none outlives the tool
 	if (m.mon) rtlfm_monitor_destroy(m.mon);
@@ -929,6 +1055,8 @@ void usage()
 	        "\t[-C command_file  with -N n: measurement line i of the file (freq, gain, in|out|lt|gt, level dB, tolerance dB,\n"
 	        "\t       #meas, #blocks, command, args) is watched by source i - the file must hold n such lines; adc / adcmax /\n"
 	        "\t       adcrms lines add the ADC statistics of the raw bytes; sets -M raw; -v prints every event]\n"
+	        "\t[-S scan_file  scanning: line i of the file is the frequency list of source i (-N n, or one source): frequencies\n"
+	        "\t       and a:b:step ranges; needs -l; a source whose squelch holds a buffer hops to its next frequency; not with -C]\n"
 	        "\t[-M modulation (default: fm)]  fm, wbfm, raw, am, usb, lsb\n"
 	        "\t[-s sample_rate (default: 24k)]  [-r resample_rate (default: none / same as -s)]\n"
 	        "\t[-m minimum_capture_rate Hz (default: 1m)]\n"
@@ -962,17 +1090,18 @@ int main(int argc, char **argv)
 	int nstreams = 1;
 	bool have_freq = false, write_wav = false, wb_mode = false;
 	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
-	const char *cmd_file = nullptr, *opt_string = nullptr;
+	const char *cmd_file = nullptr, *opt_string = nullptr, *scan_file = nullptr;
 	int agc = -1;  // -O agc=<n>; -1: not given
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
-	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:")) != -1) {
+	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:")) != -1) {
 		switch (opt) {
 		case 'd': dev_index = atoi(optarg); break;
 		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
 		case 'N': nstreams = atoi(optarg); break;
 		case 'C': cmd_file = optarg; break;
+		case 'S': scan_file = optarg; break;
 		case 'O':
 			opt_string = optarg;
 			agc = opt_string_agc(optarg);
@@ -1040,6 +1169,40 @@ int main(int argc, char **argv)
 		default: usage();
 		}
 	}
+	std::vector<std::vector<uint32_t>> scan_lists;
+	if (scan_file) {
+		// everything -S refuses is refused here, before a device is opened
+		if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
+		if (cmd_file) { fprintf(stderr, "-S (scan lists) and -C (command file) exclude each other.\n"); usage(); }
+		if (!c.squelch_level) { fprintf(stderr, "Please specify a squelch level.  Required for scanning multiple frequencies.\n"); return 1; }  // src/rtl_fm.c:1693
+		FILE *sf = fopen(scan_file, "r");
+		if (!sf) { fprintf(stderr, "-S %s: cannot open the scan file\n", scan_file); usage(); }
+		char line[65536];
+		int lineno = 0;
+		while (fgets(line, sizeof(line), sf)) {
+			lineno++;
+			const char *t = line;
+			while (*t == ' ' || *t == '\t') t++;
+			if (*t == '#' || *t == '\n' || *t == '\r' || !*t) continue;
+			int nf = 0;
+			int pr = rtlfm_scan_parse_list(t, nullptr, 0, &nf);
+			std::vector<uint32_t> fl((size_t)(nf > 0 ? nf : 0));
+			if (pr == -ENOBUFS) pr = rtlfm_scan_parse_list(t, fl.data(), nf, &nf);
+			if (pr < 0) { fclose(sf); fprintf(stderr, "-S %s: line %d is no frequency list\n", scan_file, lineno); usage(); }
+			scan_lists.push_back(std::move(fl));
+		}
+		fclose(sf);
+		if ((int)scan_lists.size() != nstreams) {
+			fprintf(stderr, "-S %s holds %zu lists, -N %d needs exactly %d: line i of the file is the list of source i.\n", scan_file,
+			        scan_lists.size(), nstreams, nstreams);
+			usage();
+		}
+		if (!have_freq) {  // a source starts on its list's first entry
+			for (const std::vector<uint32_t> &fl : scan_lists) freqs.push_back(fl[0]);
+			freq = freqs[0];
+			have_freq = true;
+		}
+	}
 	std::vector<rtlfm_monitor_rule> rules;
 	if (cmd_file) {
 		// src/rtl_fm.c:1738-1741: the command file implies -M raw; here its lines are the -N sources, in order
@@ -1075,7 +1238,7 @@ int main(int argc, char **argv)
 	const char *filename = optind < argc ? argv[optind] : "-";
 
 	if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
-	if (nstreams > 1 || cmd_file) {
+	if (nstreams > 1 || cmd_file || scan_file) {
 		// everything -N refuses is refused here, before a device is opened or a GPU handle created
 		const std::string pattern(filename);
 		const size_t at = pattern.find("%d");
@@ -1085,7 +1248,9 @@ int main(int argc, char **argv)
 			usage();
 		}
 		if (pattern == "-") { fprintf(stderr, "-N %d: no stdout; name the files, e.g. out_%%d.raw.\n", nstreams); usage(); }
-		if (at == std::string::npos || pattern.find("%d", at + 2) != std::string::npos) {
+		if (nstreams == 1 && scan_file && at == std::string::npos) {
+			// one source: the name as it is
+		} else if (at == std::string::npos || pattern.find("%d", at + 2) != std::string::npos) {
 			fprintf(stderr, "-N %d: the filename must hold exactly one %%d (the stream index), e.g. out_%%d.raw.\n", nstreams);
 			usage();
 		}
@@ -1117,7 +1282,8 @@ int main(int argc, char **argv)
 			}
 		}
 		return run_multi(planned, nstreams, dev_index, freqs, capture_freqs, capture_rate, gain, ppm, pattern, write_wav,
-		                 a.verbosity, conseq_squelch, a.print_levels, rules, opt_string, agc);
+		                 a.verbosity, conseq_squelch, a.print_levels, rules, opt_string, agc, scan_lists, wb_mode, rate_in, min_capture,
+		                 fifth, edge);
 	}
 
 	if (rtlsdr_get_device_count() == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE).\n"); return 1; }
@@ -1142,6 +1308,13 @@ int main(int argc, char **argv)
 
 	int r = rtlfm_gpu_create(&c, 1, 0, &a.gpu);
 	if (r < 0) { fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r)); return 2; }
+	if (c.squelch_level) {
+		// -l: demod_thread_fn's rule on the device where the configuration has a gate (not behind a resampler)
+		r = rtlfm_gpu_set_option(a.gpu, "conseq_squelch", conseq_squelch);
+		if (r == 0) r = rtlfm_gpu_set_option(a.gpu, "squelch_gate", 1);
+		a.use_gate = r == 0;
+		if (r < 0 && r != -ENOTSUP) { fprintf(stderr, "squelch_gate: %s\n", rtlfm_gpu_strerror(r)); return 2; }
+	}
 	if (agc == 2) {
 		r = rtlfm_gpu_set_option(a.gpu, "input_health", 1);
 		if (r == 0) r = health_create(&a.hl, {a.dev}, c.max_blocks, a.verbosity);

@@ -28,6 +28,7 @@
 #include "boxcar_kernel.h"
 #include "input_stats_kernel.h"
 #include "input_health_kernel.h"
+#include "scan_kernel.h"
 
 using namespace rtlfm;
 
@@ -99,6 +100,15 @@ struct rtlfm_gpu {
 	int stats_nblocks = 0;                 // buffers of the last run that have records ([stream][stats_nblocks])
 	rtlfm_input_health *d_ihealth = nullptr;  // the same for option input_health
 	int health_nblocks = 0;
+	// scanning (scan_kernel.h): the gate's records of the last run, allocated on first use, and the hop mute's counts
+	rtlfm_gate_rec *d_gate = nullptr;      // [nstreams*cap_blocks]
+	int gate_nblocks = 0;
+	size_t gate_rec_off = 0;               // stream-range views (ragged runs) write buffer j of the run: [stream][gate_rec_stride] + j
+	int gate_rec_stride = 0;               // 0: the run's own buffer count
+	uint32_t *mute_left = nullptr;         // host, [nstreams]: bytes rtlfm_gpu_mute still owes each stream; allocated by the first call
+	int mute_streams = 0;                  // streams with a count pending
+	scan::MuteEntry *d_mute_entries = nullptr;
+	size_t mute_entries_cap = 0;
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -138,6 +148,8 @@ struct rtlfm_gpu {
 		int input_stats = 0;   // 1: k_input_stats in front of every run's front end (rtlfm_gpu_input_stats)
 		int input_stats_nt = 1; // its loads non-temporal (the A/B of LAB.md)
 		int input_health = 0;  // 1: k_input_health in front of every run's front end (rtlfm_gpu_input_health)
+		int squelch_gate = 0;  // 1: k_scan_gate at the end of every run (rtlfm_gpu_gate)
+		int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
 		int verify_twice = 0;  // debug: every run_device runs twice - into a shadow output, then into the caller's - and the two are compared on the device
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
@@ -145,6 +157,7 @@ struct rtlfm_gpu {
 	size_t vt_out_cap = 0;        // int16 elements
 	int32_t *vt_len = nullptr, *vt_len2 = nullptr;
 	state_t *vt_state = nullptr;
+	rtlfm_gate_rec *vt_gate = nullptr;     // the first execution's gate records
 	unsigned long long *vt_cnt = nullptr;  // [4]: differing PCM dwords, differing lengths, differing state dwords, first differing (stream << 32 | index) + 1
 	long vt_mismatches = 0, vt_runs = 0;
 
@@ -505,9 +518,11 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	void *ptrs[] = {h->d_arb_i, h->d_arb_frac, h->d_arb_tab, h->d_deemph_tab, h->d_deemph_inc, h->d_lpr_chunks, h->deepA, h->deepB, h->bufA, h->bufB, h->res[0][0], h->res[0][1], h->res_one_block ? nullptr : (void *)h->res[1][0], h->res[1][1],
 	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
-	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth};
+	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth,
+	                h->d_gate, h->vt_gate, h->d_mute_entries};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
+	delete[] h->mute_left;
 	h->fws.release();
 	ingest_destroy(h);
 	// The streams go back to the process-wide pool, never to hipStreamDestroy (stream_pool.h: the runtime releases a freed
@@ -611,6 +626,17 @@ extern "C" int rtlfm_gpu_set_path(rtlfm_gpu *h, int path)
 }
 extern "C" int rtlfm_gpu_last_path(rtlfm_gpu *h) { return h ? h->last_path : -EINVAL; }
 
+// What the squelch gate (scan_kernel.h) needs of a configuration: a squelch, and a final PCM row in which buffer b owns the
+// samples dec_block_begin(b) .. dec_block_begin(b + 1) - no resampler, no low_pass_simple, no pass that is handed a length
+// it does not divide.  (-M raw returns in front of the audio tail: its rows are the decimated I, Q pairs whatever the rest says.)
+static int gate_supported(const rtlfm_cfg &c)
+{
+	if (!c.squelch_level) return -EINVAL;
+	if (c.mode != RTLFM_MODE_RAW && (c.rate_out2 > 0 || c.post_downsample > 1)) return -ENOTSUP;
+	if (c.downsample_passes > 0 && first_irregular_pass(c) < c.downsample_passes) return -ENOTSUP;
+	return 0;
+}
+
 // The one place the library's tunables and A/B switches live (no environment look-ups on the
 // launch path).  RTLFM_OPTIONS="name=value,..." is applied once, by rtlfm_gpu_create.
 static int *option_slot(rtlfm_gpu *h, const char *name)
@@ -626,6 +652,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"verify_twice", &h->opt.verify_twice}, {"verify_inject", &h->opt.verify_inject}, {"lpr_slim", &h->opt.lpr_slim}, {"lpr_slim_chunk", &h->opt.lpr_slim_chunk}, {"lpr_slim_prio", &h->opt.lpr_slim_prio},
 		{"input_stats", &h->opt.input_stats}, {"input_stats_nt", &h->opt.input_stats_nt},
 		{"input_health", &h->opt.input_health},
+		{"squelch_gate", &h->opt.squelch_gate}, {"conseq_squelch", &h->opt.conseq_squelch},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -670,6 +697,14 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 	if ((!strcmp(name, "lpr_chunk") || !strcmp(name, "lpr_slim_chunk")) && (value < 256 || value > (1 << 20))) return -EINVAL;
 	if ((!strcmp(name, "input_stats") || !strcmp(name, "input_stats_nt") || !strcmp(name, "input_health")) && value != 0 && value != 1)
 		return -EINVAL;
+	if (!strcmp(name, "squelch_gate")) {
+		if (value != 0 && value != 1) return -EINVAL;
+		if (value == 1) {
+			const int g = gate_supported(h->cfg);
+			if (g < 0) return g;
+		}
+	}
+	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
 	if (!strcmp(name, "arb_chunk") && value != 32 && value != 64) return -EINVAL;
 	if (!strcmp(name, "arb_waves") && (value < 0 || value > kSpecArbMaxWaves)) return -EINVAL;
 	if (!strcmp(name, "lpr_threads") && (value < 64 || value > kSpecLprThreads || value % 64)) return -EINVAL;
@@ -1810,6 +1845,42 @@ static int launch_input_readers(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream
 	return 0;
 }
 
+static int ensure_gate(rtlfm_gpu *h)
+{
+	if (!h->d_gate)
+		HIP_TRY(hipMalloc(&h->d_gate, (size_t)h->nstreams * h->cap_blocks * sizeof(rtlfm_gate_rec)));
+	return 0;
+}
+
+// The squelch gate, the last launch of a run (option squelch_gate): on the handle's stream, behind the audio tail wherever
+// that ran.  Reads this step's sin and the finished rows; writes the records, the clamped squelch_hits of sout and the
+// per-stream counts (d_cnt of this step and the caller's d_out_len).
+static int launch_gate(rtlfm_gpu *h, int nblocks, int16_t *d_out, size_t out_stride, int32_t *d_out_len)
+{
+	const rtlfm_cfg &c = h->cfg;
+	if (gate_supported(c) < 0) return -ENOTSUP;  // (a short buffer of a ragged run may be one the passes do not divide)
+	if (!h->d_gate) return -EFAULT;              // views do not allocate: rtlfm_gpu_run_device / run_ragged did
+	const int par = (int)(h->step & 1);
+	if (h->tail_pending[par]) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_tail[par], 0));  // this step's tail, on its own stream
+	scan::GateParams p{};
+	p.levels = h->d_levels;
+	p.sin = h->st[h->st_cur]; p.sout = h->st[(h->st_cur + 1) % 3];
+	p.R = d_out; p.rstride = out_stride;
+	p.recs = h->d_gate + h->gate_rec_off;
+	p.rec_stride = h->gate_rec_stride ? h->gate_rec_stride : nblocks;
+	p.cnt = h->d_cnt[par]; p.cnt2 = d_out_len;
+	p.nblocks = nblocks;
+	p.N = c.downsample_passes > 0 ? (int)((c.block_len / 2) >> c.downsample_passes) : (int)(c.block_len / 2);
+	p.D = c.downsample_passes > 0 ? 1 : c.downsample;
+	p.mul = c.mode == RTLFM_MODE_RAW ? 2 : 1;
+	p.level = c.squelch_level; p.conseq = h->opt.conseq_squelch;
+	std::pair<hipEvent_t, hipEvent_t> ev;
+	int r = timing_begin(h, ev);
+	if (r < 0) return r;
+	if ((r = scan::launch_gate(p, h->nstreams, h->stream)) < 0) return r;
+	return timing_end(h, ev);
+}
+
 // one execution of a run: everything rtlfm_gpu_run_device does except moving on to the next state copy / step
 static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
                            int16_t *d_out, size_t out_stride, int32_t *d_out_len)
@@ -1864,6 +1935,7 @@ static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		h->last_path = 1;
 	}
 	if (r < 0) return r;
+	if (h->opt.squelch_gate && (r = launch_gate(h, nblocks, d_out, out_stride, d_out_len)) < 0) return r;
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -1918,6 +1990,10 @@ static int run_device_verified(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 	// before it has run - the second execution, on a non-blocking stream, then overwrote the record while it was being copied,
 	// and the comparison reported state words that had never differed: one red run of the suite in round 6)
 	HIP_TRY(hipMemcpyAsync(h->vt_state, sout, S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
+	if (h->opt.squelch_gate) {
+		if (!h->vt_gate) HIP_TRY(hipMalloc(&h->vt_gate, S * h->cap_blocks * sizeof(rtlfm_gate_rec)));
+		HIP_TRY(hipMemcpyAsync(h->vt_gate, h->d_gate, S * nblocks * sizeof(rtlfm_gate_rec), hipMemcpyDeviceToDevice, h->stream));
+	}
 	HIP_TRY(hipStreamSynchronize(h->stream));
 	if (h->opt.verify_inject) {
 		// (tests: a difference the comparison must report - the shadow's first sample with every bit turned over)
@@ -1936,6 +2012,11 @@ static int run_device_verified(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 	const size_t nw = S * sizeof(state_t) / 4;
 	k_verify_words<<<(unsigned)((nw + 255) / 256), 256, 0, h->stream>>>(reinterpret_cast<const uint32_t *>(h->vt_state),
 	                                                                  reinterpret_cast<const uint32_t *>(sout), nw, h->vt_cnt);
+	if (h->opt.squelch_gate) {  // the gate's records count with the state words
+		const size_t gw = S * nblocks * sizeof(rtlfm_gate_rec) / 4;
+		k_verify_words<<<(unsigned)((gw + 255) / 256), 256, 0, h->stream>>>(reinterpret_cast<const uint32_t *>(h->vt_gate),
+		                                                                  reinterpret_cast<const uint32_t *>(h->d_gate), gw, h->vt_cnt);
+	}
 	unsigned long long got[4];
 	HIP_TRY(hipMemcpyAsync(got, h->vt_cnt, sizeof(got), hipMemcpyDeviceToHost, h->stream));
 	HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1950,14 +2031,29 @@ static int run_device_verified(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 	return 0;
 }
 
+static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
+                           int16_t *d_out, size_t out_stride, int32_t *d_out_len);
+
 extern "C" int rtlfm_gpu_run_device(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
                                     int16_t *d_out, size_t out_stride, int32_t *d_out_len)
+{
+	if (!h) return -EINVAL;
+	if (h->mute_streams > 0) return -EBUSY;  // the input is const here: a pending rtlfm_gpu_mute belongs to push / run
+	return run_device_impl(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
+}
+
+static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
+                           int16_t *d_out, size_t out_stride, int32_t *d_out_len)
 {
 	if (!h || !d_iq || !d_out || nblocks < 1) return -EINVAL;
 	if (nblocks > h->cap_blocks) return -E2BIG;
 	if (((uintptr_t)d_iq & 15) || (stream_stride & 15) || ((uintptr_t)d_out & 3) || (out_stride & 1)) return -EINVAL;
 	if (stream_stride < (size_t)nblocks * h->cfg.block_len) return -EINVAL;
 	HIP_TRY(hipSetDevice(h->device));
+	if (h->opt.squelch_gate && !h->gate_rec_stride) {  // (a view's records were allocated by run_ragged)
+		const int g = ensure_gate(h);
+		if (g < 0) return g;
+	}
 	const int r = h->opt.verify_twice ? run_device_verified(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
 	                                  : run_device_once(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
 	if (r < 0) return r;
@@ -1966,7 +2062,77 @@ extern "C" int rtlfm_gpu_run_device(rtlfm_gpu *h, const uint8_t *d_iq, size_t st
 	h->last_nblocks = nblocks;
 	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
 	h->health_nblocks = h->opt.input_health ? nblocks : 0;
+	h->gate_nblocks = h->opt.squelch_gate ? nblocks : 0;
 	return 0;
+}
+
+// The last run's gate records (k_scan_gate, option squelch_gate): the contract of rtlfm_gpu_levels.
+extern "C" int rtlfm_gpu_gate(rtlfm_gpu *h, int stream, rtlfm_gate_rec *out, int cap, int *n)
+{
+	if (!h || !out || !n || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (!h->opt.squelch_gate) return -ENODATA;
+	*n = h->gate_nblocks;
+	if (h->gate_nblocks > cap) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (h->gate_nblocks > 0)
+		HIP_TRY(hipMemcpy(out, h->d_gate + (size_t)stream * h->gate_nblocks, (size_t)h->gate_nblocks * sizeof(rtlfm_gate_rec),
+		                  hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_gate_all(rtlfm_gpu *h, rtlfm_gate_rec *out, int cap, int *n)
+{
+	if (!h || !out || !n) return -EINVAL;
+	if (!h->opt.squelch_gate) return -ENODATA;
+	*n = h->gate_nblocks;
+	if (h->gate_nblocks > cap) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (h->gate_nblocks > 0)
+		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(rtlfm_gate_rec), h->d_gate, (size_t)h->gate_nblocks * sizeof(rtlfm_gate_rec),
+		                    (size_t)h->gate_nblocks * sizeof(rtlfm_gate_rec), (size_t)h->nstreams, hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_mute(rtlfm_gpu *h, int stream, uint32_t nbytes)
+{
+	if (!h || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (!h->mute_left) {
+		if (!nbytes) return 0;
+		h->mute_left = new (std::nothrow) uint32_t[(size_t)h->nstreams]();
+		if (!h->mute_left) return -ENOMEM;
+	}
+	h->mute_streams += (nbytes ? 1 : 0) - (h->mute_left[stream] ? 1 : 0);
+	h->mute_left[stream] = nbytes;  // replaces what was pending, as `dongle.mute = ...`
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_mute_device(int device, uint8_t *d_iq, size_t stream_stride, int nstreams, size_t row_bytes,
+                                     const uint32_t *mute_bytes, void *hip_stream)
+{
+	if (!d_iq || !mute_bytes || nstreams < 1) return -EINVAL;
+	if (nstreams > 1 && stream_stride < row_bytes) return -EINVAL;
+	int ndev = 0;
+	if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return -ENODEV;
+	HIP_TRY(hipSetDevice(device));
+	std::vector<scan::MuteEntry> ent;
+	uint32_t mx = 0;
+	for (int s = 0; s < nstreams; s++) {
+		const uint32_t m = (size_t)mute_bytes[s] < row_bytes ? mute_bytes[s] : (uint32_t)row_bytes;
+		if (!m) continue;
+		ent.push_back({(unsigned long long)s * stream_stride, m, 0});
+		if (m > mx) mx = m;
+	}
+	if (ent.empty()) return 0;
+	hipStream_t q = (hipStream_t)hip_stream;
+	scan::MuteEntry *d_ent = nullptr;
+	HIP_TRY(hipMalloc(&d_ent, ent.size() * sizeof(scan::MuteEntry)));
+	hipError_t e = hipMemcpy(d_ent, ent.data(), ent.size() * sizeof(scan::MuteEntry), hipMemcpyHostToDevice);
+	int r = e == hipSuccess ? scan::launch_mute(d_iq, d_ent, (int)ent.size(), mx, q) : -EIO;
+	if (hipStreamSynchronize(q) != hipSuccess) r = -EIO;  // the entries are freed below
+	(void)hipFree(d_ent);
+	return r;
 }
 
 extern "C" int rtlfm_gpu_levels(rtlfm_gpu *h, int stream, int32_t *rms, int cap, int *n)
@@ -2414,6 +2580,7 @@ static rtlfm_gpu make_view(rtlfm_gpu *h, int s0, int ns, uint32_t block_len)
 	v.no_deemph_scan = true;
 	v.opt.input_stats = 0;   // run_ragged takes the statistics itself, into the run's own rows
 	v.opt.input_health = 0;  // ... and the health records
+	v.mute_streams = 0;      // rtlfm_gpu_run_end has applied the mute to the whole run's input
 	v.opt.verify_twice = 0;  // views must not allocate (the shadow rows): ragged runs are not verified
 	v.ev_pending.clear(); v.ev_free.clear();
 	const size_t cb = (size_t)h->cap_blocks;
@@ -2447,6 +2614,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	if (fused::ensure_dummy_tile(h->fws)) return -ENOMEM;
 	if (h->opt.input_stats && (r = ensure_input_stats(h)) < 0) return r;
 	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
+	if (h->opt.squelch_gate && (r = ensure_gate(h)) < 0) return r;
 	if (!in->d_tmp) {
 		HIP_TRY(hipMalloc(&in->d_tmp, (size_t)S * in->ostride * sizeof(int16_t)));
 		HIP_TRY(hipMalloc(&in->d_tmp_len, (size_t)S * sizeof(int32_t)));
@@ -2479,7 +2647,9 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 			rtlfm_gpu v = make_view(h, s0, s1 - s0, len);
 			v.st_cur = cur;
 			v.step = step;
-			r = rtlfm_gpu_run_device(&v, in->d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, 1,
+			v.gate_rec_off = (size_t)s0 * nb + j;  // the gate's records filed as [stream][nb] like a batched run's
+			v.gate_rec_stride = nb;
+			r = run_device_impl(&v, in->d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, 1,
 			                         in->d_tmp + (size_t)s0 * in->ostride, in->ostride, in->d_tmp_len + s0);
 			h->fws = v.fws;  // lazily created tap tables / probe buffers belong to the handle
 			h->last_path = v.last_path;
@@ -2493,8 +2663,50 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	}
 	h->stats_nblocks = h->opt.input_stats ? nb : 0;
 	h->health_nblocks = h->opt.input_health ? nb : 0;
+	h->gate_nblocks = h->opt.squelch_gate ? nb : 0;
 	HIP_TRY(hipGetLastError());
 	return 0;
+}
+
+// The hop mute (rtlfm_gpu_mute) on the run's device input, behind its transfer and in front of everything that reads it:
+// of every stream with a count pending the first bytes of its buffers, in order, each buffer over its own length, until
+// the count is used up or the run ends (what is left waits for the next run).  One launch.
+static int apply_mute(rtlfm_gpu *h, Ingest *in, int f, int nb)
+{
+	const size_t L = h->cfg.block_len;
+	std::vector<scan::MuteEntry> ent;
+	uint32_t mx = 0;
+	for (int s = 0; s < h->nstreams; s++) {
+		uint32_t left = h->mute_left[s];
+		if (!left) continue;
+		for (int j = 0; j < nb && left; j++) {
+			const size_t at = (size_t)s * h->cap_blocks + j;
+			const uint32_t len = in->h_len[f][at];
+			const uint32_t m = left < len ? left : len;
+			ent.push_back({(unsigned long long)(at * L), m, 0});
+			if (m > mx) mx = m;
+			left -= m;
+		}
+		h->mute_left[s] = left;
+		if (!left) h->mute_streams--;
+	}
+	if (ent.empty()) return 0;
+	if (h->mute_entries_cap < ent.size()) {
+		if (h->d_mute_entries) HIP_TRY(hipFree(h->d_mute_entries));
+		h->d_mute_entries = nullptr; h->mute_entries_cap = 0;
+		const size_t cap = (size_t)h->nstreams * h->cap_blocks;
+		HIP_TRY(hipMalloc(&h->d_mute_entries, cap * sizeof(scan::MuteEntry)));
+		h->mute_entries_cap = cap;
+	}
+	// (a blocking copy: the entries are on the device before the launch is queued, and an earlier run's launch that read
+	// the same array has been waited for by it)
+	HIP_TRY(hipStreamSynchronize(h->stream));
+	HIP_TRY(hipMemcpy(h->d_mute_entries, ent.data(), ent.size() * sizeof(scan::MuteEntry), hipMemcpyHostToDevice));
+	std::pair<hipEvent_t, hipEvent_t> ev;
+	int r = timing_begin(h, ev);
+	if (r < 0) return r;
+	if ((r = scan::launch_mute(in->d_in[f], h->d_mute_entries, (int)ent.size(), mx, h->stream)) < 0) return r;
+	return timing_end(h, ev);
 }
 
 // rtlfm_gpu_run() in two steps, for a caller that gates its producers around the flip only (host/rtl_fm_hip.cpp): _begin
@@ -2566,8 +2778,9 @@ extern "C" int rtlfm_gpu_run_end(rtlfm_gpu *h)
 	HIP_TRY(hipEventRecord(in->ev_h2d[f], in->copy_stream));
 	in->h2d_pending[f] = true;
 	HIP_TRY(hipStreamWaitEvent(h->stream, in->ev_h2d[f], 0));
+	if (h->mute_streams > 0 && (r = apply_mute(h, in, f, nb)) < 0) return r;
 	if (ragged) r = run_ragged(h, in, f, nb);
-	else r = rtlfm_gpu_run_device(h, in->d_in[f], stride, nb, in->d_result[f], in->ostride, in->d_result_len[f]);
+	else r = run_device_impl(h, in->d_in[f], stride, nb, in->d_result[f], in->ostride, in->d_result_len[f]);
 	if (r < 0) return r;
 	HIP_TRY(hipEventRecord(in->ev_run[f], h->stream));
 	in->run_pending[f] = true;
@@ -2810,8 +3023,10 @@ extern "C" const char *rtlfm_gpu_strerror(int err)
 	case -ENOMEM: return "out of device memory";
 	case -ENOSPC: return "max_blocks already queued for this stream";
 	case -EAGAIN: return "streams have unequal / zero queued blocks, or a producer still holds an acquired slot";
-	case -EBUSY: return "the stream's previous slot is still open (rtlfm_gpu_acquire without rtlfm_gpu_commit)";
-	case -ENOTSUP: return "configuration not supported on this path";
+	case -EBUSY: return "the stream's previous slot is still open (rtlfm_gpu_acquire without rtlfm_gpu_commit), or rtlfm_gpu_run_device while "
+	                    "a rtlfm_gpu_mute count is pending (it never writes its input)";
+	case -ENOTSUP: return "configuration not supported on this path; squelch_gate: not behind a resampler (rate_out2 > 0), "
+	                      "post_downsample > 1 or a buffer the fifth_order passes do not divide";
 	case -EDOM: return "outside the reference's own domain: a boxcar longer than the buffer (fm_demod reads lowpassed[-2]), low_pass_simple on a "
 	                   "count its step does not divide (src/rtl_fm.c:740), or rate_out2 > rate_out with low_pass_real (division by zero, :769)";
 	case -E2BIG: return "more blocks than cfg.max_blocks";

@@ -20,7 +20,7 @@ class GpuDemod:
     """``nstreams`` independent rtl_fm demodulators sharing one configuration."""
 
     def __init__(self, cfg: RtlfmCfg, nstreams: int = 1, device: int = 0, lib_path: str | None = None,
-                 options: dict | None = None):
+                 options: dict | None = None, squelch_gate: bool | None = None, conseq_squelch: int | None = None):
         self.lib = capi.load(lib_path)  # lib_path: another build of the library (A/B measurements)
         self.cfg = cfg
         self.nstreams = nstreams
@@ -30,6 +30,11 @@ class GpuDemod:
         self._h = h
         for k, v in (options or {}).items():
             self.set_option(k, v)
+        # the scanner's squelch gate (include/rtlfm_hip.h, rtlfm_gpu_gate): off unless asked for
+        if conseq_squelch is not None:
+            self.set_option("conseq_squelch", conseq_squelch)
+        if squelch_gate is not None:
+            self.set_option("squelch_gate", int(bool(squelch_gate)))
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -177,6 +182,23 @@ class GpuDemod:
         n = C.c_int()
         check(self.lib.rtlfm_gpu_input_health_all(self._h, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_input_health_all")
         return out[:, :n.value].copy()
+
+    def gate(self, stream: int | None = None) -> np.ndarray:
+        """The squelch gate's records of the last run (``set_option("squelch_gate", 1)`` before it): a record array with
+        hits_after and emit per buffer - of ``stream``, or [nstreams, buffers] for every stream in one copy."""
+        cap = max(1, self.cfg.max_blocks)
+        n = C.c_int()
+        if stream is None:
+            out = np.zeros((self.nstreams, cap), dtype=capi.GATE_REC_DTYPE)
+            check(self.lib.rtlfm_gpu_gate_all(self._h, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_gate_all")
+            return out[:, :n.value].copy()
+        out = np.zeros(cap, dtype=capi.GATE_REC_DTYPE)
+        check(self.lib.rtlfm_gpu_gate(self._h, stream, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_gate")
+        return out[:n.value].copy()
+
+    def mute(self, stream: int, nbytes: int):
+        """rtlfm_gpu_mute: the next ``nbytes`` that ``stream`` hands over read as 127 (the callback's mute after a retune)."""
+        check(self.lib.rtlfm_gpu_mute(self._h, stream, int(nbytes)), "rtlfm_gpu_mute")
 
     # -- state & plumbing ------------------------------------------------------
     def state_get(self, stream: int = 0) -> RtlfmStreamState:
