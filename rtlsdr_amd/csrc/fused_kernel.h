@@ -402,6 +402,54 @@ __device__ __forceinline__ void fifth_history_dpp(const uint32_t (&Y)[C], uint32
 	for (int k = 0; k < 5; k++) carry[k] = drop_newest_next ? t[k] : t[k + 1];
 }
 
+// The carry in a VGPR (RTLFM_DPP_VGPR_CARRY; whole-tile kernels: the tile's last lane is lane 63): two DPP moves per
+// dword and nothing else.  Receiving: wave_shr:1 without bound_ctrl leaves lane 0, which has no source lane, holding
+// `old` - so the carry IS the old operand and no select is needed.  Leaving: wave_ror:1 puts lane 63's value into
+// lane 0 of the next carry (only lane 0 of a carry means anything) - no v_readlane, no SGPR.  Every lane must be active
+// where these run.
+template <int W>
+__device__ __forceinline__ void hand_off_dppv(const uint32_t (&mine)[W], uint32_t (&prev)[W], const uint32_t (&carry)[W])
+{
+#pragma unroll
+	for (int k = 0; k < W; k++)
+		prev[k] = (uint32_t)__builtin_amdgcn_update_dpp((int)carry[k], (int)mine[k], 0x138, 0xf, 0xf, false);  // wave_shr:1
+}
+// (mov_dpp: every lane has a source lane, so there is no old value to keep and none is set up)
+template <int W>
+__device__ __forceinline__ void leave_carry_dppv(const uint32_t (&from)[W], uint32_t (&carry)[W])
+{
+#pragma unroll
+	for (int k = 0; k < W; k++)
+		carry[k] = (uint32_t)__builtin_amdgcn_mov_dpp((int)from[k], 0x13C, 0xf, 0xf, false);  // wave_ror:1
+}
+// (the carry is left by next_carry_dppv below, after h's last use: the old carry's registers are free by then)
+template <int C>
+__device__ __forceinline__ void fifth_history_dppv(const uint32_t (&Y)[C], uint32_t (&h)[5], const uint32_t (&carry)[5])
+{
+	const uint32_t mine[5] = {Y[C - 5], Y[C - 4], Y[C - 3], Y[C - 2], Y[C - 1]};
+	hand_off_dppv<5>(mine, h, carry);
+}
+// what the next tile's lane 0 sees: the last lane's newest five, or (the next tile starts a buffer) the five before
+// the newest.  drop_newest_next is wave-uniform: a scalar branch, not both forms and a select.
+// u0..u2: the three outputs of the pass that h went into.  The received values sit in the old carry's registers (the
+// shift's tied old operand); a carry left while they are still live lands in other registers and is copied at the loop's
+// back edge - and the compiler does sink the pass's arithmetic below this branch.  The empty statement makes the branch
+// wait for u0..u2, that is for h's last use, and the new carry takes the old one's registers.
+template <int C>
+__device__ __forceinline__ void next_carry_dppv(const uint32_t (&Y)[C], uint32_t (&carry)[5], bool drop_newest_next,
+                                                uint32_t u0, uint32_t u1, uint32_t u2)
+{
+	int drop = __builtin_amdgcn_readfirstlane((int)drop_newest_next);  // (the compiler does not see that it is uniform)
+	asm volatile("" : "+s"(drop) : "v"(u0), "v"(u1), "v"(u2));
+	if (drop) {
+		const uint32_t from[5] = {Y[C - 6], Y[C - 5], Y[C - 4], Y[C - 3], Y[C - 2]};
+		leave_carry_dppv<5>(from, carry);
+	} else {
+		const uint32_t from[5] = {Y[C - 5], Y[C - 4], Y[C - 3], Y[C - 2], Y[C - 1]};
+		leave_carry_dppv<5>(from, carry);
+	}
+}
+
 // linear ring: this tile's C values per lane go into the transient body, every lane reads the H entries
 // before its first - from the body, or, for positions before the tile, from the ring's prefix (the last
 // kPre entries of the previous tile) - and then the lanes that hold the tile's last kPre entries leave
@@ -526,6 +574,19 @@ struct AtanNodesLds {
 #ifndef RTLFM_DPP_EXCHANGE
 #define RTLFM_DPP_EXCHANGE 1  // lane-to-lane hand-offs of the first passes and the discriminator through DPP + SGPR carries instead of LDS
 #endif
+#ifndef RTLFM_DPP_VGPR_CARRY
+#define RTLFM_DPP_VGPR_CARRY 1  // ... and the carries in VGPRs, left by a second DPP move (wave_ror:1), where dpp_vgpr_carry() says so
+#endif
+// Which instantiations keep the hand-offs' carries in VGPRs (hand_off_dppv): the whole-tile kernels - a partial tile's
+// last lane is not lane 63 - that stay within 128 VGPRs (four waves per SIMD) and without scratch with the 16 registers
+// the carries take.  The run-time-discriminator kernels with the FIR on the MFMA engine sit at 128 VGPRs as they are, and
+// five of the eight spill with the carries on top.  The others keep the SGPR form and compile to what they were
+// (tools/handoff_isa.py --diff; LAB.md I.36 has the table).
+template <int P, bool FIR9, bool STD, bool MFMA0, bool RDC, bool PT>
+constexpr bool dpp_vgpr_carry()
+{
+	return RTLFM_DPP_EXCHANGE && RTLFM_DPP_VGPR_CARRY && P >= 3 && !PT && !(FIR9 && !STD && MFMA0);
+}
 #ifndef RTLFM_FUSED_WAVES_PER_SIMD
 #define RTLFM_FUSED_WAVES_PER_SIMD 4
 #endif
@@ -665,8 +726,19 @@ __global__ void __launch_bounds__(64, (P == 1 ? 2 : P == 2 ? 3 : RTLFM_FUSED_WAV
 	// carries in SGPRs the allocator of four of their RDC variants copied prefetched registers in front of the back-edge -
 	// a wait on the tile loads, tools/check_prefetch.py; their exchanges are a small share of the tile anyway)
 	constexpr bool DPPX = RTLFM_DPP_EXCHANGE && P >= 3;
+	// ... or, where dpp_vgpr_carry() says so, in VGPRs of which only lane 0 means anything (every lane reads the one
+	// LDS word: a broadcast)
+	constexpr bool DPPV = dpp_vgpr_carry<P, FIR9, STD, MFMA0, RDC, PT>();
 	uint32_t cy0[5] = {0, 0, 0, 0, 0}, cy1[5] = {0, 0, 0, 0, 0}, cy2[5] = {0, 0, 0, 0, 0}, czd[1] = {0};
-	if constexpr (DPPX) {
+	if constexpr (DPPV) {
+#pragma unroll
+		for (int k = 0; k < 5; k++) {
+			cy0[k] = lds[L::c_y0 + k];
+			cy1[k] = lds[L::c_y1 + k];
+			if (P >= 4) cy2[k] = lds[L::c_y2 + k];
+		}
+		czd[0] = lds[L::c_zd];
+	} else if constexpr (DPPX) {
 #pragma unroll
 		for (int k = 0; k < 5; k++) {
 			if (P >= 2) cy0[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds[L::c_y0 + k]);
@@ -1076,9 +1148,11 @@ __global__ void __launch_bounds__(64, (P == 1 ? 2 : P == 2 ? 3 : RTLFM_FUSED_WAV
 		} else {
 			uint32_t h5[5];
 			uint32_t Y1[16];
-			if constexpr (DPPX) fifth_history_dpp<32>(Y0, h5, cy0, lz, next_bs, last_lane);
+			if constexpr (DPPV) fifth_history_dppv<32>(Y0, h5, cy0);
+			else if constexpr (DPPX) fifth_history_dpp<32>(Y0, h5, cy0, lz, next_bs, last_lane);
 			else fifth_history<32>(lds + L::tr, lds + L::c_y0, Y0, h5, lz, next_bs, last_lane);
 			fifth_lane<32, true>(Y0, h5, Y1);
+			if constexpr (DPPV) next_carry_dppv<32>(Y0, cy0, next_bs, Y1[0], Y1[1], Y1[2]);
 			archive_regs(Y0, std::integral_constant<int, 32>(), 1);
 			if (MFMA0 && RTLFM_MFMA_RELOAD_AT == 2) reload(gt, more);
 			if constexpr (P == 2) {
@@ -1086,21 +1160,25 @@ __global__ void __launch_bounds__(64, (P == 1 ? 2 : P == 2 ? 3 : RTLFM_FUSED_WAV
 				for (int k = 0; k < 16; k++) Z[k] = Y1[k];
 			} else {
 				uint32_t Y2[8];
-				if constexpr (DPPX) fifth_history_dpp<16>(Y1, h5, cy1, lz, next_bs, last_lane);
+				if constexpr (DPPV) fifth_history_dppv<16>(Y1, h5, cy1);
+				else if constexpr (DPPX) fifth_history_dpp<16>(Y1, h5, cy1, lz, next_bs, last_lane);
 				else fifth_history<16>(lds + L::tr, lds + L::c_y1, Y1, h5, lz, next_bs, last_lane);
 				fifth_lane<16, true>(Y1, h5, Y2);
+				if constexpr (DPPV) next_carry_dppv<16>(Y1, cy1, next_bs, Y2[0], Y2[1], Y2[2]);
 				archive_regs(Y1, std::integral_constant<int, 16>(), 2);
 				if constexpr (P == 3) {
 #pragma unroll
 					for (int k = 0; k < 8; k++) Z[k] = Y2[k];
 				} else {
 					uint32_t Y3[4];
-					if constexpr (DPPX) fifth_history_dpp<8>(Y2, h5, cy2, lz, next_bs, last_lane);
+					if constexpr (DPPV) fifth_history_dppv<8>(Y2, h5, cy2);
+					else if constexpr (DPPX) fifth_history_dpp<8>(Y2, h5, cy2, lz, next_bs, last_lane);
 					else fifth_history<8>(lds + L::tr, lds + L::c_y2, Y2, h5, lz, next_bs, last_lane);
 					// with rotation |x| <= 1023 here, so the 16-bit form cannot overflow;
 					// without it an all-255 input reaches exactly 2^15
 					if (rotate && !RDC) fifth_lane<8, true>(Y2, h5, Y3);
 					else fifth_lane<8, false>(Y2, h5, Y3);
+					if constexpr (DPPV) next_carry_dppv<8>(Y2, cy2, next_bs, Y3[0], Y3[1], Y3[2]);
 					archive_regs(Y2, std::integral_constant<int, 8>(), 3);
 					if constexpr (P == 4) {
 #pragma unroll
@@ -1208,7 +1286,9 @@ __global__ void __launch_bounds__(64, (P == 1 ? 2 : P == 2 ? 3 : RTLFM_FUSED_WAV
 		uint32_t pv;
 		{
 			uint32_t mine[1] = {V[CZ - 1]}, prev[1];
-			if constexpr (DPPX) {
+			if constexpr (DPPV) {
+				hand_off_dppv<1>(mine, prev, czd);  // (its carry is left behind the discriminator, where pv is dead)
+			} else if constexpr (DPPX) {
 				hand_off_dpp<1>(mine, prev, czd, lz);
 				czd[0] = (uint32_t)__builtin_amdgcn_readlane((int)mine[0], last_lane);
 			} else {
@@ -1248,6 +1328,10 @@ __global__ void __launch_bounds__(64, (P == 1 ? 2 : P == 2 ? 3 : RTLFM_FUSED_WAV
 			pcm[n] = (int16_t)v;
 		}
 		(void)q0;
+		if constexpr (DPPV) {
+			const uint32_t mine[1] = {V[CZ - 1]};
+			leave_carry_dppv<1>(mine, czd);
+		}
 		RTLFM_MARK("demod_done");
 		FUSED_PHASE(3);
 		if (emit && (!PT || lane < nlanes)) {
