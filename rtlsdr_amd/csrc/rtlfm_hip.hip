@@ -14,6 +14,7 @@
 #include <cstring>
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <shared_mutex>
@@ -1319,11 +1320,62 @@ static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_s
 	return 0;
 }
 
+// -M raw: two int16 per decimated sample - of the counts the front end left (`cnt`), or of T everywhere
+static int raw_out_len(rtlfm_gpu *h, int32_t *d_out_len, const int32_t *cnt, int T)
+{
+	const int S = h->nstreams;
+	hipStream_t q = h->stream;
+	if (!d_out_len) return 0;
+	if (cnt) {
+		HIP_TRY(hipMemcpyAsync(d_out_len, cnt, S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
+		k_scale_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2, 1);
+	} else {
+		k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * T);
+	}
+	return 0;
+}
+
+// The back half of full_demod() behind every decimator that leaves IQ (run_staged, and the emit modes of both front
+// ends): the power squelch (src/rtl_fm.c:1204-1215) and -L levels, mode_demod incl. -M raw (:1256-1259), the audio tail.
+// `cur`: the decimated IQ, T samples per stream - or, with `cnt`, the per-stream counts of a boxcar that does not divide
+// the buffer (T is then their upper bound); buffer extents as run_tail's (Nblk, D).
+// d_iq / iq_bytes: run_staged, which has not allocated the tail's work buffers in front of its launches as the front ends do.
+static int run_back_half(rtlfm_gpu *h, uint32_t *cur, size_t xstride, int T, int Nblk, int D, int nblocks, const int32_t *cnt,
+                         const TailPlan &tp, int16_t *d_out, size_t out_stride, int32_t *d_out_len, const uint8_t *d_iq = nullptr,
+                         size_t iq_bytes = 0)
+{
+	const rtlfm_cfg &c = h->cfg;
+	const int S = h->nstreams;
+	hipStream_t q = h->stream;
+	const state_t *sin = h->st[h->st_cur];
+	state_t *sout = h->st[(h->st_cur + 1) % 3];
+	if (c.squelch_level || c.report_levels)
+		k_squelch_rms<<<S * nblocks, 256, 0, q>>>(cur, xstride, Nblk, D, nblocks, sin, c.squelch_level,
+		                                         c.dc_block_raw, h->d_mute, h->d_levels);
+	if (c.squelch_level) {
+		k_squelch_hits<<<grid_for(S, 64), 64, 0, q>>>(h->d_mute, nblocks, S, sin, sout);
+		k_squelch_zero<<<S * nblocks, 256, 0, q>>>(cur, xstride, Nblk, D, nblocks, S, T, sin,
+		                                                     h->d_mute);
+	}
+	if (d_iq && tp.any()) {
+		const int r = ensure_res_buffers(h, d_iq, iq_bytes);
+		if (r < 0) return r;
+	}
+	int16_t *dd; size_t dds;
+	tail_route(h, tp, d_out, out_stride, &dd, &dds);
+	if (c.mode == RTLFM_MODE_FM)
+		k_fm_demod<<<S * nblocks, 256, 0, q>>>(cur, xstride, dd, dds, T, S, Nblk, D, nblocks,
+		                                         c.custom_atan, h->d_lut, cnt, sin, sout);
+	else
+		k_simple_demod<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, xstride, dd, dds, T, S, c.mode,
+		                                                     c.output_scale, cnt);
+	if (c.mode == RTLFM_MODE_RAW) return raw_out_len(h, d_out_len, cnt, T);
+	return run_tail(h, tp, dd, dds, T, cnt != nullptr, nblocks, Nblk, D, d_out, out_stride, d_out_len);
+}
+
 // Passes first .. passes - 1 where `first` is handed a length that is not a multiple of four elements, and everything
 // up to mode_demod() behind them (staged_kernels.h, k_fifth_irregular); then the ordinary audio tail.  `cur` holds the
 // level in front of pass `first` (n_in samples per buffer, buffers back to back).
-static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_stride, int T, bool varcnt,
-                    int nblocks, int Nblk, int D, int16_t *final_dst, size_t final_stride, int32_t *d_out_len);
 static int run_irregular_rest(rtlfm_gpu *h, const uint32_t *cur, size_t xstride, int first, int nblocks, int16_t *d_out,
                               size_t out_stride, int32_t *d_out_len, const uint8_t *d_iq, size_t iq_bytes)
 {
@@ -1426,42 +1478,8 @@ static int run_staged(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, i
 	}
 	r = timing_end(h, ev);
 	if (r < 0) return r;
-	// --- power squelch (src/rtl_fm.c:1204-1215)
-	if (c.squelch_level || c.report_levels)
-		k_squelch_rms<<<S * nblocks, 256, 0, q>>>(cur, h->xstride, Nblk, D, nblocks, sin, c.squelch_level,
-		                                         c.dc_block_raw, h->d_mute, h->d_levels);
-	if (c.squelch_level) {
-		k_squelch_hits<<<grid_for(S, 64), 64, 0, q>>>(h->d_mute, nblocks, S, sin, sout);
-		k_squelch_zero<<<S * nblocks, 256, 0, q>>>(cur, h->xstride, Nblk, D, nblocks, S, T, sin,
-		                                                     h->d_mute);
-	}
-	// --- mode_demod (src/rtl_fm.c:1256-1259)
-	TailPlan tp = plan_tail(h, nblocks);
-	if (tp.any()) {
-		r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
-		if (r < 0) return r;
-	}
-	int16_t *dd; size_t dds;
-	tail_route(h, tp, d_out, out_stride, &dd, &dds);
-	const int32_t *cnt = varcnt ? h->d_cnt[h->step & 1] : nullptr;
-	if (c.mode == RTLFM_MODE_FM)
-		k_fm_demod<<<S * nblocks, 256, 0, q>>>(cur, h->xstride, dd, dds, T, S, Nblk, D, nblocks,
-		                                         c.custom_atan, h->d_lut, cnt, sin, sout);
-	else
-		k_simple_demod<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, h->xstride, dd, dds, T, S, c.mode,
-		                                                     c.output_scale, cnt);
-	if (c.mode == RTLFM_MODE_RAW) {
-		if (d_out_len) {
-			if (varcnt) {
-				HIP_TRY(hipMemcpyAsync(d_out_len, h->d_cnt[h->step & 1], S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-				k_scale_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2, 1);
-			} else {
-				k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * T);
-			}
-		}
-		return 0;
-	}
-	return run_tail(h, tp, dd, dds, T, varcnt, nblocks, Nblk, D, d_out, out_stride, d_out_len);
+	return run_back_half(h, cur, h->xstride, T, Nblk, D, nblocks, varcnt ? h->d_cnt[h->step & 1] : nullptr, plan_tail(h, nblocks), d_out,
+	                     out_stride, d_out_len, d_iq, iq_extent(h, stream_stride, nblocks));
 }
 
 
@@ -1610,10 +1628,7 @@ static int run_fused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_strid
 	if (r < 0) return r;
 	r = timing_end(h, ev);
 	if (r < 0) return r;
-	if (raw_direct) {
-		if (d_out_len) k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * nblocks * (N0 >> c.downsample_passes));
-		return 0;
-	}
+	if (raw_direct) return raw_out_len(h, d_out_len, nullptr, nblocks * (N0 >> c.downsample_passes));
 	uint32_t *cur = h->deepA, *oth = h->deepB;
 	const int first_irr = first_irregular_pass(c);
 	// seven and more passes on buffers they divide: the passes beyond six, generic_fir and (without a squelch) the
@@ -1638,26 +1653,8 @@ static int run_fused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_strid
 			k_deep_rest<<<(unsigned)((size_t)S * nblocks), 256, lds_b, q>>>(dp);
 			if (demod_here) return run_tail(h, tp, dd2, dds2, T2, false, nblocks, nF, 1, d_out, out_stride, d_out_len);
 			std::swap(cur, oth);
-			// the squelch, -L, -M raw on the final level, as below
-			const int Nblk2 = nF;
-			if (c.squelch_level || c.report_levels)
-				k_squelch_rms<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, Nblk2, 1, nblocks, sin, c.squelch_level,
-				                                         c.dc_block_raw, h->d_mute, h->d_levels);
-			if (c.squelch_level) {
-				k_squelch_hits<<<grid_for(S, 64), 64, 0, q>>>(h->d_mute, nblocks, S, sin, sout);
-				k_squelch_zero<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, Nblk2, 1, nblocks, S, T2, sin, h->d_mute);
-			}
-			if (c.mode == RTLFM_MODE_FM)
-				k_fm_demod<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, dd2, dds2, T2, S, Nblk2, 1, nblocks, c.custom_atan,
-				                                         h->d_lut, nullptr, sin, sout);
-			else
-				k_simple_demod<<<grid_for((size_t)S * T2), 256, 0, q>>>(cur, h->deep_stride, dd2, dds2, T2, S, c.mode,
-				                                                      c.output_scale, nullptr);
-			if (c.mode == RTLFM_MODE_RAW) {
-				if (d_out_len) k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * T2);
-				return 0;
-			}
-			return run_tail(h, tp, dd2, dds2, T2, false, nblocks, Nblk2, 1, d_out, out_stride, d_out_len);
+			// the squelch, -L, -M raw on the final level
+			return run_back_half(h, cur, h->deep_stride, T2, nF, 1, nblocks, nullptr, tp, d_out, out_stride, d_out_len);
 		}
 	}
 	for (int p = level; p < c.downsample_passes && p < first_irr; p++) {
@@ -1675,27 +1672,7 @@ static int run_fused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_strid
 		k_fir9<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, oth, h->deep_stride, T, S, c.downsample_passes, sin, sout);
 		std::swap(cur, oth);
 	}
-	if (c.squelch_level || c.report_levels)
-		k_squelch_rms<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, Nblk, 1, nblocks, sin, c.squelch_level,
-		                                         c.dc_block_raw, h->d_mute, h->d_levels);
-	if (c.squelch_level) {
-		k_squelch_hits<<<grid_for(S, 64), 64, 0, q>>>(h->d_mute, nblocks, S, sin, sout);
-		k_squelch_zero<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, Nblk, 1, nblocks, S, T, sin,
-		                                                     h->d_mute);
-	}
-	int16_t *dd; size_t dds;
-	tail_route(h, tp, d_out, out_stride, &dd, &dds);
-	if (c.mode == RTLFM_MODE_FM)
-		k_fm_demod<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, dd, dds, T, S, Nblk, 1, nblocks, c.custom_atan,
-		                                         h->d_lut, nullptr, sin, sout);
-	else
-		k_simple_demod<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, h->deep_stride, dd, dds, T, S, c.mode,
-		                                                     c.output_scale, nullptr);
-	if (c.mode == RTLFM_MODE_RAW) {
-		if (d_out_len) k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * T);
-		return 0;
-	}
-	return run_tail(h, tp, dd, dds, T, false, nblocks, Nblk, 1, d_out, out_stride, d_out_len);
+	return run_back_half(h, cur, h->deep_stride, T, Nblk, 1, nblocks, nullptr, tp, d_out, out_stride, d_out_len);
 }
 
 // The boxcar (low_pass) front end in one launch; output counts may differ per buffer and
@@ -1775,45 +1752,8 @@ static int run_boxfused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_st
 	const int Tin = nblocks * N0;
 	const bool varcnt = (N0 % D) != 0;
 	const int T = varcnt ? Tin / D + 1 : Tin / D;
-	if (raw_direct) {
-		if (d_out_len) {
-			if (varcnt) {
-				HIP_TRY(hipMemcpyAsync(d_out_len, dcnt, S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-				k_scale_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2, 1);
-			} else {
-				k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * T);
-			}
-		}
-		return 0;
-	}
-	uint32_t *cur = h->deepA;
-	if (c.squelch_level || c.report_levels)
-		k_squelch_rms<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, N0, D, nblocks, sin, c.squelch_level, c.dc_block_raw,
-		                                         h->d_mute, h->d_levels);
-	if (c.squelch_level) {
-		k_squelch_hits<<<grid_for(S, 64), 64, 0, q>>>(h->d_mute, nblocks, S, sin, sout);
-		k_squelch_zero<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, N0, D, nblocks, S, T, sin, h->d_mute);
-	}
-	int16_t *dd; size_t dds;
-	tail_route(h, tp, d_out, out_stride, &dd, &dds);
-	const int32_t *cnt = varcnt ? dcnt : nullptr;
-	if (c.mode == RTLFM_MODE_FM)
-		k_fm_demod<<<S * nblocks, 256, 0, q>>>(cur, h->deep_stride, dd, dds, T, S, N0, D, nblocks, c.custom_atan, h->d_lut, cnt,
-		                                         sin, sout);
-	else
-		k_simple_demod<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, h->deep_stride, dd, dds, T, S, c.mode, c.output_scale, cnt);
-	if (c.mode == RTLFM_MODE_RAW) {
-		if (d_out_len) {
-			if (varcnt) {
-				HIP_TRY(hipMemcpyAsync(d_out_len, dcnt, S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-				k_scale_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2, 1);
-			} else {
-				k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * T);
-			}
-		}
-		return 0;
-	}
-	return run_tail(h, tp, dd, dds, T, varcnt, nblocks, N0, D, d_out, out_stride, d_out_len);
+	if (raw_direct) return raw_out_len(h, d_out_len, varcnt ? dcnt : nullptr, T);
+	return run_back_half(h, h->deepA, h->deep_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
 }
 
 static int ensure_input_stats(rtlfm_gpu *h)
@@ -2066,33 +2006,112 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	return 0;
 }
 
-// The last run's gate records (k_scan_gate, option squelch_gate): the contract of rtlfm_gpu_levels.
-extern "C" int rtlfm_gpu_gate(rtlfm_gpu *h, int stream, rtlfm_gate_rec *out, int cap, int *n)
+// The records a run leaves per buffer on the device, [stream][count]: one stream's, or (`all`) every stream's as rows of
+// `cap` records.  One contract for all of them, rtlfm_gpu_levels': bad arguments, then "not enabled", then the count -
+// written even where it does not fit -, then the copy.
+template <class Rec>
+static int fetch_records(rtlfm_gpu *h, Rec *rtlfm_gpu::*recs, int rtlfm_gpu::*count_of, bool (*enabled)(const rtlfm_gpu *),
+                         bool all, int stream, Rec *out, int cap, int *n)
 {
-	if (!h || !out || !n || stream < 0 || stream >= h->nstreams) return -EINVAL;
-	if (!h->opt.squelch_gate) return -ENODATA;
-	*n = h->gate_nblocks;
-	if (h->gate_nblocks > cap) return -ENOBUFS;
+	if (!h || !out || !n || (!all && (stream < 0 || stream >= h->nstreams))) return -EINVAL;
+	if (!enabled(h)) return -ENODATA;
+	const int count = h->*count_of;
+	*n = count;
+	if (count > cap) return -ENOBUFS;
 	HIP_TRY(hipSetDevice(h->device));
 	HIP_TRY(sync_all(h));
-	if (h->gate_nblocks > 0)
-		HIP_TRY(hipMemcpy(out, h->d_gate + (size_t)stream * h->gate_nblocks, (size_t)h->gate_nblocks * sizeof(rtlfm_gate_rec),
-		                  hipMemcpyDeviceToHost));
+	if (count <= 0) return 0;
+	const size_t row = (size_t)count * sizeof(Rec);
+	if (all)
+		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(Rec), h->*recs, row, row, (size_t)h->nstreams, hipMemcpyDeviceToHost));
+	else
+		HIP_TRY(hipMemcpy(out, h->*recs + (size_t)stream * count, row, hipMemcpyDeviceToHost));
+	return 0;
+}
+static bool levels_on(const rtlfm_gpu *h) { return h->cfg.squelch_level || h->cfg.report_levels; }
+static bool gate_on(const rtlfm_gpu *h) { return h->opt.squelch_gate != 0; }
+static bool stats_on(const rtlfm_gpu *h) { return h->opt.input_stats != 0; }
+static bool health_on(const rtlfm_gpu *h) { return h->opt.input_health != 0; }
+
+// rms() per buffer of the last run (the squelch's, -L's)
+extern "C" int rtlfm_gpu_levels(rtlfm_gpu *h, int stream, int32_t *rms, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_levels, &rtlfm_gpu::last_nblocks, levels_on, false, stream, rms, cap, n);
+}
+extern "C" int rtlfm_gpu_levels_all(rtlfm_gpu *h, int32_t *rms, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_levels, &rtlfm_gpu::last_nblocks, levels_on, true, 0, rms, cap, n);
+}
+// The last run's gate records (k_scan_gate, option squelch_gate)
+extern "C" int rtlfm_gpu_gate(rtlfm_gpu *h, int stream, rtlfm_gate_rec *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_gate, &rtlfm_gpu::gate_nblocks, gate_on, false, stream, out, cap, n);
+}
+extern "C" int rtlfm_gpu_gate_all(rtlfm_gpu *h, rtlfm_gate_rec *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_gate, &rtlfm_gpu::gate_nblocks, gate_on, true, 0, out, cap, n);
+}
+// The last run's ADC statistics (k_input_stats, option input_stats)
+extern "C" int rtlfm_gpu_input_stats(rtlfm_gpu *h, int stream, rtlfm_input_stat *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_istats, &rtlfm_gpu::stats_nblocks, stats_on, false, stream, out, cap, n);
+}
+extern "C" int rtlfm_gpu_input_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_istats, &rtlfm_gpu::stats_nblocks, stats_on, true, 0, out, cap, n);
+}
+// The last run's input health records (k_input_health, option input_health)
+extern "C" int rtlfm_gpu_input_health(rtlfm_gpu *h, int stream, rtlfm_input_health *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_ihealth, &rtlfm_gpu::health_nblocks, health_on, false, stream, out, cap, n);
+}
+extern "C" int rtlfm_gpu_input_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_ihealth, &rtlfm_gpu::health_nblocks, health_on, true, 0, out, cap, n);
+}
+
+// The raw-byte readers as standalone operators on device memory (no handle): tools/input_stats_bench.py times them, and a
+// caller that only wants to know which front ends clip needs no demodulator.  `outs`: the record arrays, 16-byte aligned.
+template <class Launch>
+static int reader_device_op(int device, const uint8_t *d_iq, std::initializer_list<const void *> outs, Launch launch)
+{
+	if (!d_iq) return -EINVAL;
+	for (const void *p : outs)
+		if (!p || ((uintptr_t)p & 15)) return -EINVAL;
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
+	HIP_TRY(hipSetDevice(device));
+	const int r = launch();
+	if (r < 0) return r;
+	HIP_TRY(hipGetLastError());
 	return 0;
 }
 
-extern "C" int rtlfm_gpu_gate_all(rtlfm_gpu *h, rtlfm_gate_rec *out, int cap, int *n)
+extern "C" int rtlfm_gpu_input_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                            int nstreams, rtlfm_input_stat *d_out, int nontemporal, void *hip_stream)
 {
-	if (!h || !out || !n) return -EINVAL;
-	if (!h->opt.squelch_gate) return -ENODATA;
-	*n = h->gate_nblocks;
-	if (h->gate_nblocks > cap) return -ENOBUFS;
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(sync_all(h));
-	if (h->gate_nblocks > 0)
-		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(rtlfm_gate_rec), h->d_gate, (size_t)h->gate_nblocks * sizeof(rtlfm_gate_rec),
-		                    (size_t)h->gate_nblocks * sizeof(rtlfm_gate_rec), (size_t)h->nstreams, hipMemcpyDeviceToHost));
-	return 0;
+	return reader_device_op(device, d_iq, {d_out}, [&] {
+		return istats::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream);
+	});
+}
+
+extern "C" int rtlfm_gpu_input_health_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                             int nstreams, rtlfm_input_health *d_out, int nontemporal, void *hip_stream)
+{
+	return reader_device_op(device, d_iq, {d_out}, [&] {
+		return ihealth::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream);
+	});
+}
+
+// ... and the launch a handle with both options on makes: both record arrays from one read of the input
+extern "C" int rtlfm_gpu_input_health_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
+                                                   int nstreams, rtlfm_input_health *d_out, rtlfm_input_stat *d_stats, int nontemporal,
+                                                   void *hip_stream)
+{
+	return reader_device_op(device, d_iq, {d_out, d_stats}, [&] {
+		return ihealth::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream,
+		                       d_stats);
+	});
 }
 
 extern "C" int rtlfm_gpu_mute(rtlfm_gpu *h, int stream, uint32_t nbytes)
@@ -2133,138 +2152,6 @@ extern "C" int rtlfm_gpu_mute_device(int device, uint8_t *d_iq, size_t stream_st
 	if (hipStreamSynchronize(q) != hipSuccess) r = -EIO;  // the entries are freed below
 	(void)hipFree(d_ent);
 	return r;
-}
-
-extern "C" int rtlfm_gpu_levels(rtlfm_gpu *h, int stream, int32_t *rms, int cap, int *n)
-{
-	if (!h || !rms || !n || stream < 0 || stream >= h->nstreams) return -EINVAL;
-	if (!h->cfg.squelch_level && !h->cfg.report_levels) return -ENODATA;
-	*n = h->last_nblocks;
-	if (h->last_nblocks > cap) return -ENOBUFS;
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(sync_all(h));
-	// the kernels index the buffers of a run [stream][nblocks]
-	if (h->last_nblocks > 0)
-		HIP_TRY(hipMemcpy(rms, h->d_levels + (size_t)stream * h->last_nblocks, (size_t)h->last_nblocks * sizeof(int32_t),
-		                  hipMemcpyDeviceToHost));
-	return 0;
-}
-
-extern "C" int rtlfm_gpu_levels_all(rtlfm_gpu *h, int32_t *rms, int cap, int *n)
-{
-	if (!h || !rms || !n) return -EINVAL;
-	if (!h->cfg.squelch_level && !h->cfg.report_levels) return -ENODATA;
-	*n = h->last_nblocks;
-	if (h->last_nblocks > cap) return -ENOBUFS;
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(sync_all(h));
-	if (h->last_nblocks > 0)
-		HIP_TRY(hipMemcpy2D(rms, (size_t)cap * sizeof(int32_t), h->d_levels, (size_t)h->last_nblocks * sizeof(int32_t),
-		                    (size_t)h->last_nblocks * sizeof(int32_t), (size_t)h->nstreams, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-// The last run's ADC statistics (k_input_stats, option input_stats): the contract of rtlfm_gpu_levels.
-extern "C" int rtlfm_gpu_input_stats(rtlfm_gpu *h, int stream, rtlfm_input_stat *out, int cap, int *n)
-{
-	if (!h || !out || !n || stream < 0 || stream >= h->nstreams) return -EINVAL;
-	if (!h->opt.input_stats) return -ENODATA;
-	*n = h->stats_nblocks;
-	if (h->stats_nblocks > cap) return -ENOBUFS;
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(sync_all(h));
-	// the kernel indexes the records of a run [stream][nblocks]
-	if (h->stats_nblocks > 0)
-		HIP_TRY(hipMemcpy(out, h->d_istats + (size_t)stream * h->stats_nblocks, (size_t)h->stats_nblocks * sizeof(rtlfm_input_stat),
-		                  hipMemcpyDeviceToHost));
-	return 0;
-}
-
-extern "C" int rtlfm_gpu_input_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int *n)
-{
-	if (!h || !out || !n) return -EINVAL;
-	if (!h->opt.input_stats) return -ENODATA;
-	*n = h->stats_nblocks;
-	if (h->stats_nblocks > cap) return -ENOBUFS;
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(sync_all(h));
-	if (h->stats_nblocks > 0)
-		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(rtlfm_input_stat), h->d_istats, (size_t)h->stats_nblocks * sizeof(rtlfm_input_stat),
-		                    (size_t)h->stats_nblocks * sizeof(rtlfm_input_stat), (size_t)h->nstreams, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-// The same statistics as a standalone operator on device memory (no handle): tools/input_stats_bench.py times it, and a
-// caller that only wants to know which front ends clip needs no demodulator.
-extern "C" int rtlfm_gpu_input_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
-                                            int nstreams, rtlfm_input_stat *d_out, int nontemporal, void *hip_stream)
-{
-	if (!d_iq || !d_out || ((uintptr_t)d_out & 15)) return -EINVAL;
-	int count = 0;
-	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
-	HIP_TRY(hipSetDevice(device));
-	const int r = istats::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream);
-	if (r < 0) return r;
-	HIP_TRY(hipGetLastError());
-	return 0;
-}
-
-// The last run's input health records (k_input_health, option input_health): the contract of rtlfm_gpu_input_stats.
-extern "C" int rtlfm_gpu_input_health(rtlfm_gpu *h, int stream, rtlfm_input_health *out, int cap, int *n)
-{
-	if (!h || !out || !n || stream < 0 || stream >= h->nstreams) return -EINVAL;
-	if (!h->opt.input_health) return -ENODATA;
-	*n = h->health_nblocks;
-	if (h->health_nblocks > cap) return -ENOBUFS;
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(sync_all(h));
-	if (h->health_nblocks > 0)
-		HIP_TRY(hipMemcpy(out, h->d_ihealth + (size_t)stream * h->health_nblocks, (size_t)h->health_nblocks * sizeof(rtlfm_input_health),
-		                  hipMemcpyDeviceToHost));
-	return 0;
-}
-
-extern "C" int rtlfm_gpu_input_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n)
-{
-	if (!h || !out || !n) return -EINVAL;
-	if (!h->opt.input_health) return -ENODATA;
-	*n = h->health_nblocks;
-	if (h->health_nblocks > cap) return -ENOBUFS;
-	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(sync_all(h));
-	if (h->health_nblocks > 0)
-		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(rtlfm_input_health), h->d_ihealth, (size_t)h->health_nblocks * sizeof(rtlfm_input_health),
-		                    (size_t)h->health_nblocks * sizeof(rtlfm_input_health), (size_t)h->nstreams, hipMemcpyDeviceToHost));
-	return 0;
-}
-
-extern "C" int rtlfm_gpu_input_health_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
-                                             int nstreams, rtlfm_input_health *d_out, int nontemporal, void *hip_stream)
-{
-	if (!d_iq || !d_out || ((uintptr_t)d_out & 15)) return -EINVAL;
-	int count = 0;
-	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
-	HIP_TRY(hipSetDevice(device));
-	const int r = ihealth::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream);
-	if (r < 0) return r;
-	HIP_TRY(hipGetLastError());
-	return 0;
-}
-
-// ... and the launch a handle with both options on makes: both record arrays from one read of the input
-extern "C" int rtlfm_gpu_input_health_stats_device(int device, const uint8_t *d_iq, size_t stream_stride, uint32_t block_len, int nblocks,
-                                                   int nstreams, rtlfm_input_health *d_out, rtlfm_input_stat *d_stats, int nontemporal,
-                                                   void *hip_stream)
-{
-	if (!d_iq || !d_out || !d_stats || ((uintptr_t)d_out & 15) || ((uintptr_t)d_stats & 15)) return -EINVAL;
-	int count = 0;
-	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
-	HIP_TRY(hipSetDevice(device));
-	const int r = ihealth::launch(d_iq, stream_stride, block_len, nblocks, nstreams, d_out, nblocks, nontemporal != 0, (hipStream_t)hip_stream,
-	                              d_stats);
-	if (r < 0) return r;
-	HIP_TRY(hipGetLastError());
-	return 0;
 }
 
 // --------------------------------------------- callback-side: push / fetch ----

@@ -12,19 +12,23 @@ import sys
 
 import pytest
 
+from rtlsdr_amd import build as hipbuild
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def device_asm(tmp_path_factory):
-    """The gfx950 assembly of both translation units, compiled once (side by side) for every lint of this file."""
+    """The gfx950 assembly of every device unit (rtlsdr_amd/build.py has the list; the k_fused unit first), compiled once
+    (side by side) for every lint of this file."""
+    assert hipbuild.DEVICE_UNITS[0] == hipbuild.FUSED_UNIT
     td = tmp_path_factory.mktemp("isa")
     procs = []
-    for u in ("rtlfm_hip", "rtlpower_hip", "rtlfm_place"):
-        out = str(td / (u + ".s"))
+    for u in hipbuild.DEVICE_UNITS:
+        out = str(td / (os.path.splitext(u)[0] + ".s"))
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
                "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
-               os.path.join(ROOT, "rtlsdr_amd", "csrc", u + ".hip"), "-o", out]
+               os.path.join(hipbuild.CSRC, u), "-o", out]
         procs.append((out, subprocess.Popen(cmd, stderr=subprocess.DEVNULL)))
     outs = []
     for out, p in procs:

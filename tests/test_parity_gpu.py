@@ -38,9 +38,10 @@ def assert_parity(got, want, cfg, what=""):
     assert nbad <= max(1, int(1e-4 * got.size)), f"{what}: {nbad}/{got.size} differ by 1 LSB"
 
 
-def gpu_run(cfg, iq2d, path=0, splits=None, options=None):
+def gpu_run(cfg, iq2d, path=0, splits=None, options=None, levels=None):
     """iq2d: uint8 [ns, nb*L].  Returns (list of per-stream outputs, states, path used).
-    options: rtlfm_gpu_set_option name -> value (segmentation of the front end, A/B switches)."""
+    options: rtlfm_gpu_set_option name -> value (segmentation of the front end, A/B switches).
+    levels: a list that receives rtlfm_gpu_levels_all() of the last run, int32 [ns, its buffers]."""
     from rtlsdr_amd.demod import GpuDemod
     ns = iq2d.shape[0]
     L = int(cfg.block_len)
@@ -62,6 +63,8 @@ def gpu_run(cfg, iq2d, path=0, splits=None, options=None):
                 outs[s].append(o[s, :n[s]].copy())
         states = [g.state_get(s) for s in range(ns)]
         used = g.last_path
+        if levels is not None:
+            levels.append(g.levels_all())
     return [np.concatenate(x) for x in outs], states, used
 
 
@@ -1069,26 +1072,36 @@ def test_fused_deep_passes(oracle_lib, passes, fir9, atan, mode, L, nb, ns):
     dict(mode=capi.MODE_FM, downsample=32, downsample_passes=5, comp_fir_size=9, squelch_level=3000, deemph=1, deemph_a=2),
     dict(mode=capi.MODE_AM, downsample=128, downsample_passes=7, squelch_level=200, output_scale=2),
     dict(mode=capi.MODE_USB, downsample=8, downsample_passes=3, squelch_level=1),
+    # behind seven and more passes: the squelch with -M raw, and -L levels in front of fm_demod
+    dict(mode=capi.MODE_RAW, downsample=128, downsample_passes=7, squelch_level=200),
+    dict(mode=capi.MODE_FM, downsample=256, downsample_passes=8, comp_fir_size=9, report_levels=1),
 ])
 def test_fused_emit_raw_and_squelch(oracle_lib, ov):
     """-M raw and the power squelch behind the fused front end in emit mode (decimated,
     FIR-compensated IQ handed to the staged squelch / demod kernels): against the oracle and the
-    all-staged path, incl. squelch_hits and streams that are muted (low amplitude) or not."""
+    all-staged path, incl. squelch_hits and streams that are muted (low amplitude) or not.  Every row
+    twice: the passes beyond six in one launch (k_deep_rest, the default) and as a launch each (deep_rest=0)."""
     L, nb, ns = 16384, 4, 6
     cfg = make_cfg(dict(rate_out=24000, **ov), L, nb)
     loud = synth.fm_iq_u8(ns // 2, L // 2 * nb, seed=4100, fs=1.024e6, dev_hz=5e3, amplitude=60.0)
     quiet = synth.fm_iq_u8(ns - ns // 2, L // 2 * nb, seed=4101, fs=1.024e6, dev_hz=5e3, amplitude=1.5)
     iq = np.concatenate([loud, quiet])
     want, want_len, wst = oracle_lib.run_batch(cfg, iq, nthreads=4)
-    fo, fst, used = gpu_run(cfg, iq, path=2, splits=[(0, 2), (2, nb)])
-    assert used == 2
-    so, sst, used1 = gpu_run(cfg, iq, path=1)
+    has_levels = bool(ov.get("squelch_level") or ov.get("report_levels"))  # rms() per buffer: what the squelch and -L read
+    slev = [] if has_levels else None
+    so, sst, used1 = gpu_run(cfg, iq, path=1, levels=slev)
     assert used1 == 1
-    for s in range(ns):
-        assert len(fo[s]) == want_len[s]
-        assert np.array_equal(fo[s], so[s]), (ov, s)
-        assert_parity(fo[s], want[s, :want_len[s]], cfg, f"emit {ov}[{s}]")
-        assert gu.state_dict(fst[s], False) == gu.state_dict(wst[s], False)
+    for options in (None, dict(deep_rest=0)):
+        flev = [] if has_levels else None
+        fo, fst, used = gpu_run(cfg, iq, path=2, splits=[(0, 2), (2, nb)], options=options, levels=flev)
+        assert used == 2
+        if has_levels:  # the last launch held buffers 2 .. nb - 1
+            assert flev[0].shape == (ns, nb - 2) and np.array_equal(flev[0], slev[0][:, 2:]), (ov, options)
+        for s in range(ns):
+            assert len(fo[s]) == want_len[s]
+            assert np.array_equal(fo[s], so[s]), (ov, options, s)
+            assert_parity(fo[s], want[s, :want_len[s]], cfg, f"emit {ov} {options}[{s}]")
+            assert gu.state_dict(fst[s], False) == gu.state_dict(wst[s], False)
 
 
 @pytest.mark.parametrize("a", [2, 3, 8, 13, 19, 30, 31])

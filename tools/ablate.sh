@@ -13,11 +13,12 @@ set -e
 cd "$(dirname "$0")/.."
 VARIANTS=${VARIANTS:-"0 1"}
 if [ "$1" = build ]; then
+  UNITS=$(python -c "from rtlsdr_amd.build import DEVICE_UNITS; print(' '.join('build_ablate/src/rtlsdr_amd/csrc/' + u for u in DEVICE_UNITS))")
   rm -rf build_ablate/src && mkdir -p build_ablate/src/rtlsdr_amd && cp -r rtlsdr_amd/csrc build_ablate/src/rtlsdr_amd/csrc && cp -r include build_ablate/src/include
   (cd build_ablate/src && patch -p1 < ../../tools/ablate.patch)
   for v in $VARIANTS; do
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -w -Ibuild_ablate/src/include -DRTLFM_ABLATE=$v \
-      build_ablate/src/rtlsdr_amd/csrc/rtlfm_hip.hip build_ablate/src/rtlsdr_amd/csrc/rtlpower_hip.hip -o build_ablate/librtlfm_hip_a$v.so &
+      $UNITS -o build_ablate/librtlfm_hip_a$v.so &
     [ $(jobs -r | wc -l) -ge 4 ] && wait -n
   done
   wait

@@ -19,7 +19,10 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ["rtlsdr_amd/csrc/rtlfm_hip.hip", "rtlsdr_amd/csrc/rtlpower_hip.hip", "rtlsdr_amd/csrc/rtlfm_place.hip"]
+sys.path.insert(0, ROOT)
+from rtlsdr_amd.build import CSRC, DEVICE_UNITS  # noqa: E402
+
+UNITS = [os.path.join(CSRC, u) for u in DEVICE_UNITS]
 READ_WAIT, WRITE_WAIT = 3, 2
 
 REG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
@@ -121,7 +124,7 @@ def compile_units(defs):
     for u in UNITS:
         out = os.path.join(td, os.path.basename(u) + ".s")
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
-               "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", *defs, os.path.join(ROOT, u), "-o", out]
+               "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", *defs, u, "-o", out]
         procs.append((out, subprocess.Popen(cmd, stderr=subprocess.DEVNULL)))
     for out, p in procs:
         if p.wait() != 0:

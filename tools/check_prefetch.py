@@ -6,12 +6,12 @@ the middle of a tile and consumes them at the top of the next iteration.  The
 register allocator sometimes splits the live range of a loaded register and
 inserts `s_waitcnt vmcnt(N)` + v_mov right after the loads (or at the loop
 bottom), which stalls the wave for a full HBM latency every tile.  This script
-compiles rtlfm_hip.hip to assembly and reports, per kernel, every vmcnt wait
+compiles the k_fused unit (rtlsdr_amd/build.py: FUSED_UNIT) to assembly and reports, per kernel, every vmcnt wait
 between the tile loads and the loop back-edge that forces one of them to
 complete (vmcnt counts in order: a wait for N forces every operation that has
 at least N younger ones).
 
-    python tools/check_prefetch.py [-DNAME=VALUE ...] [rtlfm_hip.s]      exit 1 if any kernel stalls
+    python tools/check_prefetch.py [-DNAME=VALUE ...] [fused_unit.s]      exit 1 if any kernel stalls
 (an assembly file that exists already - tests/test_isa_lint.py compiles once for both of its lints - is read instead of compiling)
 """
 import os
@@ -21,6 +21,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from rtlsdr_amd.build import CSRC, FUSED_UNIT  # noqa: E402
 
 
 def kernels(asm):
@@ -78,7 +80,7 @@ def compile_asm(defs):
         out = os.path.join(td, "fm.s")
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
                "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", *defs,
-               os.path.join(ROOT, "rtlsdr_amd/csrc/rtlfm_hip.hip"), "-o", out]
+               os.path.join(CSRC, FUSED_UNIT), "-o", out]
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
         return open(out).read()
 

@@ -3,7 +3,8 @@
 
     python tools/isa_count.py k_boxcar_scan [file.s]
 
-Without a file the library's HIP source is compiled to gfx950 assembly in a temp dir."""
+Without a file one unit of the library (ISA_SRC=<unit>; by default rtlsdr_amd/build.py's FUSED_UNIT, which holds the
+rtl_fm kernels) is compiled to gfx950 assembly in a temp dir."""
 import collections
 import os
 import re
@@ -12,19 +13,21 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from rtlsdr_amd.build import CSRC, FUSED_UNIT  # noqa: E402
 
 
-def assembly(src="rtlfm_hip.hip"):
+def assembly(src):
     d = tempfile.mkdtemp()
     out = os.path.join(d, "k.s")
     subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-w",
-                           "--cuda-device-only", "-S", "-o", out, os.path.join(ROOT, "rtlsdr_amd", "csrc", src)])
+                           "--cuda-device-only", "-S", "-o", out, os.path.join(CSRC, src)])
     return out
 
 
 def main():
     pat = sys.argv[1]
-    path = sys.argv[2] if len(sys.argv) > 2 else assembly(os.environ.get("ISA_SRC", "rtlfm_hip.hip"))
+    path = sys.argv[2] if len(sys.argv) > 2 else assembly(os.environ.get("ISA_SRC", FUSED_UNIT))
     s = open(path).read()
     for m in re.finditer(r"^(_Z\S*" + re.escape(pat) + r"\S*):", s, re.M):
         name = m.group(1)
