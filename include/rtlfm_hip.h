@@ -334,6 +334,47 @@ int rtlfm_gpu_state_set(rtlfm_gpu *h, int stream, const rtlfm_stream_state *st);
 /* demod_init() values for every stream. */
 int rtlfm_gpu_reset(rtlfm_gpu *h);
 
+/*
+ * The stream lifecycle: the carried state of MANY streams in one operation ("Checkpoint /
+ * resume": the persisting fields of struct demod_state, src/rtl_fm.c:172-208, are one explicit, copyable record per
+ * stream).  rtlfm_gpu_state_get / _set wait for the handle and make one small blocking copy per call; a loop of them
+ * over thousands of streams costs thousands of times a run (DESIGN.md sections 8.3, 8.4).
+ *
+ * rtlfm_gpu_state_get_all / _set_all: every stream's record in one wait and one copy, with the semantics of the
+ * per-stream calls.  get_all: *n = the handle's stream count (written even where it does not fit), -ENOBUFS when
+ * cap is smaller.  set_all: n must be the handle's stream count (-EINVAL).
+ *
+ * rtlfm_gpu_state_move: stream k of dst takes the carried state AND the hop mute still owed (rtlfm_gpu_mute) of
+ * stream map[k] of src; map[k] == -1 gives it demod_init()'s state and no mute.  n must be dst's stream count and
+ * every map[k] must lie in [-1, src's stream count); an entry may occur several times (one stream fans out to
+ * several).  dst == src is allowed: a permutation, a fan-out or a reset of single streams in place.  The handles
+ * share one configuration by the caller's word - a record means what its handle's configuration makes of it.
+ * What a stream carries moves; what describes a run does not: the per-run records (levels, gate, input statistics
+ * and health) and the results stay where they are, and buffers queued in src's ring stay with src, which is left
+ * exactly as it was (when it is not dst).
+ * Blocks like rtlfm_gpu_state_set: waits for everything both handles have queued, then ONE kernel launch
+ * (k_state_move, csrc/state_kernel.h) whatever n is - the map travels to the device as one small array - and no
+ * call into the HIP runtime per stream.
+ *   -EBUSY   either handle has a run begun and not ended (rtlfm_gpu_run_begin) or a ring slot open (rtlfm_gpu_acquire)
+ *   -EXDEV   the handles are on different devices: go through rtlfm_gpu_state_get_all / _set_all
+ *   -EINVAL  anything out of range; both handles are left as they were (as after every failure)
+ *
+ * rtlfm_gpu_save / _load: every stream's record and owed mute to / from a file (include/rtlfm_snapshot.h, host-only
+ * format: checksummed, written through a temporary file and rename).  save = get_all + the mutes +
+ * rtlfm_snapshot_write; load = rtlfm_snapshot_read + set_all + rtlfm_gpu_mute.  load changes nothing and says
+ *   -ERANGE       the file holds another number of streams than the handle
+ *   -EMEDIUMTYPE  it was saved under another configuration: any rtlfm_cfg field but max_blocks and report_levels
+ *                 differs (those two change how much a run takes and what it reports, not what a stream carries)
+ *   -EILSEQ       it is damaged or no snapshot at all
+ * A restarted service that loads what it saved goes on without a click: its first output sample is the one the
+ * uninterrupted run would have produced.
+ */
+int rtlfm_gpu_state_get_all(rtlfm_gpu *h, rtlfm_stream_state *out, int cap, int *n);
+int rtlfm_gpu_state_set_all(rtlfm_gpu *h, const rtlfm_stream_state *in, int n);
+int rtlfm_gpu_state_move(rtlfm_gpu *dst, rtlfm_gpu *src, const int32_t *map, int n);
+int rtlfm_gpu_save(rtlfm_gpu *h, const char *path);
+int rtlfm_gpu_load(rtlfm_gpu *h, const char *path);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,

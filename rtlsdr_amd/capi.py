@@ -306,6 +306,11 @@ _SIGNATURES = [
     ("rtlfm_gpu_state_get", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_state_set", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_reset", C.c_int, [C.c_void_p]),
+    ("rtlfm_gpu_state_get_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_state_set_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("rtlfm_gpu_state_move", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("rtlfm_gpu_save", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rtlfm_gpu_load", C.c_int, [C.c_void_p, C.c_char_p]),
     ("rtlfm_gpu_sync", C.c_int, [C.c_void_p]),
     ("rtlfm_gpu_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtlfm_gpu_wait_for", C.c_int, [C.c_void_p, C.c_void_p]),
@@ -430,6 +435,14 @@ _SCAN_SIGNATURES = [
 ]
 DECLARED_SCAN_SYMBOLS = [s[0] for s in _SCAN_SIGNATURES]
 
+# ... and include/rtlfm_snapshot.h (the snapshot file of rtlfm_gpu_save / _load; host code inside the same library)
+_SNAPSHOT_SIGNATURES = [
+    ("rtlfm_snapshot_write", C.c_int, [C.c_char_p, _P(RtlfmCfg), C.c_int, C.c_void_p, C.c_void_p]),
+    ("rtlfm_snapshot_info", C.c_int, [C.c_char_p, _P(RtlfmCfg), _P(C.c_int)]),
+    ("rtlfm_snapshot_read", C.c_int, [C.c_char_p, _P(RtlfmCfg), C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+]
+DECLARED_SNAPSHOT_SYMBOLS = [s[0] for s in _SNAPSHOT_SIGNATURES]
+
 DECLARED_SYMBOLS = [s[0] for s in _SIGNATURES]
 DECLARED_FM_SYMBOLS = [s[0] for s in _SIGNATURES if s[0].startswith("rtlfm_")]
 DECLARED_POWER_SYMBOLS = [s[0] for s in _POWER_SIGNATURES]
@@ -463,7 +476,7 @@ def load(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES:
+    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES + _SNAPSHOT_SIGNATURES:
         if path is not None and not hasattr(lib, name):
             continue  # an explicitly named other build (A/B against an earlier revision) may predate a symbol
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
@@ -485,3 +498,11 @@ def check(code: int, what: str) -> int:
     if code < 0:
         raise RtlfmError(code, what)
     return code
+
+
+def snapshot_info(path: str):
+    """rtlfm_snapshot_info: (RtlfmCfg, stream count) of a snapshot file that passes every check of its format (the
+    checksum included); RtlfmError otherwise (-EILSEQ for a damaged file).  Needs no GPU."""
+    cfg, n = RtlfmCfg(), C.c_int()
+    check(load().rtlfm_snapshot_info(os.fsencode(path), C.byref(cfg), C.byref(n)), "rtlfm_snapshot_info")
+    return cfg, n.value

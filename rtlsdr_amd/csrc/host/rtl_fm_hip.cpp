@@ -51,6 +51,16 @@
 // -l / -t hold the output back as demod_thread_fn does (:1366-1370): on the device (squelch_gate / conseq_squelch) where
 // the configuration has a gate, else per stream through the carried state.  -L prints full_demod()'s level lines.
 //
+// -K file / -R file (not reference letters): keep and resume.  -K writes every stream's carried state (the persisting
+// fields of struct demod_state, src/rtl_fm.c:172-208; include/rtlfm_snapshot.h) at exit, behind the last run; -R loads
+// such a file after the handle is created and before the first buffer, so that the output continues as if the tool had
+// never stopped: the PCM of "first half with -K" + "second half with -R" is the PCM of the whole capture.  Under -N n the
+// file holds n records in source order; a source that left the batch earlier contributes the record it had when it left.
+// -R wants a file of exactly n records saved under the same configuration (everything the command line plans but how
+// many buffers a run takes); anything else is refused with the library's text, exit status 2, before a device is opened.
+// Not with -S, -C or -O agc=2: those host engines carry state of their own (hop position and settle counters, the
+// monitor's cycles, the AGC's index and counters) that the snapshot does not hold.
+//
 // Not restated (out of scope): the command file's own hop (its 2 x 3 200 000 byte mute, the DC-filter reset, -B), and
 // -t negative (terminate on squelch).
 #include <getopt.h>
@@ -76,6 +86,7 @@
 #include "../../../include/rtlfm_agc.h"
 #include "../../../include/rtlfm_monitor.h"
 #include "../../../include/rtlfm_scan.h"
+#include "../../../include/rtlfm_snapshot.h"
 #include "../../../include/rtlsdr_file.h"
 #include "wavhdr.h"
 
@@ -225,6 +236,7 @@ struct App {
 	uint32_t user_freq = 0;
 	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
 	bool use_gate = false;             // -l through the device's squelch gate (rtlfm_gpu_gate)
+	const char *keep_file = nullptr;   // -K: the snapshot written at exit
 	bool zero_copy = false;            // -Z: the device layer reads straight into the pinned staging ring
 	unsigned char *open_slot = nullptr;  // the slot the device layer is filling (rtlfm_gpu_acquire)
 	Health hl;                         // -O agc=2
@@ -390,10 +402,14 @@ void demod_thread(App *a)
 			// demod_thread_fn(), src/rtl_fm.c:1366-1370: while the squelch has been closed for more than
 			// conseq_squelch buffers nothing goes to the output thread, and the counter is held one above
 			// the limit ("hair trigger").  squelch_hits starts at 11 (:1615): silence until it first opens.
+			// One read of the state per run, and a write only when the counter was clamped.
 			rtlfm_stream_state st;
-			if (rtlfm_gpu_state_get(a->gpu, 0, &st) == 0 && st.squelch_hits > a->conseq_squelch) {
-				st.squelch_hits = a->conseq_squelch + 1;
-				rtlfm_gpu_state_set(a->gpu, 0, &st);
+			int ns = 0;
+			if (rtlfm_gpu_state_get_all(a->gpu, &st, 1, &ns) == 0 && st.squelch_hits > a->conseq_squelch) {
+				if (st.squelch_hits != a->conseq_squelch + 1) {
+					st.squelch_hits = a->conseq_squelch + 1;
+					rtlfm_gpu_state_set_all(a->gpu, &st, 1);
+				}
 				a->blocks_squelched++;
 				continue;
 			}
@@ -455,7 +471,6 @@ struct Source {
 	int print_level_no = 1, level_max = 0, level_max_max = 0;
 	double level_sum = 0.0;
 	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
-	uint32_t mute_owed = 0;                   // -S: bytes of the hop mute the handle still owes this source
 };
 
 struct RunOut {
@@ -487,6 +502,11 @@ struct Multi {
 	std::vector<rtlfm_gate_rec> gate_recs;
 	bool wb_mode = false;
 	int rate_in = 0, min_capture = 0, fifth = 0, edge = 0;  // what optimal_settings() is asked with for a hop
+	// -K: record i = source i.  A source that leaves the batch leaves its record here (shrink); the others' are read at exit
+	const char *keep_file = nullptr;
+	std::vector<rtlfm_stream_state> kept;
+	std::vector<int> live;                   // handle stream k -> source, as the demod thread left it
+	std::vector<rtlfm_stream_state> states;  // one rtlfm_gpu_state_get_all: -l without a device gate, -K
 };
 
 // the options a handle of this tool runs with besides its configuration
@@ -545,22 +565,36 @@ void dongle_thread_multi(Source *s)
 	s->m->cv_work.notify_one();
 }
 
-// the streams in `stay` (a subsequence of `live`) go on, on a new handle with stay.size() streams
+// -K: the records of the handle's streams (stream k = source live[k]) into m->kept - with `stay`, only those of the
+// sources that are not in it (the ones that leave)
+int keep_states(Multi *m, const std::vector<int> &live, const std::vector<int> *stay)
+{
+	m->states.resize(live.size());
+	int n = 0;
+	const int r = rtlfm_gpu_state_get_all(m->gpu, m->states.data(), (int)live.size(), &n);
+	if (r < 0) return r;
+	for (size_t k = 0; k < live.size(); k++)
+		if (!stay || std::find(stay->begin(), stay->end(), live[k]) == stay->end()) m->kept[(size_t)live[k]] = m->states[k];
+	return 0;
+}
+
+// the streams in `stay` (a subsequence of `live`) go on, on a new handle with stay.size() streams: ONE
+// rtlfm_gpu_state_move, which takes each stream's carried state and the hop mute the old handle still owed it
 int shrink(Multi *m, const std::vector<int> &live, const std::vector<int> &stay)
 {
+	int r = 0;
+	if (m->keep_file && (r = keep_states(m, live, &stay)) < 0) return r;  // in front of the regroup: what the leaving sources carried
 	rtlfm_gpu *nh = nullptr;
-	int r = rtlfm_gpu_create(&m->cfg, (int)stay.size(), 0, &nh);
+	r = rtlfm_gpu_create(&m->cfg, (int)stay.size(), 0, &nh);
 	if (r < 0) return r;
-	for (size_t i = 0, k = 0; i < live.size() && k < stay.size() && r == 0; i++) {
+	std::vector<int32_t> map;
+	for (size_t i = 0, k = 0; i < live.size() && k < stay.size(); i++) {
 		if (live[i] != stay[k]) continue;
-		rtlfm_stream_state st;
-		r = rtlfm_gpu_state_get(m->gpu, (int)i, &st);
-		if (r == 0) r = rtlfm_gpu_state_set(nh, (int)k, &st);
+		map.push_back((int32_t)i);
 		k++;
 	}
-	if (r == 0) r = handle_options(m, nh);
-	for (size_t k = 0; k < stay.size() && r == 0; k++)  // a hop mute the old handle had not applied yet
-		if (m->src[(size_t)stay[k]].mute_owed) r = rtlfm_gpu_mute(nh, (int)k, m->src[(size_t)stay[k]].mute_owed);
+	r = map.size() == stay.size() ? handle_options(m, nh) : -EPROTO;
+	if (r == 0) r = rtlfm_gpu_state_move(nh, m->gpu, map.data(), (int)map.size());
 	if (r < 0) {
 		rtlfm_gpu_destroy(nh);
 		return r;
@@ -678,9 +712,6 @@ int gate_step(Multi *m, const std::vector<int> &live)
 	if (r < 0) return r;
 	for (size_t k = 0; k < live.size(); k++) {
 		Source &s = m->src[(size_t)live[k]];
-		uint64_t bytes = 0;
-		for (const std::vector<uint8_t> &buf : s.taken) bytes += buf.size();
-		s.mute_owed = bytes >= s.mute_owed ? 0 : (uint32_t)(s.mute_owed - bytes);  // this run's input was muted so far
 		for (int b = 0; b < n; b++)
 			if (!m->gate_recs[k * (size_t)cap + b].emit) s.blocks_squelched++;
 		if (m->scan && (r = rtlfm_scan_feed(m->scan, live[k], m->gate_recs.data() + k * (size_t)cap, n)) < 0) return r;
@@ -710,8 +741,7 @@ int gate_step(Multi *m, const std::vector<int> &live)
 	for (int i = 0; i < nh; i++) {
 		const size_t k = (size_t)(std::find(live.begin(), live.end(), (int)hopped[(size_t)i]) - live.begin());
 		if (k == live.size()) continue;
-		m->src[(size_t)hopped[(size_t)i]].mute_owed = RTLFM_SCAN_DEFAULT_DUMP;  // dongle.mute = DEFAULT_BUFFER_DUMP, :1507
-		if ((r = rtlfm_gpu_mute(m->gpu, (int)k, RTLFM_SCAN_DEFAULT_DUMP)) < 0) return r;
+		if ((r = rtlfm_gpu_mute(m->gpu, (int)k, RTLFM_SCAN_DEFAULT_DUMP)) < 0) return r;  // dongle.mute = DEFAULT_BUFFER_DUMP, :1507
 	}
 	return 0;
 }
@@ -757,7 +787,7 @@ void demod_thread_multi(Multi *m)
 			int r = shrink(m, live, stay);
 			if (r < 0) {
 				std::lock_guard<std::mutex> g(m->m);
-				fail_multi(m, "rtlfm_gpu_create / state_get / state_set", r);
+				fail_multi(m, "rtlfm_gpu_create / rtlfm_gpu_state_move", r);
 				break;
 			}
 			if (m->verbosity)
@@ -826,18 +856,24 @@ void demod_thread_multi(Multi *m)
 		t_run += since(t0);
 		t0 = clk::now();
 		runs++;
-		for (size_t k = 0; k < ns; k++) {
-			Source &s = m->src[live[k]];
-			if (m->print_levels) levels_multi(m, s, (int)k);
-			if (m->cfg.squelch_level && !m->use_gate) {
-				// demod_thread's squelch rule (src/rtl_fm.c:1366-1370), per stream; max_blocks is 1 here
-				rtlfm_stream_state st;
-				if (rtlfm_gpu_state_get(m->gpu, (int)k, &st) == 0 && st.squelch_hits > m->conseq_squelch) {
+		if (m->print_levels)
+			for (size_t k = 0; k < ns; k++) levels_multi(m, m->src[live[k]], (int)k);
+		if (m->cfg.squelch_level && !m->use_gate) {
+			// demod_thread's squelch rule (src/rtl_fm.c:1366-1370), per stream; max_blocks is 1 here.  Every stream's state in
+			// one copy, and one copy back only in a run that clamped a counter
+			m->states.resize(ns);
+			int got = 0;
+			bool clamped = false;
+			if (rtlfm_gpu_state_get_all(m->gpu, m->states.data(), (int)ns, &got) == 0) {
+				for (size_t k = 0; k < ns; k++) {
+					rtlfm_stream_state &st = m->states[k];
+					if (st.squelch_hits <= m->conseq_squelch) continue;
+					clamped |= st.squelch_hits != m->conseq_squelch + 1;
 					st.squelch_hits = m->conseq_squelch + 1;
-					rtlfm_gpu_state_set(m->gpu, (int)k, &st);
-					s.blocks_squelched++;
+					m->src[live[k]].blocks_squelched++;
 					o.lens[k] = 0;
 				}
+				if (clamped) rtlfm_gpu_state_set_all(m->gpu, m->states.data(), (int)ns);
 			}
 		}
 		t_per_stream += since(t0);
@@ -850,6 +886,7 @@ void demod_thread_multi(Multi *m)
 		m->out_q.push_back(std::move(o));
 		m->cv_out.notify_one();
 	}
+	m->live = live;
 	if (m->verbosity >= 2)
 		fprintf(stderr, "demod thread: %llu runs; %.3f s waiting for buffers, %.3f s pushing, %.3f s run + fetch_all, %.3f s -l / -L\n",
 		        (unsigned long long)runs, t_wait, t_push, t_run, t_per_stream);
@@ -886,9 +923,11 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
               const std::vector<uint32_t> &capture_freqs, uint32_t capture_rate, int gain, int ppm, const std::string &pattern,
               bool write_wav, int verbosity, int conseq_squelch, int print_levels, const std::vector<rtlfm_monitor_rule> &rules,
               const char *opt_string, int agc, const std::vector<std::vector<uint32_t>> &scan_lists, bool wb_mode, int rate_in,
-              int min_capture, int fifth, int edge)
+              int min_capture, int fifth, int edge, const char *keep_file, const char *resume_file)
 {
 	Multi m;
+	m.keep_file = keep_file;
+	m.kept.resize((size_t)n);
 	m.wb_mode = wb_mode; m.rate_in = rate_in; m.min_capture = min_capture; m.fifth = fifth; m.edge = edge;
 	m.rules = rules;
 	m.cfg = planned;
@@ -957,6 +996,10 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 				fprintf(stderr, "rtlfm_monitor_create: %s\n", rtlfm_gpu_strerror(r));
 				ret = 2;
 			}
+		}
+		if (!ret && resume_file && (r = rtlfm_gpu_load(m.gpu, resume_file)) < 0) {
+			fprintf(stderr, "-R %s: %s\n", resume_file, rtlfm_gpu_strerror(r));
+			ret = 2;
 		}
 		if (!ret && c.squelch_level) {
 			// -l: demod_thread_fn's rule on the device where the configuration has a gate (not behind a resampler)
@@ -1027,6 +1070,15 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 				        (unsigned long long)held, f + (wb_mode ? 16000u : 0u));
 			}
 		if (m.failed) ret = 3;
+		if (!ret && keep_file) {
+			// behind the last run: the sources that were in the batch to the end, beside the records the others left
+			int r = keep_states(&m, m.live, nullptr);
+			if (r == 0) r = rtlfm_snapshot_write(keep_file, &c, n, m.kept.data(), nullptr);
+			if (r < 0) {
+				fprintf(stderr, "-K %s: %s\n", keep_file, rtlfm_gpu_strerror(r));
+				ret = 3;
+			}
+		}
 	}
 	if (m.scan) rtlfm_scan_destroy(m.scan);
 	if (m.hl.agc) rtlfm_agc_destroy(m.hl.agc);
@@ -1043,6 +1095,24 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 	return ret;
 }
 
+// -R: the file against what the command line plans, before a device is opened: 0, or the exit status (2) behind the
+// library's text.  The handle checks the same again when it loads the file (rtlfm_gpu_load).
+int check_resume(const char *path, const rtlfm_cfg &planned, int nstreams)
+{
+	rtlfm_cfg saved;
+	int n = 0;
+	int r = rtlfm_snapshot_info(path, &saved, &n);
+	if (r == 0 && n != nstreams) r = -ERANGE;
+	if (r == 0) {
+		saved.max_blocks = planned.max_blocks;        // how much a run takes and what it reports, not what a stream carries
+		saved.report_levels = planned.report_levels;
+		if (memcmp(&saved, &planned, sizeof(saved)) != 0) r = -EMEDIUMTYPE;
+	}
+	if (r == 0) return 0;
+	fprintf(stderr, "-R %s: %s\n", path, rtlfm_gpu_strerror(r));
+	return 2;
+}
+
 void usage()
 {
 	fprintf(stderr,
@@ -1057,6 +1127,10 @@ void usage()
 	        "\t       adcrms lines add the ADC statistics of the raw bytes; sets -M raw; -v prints every event]\n"
 	        "\t[-S scan_file  scanning: line i of the file is the frequency list of source i (-N n, or one source): frequencies\n"
 	        "\t       and a:b:step ranges; needs -l; a source whose squelch holds a buffer hops to its next frequency; not with -C]\n"
+	        "\t[-K file  keep: write every stream's carried filter state to file at exit (with -N n: n records, in source order)]\n"
+	        "\t[-R file  resume: load such a file before the first buffer - it must hold as many records as there are sources and\n"
+	        "\t       come from the same -M / -s / -r / -F / -A / -E / -l / -W ... plan, else exit 2; the output continues as if the tool had\n"
+	        "\t       never stopped.  -K / -R not with -S, -C or -O agc=2: those engines carry state the file does not hold]\n"
 	        "\t[-M modulation (default: fm)]  fm, wbfm, raw, am, usb, lsb\n"
 	        "\t[-s sample_rate (default: 24k)]  [-r resample_rate (default: none / same as -s)]\n"
 	        "\t[-m minimum_capture_rate Hz (default: 1m)]\n"
@@ -1090,18 +1164,20 @@ int main(int argc, char **argv)
 	int nstreams = 1;
 	bool have_freq = false, write_wav = false, wb_mode = false;
 	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
-	const char *cmd_file = nullptr, *opt_string = nullptr, *scan_file = nullptr;
+	const char *cmd_file = nullptr, *opt_string = nullptr, *scan_file = nullptr, *keep_file = nullptr, *resume_file = nullptr;
 	int agc = -1;  // -O agc=<n>; -1: not given
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
-	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:")) != -1) {
+	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:K:R:")) != -1) {
 		switch (opt) {
 		case 'd': dev_index = atoi(optarg); break;
 		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
 		case 'N': nstreams = atoi(optarg); break;
 		case 'C': cmd_file = optarg; break;
 		case 'S': scan_file = optarg; break;
+		case 'K': keep_file = optarg; break;
+		case 'R': resume_file = optarg; break;
 		case 'O':
 			opt_string = optarg;
 			agc = opt_string_agc(optarg);
@@ -1168,6 +1244,12 @@ int main(int argc, char **argv)
 		case 'v': a.verbosity++; break;
 		default: usage();
 		}
+	}
+	if ((keep_file || resume_file) && (scan_file || cmd_file || agc == 2)) {
+		// before a device is opened: the hop engine, the monitor and the software AGC carry state of their own
+		fprintf(stderr, "-K / -R (keep / resume the carried state) do not go with -S, -C or -O agc=2: those engines carry state of "
+		                "their own that the snapshot does not hold.\n");
+		return 1;
 	}
 	std::vector<std::vector<uint32_t>> scan_lists;
 	if (scan_file) {
@@ -1238,6 +1320,7 @@ int main(int argc, char **argv)
 	const char *filename = optind < argc ? argv[optind] : "-";
 
 	if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
+	int r_resume = 0;
 	if (nstreams > 1 || cmd_file || scan_file) {
 		// everything -N refuses is refused here, before a device is opened or a GPU handle created
 		const std::string pattern(filename);
@@ -1281,11 +1364,19 @@ int main(int argc, char **argv)
 				return 1;
 			}
 		}
+		if (resume_file && (r_resume = check_resume(resume_file, planned, nstreams)) != 0) return r_resume;
 		return run_multi(planned, nstreams, dev_index, freqs, capture_freqs, capture_rate, gain, ppm, pattern, write_wav,
 		                 a.verbosity, conseq_squelch, a.print_levels, rules, opt_string, agc, scan_lists, wb_mode, rate_in, min_capture,
-		                 fifth, edge);
+		                 fifth, edge, keep_file, resume_file);
 	}
 
+	if (resume_file) {
+		// the plan the handle will be created with, before a device is opened (optimal_settings() and deemph_a are host arithmetic)
+		rtlfm_cfg planned = c;
+		if (planned.deemph) planned.deemph_a = rtlfm_deemph_a(planned.rate_out, time_constant);
+		rtlfm_optimal_settings(&planned, freq, rate_in, min_capture, fifth, edge, nullptr, nullptr);
+		if ((r_resume = check_resume(resume_file, planned, 1)) != 0) return r_resume;
+	}
 	if (rtlsdr_get_device_count() == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE).\n"); return 1; }
 	if (rtlsdr_open(&a.dev, (uint32_t)dev_index) < 0) { fprintf(stderr, "Failed to open rtlsdr device #%d.\n", dev_index); return 1; }
 	if (c.deemph) c.deemph_a = rtlfm_deemph_a(c.rate_out, time_constant);
@@ -1308,6 +1399,8 @@ int main(int argc, char **argv)
 
 	int r = rtlfm_gpu_create(&c, 1, 0, &a.gpu);
 	if (r < 0) { fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r)); return 2; }
+	if (resume_file && (r = rtlfm_gpu_load(a.gpu, resume_file)) < 0) { fprintf(stderr, "-R %s: %s\n", resume_file, rtlfm_gpu_strerror(r)); return 2; }
+	a.keep_file = keep_file;
 	if (c.squelch_level) {
 		// -l: demod_thread_fn's rule on the device where the configuration has a gate (not behind a resampler)
 		r = rtlfm_gpu_set_option(a.gpu, "conseq_squelch", conseq_squelch);
@@ -1340,6 +1433,10 @@ int main(int argc, char **argv)
 	if (a.hl.agc) {
 		health_report(&a.hl);
 		rtlfm_agc_destroy(a.hl.agc);
+	}
+	if (a.keep_file && !a.p.failed && (r = rtlfm_gpu_save(a.gpu, a.keep_file)) < 0) {  // behind the last run
+		fprintf(stderr, "-K %s: %s\n", a.keep_file, rtlfm_gpu_strerror(r));
+		a.p.failed = true;
 	}
 	rtlfm_gpu_destroy(a.gpu);
 	rtlsdr_close(a.dev);

@@ -30,6 +30,8 @@
 #include "input_stats_kernel.h"
 #include "input_health_kernel.h"
 #include "scan_kernel.h"
+#include "state_kernel.h"
+#include "../../include/rtlfm_snapshot.h"
 
 using namespace rtlfm;
 
@@ -110,6 +112,7 @@ struct rtlfm_gpu {
 	int mute_streams = 0;                  // streams with a count pending
 	scan::MuteEntry *d_mute_entries = nullptr;
 	size_t mute_entries_cap = 0;
+	int32_t *d_move_map = nullptr;         // [nstreams]: rtlfm_gpu_state_move's map on the device, allocated by the first move into this handle
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -322,6 +325,7 @@ static int options_from_env(rtlfm_gpu *h);
 static long placement_held_mb(rtlfm_gpu *h);
 static void ingest_destroy(rtlfm_gpu *h);
 static void ingest_reset(rtlfm_gpu *h);
+static bool ingest_busy(rtlfm_gpu *h);
 
 // everything the handle has launched: the front end's stream, then the audio tail's
 static hipError_t sync_all(rtlfm_gpu *h)
@@ -520,7 +524,7 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
 	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth,
-	                h->d_gate, h->vt_gate, h->d_mute_entries};
+	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	delete[] h->mute_left;
@@ -569,6 +573,132 @@ extern "C" int rtlfm_gpu_state_set(rtlfm_gpu *h, int stream, const rtlfm_stream_
 	HIP_TRY(sync_all(h));
 	HIP_TRY(hipMemcpy(h->st[h->st_cur] + stream, st, sizeof(*st), hipMemcpyHostToDevice));
 	return 0;
+}
+
+// ---- the stream lifecycle: every stream's carried state in one operation (include/rtlfm_hip.h) ----
+
+extern "C" int rtlfm_gpu_state_get_all(rtlfm_gpu *h, rtlfm_stream_state *out, int cap, int *n)
+{
+	if (!h || !out || !n) return -EINVAL;
+	*n = h->nstreams;
+	if (cap < h->nstreams) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	HIP_TRY(hipMemcpy(out, h->st[h->st_cur], (size_t)h->nstreams * sizeof(state_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_state_set_all(rtlfm_gpu *h, const rtlfm_stream_state *in, int n)
+{
+	if (!h || !in || n != h->nstreams) return -EINVAL;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	HIP_TRY(hipMemcpy(h->st[h->st_cur], in, (size_t)h->nstreams * sizeof(state_t), hipMemcpyHostToDevice));
+	return 0;
+}
+
+// every stream's owed mute at once (what rtlfm_gpu_mute keeps per stream)
+static int set_mutes(rtlfm_gpu *h, const uint32_t *mutes)
+{
+	bool any = false;
+	for (int s = 0; s < h->nstreams; s++) any |= mutes[s] != 0;
+	if (!h->mute_left) {
+		if (!any) return 0;
+		h->mute_left = new (std::nothrow) uint32_t[(size_t)h->nstreams]();
+		if (!h->mute_left) return -ENOMEM;
+	}
+	h->mute_streams = 0;
+	for (int s = 0; s < h->nstreams; s++) {
+		h->mute_left[s] = mutes[s];
+		h->mute_streams += mutes[s] ? 1 : 0;
+	}
+	return 0;
+}
+
+// dst[k] = src[map[k]] (-1: the initial record), state and owed mute; one launch (k_state_move, state_kernel.h).
+// Ordering, also for dst == src: both handles are idle behind sync_all - no run, no tail reads or writes any state copy -,
+// the kernel reads src->st[src->st_cur] and writes dst's NEXT copy, which nothing reads before st_cur has advanced, and
+// st_cur advances only behind the synchronisation that follows the launch.  A failure before that leaves st_cur, and so
+// the handle's state, where it was.
+extern "C" int rtlfm_gpu_state_move(rtlfm_gpu *dst, rtlfm_gpu *src, const int32_t *map, int n)
+{
+	if (!dst || !src || !map || n != dst->nstreams) return -EINVAL;
+	for (int k = 0; k < n; k++)
+		if (map[k] < -1 || map[k] >= src->nstreams) return -EINVAL;
+	if (dst->device != src->device) return -EXDEV;
+	if (ingest_busy(dst) || (src != dst && ingest_busy(src))) return -EBUSY;
+	std::vector<uint32_t> mutes;  // (taken before anything changes: in place, map reads what the loop below would overwrite)
+	try {
+		mutes.assign((size_t)n, 0u);
+	} catch (const std::bad_alloc &) {
+		return -ENOMEM;
+	}
+	if (src->mute_left)
+		for (int k = 0; k < n; k++)
+			if (map[k] >= 0) mutes[(size_t)k] = src->mute_left[map[k]];
+	HIP_TRY(hipSetDevice(dst->device));
+	if (!dst->d_move_map) HIP_TRY(hipMalloc(&dst->d_move_map, (size_t)n * sizeof(int32_t)));
+	HIP_TRY(sync_all(src));
+	if (src != dst) HIP_TRY(sync_all(dst));
+	HIP_TRY(hipMemcpy(dst->d_move_map, map, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+	const int next = (dst->st_cur + 1) % 3;
+	const int r = statemove::launch(dst->st[next], src->st[src->st_cur], dst->d_move_map, n, dst->stream);
+	if (r < 0) return r;
+	HIP_TRY(hipStreamSynchronize(dst->stream));
+	const int m = set_mutes(dst, mutes.data());
+	if (m < 0) return m;
+	dst->st_cur = next;
+	return 0;
+}
+
+// what a stream carries depends on every field of the configuration but these two
+static bool same_carried_cfg(rtlfm_cfg a, const rtlfm_cfg &b)
+{
+	a.max_blocks = b.max_blocks;
+	a.report_levels = b.report_levels;
+	return memcmp(&a, &b, sizeof(a)) == 0;
+}
+
+extern "C" int rtlfm_gpu_save(rtlfm_gpu *h, const char *path)
+{
+	if (!h || !path) return -EINVAL;
+	std::vector<state_t> st;
+	std::vector<uint32_t> mutes;
+	try {
+		st.resize((size_t)h->nstreams);
+		mutes.assign((size_t)h->nstreams, 0u);
+	} catch (const std::bad_alloc &) {
+		return -ENOMEM;
+	}
+	int n = 0;
+	const int r = rtlfm_gpu_state_get_all(h, st.data(), h->nstreams, &n);
+	if (r < 0) return r;
+	if (h->mute_left) memcpy(mutes.data(), h->mute_left, mutes.size() * sizeof(uint32_t));
+	return rtlfm_snapshot_write(path, &h->cfg, h->nstreams, st.data(), mutes.data());
+}
+
+extern "C" int rtlfm_gpu_load(rtlfm_gpu *h, const char *path)
+{
+	if (!h || !path) return -EINVAL;
+	rtlfm_cfg cfg;
+	int n = 0;
+	int r = rtlfm_snapshot_info(path, &cfg, &n);  // (checks the whole file, the checksum included)
+	if (r < 0) return r;
+	if (n != h->nstreams) return -ERANGE;
+	if (!same_carried_cfg(cfg, h->cfg)) return -EMEDIUMTYPE;
+	std::vector<state_t> st;
+	std::vector<uint32_t> mutes;
+	try {
+		st.resize((size_t)n);
+		mutes.assign((size_t)n, 0u);
+	} catch (const std::bad_alloc &) {
+		return -ENOMEM;
+	}
+	int got = 0;
+	if ((r = rtlfm_snapshot_read(path, nullptr, st.data(), mutes.data(), n, &got)) < 0) return r;
+	if (got != n) return -EILSEQ;  // (the file changed between the two reads)
+	if ((r = rtlfm_gpu_state_set_all(h, st.data(), n)) < 0) return r;
+	return set_mutes(h, mutes.data());
 }
 
 extern "C" int rtlfm_gpu_sync(rtlfm_gpu *h)
@@ -2358,6 +2488,18 @@ static void ingest_reset(rtlfm_gpu *h)
 	in->mirror_valid = false;
 }
 
+// a run begun and not ended, or a slot out between acquire and commit: the ring is in the middle of something
+static bool ingest_busy(rtlfm_gpu *h)
+{
+	Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE);
+	if (!in) return false;
+	std::shared_lock<std::shared_mutex> g(in->mu);
+	if (in->pending_f >= 0) return true;
+	for (int s = 0; s < h->nstreams; s++)
+		if (in->open_slot[s].load(std::memory_order_acquire)) return true;
+	return false;
+}
+
 extern "C" int rtlfm_gpu_push(rtlfm_gpu *h, int stream, const uint8_t *iq, uint32_t len)
 {
 	if (!h || !iq || stream < 0 || stream >= h->nstreams) return -EINVAL;
@@ -2911,7 +3053,12 @@ extern "C" const char *rtlfm_gpu_strerror(int err)
 	case -ENOSPC: return "max_blocks already queued for this stream";
 	case -EAGAIN: return "streams have unequal / zero queued blocks, or a producer still holds an acquired slot";
 	case -EBUSY: return "the stream's previous slot is still open (rtlfm_gpu_acquire without rtlfm_gpu_commit), or rtlfm_gpu_run_device while "
-	                    "a rtlfm_gpu_mute count is pending (it never writes its input)";
+	                    "a rtlfm_gpu_mute count is pending (it never writes its input), or rtlfm_gpu_state_move while a handle has a run "
+	                    "begun and not ended or a ring slot open";
+	case -EXDEV: return "rtlfm_gpu_state_move: the handles are on different devices (use rtlfm_gpu_state_get_all / _set_all)";
+	case -ERANGE: return "the snapshot holds another number of streams than the handle";
+	case -EMEDIUMTYPE: return "the snapshot was saved under another configuration (a rtlfm_cfg field other than max_blocks / report_levels differs)";
+	case -EILSEQ: return "the snapshot file is damaged or no snapshot (magic, version, sizes, length or checksum)";
 	case -ENOTSUP: return "configuration not supported on this path; squelch_gate: not behind a resampler (rate_out2 > 0), "
 	                      "post_downsample > 1 or a buffer the fifth_order passes do not divide";
 	case -EDOM: return "outside the reference's own domain: a boxcar longer than the buffer (fm_demod reads lowpassed[-2]), low_pass_simple on a "

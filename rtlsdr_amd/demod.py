@@ -9,6 +9,7 @@ HIP library; this class only moves pointers.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -208,6 +209,35 @@ class GpuDemod:
 
     def state_set(self, stream: int, st: RtlfmStreamState):
         check(self.lib.rtlfm_gpu_state_set(self._h, stream, C.byref(st)), "rtlfm_gpu_state_set")
+
+    def state_get_all(self):
+        """Every stream's record in one wait and one copy: a ctypes array of ``RtlfmStreamState`` [nstreams]."""
+        out = (RtlfmStreamState * self.nstreams)()
+        n = C.c_int()
+        check(self.lib.rtlfm_gpu_state_get_all(self._h, out, self.nstreams, C.byref(n)), "rtlfm_gpu_state_get_all")
+        return out
+
+    def state_set_all(self, states):
+        """The reverse: ``states`` holds exactly nstreams records (a ctypes array as state_get_all returns, or a sequence
+        of ``RtlfmStreamState``)."""
+        if not isinstance(states, C.Array):
+            states = (RtlfmStreamState * len(states))(*states)
+        check(self.lib.rtlfm_gpu_state_set_all(self._h, states, len(states)), "rtlfm_gpu_state_set_all")
+
+    def move_from(self, src: "GpuDemod", map):
+        """rtlfm_gpu_state_move: stream k of this handle takes the carried state and the owed mute of stream ``map[k]`` of
+        ``src`` (-1: the initial state); ``src`` may be this handle itself.  One kernel launch for all streams."""
+        m = np.ascontiguousarray(map, dtype=np.int32)
+        check(self.lib.rtlfm_gpu_state_move(self._h, src._h, m.ctypes.data, m.size), "rtlfm_gpu_state_move")
+
+    def save(self, path):
+        """rtlfm_gpu_save: every stream's record and owed mute into a snapshot file (include/rtlfm_snapshot.h)."""
+        check(self.lib.rtlfm_gpu_save(self._h, os.fsencode(path)), "rtlfm_gpu_save")
+
+    def load(self, path):
+        """rtlfm_gpu_load: the reverse, into a handle of the same stream count and configuration (max_blocks and
+        report_levels may differ); a file that does not fit or is damaged changes nothing (RtlfmError)."""
+        check(self.lib.rtlfm_gpu_load(self._h, os.fsencode(path)), "rtlfm_gpu_load")
 
     def reset(self):
         check(self.lib.rtlfm_gpu_reset(self._h), "rtlfm_gpu_reset")
