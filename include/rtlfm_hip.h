@@ -375,6 +375,50 @@ int rtlfm_gpu_state_move(rtlfm_gpu *dst, rtlfm_gpu *src, const int32_t *map, int
 int rtlfm_gpu_save(rtlfm_gpu *h, const char *path);
 int rtlfm_gpu_load(rtlfm_gpu *h, const char *path);
 
+/*
+ * Channels: K demodulated channels per wideband source through one NCO front end.
+ *
+ * The reference tunes one dongle to one channel; its only frequency translation is rotate16_neg90 (src/rtl_fm.c:424-434),
+ * fs/4 and fixed.  With channels on, stream s of the handle is channel s % per_source of SOURCE s / per_source, and the
+ * rotation's place is taken by a mixer with a per-stream step.  Integer and bit-exact everywhere:
+ *   table    1024 entries, Q14: c[i] = lround(16384 cos(2 pi i / 1024)), s[i] the same of sin, in double (rtlfm_channel_table)
+ *   phase    sample n of a run: (uint32)((pos + n) * step), table index = phase >> 22; pos = complex samples the handle
+ *            has consumed since rtlfm_gpu_set_channels / rtlfm_gpu_reset / rtlfm_gpu_channels_seek - one counter per
+ *            handle, the streams run in lockstep; all of it modulo 2^32
+ *   mixer    x = I - 127, y = Q - 127 (rtlsdr_callback, src/rtl_fm.c:1326-1328):
+ *            I' = (x c + y s + 8192) >> 14,  Q' = (y c - x s + 8192) >> 14: multiplication by e^(-j theta).
+ *            step = 2^30 is rotate16_neg90's 1, -j, -1, +j to the bit, step = 0 the identity (offset_tuning = 1)
+ *   step     rtlfm_channel_step(shift_hz, capture_rate) = (uint32) round_half_up(shift_hz 2^32 / capture_rate), in
+ *            integers; 0 for capture_rate == 0.  shift_hz = channel_freq - capture_freq: how far ABOVE the frequency the
+ *            source is tuned to the channel lies (a carrier at +shift_hz in the capture comes to rest at 0).  rtl_fm's
+ *            own tuning (capture_freq = freq - capture_rate / 4, src/rtl_fm.c:1423-1428, rtlfm_optimal_settings) puts its
+ *            one channel at +capture_rate / 4 -> 2^30: the reference's own chain, its sign convention
+ * Behind the mixer the chain is the stream's own, unchanged: low_pass or fifth_order (+ generic_fir) on I', Q' with the
+ * stream's carried state, then the squelch, -L levels (rtlfm_gpu_levels*), every -M mode and every audio tail;
+ * rtlfm_gpu_state_get / _set(_all) and rtlfm_gpu_set_path work per channel as they do per stream.
+ *
+ * rtlfm_gpu_set_channels: per_source >= 1 must divide the handle's stream count (-EINVAL), steps[nstreams] is copied;
+ * per_source == 0 switches channels off (steps may be NULL).  Sets pos = 0.  Waits for what the handle has queued.
+ * While channels are on, rtlfm_gpu_run_device
+ *   - reads d_iq as nstreams / per_source rows, stream_stride apart: one per source;
+ *   - ignores cfg.offset_tuning;
+ *   - adds nblocks * block_len / 2 to pos once per successful run (also under verify_twice, whose two executions use
+ *     the same pos);
+ *   - takes the boxcar (downsample_passes == 0, rtl_fm's default decimator) through ONE launch from source bytes to
+ *     every channel's decimated IQ (k_channel_boxcar; rtlfm_gpu_last_path says 2), everything else through the staged
+ *     kernels behind k_channel_mix (1); rtlfm_gpu_set_path(1) forces the latter, 2 with fifth_order passes is -ENOTSUP.
+ * What reads or owns per-STREAM input rows, or would lose pos, is refused with -ENOTSUP and changes nothing while
+ * channels are on: rtlfm_gpu_push / _acquire / _commit / _run / _run_begin (the ring), the options input_stats,
+ * input_health and squelch_gate, rtlfm_gpu_mute, rtlfm_gpu_save / _load / _state_move; and rtlfm_gpu_set_channels itself
+ * on a handle with cfg.dc_block_raw or one of those options on (-EBUSY with a run begun, a ring slot open or a mute owed).
+ * rtlfm_gpu_channels_seek / _tell: set / read pos (a caller that resumes a recording sets where it is).
+ */
+uint32_t rtlfm_channel_step(int32_t shift_hz, uint32_t capture_rate);
+int rtlfm_channel_table(int16_t *cos_sin /* [1024][2] */);
+int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32_t *steps /* [nstreams] */);
+int rtlfm_gpu_channels_seek(rtlfm_gpu *h, uint64_t pos);
+int rtlfm_gpu_channels_tell(rtlfm_gpu *h, uint64_t *pos);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,

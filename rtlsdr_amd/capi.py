@@ -311,6 +311,11 @@ _SIGNATURES = [
     ("rtlfm_gpu_state_move", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("rtlfm_gpu_save", C.c_int, [C.c_void_p, C.c_char_p]),
     ("rtlfm_gpu_load", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rtlfm_channel_step", C.c_uint32, [C.c_int32, C.c_uint32]),
+    ("rtlfm_channel_table", C.c_int, [C.c_void_p]),
+    ("rtlfm_gpu_set_channels", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    ("rtlfm_gpu_channels_seek", C.c_int, [C.c_void_p, C.c_uint64]),
+    ("rtlfm_gpu_channels_tell", C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     ("rtlfm_gpu_sync", C.c_int, [C.c_void_p]),
     ("rtlfm_gpu_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtlfm_gpu_wait_for", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -31,6 +31,7 @@
 #include "input_health_kernel.h"
 #include "scan_kernel.h"
 #include "state_kernel.h"
+#include "channel_kernel.h"
 #include "../../include/rtlfm_snapshot.h"
 
 using namespace rtlfm;
@@ -113,6 +114,13 @@ struct rtlfm_gpu {
 	scan::MuteEntry *d_mute_entries = nullptr;
 	size_t mute_entries_cap = 0;
 	int32_t *d_move_map = nullptr;         // [nstreams]: rtlfm_gpu_state_move's map on the device, allocated by the first move into this handle
+	// channels (channel_kernel.h; rtlfm_gpu_set_channels): stream s = channel s % chan_per of source s / chan_per
+	int chan_per = 0;                      // 0: off
+	uint64_t chan_pos = 0;                 // complex samples consumed since set_channels / reset / seek: ONE counter, the streams run in lockstep
+	uint32_t *d_chan_steps = nullptr;      // [nstreams]
+	uint32_t *d_chan_table = nullptr;      // [channel::kTableSize], uploaded by the first set_channels
+	uint32_t *chan_iq = nullptr;           // what k_channel_boxcar leaves for the back half: [nstreams][chan_stride] decimated IQ
+	size_t chan_stride = 0;
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -507,7 +515,8 @@ static int ensure_res_buffers(rtlfm_gpu *h, const uint8_t *d_iq = nullptr, size_
 // bytes of the caller's input a run really covers: (S - 1) strides + the last stream's buffers (the stride may be padded)
 static inline size_t iq_extent(const rtlfm_gpu *h, size_t stream_stride, int nblocks)
 {
-	return (size_t)(h->nstreams - 1) * stream_stride + (size_t)nblocks * h->cfg.block_len;
+	const int rows = h->chan_per > 0 ? h->nstreams / h->chan_per : h->nstreams;  // (channels on: one row per SOURCE)
+	return (size_t)(rows - 1) * stream_stride + (size_t)nblocks * h->cfg.block_len;
 }
 
 extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
@@ -524,7 +533,7 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
 	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth,
-	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map};
+	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	delete[] h->mute_left;
@@ -554,6 +563,7 @@ extern "C" int rtlfm_gpu_reset(rtlfm_gpu *h)
 	HIP_TRY(sync_all(h));
 	HIP_TRY(hipMemcpy(h->st[h->st_cur], init.data(), init.size() * sizeof(state_t), hipMemcpyHostToDevice));
 	ingest_reset(h);
+	h->chan_pos = 0;
 	return 0;
 }
 
@@ -623,6 +633,7 @@ static int set_mutes(rtlfm_gpu *h, const uint32_t *mutes)
 extern "C" int rtlfm_gpu_state_move(rtlfm_gpu *dst, rtlfm_gpu *src, const int32_t *map, int n)
 {
 	if (!dst || !src || !map || n != dst->nstreams) return -EINVAL;
+	if (dst->chan_per > 0 || src->chan_per > 0) return -ENOTSUP;  // (channels: the record does not hold pos)
 	for (int k = 0; k < n; k++)
 		if (map[k] < -1 || map[k] >= src->nstreams) return -EINVAL;
 	if (dst->device != src->device) return -EXDEV;
@@ -662,6 +673,7 @@ static bool same_carried_cfg(rtlfm_cfg a, const rtlfm_cfg &b)
 extern "C" int rtlfm_gpu_save(rtlfm_gpu *h, const char *path)
 {
 	if (!h || !path) return -EINVAL;
+	if (h->chan_per > 0) return -ENOTSUP;  // (channels: a snapshot does not hold pos)
 	std::vector<state_t> st;
 	std::vector<uint32_t> mutes;
 	try {
@@ -680,6 +692,7 @@ extern "C" int rtlfm_gpu_save(rtlfm_gpu *h, const char *path)
 extern "C" int rtlfm_gpu_load(rtlfm_gpu *h, const char *path)
 {
 	if (!h || !path) return -EINVAL;
+	if (h->chan_per > 0) return -ENOTSUP;
 	rtlfm_cfg cfg;
 	int n = 0;
 	int r = rtlfm_snapshot_info(path, &cfg, &n);  // (checks the whole file, the checksum included)
@@ -699,6 +712,64 @@ extern "C" int rtlfm_gpu_load(rtlfm_gpu *h, const char *path)
 	if (got != n) return -EILSEQ;  // (the file changed between the two reads)
 	if ((r = rtlfm_gpu_state_set_all(h, st.data(), n)) < 0) return r;
 	return set_mutes(h, mutes.data());
+}
+
+// ---- channels: K channels per wideband source (include/rtlfm_hip.h, channel_kernel.h) ----
+
+extern "C" uint32_t rtlfm_channel_step(int32_t shift_hz, uint32_t capture_rate)
+{
+	if (!capture_rate) return 0;
+	// round_half_up(shift * 2^32 / rate) = floor((2 shift 2^32 + rate) / (2 rate)), exactly; the result modulo 2^32
+	const __int128 a = (((__int128)shift_hz) << 33) + (__int128)capture_rate, b = 2 * (__int128)capture_rate;
+	__int128 quo = a / b;
+	if (a % b < 0) quo -= 1;  // C truncates towards zero
+	return (uint32_t)(unsigned __int128)quo;
+}
+
+extern "C" int rtlfm_channel_table(int16_t *cos_sin)
+{
+	if (!cos_sin) return -EINVAL;
+	channel::build_table(cos_sin);
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32_t *steps)
+{
+	if (!h || per_source < 0) return -EINVAL;
+	if (per_source > 0 && (!steps || h->nstreams % per_source)) return -EINVAL;
+	if (ingest_busy(h) || h->mute_streams > 0) return -EBUSY;
+	if (per_source > 0 && (h->cfg.dc_block_raw || h->opt.input_stats || h->opt.input_health || h->opt.squelch_gate)) return -ENOTSUP;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (per_source > 0) {
+		if (!h->d_chan_table) {
+			std::vector<int16_t> tab(2 * channel::kTableSize);
+			channel::build_table(tab.data());  // (int16 cos, int16 sin = the kernels' packed dword)
+			uint32_t *d = nullptr;
+			HIP_TRY(hipMalloc(&d, channel::kTableSize * sizeof(uint32_t)));
+			if (hipMemcpy(d, tab.data(), channel::kTableSize * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return -EIO; }
+			h->d_chan_table = d;
+		}
+		if (!h->d_chan_steps) HIP_TRY(hipMalloc(&h->d_chan_steps, (size_t)h->nstreams * sizeof(uint32_t)));
+		HIP_TRY(hipMemcpy(h->d_chan_steps, steps, (size_t)h->nstreams * sizeof(uint32_t), hipMemcpyHostToDevice));
+	}
+	h->chan_per = per_source;
+	h->chan_pos = 0;
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_channels_seek(rtlfm_gpu *h, uint64_t pos)
+{
+	if (!h) return -EINVAL;
+	h->chan_pos = pos;  // (read by the next run's launch; runs already queued took theirs by value)
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_channels_tell(rtlfm_gpu *h, uint64_t *pos)
+{
+	if (!h || !pos) return -EINVAL;
+	*pos = h->chan_pos;
+	return 0;
 }
 
 extern "C" int rtlfm_gpu_sync(rtlfm_gpu *h)
@@ -818,6 +889,9 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 	}
 	int *slot = option_slot(h, name);
 	if (!slot) return -ENOENT;
+	// channels on: what reads or owns per-STREAM input rows stays off (rtlfm_gpu_set_channels)
+	if (h->chan_per > 0 && value != 0 && (!strcmp(name, "input_stats") || !strcmp(name, "input_health") || !strcmp(name, "squelch_gate")))
+		return -ENOTSUP;
 	// every range check first: a refused value must leave the handle as it was
 	if ((!strcmp(name, "fused_waves") || !strcmp(name, "fused_waves_tail")) && value < 1) return -EINVAL;
 	if (!strcmp(name, "pass0_engine") && (value < -1 || value > 1)) return -EINVAL;
@@ -1565,9 +1639,14 @@ static int run_staged(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, i
 		                                           h->d_rdc_avg);
 		rdc = h->d_rdc_avg;
 	}
-	k_convert<<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S,
-	                                                                  h->bufA, h->xstride,
-	                                                                  c.offset_tuning ? 0 : 1, rdc);
+	if (h->chan_per > 0)  // channels: the NCO mixer in rotate16_neg90's place, the source's row in the stream's
+		channel::k_channel_mix<<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S, h->chan_per,
+		                                                                               h->d_chan_steps, h->d_chan_table,
+		                                                                               (uint32_t)h->chan_pos, h->bufA, h->xstride);
+	else
+		k_convert<<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S,
+		                                                                  h->bufA, h->xstride,
+		                                                                  c.offset_tuning ? 0 : 1, rdc);
 	uint32_t *cur = h->bufA, *oth = h->bufB;
 	// --- decimation (src/rtl_fm.c:1187-1202)
 	int T;          // decimated complex samples per stream (upper bound if varcnt)
@@ -1886,6 +1965,54 @@ static int run_boxfused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_st
 	return run_back_half(h, h->deepA, h->deep_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
 }
 
+// Channels on, the boxcar: k_channel_boxcar takes the source bytes to every channel's decimated IQ in one launch
+// (channel_kernel.h), then full_demod() goes on as behind low_pass() (run_back_half).  -M raw without the squelch: what
+// the launch leaves IS the output and goes straight into the caller's rows, as run_boxfused_emit's.
+static int run_channels(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
+                        size_t out_stride, int32_t *d_out_len)
+{
+	const rtlfm_cfg &c = h->cfg;
+	const int S = h->nstreams;
+	hipStream_t q = h->stream;
+	const int N0 = (int)(c.block_len / 2), D = c.downsample;
+	const int Tin = nblocks * N0;
+	const bool varcnt = (N0 % D) != 0;
+	const int T = varcnt ? Tin / D + 1 : Tin / D;
+	// (a row the launch writes has one spare dword behind its last possible output: channel_kernel.h)
+	const bool raw_direct = c.mode == RTLFM_MODE_RAW && !c.squelch_level && !c.report_levels && out_stride / 2 >= (size_t)Tin / D + 2;
+	if (!raw_direct && !h->chan_iq) {
+		h->chan_stride = (((size_t)h->cap_blocks * N0) / D + 1 + 16 + 3) & ~(size_t)3;  // rows start on 16-byte lines
+		HIP_TRY(hipMalloc(&h->chan_iq, (size_t)S * h->chan_stride * sizeof(uint32_t)));
+	}
+	TailPlan tp = plan_tail(h, nblocks);
+	int r;
+	if (!raw_direct && tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
+	channel::BoxParams p{};
+	p.iq = d_iq; p.src_stride = stream_stride;
+	p.steps = h->d_chan_steps; p.table = h->d_chan_table;
+	p.pos = (uint32_t)h->chan_pos;
+	p.T = Tin; p.D = D;
+	p.per_source = h->chan_per; p.groups = (h->chan_per + channel::kWaves - 1) / channel::kWaves;
+	p.ntiles = (Tin + channel::kTileSamples - 1) / channel::kTileSamples;
+	channel::plan(S, p.ntiles, D, tp.any() ? h->fws.target_waves_tail : h->fws.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg,
+	              &p.segs, &p.tiles_per_seg);
+	p.Y = raw_direct ? reinterpret_cast<uint32_t *>(d_out) : h->chan_iq;
+	p.ystride = raw_direct ? out_stride / 2 : h->chan_stride;
+	p.maxout = Tin / D + 1;
+	int32_t *dcnt = h->d_cnt[h->step & 1];
+	p.cnt = dcnt;
+	p.sin = h->st[h->st_cur]; p.sout = h->st[(h->st_cur + 1) % 3];
+	const size_t grid = (size_t)(S / h->chan_per) * p.segs * p.groups;
+	if (grid > 0x7fffffffu) return -E2BIG;
+	std::pair<hipEvent_t, hipEvent_t> ev;
+	if ((r = timing_begin(h, ev)) < 0) return r;
+	if (D >= channel::kStageMinD) channel::k_channel_boxcar<true><<<(unsigned)grid, channel::kWaves * 64, 0, q>>>(p);
+	else channel::k_channel_boxcar<false><<<(unsigned)grid, channel::kWaves * 64, 0, q>>>(p);
+	if ((r = timing_end(h, ev)) < 0) return r;
+	if (raw_direct) return raw_out_len(h, d_out_len, varcnt ? dcnt : nullptr, T);
+	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
+}
+
 static int ensure_input_stats(rtlfm_gpu *h)
 {
 	if (!h->d_istats)
@@ -1977,6 +2104,19 @@ static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 			HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_tail[par], 0));
 			h->tail_pending[par] = false;
 		}
+	}
+	if (h->chan_per > 0) {
+		// Channels on: the boxcar has the one-launch front end; every other decimator runs staged behind k_channel_mix.
+		// (Both leave the other fields of the record to the copy, as the staged kernels always do.)
+		const bool boxed = h->path != 1 && h->cfg.downsample_passes == 0;
+		if (h->path == 2 && !boxed) return -ENOTSUP;
+		HIP_TRY(hipMemcpyAsync(h->st[(h->st_cur + 1) % 3], h->st[h->st_cur], S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
+		r = boxed ? run_channels(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
+		          : run_staged(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
+		if (r < 0) return r;
+		h->last_path = boxed ? 2 : 1;
+		HIP_TRY(hipGetLastError());
+		return 0;
 	}
 	if (h->path == 2 && !can_fuse && !can_box && !can_box_emit && !can_deep) return -ENOTSUP;
 	// the callback's ADC statistics (src/rtl_fm.c:1302-1324) come before the conversion: in front of whichever front end runs
@@ -2129,6 +2269,7 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	if (r < 0) return r;
 	h->st_cur = (h->st_cur + 1) % 3;
 	h->step++;
+	if (h->chan_per > 0) h->chan_pos += (uint64_t)nblocks * (h->cfg.block_len / 2);  // (once per run, also under verify_twice)
 	h->last_nblocks = nblocks;
 	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
 	h->health_nblocks = h->opt.input_health ? nblocks : 0;
@@ -2247,6 +2388,7 @@ extern "C" int rtlfm_gpu_input_health_stats_device(int device, const uint8_t *d_
 extern "C" int rtlfm_gpu_mute(rtlfm_gpu *h, int stream, uint32_t nbytes)
 {
 	if (!h || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (h->chan_per > 0) return -ENOTSUP;  // (channels: the mute counts a stream's own input bytes)
 	if (!h->mute_left) {
 		if (!nbytes) return 0;
 		h->mute_left = new (std::nothrow) uint32_t[(size_t)h->nstreams]();
@@ -2503,6 +2645,7 @@ static bool ingest_busy(rtlfm_gpu *h)
 extern "C" int rtlfm_gpu_push(rtlfm_gpu *h, int stream, const uint8_t *iq, uint32_t len)
 {
 	if (!h || !iq || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (h->chan_per > 0) return -ENOTSUP;  // (channels: the ring's rows are per stream)
 	// actual_length of a bulk transfer: whole 512-byte USB packets, at most the buffer
 	if (len == 0 || len > h->cfg.block_len || len % 512) return -EINVAL;
 	if (len != h->cfg.block_len) {
@@ -2542,6 +2685,7 @@ extern "C" int rtlfm_gpu_push(rtlfm_gpu *h, int stream, const uint8_t *iq, uint3
 extern "C" int rtlfm_gpu_acquire(rtlfm_gpu *h, int stream, uint8_t **buf, uint32_t *cap)
 {
 	if (!h || !buf || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (h->chan_per > 0) return -ENOTSUP;
 	int r = ingest_ensure(h);
 	if (r < 0) return r;
 	Ingest *in = h->ing;
@@ -2559,6 +2703,7 @@ extern "C" int rtlfm_gpu_acquire(rtlfm_gpu *h, int stream, uint8_t **buf, uint32
 extern "C" int rtlfm_gpu_commit(rtlfm_gpu *h, int stream, uint32_t len)
 {
 	if (!h || stream < 0 || stream >= h->nstreams) return -EINVAL;
+	if (h->chan_per > 0) return -ENOTSUP;
 	Ingest *in = h->ing;
 	if (!in) return -EINVAL;
 	std::shared_lock<std::shared_mutex> g(in->mu);
@@ -2745,6 +2890,7 @@ static int apply_mute(rtlfm_gpu *h, Ingest *in, int f, int nb)
 extern "C" int rtlfm_gpu_run_begin(rtlfm_gpu *h, int *taken)
 {
 	if (!h) return -EINVAL;
+	if (h->chan_per > 0) return -ENOTSUP;  // (so rtlfm_gpu_run: it begins here)
 	int r = ingest_ensure(h);
 	if (r < 0) return r;
 	Ingest *in = h->ing;

@@ -29,6 +29,7 @@ class GpuDemod:
         h = C.c_void_p()
         check(self.lib.rtlfm_gpu_create(C.byref(cfg), nstreams, device, C.byref(h)), "rtlfm_gpu_create")
         self._h = h
+        self._per_source = 0  # channels (set_channels): 0 = off
         for k, v in (options or {}).items():
             self.set_option(k, v)
         # the scanner's squelch gate (include/rtlfm_hip.h, rtlfm_gpu_gate): off unless asked for
@@ -121,7 +122,8 @@ class GpuDemod:
         results can be used from torch without ``sync()`` and the caching allocator cannot hand
         ``out`` to someone else while the kernels still write it.  ``run_device`` does neither."""
         import torch
-        assert iq.dtype == torch.uint8 and iq.is_cuda and iq.dim() == 2 and iq.shape[0] == self.nstreams
+        rows = self.nstreams // self._per_source if self._per_source else self.nstreams  # channels on: one row per source
+        assert iq.dtype == torch.uint8 and iq.is_cuda and iq.dim() == 2 and iq.shape[0] == rows
         assert iq.stride(1) == 1
         L = int(self.cfg.block_len)
         nb = iq.shape[1] // L
@@ -200,6 +202,35 @@ class GpuDemod:
     def mute(self, stream: int, nbytes: int):
         """rtlfm_gpu_mute: the next ``nbytes`` that ``stream`` hands over read as 127 (the callback's mute after a retune)."""
         check(self.lib.rtlfm_gpu_mute(self._h, stream, int(nbytes)), "rtlfm_gpu_mute")
+
+    # -- channels: K channels per wideband source ------------------------------------
+    def set_channels(self, per_source: int, steps=None, shifts_hz=None, capture_rate: int | None = None):
+        """rtlfm_gpu_set_channels: stream s becomes channel ``s % per_source`` of source ``s // per_source``, mixed down by
+        ``steps[s]`` (uint32 phase steps), or by ``channel_step(shifts_hz[s], capture_rate)`` with
+        ``shifts_hz[s] = channel_freq - capture_freq`` (how far above the sources' tuned frequency the channel lies).  ``per_source = 0`` switches channels off.  While they are on,
+        ``run_torch`` / ``run_device`` take ``nstreams // per_source`` input rows (include/rtlfm_hip.h has the rest)."""
+        if per_source == 0:
+            check(self.lib.rtlfm_gpu_set_channels(self._h, 0, None), "rtlfm_gpu_set_channels")
+            self._per_source = 0
+            return
+        if steps is None:
+            if shifts_hz is None or capture_rate is None:
+                raise ValueError("set_channels needs steps, or shifts_hz and capture_rate")
+            steps = [channel_step(int(f), int(capture_rate)) for f in shifts_hz]
+        st = np.ascontiguousarray(steps, dtype=np.uint32)
+        if st.shape != (self.nstreams,):
+            raise ValueError(f"one step per stream: {self.nstreams}, not {st.shape}")
+        check(self.lib.rtlfm_gpu_set_channels(self._h, int(per_source), st.ctypes.data), "rtlfm_gpu_set_channels")
+        self._per_source = int(per_source)
+
+    def channels_seek(self, pos: int):
+        """rtlfm_gpu_channels_seek: the complex samples the sources have delivered so far (what the NCO phase counts from)."""
+        check(self.lib.rtlfm_gpu_channels_seek(self._h, int(pos)), "rtlfm_gpu_channels_seek")
+
+    def channels_tell(self) -> int:
+        pos = C.c_uint64()
+        check(self.lib.rtlfm_gpu_channels_tell(self._h, C.byref(pos)), "rtlfm_gpu_channels_tell")
+        return pos.value
 
     # -- state & plumbing ------------------------------------------------------
     def state_get(self, stream: int = 0) -> RtlfmStreamState:
@@ -306,3 +337,16 @@ def optimal_settings(cfg: RtlfmCfg, freq: int, rate_in: int, min_capture_rate: i
 
 def deemph_a(rate_out: int, time_constant_us: int = 75) -> int:
     return capi.load().rtlfm_deemph_a(rate_out, time_constant_us)
+
+
+def channel_step(shift_hz: int, capture_rate: int) -> int:
+    """rtlfm_channel_step: the NCO phase step (uint32) that brings a channel ``shift_hz = channel_freq - capture_freq`` above the tuned frequency to rest at
+    ``capture_rate``: round_half_up(shift_hz * 2^32 / capture_rate) modulo 2^32, in integers.  Needs no GPU."""
+    return int(capi.load().rtlfm_channel_step(int(shift_hz), int(capture_rate)))
+
+
+def channel_table() -> np.ndarray:
+    """rtlfm_channel_table: the NCO's table, int16 [1024, 2] = (cos, sin) in Q14.  Needs no GPU."""
+    out = np.zeros((1024, 2), dtype=np.int16)
+    check(capi.load().rtlfm_channel_table(out.ctypes.data), "rtlfm_channel_table")
+    return out
