@@ -419,6 +419,53 @@ int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32_t *steps /
 int rtlfm_gpu_channels_seek(rtlfm_gpu *h, uint64_t pos);
 int rtlfm_gpu_channels_tell(rtlfm_gpu *h, uint64_t *pos);
 
+/*
+ * The channel filter: a caller-supplied FIR in the boxcar's place (csrc/channel_fir_kernel.h).
+ *
+ * A boxcar /D is a sinc whose first sidelobe lies 13 dB down, and a channel cut out of a wideband capture has no tuner
+ * filter in front of it: a neighbour 1.5 channel spacings away folds onto the output at that level.  With a filter set
+ * and channels on, low_pass()'s sum (src/rtl_fm.c:461-481) is replaced; everything behind it stays the stream's chain.
+ * Integers only, one definition for every path:
+ *   m[n]     a channel's mixed I' (or Q') as above, |m| <= 182; n counts the complex samples since the history was last
+ *            cleared, m[n] = 0 for n < 0
+ *   outputs  are due at exactly the samples e at which low_pass() emits one: where the stream's prev_index reaches D =
+ *            cfg.downsample.  prev_index and the count of outputs are kept as the boxcar keeps them; now_r / now_j are
+ *            carried along unchanged and not used
+ *   value    sat16((sum_{j < ntaps} taps[j] m[e - j] + r) >> shift), r = shift ? 1 << (shift - 1) : 0, the shift
+ *            arithmetic, sat16 a clamp to [-32768, 32767].  The sum is an int32 that cannot overflow (the check below),
+ *            so every order of summation gives the same bits.  Taps of D ones with shift 0 are the boxcar.
+ * rtlfm_channel_filter_check (host only, no GPU): -EINVAL unless 1 <= ntaps <= RTLFM_CHANNEL_MAX_TAPS, 0 <= shift <= 30
+ * and taps != NULL; -ERANGE unless 182 sum|taps[j]| + r <= 2^31 - 1.
+ * rtlfm_channel_lowpass (host only, no GPU): a Hamming-windowed sinc in double, cutoff in cycles per capture sample
+ * (0 < cutoff < 0.5, else -EINVAL; D >= 1), normalised to a sum of 1, taps[j] = floor(h[j] D 2^14 + 0.5), *shift = 14: the
+ * boxcar's DC gain D, so squelch levels and every -M mode see the amplitudes they see today.  -ERANGE if a tap does not
+ * fit an int16 or the check fails.
+ * rtlfm_gpu_set_channel_filter: runs the check first; ntaps == 0 removes the filter (the boxcar is back, bit for bit).
+ * -ENOTSUP, changing nothing, on a handle with cfg.downsample_passes > 0 (the filter takes the boxcar's place, not
+ * fifth_order's); -EBUSY while a run is begun and not ended.  May be called with channels off: the taps are kept and act
+ * only while channels are on.  Waits for what the handle has queued.  One filter and one D for all channels.
+ * rtlfm_gpu_get_channel_filter: *ntaps and *shift are always written; the taps are copied if ntaps <= cap, else -ENOBUFS.
+ *
+ * History: what is carried from run to run is every SOURCE's last ntaps - 1 complex samples (the handle keeps 1024) as
+ * raw bytes in a device buffer of the handle - not in rtlfm_stream_state, whose size and snapshot format stay.  The mixer
+ * is a pure function of pos and the bytes: a run mixes what it needs of them again.  A run shorter than the history
+ * shifts it.  It is cleared to bytes 127 (mixed zeros: m[n < 0] = 0) by
+ *   rtlfm_gpu_set_channel_filter   (new taps start from silence),
+ *   rtlfm_gpu_set_channels         (other sources, pos = 0),
+ *   rtlfm_gpu_reset                (with the state records and pos),
+ *   rtlfm_gpu_channels_seek        (the bytes belong to the old position).
+ * Under verify_twice both executions of a run see one pos and one history.
+ * Paths: rtlfm_gpu_set_path(0 / 2) - one launch from source bytes to every channel's decimated IQ (k_channel_fir;
+ * rtlfm_gpu_last_path says 2), the default; (1) - k_channel_mix over the history and the run, then a plain kernel with
+ * one lane per output (the cross-check).  Both read and write the same history: changing the path between two runs
+ * changes no output bit.
+ */
+#define RTLFM_CHANNEL_MAX_TAPS 1024
+int rtlfm_channel_filter_check(const int16_t *taps, int ntaps, int shift);
+int rtlfm_channel_lowpass(int ntaps, double cutoff, int D, int16_t *taps, int *shift);
+int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, int ntaps, int shift);
+int rtlfm_gpu_get_channel_filter(rtlfm_gpu *h, int16_t *taps, int cap, int *ntaps, int *shift);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,

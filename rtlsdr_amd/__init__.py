@@ -7,5 +7,13 @@ of the reference's per-buffer interface (``rtlsdr_callback`` -> ``full_demod``
 """
 from . import capi  # noqa: F401
 
-__all__ = ["capi"]
+
+
+def channel_lowpass(ntaps: int, cutoff: float, D: int):
+    """``(taps, shift)`` of rtlfm_channel_lowpass: a channel filter for ``GpuDemod.set_channel_filter`` (demod.py)."""
+    from .demod import channel_lowpass as make
+    return make(ntaps, cutoff, D)
+
+
+__all__ = ["capi", "channel_lowpass"]
 __version__ = "0.1.0"

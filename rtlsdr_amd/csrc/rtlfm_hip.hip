@@ -32,6 +32,7 @@
 #include "scan_kernel.h"
 #include "state_kernel.h"
 #include "channel_kernel.h"
+#include "channel_fir_kernel.h"
 #include "../../include/rtlfm_snapshot.h"
 
 using namespace rtlfm;
@@ -121,6 +122,15 @@ struct rtlfm_gpu {
 	uint32_t *d_chan_table = nullptr;      // [channel::kTableSize], uploaded by the first set_channels
 	uint32_t *chan_iq = nullptr;           // what k_channel_boxcar leaves for the back half: [nstreams][chan_stride] decimated IQ
 	size_t chan_stride = 0;
+	// the channel filter (channel_fir_kernel.h; rtlfm_gpu_set_channel_filter): acts while channels are on
+	int fir_ntaps = 0, fir_shift = 0;      // 0 taps: none, the boxcar
+	std::vector<int16_t> fir_taps;         // what the getter hands back
+	int16_t *d_fir_taps = nullptr;         // [ntaps], k_channel_fir_plain's
+	uint32_t *d_fir_taps8 = nullptr;       // chanfir::shifted_taps(), k_channel_fir's
+	uint8_t *d_chan_tail[2] = {nullptr, nullptr};  // [nstreams][chanfir::kTail * 2] raw bytes: every SOURCE's last samples; a run reads [chan_tail_cur] and writes the other
+	int chan_tail_cur = 0;
+	uint32_t *chan_fir_x = nullptr;        // path 1: k_channel_mix's samples of the tail and the run, [nstreams][chan_fir_xstride]
+	size_t chan_fir_xstride = 0;
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -533,7 +543,8 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
 	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth,
-	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq};
+	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq,
+	                h->d_fir_taps, h->d_fir_taps8, h->d_chan_tail[0], h->d_chan_tail[1], h->chan_fir_x};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	delete[] h->mute_left;
@@ -554,6 +565,15 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	return 0;
 }
 
+// The channel filter's history - every source's carried bytes - back to 127: mixed zeros, m[n < 0] = 0.  On the handle's
+// stream: behind the runs already queued, in front of the next.
+static int chan_tail_clear(rtlfm_gpu *h)
+{
+	if (!h->d_chan_tail[0]) return 0;
+	HIP_TRY(hipMemsetAsync(h->d_chan_tail[h->chan_tail_cur], 127, (size_t)h->nstreams * chanfir::kTail * 2, h->stream));
+	return 0;
+}
+
 extern "C" int rtlfm_gpu_reset(rtlfm_gpu *h)
 {
 	if (!h) return -EINVAL;
@@ -564,7 +584,7 @@ extern "C" int rtlfm_gpu_reset(rtlfm_gpu *h)
 	HIP_TRY(hipMemcpy(h->st[h->st_cur], init.data(), init.size() * sizeof(state_t), hipMemcpyHostToDevice));
 	ingest_reset(h);
 	h->chan_pos = 0;
-	return 0;
+	return chan_tail_clear(h);
 }
 
 extern "C" int rtlfm_gpu_state_get(rtlfm_gpu *h, int stream, rtlfm_stream_state *st)
@@ -755,13 +775,93 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	}
 	h->chan_per = per_source;
 	h->chan_pos = 0;
-	return 0;
+	return chan_tail_clear(h);
 }
 
 extern "C" int rtlfm_gpu_channels_seek(rtlfm_gpu *h, uint64_t pos)
 {
 	if (!h) return -EINVAL;
 	h->chan_pos = pos;  // (read by the next run's launch; runs already queued took theirs by value)
+	if (!h->d_chan_tail[0]) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	return chan_tail_clear(h);  // (the filter's history belongs to the old position)
+}
+
+// ---- the channel filter: a caller-supplied FIR in the boxcar's place (include/rtlfm_hip.h, channel_fir_kernel.h) ----
+
+extern "C" int rtlfm_channel_filter_check(const int16_t *taps, int ntaps, int shift)
+{
+	if (!taps || ntaps < 1 || ntaps > RTLFM_CHANNEL_MAX_TAPS || shift < 0 || shift > 30) return -EINVAL;
+	long long sum = 0;
+	for (int j = 0; j < ntaps; j++) sum += taps[j] < 0 ? -(long long)taps[j] : (long long)taps[j];
+	const long long r = shift ? 1ll << (shift - 1) : 0;
+	return 182 * sum + r <= 0x7fffffffll ? 0 : -ERANGE;  // |m| <= 182: the int32 sum and its rounding cannot overflow
+}
+
+extern "C" int rtlfm_channel_lowpass(int ntaps, double cutoff, int D, int16_t *taps, int *shift)
+{
+	if (!taps || !shift || ntaps < 1 || ntaps > RTLFM_CHANNEL_MAX_TAPS || D < 1 || !(cutoff > 0.0 && cutoff < 0.5)) return -EINVAL;
+	std::vector<double> hh((size_t)ntaps);
+	const double mid = (ntaps - 1) / 2.0;
+	double sum = 0;
+	for (int j = 0; j < (ntaps + 1) / 2; j++) {  // (one half computed, the other its mirror image: symmetric to the bit)
+		const double x = 2.0 * cutoff * ((double)j - mid);
+		const double sinc = x == 0.0 ? 1.0 : sin(M_PI * x) / (M_PI * x);
+		const double win = ntaps > 1 ? 0.54 - 0.46 * cos(2.0 * M_PI * (double)j / (double)(ntaps - 1)) : 1.0;
+		hh[j] = hh[ntaps - 1 - j] = sinc * win;
+	}
+	for (int j = 0; j < ntaps; j++) sum += hh[j];
+	if (!(fabs(sum) > 0.0)) return -ERANGE;
+	std::vector<int16_t> q((size_t)ntaps);
+	for (int j = 0; j < ntaps; j++) {
+		const double v = floor(hh[j] / sum * (double)D * 16384.0 + 0.5);
+		if (!(v >= -32768.0 && v <= 32767.0)) return -ERANGE;
+		q[j] = (int16_t)v;
+	}
+	const int r = rtlfm_channel_filter_check(q.data(), ntaps, 14);
+	if (r < 0) return r;
+	memcpy(taps, q.data(), (size_t)ntaps * sizeof(int16_t));
+	*shift = 14;
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, int ntaps, int shift)
+{
+	if (!h) return -EINVAL;
+	if (ntaps != 0) {
+		const int r = rtlfm_channel_filter_check(taps, ntaps, shift);
+		if (r < 0) return r;
+	}
+	if (h->cfg.downsample_passes > 0) return -ENOTSUP;  // (the filter takes the boxcar's place, not fifth_order's)
+	if (ingest_busy(h)) return -EBUSY;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (ntaps > 0) {
+		if (!h->d_fir_taps) HIP_TRY(hipMalloc(&h->d_fir_taps, RTLFM_CHANNEL_MAX_TAPS * sizeof(int16_t)));
+		if (!h->d_fir_taps8)
+			HIP_TRY(hipMalloc(&h->d_fir_taps8, (size_t)chanfir::kGroup * chanfir::padded_taps(RTLFM_CHANNEL_MAX_TAPS) * sizeof(int16_t)));
+		for (int i = 0; i < 2; i++)
+			if (!h->d_chan_tail[i]) HIP_TRY(hipMalloc(&h->d_chan_tail[i], (size_t)h->nstreams * chanfir::kTail * 2));
+		std::vector<int16_t> t8((size_t)chanfir::kGroup * chanfir::padded_taps(ntaps));
+		chanfir::shifted_taps(taps, ntaps, t8.data());
+		HIP_TRY(hipMemcpy(h->d_fir_taps, taps, (size_t)ntaps * sizeof(int16_t), hipMemcpyHostToDevice));
+		HIP_TRY(hipMemcpy(h->d_fir_taps8, t8.data(), t8.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+		h->fir_taps.assign(taps, taps + ntaps);
+	} else {
+		h->fir_taps.clear();
+	}
+	h->fir_ntaps = ntaps;
+	h->fir_shift = ntaps > 0 ? shift : 0;
+	return chan_tail_clear(h);
+}
+
+extern "C" int rtlfm_gpu_get_channel_filter(rtlfm_gpu *h, int16_t *taps, int cap, int *ntaps, int *shift)
+{
+	if (!h || !ntaps || !shift || cap < 0 || (cap > 0 && !taps)) return -EINVAL;
+	*ntaps = h->fir_ntaps;  // (written even where the taps do not fit, as rtlfm_gpu_levels' count)
+	*shift = h->fir_shift;
+	if (h->fir_ntaps > cap) return -ENOBUFS;
+	if (h->fir_ntaps > 0) memcpy(taps, h->fir_taps.data(), (size_t)h->fir_ntaps * sizeof(int16_t));
 	return 0;
 }
 
@@ -2013,6 +2113,77 @@ static int run_channels(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride,
 	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
 }
 
+// Channels on with a filter set (rtlfm_gpu_set_channel_filter): the filter in the boxcar's place, then run_back_half() as
+// behind low_pass().  fused: k_channel_fir, one launch from source bytes to decimated IQ; else the cross-check -
+// k_channel_mix over the carried tail and over the run, k_channel_fir_plain, k_channel_tail.  Both read the tail
+// d_chan_tail[chan_tail_cur] and write the other; rtlfm_gpu_run_device changes over once per run.
+static int run_channels_fir(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
+                            size_t out_stride, int32_t *d_out_len)
+{
+	const rtlfm_cfg &c = h->cfg;
+	const int S = h->nstreams;
+	hipStream_t q = h->stream;
+	const int N0 = (int)(c.block_len / 2), D = c.downsample;
+	const int Tin = nblocks * N0;
+	const bool varcnt = (N0 % D) != 0;
+	const int T = varcnt ? Tin / D + 1 : Tin / D;
+	const int nsrc = S / h->chan_per;
+	if (!h->chan_iq) {
+		h->chan_stride = (((size_t)h->cap_blocks * N0) / D + 1 + 16 + 3) & ~(size_t)3;  // (run_channels': one allocation serves both)
+		HIP_TRY(hipMalloc(&h->chan_iq, (size_t)S * h->chan_stride * sizeof(uint32_t)));
+	}
+	if (!fused_path && !h->chan_fir_x) {
+		h->chan_fir_xstride = (size_t)chanfir::kTail + (size_t)h->cap_blocks * N0;
+		HIP_TRY(hipMalloc(&h->chan_fir_x, (size_t)S * h->chan_fir_xstride * sizeof(uint32_t)));
+	}
+	TailPlan tp = plan_tail(h, nblocks);
+	int r;
+	if (tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
+	const uint8_t *tail_in = h->d_chan_tail[h->chan_tail_cur];
+	uint8_t *tail_out = h->d_chan_tail[h->chan_tail_cur ^ 1];
+	int32_t *dcnt = h->d_cnt[h->step & 1];
+	const state_t *sin = h->st[h->st_cur];
+	state_t *sout = h->st[(h->st_cur + 1) % 3];
+	const int maxout = Tin / D + 1;
+	std::pair<hipEvent_t, hipEvent_t> ev;
+	if (fused_path) {
+		chanfir::FirParams p{};
+		p.iq = d_iq; p.src_stride = stream_stride;
+		p.tail_in = tail_in; p.tail_out = tail_out;
+		p.steps = h->d_chan_steps; p.table = h->d_chan_table; p.taps8 = h->d_fir_taps8;
+		p.pos = (uint32_t)h->chan_pos;
+		p.T = Tin; p.D = D;
+		p.ntaps = h->fir_ntaps; p.nt8 = chanfir::padded_taps(h->fir_ntaps); p.halo = chanfir::halo_of(h->fir_ntaps); p.shift = h->fir_shift;
+		p.maxout = maxout;
+		p.per_source = h->chan_per; p.groups = (h->chan_per + chanfir::kWaves - 1) / chanfir::kWaves;
+		p.ntiles = (Tin + chanfir::kTile - 1) / chanfir::kTile;
+		// (kMaxD's limit is the boxcar's warm-up tile; here every D goes with every segmentation: D = 1 for the plan)
+		channel::plan(S, p.ntiles, 1, tp.any() ? h->fws.target_waves_tail : h->fws.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg,
+		              &p.segs, &p.tiles_per_seg);
+		p.Y = h->chan_iq; p.ystride = h->chan_stride;
+		p.cnt = dcnt; p.sin = sin; p.sout = sout;
+		const size_t grid = (size_t)nsrc * p.segs * p.groups;
+		if (grid > 0x7fffffffu) return -E2BIG;
+		if ((r = timing_begin(h, ev)) < 0) return r;
+		chanfir::k_channel_fir<<<(unsigned)grid, chanfir::kWaves * 64, chanfir::lds_bytes(h->fir_ntaps), q>>>(p);
+		if ((r = timing_end(h, ev)) < 0) return r;
+	} else {
+		if ((r = timing_begin(h, ev)) < 0) return r;
+		channel::k_channel_mix<<<grid_for((size_t)S * (chanfir::kTail / 8)), 256, 0, q>>>(
+			tail_in, (size_t)chanfir::kTail * 2, (uint32_t)chanfir::kTail * 2, 1, S, h->chan_per, h->d_chan_steps, h->d_chan_table,
+			(uint32_t)h->chan_pos - (uint32_t)chanfir::kTail, h->chan_fir_x, h->chan_fir_xstride);
+		channel::k_channel_mix<<<grid_for((size_t)S * nblocks * (c.block_len / 16)), 256, 0, q>>>(
+			d_iq, stream_stride, c.block_len, nblocks, S, h->chan_per, h->d_chan_steps, h->d_chan_table, (uint32_t)h->chan_pos,
+			h->chan_fir_x + chanfir::kTail, h->chan_fir_xstride);
+		chanfir::k_channel_fir_plain<<<grid_for((size_t)S * maxout), 256, 0, q>>>(h->chan_fir_x, h->chan_fir_xstride, S, Tin, D, h->d_fir_taps,
+		                                                                       h->fir_ntaps, h->fir_shift, maxout, h->chan_iq,
+		                                                                       h->chan_stride, dcnt, sin, sout);
+		chanfir::k_channel_tail<<<grid_for((size_t)nsrc * (chanfir::kTail / 8)), 256, 0, q>>>(d_iq, stream_stride, tail_in, tail_out, nsrc, Tin);
+		if ((r = timing_end(h, ev)) < 0) return r;
+	}
+	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
+}
+
 static int ensure_input_stats(rtlfm_gpu *h)
 {
 	if (!h->d_istats)
@@ -2111,7 +2282,9 @@ static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		const bool boxed = h->path != 1 && h->cfg.downsample_passes == 0;
 		if (h->path == 2 && !boxed) return -ENOTSUP;
 		HIP_TRY(hipMemcpyAsync(h->st[(h->st_cur + 1) % 3], h->st[h->st_cur], S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
-		r = boxed ? run_channels(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
+		// (a filter is only ever set on a handle without fifth_order passes: with it, both paths are the filter's)
+		r = h->fir_ntaps > 0 ? run_channels_fir(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
+		  : boxed ? run_channels(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
 		          : run_staged(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
 		if (r < 0) return r;
 		h->last_path = boxed ? 2 : 1;
@@ -2270,6 +2443,7 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	h->st_cur = (h->st_cur + 1) % 3;
 	h->step++;
 	if (h->chan_per > 0) h->chan_pos += (uint64_t)nblocks * (h->cfg.block_len / 2);  // (once per run, also under verify_twice)
+	if (h->chan_per > 0 && h->fir_ntaps > 0) h->chan_tail_cur ^= 1;  // (the same: both executions read one tail and wrote the other)
 	h->last_nblocks = nblocks;
 	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
 	h->health_nblocks = h->opt.input_health ? nblocks : 0;

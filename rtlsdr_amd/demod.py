@@ -232,6 +232,23 @@ class GpuDemod:
         check(self.lib.rtlfm_gpu_channels_tell(self._h, C.byref(pos)), "rtlfm_gpu_channels_tell")
         return pos.value
 
+    def set_channel_filter(self, taps=None, shift: int = 0):
+        """rtlfm_gpu_set_channel_filter: int16 ``taps`` and ``shift`` in the boxcar's place while channels are on -
+        ``sat16((sum taps[j] m[e - j] + r) >> shift)`` at the samples the boxcar emits at (``channel_lowpass`` makes a
+        set).  ``None`` or no taps removes the filter.  Clears the filter's history."""
+        t = np.ascontiguousarray([] if taps is None else taps, dtype=np.int16)
+        if t.ndim != 1:
+            raise ValueError("taps: one dimension")
+        check(self.lib.rtlfm_gpu_set_channel_filter(self._h, t.ctypes.data if t.size else None, int(t.size), int(shift) if t.size else 0),
+              "rtlfm_gpu_set_channel_filter")
+
+    def channel_filter(self):
+        """rtlfm_gpu_get_channel_filter: ``(taps, shift)`` as set; ``(empty, 0)`` without a filter."""
+        out = np.zeros(capi.CHANNEL_MAX_TAPS, dtype=np.int16)
+        n, sh = C.c_int(), C.c_int()
+        check(self.lib.rtlfm_gpu_get_channel_filter(self._h, out.ctypes.data, out.size, C.byref(n), C.byref(sh)), "rtlfm_gpu_get_channel_filter")
+        return out[:n.value].copy(), sh.value
+
     # -- state & plumbing ------------------------------------------------------
     def state_get(self, stream: int = 0) -> RtlfmStreamState:
         st = RtlfmStreamState()
@@ -343,6 +360,15 @@ def channel_step(shift_hz: int, capture_rate: int) -> int:
     """rtlfm_channel_step: the NCO phase step (uint32) that brings a channel ``shift_hz = channel_freq - capture_freq`` above the tuned frequency to rest at
     ``capture_rate``: round_half_up(shift_hz * 2^32 / capture_rate) modulo 2^32, in integers.  Needs no GPU."""
     return int(capi.load().rtlfm_channel_step(int(shift_hz), int(capture_rate)))
+
+
+def channel_lowpass(ntaps: int, cutoff: float, D: int):
+    """rtlfm_channel_lowpass: ``(taps, shift)`` of a Hamming-windowed sinc with ``cutoff`` in cycles per capture sample and
+    the boxcar's DC gain ``D`` (int16 taps, shift 14).  Needs no GPU."""
+    out = np.zeros(max(int(ntaps), 1), dtype=np.int16)
+    sh = C.c_int()
+    check(capi.load().rtlfm_channel_lowpass(int(ntaps), float(cutoff), int(D), out.ctypes.data, C.byref(sh)), "rtlfm_channel_lowpass")
+    return out, sh.value
 
 
 def channel_table() -> np.ndarray:
