@@ -466,6 +466,62 @@ int rtlfm_channel_lowpass(int ntaps, double cutoff, int D, int16_t *taps, int *s
 int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, int ntaps, int shift);
 int rtlfm_gpu_get_channel_filter(rtlfm_gpu *h, int16_t *taps, int cap, int *ntaps, int *shift);
 
+/*
+ * The channel bank: uniformly spaced channels by polyphase sums and one fix_fft (DESIGN.md section 8.5,
+ * csrc/channel_bank_kernel.h).
+ *
+ * The mixer paths pay for every source sample once per channel.  Where the channels are spaced fs / K apart the mixer
+ * bank collapses: group the filter's taps by n mod K - K polyphase sums per output instant - and apply one K-point
+ * transform; bin k is the channel at +k fs / K.  The work per source sample no longer grows with K.  The transform is
+ * rtl_power's fix_fft (src/rtl_power.c:271-327), which the project already runs bit for bit on the device.  Integers
+ * only, one definition for every path:
+ *   K, taps  K = 2^m, 2 <= m <= 8; taps[ntaps] int16, 1 <= ntaps <= RTLFM_BANK_MAX_TAPS; 0 <= shift <= 30; D =
+ *            cfg.downsample, any D (it need not relate to K)
+ *   bins     bins[per_source], each in [0, K), duplicates allowed: channel c of every source is bin bins[c].  NULL is
+ *            the identity and needs per_source == K
+ *   x[n]     (I - 127, Q - 127) of the source; n is absolute, pos (rtlfm_gpu_channels_tell) + the index within the run;
+ *            x = 0 before the point where the bank's history was last cleared
+ *   outputs  are due at the samples e at which low_pass() emits one, as for the channel filter - here with ONE schedule per
+ *            source, taken from the prev_index of the source's channel 0; a run writes the new prev_index and the count
+ *            to every channel of the source.  now_r / now_j are copied, not used
+ *   sums     per component, r = 0 .. K - 1: u_r = sum over j < ntaps with (e - j) mod K == r of taps[j] x[e - j]  (K is a
+ *            power of two: (pos + i) & (K - 1) is exact across pos wrapping 2^32);
+ *            v_r = sat16((u_r + rnd) >> shift), rnd = shift ? 1 << (shift - 1) : 0
+ *   Y        = fix_fft(v) exactly as rtl_power defines it with N_WAVE = K: bit reversal, one halving per stage, FIX_MPY
+ *            rounding, int16 wrap on every store, sine_table(m).  Channel c's decimated IQ sample is Y[bins[c]].  A
+ *            carrier k fs / K ABOVE the tuned frequency comes to rest at 0 in bin k (the sign convention of
+ *            rtlfm_channel_step); bins >= K / 2 are the negative shifts
+ * Behind it the stream's chain is unchanged: squelch, -L levels, every -M mode, every audio tail.  The steps given to
+ * rtlfm_gpu_set_channels are kept and not used while the bank is on.
+ * rtlfm_channel_bank_check (host only, no GPU): -EINVAL for a bad K, ntaps or shift or NULL taps; -ERANGE unless
+ * 128 max over branches b of sum_q |taps[b + q K]| + rnd <= 2^31 - 1: u_r is an int32 that cannot overflow, so every order
+ * of summation gives the same bits.  rtlfm_channel_lowpass(ntaps, cutoff, D) with shift = 14 - m gives the boxcar's DC
+ * gain D (the transform halves once per stage: 2^-m).
+ * rtlfm_gpu_set_channel_bank: runs the check first; K == 0 removes the bank (the mixer paths are back, bit for bit).
+ * -EINVAL with channels off or a bin outside [0, K) (or bins == NULL with per_source != K); -ENOTSUP, changing nothing,
+ * with cfg.downsample_passes > 0; -EBUSY while a run is begun and not ended.  Waits for what the handle has queued and
+ * clears the bank's history.  While on, the bank takes precedence over a set channel filter: the filter's taps are kept
+ * and act again once the bank is removed.  rtlfm_gpu_set_channels removes the bank (bins belongs to the old per_source).
+ * rtlfm_gpu_get_channel_bank: *K, *ntaps and *shift are always written (0 without a bank); bins (per_source of them) and
+ * taps are copied if both caps suffice, else -ENOBUFS.
+ *
+ * History: every SOURCE's last 4096 complex samples as raw bytes in two device buffers of the handle: a run reads one
+ * and writes the other, changed over where pos advances - the channel filter's scheme, and separate from it.
+ * rtlfm_stream_state, its size and the snapshot format stay.  Cleared to bytes 127 by rtlfm_gpu_set_channel_bank,
+ * rtlfm_gpu_set_channels, rtlfm_gpu_reset and rtlfm_gpu_channels_seek.  Under verify_twice both executions of a run see
+ * one pos and one history.
+ * Paths: rtlfm_gpu_set_path(0 / 2) - k_channel_bank, one launch from source bytes to every selected channel's decimated
+ * IQ (rtlfm_gpu_last_path says 2), the default; (1) - the plain cross-check: one lane per (frame, residue) forms v in
+ * memory, one lane per frame runs fix_fft in the reference's loop order, a scatter and a history kernel follow.  Both
+ * read and write the same history: changing the path between two runs changes no output bit.
+ * Everything refused while channels are on stays refused; with the bank off no kernel, path or result changes.
+ */
+#define RTLFM_BANK_MAX_TAPS 4096
+int rtlfm_channel_bank_check(int K, const int16_t *taps, int ntaps, int shift);
+int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bins /* [per_source] or NULL */, const int16_t *taps, int ntaps,
+                               int shift);
+int rtlfm_gpu_get_channel_bank(rtlfm_gpu *h, int *K, int32_t *bins, int bins_cap, int16_t *taps, int taps_cap, int *ntaps, int *shift);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,

@@ -15,5 +15,11 @@ def channel_lowpass(ntaps: int, cutoff: float, D: int):
     return make(ntaps, cutoff, D)
 
 
-__all__ = ["capi", "channel_lowpass"]
+def channel_bank_check(K: int, taps, shift: int) -> int:
+    """rtlfm_channel_bank_check for ``GpuDemod.set_channel_bank`` (demod.py): 0 or a negative errno."""
+    from .demod import channel_bank_check as chk
+    return chk(K, taps, shift)
+
+
+__all__ = ["capi", "channel_lowpass", "channel_bank_check"]
 __version__ = "0.1.0"

@@ -17,6 +17,7 @@ RTLFM_MAX_BLOCK_LEN = 262144
 
 MODE_FM, MODE_AM, MODE_USB, MODE_LSB, MODE_RAW = range(5)
 CHANNEL_MAX_TAPS = 1024  # RTLFM_CHANNEL_MAX_TAPS
+BANK_MAX_TAPS = 4096  # RTLFM_BANK_MAX_TAPS
 ATAN_STD, ATAN_FAST, ATAN_LUT = range(3)
 RESAMPLE_LOW_PASS_REAL, RESAMPLE_ARBITRARY = range(2)
 PATH_AUTO, PATH_STAGED, PATH_FUSED = range(3)
@@ -321,6 +322,10 @@ _SIGNATURES = [
     ("rtlfm_channel_lowpass", C.c_int, [C.c_int, C.c_double, C.c_int, C.c_void_p, _P(C.c_int)]),
     ("rtlfm_gpu_set_channel_filter", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("rtlfm_gpu_get_channel_filter", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int), _P(C.c_int)]),
+    ("rtlfm_channel_bank_check", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    ("rtlfm_gpu_set_channel_bank", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ("rtlfm_gpu_get_channel_bank", C.c_int,
+     [C.c_void_p, _P(C.c_int), C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int), _P(C.c_int)]),
     ("rtlfm_gpu_sync", C.c_int, [C.c_void_p]),
     ("rtlfm_gpu_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtlfm_gpu_wait_for", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -1,0 +1,379 @@
+// channel_bank_kernel.h — the channel bank: K uniformly spaced channels of one wideband source by K polyphase sums and one
+// K-point fix_fft per output instant, in the mixer bank's place (include/rtlfm_hip.h, rtlfm_gpu_set_channel_bank;
+// DESIGN.md section 8.5).
+//
+// With x[n] = (I - 127, Q - 127) of the source, n = pos + the index within the run, an output is due at the samples e at
+// which low_pass() (src/rtl_fm.c:461-481) emits one for the source's channel 0, and per component
+//     u_r = sum over j < ntaps with (e - j) mod K == r of taps[j] x[e - j],   v_r = sat16((u_r + rnd) >> shift)
+//     Y   = fix_fft(v) as rtl_power defines it (src/rtl_power.c:271-327) with N_WAVE = K
+// channel c's decimated IQ sample is Y[bins[c]].  u_r is an int32 that cannot overflow (rtlfm_channel_bank_check), so every
+// order of summation gives the same bits; every butterfly is rtlpower::butterfly (fix_fft_butterfly.h), the reference's
+// bit for bit, and the butterflies of one stage are independent of each other.
+//
+// What is carried from run to run is the SOURCE's last kHist complex samples as raw bytes (bytes 127 where nothing has
+// been consumed yet: x = 0), in two copies: a run reads one and writes the other, the handle changes over once per run.
+//
+//   k_channel_bank   the product.  One launch from source bytes to every selected channel's decimated IQ.  A workgroup is
+//                    one source over a stretch of tiles of F output instants ("frames").  Per tile the bytes the frames'
+//                    windows cover are staged in LDS once, as int16 in polyphase order (I and Q apart, the samples of one
+//                    residue contiguous); the taps lie there per branch, reversed, in two copies (one shifted by a sample:
+//                    a window starts on either parity of its row), so that a sum is v_dot2_i32_i16 over pairs.  A lane
+//                    forms one (frame, residue) sum and writes it where fix_fft's bit reversal would put it; a wave then
+//                    runs the log2 K stages over its batch of max(128, K) points (128 / K frames, or one frame with two
+//                    butterflies per lane), leaves the last stage's results in LDS as [bin][frame], and the workgroup
+//                    hands every selected bin's row its stretch of frames as one contiguous piece.
+//   k_bank_sums, k_bank_fft, k_bank_scatter, k_bank_hist
+//                    the cross-check: one lane per (frame, residue) forms v in memory, one lane per frame runs fix_fft in
+//                    the reference's own loop order with FIX_MPY spelled out, a scatter and a history kernel follow.
+#pragma once
+
+#include "channel_kernel.h"
+#include "fix_fft_butterfly.h"
+#include "fused_kernel.h"
+
+namespace rtlfm {
+namespace chanbank {
+
+constexpr int kMaxTaps = RTLFM_BANK_MAX_TAPS;
+constexpr int kHist = 4096;       // complex samples of every source the handle carries (>= kMaxTaps - 1, a multiple of 8)
+constexpr int kMinLog2 = 2, kMaxLog2 = 8;
+constexpr int kWaves = 4;
+constexpr int kBatchMin = 128;    // points a wave transforms at once: every lane has a butterfly in every stage
+constexpr int kOutDwords = 4096;  // [bin][frame] results of a tile
+constexpr int kSpanMax = 6144;    // samples staged per tile at most
+constexpr int kFramesMax = 256;
+constexpr size_t kLdsMax = 64 * 1024;
+static_assert(kHist >= kMaxTaps - 1 && kHist % 8 == 0, "history geometry");
+
+// What host and kernel agree on for one (K, ntaps, D).
+struct Geometry {
+	int m, K;
+	int Q;      // taps per branch (the longest)
+	int Qp;     // int16 per branch as stored: Q, a sample of shift, zeros up to an even count whose half is odd (LDS banks)
+	int lead;   // samples staged in front of a tile's first frame: (Q + 1) K, so that no window index is negative
+	int F;      // frames per tile
+	int Ls;     // int16 per residue row of the staged samples (even, its half odd)
+	int Fs;     // dwords per bin row of the results (odd)
+	int batch;  // points per wave and turn
+	size_t lds; // bytes
+};
+
+inline size_t lds_of(const Geometry &g)
+{
+	return 4 * ((size_t)g.K + (size_t)g.K * g.Qp + (size_t)g.K * g.Ls + (size_t)kWaves * g.batch + (size_t)g.K * g.Fs);
+}
+
+inline Geometry geometry(int m, int ntaps, int D)
+{
+	Geometry g{};
+	g.m = m; g.K = 1 << m;
+	g.Q = (ntaps + g.K - 1) / g.K;
+	g.Qp = (g.Q + 2) & ~1;
+	if (!((g.Qp / 2) & 1)) g.Qp += 2;
+	g.lead = (g.Q + 1) * g.K;
+	g.batch = g.K > kBatchMin ? g.K : kBatchMin;
+	long long f = ((long long)kSpanMax - g.lead - 1) / D + 1;
+	if (f > kOutDwords / g.K) f = kOutDwords / g.K;
+	if (f > kFramesMax) f = kFramesMax;
+	if (f < 1) f = 1;
+	g.F = (int)f;
+	for (;;) {
+		const long long span = (long long)(g.F - 1) * D + g.lead + 1;
+		const int qmax = (int)((span + g.K - 2) >> m);  // the last row index a staged sample gets
+		g.Ls = (qmax + 6 + 1) & ~1;                     // a window reads up to Qp - Q <= 4 entries past its newest sample
+		if (!((g.Ls / 2) & 1)) g.Ls += 2;
+		g.Fs = g.F | 1;
+		g.lds = lds_of(g);
+		if (g.lds <= kLdsMax || g.F == 1) break;
+		g.F = (g.F + 1) / 2;
+	}
+	return g;
+}
+
+// The two copies of the taps: copy v, branch b, entry i multiplies the row sample i - v places behind the window's first,
+// the window's newest sample being entry Q - 1 + v: taps[b + (Q - 1 + v - i) K], zero outside the filter.
+inline void branch_taps(const int16_t *taps, int ntaps, const Geometry &g, int16_t *out /* [2][K][Qp] */)
+{
+	for (int v = 0; v < 2; v++)
+		for (int b = 0; b < g.K; b++)
+			for (int i = 0; i < g.Qp; i++) {
+				const int qq = g.Q - 1 + v - i;
+				const long long j = (long long)b + (long long)qq * g.K;
+				out[((size_t)v * g.K + b) * g.Qp + i] = (qq >= 0 && qq < g.Q && j < ntaps) ? taps[j] : (int16_t)0;
+			}
+}
+
+struct BankParams {
+	const uint8_t *iq;        // source rows
+	size_t src_stride;
+	const uint8_t *hist_in;   // [sources][kHist * 2]: the bytes in front of the run
+	uint8_t *hist_out;        // the same behind it (another buffer)
+	const uint32_t *taps2;    // branch_taps(), as dwords
+	const uint32_t *tw;       // [K] fix_fft's twiddles per stage, doubled and packed (fix_fft_butterfly.h)
+	const int32_t *bins;      // [per_source]
+	uint32_t pos;
+	int T, D;                 // complex samples of the run (a multiple of 8); outputs every D samples
+	int m, Q, Qp, lead, F, Ls, Fs, shift;
+	int maxout;               // most outputs a run can have; a Y row has room for them
+	int per_source;
+	int segs, tiles_per_seg, ntiles;
+	uint32_t *Y;              // decimated IQ, packed int16 pairs
+	size_t ystride;           // dwords per stream
+	int32_t *cnt;             // [nstreams]
+	const state_t *sin;
+	state_t *sout;            // already a copy of sin: prev_index is written here
+};
+
+__device__ __forceinline__ uint32_t finish(int ai, int aq, int shift)
+{
+	const int r = shift ? 1 << (shift - 1) : 0;
+	return pack_iq(min(max((ai + r) >> shift, -32768), 32767), min(max((aq + r) >> shift, -32768), 32767));
+}
+
+// Where the new history's 16-byte piece u comes from: run sample T - kHist + 8 u, or - a run shorter than the history -
+// the old history, shifted.  (T is a multiple of 8: nothing straddles.)
+__device__ __forceinline__ uint4 hist_piece(const uint8_t *row, const uint8_t *hold, int T, int u)
+{
+	const int n = T - kHist + u * 8;
+	return n >= 0 ? *reinterpret_cast<const uint4 *>(row + (size_t)n * 2)
+	              : *reinterpret_cast<const uint4 *>(hold + (size_t)(kHist + n) * 2);
+}
+
+// One complex sample of the source as a dword (I | Q << 8): run sample g, the history in front of the run, or silence.
+__device__ __forceinline__ uint32_t sample_at(const uint8_t *row, const uint8_t *hold, int T, int g)
+{
+	if (g >= T || g < -kHist) return 0x7f7fu;
+	return g >= 0 ? (uint32_t)*reinterpret_cast<const uint16_t *>(row + (size_t)g * 2)
+	              : (uint32_t)*reinterpret_cast<const uint16_t *>(hold + (size_t)(kHist + g) * 2);
+}
+
+__device__ __forceinline__ void wave_sync()
+{
+	// (one wave's LDS operations complete in the order it issues them: the fences are for the compiler)
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Grid: source * segs + seg.  Dynamic LDS: Geometry::lds.
+__global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p)
+{
+	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+	const int m = p.m, K = 1 << m, Km = K - 1;
+	const int batch = K > kBatchMin ? K : kBatchMin;
+	const int Lh = p.Ls / 2, Qh = p.Qp / 2;
+	uint32_t *s_tw = lds;
+	uint32_t *s_taps = s_tw + K;
+	uint32_t *s_I = s_taps + K * p.Qp;
+	uint32_t *s_Q = s_I + K * Lh;
+	uint32_t *s_work = s_Q + K * Lh;
+	uint32_t *s_out = s_work + kWaves * batch;
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int seg = (int)(blockIdx.x % (unsigned)p.segs);
+	const size_t src = (size_t)(blockIdx.x / (unsigned)p.segs);
+	const size_t s0 = src * (size_t)p.per_source;
+
+	for (int i = tid; i < K; i += kWaves * 64) s_tw[i] = p.tw[i];
+	for (int i = tid; i < K * p.Qp; i += kWaves * 64) s_taps[i] = p.taps2[i];
+
+	const uint8_t *row = p.iq + src * p.src_stride;
+	const uint8_t *hold = p.hist_in + src * (size_t)(kHist * 2);
+	const int D = p.D;
+	const int p0 = p.sin[s0].prev_index;         // one schedule per source: channel 0's
+	const int p0c = min(max(p0, 0), D - 1);      // (a broken record moves outputs, never an index out of its row)
+	const int E = min((p.T + p0c) / D, p.maxout);
+	const int t_begin = seg * p.tiles_per_seg;
+	const int t_end = min(p.ntiles, t_begin + p.tiles_per_seg);
+	int16_t *hI = reinterpret_cast<int16_t *>(s_I), *hQ = reinterpret_cast<int16_t *>(s_Q);
+	uint32_t *wk = s_work + wave * batch;
+	const int gf = batch >> m;  // frames per batch
+
+	for (int t = t_begin; t < t_end; t++) {
+		const int k0 = t * p.F;
+		if (k0 >= E) break;  // (the same for the whole workgroup)
+		const int nf = min(p.F, E - k0);
+		const int e0 = (k0 + 1) * D - p0c - 1;  // the run sample the tile's first frame is due at
+		const int g0 = e0 - p.lead;             // the run sample staged first (below 0: the history's)
+		const int base = (int)((p.pos + (uint32_t)g0) & (uint32_t)Km);  // its residue: row index = (u + base) >> m
+		const int span = (nf - 1) * D + p.lead + 1;
+		__syncthreads();  // the tile before this one has been summed and stored by every wave
+		for (int u = tid; u < span; u += kWaves * 64) {
+			const uint32_t w = sample_at(row, hold, p.T, g0 + u);
+			const int up = u + base;
+			const int at = (up & Km) * p.Ls + (up >> m);
+			hI[at] = (int16_t)((int)(w & 0xffu) - 127);
+			hQ[at] = (int16_t)((int)(w >> 8) - 127);
+		}
+		__syncthreads();
+		const int nb = (nf + gf - 1) / gf;
+		for (int bt = wave; bt < nb; bt += kWaves) {
+			wave_sync();  // (the batch before this one has left the work buffer)
+			// the polyphase sums, one (frame, residue) per lane and turn, to where the bit reversal puts them
+			for (int i = lane; i < batch; i += 64) {
+				const int f = min(bt * gf + (i >> m), nf - 1);  // (a frame past the tile's end repeats the last; never stored)
+				const int r = i & Km;
+				const int ue = f * D + p.lead + base;
+				const int b = (ue - r) & Km;      // the branch: the newest tap that meets residue r
+				const int qn = (ue - b) >> m;     // row index of the newest sample of the window
+				const int qs = qn - p.Q + 1, v = qs & 1;
+				const uint32_t *pt = s_taps + (v * K + b) * Qh;
+				const uint32_t *pi = s_I + r * Lh + ((qs - v) >> 1);
+				const uint32_t *pq = s_Q + r * Lh + ((qs - v) >> 1);
+				int ai = 0, aq = 0;
+				for (int j = 0; j < Qh; j++) {
+					int r0, r1;
+					fused::dot2_pair(pt[j], pi[j], pq[j], r0, r1);
+					ai += r0;
+					aq += r1;
+				}
+				wk[(i & ~Km) | (int)(__brev((unsigned)r) >> (32 - m))] = finish(ai, aq, p.shift);
+			}
+			wave_sync();
+			for (int st = 0; st < m; st++) {
+				const int half = 1 << st;
+				for (int t2 = lane; t2 < batch / 2; t2 += 64) {
+					const int fr = t2 >> (m - 1), tt = t2 & (K / 2 - 1);
+					const int q = tt & (half - 1);
+					const int i = ((tt >> st) << (st + 1)) | q;
+					const int at = (fr << m) | i;
+					uint32_t a = wk[at], b = wk[at + half];
+					rtlpower::butterfly<0>(a, b, s_tw[half - 1 + q]);
+					if (st < m - 1) {
+						wk[at] = a;
+						wk[at + half] = b;
+					} else {
+						const int f = bt * gf + fr;
+						if (f < nf) {
+							s_out[i * p.Fs + f] = a;
+							s_out[(i + half) * p.Fs + f] = b;
+						}
+					}
+				}
+				wave_sync();
+			}
+		}
+		__syncthreads();
+		// every selected bin's row receives the tile's frames as one contiguous piece: consecutive lanes, consecutive dwords
+		for (int x = tid; x < p.per_source * nf; x += kWaves * 64) {
+			const int c = x / nf, f = x - c * nf;
+			p.Y[(s0 + (size_t)c) * p.ystride + (size_t)(k0 + f)] = s_out[p.bins[c] * p.Fs + f];
+		}
+	}
+	if (seg == p.segs - 1) {
+		const int En = (p0 + p.T) / D;
+		for (int c = tid; c < p.per_source; c += kWaves * 64) {
+			p.sout[s0 + c].prev_index = p0 + p.T - En * D;
+			p.cnt[s0 + c] = En;
+		}
+		for (int u = tid; u < kHist / 8; u += kWaves * 64)
+			reinterpret_cast<uint4 *>(p.hist_out + src * (size_t)(kHist * 2))[u] = hist_piece(row, hold, p.T, u);
+	}
+}
+
+// ---- the cross-check ----
+// V: [sources][maxout][K] the sums v, then in place their transforms.
+__global__ void __launch_bounds__(256)
+k_bank_sums(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__restrict__ hist_in, const int16_t *__restrict__ taps,
+            int ntaps, int m, int shift, uint32_t pos, int nsources, int per_source, int T, int D, int maxout,
+            const state_t *__restrict__ sin, uint32_t *__restrict__ V)
+{
+	const int K = 1 << m;
+	RTLFM_GRID_STRIDE(g, ((size_t)nsources * maxout) << m) {
+		const int r = (int)(g & (size_t)(K - 1));
+		const size_t sk = g >> m;
+		const int k = (int)(sk % (size_t)maxout);
+		const size_t src = sk / (size_t)maxout;
+		const int p0c = min(max(sin[src * per_source].prev_index, 0), D - 1);
+		if (k >= min((T + p0c) / D, maxout)) continue;
+		const int e = (k + 1) * D - p0c - 1;
+		const uint8_t *row = iq + src * src_stride;
+		const uint8_t *hold = hist_in + src * (size_t)(kHist * 2);
+		int ai = 0, aq = 0;
+		for (int j = (int)((pos + (uint32_t)e - (uint32_t)r) & (uint32_t)(K - 1)); j < ntaps; j += K) {
+			const uint32_t w = sample_at(row, hold, T, e - j);
+			ai += (int)taps[j] * ((int)(w & 0xffu) - 127);
+			aq += (int)taps[j] * ((int)(w >> 8) - 127);
+		}
+		V[g] = finish(ai, aq, shift);
+	}
+}
+
+// fix_fft (src/rtl_power.c:271-327) on one frame per lane, in the reference's loop order; sine: sine_table(m), [3 K / 4]
+__global__ void __launch_bounds__(256)
+k_bank_fft(uint32_t *__restrict__ V, const int16_t *__restrict__ sine, int m, int nsources, int per_source, int T, int D, int maxout,
+           const state_t *__restrict__ sin)
+{
+	const int n = 1 << m;
+	RTLFM_GRID_STRIDE(g, (size_t)nsources * maxout) {
+		const int k = (int)(g % (size_t)maxout);
+		const size_t src = g / (size_t)maxout;
+		const int p0c = min(max(sin[src * per_source].prev_index, 0), D - 1);
+		if (k >= min((T + p0c) / D, maxout)) continue;
+		uint32_t *x = V + (g << m);
+		int rev = 0;
+		for (int idx = 1; idx <= n - 1; idx++) {
+			int bit = n;
+			do {
+				bit >>= 1;
+			} while (rev + bit > n - 1);
+			rev = (rev & (bit - 1)) + bit;
+			if (rev <= idx) continue;
+			const uint32_t tmp = x[idx];
+			x[idx] = x[rev];
+			x[rev] = tmp;
+		}
+		int kk = m - 1;
+		for (int half = 1; half < n; half <<= 1, kk--) {
+			const int step = half << 1;
+			for (int q = 0; q < half; q++) {
+				const int j = q << kk;
+				const int wr = (int)(int16_t)sine[j + n / 4] >> 1, wi = (int)(int16_t)(-sine[j]) >> 1;
+				for (int i = q; i < n; i += step) {
+					const iq16 a = unpack_iq(x[i]), b = unpack_iq(x[i + half]);
+					const int tr = (int)(int16_t)(rtlpower::fix_mpy(wr, b.i) - rtlpower::fix_mpy(wi, b.q));
+					const int ti = (int)(int16_t)(rtlpower::fix_mpy(wr, b.q) + rtlpower::fix_mpy(wi, b.i));
+					const int qr = a.i >> 1, qi = a.q >> 1;
+					x[i + half] = pack_iq((int)(int16_t)(qr - tr), (int)(int16_t)(qi - ti));
+					x[i] = pack_iq((int)(int16_t)(qr + tr), (int)(int16_t)(qi + ti));
+				}
+			}
+		}
+	}
+}
+
+__global__ void __launch_bounds__(256)
+k_bank_scatter(const uint32_t *__restrict__ V, const int32_t *__restrict__ bins, int m, int nstreams, int per_source, int T, int D,
+               int maxout, uint32_t *__restrict__ Y, size_t ystride, int32_t *__restrict__ cnt, const state_t *__restrict__ sin,
+               state_t *__restrict__ sout)
+{
+	RTLFM_GRID_STRIDE(g, (size_t)nstreams * maxout) {
+		const size_t s = g / (size_t)maxout;
+		const int k = (int)(g % (size_t)maxout);
+		const size_t src = s / (size_t)per_source;
+		const int c = (int)(s % (size_t)per_source);
+		const int p0 = sin[src * per_source].prev_index;
+		const int p0c = min(max(p0, 0), D - 1);
+		if (k == 0) {
+			const int En = (p0 + T) / D;
+			sout[s].prev_index = p0 + T - En * D;
+			cnt[s] = En;
+		}
+		if (k >= min((T + p0c) / D, maxout)) continue;
+		Y[s * ystride + k] = V[(((src * (size_t)maxout) + k) << m) + bins[c]];
+	}
+}
+
+__global__ void __launch_bounds__(256)
+k_bank_hist(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__restrict__ hist_in, uint8_t *__restrict__ hist_out,
+            int nsources, int T)
+{
+	RTLFM_GRID_STRIDE(g, (size_t)nsources * (kHist / 8)) {
+		const size_t src = g / (kHist / 8);
+		const int u = (int)(g % (kHist / 8));
+		reinterpret_cast<uint4 *>(hist_out + src * (size_t)(kHist * 2))[u] =
+			hist_piece(iq + src * src_stride, hist_in + src * (size_t)(kHist * 2), T, u);
+	}
+}
+
+}  // namespace chanbank
+}  // namespace rtlfm

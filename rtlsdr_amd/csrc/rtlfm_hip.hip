@@ -33,6 +33,7 @@
 #include "state_kernel.h"
 #include "channel_kernel.h"
 #include "channel_fir_kernel.h"
+#include "channel_bank_kernel.h"
 #include "../../include/rtlfm_snapshot.h"
 
 using namespace rtlfm;
@@ -131,6 +132,19 @@ struct rtlfm_gpu {
 	int chan_tail_cur = 0;
 	uint32_t *chan_fir_x = nullptr;        // path 1: k_channel_mix's samples of the tail and the run, [nstreams][chan_fir_xstride]
 	size_t chan_fir_xstride = 0;
+	// the channel bank (channel_bank_kernel.h; rtlfm_gpu_set_channel_bank): while on it takes the mixer paths' place
+	int bank_m = 0, bank_K = 0, bank_ntaps = 0, bank_shift = 0;  // K == 0: none
+	std::vector<int16_t> bank_taps;        // what the getter hands back
+	std::vector<int32_t> bank_bins;        // [chan_per]
+	int16_t *d_bank_taps = nullptr;        // [ntaps], k_bank_sums'
+	uint32_t *d_bank_taps2 = nullptr;      // chanbank::branch_taps(), k_channel_bank's
+	uint32_t *d_bank_tw = nullptr;         // [K] twiddles per stage, doubled and packed
+	int16_t *d_bank_sine = nullptr;        // [3 K / 4] sine_table(m), k_bank_fft's
+	int32_t *d_bank_bins = nullptr;        // [chan_per]
+	uint8_t *d_bank_hist[2] = {nullptr, nullptr};  // [bank_hist_srcs][chanbank::kHist * 2] raw bytes; a run reads [bank_hist_cur] and writes the other
+	int bank_hist_cur = 0, bank_hist_srcs = 0;
+	uint32_t *bank_v = nullptr;            // path 1: [sources][maxout][K] sums, transformed in place
+	size_t bank_v_dwords = 0;
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -544,7 +558,9 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
 	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth,
 	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq,
-	                h->d_fir_taps, h->d_fir_taps8, h->d_chan_tail[0], h->d_chan_tail[1], h->chan_fir_x};
+	                h->d_fir_taps, h->d_fir_taps8, h->d_chan_tail[0], h->d_chan_tail[1], h->chan_fir_x,
+	                h->d_bank_taps, h->d_bank_taps2, h->d_bank_tw, h->d_bank_sine, h->d_bank_bins, h->d_bank_hist[0], h->d_bank_hist[1],
+	                h->bank_v};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	delete[] h->mute_left;
@@ -569,6 +585,9 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 // stream: behind the runs already queued, in front of the next.
 static int chan_tail_clear(rtlfm_gpu *h)
 {
+	// (the bank's history likewise: x = 0 before this point)
+	if (h->d_bank_hist[0])
+		HIP_TRY(hipMemsetAsync(h->d_bank_hist[h->bank_hist_cur], 127, (size_t)h->bank_hist_srcs * chanbank::kHist * 2, h->stream));
 	if (!h->d_chan_tail[0]) return 0;
 	HIP_TRY(hipMemsetAsync(h->d_chan_tail[h->chan_tail_cur], 127, (size_t)h->nstreams * chanfir::kTail * 2, h->stream));
 	return 0;
@@ -775,6 +794,7 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	}
 	h->chan_per = per_source;
 	h->chan_pos = 0;
+	h->bank_K = 0;  // (the bank's bins belong to the old per_source)
 	return chan_tail_clear(h);
 }
 
@@ -782,9 +802,9 @@ extern "C" int rtlfm_gpu_channels_seek(rtlfm_gpu *h, uint64_t pos)
 {
 	if (!h) return -EINVAL;
 	h->chan_pos = pos;  // (read by the next run's launch; runs already queued took theirs by value)
-	if (!h->d_chan_tail[0]) return 0;
+	if (!h->d_chan_tail[0] && !h->d_bank_hist[0]) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	return chan_tail_clear(h);  // (the filter's history belongs to the old position)
+	return chan_tail_clear(h);  // (the filter's and the bank's history belong to the old position)
 }
 
 // ---- the channel filter: a caller-supplied FIR in the boxcar's place (include/rtlfm_hip.h, channel_fir_kernel.h) ----
@@ -853,6 +873,107 @@ extern "C" int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, i
 	h->fir_ntaps = ntaps;
 	h->fir_shift = ntaps > 0 ? shift : 0;
 	return chan_tail_clear(h);
+}
+
+// ---- the channel bank: uniform channels by polyphase sums and one fix_fft (include/rtlfm_hip.h, channel_bank_kernel.h) ----
+
+extern "C" int rtlfm_channel_bank_check(int K, const int16_t *taps, int ntaps, int shift)
+{
+	int m = 0;
+	while (m <= chanbank::kMaxLog2 && (1 << m) != K) m++;
+	if (m < chanbank::kMinLog2 || m > chanbank::kMaxLog2) return -EINVAL;
+	if (!taps || ntaps < 1 || ntaps > RTLFM_BANK_MAX_TAPS || shift < 0 || shift > 30) return -EINVAL;
+	long long most = 0;
+	for (int b = 0; b < K && b < ntaps; b++) {
+		long long sum = 0;
+		for (int j = b; j < ntaps; j += K) sum += taps[j] < 0 ? -(long long)taps[j] : (long long)taps[j];
+		if (sum > most) most = sum;
+	}
+	const long long r = shift ? 1ll << (shift - 1) : 0;
+	return 128 * most + r <= 0x7fffffffll ? 0 : -ERANGE;  // |x| <= 128: a branch's int32 sum and its rounding cannot overflow
+}
+
+template <typename T>
+static int bank_upload(T **dst, const T *src, size_t n)
+{
+	if (*dst) { hipFree(*dst); *dst = nullptr; }
+	HIP_TRY(hipMalloc(dst, n * sizeof(T)));
+	HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bins, const int16_t *taps, int ntaps, int shift)
+{
+	if (!h) return -EINVAL;
+	if (K != 0) {
+		int r = rtlfm_channel_bank_check(K, taps, ntaps, shift);
+		if (r < 0) return r;
+	}
+	if (ingest_busy(h)) return -EBUSY;  // (a begun run means channels off: asked first, or it could never be the answer)
+	if (h->cfg.downsample_passes > 0) return -ENOTSUP;  // (the bank takes the boxcar front end's place, not fifth_order's)
+	if (K != 0) {
+		if (h->chan_per <= 0) return -EINVAL;
+		if (!bins && h->chan_per != K) return -EINVAL;
+		for (int c = 0; bins && c < h->chan_per; c++)
+			if (bins[c] < 0 || bins[c] >= K) return -EINVAL;
+	}
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (K == 0) {
+		h->bank_K = 0;
+		return chan_tail_clear(h);
+	}
+	int m = 0;
+	while ((1 << m) != K) m++;
+	const int nsrc = h->nstreams / h->chan_per;
+	if (h->bank_hist_srcs < nsrc) {
+		for (int i = 0; i < 2; i++) {
+			if (h->d_bank_hist[i]) { hipFree(h->d_bank_hist[i]); h->d_bank_hist[i] = nullptr; }
+			HIP_TRY(hipMalloc(&h->d_bank_hist[i], (size_t)nsrc * chanbank::kHist * 2));
+		}
+		h->bank_hist_srcs = nsrc;
+	}
+	std::vector<int32_t> b((size_t)h->chan_per);
+	for (int c = 0; c < h->chan_per; c++) b[c] = bins ? bins[c] : c;
+	const chanbank::Geometry g = chanbank::geometry(m, ntaps, h->cfg.downsample);
+	std::vector<int16_t> t2((size_t)2 * K * g.Qp);
+	chanbank::branch_taps(taps, ntaps, g, t2.data());
+	// sine_table(), src/rtl_power.c:247-261, for N_WAVE = K, and regrouped per stage as rtl_power's transforms read it:
+	// entry (1 << s) - 1 + q holds (2 wr, 2 wi) of wr = Sinewave[j + K/4] >> 1, wi = -Sinewave[j] >> 1 at j = q << (m - 1 - s)
+	std::vector<int16_t> sine((size_t)K * 3 / 4 + 1);
+	for (int i = 0; i < K * 3 / 4; i++) sine[i] = (int16_t)(int)round(32767 * sin((double)i * 2.0 * M_PI / K));
+	std::vector<uint32_t> tw((size_t)K, 0u);
+	for (int st = 0; st < m; st++)
+		for (int q = 0; q < (1 << st); q++) {
+			const int j = q << (m - 1 - st);
+			int16_t wr = sine[j + K / 4], wi = (int16_t)(-sine[j]);
+			wr >>= 1; wi >>= 1;
+			tw[(size_t)(1 << st) - 1 + q] = (uint32_t)(uint16_t)(wr * 2) | ((uint32_t)(uint16_t)(wi * 2) << 16);
+		}
+	int r;
+	if ((r = bank_upload(&h->d_bank_taps, taps, (size_t)ntaps)) < 0) return r;
+	if ((r = bank_upload(&h->d_bank_taps2, reinterpret_cast<const uint32_t *>(t2.data()), t2.size() / 2)) < 0) return r;
+	if ((r = bank_upload(&h->d_bank_tw, tw.data(), tw.size())) < 0) return r;
+	if ((r = bank_upload(&h->d_bank_sine, sine.data(), sine.size())) < 0) return r;
+	if ((r = bank_upload(&h->d_bank_bins, b.data(), b.size())) < 0) return r;
+	h->bank_taps.assign(taps, taps + ntaps);
+	h->bank_bins = b;
+	h->bank_m = m; h->bank_K = K; h->bank_ntaps = ntaps; h->bank_shift = shift;
+	return chan_tail_clear(h);
+}
+
+extern "C" int rtlfm_gpu_get_channel_bank(rtlfm_gpu *h, int *K, int32_t *bins, int bins_cap, int16_t *taps, int taps_cap, int *ntaps,
+                                          int *shift)
+{
+	if (!h || !K || !ntaps || !shift || bins_cap < 0 || taps_cap < 0 || (bins_cap > 0 && !bins) || (taps_cap > 0 && !taps)) return -EINVAL;
+	*K = h->bank_K;  // (written even where bins or taps do not fit)
+	*ntaps = h->bank_K ? h->bank_ntaps : 0;
+	*shift = h->bank_K ? h->bank_shift : 0;
+	if (!h->bank_K) return 0;
+	if ((int)h->bank_bins.size() > bins_cap || h->bank_ntaps > taps_cap) return -ENOBUFS;
+	memcpy(bins, h->bank_bins.data(), h->bank_bins.size() * sizeof(int32_t));
+	memcpy(taps, h->bank_taps.data(), (size_t)h->bank_ntaps * sizeof(int16_t));
+	return 0;
 }
 
 extern "C" int rtlfm_gpu_get_channel_filter(rtlfm_gpu *h, int16_t *taps, int cap, int *ntaps, int *shift)
@@ -2184,6 +2305,79 @@ static int run_channels_fir(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, 
 	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
 }
 
+// Channels on with the bank set (rtlfm_gpu_set_channel_bank): K polyphase sums and one fix_fft per output instant in the
+// mixer paths' place, then run_back_half() as behind low_pass().  fused: k_channel_bank, one launch; else the cross-check -
+// k_bank_sums, k_bank_fft, k_bank_scatter, k_bank_hist.  Both read the history d_bank_hist[bank_hist_cur] and write the
+// other; rtlfm_gpu_run_device changes over once per run.
+static int run_channels_bank(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
+                             size_t out_stride, int32_t *d_out_len)
+{
+	const rtlfm_cfg &c = h->cfg;
+	const int S = h->nstreams;
+	hipStream_t q = h->stream;
+	const int N0 = (int)(c.block_len / 2), D = c.downsample;
+	const int Tin = nblocks * N0;
+	const bool varcnt = (N0 % D) != 0;
+	const int T = varcnt ? Tin / D + 1 : Tin / D;
+	const int nsrc = S / h->chan_per;
+	if (!h->chan_iq) {
+		h->chan_stride = (((size_t)h->cap_blocks * N0) / D + 1 + 16 + 3) & ~(size_t)3;  // (run_channels': one allocation serves all)
+		HIP_TRY(hipMalloc(&h->chan_iq, (size_t)S * h->chan_stride * sizeof(uint32_t)));
+	}
+	const int maxout = Tin / D + 1;
+	const size_t vneed = ((size_t)nsrc * maxout) << h->bank_m;
+	if (!fused_path && h->bank_v_dwords < vneed) {
+		if (h->bank_v) { hipFree(h->bank_v); h->bank_v = nullptr; h->bank_v_dwords = 0; }
+		const size_t most = ((size_t)nsrc * ((size_t)h->cap_blocks * N0 / D + 1)) << h->bank_m;
+		HIP_TRY(hipMalloc(&h->bank_v, most * sizeof(uint32_t)));
+		h->bank_v_dwords = most;
+	}
+	TailPlan tp = plan_tail(h, nblocks);
+	int r;
+	if (tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
+	const uint8_t *hist_in = h->d_bank_hist[h->bank_hist_cur];
+	uint8_t *hist_out = h->d_bank_hist[h->bank_hist_cur ^ 1];
+	int32_t *dcnt = h->d_cnt[h->step & 1];
+	const state_t *sin = h->st[h->st_cur];
+	state_t *sout = h->st[(h->st_cur + 1) % 3];
+	std::pair<hipEvent_t, hipEvent_t> ev;
+	if (fused_path) {
+		const chanbank::Geometry g = chanbank::geometry(h->bank_m, h->bank_ntaps, D);
+		chanbank::BankParams p{};
+		p.iq = d_iq; p.src_stride = stream_stride;
+		p.hist_in = hist_in; p.hist_out = hist_out;
+		p.taps2 = h->d_bank_taps2; p.tw = h->d_bank_tw; p.bins = h->d_bank_bins;
+		p.pos = (uint32_t)h->chan_pos;
+		p.T = Tin; p.D = D;
+		p.m = g.m; p.Q = g.Q; p.Qp = g.Qp; p.lead = g.lead; p.F = g.F; p.Ls = g.Ls; p.Fs = g.Fs; p.shift = h->bank_shift;
+		p.maxout = maxout;
+		p.per_source = h->chan_per;
+		p.ntiles = (maxout + g.F - 1) / g.F;
+		// (frames are independent: every D goes with every segmentation - D = 1 for the plan; one workgroup per source and segment)
+		channel::plan(nsrc * chanbank::kWaves, p.ntiles, 1, tp.any() ? h->fws.target_waves_tail : h->fws.target_waves, h->fws.min_tiles,
+		              h->fws.tiles_per_seg, &p.segs, &p.tiles_per_seg);
+		p.Y = h->chan_iq; p.ystride = h->chan_stride;
+		p.cnt = dcnt; p.sin = sin; p.sout = sout;
+		const size_t grid = (size_t)nsrc * p.segs;
+		if (grid > 0x7fffffffu) return -E2BIG;
+		if ((r = timing_begin(h, ev)) < 0) return r;
+		chanbank::k_channel_bank<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+		if ((r = timing_end(h, ev)) < 0) return r;
+	} else {
+		if ((r = timing_begin(h, ev)) < 0) return r;
+		chanbank::k_bank_sums<<<grid_for(vneed), 256, 0, q>>>(d_iq, stream_stride, hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
+		                                                     h->bank_shift, (uint32_t)h->chan_pos, nsrc, h->chan_per, Tin, D, maxout, sin,
+		                                                     h->bank_v);
+		chanbank::k_bank_fft<<<grid_for((size_t)nsrc * maxout), 256, 0, q>>>(h->bank_v, h->d_bank_sine, h->bank_m, nsrc, h->chan_per, Tin, D,
+		                                                                    maxout, sin);
+		chanbank::k_bank_scatter<<<grid_for((size_t)S * maxout), 256, 0, q>>>(h->bank_v, h->d_bank_bins, h->bank_m, S, h->chan_per, Tin, D,
+		                                                                     maxout, h->chan_iq, h->chan_stride, dcnt, sin, sout);
+		chanbank::k_bank_hist<<<grid_for((size_t)nsrc * (chanbank::kHist / 8)), 256, 0, q>>>(d_iq, stream_stride, hist_in, hist_out, nsrc, Tin);
+		if ((r = timing_end(h, ev)) < 0) return r;
+	}
+	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
+}
+
 static int ensure_input_stats(rtlfm_gpu *h)
 {
 	if (!h->d_istats)
@@ -2283,7 +2477,9 @@ static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		if (h->path == 2 && !boxed) return -ENOTSUP;
 		HIP_TRY(hipMemcpyAsync(h->st[(h->st_cur + 1) % 3], h->st[h->st_cur], S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
 		// (a filter is only ever set on a handle without fifth_order passes: with it, both paths are the filter's)
-		r = h->fir_ntaps > 0 ? run_channels_fir(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
+		// (the bank, like the filter, is only ever set without fifth_order passes; while on it takes precedence over the filter)
+		r = h->bank_K > 0 ? run_channels_bank(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
+		  : h->fir_ntaps > 0 ? run_channels_fir(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
 		  : boxed ? run_channels(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
 		          : run_staged(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
 		if (r < 0) return r;
@@ -2443,7 +2639,8 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	h->st_cur = (h->st_cur + 1) % 3;
 	h->step++;
 	if (h->chan_per > 0) h->chan_pos += (uint64_t)nblocks * (h->cfg.block_len / 2);  // (once per run, also under verify_twice)
-	if (h->chan_per > 0 && h->fir_ntaps > 0) h->chan_tail_cur ^= 1;  // (the same: both executions read one tail and wrote the other)
+	if (h->chan_per > 0 && h->bank_K > 0) h->bank_hist_cur ^= 1;  // (the bank's history likewise; the filter's rests while the bank is on)
+	else if (h->chan_per > 0 && h->fir_ntaps > 0) h->chan_tail_cur ^= 1;  // (the same: both executions read one tail and wrote the other)
 	h->last_nblocks = nblocks;
 	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
 	h->health_nblocks = h->opt.input_health ? nblocks : 0;

@@ -249,6 +249,34 @@ class GpuDemod:
         check(self.lib.rtlfm_gpu_get_channel_filter(self._h, out.ctypes.data, out.size, C.byref(n), C.byref(sh)), "rtlfm_gpu_get_channel_filter")
         return out[:n.value].copy(), sh.value
 
+    def set_channel_bank(self, K: int, taps=None, shift: int = 0, bins=None):
+        """rtlfm_gpu_set_channel_bank: channel ``c`` of every source becomes bin ``bins[c]`` of a ``K``-point fix_fft over
+        the ``K`` polyphase sums of int16 ``taps`` (``v_r = sat16((u_r + rnd) >> shift)``), in the mixer paths' place while
+        channels are on.  ``bins = None`` is the identity (``per_source == K``).  ``K = 0`` removes the bank.  Clears the
+        bank's history."""
+        if not K:
+            check(self.lib.rtlfm_gpu_set_channel_bank(self._h, 0, None, None, 0, 0), "rtlfm_gpu_set_channel_bank")
+            return
+        t = np.ascontiguousarray([] if taps is None else taps, dtype=np.int16)
+        if t.ndim != 1:
+            raise ValueError("taps: one dimension")
+        b = None
+        if bins is not None:
+            b = np.ascontiguousarray(bins, dtype=np.int32)
+            if b.shape != (self._per_source,):
+                raise ValueError(f"one bin per channel of a source: {self._per_source}, not {b.shape}")
+        check(self.lib.rtlfm_gpu_set_channel_bank(self._h, int(K), None if b is None else b.ctypes.data, t.ctypes.data if t.size else None,
+                                                  int(t.size), int(shift)), "rtlfm_gpu_set_channel_bank")
+
+    def get_channel_bank(self):
+        """rtlfm_gpu_get_channel_bank: ``(K, bins, taps, shift)`` as set; ``(0, empty, empty, 0)`` without a bank."""
+        bins = np.zeros(max(self._per_source, 1), dtype=np.int32)
+        taps = np.zeros(capi.BANK_MAX_TAPS, dtype=np.int16)
+        K, n, sh = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.rtlfm_gpu_get_channel_bank(self._h, C.byref(K), bins.ctypes.data, bins.size, taps.ctypes.data, taps.size, C.byref(n),
+                                                  C.byref(sh)), "rtlfm_gpu_get_channel_bank")
+        return K.value, (bins[:self._per_source].copy() if K.value else bins[:0].copy()), taps[:n.value].copy(), sh.value
+
     # -- state & plumbing ------------------------------------------------------
     def state_get(self, stream: int = 0) -> RtlfmStreamState:
         st = RtlfmStreamState()
@@ -369,6 +397,13 @@ def channel_lowpass(ntaps: int, cutoff: float, D: int):
     sh = C.c_int()
     check(capi.load().rtlfm_channel_lowpass(int(ntaps), float(cutoff), int(D), out.ctypes.data, C.byref(sh)), "rtlfm_channel_lowpass")
     return out, sh.value
+
+
+def channel_bank_check(K: int, taps, shift: int) -> int:
+    """rtlfm_channel_bank_check: 0, or a negative errno (-EINVAL for a bad K / taps / shift, -ERANGE where a branch's sum
+    could overflow an int32).  Needs no GPU."""
+    t = np.ascontiguousarray(taps, dtype=np.int16)
+    return int(capi.load().rtlfm_channel_bank_check(int(K), t.ctypes.data if t.size else None, int(t.size), int(shift)))
 
 
 def channel_table() -> np.ndarray:
