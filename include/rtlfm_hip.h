@@ -446,19 +446,26 @@ int rtlfm_gpu_channels_tell(rtlfm_gpu *h, uint64_t *pos);
  * only while channels are on.  Waits for what the handle has queued.  One filter and one D for all channels.
  * rtlfm_gpu_get_channel_filter: *ntaps and *shift are always written; the taps are copied if ntaps <= cap, else -ENOBUFS.
  *
- * History: what is carried from run to run is every SOURCE's last ntaps - 1 complex samples (the handle keeps 1024) as
- * raw bytes in a device buffer of the handle - not in rtlfm_stream_state, whose size and snapshot format stay.  The mixer
- * is a pure function of pos and the bytes: a run mixes what it needs of them again.  A run shorter than the history
- * shifts it.  It is cleared to bytes 127 (mixed zeros: m[n < 0] = 0) by
- *   rtlfm_gpu_set_channel_filter   (new taps start from silence),
+ * History, the filter's and the channel bank's (below) alike - there is one: what is carried from run to run is every
+ * SOURCE's last 4096 complex samples as raw bytes (the filter reads ntaps - 1 of them, the bank up to ntaps + K), in two
+ * device buffers of the handle: a run reads one and writes the other, changed over where pos advances.  Not in
+ * rtlfm_stream_state, whose size and snapshot format stay.  The mixer is a pure function of pos and the bytes: a run
+ * mixes what it needs of them again.  A run shorter than the history shifts it.  The buffers hold 16 KiB per source - not
+ * per stream - and are allocated once channels are on and a filter or a bank is set (grown when rtlfm_gpu_set_channels
+ * brings more sources, never shrunk): 2 x 16 KiB x sources, which with a filter alone and fewer than 4 channels per source
+ * is more than the 4 KiB per stream the filter would need by itself.  The history is cleared to bytes 127 (mixed zeros,
+ * m[n < 0] = 0; x[n < 0] = 0) by
+ *   rtlfm_gpu_set_channel_filter   (new taps start from silence; also while the bank is on and the filter rests, and
+ *                                   also with ntaps == 0),
+ *   rtlfm_gpu_set_channel_bank     (the same; also with K == 0, so the filter that acts again starts from silence),
  *   rtlfm_gpu_set_channels         (other sources, pos = 0),
  *   rtlfm_gpu_reset                (with the state records and pos),
  *   rtlfm_gpu_channels_seek        (the bytes belong to the old position).
- * Under verify_twice both executions of a run see one pos and one history.
+ * A call that is refused clears nothing.  Under verify_twice both executions of a run see one pos and one history.
  * Paths: rtlfm_gpu_set_path(0 / 2) - one launch from source bytes to every channel's decimated IQ (k_channel_fir;
  * rtlfm_gpu_last_path says 2), the default; (1) - k_channel_mix over the history and the run, then a plain kernel with
- * one lane per output (the cross-check).  Both read and write the same history: changing the path between two runs
- * changes no output bit.
+ * one lane per output, and a history kernel (the cross-check).  Both read and write the same history: changing the path
+ * between two runs changes no output bit.
  */
 #define RTLFM_CHANNEL_MAX_TAPS 1024
 int rtlfm_channel_filter_check(const int16_t *taps, int ntaps, int shift);
@@ -480,7 +487,7 @@ int rtlfm_gpu_get_channel_filter(rtlfm_gpu *h, int16_t *taps, int cap, int *ntap
  *   bins     bins[per_source], each in [0, K), duplicates allowed: channel c of every source is bin bins[c].  NULL is
  *            the identity and needs per_source == K
  *   x[n]     (I - 127, Q - 127) of the source; n is absolute, pos (rtlfm_gpu_channels_tell) + the index within the run;
- *            x = 0 before the point where the bank's history was last cleared
+ *            x = 0 before the point where the history was last cleared
  *   outputs  are due at the samples e at which low_pass() emits one, as for the channel filter - here with ONE schedule per
  *            source, taken from the prev_index of the source's channel 0; a run writes the new prev_index and the count
  *            to every channel of the source.  now_r / now_j are copied, not used
@@ -500,16 +507,12 @@ int rtlfm_gpu_get_channel_filter(rtlfm_gpu *h, int16_t *taps, int cap, int *ntap
  * rtlfm_gpu_set_channel_bank: runs the check first; K == 0 removes the bank (the mixer paths are back, bit for bit).
  * -EINVAL with channels off or a bin outside [0, K) (or bins == NULL with per_source != K); -ENOTSUP, changing nothing,
  * with cfg.downsample_passes > 0; -EBUSY while a run is begun and not ended.  Waits for what the handle has queued and
- * clears the bank's history.  While on, the bank takes precedence over a set channel filter: the filter's taps are kept
+ * clears the history.  While on, the bank takes precedence over a set channel filter: the filter's taps are kept
  * and act again once the bank is removed.  rtlfm_gpu_set_channels removes the bank (bins belongs to the old per_source).
  * rtlfm_gpu_get_channel_bank: *K, *ntaps and *shift are always written (0 without a bank); bins (per_source of them) and
  * taps are copied if both caps suffice, else -ENOBUFS.
  *
- * History: every SOURCE's last 4096 complex samples as raw bytes in two device buffers of the handle: a run reads one
- * and writes the other, changed over where pos advances - the channel filter's scheme, and separate from it.
- * rtlfm_stream_state, its size and the snapshot format stay.  Cleared to bytes 127 by rtlfm_gpu_set_channel_bank,
- * rtlfm_gpu_set_channels, rtlfm_gpu_reset and rtlfm_gpu_channels_seek.  Under verify_twice both executions of a run see
- * one pos and one history.
+ * History: the one described with the channel filter above - its size, its five clearing calls, verify_twice.
  * Paths: rtlfm_gpu_set_path(0 / 2) - k_channel_bank, one launch from source bytes to every selected channel's decimated
  * IQ (rtlfm_gpu_last_path says 2), the default; (1) - the plain cross-check: one lane per (frame, residue) forms v in
  * memory, one lane per frame runs fix_fft in the reference's loop order, a scatter and a history kernel follow.  Both

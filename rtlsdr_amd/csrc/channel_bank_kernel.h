@@ -10,8 +10,7 @@
 // order of summation gives the same bits; every butterfly is rtlpower::butterfly (fix_fft_butterfly.h), the reference's
 // bit for bit, and the butterflies of one stage are independent of each other.
 //
-// What is carried from run to run is the SOURCE's last kHist complex samples as raw bytes (bytes 127 where nothing has
-// been consumed yet: x = 0), in two copies: a run reads one and writes the other, the handle changes over once per run.
+// What is carried from run to run is the source history (channel_kernel.h, kHist; bytes 127: x = 0).
 //
 //   k_channel_bank   the product.  One launch from source bytes to every selected channel's decimated IQ.  A workgroup is
 //                    one source over a stretch of tiles of F output instants ("frames").  Per tile the bytes the frames'
@@ -22,9 +21,10 @@
 //                    runs the log2 K stages over its batch of max(128, K) points (128 / K frames, or one frame with two
 //                    butterflies per lane), leaves the last stage's results in LDS as [bin][frame], and the workgroup
 //                    hands every selected bin's row its stretch of frames as one contiguous piece.
-//   k_bank_sums, k_bank_fft, k_bank_scatter, k_bank_hist
+//   k_bank_sums, k_bank_fft, k_bank_scatter
 //                    the cross-check: one lane per (frame, residue) forms v in memory, one lane per frame runs fix_fft in
-//                    the reference's own loop order with FIX_MPY spelled out, a scatter and a history kernel follow.
+//                    the reference's own loop order with FIX_MPY spelled out, a scatter and channel::k_source_history
+//                    follow.
 #pragma once
 
 #include "channel_kernel.h"
@@ -35,7 +35,7 @@ namespace rtlfm {
 namespace chanbank {
 
 constexpr int kMaxTaps = RTLFM_BANK_MAX_TAPS;
-constexpr int kHist = 4096;       // complex samples of every source the handle carries (>= kMaxTaps - 1, a multiple of 8)
+constexpr int kHist = channel::kHist;
 constexpr int kMinLog2 = 2, kMaxLog2 = 8;
 constexpr int kWaves = 4;
 constexpr int kBatchMin = 128;    // points a wave transforms at once: every lane has a butterfly in every stage
@@ -43,7 +43,7 @@ constexpr int kOutDwords = 4096;  // [bin][frame] results of a tile
 constexpr int kSpanMax = 6144;    // samples staged per tile at most
 constexpr int kFramesMax = 256;
 constexpr size_t kLdsMax = 64 * 1024;
-static_assert(kHist >= kMaxTaps - 1 && kHist % 8 == 0, "history geometry");
+static_assert(kHist >= kMaxTaps - 1, "history geometry");
 
 // What host and kernel agree on for one (K, ntaps, D).
 struct Geometry {
@@ -104,40 +104,14 @@ inline void branch_taps(const int16_t *taps, int ntaps, const Geometry &g, int16
 }
 
 struct BankParams {
-	const uint8_t *iq;        // source rows
-	size_t src_stride;
+	channel::Frame f;         // (tiles: of F frames; T need only be a multiple of 8)
 	const uint8_t *hist_in;   // [sources][kHist * 2]: the bytes in front of the run
 	uint8_t *hist_out;        // the same behind it (another buffer)
 	const uint32_t *taps2;    // branch_taps(), as dwords
 	const uint32_t *tw;       // [K] fix_fft's twiddles per stage, doubled and packed (fix_fft_butterfly.h)
 	const int32_t *bins;      // [per_source]
-	uint32_t pos;
-	int T, D;                 // complex samples of the run (a multiple of 8); outputs every D samples
 	int m, Q, Qp, lead, F, Ls, Fs, shift;
-	int maxout;               // most outputs a run can have; a Y row has room for them
-	int per_source;
-	int segs, tiles_per_seg, ntiles;
-	uint32_t *Y;              // decimated IQ, packed int16 pairs
-	size_t ystride;           // dwords per stream
-	int32_t *cnt;             // [nstreams]
-	const state_t *sin;
-	state_t *sout;            // already a copy of sin: prev_index is written here
 };
-
-__device__ __forceinline__ uint32_t finish(int ai, int aq, int shift)
-{
-	const int r = shift ? 1 << (shift - 1) : 0;
-	return pack_iq(min(max((ai + r) >> shift, -32768), 32767), min(max((aq + r) >> shift, -32768), 32767));
-}
-
-// Where the new history's 16-byte piece u comes from: run sample T - kHist + 8 u, or - a run shorter than the history -
-// the old history, shifted.  (T is a multiple of 8: nothing straddles.)
-__device__ __forceinline__ uint4 hist_piece(const uint8_t *row, const uint8_t *hold, int T, int u)
-{
-	const int n = T - kHist + u * 8;
-	return n >= 0 ? *reinterpret_cast<const uint4 *>(row + (size_t)n * 2)
-	              : *reinterpret_cast<const uint4 *>(hold + (size_t)(kHist + n) * 2);
-}
 
 // One complex sample of the source as a dword (I | Q << 8): run sample g, the history in front of the run, or silence.
 __device__ __forceinline__ uint32_t sample_at(const uint8_t *row, const uint8_t *hold, int T, int g)
@@ -145,14 +119,6 @@ __device__ __forceinline__ uint32_t sample_at(const uint8_t *row, const uint8_t 
 	if (g >= T || g < -kHist) return 0x7f7fu;
 	return g >= 0 ? (uint32_t)*reinterpret_cast<const uint16_t *>(row + (size_t)g * 2)
 	              : (uint32_t)*reinterpret_cast<const uint16_t *>(hold + (size_t)(kHist + g) * 2);
-}
-
-__device__ __forceinline__ void wave_sync()
-{
-	// (one wave's LDS operations complete in the order it issues them: the fences are for the compiler)
-	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Grid: source * segs + seg.  Dynamic LDS: Geometry::lds.
@@ -169,21 +135,22 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 	uint32_t *s_work = s_Q + K * Lh;
 	uint32_t *s_out = s_work + kWaves * batch;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int seg = (int)(blockIdx.x % (unsigned)p.segs);
-	const size_t src = (size_t)(blockIdx.x / (unsigned)p.segs);
-	const size_t s0 = src * (size_t)p.per_source;
+	const int seg = (int)(blockIdx.x % (unsigned)p.f.segs);
+	const size_t src = (size_t)(blockIdx.x / (unsigned)p.f.segs);
+	const size_t s0 = src * (size_t)p.f.per_source;
 
 	for (int i = tid; i < K; i += kWaves * 64) s_tw[i] = p.tw[i];
 	for (int i = tid; i < K * p.Qp; i += kWaves * 64) s_taps[i] = p.taps2[i];
 
-	const uint8_t *row = p.iq + src * p.src_stride;
+	const uint8_t *row = p.f.iq + src * p.f.src_stride;
 	const uint8_t *hold = p.hist_in + src * (size_t)(kHist * 2);
-	const int D = p.D;
-	const int p0 = p.sin[s0].prev_index;         // one schedule per source: channel 0's
-	const int p0c = min(max(p0, 0), D - 1);      // (a broken record moves outputs, never an index out of its row)
-	const int E = min((p.T + p0c) / D, p.maxout);
-	const int t_begin = seg * p.tiles_per_seg;
-	const int t_end = min(p.ntiles, t_begin + p.tiles_per_seg);
+	const int D = p.f.D;
+	const int p0 = p.f.sin[s0].prev_index;         // one schedule per source: channel 0's
+	const channel::Schedule sc = channel::schedule(p0, p.f.T, D);
+	const int p0c = sc.p0c;
+	const int E = min((p.f.T + p0c) / D, p.f.maxout);
+	const int t_begin = seg * p.f.tiles_per_seg;
+	const int t_end = min(p.f.ntiles, t_begin + p.f.tiles_per_seg);
 	int16_t *hI = reinterpret_cast<int16_t *>(s_I), *hQ = reinterpret_cast<int16_t *>(s_Q);
 	uint32_t *wk = s_work + wave * batch;
 	const int gf = batch >> m;  // frames per batch
@@ -194,11 +161,11 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 		const int nf = min(p.F, E - k0);
 		const int e0 = (k0 + 1) * D - p0c - 1;  // the run sample the tile's first frame is due at
 		const int g0 = e0 - p.lead;             // the run sample staged first (below 0: the history's)
-		const int base = (int)((p.pos + (uint32_t)g0) & (uint32_t)Km);  // its residue: row index = (u + base) >> m
+		const int base = (int)((p.f.pos + (uint32_t)g0) & (uint32_t)Km);  // its residue: row index = (u + base) >> m
 		const int span = (nf - 1) * D + p.lead + 1;
 		__syncthreads();  // the tile before this one has been summed and stored by every wave
 		for (int u = tid; u < span; u += kWaves * 64) {
-			const uint32_t w = sample_at(row, hold, p.T, g0 + u);
+			const uint32_t w = sample_at(row, hold, p.f.T, g0 + u);
 			const int up = u + base;
 			const int at = (up & Km) * p.Ls + (up >> m);
 			hI[at] = (int16_t)((int)(w & 0xffu) - 127);
@@ -207,7 +174,7 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 		__syncthreads();
 		const int nb = (nf + gf - 1) / gf;
 		for (int bt = wave; bt < nb; bt += kWaves) {
-			wave_sync();  // (the batch before this one has left the work buffer)
+			channel::wave_sync();  // (the batch before this one has left the work buffer)
 			// the polyphase sums, one (frame, residue) per lane and turn, to where the bit reversal puts them
 			for (int i = lane; i < batch; i += 64) {
 				const int f = min(bt * gf + (i >> m), nf - 1);  // (a frame past the tile's end repeats the last; never stored)
@@ -226,9 +193,9 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 					ai += r0;
 					aq += r1;
 				}
-				wk[(i & ~Km) | (int)(__brev((unsigned)r) >> (32 - m))] = finish(ai, aq, p.shift);
+				wk[(i & ~Km) | (int)(__brev((unsigned)r) >> (32 - m))] = channel::round_sat_pack(ai, aq, p.shift);
 			}
-			wave_sync();
+			channel::wave_sync();
 			for (int st = 0; st < m; st++) {
 				const int half = 1 << st;
 				for (int t2 = lane; t2 < batch / 2; t2 += 64) {
@@ -249,24 +216,20 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 						}
 					}
 				}
-				wave_sync();
+				channel::wave_sync();
 			}
 		}
 		__syncthreads();
 		// every selected bin's row receives the tile's frames as one contiguous piece: consecutive lanes, consecutive dwords
-		for (int x = tid; x < p.per_source * nf; x += kWaves * 64) {
+		for (int x = tid; x < p.f.per_source * nf; x += kWaves * 64) {
 			const int c = x / nf, f = x - c * nf;
-			p.Y[(s0 + (size_t)c) * p.ystride + (size_t)(k0 + f)] = s_out[p.bins[c] * p.Fs + f];
+			p.f.Y[(s0 + (size_t)c) * p.f.ystride + (size_t)(k0 + f)] = s_out[p.bins[c] * p.Fs + f];
 		}
 	}
-	if (seg == p.segs - 1) {
-		const int En = (p0 + p.T) / D;
-		for (int c = tid; c < p.per_source; c += kWaves * 64) {
-			p.sout[s0 + c].prev_index = p0 + p.T - En * D;
-			p.cnt[s0 + c] = En;
-		}
+	if (seg == p.f.segs - 1) {
+		for (int c = tid; c < p.f.per_source; c += kWaves * 64) channel::leave_schedule(p.f.sout, p.f.cnt, s0 + c, sc);
 		for (int u = tid; u < kHist / 8; u += kWaves * 64)
-			reinterpret_cast<uint4 *>(p.hist_out + src * (size_t)(kHist * 2))[u] = hist_piece(row, hold, p.T, u);
+			reinterpret_cast<uint4 *>(p.hist_out + src * (size_t)(kHist * 2))[u] = channel::history_piece(row, hold, p.f.T, u);
 	}
 }
 
@@ -283,7 +246,7 @@ k_bank_sums(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__
 		const size_t sk = g >> m;
 		const int k = (int)(sk % (size_t)maxout);
 		const size_t src = sk / (size_t)maxout;
-		const int p0c = min(max(sin[src * per_source].prev_index, 0), D - 1);
+		const int p0c = channel::schedule(sin[src * per_source].prev_index, T, D).p0c;
 		if (k >= min((T + p0c) / D, maxout)) continue;
 		const int e = (k + 1) * D - p0c - 1;
 		const uint8_t *row = iq + src * src_stride;
@@ -294,7 +257,7 @@ k_bank_sums(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__
 			ai += (int)taps[j] * ((int)(w & 0xffu) - 127);
 			aq += (int)taps[j] * ((int)(w >> 8) - 127);
 		}
-		V[g] = finish(ai, aq, shift);
+		V[g] = channel::round_sat_pack(ai, aq, shift);
 	}
 }
 
@@ -307,7 +270,7 @@ k_bank_fft(uint32_t *__restrict__ V, const int16_t *__restrict__ sine, int m, in
 	RTLFM_GRID_STRIDE(g, (size_t)nsources * maxout) {
 		const int k = (int)(g % (size_t)maxout);
 		const size_t src = g / (size_t)maxout;
-		const int p0c = min(max(sin[src * per_source].prev_index, 0), D - 1);
+		const int p0c = channel::schedule(sin[src * per_source].prev_index, T, D).p0c;
 		if (k >= min((T + p0c) / D, maxout)) continue;
 		uint32_t *x = V + (g << m);
 		int rev = 0;
@@ -351,27 +314,10 @@ k_bank_scatter(const uint32_t *__restrict__ V, const int32_t *__restrict__ bins,
 		const int k = (int)(g % (size_t)maxout);
 		const size_t src = s / (size_t)per_source;
 		const int c = (int)(s % (size_t)per_source);
-		const int p0 = sin[src * per_source].prev_index;
-		const int p0c = min(max(p0, 0), D - 1);
-		if (k == 0) {
-			const int En = (p0 + T) / D;
-			sout[s].prev_index = p0 + T - En * D;
-			cnt[s] = En;
-		}
-		if (k >= min((T + p0c) / D, maxout)) continue;
+		const channel::Schedule sc = channel::schedule(sin[src * per_source].prev_index, T, D);
+		if (k == 0) channel::leave_schedule(sout, cnt, s, sc);
+		if (k >= min((T + sc.p0c) / D, maxout)) continue;
 		Y[s * ystride + k] = V[(((src * (size_t)maxout) + k) << m) + bins[c]];
-	}
-}
-
-__global__ void __launch_bounds__(256)
-k_bank_hist(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__restrict__ hist_in, uint8_t *__restrict__ hist_out,
-            int nsources, int T)
-{
-	RTLFM_GRID_STRIDE(g, (size_t)nsources * (kHist / 8)) {
-		const size_t src = g / (kHist / 8);
-		const int u = (int)(g % (kHist / 8));
-		reinterpret_cast<uint4 *>(hist_out + src * (size_t)(kHist * 2))[u] =
-			hist_piece(iq + src * src_stride, hist_in + src * (size_t)(kHist * 2), T, u);
 	}
 }
 

@@ -7,10 +7,8 @@
 // of the mixed samples m (channel_kernel.h: the same table, phase and rounding), on I' and on Q'.  The sum is an int32
 // that cannot overflow (rtlfm_channel_filter_check), so every order of summation gives the same bits.
 //
-// What is carried from run to run is the SOURCE's last kTail complex samples as raw bytes (at least ntaps - 1 of them
-// whatever ntaps is; bytes 127 where nothing has been consumed yet, which mix to 0 at every phase): the mixer is a pure
-// function of pos and the bytes, so a launch mixes what it needs of the tail again.  Two copies: a run reads one and
-// writes the other, and the handle changes over once per run - the two executions of verify_twice read the same tail.
+// What is carried from run to run is the source history (channel_kernel.h, kHist: at least ntaps - 1 samples whatever
+// ntaps is): the mixer is a pure function of pos and the bytes, so a launch mixes what it needs of the history again.
 //
 //   k_channel_fir        the product.  One launch from source bytes to every channel's decimated IQ, in k_channel_boxcar's
 //                        frame: a workgroup is kWaves channels of one source over a stretch of tiles; a tile's source
@@ -19,8 +17,9 @@
 //                        from 16-byte LDS reads of its window and of the taps with v_dot2_i32_i16.  Nothing at the capture
 //                        rate goes to memory.  A segment owns the outputs that end inside it and needs no warm-up but the
 //                        halo: there is no running sum, so any D goes with any segmentation.
-//   k_channel_fir_plain  the cross-check: one lane per output over what k_channel_mix left of the tail and the run.
-//   k_channel_tail       the cross-check's copy of the new tail (k_channel_fir writes it itself).
+//   k_channel_fir_plain  the cross-check: one lane per output over what k_channel_mix left of the history's last kHaloMax
+//                        samples and the run (channel::k_source_history then writes the new history; k_channel_fir
+//                        writes it itself).
 #pragma once
 
 #include "channel_kernel.h"
@@ -30,12 +29,13 @@ namespace rtlfm {
 namespace chanfir {
 
 constexpr int kMaxTaps = RTLFM_CHANNEL_MAX_TAPS;
-constexpr int kTail = 1024;      // complex samples of every source the handle carries (>= kMaxTaps - 1, a multiple of 8)
+constexpr int kHaloMax = 1024;   // samples of the history the cross-check mixes in front of a run (>= kMaxTaps - 1, a multiple of 8)
 constexpr int kTile = 1024;      // complex samples per tile (2 KiB of source bytes)
 constexpr int kWaves = channel::kWaves;
 constexpr int kGroup = 8;        // int16 per 16-byte LDS read: windows and taps are read in groups of eight
 constexpr int kPad = 16;         // int16 behind a wave's mixed samples that a window's last group may reach into
-static_assert(kTail >= kMaxTaps - 1 && kTail % kGroup == 0 && kTile % 256 == 0, "tail / tile geometry");
+static_assert(channel::kHist >= kMaxTaps - 1 && kHaloMax >= kMaxTaps - 1 && kHaloMax <= channel::kHist && kHaloMax % kGroup == 0 &&
+              kTile % 256 == 0, "history / tile geometry");
 
 // taps as the kernels read them: ntaps rounded up so that a window that starts anywhere in a group ends in a whole one
 inline int padded_taps(int ntaps) { return (ntaps + 2 * kGroup - 2) / kGroup * kGroup; }
@@ -63,42 +63,15 @@ inline void shifted_taps(const int16_t *taps, int ntaps, int16_t *out /* [kGroup
 }
 
 struct FirParams {
-	const uint8_t *iq;        // source rows
-	size_t src_stride;
-	const uint8_t *tail_in;   // [sources][kTail * 2]: the bytes in front of the run
-	uint8_t *tail_out;        // the same behind it (another buffer)
+	channel::Frame f;         // (sout: now_r, now_j stay the copy's)
+	const uint8_t *hist_in;   // [sources][channel::kHist * 2]: the bytes in front of the run
+	uint8_t *hist_out;        // the same behind it (another buffer)
 	const uint32_t *steps;    // [nstreams]
 	const uint32_t *table;    // [channel::kTableSize]
 	const uint32_t *taps8;    // shifted_taps(), as dwords
-	uint32_t pos;
-	int T, D;                 // complex samples of the run (a multiple of 256); outputs every D samples
 	int ntaps, nt8, halo, shift;
-	int maxout;               // most outputs a stream's run can have; a Y row has room for one dword more
-	int per_source, groups;
-	int segs, tiles_per_seg, ntiles;
-	uint32_t *Y;              // decimated IQ, packed int16 pairs
-	size_t ystride;           // dwords per stream
-	int32_t *cnt;             // [nstreams]
-	const state_t *sin;
-	state_t *sout;            // already a copy of sin: prev_index is written here (now_r, now_j stay the copy's)
+	int groups;               // workgroups that share a source tile = ceil(per_source / kWaves)
 };
-
-__device__ __forceinline__ int sat16(int v) { return min(max(v, -32768), 32767); }
-
-__device__ __forceinline__ uint32_t finish(int ai, int aq, int shift)
-{
-	const int r = shift ? 1 << (shift - 1) : 0;
-	return pack_iq(sat16((ai + r) >> shift), sat16((aq + r) >> shift));
-}
-
-// Where the new tail's 16-byte piece u comes from: run sample T - kTail + 8 u, or - a run shorter than the tail - the old
-// tail, shifted.  (T is a multiple of 8: nothing straddles.)
-__device__ __forceinline__ uint4 tail_piece(const uint8_t *row, const uint8_t *told, int T, int u)
-{
-	const int n = T - kTail + u * kGroup;
-	return n >= 0 ? *reinterpret_cast<const uint4 *>(row + (size_t)n * 2)
-	              : *reinterpret_cast<const uint4 *>(told + (size_t)(kTail + n) * 2);
-}
 
 // Grid: ((source * segs) + seg) * groups + group; wave w = channel group * kWaves + w of the source (k_channel_boxcar's).
 // Dynamic LDS: lds_bytes(ntaps).
@@ -114,33 +87,33 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 	uint32_t *mI = s_src + span / 2 + wave * 2 * W, *mQ = mI + W;
 	const int group = (int)(blockIdx.x % (unsigned)p.groups);
 	const int sseg = (int)(blockIdx.x / (unsigned)p.groups);
-	const int seg = sseg % p.segs;
-	const size_t src = (size_t)(sseg / p.segs);
+	const int seg = sseg % p.f.segs;
+	const size_t src = (size_t)(sseg / p.f.segs);
 	const int ch = group * kWaves + wave;
-	const bool active = ch < p.per_source;
-	const size_t s = src * (size_t)p.per_source + (size_t)(active ? ch : 0);
+	const bool active = ch < p.f.per_source;
+	const size_t s = src * (size_t)p.f.per_source + (size_t)(active ? ch : 0);
 
 	for (int i = tid; i < channel::kTableSize; i += kWaves * 64) s_table[i] = p.table[i];
 	for (int i = tid; i < kGroup * p.nt8 / 2; i += kWaves * 64) s_taps[i] = p.taps8[i];
 
-	const int t_begin = seg * p.tiles_per_seg;
-	const int t_end = min(p.ntiles, t_begin + p.tiles_per_seg);
-	const uint8_t *row = p.iq + src * p.src_stride;
-	const uint8_t *told = p.tail_in + src * (size_t)(kTail * 2);
+	const int t_begin = seg * p.f.tiles_per_seg;
+	const int t_end = min(p.f.ntiles, t_begin + p.f.tiles_per_seg);
+	const uint8_t *row = p.f.iq + src * p.f.src_stride;
+	const uint8_t *hold = p.hist_in + src * (size_t)(channel::kHist * 2);
 	const uint32_t step = p.steps[s];
-	const int D = p.D;
-	const int p0 = p.sin[s].prev_index;
-	const int p0c = min(max(p0, 0), D - 1);  // (a broken record moves outputs, never an index out of its row)
-	uint32_t *Ys = p.Y + s * p.ystride;
+	const int D = p.f.D;
+	const int p0 = p.f.sin[s].prev_index;
+	const int p0c = channel::schedule(p0, p.f.T, D).p0c;
+	uint32_t *Ys = p.f.Y + s * p.f.ystride;
 
 	for (int t = t_begin; t < t_end; t++) {
-		const int g0 = t * kTile - p.halo;  // the run sample staged first (below 0: the tail's)
+		const int g0 = t * kTile - p.halo;  // the run sample staged first (below 0: the history's)
 		__syncthreads();  // the source bytes of the tile before this one have been mixed by every wave
 		for (int u = tid; u < span / kGroup; u += kWaves * 64) {
 			const int g = g0 + u * kGroup;
 			uint4 v = make_uint4(0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu);
-			if (g < 0) v = *reinterpret_cast<const uint4 *>(told + (size_t)(kTail + g) * 2);
-			else if (g < p.T) v = *reinterpret_cast<const uint4 *>(row + (size_t)g * 2);
+			if (g < 0) v = *reinterpret_cast<const uint4 *>(hold + (size_t)(channel::kHist + g) * 2);
+			else if (g < p.f.T) v = *reinterpret_cast<const uint4 *>(row + (size_t)g * 2);
 			reinterpret_cast<uint4 *>(s_src)[u] = v;
 		}
 		__syncthreads();
@@ -148,20 +121,17 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 		// the channel's mixed samples of the halo and the tile: two per lane and turn
 		for (int i = lane; i < span / 2; i += 64) {
 			const uint32_t w = s_src[i];
-			const uint32_t ph = (p.pos + (uint32_t)(g0 + 2 * i)) * step;
+			const uint32_t ph = (p.f.pos + (uint32_t)(g0 + 2 * i)) * step;
 			int i0, q0, i1, q1;
 			channel::mix(w, 0, s_table[ph >> channel::kPhaseShift], i0, q0);
 			channel::mix(w, 1, s_table[(ph + step) >> channel::kPhaseShift], i1, q1);
 			mI[i] = pack_iq(i0, i1);
 			mQ[i] = pack_iq(q0, q1);
 		}
-		// (one wave's LDS operations complete in the order it issues them: the fences are for the compiler)
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+		channel::wave_sync();
 		// the outputs that end inside the tile, one per lane and turn: consecutive lanes store consecutive dwords
-		const int ts = t * kTile, te = min(ts + kTile, p.T);
-		const int kt0 = (ts + p0c) / D, kt1 = min((te + p0c) / D, p.maxout);
+		const int ts = t * kTile, te = min(ts + kTile, p.f.T);
+		const int kt0 = (ts + p0c) / D, kt1 = min((te + p0c) / D, p.f.maxout);
 		for (int k = kt0 + lane; k < kt1; k += 64) {
 			const int e = (k + 1) * D - p0c - 1;                            // the run sample the output is due at
 			const int l0 = min(max(e - g0 - p.ntaps + 1, 0), span - p.ntaps);  // its window's first sample, as staged
@@ -179,20 +149,19 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 				ai += (r0 + r2) + (r4 + r6);
 				aq += (r1 + r3) + (r5 + r7);
 			}
-			Ys[k] = finish(ai, aq, p.shift);
+			Ys[k] = channel::round_sat_pack(ai, aq, p.shift);
 		}
 	}
-	if (active && seg == p.segs - 1 && lane == 0) {
-		const int E = (p0 + p.T) / D;
-		p.sout[s].prev_index = p0 + p.T - E * D;
-		p.cnt[s] = E;
+	if (active && seg == p.f.segs - 1 && lane == 0) channel::leave_schedule(p.f.sout, p.f.cnt, s, channel::schedule(p0, p.f.T, D));
+	if (group == 0 && seg == p.f.segs - 1) {
+#pragma unroll
+		for (int u = tid; u < channel::kHist / kGroup; u += kWaves * 64)
+			reinterpret_cast<uint4 *>(p.hist_out + src * (size_t)(channel::kHist * 2))[u] = channel::history_piece(row, hold, p.f.T, u);
 	}
-	if (group == 0 && seg == p.segs - 1 && tid < kTail / kGroup)
-		reinterpret_cast<uint4 *>(p.tail_out + src * (size_t)(kTail * 2))[tid] = tail_piece(row, told, p.T, tid);
 }
 
 // ---- the cross-check ----
-// X: [nstreams][xstride] mixed samples, the tail's kTail in front of the run's T (k_channel_mix, twice).
+// X: [nstreams][xstride] mixed samples, the history's last kHaloMax in front of the run's T (k_channel_mix, twice).
 __global__ void __launch_bounds__(256)
 k_channel_fir_plain(const uint32_t *__restrict__ X, size_t xstride, int nstreams, int T, int D, const int16_t *__restrict__ taps,
                     int ntaps, int shift, int maxout, uint32_t *__restrict__ Y, size_t ystride, int32_t *__restrict__ cnt,
@@ -201,34 +170,17 @@ k_channel_fir_plain(const uint32_t *__restrict__ X, size_t xstride, int nstreams
 	RTLFM_GRID_STRIDE(g, (size_t)nstreams * maxout) {
 		const size_t s = g / (size_t)maxout;
 		const int k = (int)(g % (size_t)maxout);
-		const int p0 = sin[s].prev_index;
-		const int p0c = min(max(p0, 0), D - 1);
-		const int E = (p0 + T) / D;
-		if (k == 0) {
-			sout[s].prev_index = p0 + T - E * D;
-			cnt[s] = E;
-		}
-		if (k >= (T + p0c) / D) continue;
-		const uint32_t *x = X + s * xstride + kTail + ((k + 1) * D - p0c - 1);
+		const channel::Schedule sc = channel::schedule(sin[s].prev_index, T, D);
+		if (k == 0) channel::leave_schedule(sout, cnt, s, sc);
+		if (k >= (T + sc.p0c) / D) continue;
+		const uint32_t *x = X + s * xstride + kHaloMax + ((k + 1) * D - sc.p0c - 1);
 		int ai = 0, aq = 0;
 		for (int j = 0; j < ntaps; j++) {
 			const iq16 m = unpack_iq(x[-j]);
 			ai += (int)taps[j] * m.i;
 			aq += (int)taps[j] * m.q;
 		}
-		Y[s * ystride + k] = finish(ai, aq, shift);
-	}
-}
-
-__global__ void __launch_bounds__(256)
-k_channel_tail(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__restrict__ tail_in, uint8_t *__restrict__ tail_out,
-               int nsources, int T)
-{
-	RTLFM_GRID_STRIDE(g, (size_t)nsources * (kTail / kGroup)) {
-		const size_t src = g / (kTail / kGroup);
-		const int u = (int)(g % (kTail / kGroup));
-		reinterpret_cast<uint4 *>(tail_out + src * (size_t)(kTail * 2))[u] =
-			tail_piece(iq + src * src_stride, tail_in + src * (size_t)(kTail * 2), T, u);
+		Y[s * ystride + k] = channel::round_sat_pack(ai, aq, shift);
 	}
 }
 

@@ -13,6 +13,10 @@
 //   k_channel_boxcar   low_pass() (src/rtl_fm.c:461-481) behind the mixer in one launch, source bytes to decimated IQ:
 //                      a workgroup stages an 8 KiB tile of ONE source in LDS once, and each of its waves mixes and sums
 //                      it for another channel of that source.  Nothing at the capture rate goes back to memory.
+//   k_source_history   the cross-checks' copy of the carried source history (the one-launch kernels write it themselves).
+//
+// The channel filter (channel_fir_kernel.h) and the channel bank (channel_bank_kernel.h) stand in k_channel_boxcar's place
+// and share what is here: the launch frame, the output schedule, the rounding of a sum and the source history.
 #pragma once
 
 #include <cmath>
@@ -34,6 +38,12 @@ constexpr int kRowStride = kRowDwords + 4;   // rows 144 bytes apart: the lanes 
 constexpr int kMaxD = kTileSamples;          // up to here one warm-up tile reaches back a whole boxcar; beyond, one segment
 constexpr int kStageMinD = 4;                // from here on a tile's outputs of a channel leave through LDS, as whole lines
 constexpr int kOutCap = kTileSamples / kStageMinD + 8;  // ... and this is room for them (4096 / D + 1 at most)
+// The history: what the handle carries from run to run for the filter and the bank is every SOURCE's last kHist complex
+// samples as raw bytes (bytes 127 where nothing has been consumed yet: they mix to 0 at every phase), in two copies: a run
+// reads one and writes the other, and the handle changes over once per run - the two executions of verify_twice read the
+// same history.
+constexpr int kHist = 4096;
+static_assert(kHist % 8 == 0, "the history moves in 16-byte pieces");
 
 // the table as rtlfm_channel_table hands it out: [i][0] = lround(16384 cos(2 pi i / 1024)), [i][1] = the same of sin
 inline void build_table(int16_t *cos_sin)
@@ -60,6 +70,81 @@ __device__ __forceinline__ void mix(uint32_t w, int half, uint32_t cs, int &i, i
 	const pk16 c_ms = c_s * (pk16){1, -1};
 	i = __builtin_amdgcn_sdot2(xy, c_s, 8192, false) >> 14;
 	q = __builtin_amdgcn_sdot2(yx, c_ms, 8192, false) >> 14;
+}
+
+// (one wave's LDS operations complete in the order it issues them: the fences are for the compiler)
+__device__ __forceinline__ void wave_sync()
+{
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// an int32 sum of the filter or the bank as a sample: rounded, shifted, saturated, packed
+__device__ __forceinline__ uint32_t round_sat_pack(int ai, int aq, int shift)
+{
+	const int r = shift ? 1 << (shift - 1) : 0;
+	return pack_iq(min(max((ai + r) >> shift, -32768), 32767), min(max((aq + r) >> shift, -32768), 32767));
+}
+
+// What every front end has in common: the run, its cut into segments, and where the results go.
+struct Frame {
+	const uint8_t *iq;        // source rows
+	size_t src_stride;
+	uint32_t pos;             // complex samples consumed before this run (mod 2^32: all the phase needs)
+	int T;                    // complex samples of the run (a multiple of 256: buffers are multiples of 512 bytes)
+	int D;                    // outputs every D samples
+	int maxout;               // most outputs a stream's run can have; a Y row has room for one dword more
+	int per_source;           // channels per source
+	int segs, tiles_per_seg, ntiles;
+	uint32_t *Y;              // decimated IQ, packed int16 pairs
+	size_t ystride;           // dwords per stream
+	int32_t *cnt;             // [nstreams] outputs of the run
+	const state_t *sin;
+	state_t *sout;            // already a copy of sin: prev_index (the boxcar: and now_r, now_j) is written here
+};
+
+// Where a run's outputs fall: with p0 = prev_index samples of an output already consumed, output k is due at run sample
+// (k + 1) D - p0 - 1 (low_pass(), src/rtl_fm.c:461-481).  The count and the record take p0 as it is; the filter and the
+// bank place their outputs by p0c (a broken record moves outputs, never an index out of its row).
+struct Schedule {
+	int p0c;         // p0 inside [0, D)
+	int E;           // outputs of the run
+	int prev_index;  // p0 of the next run
+};
+__device__ __forceinline__ Schedule schedule(int p0, int T, int D)
+{
+	Schedule sc;
+	sc.p0c = min(max(p0, 0), D - 1);
+	sc.E = (p0 + T) / D;
+	sc.prev_index = p0 + T - sc.E * D;
+	return sc;
+}
+__device__ __forceinline__ void leave_schedule(state_t *sout, int32_t *cnt, size_t s, const Schedule &sc)
+{
+	sout[s].prev_index = sc.prev_index;
+	cnt[s] = sc.E;
+}
+
+// Where the new history's 16-byte piece u comes from: run sample T - kHist + 8 u, or - a run shorter than the history -
+// the old history, shifted.  (T is a multiple of 8: nothing straddles.)
+__device__ __forceinline__ uint4 history_piece(const uint8_t *row, const uint8_t *hold, int T, int u)
+{
+	const int n = T - kHist + u * 8;
+	return n >= 0 ? *reinterpret_cast<const uint4 *>(row + (size_t)n * 2)
+	              : *reinterpret_cast<const uint4 *>(hold + (size_t)(kHist + n) * 2);
+}
+
+__global__ void __launch_bounds__(256)
+k_source_history(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__restrict__ hist_in, uint8_t *__restrict__ hist_out,
+                 int nsources, int T)
+{
+	RTLFM_GRID_STRIDE(g, (size_t)nsources * (kHist / 8)) {
+		const size_t src = g / (kHist / 8);
+		const int u = (int)(g % (kHist / 8));
+		reinterpret_cast<uint4 *>(hist_out + src * (size_t)(kHist * 2))[u] =
+			history_piece(iq + src * src_stride, hist_in + src * (size_t)(kHist * 2), T, u);
+	}
 }
 
 // ---------------------------------------------------------------- k_channel_mix ----
@@ -101,21 +186,10 @@ k_channel_mix(const uint8_t *__restrict__ iq, size_t src_stride, uint32_t L, int
 
 // ------------------------------------------------------------- k_channel_boxcar ----
 struct BoxParams {
-	const uint8_t *iq;        // source rows
-	size_t src_stride;
+	Frame f;                  // (D: the boxcar's length)
 	const uint32_t *steps;    // [nstreams]
 	const uint32_t *table;    // [kTableSize]
-	uint32_t pos;             // complex samples consumed before this run (mod 2^32: all the phase needs)
-	int T;                    // complex samples of the run (a multiple of 256: buffers are multiples of 512 bytes)
-	int D;                    // boxcar length
-	int maxout;               // most outputs a stream's run can have; a Y row has room for one dword more
-	int per_source, groups;   // channels per source; workgroups that share a source tile = ceil(per_source / kWaves)
-	int segs, tiles_per_seg, ntiles;
-	uint32_t *Y;              // decimated IQ, packed int16 pairs
-	size_t ystride;           // dwords per stream
-	int32_t *cnt;             // [nstreams] outputs of the run
-	const state_t *sin;
-	state_t *sout;            // already a copy of sin: now_r, now_j, prev_index are written here
+	int groups;               // workgroups that share a source tile = ceil(per_source / kWaves)
 };
 
 // inclusive prefix sum over the wave's 64 lanes (wrapping)
@@ -151,19 +225,19 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const int group = (int)(blockIdx.x % (unsigned)p.groups);
 	const int sseg = (int)(blockIdx.x / (unsigned)p.groups);
-	const int seg = sseg % p.segs;
-	const size_t src = (size_t)(sseg / p.segs);
+	const int seg = sseg % p.f.segs;
+	const size_t src = (size_t)(sseg / p.f.segs);
 	const int ch = group * kWaves + wave;
-	const bool active = ch < p.per_source;
-	const size_t s = src * (size_t)p.per_source + (size_t)(active ? ch : 0);
+	const bool active = ch < p.f.per_source;
+	const size_t s = src * (size_t)p.f.per_source + (size_t)(active ? ch : 0);
 
 	for (int i = tid; i < kTableSize; i += kWaves * 64) s_table[i] = p.table[i];
 
-	const int t_begin = seg * p.tiles_per_seg;
-	const int t_end = min(p.ntiles, t_begin + p.tiles_per_seg);
+	const int t_begin = seg * p.f.tiles_per_seg;
+	const int t_end = min(p.f.ntiles, t_begin + p.f.tiles_per_seg);
 	const int t_first = seg > 0 ? t_begin - 1 : 0;  // the warm-up tile
-	const uint8_t *row = p.iq + src * p.src_stride;
-	const size_t run_bytes = (size_t)p.T * 2;
+	const uint8_t *row = p.f.iq + src * p.f.src_stride;
+	const size_t run_bytes = (size_t)p.f.T * 2;
 
 	// the tile a thread stages: 16-byte pieces tid and tid + 256
 	uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0;
@@ -175,12 +249,12 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 	fetch(t_first);
 
 	const uint32_t step = p.steps[s];
-	const int D = p.D;
-	const int p0 = p.sin[s].prev_index;
+	const int D = p.f.D;
+	const int p0 = p.f.sin[s].prev_index;
 	// P at the current tile's first sample, and P at the last boundary so far (wave-uniform)
 	uint32_t carry_i = 0, carry_q = 0, last_i = 0, last_q = 0;
-	if (seg == 0) { carry_i = (uint32_t)p.sin[s].now_r; carry_q = (uint32_t)p.sin[s].now_j; }
-	uint32_t *Ys = p.Y + s * p.ystride;
+	if (seg == 0) { carry_i = (uint32_t)p.f.sin[s].now_r; carry_q = (uint32_t)p.f.sin[s].now_j; }
+	uint32_t *Ys = p.f.Y + s * p.f.ystride;
 	uint32_t *outw = &s_out[STAGE ? wave * kOutCap : 0];
 
 	for (int t = t_first; t < t_end; t++) {
@@ -198,11 +272,11 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 		uint32_t k = k0;
 		// stores go to min(max(k, lo), hi): the output's place, or - in the warm-up tile, and for an index a broken record
 		// would lead to - the spare dword behind the row's last possible output
-		const uint32_t hi = (uint32_t)p.maxout, lo = emit ? 0u : hi;
+		const uint32_t hi = (uint32_t)p.f.maxout, lo = emit ? 0u : hi;
 		const uint32_t kt0 = (uint32_t)((t * kTileSamples + p0) / D);  // the first output that ends inside the tile
-		if (a < p.T) {
+		if (a < p.f.T) {
 			int left = (int)(k0 + 1) * D - p0 - a;  // samples up to and including the one the next output ends behind
-			uint32_t ph = (p.pos + (uint32_t)a) * step;
+			uint32_t ph = (p.f.pos + (uint32_t)a) * step;
 			const uint4 *rowp = reinterpret_cast<const uint4 *>(&s_tile[lane * kRowStride]);
 			for (int v = 0; v < kRowDwords / 4; v++) {
 				const uint4 raw = rowp[v];
@@ -246,12 +320,9 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 				const iq16 mine = unpack_iq(outw[at]);
 				outw[at] = pack_iq((int)((uint32_t)(int)mine.i + pex_i - prev_i), (int)((uint32_t)(int)mine.q + pex_q - prev_q));
 			}
-			// (one wave's LDS operations complete in the order it issues them: the fences are for the compiler)
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+			wave_sync();
 			if (emit) {
-				const int tile_end = min((t + 1) * kTileSamples, p.T);
+				const int tile_end = min((t + 1) * kTileSamples, p.f.T);
 				const uint32_t kt1 = min((uint32_t)((tile_end + p0) / D), hi);  // one past the last output that ends inside the tile
 				for (uint32_t i = (uint32_t)lane; kt0 + i < kt1 && i < (uint32_t)kOutCap; i += 64) Ys[kt0 + i] = outw[i];
 			}
@@ -267,13 +338,11 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 		carry_i += (uint32_t)__shfl((int)inc_i, 63, 64);
 		carry_q += (uint32_t)__shfl((int)inc_q, 63, 64);
 	}
-	if (active && seg == p.segs - 1 && lane == 0) {
+	if (active && seg == p.f.segs - 1 && lane == 0) {
 		// the partial sum that stays behind
-		const int E = (p0 + p.T) / D;
-		p.sout[s].now_r = (int)(carry_i - last_i);
-		p.sout[s].now_j = (int)(carry_q - last_q);
-		p.sout[s].prev_index = p0 + p.T - E * D;
-		p.cnt[s] = E;
+		p.f.sout[s].now_r = (int)(carry_i - last_i);
+		p.f.sout[s].now_j = (int)(carry_q - last_q);
+		leave_schedule(p.f.sout, p.f.cnt, s, schedule(p0, p.f.T, D));
 	}
 }
 

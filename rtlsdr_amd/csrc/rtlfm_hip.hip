@@ -121,16 +121,18 @@ struct rtlfm_gpu {
 	uint64_t chan_pos = 0;                 // complex samples consumed since set_channels / reset / seek: ONE counter, the streams run in lockstep
 	uint32_t *d_chan_steps = nullptr;      // [nstreams]
 	uint32_t *d_chan_table = nullptr;      // [channel::kTableSize], uploaded by the first set_channels
-	uint32_t *chan_iq = nullptr;           // what k_channel_boxcar leaves for the back half: [nstreams][chan_stride] decimated IQ
+	uint32_t *chan_iq = nullptr;           // what a channel front end leaves for the back half: [nstreams][chan_stride] decimated IQ
 	size_t chan_stride = 0;
+	// the source history of the filter and the bank (channel_kernel.h, kHist): [src_hist_srcs][channel::kHist * 2] raw bytes,
+	// every SOURCE's last samples; a run reads [src_hist_cur] and writes the other
+	uint8_t *d_src_hist[2] = {nullptr, nullptr};
+	int src_hist_cur = 0, src_hist_srcs = 0;
 	// the channel filter (channel_fir_kernel.h; rtlfm_gpu_set_channel_filter): acts while channels are on
 	int fir_ntaps = 0, fir_shift = 0;      // 0 taps: none, the boxcar
 	std::vector<int16_t> fir_taps;         // what the getter hands back
 	int16_t *d_fir_taps = nullptr;         // [ntaps], k_channel_fir_plain's
 	uint32_t *d_fir_taps8 = nullptr;       // chanfir::shifted_taps(), k_channel_fir's
-	uint8_t *d_chan_tail[2] = {nullptr, nullptr};  // [nstreams][chanfir::kTail * 2] raw bytes: every SOURCE's last samples; a run reads [chan_tail_cur] and writes the other
-	int chan_tail_cur = 0;
-	uint32_t *chan_fir_x = nullptr;        // path 1: k_channel_mix's samples of the tail and the run, [nstreams][chan_fir_xstride]
+	uint32_t *chan_fir_x = nullptr;        // path 1: k_channel_mix's samples of the history's end and the run, [nstreams][chan_fir_xstride]
 	size_t chan_fir_xstride = 0;
 	// the channel bank (channel_bank_kernel.h; rtlfm_gpu_set_channel_bank): while on it takes the mixer paths' place
 	int bank_m = 0, bank_K = 0, bank_ntaps = 0, bank_shift = 0;  // K == 0: none
@@ -141,8 +143,6 @@ struct rtlfm_gpu {
 	uint32_t *d_bank_tw = nullptr;         // [K] twiddles per stage, doubled and packed
 	int16_t *d_bank_sine = nullptr;        // [3 K / 4] sine_table(m), k_bank_fft's
 	int32_t *d_bank_bins = nullptr;        // [chan_per]
-	uint8_t *d_bank_hist[2] = {nullptr, nullptr};  // [bank_hist_srcs][chanbank::kHist * 2] raw bytes; a run reads [bank_hist_cur] and writes the other
-	int bank_hist_cur = 0, bank_hist_srcs = 0;
 	uint32_t *bank_v = nullptr;            // path 1: [sources][maxout][K] sums, transformed in place
 	size_t bank_v_dwords = 0;
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
@@ -558,9 +558,8 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
 	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth,
 	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq,
-	                h->d_fir_taps, h->d_fir_taps8, h->d_chan_tail[0], h->d_chan_tail[1], h->chan_fir_x,
-	                h->d_bank_taps, h->d_bank_taps2, h->d_bank_tw, h->d_bank_sine, h->d_bank_bins, h->d_bank_hist[0], h->d_bank_hist[1],
-	                h->bank_v};
+	                h->d_src_hist[0], h->d_src_hist[1], h->d_fir_taps, h->d_fir_taps8, h->chan_fir_x,
+	                h->d_bank_taps, h->d_bank_taps2, h->d_bank_tw, h->d_bank_sine, h->d_bank_bins, h->bank_v};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
 	delete[] h->mute_left;
@@ -581,16 +580,31 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	return 0;
 }
 
-// The channel filter's history - every source's carried bytes - back to 127: mixed zeros, m[n < 0] = 0.  On the handle's
-// stream: behind the runs already queued, in front of the next.
-static int chan_tail_clear(rtlfm_gpu *h)
+// The source history - every source's carried bytes - back to 127: mixed zeros, m[n < 0] = 0 and x[n < 0] = 0.  On the
+// handle's stream: behind the runs already queued, in front of the next.
+static int history_clear(rtlfm_gpu *h)
 {
-	// (the bank's history likewise: x = 0 before this point)
-	if (h->d_bank_hist[0])
-		HIP_TRY(hipMemsetAsync(h->d_bank_hist[h->bank_hist_cur], 127, (size_t)h->bank_hist_srcs * chanbank::kHist * 2, h->stream));
-	if (!h->d_chan_tail[0]) return 0;
-	HIP_TRY(hipMemsetAsync(h->d_chan_tail[h->chan_tail_cur], 127, (size_t)h->nstreams * chanfir::kTail * 2, h->stream));
+	if (!h->d_src_hist[0]) return 0;
+	HIP_TRY(hipMemsetAsync(h->d_src_hist[h->src_hist_cur], 127, (size_t)h->src_hist_srcs * channel::kHist * 2, h->stream));
 	return 0;
+}
+
+// The history's two copies, for the sources there are now: allocated or grown (never shrunk) once channels are on and a
+// filter or a bank is set - a filter may be set while channels are off, when nobody knows how many sources there will be -
+// and cleared, as every caller is about to ask anyway (what a fresh allocation holds must not reach a run).  The handle is
+// idle: its callers have waited for it.
+static int ensure_history(rtlfm_gpu *h)
+{
+	const int nsrc = h->chan_per > 0 && (h->fir_ntaps > 0 || h->bank_K > 0) ? h->nstreams / h->chan_per : 0;
+	if (h->src_hist_srcs < nsrc) {
+		h->src_hist_srcs = 0;  // (until both copies are there: chan_run_prepare refuses a run without them)
+		for (int i = 0; i < 2; i++) {
+			if (h->d_src_hist[i]) { hipFree(h->d_src_hist[i]); h->d_src_hist[i] = nullptr; }
+			HIP_TRY(hipMalloc(&h->d_src_hist[i], (size_t)nsrc * channel::kHist * 2));
+		}
+		h->src_hist_srcs = nsrc;
+	}
+	return history_clear(h);
 }
 
 extern "C" int rtlfm_gpu_reset(rtlfm_gpu *h)
@@ -603,7 +617,7 @@ extern "C" int rtlfm_gpu_reset(rtlfm_gpu *h)
 	HIP_TRY(hipMemcpy(h->st[h->st_cur], init.data(), init.size() * sizeof(state_t), hipMemcpyHostToDevice));
 	ingest_reset(h);
 	h->chan_pos = 0;
-	return chan_tail_clear(h);
+	return history_clear(h);
 }
 
 extern "C" int rtlfm_gpu_state_get(rtlfm_gpu *h, int stream, rtlfm_stream_state *st)
@@ -795,16 +809,16 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	h->chan_per = per_source;
 	h->chan_pos = 0;
 	h->bank_K = 0;  // (the bank's bins belong to the old per_source)
-	return chan_tail_clear(h);
+	return ensure_history(h);
 }
 
 extern "C" int rtlfm_gpu_channels_seek(rtlfm_gpu *h, uint64_t pos)
 {
 	if (!h) return -EINVAL;
 	h->chan_pos = pos;  // (read by the next run's launch; runs already queued took theirs by value)
-	if (!h->d_chan_tail[0] && !h->d_bank_hist[0]) return 0;
+	if (!h->d_src_hist[0]) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	return chan_tail_clear(h);  // (the filter's and the bank's history belong to the old position)
+	return history_clear(h);  // (the history belongs to the old position)
 }
 
 // ---- the channel filter: a caller-supplied FIR in the boxcar's place (include/rtlfm_hip.h, channel_fir_kernel.h) ----
@@ -860,8 +874,6 @@ extern "C" int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, i
 		if (!h->d_fir_taps) HIP_TRY(hipMalloc(&h->d_fir_taps, RTLFM_CHANNEL_MAX_TAPS * sizeof(int16_t)));
 		if (!h->d_fir_taps8)
 			HIP_TRY(hipMalloc(&h->d_fir_taps8, (size_t)chanfir::kGroup * chanfir::padded_taps(RTLFM_CHANNEL_MAX_TAPS) * sizeof(int16_t)));
-		for (int i = 0; i < 2; i++)
-			if (!h->d_chan_tail[i]) HIP_TRY(hipMalloc(&h->d_chan_tail[i], (size_t)h->nstreams * chanfir::kTail * 2));
 		std::vector<int16_t> t8((size_t)chanfir::kGroup * chanfir::padded_taps(ntaps));
 		chanfir::shifted_taps(taps, ntaps, t8.data());
 		HIP_TRY(hipMemcpy(h->d_fir_taps, taps, (size_t)ntaps * sizeof(int16_t), hipMemcpyHostToDevice));
@@ -872,7 +884,7 @@ extern "C" int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, i
 	}
 	h->fir_ntaps = ntaps;
 	h->fir_shift = ntaps > 0 ? shift : 0;
-	return chan_tail_clear(h);
+	return ensure_history(h);  // (cleared also where the bank is on and the filter rests: one history)
 }
 
 // ---- the channel bank: uniform channels by polyphase sums and one fix_fft (include/rtlfm_hip.h, channel_bank_kernel.h) ----
@@ -921,18 +933,10 @@ extern "C" int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bi
 	HIP_TRY(sync_all(h));
 	if (K == 0) {
 		h->bank_K = 0;
-		return chan_tail_clear(h);
+		return history_clear(h);
 	}
 	int m = 0;
 	while ((1 << m) != K) m++;
-	const int nsrc = h->nstreams / h->chan_per;
-	if (h->bank_hist_srcs < nsrc) {
-		for (int i = 0; i < 2; i++) {
-			if (h->d_bank_hist[i]) { hipFree(h->d_bank_hist[i]); h->d_bank_hist[i] = nullptr; }
-			HIP_TRY(hipMalloc(&h->d_bank_hist[i], (size_t)nsrc * chanbank::kHist * 2));
-		}
-		h->bank_hist_srcs = nsrc;
-	}
 	std::vector<int32_t> b((size_t)h->chan_per);
 	for (int c = 0; c < h->chan_per; c++) b[c] = bins ? bins[c] : c;
 	const chanbank::Geometry g = chanbank::geometry(m, ntaps, h->cfg.downsample);
@@ -959,7 +963,7 @@ extern "C" int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bi
 	h->bank_taps.assign(taps, taps + ntaps);
 	h->bank_bins = b;
 	h->bank_m = m; h->bank_K = K; h->bank_ntaps = ntaps; h->bank_shift = shift;
-	return chan_tail_clear(h);
+	return ensure_history(h);
 }
 
 extern "C" int rtlfm_gpu_get_channel_bank(rtlfm_gpu *h, int *K, int32_t *bins, int bins_cap, int16_t *taps, int taps_cap, int *ntaps,
@@ -2186,196 +2190,181 @@ static int run_boxfused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_st
 	return run_back_half(h, h->deepA, h->deep_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
 }
 
-// Channels on, the boxcar: k_channel_boxcar takes the source bytes to every channel's decimated IQ in one launch
-// (channel_kernel.h), then full_demod() goes on as behind low_pass() (run_back_half).  -M raw without the squelch: what
-// the launch leaves IS the output and goes straight into the caller's rows, as run_boxfused_emit's.
-static int run_channels(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                        size_t out_stride, int32_t *d_out_len)
+// Channels on.  One of three front ends takes the source bytes to every channel's decimated IQ (chan_iq), then full_demod()
+// goes on as behind low_pass() (run_back_half).  What the three share of a run:
+struct ChanRun {
+	int N0, D, Tin;        // complex samples per buffer, outputs every D of them, complex samples of the run
+	bool varcnt;           // D does not divide a buffer: per-stream counts
+	int T, maxout, nsrc;   // outputs of a stream's run (with varcnt: at most), the most a run can have, sources
+	int nblocks;
+	TailPlan tp;
+	int target_waves;      // for channel::plan
+	bool raw_direct;       // the boxcar alone: the launch's rows ARE the output
+	int32_t *dcnt;
+	const state_t *sin;
+	state_t *sout;
+	const uint8_t *hist_in;  // the source history in front of the run
+	uint8_t *hist_out;       // ... and behind it; rtlfm_gpu_run_device changes over once per run
+	channel::Frame f;        // (segs, tiles_per_seg, ntiles: the front end's own)
+};
+
+static int chan_run_prepare(rtlfm_gpu *h, bool box, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
+                            size_t out_stride, ChanRun &cr)
 {
 	const rtlfm_cfg &c = h->cfg;
 	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	const int N0 = (int)(c.block_len / 2), D = c.downsample;
-	const int Tin = nblocks * N0;
-	const bool varcnt = (N0 % D) != 0;
-	const int T = varcnt ? Tin / D + 1 : Tin / D;
-	// (a row the launch writes has one spare dword behind its last possible output: channel_kernel.h)
-	const bool raw_direct = c.mode == RTLFM_MODE_RAW && !c.squelch_level && !c.report_levels && out_stride / 2 >= (size_t)Tin / D + 2;
-	if (!raw_direct && !h->chan_iq) {
-		h->chan_stride = (((size_t)h->cap_blocks * N0) / D + 1 + 16 + 3) & ~(size_t)3;  // rows start on 16-byte lines
+	cr.N0 = (int)(c.block_len / 2); cr.D = c.downsample;
+	cr.Tin = nblocks * cr.N0;
+	cr.varcnt = (cr.N0 % cr.D) != 0;
+	cr.T = cr.varcnt ? cr.Tin / cr.D + 1 : cr.Tin / cr.D;
+	cr.maxout = cr.Tin / cr.D + 1;
+	cr.nsrc = S / h->chan_per;
+	cr.nblocks = nblocks;
+	if (!box && h->src_hist_srcs < cr.nsrc) return -ENOMEM;  // (ensure_history failed in the setter, which said so)
+	// -M raw without the squelch behind the boxcar: what the launch leaves IS the output and goes straight into the caller's
+	// rows, as run_boxfused_emit's (a row the launch writes has one spare dword behind its last possible output: channel_kernel.h)
+	cr.raw_direct = box && c.mode == RTLFM_MODE_RAW && !c.squelch_level && !c.report_levels && out_stride / 2 >= (size_t)cr.Tin / cr.D + 2;
+	if (!cr.raw_direct && !h->chan_iq) {
+		h->chan_stride = (((size_t)h->cap_blocks * cr.N0) / cr.D + 1 + 16 + 3) & ~(size_t)3;  // rows start on 16-byte lines
 		HIP_TRY(hipMalloc(&h->chan_iq, (size_t)S * h->chan_stride * sizeof(uint32_t)));
 	}
-	TailPlan tp = plan_tail(h, nblocks);
+	cr.tp = plan_tail(h, nblocks);
 	int r;
-	if (!raw_direct && tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
-	channel::BoxParams p{};
-	p.iq = d_iq; p.src_stride = stream_stride;
-	p.steps = h->d_chan_steps; p.table = h->d_chan_table;
-	p.pos = (uint32_t)h->chan_pos;
-	p.T = Tin; p.D = D;
-	p.per_source = h->chan_per; p.groups = (h->chan_per + channel::kWaves - 1) / channel::kWaves;
-	p.ntiles = (Tin + channel::kTileSamples - 1) / channel::kTileSamples;
-	channel::plan(S, p.ntiles, D, tp.any() ? h->fws.target_waves_tail : h->fws.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg,
-	              &p.segs, &p.tiles_per_seg);
-	p.Y = raw_direct ? reinterpret_cast<uint32_t *>(d_out) : h->chan_iq;
-	p.ystride = raw_direct ? out_stride / 2 : h->chan_stride;
-	p.maxout = Tin / D + 1;
-	int32_t *dcnt = h->d_cnt[h->step & 1];
-	p.cnt = dcnt;
-	p.sin = h->st[h->st_cur]; p.sout = h->st[(h->st_cur + 1) % 3];
-	const size_t grid = (size_t)(S / h->chan_per) * p.segs * p.groups;
-	if (grid > 0x7fffffffu) return -E2BIG;
-	std::pair<hipEvent_t, hipEvent_t> ev;
-	if ((r = timing_begin(h, ev)) < 0) return r;
-	if (D >= channel::kStageMinD) channel::k_channel_boxcar<true><<<(unsigned)grid, channel::kWaves * 64, 0, q>>>(p);
-	else channel::k_channel_boxcar<false><<<(unsigned)grid, channel::kWaves * 64, 0, q>>>(p);
-	if ((r = timing_end(h, ev)) < 0) return r;
-	if (raw_direct) return raw_out_len(h, d_out_len, varcnt ? dcnt : nullptr, T);
-	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
+	if (!cr.raw_direct && cr.tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
+	cr.target_waves = cr.tp.any() ? h->fws.target_waves_tail : h->fws.target_waves;
+	cr.dcnt = h->d_cnt[h->step & 1];
+	cr.sin = h->st[h->st_cur]; cr.sout = h->st[(h->st_cur + 1) % 3];
+	cr.hist_in = h->d_src_hist[h->src_hist_cur]; cr.hist_out = h->d_src_hist[h->src_hist_cur ^ 1];
+	channel::Frame &f = cr.f;
+	f = channel::Frame{};
+	f.iq = d_iq; f.src_stride = stream_stride;
+	f.pos = (uint32_t)h->chan_pos;
+	f.T = cr.Tin; f.D = cr.D;
+	f.maxout = cr.maxout;
+	f.per_source = h->chan_per;
+	f.Y = cr.raw_direct ? reinterpret_cast<uint32_t *>(d_out) : h->chan_iq;
+	f.ystride = cr.raw_direct ? out_stride / 2 : h->chan_stride;
+	f.cnt = cr.dcnt; f.sin = cr.sin; f.sout = cr.sout;
+	return 0;
 }
 
-// Channels on with a filter set (rtlfm_gpu_set_channel_filter): the filter in the boxcar's place, then run_back_half() as
-// behind low_pass().  fused: k_channel_fir, one launch from source bytes to decimated IQ; else the cross-check -
-// k_channel_mix over the carried tail and over the run, k_channel_fir_plain, k_channel_tail.  Both read the tail
-// d_chan_tail[chan_tail_cur] and write the other; rtlfm_gpu_run_device changes over once per run.
-static int run_channels_fir(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                            size_t out_stride, int32_t *d_out_len)
+// The boxcar: k_channel_boxcar, one launch (channel_kernel.h).
+static int launch_channel_boxcar(rtlfm_gpu *h, const ChanRun &cr)
 {
-	const rtlfm_cfg &c = h->cfg;
+	channel::BoxParams p{};
+	p.f = cr.f;
+	p.steps = h->d_chan_steps; p.table = h->d_chan_table;
+	p.groups = (h->chan_per + channel::kWaves - 1) / channel::kWaves;
+	p.f.ntiles = (cr.Tin + channel::kTileSamples - 1) / channel::kTileSamples;
+	channel::plan(h->nstreams, p.f.ntiles, cr.D, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs, &p.f.tiles_per_seg);
+	const size_t grid = (size_t)cr.nsrc * p.f.segs * p.groups;
+	if (grid > 0x7fffffffu) return -E2BIG;
+	if (cr.D >= channel::kStageMinD) channel::k_channel_boxcar<true><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+	else channel::k_channel_boxcar<false><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+	return 0;
+}
+
+// A filter set (rtlfm_gpu_set_channel_filter): the filter in the boxcar's place.  fused: k_channel_fir, one launch from
+// source bytes to decimated IQ; else the cross-check - k_channel_mix over the end of the history and over the run,
+// k_channel_fir_plain, k_source_history.
+static int launch_channel_fir(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
+{
 	const int S = h->nstreams;
 	hipStream_t q = h->stream;
-	const int N0 = (int)(c.block_len / 2), D = c.downsample;
-	const int Tin = nblocks * N0;
-	const bool varcnt = (N0 % D) != 0;
-	const int T = varcnt ? Tin / D + 1 : Tin / D;
-	const int nsrc = S / h->chan_per;
-	if (!h->chan_iq) {
-		h->chan_stride = (((size_t)h->cap_blocks * N0) / D + 1 + 16 + 3) & ~(size_t)3;  // (run_channels': one allocation serves both)
-		HIP_TRY(hipMalloc(&h->chan_iq, (size_t)S * h->chan_stride * sizeof(uint32_t)));
-	}
-	if (!fused_path && !h->chan_fir_x) {
-		h->chan_fir_xstride = (size_t)chanfir::kTail + (size_t)h->cap_blocks * N0;
-		HIP_TRY(hipMalloc(&h->chan_fir_x, (size_t)S * h->chan_fir_xstride * sizeof(uint32_t)));
-	}
-	TailPlan tp = plan_tail(h, nblocks);
-	int r;
-	if (tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
-	const uint8_t *tail_in = h->d_chan_tail[h->chan_tail_cur];
-	uint8_t *tail_out = h->d_chan_tail[h->chan_tail_cur ^ 1];
-	int32_t *dcnt = h->d_cnt[h->step & 1];
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	const int maxout = Tin / D + 1;
-	std::pair<hipEvent_t, hipEvent_t> ev;
 	if (fused_path) {
 		chanfir::FirParams p{};
-		p.iq = d_iq; p.src_stride = stream_stride;
-		p.tail_in = tail_in; p.tail_out = tail_out;
+		p.f = cr.f;
+		p.hist_in = cr.hist_in; p.hist_out = cr.hist_out;
 		p.steps = h->d_chan_steps; p.table = h->d_chan_table; p.taps8 = h->d_fir_taps8;
-		p.pos = (uint32_t)h->chan_pos;
-		p.T = Tin; p.D = D;
 		p.ntaps = h->fir_ntaps; p.nt8 = chanfir::padded_taps(h->fir_ntaps); p.halo = chanfir::halo_of(h->fir_ntaps); p.shift = h->fir_shift;
-		p.maxout = maxout;
-		p.per_source = h->chan_per; p.groups = (h->chan_per + chanfir::kWaves - 1) / chanfir::kWaves;
-		p.ntiles = (Tin + chanfir::kTile - 1) / chanfir::kTile;
+		p.groups = (h->chan_per + chanfir::kWaves - 1) / chanfir::kWaves;
+		p.f.ntiles = (cr.Tin + chanfir::kTile - 1) / chanfir::kTile;
 		// (kMaxD's limit is the boxcar's warm-up tile; here every D goes with every segmentation: D = 1 for the plan)
-		channel::plan(S, p.ntiles, 1, tp.any() ? h->fws.target_waves_tail : h->fws.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg,
-		              &p.segs, &p.tiles_per_seg);
-		p.Y = h->chan_iq; p.ystride = h->chan_stride;
-		p.cnt = dcnt; p.sin = sin; p.sout = sout;
-		const size_t grid = (size_t)nsrc * p.segs * p.groups;
+		channel::plan(S, p.f.ntiles, 1, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs, &p.f.tiles_per_seg);
+		const size_t grid = (size_t)cr.nsrc * p.f.segs * p.groups;
 		if (grid > 0x7fffffffu) return -E2BIG;
-		if ((r = timing_begin(h, ev)) < 0) return r;
 		chanfir::k_channel_fir<<<(unsigned)grid, chanfir::kWaves * 64, chanfir::lds_bytes(h->fir_ntaps), q>>>(p);
-		if ((r = timing_end(h, ev)) < 0) return r;
-	} else {
-		if ((r = timing_begin(h, ev)) < 0) return r;
-		channel::k_channel_mix<<<grid_for((size_t)S * (chanfir::kTail / 8)), 256, 0, q>>>(
-			tail_in, (size_t)chanfir::kTail * 2, (uint32_t)chanfir::kTail * 2, 1, S, h->chan_per, h->d_chan_steps, h->d_chan_table,
-			(uint32_t)h->chan_pos - (uint32_t)chanfir::kTail, h->chan_fir_x, h->chan_fir_xstride);
-		channel::k_channel_mix<<<grid_for((size_t)S * nblocks * (c.block_len / 16)), 256, 0, q>>>(
-			d_iq, stream_stride, c.block_len, nblocks, S, h->chan_per, h->d_chan_steps, h->d_chan_table, (uint32_t)h->chan_pos,
-			h->chan_fir_x + chanfir::kTail, h->chan_fir_xstride);
-		chanfir::k_channel_fir_plain<<<grid_for((size_t)S * maxout), 256, 0, q>>>(h->chan_fir_x, h->chan_fir_xstride, S, Tin, D, h->d_fir_taps,
-		                                                                       h->fir_ntaps, h->fir_shift, maxout, h->chan_iq,
-		                                                                       h->chan_stride, dcnt, sin, sout);
-		chanfir::k_channel_tail<<<grid_for((size_t)nsrc * (chanfir::kTail / 8)), 256, 0, q>>>(d_iq, stream_stride, tail_in, tail_out, nsrc, Tin);
-		if ((r = timing_end(h, ev)) < 0) return r;
+		return 0;
 	}
-	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
+	constexpr int halo = chanfir::kHaloMax;
+	if (!h->chan_fir_x) {
+		h->chan_fir_xstride = (size_t)halo + (size_t)h->cap_blocks * cr.N0;
+		HIP_TRY(hipMalloc(&h->chan_fir_x, (size_t)S * h->chan_fir_xstride * sizeof(uint32_t)));
+	}
+	// (the history's last `halo` samples: rows channel::kHist * 2 bytes apart, one buffer of halo * 2 bytes each)
+	channel::k_channel_mix<<<grid_for((size_t)S * (halo / 8)), 256, 0, q>>>(
+		cr.hist_in + (size_t)(channel::kHist - halo) * 2, (size_t)channel::kHist * 2, (uint32_t)halo * 2, 1, S, h->chan_per, h->d_chan_steps,
+		h->d_chan_table, (uint32_t)h->chan_pos - (uint32_t)halo, h->chan_fir_x, h->chan_fir_xstride);
+	channel::k_channel_mix<<<grid_for((size_t)S * cr.nblocks * (h->cfg.block_len / 16)), 256, 0, q>>>(
+		cr.f.iq, cr.f.src_stride, h->cfg.block_len, cr.nblocks, S, h->chan_per, h->d_chan_steps, h->d_chan_table, (uint32_t)h->chan_pos,
+		h->chan_fir_x + halo, h->chan_fir_xstride);
+	chanfir::k_channel_fir_plain<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->chan_fir_x, h->chan_fir_xstride, S, cr.Tin, cr.D,
+	                                                                          h->d_fir_taps, h->fir_ntaps, h->fir_shift, cr.maxout, h->chan_iq,
+	                                                                          h->chan_stride, cr.dcnt, cr.sin, cr.sout);
+	channel::k_source_history<<<grid_for((size_t)cr.nsrc * (channel::kHist / 8)), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, cr.hist_out,
+	                                                                                        cr.nsrc, cr.Tin);
+	return 0;
 }
 
-// Channels on with the bank set (rtlfm_gpu_set_channel_bank): K polyphase sums and one fix_fft per output instant in the
-// mixer paths' place, then run_back_half() as behind low_pass().  fused: k_channel_bank, one launch; else the cross-check -
-// k_bank_sums, k_bank_fft, k_bank_scatter, k_bank_hist.  Both read the history d_bank_hist[bank_hist_cur] and write the
-// other; rtlfm_gpu_run_device changes over once per run.
-static int run_channels_bank(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                             size_t out_stride, int32_t *d_out_len)
+// The bank set (rtlfm_gpu_set_channel_bank): K polyphase sums and one fix_fft per output instant in the mixer paths' place.
+// fused: k_channel_bank, one launch; else the cross-check - k_bank_sums, k_bank_fft, k_bank_scatter, k_source_history.
+static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 {
-	const rtlfm_cfg &c = h->cfg;
 	const int S = h->nstreams;
 	hipStream_t q = h->stream;
-	const int N0 = (int)(c.block_len / 2), D = c.downsample;
-	const int Tin = nblocks * N0;
-	const bool varcnt = (N0 % D) != 0;
-	const int T = varcnt ? Tin / D + 1 : Tin / D;
-	const int nsrc = S / h->chan_per;
-	if (!h->chan_iq) {
-		h->chan_stride = (((size_t)h->cap_blocks * N0) / D + 1 + 16 + 3) & ~(size_t)3;  // (run_channels': one allocation serves all)
-		HIP_TRY(hipMalloc(&h->chan_iq, (size_t)S * h->chan_stride * sizeof(uint32_t)));
+	if (fused_path) {
+		const chanbank::Geometry g = chanbank::geometry(h->bank_m, h->bank_ntaps, cr.D);
+		chanbank::BankParams p{};
+		p.f = cr.f;
+		p.hist_in = cr.hist_in; p.hist_out = cr.hist_out;
+		p.taps2 = h->d_bank_taps2; p.tw = h->d_bank_tw; p.bins = h->d_bank_bins;
+		p.m = g.m; p.Q = g.Q; p.Qp = g.Qp; p.lead = g.lead; p.F = g.F; p.Ls = g.Ls; p.Fs = g.Fs; p.shift = h->bank_shift;
+		p.f.ntiles = (cr.maxout + g.F - 1) / g.F;
+		// (frames are independent: every D goes with every segmentation - D = 1 for the plan; one workgroup per source and segment)
+		channel::plan(cr.nsrc * chanbank::kWaves, p.f.ntiles, 1, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs,
+		              &p.f.tiles_per_seg);
+		const size_t grid = (size_t)cr.nsrc * p.f.segs;
+		if (grid > 0x7fffffffu) return -E2BIG;
+		chanbank::k_channel_bank<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+		return 0;
 	}
-	const int maxout = Tin / D + 1;
-	const size_t vneed = ((size_t)nsrc * maxout) << h->bank_m;
-	if (!fused_path && h->bank_v_dwords < vneed) {
+	const size_t vneed = ((size_t)cr.nsrc * cr.maxout) << h->bank_m;
+	if (h->bank_v_dwords < vneed) {
 		if (h->bank_v) { hipFree(h->bank_v); h->bank_v = nullptr; h->bank_v_dwords = 0; }
-		const size_t most = ((size_t)nsrc * ((size_t)h->cap_blocks * N0 / D + 1)) << h->bank_m;
+		const size_t most = ((size_t)cr.nsrc * ((size_t)h->cap_blocks * cr.N0 / cr.D + 1)) << h->bank_m;
 		HIP_TRY(hipMalloc(&h->bank_v, most * sizeof(uint32_t)));
 		h->bank_v_dwords = most;
 	}
-	TailPlan tp = plan_tail(h, nblocks);
-	int r;
-	if (tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
-	const uint8_t *hist_in = h->d_bank_hist[h->bank_hist_cur];
-	uint8_t *hist_out = h->d_bank_hist[h->bank_hist_cur ^ 1];
-	int32_t *dcnt = h->d_cnt[h->step & 1];
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
+	chanbank::k_bank_sums<<<grid_for(vneed), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
+	                                                     h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.Tin, cr.D, cr.maxout,
+	                                                     cr.sin, h->bank_v);
+	chanbank::k_bank_fft<<<grid_for((size_t)cr.nsrc * cr.maxout), 256, 0, q>>>(h->bank_v, h->d_bank_sine, h->bank_m, cr.nsrc, h->chan_per, cr.Tin,
+	                                                                          cr.D, cr.maxout, cr.sin);
+	chanbank::k_bank_scatter<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->bank_v, h->d_bank_bins, h->bank_m, S, h->chan_per, cr.Tin, cr.D,
+	                                                                        cr.maxout, h->chan_iq, h->chan_stride, cr.dcnt, cr.sin, cr.sout);
+	channel::k_source_history<<<grid_for((size_t)cr.nsrc * (channel::kHist / 8)), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, cr.hist_out,
+	                                                                                        cr.nsrc, cr.Tin);
+	return 0;
+}
+
+// The channel front end of a run and what follows it.  The bank, while set, takes precedence over the filter, and the
+// filter over the boxcar; fused_path: the one-launch kernel, else the filter's or the bank's cross-check (the boxcar's is
+// run_staged behind k_channel_mix: not here).
+static int run_channels(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
+                        size_t out_stride, int32_t *d_out_len)
+{
+	const bool bank = h->bank_K > 0, fir = !bank && h->fir_ntaps > 0;
+	ChanRun cr;
+	int r = chan_run_prepare(h, !bank && !fir, d_iq, stream_stride, nblocks, d_out, out_stride, cr);
+	if (r < 0) return r;
 	std::pair<hipEvent_t, hipEvent_t> ev;
-	if (fused_path) {
-		const chanbank::Geometry g = chanbank::geometry(h->bank_m, h->bank_ntaps, D);
-		chanbank::BankParams p{};
-		p.iq = d_iq; p.src_stride = stream_stride;
-		p.hist_in = hist_in; p.hist_out = hist_out;
-		p.taps2 = h->d_bank_taps2; p.tw = h->d_bank_tw; p.bins = h->d_bank_bins;
-		p.pos = (uint32_t)h->chan_pos;
-		p.T = Tin; p.D = D;
-		p.m = g.m; p.Q = g.Q; p.Qp = g.Qp; p.lead = g.lead; p.F = g.F; p.Ls = g.Ls; p.Fs = g.Fs; p.shift = h->bank_shift;
-		p.maxout = maxout;
-		p.per_source = h->chan_per;
-		p.ntiles = (maxout + g.F - 1) / g.F;
-		// (frames are independent: every D goes with every segmentation - D = 1 for the plan; one workgroup per source and segment)
-		channel::plan(nsrc * chanbank::kWaves, p.ntiles, 1, tp.any() ? h->fws.target_waves_tail : h->fws.target_waves, h->fws.min_tiles,
-		              h->fws.tiles_per_seg, &p.segs, &p.tiles_per_seg);
-		p.Y = h->chan_iq; p.ystride = h->chan_stride;
-		p.cnt = dcnt; p.sin = sin; p.sout = sout;
-		const size_t grid = (size_t)nsrc * p.segs;
-		if (grid > 0x7fffffffu) return -E2BIG;
-		if ((r = timing_begin(h, ev)) < 0) return r;
-		chanbank::k_channel_bank<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
-		if ((r = timing_end(h, ev)) < 0) return r;
-	} else {
-		if ((r = timing_begin(h, ev)) < 0) return r;
-		chanbank::k_bank_sums<<<grid_for(vneed), 256, 0, q>>>(d_iq, stream_stride, hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
-		                                                     h->bank_shift, (uint32_t)h->chan_pos, nsrc, h->chan_per, Tin, D, maxout, sin,
-		                                                     h->bank_v);
-		chanbank::k_bank_fft<<<grid_for((size_t)nsrc * maxout), 256, 0, q>>>(h->bank_v, h->d_bank_sine, h->bank_m, nsrc, h->chan_per, Tin, D,
-		                                                                    maxout, sin);
-		chanbank::k_bank_scatter<<<grid_for((size_t)S * maxout), 256, 0, q>>>(h->bank_v, h->d_bank_bins, h->bank_m, S, h->chan_per, Tin, D,
-		                                                                     maxout, h->chan_iq, h->chan_stride, dcnt, sin, sout);
-		chanbank::k_bank_hist<<<grid_for((size_t)nsrc * (chanbank::kHist / 8)), 256, 0, q>>>(d_iq, stream_stride, hist_in, hist_out, nsrc, Tin);
-		if ((r = timing_end(h, ev)) < 0) return r;
-	}
-	return run_back_half(h, h->chan_iq, h->chan_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
+	if ((r = timing_begin(h, ev)) < 0) return r;
+	r = bank ? launch_channel_bank(h, fused_path, cr) : fir ? launch_channel_fir(h, fused_path, cr) : launch_channel_boxcar(h, cr);
+	if (r < 0) return r;
+	if ((r = timing_end(h, ev)) < 0) return r;
+	const int32_t *cnt = cr.varcnt ? cr.dcnt : nullptr;
+	if (cr.raw_direct) return raw_out_len(h, d_out_len, cnt, cr.T);
+	return run_back_half(h, h->chan_iq, h->chan_stride, cr.T, cr.N0, cr.D, nblocks, cnt, cr.tp, d_out, out_stride, d_out_len);
 }
 
 static int ensure_input_stats(rtlfm_gpu *h)
@@ -2476,12 +2465,9 @@ static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		const bool boxed = h->path != 1 && h->cfg.downsample_passes == 0;
 		if (h->path == 2 && !boxed) return -ENOTSUP;
 		HIP_TRY(hipMemcpyAsync(h->st[(h->st_cur + 1) % 3], h->st[h->st_cur], S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
-		// (a filter is only ever set on a handle without fifth_order passes: with it, both paths are the filter's)
-		// (the bank, like the filter, is only ever set without fifth_order passes; while on it takes precedence over the filter)
-		r = h->bank_K > 0 ? run_channels_bank(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
-		  : h->fir_ntaps > 0 ? run_channels_fir(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
-		  : boxed ? run_channels(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
-		          : run_staged(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
+		// (a filter or a bank is only ever set on a handle without fifth_order passes: with one, both paths are its own)
+		r = boxed || h->bank_K > 0 || h->fir_ntaps > 0 ? run_channels(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
+		                                                 : run_staged(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
 		if (r < 0) return r;
 		h->last_path = boxed ? 2 : 1;
 		HIP_TRY(hipGetLastError());
@@ -2639,8 +2625,7 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	h->st_cur = (h->st_cur + 1) % 3;
 	h->step++;
 	if (h->chan_per > 0) h->chan_pos += (uint64_t)nblocks * (h->cfg.block_len / 2);  // (once per run, also under verify_twice)
-	if (h->chan_per > 0 && h->bank_K > 0) h->bank_hist_cur ^= 1;  // (the bank's history likewise; the filter's rests while the bank is on)
-	else if (h->chan_per > 0 && h->fir_ntaps > 0) h->chan_tail_cur ^= 1;  // (the same: both executions read one tail and wrote the other)
+	if (h->chan_per > 0 && (h->bank_K > 0 || h->fir_ntaps > 0)) h->src_hist_cur ^= 1;  // (the same: both executions read one history and wrote the other)
 	h->last_nblocks = nblocks;
 	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
 	h->health_nblocks = h->opt.input_health ? nblocks : 0;

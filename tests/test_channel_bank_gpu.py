@@ -16,82 +16,16 @@ import pytest
 import channel_bank_model as bm
 import channel_model as cm
 from cases import case, make_cfg
+from channel_common import (BACK, SEEK_TO, assert_call_clears_the_history, assert_rows, bank_handle, bounded, demod, full_scale,
+                            model_runs, raw_cfg, run_gpu, run_once, steps_for, tone_fit)
+from channel_common import random_bank_taps as random_taps
 from rtlsdr_amd import capi, synth
-from rtlsdr_amd.capi import ATAN_FAST, MODE_AM, MODE_FM, MODE_RAW
+from rtlsdr_amd.capi import MODE_FM
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 RUNS = (1, 3, 2)
-
-
-def demod(cfg, ns, **options):
-    from rtlsdr_amd.demod import GpuDemod
-    return GpuDemod(cfg, ns, 0, options=options)
-
-
-def raw_cfg(D, L, nb=3, **ov):
-    return make_cfg(dict(mode=MODE_RAW, downsample=D, **ov), L, nb)
-
-
-def run_once(g, d, L, b0, nb):
-    """One run of buffers b0 .. b0 + nb of the device rows d: (per stream PCM, last_path)."""
-    o, n = g.run_torch(d[:, b0 * L:(b0 + nb) * L].contiguous())
-    g.sync()
-    o, n = o.cpu().numpy(), n.cpu().numpy()
-    return [o[s, :n[s]].copy() for s in range(g.nstreams)], g.last_path
-
-
-def run_gpu(g, rows_u8, L, runs, paths=None):
-    """Consecutive runs; paths: set_path() in front of each.  Returns (per stream PCM of all runs, last_path of every run)."""
-    d = torch.from_numpy(np.ascontiguousarray(rows_u8)).cuda()
-    per_run, seen, b0 = [], [], 0
-    for r, nb in enumerate(runs):
-        if paths is not None:
-            g.set_path(paths[r])
-        rows, p = run_once(g, d, L, b0, nb)
-        per_run.append(rows)
-        seen.append(p)
-        b0 += nb
-    return [np.concatenate([pr[s] for pr in per_run]) for s in range(g.nstreams)], seen
-
-
-def model_runs(model, src, L, runs):
-    """The model over the same runs: (per stream raw rows of all runs, per run (I, Q))."""
-    per_run, b0 = [], 0
-    for nb in runs:
-        per_run.append(model.run(src[:, b0 * L:(b0 + nb) * L]))
-        b0 += nb
-    rows = [np.concatenate([bm.raw_rows(I, Q)[s] for I, Q in per_run]) for s in range(model.S)]
-    return rows, per_run
-
-
-def random_taps(K, ntaps, seed):
-    """int16 taps and a shift that keeps most sums of full-scale input inside an int16 and lets some saturate."""
-    rng = np.random.default_rng(seed)
-    Q = (ntaps + K - 1) // K
-    return rng.integers(-2000, 2001, size=ntaps).astype(np.int16), int(np.log2(Q)) // 2 + 3
-
-
-def full_scale(rows, nbytes, seed):
-    rng = np.random.default_rng(seed)
-    src = rng.integers(0, 256, size=(rows, nbytes), dtype=np.uint8)
-    src[0, : nbytes // 2] = rng.integers(0, 2, size=nbytes // 2).astype(np.uint8) * 255
-    return src
-
-
-def bounded(rows, nbytes, seed, bound):
-    rng = np.random.default_rng(seed)
-    return (rng.integers(-bound, bound + 1, size=(rows, nbytes)) + 127).astype(np.uint8)
-
-
-def assert_rows(got, want, what):
-    for s, (a, b) in enumerate(zip(got, want, strict=True)):
-        assert a.shape == b.shape, (what, s, a.shape, b.shape)
-        if not np.array_equal(a, b):
-            bad = np.flatnonzero(a != b)
-            raise AssertionError(f"{what} stream {s}: {bad.size} of {a.size} differ, first at {bad[:8].tolist()}: "
-                                 f"{a[bad[:4]].tolist()} for {b[bad[:4]].tolist()}")
 
 
 def bins_of(kind, K, seed=0):
@@ -108,19 +42,6 @@ def bins_of(kind, K, seed=0):
 
 def ntaps_of(kind, K):
     return {"1": 1, "K-1": K - 1, "K": K, "8K": 8 * K, "5K+3": 5 * K + 3, "4096": 4096}[kind]
-
-
-def steps_for(S):
-    return np.arange(S, dtype=np.uint32) * 12345  # (kept and not used while the bank is on)
-
-
-def bank_handle(cfg, nsrc, K, bins, taps, shift, path=0, **options):
-    per = K if bins is None else len(bins)
-    g = demod(cfg, nsrc * per, **options)
-    g.set_path(path)
-    g.set_channels(per, steps=steps_for(nsrc * per))
-    g.set_channel_bank(K, taps, shift, bins=bins)
-    return g
 
 
 # ------------------------------------------- 1. shapes x taps, the model, both paths ----
@@ -276,33 +197,18 @@ def test_each_of_the_four_calls_clears_the_history(what, path):
     bins = bins_of("subset", K, 7)
     taps, shift = random_taps(K, 300, 113)
     src = full_scale(nsrc, 2 * L, 111)
-    seek_to = 123456789
-    cleared, kept = (bm.BankModel(K, taps, shift, D, nsrc, bins=bins) for _ in range(2))
-    for m in (cleared, kept):
-        m.run(src[:, :L])
-    if what in ("set_channels", "reset"):
-        cleared.pos = kept.pos = 0
-    if what == "channels_seek":
-        cleared.pos = kept.pos = seek_to
-    cleared.clear()
-    want = bm.raw_rows(*cleared.run(src[:, L:]))
-    unwanted = bm.raw_rows(*kept.run(src[:, L:]))
-    assert not any(np.array_equal(a, b) for a, b in zip(want, unwanted, strict=True))
-    with bank_handle(raw_cfg(D, L, 1), nsrc, K, bins, taps, shift, path) as g:
-        d = torch.from_numpy(src).cuda()
-        run_once(g, d, L, 0, 1)
-        if what == "set_channel_bank":
-            g.set_channel_bank(K, taps, shift, bins=bins)
-        elif what == "set_channels":
-            g.set_channels(len(bins), steps=steps_for(g.nstreams))
-            assert g.get_channel_bank()[0] == 0  # (set_channels removes the bank: bins belongs to the old per_source)
-            g.set_channel_bank(K, taps, shift, bins=bins)
-        elif what == "reset":
-            g.reset()
-        else:
-            g.channels_seek(seek_to)
-        got, _ = run_once(g, d, L, 1, 1)
-    assert_rows(got, want, f"{what} path {path}")
+
+    def again(g):
+        g.set_channels(len(bins), steps=steps_for(g.nstreams))
+        assert g.get_channel_bank()[0] == 0  # (set_channels removes the bank: bins belongs to the old per_source)
+        g.set_channel_bank(K, taps, shift, bins=bins)
+    calls = {"set_channel_bank": lambda g: g.set_channel_bank(K, taps, shift, bins=bins),
+             "set_channels": again,
+             "reset": lambda g: g.reset(),
+             "channels_seek": lambda g: g.channels_seek(SEEK_TO)}
+    assert_call_clears_the_history(lambda: bm.BankModel(K, taps, shift, D, nsrc, bins=bins),
+                                   lambda: bank_handle(raw_cfg(D, L, 1), nsrc, K, bins, taps, shift, path), calls, what, src, L,
+                                   f"{what} path {path}")
 
 
 @pytest.mark.parametrize("path", [0, 1])
@@ -332,14 +238,6 @@ def test_channel_zero_rules_the_schedule(path):
 
 
 # ------------------------------------------------------ 7. the back half, bank on ----
-
-BACK = {
-    "fmfast": dict(mode=MODE_FM, custom_atan=ATAN_FAST),
-    "am": dict(mode=MODE_AM, output_scale=3),
-    "fmfast_squelch": dict(mode=MODE_FM, custom_atan=ATAN_FAST, squelch_level=20),
-    "raw_levels": dict(mode=MODE_RAW, report_levels=1),
-}
-
 
 def gain_taps(K, ntaps, gain):
     """A Hamming sinc over 0.4 of a channel spacing whose bins have the DC gain `gain`: (taps, shift = 14 - m)."""
@@ -378,15 +276,6 @@ def test_back_half_behind_the_bank(oracle_lib, name, path):
                 assert np.array_equal(g.levels_all()[:, :nb], bm.levels_of(I, Q, nb, L // 2 // D)), (name, b0)
             b0 += nb
     assert_rows([np.concatenate(x) for x in got], want, f"{name} path {path}")
-
-
-def tone_fit(pcm, tone_hz, rate, skip):
-    """(RMS of what is left of the audio after the best fit of a tone at tone_hz and a constant, the tone's amplitude)."""
-    y = pcm[skip:].astype(np.float64)
-    t = (np.arange(y.size) + skip) / rate
-    A = np.stack([np.sin(2 * np.pi * tone_hz * t), np.cos(2 * np.pi * tone_hz * t), np.ones(y.size)], axis=1)
-    coef, *_ = np.linalg.lstsq(A, y, rcond=None)
-    return float(np.sqrt(np.mean((y - A @ coef) ** 2))), float(np.hypot(coef[0], coef[1]))
 
 
 def test_two_fm_carriers_on_their_bins(oracle_lib):

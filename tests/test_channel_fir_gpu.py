@@ -19,92 +19,18 @@ import pytest
 import channel_fir_model as fm
 import channel_model as cm
 from cases import case, make_cfg
+from channel_common import (BACK, SEEK_TO, assert_call_clears_the_history, assert_rows, bounded, demod, full_scale, make_steps,
+                            model_runs, raw_cfg, run_once)
+from channel_common import random_fir_taps as random_taps
+from channel_common import run_gpu_per_run as run_gpu
+from channel_common import tone_fit as tone_error
 from rtlsdr_amd import capi, synth
-from rtlsdr_amd.capi import ATAN_FAST, MODE_AM, MODE_FM, MODE_RAW
+from rtlsdr_amd.capi import ATAN_FAST, MODE_FM
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 RUNS = (1, 3, 2)
-
-
-def demod(cfg, ns, **options):
-    from rtlsdr_amd.demod import GpuDemod
-    return GpuDemod(cfg, ns, 0, options=options)
-
-
-def raw_cfg(D, L, nb=3, **ov):
-    return make_cfg(dict(mode=MODE_RAW, downsample=D, **ov), L, nb)
-
-
-def run_once(g, d, L, b0, nb):
-    """One run of buffers b0 .. b0 + nb of the device rows d: (per stream PCM, last_path)."""
-    o, n = g.run_torch(d[:, b0 * L:(b0 + nb) * L].contiguous())
-    g.sync()
-    o, n = o.cpu().numpy(), n.cpu().numpy()
-    return [o[s, :n[s]].copy() for s in range(g.nstreams)], g.last_path
-
-
-def run_gpu(g, rows_u8, L, runs, paths=None):
-    """Consecutive runs; paths: set_path() in front of each.  Returns (per stream PCM of all runs, per run per stream PCM,
-    last_path of every run)."""
-    d = torch.from_numpy(np.ascontiguousarray(rows_u8)).cuda()
-    per_run, seen, b0 = [], [], 0
-    for r, nb in enumerate(runs):
-        if paths is not None:
-            g.set_path(paths[r])
-        rows, p = run_once(g, d, L, b0, nb)
-        per_run.append(rows)
-        seen.append(p)
-        b0 += nb
-    return [np.concatenate([pr[s] for pr in per_run]) for s in range(g.nstreams)], per_run, seen
-
-
-def model_runs(model, src, L, runs):
-    """The model over the same runs: (per stream raw rows of all runs, per run (I, Q))."""
-    per_run, b0 = [], 0
-    for nb in runs:
-        per_run.append(model.run(src[:, b0 * L:(b0 + nb) * L]))
-        b0 += nb
-    rows = [np.concatenate([fm.raw_rows(I, Q)[s] for I, Q in per_run]) for s in range(model.S)]
-    return rows, per_run
-
-
-def make_steps(n, seed):
-    rng = np.random.default_rng(seed)
-    st = [int(v) for v in rng.integers(0, 1 << 32, size=n, dtype=np.uint64)]
-    for i, v in enumerate((0, 1 << 30, (1 << 32) - 1)[:n]):
-        st[(i * 2) % n] = v
-    return st
-
-
-def random_taps(ntaps, seed, small=False):
-    """int16 taps and a shift that keeps most outputs of full-scale input inside an int16 and lets some saturate."""
-    rng = np.random.default_rng(seed)
-    if small:
-        return rng.integers(-8, 9, size=ntaps).astype(np.int16), 0
-    return rng.integers(-2000, 2001, size=ntaps).astype(np.int16), int(np.log2(ntaps)) // 2 + 4
-
-
-def full_scale(rows, nbytes, seed):
-    rng = np.random.default_rng(seed)
-    src = rng.integers(0, 256, size=(rows, nbytes), dtype=np.uint8)
-    src[0, : nbytes // 2] = rng.integers(0, 2, size=nbytes // 2).astype(np.uint8) * 255
-    return src
-
-
-def bounded(rows, nbytes, seed, bound):
-    rng = np.random.default_rng(seed)
-    return (rng.integers(-bound, bound + 1, size=(rows, nbytes)) + 127).astype(np.uint8)
-
-
-def assert_rows(got, want, what):
-    for s, (a, b) in enumerate(zip(got, want, strict=True)):
-        assert a.shape == b.shape, (what, s, a.shape, b.shape)
-        if not np.array_equal(a, b):
-            bad = np.flatnonzero(a != b)
-            raise AssertionError(f"{what} stream {s}: {bad.size} of {a.size} differ, first at {bad[:8].tolist()}: "
-                                 f"{a[bad[:4]].tolist()} for {b[bad[:4]].tolist()}")
 
 
 # ---------------------------------------------------------------- 1. the anchor ----
@@ -277,14 +203,6 @@ def test_saturation_is_reached_and_equals_the_model(path):
 
 # ------------------------------------------------------ 7. the back half, filter on ----
 
-BACK = {
-    "fmfast": dict(mode=MODE_FM, custom_atan=ATAN_FAST),
-    "am": dict(mode=MODE_AM, output_scale=3),
-    "fmfast_squelch": dict(mode=MODE_FM, custom_atan=ATAN_FAST, squelch_level=20),
-    "raw_levels": dict(mode=MODE_RAW, report_levels=1),
-}
-
-
 @pytest.mark.parametrize("name", list(BACK))
 @pytest.mark.parametrize("path", [0, 1])
 def test_back_half_behind_the_filter(oracle_lib, name, path):
@@ -359,34 +277,19 @@ def test_each_of_the_four_calls_clears_the_history(what, path):
     src = full_scale(nsrc, 2 * L, 111)
     steps = make_steps(nsrc * per, 112)
     taps, shift = random_taps(300, 113)
-    seek_to = 123456789
-    cleared, kept = (fm.FirModel(steps, per, D, taps, shift, nsrc) for _ in range(2))
-    for m in (cleared, kept):
-        m.run(src[:, :L])
-    if what in ("set_channels", "reset"):
-        cleared.pos = kept.pos = 0
-    if what == "channels_seek":
-        cleared.pos = kept.pos = seek_to
-    cleared.clear()
-    want = fm.raw_rows(*cleared.run(src[:, L:]))
-    unwanted = fm.raw_rows(*kept.run(src[:, L:]))
-    assert not any(np.array_equal(a, b) for a, b in zip(want, unwanted, strict=True))
-    with demod(raw_cfg(D, L, 1), nsrc * per) as g:
+
+    def handle():
+        g = demod(raw_cfg(D, L, 1), nsrc * per)
         g.set_path(path)
         g.set_channels(per, steps=steps)
         g.set_channel_filter(taps, shift)
-        d = torch.from_numpy(src).cuda()
-        run_once(g, d, L, 0, 1)
-        if what == "set_channel_filter":
-            g.set_channel_filter(taps, shift)
-        elif what == "set_channels":
-            g.set_channels(per, steps=steps)
-        elif what == "reset":
-            g.reset()
-        else:
-            g.channels_seek(seek_to)
-        got, _ = run_once(g, d, L, 1, 1)
-    assert_rows(got, want, f"{what} path {path}")
+        return g
+    calls = {"set_channel_filter": lambda g: g.set_channel_filter(taps, shift),
+             "set_channels": lambda g: g.set_channels(per, steps=steps),
+             "reset": lambda g: g.reset(),
+             "channels_seek": lambda g: g.channels_seek(SEEK_TO)}
+    assert_call_clears_the_history(lambda: fm.FirModel(steps, per, D, taps, shift, nsrc), handle, calls, what, src, L,
+                                   f"{what} path {path}")
 
 
 # ---------------------------------------------------------------- 10. verify_twice ----
@@ -410,15 +313,6 @@ def test_verify_twice_sees_one_pos_and_one_tail(path):
 
 
 # ----------------------------------------------------------- 11. adjacent channels ----
-
-def tone_error(pcm, tone_hz, rate, skip):
-    """RMS of what is left of the audio after the best fit of a tone at tone_hz and a constant."""
-    y = pcm[skip:].astype(np.float64)
-    t = (np.arange(y.size) + skip) / rate
-    A = np.stack([np.sin(2 * np.pi * tone_hz * t), np.cos(2 * np.pi * tone_hz * t), np.ones(y.size)], axis=1)
-    coef, *_ = np.linalg.lstsq(A, y, rcond=None)
-    return float(np.sqrt(np.mean((y - A @ coef) ** 2))), float(np.hypot(coef[0], coef[1]))
-
 
 def test_two_fm_carriers_one_spacing_apart(oracle_lib):
     """Two FM carriers one channel spacing (fs / D) apart in one source, demodulated as two channels with /10 and -A fast.

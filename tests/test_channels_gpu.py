@@ -21,69 +21,22 @@ import pytest
 
 import channel_model as cm
 from cases import case, make_cfg
+from channel_common import assert_row_cfg as assert_rows
+from channel_common import bounded, demod
+from channel_common import make_steps_special as make_steps
+from channel_common import run_gpu_levels as run_gpu
 from rtlsdr_amd import synth
-from rtlsdr_amd.capi import ATAN_FAST, ATAN_LUT, ATAN_STD, MODE_AM, MODE_FM, MODE_RAW, MODE_USB
+from rtlsdr_amd.capi import ATAN_FAST, ATAN_LUT, MODE_AM, MODE_FM, MODE_RAW, MODE_USB
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 Q = 1 << 30
-SPECIAL_STEPS = [0, 1, 1 << 30, 1 << 31, (1 << 32) - 1]
 BOUND = 89
 
 
-def demod(cfg, ns, **options):
-    from rtlsdr_amd.demod import GpuDemod
-    return GpuDemod(cfg, ns, 0, options=options)
-
-
-def std_fm(cfg):
-    return cfg.mode == MODE_FM and cfg.custom_atan == ATAN_STD
-
-
-def assert_rows(got, want, cfg, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if np.array_equal(got, want):
-        return
-    diff = np.abs(got.astype(np.int32) - want.astype(np.int32))
-    nbad = int((diff != 0).sum())
-    where = np.flatnonzero(diff)[:8].tolist()
-    assert std_fm(cfg), f"{what}: {nbad} of {got.size} differ, first at {where}"
-    assert diff.max() <= 1 and nbad <= max(1, int(1e-4 * got.size)), f"{what}: {nbad} of {got.size} differ, max {diff.max()}"
-
-
-def run_gpu(g, rows_u8, L, runs, levels=False):
-    """Consecutive runs of runs[k] buffers from rows_u8 [rows, buffers * L].  Returns (every stream's PCM of all runs,
-    levels_all() of all runs side by side or None, last_path of every run)."""
-    d = torch.from_numpy(np.ascontiguousarray(rows_u8)).cuda()
-    outs = [[] for _ in range(g.nstreams)]
-    lv, paths, b0 = [], [], 0
-    for nb in runs:
-        o, n = g.run_torch(d[:, b0 * L:(b0 + nb) * L].contiguous())
-        g.sync()
-        o, n = o.cpu().numpy(), n.cpu().numpy()
-        for s in range(g.nstreams):
-            outs[s].append(o[s, :n[s]].copy())
-        if levels:
-            lv.append(g.levels_all())
-        paths.append(g.last_path)
-        b0 += nb
-    return [np.concatenate(x) for x in outs], (np.concatenate(lv, axis=1) if levels else None), paths
-
-
 def bounded_bytes(rows, nbytes, seed):
-    rng = np.random.default_rng(seed)
-    return (rng.integers(-BOUND, BOUND + 1, size=(rows, nbytes)) + 127).astype(np.uint8)
-
-
-def make_steps(n, seed):
-    rng = np.random.default_rng(seed)
-    st = [int(v) for v in rng.integers(0, 1 << 32, size=n, dtype=np.uint64)]
-    k = seed % len(SPECIAL_STEPS)
-    sp = SPECIAL_STEPS[k:] + SPECIAL_STEPS[:k]
-    for i in range(min(n, len(sp))):
-        st[(i * 3) % n if n >= 15 else i] = sp[i]
-    return st
+    return bounded(rows, nbytes, seed, BOUND)
 
 
 # ---------------------------------------------------------------- 1. the anchor ----

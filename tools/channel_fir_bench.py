@@ -5,7 +5,7 @@ source and step, low_pass /10's place, -A fast - with a filter set (include/rtlf
 Timed in ONE session on one GPU, alternating, after a warm-up of each:
   boxcar       no filter: k_channel_boxcar + the back half (the yardstick the filter replaces)
   fir<N>_p2    N = 4 D and 8 D taps of rtlfm_channel_lowpass(N, 0.4 / D, D) on path 2: k_channel_fir, one launch
-  fir<N>_p1    the same on path 1: k_channel_mix over tail and run, k_channel_fir_plain, k_channel_tail
+  fir<N>_p1    the same on path 1: k_channel_mix over the history's end and the run, k_channel_fir_plain, k_source_history
 each as the front end alone (the handle's event timing) and as the whole step (host clock around --steps runs that end in
 a synchronise).  The outputs of the two paths are compared for every N (they must be equal).  Prints one JSON line.
 """
