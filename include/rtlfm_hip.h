@@ -575,16 +575,9 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        anything else -EINVAL); shorter runs get shorter chunks so that about 64 K lanes work
  *   lpr_threads          lanes per workgroup of that kernel: 64, 128, 192 or 256 (default; anything else -EINVAL).  A
  *                        workgroup owns whole streams (lpr_threads / chunks of them, or one with a loop over its chunks)
- *   lpr_slim             1: deemph_filter + low_pass_real behind a front end (-M wbfm) as k_lpr_slim_plan + k_deemph_lpr_slim:
- *                        one-wave workgroups of 32 registers and no LDS, which run as a FIFTH wave per SIMD beside the next
- *                        step's four front-end waves instead of in the place of one.  Bit-exact and no faster (the /6 front
- *                        end has no issue cycles to spare: the step stays front end + tail, LAB.md I.22): kept for A/B;
- *                        0 (default): k_deemph_spec_lpr (round 5)
- *   lpr_slim_chunk       samples per lane of that kernel (default 6120: 16 chunks per stream and one wave per SIMD at the
- *                        wbfm shape; 256 ... 2^20);  lpr_slim_prio: its waves' s_setprio, 0 ... 3 (default 3)
+ *   (retired: the options of the slim -M wbfm tail, of the span form of config 3's tail and of the three-kernel -E dc answer -ENOENT)
  *   lpr_ring             1 (default): that kernel's outputs leave through LDS in aligned 64-byte pieces; 0: 16 bytes per lane
  *   squelch_fused        1 (default): rms()'s sums per buffer inside the front end + k_squelch_apply; 0: emit mode + k_squelch_*
- *   adc_separate         1: dc_block_audio as sums / smooth / apply kernels (round 4) instead of sums + k_adc_smooth_apply
  *   box_store            how k_boxcar_scan's outputs leave: -1 (default) by the launch's output size - beyond 192 MiB (what the
  *                        256 MiB Infinity Cache cannot keep anyway) as whole 128-byte lines with non-temporal stores, the
  *                        rest of a tile's last line waiting in LDS for the next tile; below, plain stores -, 0 / 1 = always
@@ -596,10 +589,6 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        kernel per step (k_deep_rest); 0: one staged kernel per stage
  *   apart_budget_gb      most device memory (GiB, default 16, never more than half of what is free) a placement
  *                        search may hold in candidate allocations; 0 = no search, plain allocations
- *   arb_span             1: config 3's one-kernel tail as k_deemph_arb_span (the span linear in LDS, 16-byte table entries,
- *                        a four-instruction filter step for a == 2) instead of k_deemph_spec_arb: 18 % fewer instructions,
- *                        the same time - kept for A/B
- *   arb_chunk            samples per lane of k_deemph_arb_span: 32 (default) or 64, anything else -EINVAL
  *   arb_serial           where deemph_filter + arbitrary_upsample (config 3's tail) runs: 1 = on the front end's stream, behind
  *                        it; 0 = on the tail's own stream beside the next front end, as every other tail; -1 (default) = in
  *                        line from 2048 streams on (1.5 % of config 3's step).  Setting it waits for the handle's work

@@ -74,12 +74,8 @@ struct rtlfm_gpu {
 	DeemphChunk *d_deemph_tab = nullptr;  // time-parallel deemph (k_deemph_scan_*): [nstreams][deemph_chunks]
 	uint32_t *d_deemph_inc = nullptr;
 	LprChunk *d_lpr_chunks = nullptr;     // low_pass_real folded into the replay pass: [nstreams][deemph_chunks]
-	SlimPlan *d_slim_plan = nullptr;      // k_lpr_slim_plan -> k_deemph_lpr_slim: [nstreams * chunks + 64]
-	size_t slim_plan_cap = 0;             // entries
-	int slim_magic_for = 0; uint32_t slim_magic = 0; size_t slim_magic_upto = 0;  // g / chunks as one multiply-high, checked up to slim_magic_upto
 	int32_t *d_arb_i = nullptr;           // k_deemph_spec_arb: (i, frac) of every output of a buffer, [arb_len2]
 	double *d_arb_frac = nullptr;
-	ArbTab *d_arb_tab = nullptr;          // k_deemph_arb_span: the same as one 16-byte entry per output
 	int arb_len2 = 0, arb_len1 = 0;
 	int deemph_chunks = 0;   // capacity of d_deemph_tab / d_deemph_inc, chunks per stream
 	int lpr_chunks_cap = 0;  // ... of d_lpr_chunks
@@ -149,7 +145,6 @@ struct rtlfm_gpu {
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
 	int2 *d_rdc_avg = nullptr;        // [nstreams*cap_blocks]
-	int32_t *d_adc_avg = nullptr;
 	struct Ingest *ing = nullptr;     // the callback side (push / run / fetch), allocated on first use
 	bool no_deemph_scan = false;      // stream-range views (ragged runs) keep to the sequential filter
 	// placement of the write streams (rtlfm_gpu_malloc_apart_ex): what the searches found and what they cost
@@ -169,17 +164,11 @@ struct rtlfm_gpu {
 		int deemph_sequential = 0, deemph_four_pass = 0, lpr_separate = 0, lpr_scalar_stores = 0, tail_sync = 0;
 		int lpr_chunk = 5440;  // samples per lane of the one-pass deemph + low_pass_real kernel (round 5: 2720 -> 5440 with the outputs leaving through LDS)
 		int deep_rest = 1;     // 0: the passes beyond six, generic_fir and the demodulator as a launch each (round 4) instead of k_deep_rest
-		int adc_separate = 0;  // 1: dc_block_audio_filter as three kernels (sums, smoothing, subtraction) instead of two
 		int squelch_fused = 1; // 0: the squelch / -L behind the boxcar through the emit mode and k_squelch_rms / _hits / _zero / k_fm_demod (round 4) also where the front end can take rms()'s sums itself
 		int lpr_ring = 1;      // 0: the one-pass deemph + low_pass_real kernel's outputs leave in 16-byte groups from registers (round 3) instead of 64-byte pieces from LDS
-		int arb_span = 0;      // 1: k_deemph_arb_span instead of k_deemph_spec_arb for config 3's tail (18 % fewer instructions, the same time: LAB.md)
-		int arb_chunk = 32;    // samples per lane of k_deemph_arb_span: 32 or 64
 		int arb_serial = -1;   // deemph + arbitrary_upsample behind the front end on ITS stream: -1 = from 2048 streams on, 0 never, 1 always
 		int lpr_threads = 256; // lanes per workgroup of k_deemph_spec_lpr: 64, 128, 192 or 256
 		int arb_waves = 0;     // waves per stream of k_deemph_spec_arb: 0 = about 16384 waves in all, else 1 .. 8
-		int lpr_slim = 0;      // 1: -M wbfm's tail as k_lpr_slim_plan + k_deemph_lpr_slim - 32 registers, no LDS, one-wave workgroups: a fifth wave beside the next step's four front-end waves per SIMD instead of in place of one (round 6: built, bit-exact, and no faster - LAB.md I.22); 0: k_deemph_spec_lpr
-		int lpr_slim_prio = 3;      // s_setprio of that kernel's waves (0 .. 3)
-		int lpr_slim_chunk = 6120;  // samples per lane of that kernel: 16 chunks per stream at the wbfm shape = 1024 waves, one per SIMD
 		int verify_inject = 0; // tests: the shadow execution's first sample of stream 0 is overwritten before the comparison (it must be noticed)
 		int input_stats = 0;   // 1: k_input_stats in front of every run's front end (rtlfm_gpu_input_stats)
 		int input_stats_nt = 1; // its loads non-temporal (the A/B of LAB.md)
@@ -444,7 +433,6 @@ static int create_body(rtlfm_gpu *h)
 	HIP_TRY(hipMalloc(&h->d_adc_sums, S * h->cap_blocks * sizeof(long long)));
 	HIP_TRY(hipMalloc(&h->d_rdc_avg, (S * h->cap_blocks + 32) * sizeof(int2)));  // (+ slack: k_boxcar_scan reads kRdcMany entries from a tile's first buffer on)
 	HIP_TRY(hipMalloc(&h->d_sq_sums, S * h->cap_blocks * 2 * sizeof(uint32_t)));
-	HIP_TRY(hipMalloc(&h->d_adc_avg, S * h->cap_blocks * sizeof(int32_t)));
 	if (cfg->custom_atan == RTLFM_ATAN_LUT) {
 		// atan_lut_init(), src/rtl_fm.c:881-892 — built with the host libm, as
 		// the reference builds it
@@ -553,10 +541,10 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 		if (e) hipEventDestroy(e);
 	for (auto &p : h->ev_pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
 	for (auto &p : h->ev_free) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-	void *ptrs[] = {h->d_arb_i, h->d_arb_frac, h->d_arb_tab, h->d_deemph_tab, h->d_deemph_inc, h->d_lpr_chunks, h->deepA, h->deepB, h->bufA, h->bufB, h->res[0][0], h->res[0][1], h->res_one_block ? nullptr : (void *)h->res[1][0], h->res[1][1],
+	void *ptrs[] = {h->d_arb_i, h->d_arb_frac, h->d_deemph_tab, h->d_deemph_inc, h->d_lpr_chunks, h->deepA, h->deepB, h->bufA, h->bufB, h->res[0][0], h->res[0][1], h->res_one_block ? nullptr : (void *)h->res[1][0], h->res[1][1],
 	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
-	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg, h->d_adc_avg,
-	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_slim_plan, h->d_istats, h->d_ihealth,
+	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg,
+	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_istats, h->d_ihealth,
 	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq,
 	                h->d_src_hist[0], h->d_src_hist[1], h->d_fir_taps, h->d_fir_taps8, h->chan_fir_x,
 	                h->d_bank_taps, h->d_bank_taps2, h->d_bank_tw, h->d_bank_sine, h->d_bank_bins, h->bank_v};
@@ -1075,8 +1063,8 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"deemph_sequential", &h->opt.deemph_sequential}, {"deemph_four_pass", &h->opt.deemph_four_pass},
 		{"lpr_separate", &h->opt.lpr_separate}, {"lpr_scalar_stores", &h->opt.lpr_scalar_stores}, {"lpr_chunk", &h->opt.lpr_chunk},
 		{"tail_sync", &h->opt.tail_sync}, {"apart_budget_gb", &h->place.budget_gb}, {"ring_force_retry", &h->place.force_retry},
-		{"arb_span", &h->opt.arb_span}, {"arb_chunk", &h->opt.arb_chunk}, {"arb_waves", &h->opt.arb_waves}, {"lpr_threads", &h->opt.lpr_threads}, {"arb_serial", &h->opt.arb_serial}, {"lpr_ring", &h->opt.lpr_ring}, {"squelch_fused", &h->opt.squelch_fused}, {"adc_separate", &h->opt.adc_separate}, {"deep_rest", &h->opt.deep_rest}, {"box_store", &h->fws.box_store}, {"fused_store", &h->fws.fused_store},
-		{"verify_twice", &h->opt.verify_twice}, {"verify_inject", &h->opt.verify_inject}, {"lpr_slim", &h->opt.lpr_slim}, {"lpr_slim_chunk", &h->opt.lpr_slim_chunk}, {"lpr_slim_prio", &h->opt.lpr_slim_prio},
+		{"arb_waves", &h->opt.arb_waves}, {"lpr_threads", &h->opt.lpr_threads}, {"arb_serial", &h->opt.arb_serial}, {"lpr_ring", &h->opt.lpr_ring}, {"squelch_fused", &h->opt.squelch_fused}, {"deep_rest", &h->opt.deep_rest}, {"box_store", &h->fws.box_store}, {"fused_store", &h->fws.fused_store},
+		{"verify_twice", &h->opt.verify_twice}, {"verify_inject", &h->opt.verify_inject},
 		{"input_stats", &h->opt.input_stats}, {"input_stats_nt", &h->opt.input_stats_nt},
 		{"input_health", &h->opt.input_health},
 		{"squelch_gate", &h->opt.squelch_gate}, {"conseq_squelch", &h->opt.conseq_squelch},
@@ -1124,7 +1112,7 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 	if (!strcmp(name, "apart_budget_gb") && (value < 0 || value > 256)) return -EINVAL;
 	if ((!strcmp(name, "box_store") || !strcmp(name, "fused_store")) && (value < -1 || value > 1)) return -EINVAL;
 	// the chunk tables of the one-pass deemph + low_pass_real kernel are sized from it: keep it in a sane range
-	if ((!strcmp(name, "lpr_chunk") || !strcmp(name, "lpr_slim_chunk")) && (value < 256 || value > (1 << 20))) return -EINVAL;
+	if (!strcmp(name, "lpr_chunk") && (value < 256 || value > (1 << 20))) return -EINVAL;
 	if ((!strcmp(name, "input_stats") || !strcmp(name, "input_stats_nt") || !strcmp(name, "input_health")) && value != 0 && value != 1)
 		return -EINVAL;
 	if (!strcmp(name, "squelch_gate")) {
@@ -1135,7 +1123,6 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 		}
 	}
 	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
-	if (!strcmp(name, "arb_chunk") && value != 32 && value != 64) return -EINVAL;
 	if (!strcmp(name, "arb_waves") && (value < 0 || value > kSpecArbMaxWaves)) return -EINVAL;
 	if (!strcmp(name, "lpr_threads") && (value < 64 || value > kSpecLprThreads || value % 64)) return -EINVAL;
 	if (!strcmp(name, "arb_serial")) {
@@ -1333,421 +1320,403 @@ static bool arb_tail_in_line(const rtlfm_gpu *h, const TailPlan &tp)
 	       (h->opt.arb_serial > 0 || (h->opt.arb_serial < 0 && h->nstreams >= 2048));
 }
 
-// Does this tail run as ONE kernel (run_tail: k_deemph_spec_arb = 1, k_deemph_spec_lpr = 2), 0 if not?
-static int one_pass_tail(const rtlfm_gpu *h, const TailPlan &tp, const int16_t *cur, size_t cur_stride, int T, bool varcnt,
-                         int nblocks, int Nblk, int D)
+// The form deemph_filter takes in a run, with the resampler where one kernel does both: decided ONCE, at the top of
+// run_tail(), from the plan and the run as the front end left it.
+enum class Deemph {
+	none,
+	identity,       // a == 1: the filter is the identity on the samples and keeps the last one (k_deemph_identity)
+	sequential,     // a lane per stream (k_deemph): short runs, ragged views, an interval of candidate states beyond a wave
+	spec,           // nothing behind it, a long run: one pass OUT of place (k_deemph_spec) - plan_tail()'s promise
+	spec_lpr,       // the whole tail as one kernel: filter + low_pass_real (k_deemph_spec_lpr, -M wbfm)
+	spec_arb,       // the whole tail as one kernel: filter + arbitrary_upsample (k_deemph_spec_arb, config 3)
+	four_pass,      // few, long streams: parallel over time, in place (k_deemph_scan_a1 / _a2 / _b / _c)
+	four_pass_lpr,  // ... the filtered samples going straight into low_pass_real's accumulator (k_deemph_scan_c_lpr)
+};
+// The one-kernel tails write every field a tail of their configuration owns, for every stream, and the counts.
+static bool whole_tail(Deemph d) { return d == Deemph::spec_lpr || d == Deemph::spec_arb; }
+
+// deemph_a as the kernels take it: the step's constants, the form of its division (the kernels' MAGIC: 0 a division,
+// 1 a multiply-high, 2 a shift) and the samples a one-pass kernel settles over in front of a chunk
+struct DeemphForm { DeemphStep st; int M, Ws; };
+static DeemphForm deemph_form(int a)
 {
-	const rtlfm_cfg &c = h->cfg;
-	if (!tp.deemph || tp.post || tp.adc || h->opt.deemph_four_pass) return 0;
-	const bool scan = deemph_scans(h, T);
-	if (!scan) return 0;
-	if (tp.lpr) return h->opt.lpr_separate ? 0 : 2;
-	if (!tp.arb) return 0;
-	const int Ws = ((16 * c.deemph_a + 64 + 63) / 64) * 64;
-	const int arb_l2 = (int)((long long)Nblk * c.rate_out2 / c.rate_out);
-	const bool ok = D == 1 && !varcnt && Nblk >= 2 && arb_l2 > Nblk && (long long)(Nblk + 1) * arb_l2 < (1ll << 31) && Ws <= 256 &&
-	                (uintptr_t)cur % 16 == 0 && cur_stride % 8 == 0 && T == nblocks * Nblk;
-	return ok ? 1 : 0;
+	DeemphForm f{};
+	f.st.a = (uint32_t)a; f.st.half = (uint32_t)(a / 2);
+	const bool pow2 = a >= 1 && a <= 32768 && (a & (a - 1)) == 0;
+	const bool magic = !pow2 && a >= 2 && a <= 32768;
+	if (pow2) { while ((1u << f.st.magic) < f.st.a) f.st.magic++; }
+	else if (magic) f.st.magic = (uint32_t)((0x100000000ull + f.st.a - 1) / f.st.a);
+	f.M = pow2 ? 2 : magic ? 1 : 0;
+	f.Ws = a <= 32768 ? ((16 * a + 64 + 63) / 64) * 64 : 0;  // (the kernels that settle run for 2 a + 2 <= kDeemphGap only)
+	return f;
+}
+// ... and that form as a constant: with_magic(M, [&](auto mm) { k<decltype(mm)::value><<<...>>>(...); })
+template <class F>
+static void with_magic(int M, F &&launch)
+{
+	if (M == 2) launch(std::integral_constant<int, 2>{});
+	else if (M == 1) launch(std::integral_constant<int, 1>{});
+	else launch(std::integral_constant<int, 0>{});
 }
 
+// What the stages of one tail share: its queue, the state copies, and the samples where they stand now.
 // Buffer extents: buffer b of a stream owns the decimated samples [dec_block_begin(b),
 // dec_block_begin(b + 1)) of the run — Nblk input samples per buffer through a boxcar D with the
 // carried prev_index; (Nblk, 1) describes a uniform count of Nblk per buffer.
+struct TailRun {
+	rtlfm_gpu *h;
+	const rtlfm_cfg &c;
+	int S;
+	hipStream_t q;
+	const state_t *sin;
+	state_t *sout;
+	int16_t *cur; size_t cur_stride;
+	int T; int32_t *cnt;  // samples per stream; the per-stream counts where they differ (T is then their upper bound)
+	int nblocks, Nblk, D;
+	int16_t *final_dst; size_t final_stride;
+	int remaining_oop;    // out-of-place stages still to come: the last of them writes final_dst
+	int16_t *dst; size_t dst_stride;  // where the out-of-place stage at hand writes (out_of_place() ... arrived())
+	void out_of_place()
+	{
+		int16_t *const *res = h->res[h->step & 1];
+		dst = --remaining_oop == 0 ? final_dst : cur == res[0] ? res[1] : res[0];
+		dst_stride = remaining_oop == 0 ? final_stride : h->tstride;
+	}
+	void arrived() { cur = dst; cur_stride = dst_stride; }
+	void stage_done(const char *what) const  // option tail_sync
+	{
+		if (h->opt.tail_sync) fprintf(stderr, "rtlfm_hip[tail]: %s done (%s)\n", what, hipGetErrorString(hipStreamSynchronize(q)));
+	}
+};
+
+static Deemph deemph_route(const TailPlan &tp, const DeemphForm &f, const TailRun &r)
+{
+	const rtlfm_gpu *h = r.h;
+	if (!tp.deemph) return Deemph::none;
+	if (r.c.deemph_a == 1) return Deemph::identity;
+	// plan_tail() promised the out-of-place stage from an upper bound of T before the front end ran, and the routing
+	// (oop()) is built on it: tail_deemph_spec() keeps the promise for the runs that turn out otherwise
+	if (tp.deemph_spec) return Deemph::spec;
+	if (!deemph_scans(h, tp.post ? r.T / r.c.post_downsample : r.T)) return Deemph::sequential;
+	if (!tp.post && !tp.adc && !h->opt.deemph_four_pass) {
+		// One pass where the resampler follows directly: every chunk finds its incoming state from the W samples before
+		// it (staged_kernels.h, k_deemph_spec_lpr); a stream it cannot settle that way (silence) is redone by the
+		// kernel's own last lane for that stream.
+		if (tp.lpr && !h->opt.lpr_separate) return Deemph::spec_lpr;
+		// ... and where arbitrary_resample follows directly, on uniform buffers that it upsamples (config 3): one pass from
+		// the demodulated samples to the resampled output (k_deemph_spec_arb)
+		const int arb_l2 = (int)((long long)r.Nblk * r.c.rate_out2 / r.c.rate_out);
+		if (tp.arb && r.D == 1 && !r.cnt && r.Nblk >= 2 && arb_l2 > r.Nblk && (long long)(r.Nblk + 1) * arb_l2 < (1ll << 31) && f.Ws <= 256 &&
+		    (uintptr_t)r.cur % 16 == 0 && r.cur_stride % 8 == 0 && r.T == r.nblocks * r.Nblk)
+			return Deemph::spec_arb;
+	}
+	return tp.lpr && !tp.adc && !h->opt.lpr_separate ? Deemph::four_pass_lpr : Deemph::four_pass;
+}
+
+// Scratch that is sized by the run.  What may still be reading the old blocks has finished before they are freed, and the
+// caller's key to them says "none" from before this call until every allocation (and copy) behind it has succeeded: a
+// failure half way leaves no key beside freed or short memory.
+struct Scratch { void **p; size_t bytes; };
+static int replace_scratch(hipStream_t q, std::initializer_list<Scratch> blocks)
+{
+	for (const Scratch &b : blocks)
+		if (*b.p) { HIP_TRY(hipStreamSynchronize(q)); break; }
+	for (const Scratch &b : blocks)
+		if (*b.p) { HIP_TRY(hipFree(*b.p)); *b.p = nullptr; }
+	for (const Scratch &b : blocks) HIP_TRY(hipMalloc(b.p, b.bytes));
+	return 0;
+}
+static int grow_scratch(hipStream_t q, int *cap, int need, std::initializer_list<Scratch> blocks)
+{
+	if (need <= *cap) return 0;
+	*cap = 0;
+	const int e = replace_scratch(q, blocks);
+	if (e == 0) *cap = need;
+	return e;
+}
+
+// Samples per lane of a one-pass kernel: `want` where the run fills the GPU that way (-M wbfm at 1024 streams: 64 K lanes);
+// with fewer samples in all, shorter chunks - about 64 K lanes again, never so short that the settling (Ws samples walked
+// twice per chunk) outweighs the chunk (256 streams of rtl_fm -s 48k -r 24k -E deemp: 294 waves on 1024 SIMDs took 1.45 ms
+// for 102 M samples)
+static int fit_chunk(int want, int S, int T, int Ws)
+{
+	const long long fit = std::max((long long)S * T / 65536, std::max(6ll * Ws, 512ll));
+	return fit < want ? (int)fit : want;
+}
+
+static void tail_deemph_sequential(TailRun &r, const DeemphForm &f)
+{
+	with_magic(f.M, [&](auto mm) {
+		k_deemph<decltype(mm)::value><<<(unsigned)((r.S + 63) / 64), 64, 0, r.q>>>(r.cur, r.cur_stride, r.T, r.cnt, r.S, f.st, r.sin, r.sout);
+	});
+}
+
+// deemph_filter with no resampler behind it, a long run: ONE pass, out of place (staged_kernels.h, k_deemph_spec)
+static int tail_deemph_spec(TailRun &r, const DeemphForm &f)
+{
+	r.out_of_place();
+	const bool congruent = (((uintptr_t)r.cur ^ (uintptr_t)r.dst) & 15) == 0 && ((r.cur_stride * 2) & 15) == ((r.dst_stride * 2) & 15);
+	if (deemph_scans(r.h, r.T) && congruent) {
+		const int Lc = (fit_chunk(r.h->opt.lpr_chunk, r.S, r.T, f.Ws) + 63) & ~63;  // whole 128-byte rounds
+		const int mcd = r.T / Lc + 2;
+		const int spw = mcd >= kSpecLprThreads ? 1 : kSpecLprThreads / mcd;
+		with_magic(f.M, [&](auto mm) {
+			k_deemph_spec<decltype(mm)::value><<<(unsigned)((r.S + spw - 1) / spw), kSpecLprThreads, 0, r.q>>>(
+			    r.cur, r.cur_stride, r.dst, r.dst_stride, r.T, r.cnt, r.S, f.st, mcd, Lc, f.Ws, r.sin, r.sout);
+		});
+		r.stage_done("one pass (deemph)");
+	} else {
+		// (the plan promised an out-of-place stage and the run turned out otherwise - rows that do not share their
+		// alignment, a run that is shorter than planned: the sequential filter in place, then a copy)
+		tail_deemph_sequential(r, f);
+		HIP_TRY(hipMemcpy2DAsync(r.dst, r.dst_stride * sizeof(int16_t), r.cur, r.cur_stride * sizeof(int16_t), (size_t)r.T * sizeof(int16_t), r.S,
+		                         hipMemcpyDeviceToDevice, r.q));
+	}
+	r.arrived();
+	return 0;
+}
+
+// (i, frac) of every output of a buffer, as arbitrary_upsample's loop (src/rtl_fm.c:1114-1135) has them when it writes
+// buf2[j]: walked once here, shared by every stream and buffer
+// (d_arb_i: the i, a gap, then the padded LDS offset of sample i - 1 for k_deemph_spec_arb's resampler)
+static int arb_tables(rtlfm_gpu *h, hipStream_t q, int Nblk, int arb_l2)
+{
+	if (h->arb_len2 == arb_l2 && h->arb_len1 == Nblk) return 0;
+	std::vector<int32_t> ti(2 * (size_t)arb_l2 + kArbTabGap);
+	std::vector<double> tf((size_t)arb_l2);
+	int i = 1, tick = 0;
+	for (int j = 0; j < arb_l2; j++) {
+		ti[j] = i;
+		tf[j] = (double)tick / (double)arb_l2;
+		ti[(size_t)arb_l2 + kArbTabGap + j] = 2 * i + 16 * (i >> 5) - 2;
+		tick += Nblk;
+		if (tick > arb_l2) { tick -= arb_l2; i++; }
+		if (i >= Nblk) { i = Nblk - 1; tick = arb_l2; }
+	}
+	h->arb_len2 = 0; h->arb_len1 = 0;  // (the tables of another geometry may still be in use: replace_scratch waits)
+	const int e = replace_scratch(q, {{(void **)&h->d_arb_i, ti.size() * sizeof(int32_t)}, {(void **)&h->d_arb_frac, tf.size() * sizeof(double)}});
+	if (e < 0) return e;
+	HIP_TRY(hipMemcpy(h->d_arb_i, ti.data(), ti.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+	HIP_TRY(hipMemcpy(h->d_arb_frac, tf.data(), tf.size() * sizeof(double), hipMemcpyHostToDevice));
+	h->arb_len2 = arb_l2; h->arb_len1 = Nblk;
+	return 0;
+}
+
+// The one operation of config 3's tail: filter, resampler, state and counts
+static int tail_deemph_spec_arb(TailRun &r, const DeemphForm &f, int32_t *cnt_dst)
+{
+	rtlfm_gpu *h = r.h;
+	const int arb_l2 = (int)((long long)r.Nblk * r.c.rate_out2 / r.c.rate_out);
+	const size_t arb_lds = (size_t)(f.Ws / kArbChunk + 64) * kArbStride * sizeof(int16_t);
+	const int e = arb_tables(h, r.q, r.Nblk, arb_l2);
+	if (e < 0) return e;
+	r.out_of_place();
+	const int nspans = (r.T + 64 * kArbChunk - 1) / (64 * kArbChunk);
+	// a workgroup per stream (nothing crosses workgroups), its spans dealt to up to eight waves: about 16384
+	// waves in all - two and a half rounds of what the GPU holds, so that the last round is a small part of
+	// the launch (8192: config 3's tail alone 70 us instead of 65, LAB.md I.31)
+	const int wpw = std::max(1, std::min({h->opt.arb_waves > 0 ? h->opt.arb_waves : 16384 / r.S, nspans, kSpecArbMaxWaves}));
+	auto launch = [&](auto mm) {
+		k_deemph_spec_arb<decltype(mm)::value><<<(unsigned)r.S, 64 * wpw, arb_lds * wpw, r.q>>>(
+		    r.cur, r.cur_stride, r.T, r.S, f.st, f.Ws, nspans, r.Nblk, arb_l2, r.nblocks, h->d_arb_i, h->d_arb_frac, r.dst, r.dst_stride, r.sin,
+		    r.sout, arb_lds, cnt_dst);
+	};
+	// a == 2 (rtl_fm -s 24k -E deemp): the filter step is (x + avg + [x > avg]) >> 1
+	if (r.c.deemph_a == 2) launch(std::integral_constant<int, 3>{});
+	else with_magic(f.M, launch);
+	r.stage_done("one pass (arb)");
+	r.arrived();
+	return 0;
+}
+
+// The one operation of -M wbfm's tail
+static int tail_deemph_spec_lpr(TailRun &r, const DeemphForm &f, int32_t *cnt_dst)
+{
+	rtlfm_gpu *h = r.h;
+	const int T = r.T;
+	// chunk length of the one-pass form: about 2720 samples (2040: +1 %, 1360: +2 % on the wbfm step),
+	// and a multiple of the resampler's period fast / gcd(fast, slow) where that is short - then all
+	// chunks of a stream start at the same phase, the lanes of a wave emit at the same samples and
+	// the emission branch is taken by whole waves instead of by a few lanes every sample
+	const int Lwant = fit_chunk(h->opt.lpr_chunk, r.S, T, f.Ws);  // lpr_chunk: 256 .. 2^20 (rtlfm_gpu_set_option)
+	int Ls = Lwant;
+	int mcsp;
+	long long gg = r.c.rate_out, bb = r.c.rate_out2;
+	while (bb) { const long long t = gg % bb; gg = bb; bb = t; }
+	long long per = r.c.rate_out / gg;
+	while (per % 8) per *= 2;
+	if ((long long)T >= 48ll * Lwant) {
+		// long runs: a stream's chunks fill whole waves.  (T / 2720 + 2 = 130 chunks of the wbfm shape were two
+		// full waves and a third with ONE busy lane that issued every instruction of the walk again:
+		// SQ_INSTS_VALU 23.8 lane-operations per sample against 18.4 with packed lanes.)
+		const int n64 = (int)(((long long)T + 32ll * Lwant) / (64ll * Lwant));
+		const int lanes = 64 * (n64 < 1 ? 1 : n64);
+		long long L0 = ((long long)T + lanes - 1) / lanes;
+		L0 = per <= L0 ? per * ((L0 + per - 1) / per) : ((L0 + 7) & ~7ll);
+		Ls = (int)L0;
+		mcsp = lanes;
+	} else {
+		if (per <= Lwant) Ls = (int)(per * ((Lwant + per / 2) / per));
+		mcsp = T / Ls + 2;
+	}
+	const int e = grow_scratch(r.q, &h->lpr_chunks_cap, mcsp, {{(void **)&h->d_lpr_chunks, (size_t)r.S * mcsp * sizeof(LprChunk)}});
+	if (e < 0) return e;
+	r.out_of_place();
+	// outputs leave in 64-byte pieces through LDS (2; any row alignment), else in 16-byte groups where the rows allow
+	// it (1), else one by one (staged_kernels.h, LprSink)
+	int lpr_vec = (uintptr_t)r.dst % 16 == 0 && r.dst_stride % 8 == 0 && !h->opt.lpr_scalar_stores;
+	if (h->opt.lpr_ring && !h->opt.lpr_scalar_stores) lpr_vec = 2;
+	const int nthr = h->opt.lpr_threads;
+	const size_t lpr_lds = lpr_vec == 2 ? (size_t)nthr * kLprRingStride * sizeof(int16_t) : 0;
+	// a workgroup owns whole streams: 256 / chunks of them, or one with a loop over its chunks
+	const int spw = mcsp >= nthr ? 1 : nthr / mcsp;
+	with_magic(f.M, [&](auto mm) {
+		k_deemph_spec_lpr<decltype(mm)::value><<<(unsigned)((r.S + spw - 1) / spw), nthr, lpr_lds, r.q>>>(
+		    r.cur, r.cur_stride, T, r.cnt, r.S, f.st, mcsp, Ls, f.Ws, r.dst, r.dst_stride, r.c.rate_out, r.c.rate_out2, r.sin, r.sout,
+		    h->d_lpr_chunks, lpr_vec, cnt_dst);
+	});
+	r.stage_done("one pass (lpr)");
+	r.arrived();
+	return 0;
+}
+
+// The four passes, for every stream; with `fuse_lpr` the last one is low_pass_real too (counts in d_cnt2)
+static int tail_deemph_four_pass(TailRun &r, const DeemphForm &f, bool fuse_lpr)
+{
+	rtlfm_gpu *h = r.h;
+	const int S = r.S, T = r.T, fast = r.c.rate_out, slow = r.c.rate_out2;
+	// chunk length: each of the passes A1 and C is one chunk long in time; a chunk must be
+	// long enough for the interval to contract (~100 samples) and, normally, to merge
+	const int L = T >= 8192 ? 1024 : 512;
+	const int mc = T / L + 2;
+	int e = grow_scratch(r.q, &h->deemph_chunks, mc, {{(void **)&h->d_deemph_tab, (size_t)S * mc * sizeof(DeemphChunk)},
+	                                                  {(void **)&h->d_deemph_inc, (size_t)S * mc * sizeof(uint32_t)}});
+	if (e == 0 && fuse_lpr) e = grow_scratch(r.q, &h->lpr_chunks_cap, mc, {{(void **)&h->d_lpr_chunks, (size_t)S * mc * sizeof(LprChunk)}});
+	if (e < 0) return e;
+	if (fuse_lpr) r.out_of_place();
+	const int lpr_vec = fuse_lpr && (uintptr_t)r.dst % 16 == 0 && r.dst_stride % 8 == 0 && !h->opt.lpr_scalar_stores;
+	int lpc = 8;  // lanes per chunk in pass A2: the contracted interval (<= 2a + 2 states) must fit
+	while (lpc < 2 * r.c.deemph_a + 3) lpc *= 2;
+	const size_t per_wave = 64 / lpc;
+	const unsigned ga = (unsigned)(((size_t)S * mc + per_wave - 1) / per_wave), gc = (unsigned)(((size_t)S * mc + 63) / 64);
+	with_magic(f.M, [&](auto mm) {
+		constexpr int MM = decltype(mm)::value;
+		k_deemph_scan_a1<MM><<<gc, 64, 0, r.q>>>(r.cur, r.cur_stride, T, r.cnt, S, f.st, mc, L, lpc, h->d_deemph_tab);
+		r.stage_done("a1");
+		k_deemph_scan_a2<MM><<<ga, 64, 0, r.q>>>(r.cur, r.cur_stride, T, r.cnt, S, f.st, mc, L, lpc, h->d_deemph_tab);
+		r.stage_done("a2");
+		k_deemph_scan_b<MM><<<gc, 64, 0, r.q>>>(r.cur, r.cur_stride, T, r.cnt, S, f.st, mc, L, h->d_deemph_tab, h->d_deemph_inc, r.sin, r.sout);
+		r.stage_done("b");
+		if (fuse_lpr) {
+			k_deemph_scan_c_lpr<MM><<<gc, 64, 0, r.q>>>(r.cur, r.cur_stride, T, r.cnt, S, f.st, mc, L, h->d_deemph_inc, r.dst, r.dst_stride, fast, slow,
+			                                           r.sin, r.sout, h->d_lpr_chunks, lpr_vec);
+			k_lpr_fixup<<<gc, 64, 0, r.q>>>(r.cur, r.cur_stride, T, r.cnt, S, mc, L, h->d_lpr_chunks, r.dst, r.dst_stride, fast, slow, r.sin, r.sout,
+			                              h->d_cnt2);
+		} else {
+			k_deemph_scan_c<MM><<<gc, 64, 0, r.q>>>(r.cur, r.cur_stride, T, r.cnt, S, f.st, mc, L, h->d_deemph_inc, r.sout);
+		}
+		r.stage_done("c");
+	});
+	if (fuse_lpr) r.arrived();
+	return 0;
+}
+
+// The tail in order: post -> de-emphasis (in some forms with its resampler) -> -E dc -> resampler -> counts.
+// (T, varcnt, nblocks, Nblk, D: the run as the front end left it, see TailRun.)
 static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_stride, int T, bool varcnt,
                     int nblocks, int Nblk, int D, int16_t *final_dst, size_t final_stride, int32_t *d_out_len)
 {
 	const rtlfm_cfg &c = h->cfg;
 	const int S = h->nstreams;
 	const int par = (int)(h->step & 1);
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	int remaining_oop = tp.oop();
-	int32_t *cnt = varcnt ? h->d_cnt[par] : nullptr;
+	TailRun r{h, c, S, h->stream, h->st[h->st_cur], h->st[(h->st_cur + 1) % 3], cur, cur_stride, T, varcnt ? h->d_cnt[par] : nullptr,
+	          nblocks, Nblk, D, final_dst, final_stride, tp.oop(), nullptr, 0};
+	const DeemphForm f = deemph_form(c.deemph_a);
+	const Deemph form = deemph_route(tp, f, r);
 	// The tail runs behind the front end on a stream of its own, so that the front end of the next
 	// step (a different res[] set, d_cnt[] and state copy, see struct rtlfm_gpu) overlaps it: at
 	// config 3 the tail is a quarter of the step but 3 % of the bytes.  rtlfm_gpu_run_device() makes
 	// the step after next wait for it before it reuses this parity's buffers.
-	hipStream_t q = h->stream;
 	// ... but config 3's own tail in line (arb_tail_in_line above)
 	const bool own_stream = tp.any() && h->tail_overlap && !arb_tail_in_line(h, tp);
 	if (own_stream) {
 		HIP_TRY(hipEventRecord(h->ev_front[par], h->stream));
 		HIP_TRY(hipStreamWaitEvent(h->tail_stream, h->ev_front[par], 0));
-		q = h->tail_stream;
+		r.q = h->tail_stream;
 		// The front end copied the whole record sin -> sout while the previous step's tail may still
 		// have been writing the tail's fields of sin.  The tail stream is in order, so here those are
 		// final: carry them over before any stage of this tail runs (a stage that leaves a field
-		// alone - a skipped stream, an early return - then leaves the right value behind).
+		// alone - a skipped stream - then leaves the right value behind).
 		// The one-kernel tails write every field a tail of their configuration owns, for every stream: no copy.
-		if (!one_pass_tail(h, tp, cur, cur_stride, T, varcnt, nblocks, Nblk, D))
-			k_tail_state_copy<<<grid_for(S, 64), 64, 0, q>>>(sin, sout, S);
+		if (!whole_tail(form)) k_tail_state_copy<<<grid_for(S, 64), 64, 0, r.q>>>(r.sin, r.sout, S);
 	}
 	struct Done {  // whatever path leaves: mark the end of this step's tail
 		rtlfm_gpu *h; int par; bool on;
 		~Done() { if (on && hipEventRecord(h->ev_tail[par], h->tail_stream) == hipSuccess) h->tail_pending[par] = true; }
 	} done{h, par, own_stream};
-	auto next_dst = [&](int16_t **d, size_t *ds) {
-		remaining_oop--;
-		if (remaining_oop == 0) { *d = final_dst; *ds = final_stride; }
-		else { *d = (cur == h->res[par][0]) ? h->res[par][1] : h->res[par][0]; *ds = h->tstride; }
-	};
 	if (tp.post) {
 		// low_pass_simple: "length must be multiple of step" (src/rtl_fm.c:740) — validate_cfg only
 		// lets uniform per-buffer counts through
-		int16_t *d; size_t ds;
-		next_dst(&d, &ds);
-		int Tout = T / c.post_downsample;
-		k_post_downsample<<<grid_for((size_t)S * Tout), 256, 0, q>>>(cur, cur_stride, d, ds, Tout, S,
-		                                                           c.post_downsample);
-		cur = d; cur_stride = ds; T = Tout;
-		Nblk = T / nblocks; D = 1;
+		r.out_of_place();
+		r.T /= c.post_downsample;
+		k_post_downsample<<<grid_for((size_t)S * r.T), 256, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, r.T, S, c.post_downsample);
+		r.arrived();
+		r.Nblk = r.T / nblocks; r.D = 1;
 	}
-	bool fuse_lpr = false;
-	int16_t *lpr_dst = nullptr; size_t lpr_ds = 0;
-	if (tp.deemph && c.deemph_a == 1) {
-		// the filter is the identity on the samples and keeps the last one (staged_kernels.h)
-		k_deemph_identity<<<grid_for(S, 64), 64, 0, q>>>(cur, cur_stride, T, cnt, S, sout);
-	} else if (tp.deemph) {
-		DeemphStep st;
-		st.a = (uint32_t)c.deemph_a; st.half = (uint32_t)(c.deemph_a / 2);
-		const bool pow2 = c.deemph_a >= 1 && c.deemph_a <= 32768 && (c.deemph_a & (c.deemph_a - 1)) == 0;
-		const bool magic = !pow2 && c.deemph_a >= 2 && c.deemph_a <= 32768;
-		st.magic = 0;
-		if (pow2) { while ((1u << st.magic) < st.a) st.magic++; }
-		else if (magic) st.magic = (uint32_t)((0x100000000ull + st.a - 1) / st.a);
-		const int M = pow2 ? 2 : magic ? 1 : 0;
-		const unsigned grid = (unsigned)((S + 63) / 64);
-		// few, long streams: parallel over time (staged_kernels.h, k_deemph_scan_*); the interval
-		// of candidate states must fit a wave (2a + 2 <= kDeemphGap)
-		const bool scan = deemph_scans(h, T);
-		const bool dbg_sync = h->opt.tail_sync != 0;
-#define RTLFM_DBG_SYNC(what) do { if (dbg_sync) { hipError_t e_ = hipStreamSynchronize(q); fprintf(stderr, "rtlfm_hip[tail]: %s done (%s)\n", what, hipGetErrorString(e_)); } } while (0)
-		if (tp.deemph_spec) {
-			// deemph_filter with no resampler behind it, a long run: ONE pass, out of place (staged_kernels.h, k_deemph_spec)
-			int16_t *dd2; size_t dds2;
-			next_dst(&dd2, &dds2);
-			const int Ws = ((16 * c.deemph_a + 64 + 63) / 64) * 64;
-			const bool congruent = (((uintptr_t)cur ^ (uintptr_t)dd2) & 15) == 0 && ((cur_stride * 2) & 15) == ((dds2 * 2) & 15);
-			if (scan && congruent) {
-				int Lc = h->opt.lpr_chunk;
-				{
-					long long fit = (long long)S * T / 65536;
-					const long long lo = 6ll * Ws > 512 ? 6ll * Ws : 512;
-					if (fit < lo) fit = lo;
-					if (fit < Lc) Lc = (int)fit;
-				}
-				Lc = (Lc + 63) & ~63;  // whole 128-byte rounds
-				const int mcd = T / Lc + 2;
-				const int spw = mcd >= kSpecLprThreads ? 1 : kSpecLprThreads / mcd;
-				const unsigned gsp = (unsigned)((S + spw - 1) / spw);
-#define RTLFM_SPEC_ONLY(MM) k_deemph_spec<MM><<<gsp, kSpecLprThreads, 0, q>>>(cur, cur_stride, dd2, dds2, T, cnt, S, st, mcd, Lc, Ws, sin, sout)
-				if (M == 2) RTLFM_SPEC_ONLY(2); else if (M == 1) RTLFM_SPEC_ONLY(1); else RTLFM_SPEC_ONLY(0);
-#undef RTLFM_SPEC_ONLY
-				RTLFM_DBG_SYNC("one pass (deemph)");
-			} else {
-				// (the plan promised an out-of-place stage and the run turned out otherwise - rows that do not share their
-				// alignment, a run that is shorter than planned: the sequential filter in place, then a copy)
-				if (M == 2) k_deemph<2><<<grid, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, sin, sout);
-				else if (M == 1) k_deemph<1><<<grid, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, sin, sout);
-				else k_deemph<0><<<grid, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, sin, sout);
-				HIP_TRY(hipMemcpy2DAsync(dd2, dds2 * sizeof(int16_t), cur, cur_stride * sizeof(int16_t), (size_t)T * sizeof(int16_t), S,
-				                         hipMemcpyDeviceToDevice, q));
-			}
-			cur = dd2; cur_stride = dds2;
-		} else if (scan) {
-			// deemph_filter followed directly by low_pass_real (-M wbfm): the filtered samples go straight
-			// into the resampler's accumulator instead of back to memory (staged_kernels.h)
-			fuse_lpr = tp.lpr && !tp.adc && !h->opt.lpr_separate;
-			// One pass where the resampler follows directly: every chunk finds its incoming state from the
-			// W samples before it (staged_kernels.h, k_deemph_spec_lpr); a stream it cannot settle that way
-			// (silence) is redone by the kernel's own last lane for that stream.
-			// ... and where arbitrary_resample follows directly, on uniform buffers that it upsamples
-			// (config 3): one pass from the demodulated samples to the resampled output (k_deemph_spec_arb)
-			const int one = one_pass_tail(h, tp, cur, cur_stride, T, varcnt, nblocks, Nblk, D);
-			const bool spec = one == 2, spec_arb = one == 1;
-			const int Ws = ((16 * c.deemph_a + 64 + 63) / 64) * 64;
-			const int arb_l2 = (int)((long long)Nblk * c.rate_out2 / c.rate_out);
-			const size_t arb_lds = (size_t)(Ws / kArbChunk + 64) * kArbStride * sizeof(int16_t);
-			int32_t *cnt_dst = d_out_len ? d_out_len : h->d_cnt2;
-			if (spec_arb) {
-				if (h->arb_len2 != arb_l2 || h->arb_len1 != Nblk) {
-					// (i, frac) of every output of a buffer, as arbitrary_upsample's loop (src/rtl_fm.c:1114-1135)
-					// has them when it writes buf2[j]: walked once here, shared by every stream and buffer
-					// (ti: the i, a gap, then the padded LDS offset of sample i - 1 for k_deemph_spec_arb's resampler)
-					std::vector<int32_t> ti(2 * (size_t)arb_l2 + kArbTabGap);
-					std::vector<double> tf((size_t)arb_l2);
-					std::vector<ArbTab> tt((size_t)arb_l2);
-					int i = 1, tick = 0;
-					for (int j = 0; j < arb_l2; j++) {
-						ti[j] = i;
-						tf[j] = (double)tick / (double)arb_l2;
-						tt[j] = ArbTab{tf[j], i, 0};
-						ti[(size_t)arb_l2 + kArbTabGap + j] = 2 * i + 16 * (i >> 5) - 2;
-						tick += Nblk;
-						if (tick > arb_l2) { tick -= arb_l2; i++; }
-						if (i >= Nblk) { i = Nblk - 1; tick = arb_l2; }
-					}
-					HIP_TRY(hipStreamSynchronize(q));  // the tables of another geometry may still be in use
-					// the keys say "no tables" until every allocation and copy has succeeded (a failure half way must not
-					// leave the old geometry's keys beside freed or short tables)
-					h->arb_len2 = 0; h->arb_len1 = 0;
-					for (void **pp : {(void **)&h->d_arb_i, (void **)&h->d_arb_frac, (void **)&h->d_arb_tab})
-						if (*pp) { HIP_TRY(hipFree(*pp)); *pp = nullptr; }
-					HIP_TRY(hipMalloc(&h->d_arb_i, ti.size() * sizeof(int32_t)));
-					HIP_TRY(hipMalloc(&h->d_arb_frac, tf.size() * sizeof(double)));
-					HIP_TRY(hipMalloc(&h->d_arb_tab, tt.size() * sizeof(ArbTab)));
-					HIP_TRY(hipMemcpy(h->d_arb_i, ti.data(), ti.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-					HIP_TRY(hipMemcpy(h->d_arb_frac, tf.data(), tf.size() * sizeof(double), hipMemcpyHostToDevice));
-					HIP_TRY(hipMemcpy(h->d_arb_tab, tt.data(), tt.size() * sizeof(ArbTab), hipMemcpyHostToDevice));
-					h->arb_len2 = arb_l2; h->arb_len1 = Nblk;
-				}
-				int16_t *arb_dst = nullptr; size_t arb_ds = 0;
-				next_dst(&arb_dst, &arb_ds);
-				if (arb_dst != final_dst) return -EFAULT;  // routing bug
-				if (h->opt.arb_span) {
-					// round 5's form: the span linear in LDS, 32 or 64 samples per lane (staged_kernels.h, k_deemph_arb_span)
-					const int Cc = h->opt.arb_chunk == 64 ? 64 : 32;
-					const int sp_n = (T + 64 * Cc - 1) / (64 * Cc);
-					const size_t lds_w = (((size_t)(Ws + 64 * Cc) * sizeof(int16_t) + 16) + 15) & ~(size_t)15;
-					int wv = 8192 / S;
-					if (wv > sp_n) wv = sp_n;
-					if (wv > kSpecArbMaxWaves) wv = kSpecArbMaxWaves;
-					if (wv < 1) wv = 1;
-					const int M3 = c.deemph_a == 2 ? 3 : M;
-#define RTLFM_ARB_SPAN(MM, CC) k_deemph_arb_span<MM, CC><<<(unsigned)S, 64 * wv, lds_w * wv, q>>>(cur, cur_stride, T, S, st, Ws, sp_n, Nblk, arb_l2, nblocks, \
-				h->d_arb_tab, arb_dst, arb_ds, sin, sout, lds_w, cnt_dst)
-					if (Cc == 64) { if (M3 == 3) RTLFM_ARB_SPAN(3, 64); else if (M3 == 2) RTLFM_ARB_SPAN(2, 64); else if (M3 == 1) RTLFM_ARB_SPAN(1, 64); else RTLFM_ARB_SPAN(0, 64); }
-					else { if (M3 == 3) RTLFM_ARB_SPAN(3, 32); else if (M3 == 2) RTLFM_ARB_SPAN(2, 32); else if (M3 == 1) RTLFM_ARB_SPAN(1, 32); else RTLFM_ARB_SPAN(0, 32); }
-#undef RTLFM_ARB_SPAN
-					RTLFM_DBG_SYNC("one pass (arb span)");
-					return 0;
-				}
-				const int arb_spans = (T + 64 * kArbChunk - 1) / (64 * kArbChunk);
-				// a workgroup per stream (nothing crosses workgroups), its spans dealt to up to eight waves: about 16384
-				// waves in all - two and a half rounds of what the GPU holds, so that the last round is a small part of
-				// the launch (8192: config 3's tail alone 70 us instead of 65, LAB.md I.31)
-				int wpw = h->opt.arb_waves > 0 ? h->opt.arb_waves : 16384 / S;
-				if (wpw > arb_spans) wpw = arb_spans;
-				if (wpw > kSpecArbMaxWaves) wpw = kSpecArbMaxWaves;
-				if (wpw < 1) wpw = 1;
-#define RTLFM_SPEC_ARB(MM) k_deemph_spec_arb<MM><<<(unsigned)S, 64 * wpw, arb_lds * wpw, q>>>(cur, cur_stride, T, S, st, Ws, arb_spans, Nblk, arb_l2, nblocks, \
-				h->d_arb_i, h->d_arb_frac, arb_dst, arb_ds, sin, sout, arb_lds, cnt_dst)
-				// a == 2 (rtl_fm -s 24k -E deemp): the filter step is (x + avg + [x > avg]) >> 1
-				if (c.deemph_a == 2) RTLFM_SPEC_ARB(3); else if (M == 2) RTLFM_SPEC_ARB(2); else if (M == 1) RTLFM_SPEC_ARB(1); else RTLFM_SPEC_ARB(0);
-#undef RTLFM_SPEC_ARB
-				RTLFM_DBG_SYNC("one pass (arb)");
-				return 0;  // the one operation of this tail: filter, resampler, state and counts
-			}
-			if (spec) {
-				// chunk length of the one-pass form: about 2720 samples (2040: +1 %, 1360: +2 % on the wbfm step),
-				// and a multiple of the resampler's period fast / gcd(fast, slow) where that is short - then all
-				// chunks of a stream start at the same phase, the lanes of a wave emit at the same samples and
-				// the emission branch is taken by whole waves instead of by a few lanes every sample
-				// `lpr_chunk` samples per lane where the run fills the GPU that way (-M wbfm at 1024 streams: 64 K lanes); with
-				// fewer samples in all, shorter chunks - about 64 K lanes again, never so short that the settling (W samples
-				// walked twice per chunk) outweighs the chunk (256 streams of rtl_fm -s 48k -r 24k -E deemp: 294 waves on 1024
-				// SIMDs took 1.45 ms for 102 M samples)
-				const bool slim = h->opt.lpr_slim != 0;
-				int Lwant = slim ? h->opt.lpr_slim_chunk : h->opt.lpr_chunk;  // 256 .. 2^20 (rtlfm_gpu_set_option)
-				{
-					long long fit = (long long)S * T / 65536;
-					const long long lo = 6ll * Ws > 512 ? 6ll * Ws : 512;
-					if (fit < lo) fit = lo;
-					if (fit < Lwant) Lwant = (int)fit;
-				}
-				int Ls = Lwant;
-				int mcsp;
-				{
-					long long gg = c.rate_out, bb = c.rate_out2;
-					while (bb) { const long long t = gg % bb; gg = bb; bb = t; }
-					long long per = c.rate_out / gg;
-					while (per % 8) per *= 2;
-					if ((long long)T >= 48ll * Lwant) {
-						// long runs: a stream's chunks fill whole waves.  (T / 2720 + 2 = 130 chunks of the wbfm shape were two
-						// full waves and a third with ONE busy lane that issued every instruction of the walk again:
-						// SQ_INSTS_VALU 23.8 lane-operations per sample against 18.4 with packed lanes.)
-						const int n64 = (int)(((long long)T + 32ll * Lwant) / (64ll * Lwant));
-						const int lanes = 64 * (n64 < 1 ? 1 : n64);
-						long long L0 = ((long long)T + lanes - 1) / lanes;
-						L0 = per <= L0 ? per * ((L0 + per - 1) / per) : ((L0 + 7) & ~7ll);
-						Ls = (int)L0;
-						mcsp = lanes;
-					} else {
-						if (per <= Lwant) Ls = (int)(per * ((Lwant + per / 2) / per));
-						mcsp = T / Ls + 2;
-					}
-				}
-				if (slim) {
-					// Round 6: the tail as a FIFTH wave per SIMD beside the next step's front end (staged_kernels.h, k_deemph_lpr_slim):
-					// the plan - every lane's stretch, the run's totals - by a small kernel in front, then one-wave workgroups of
-					// 32 registers and no LDS.  g / chunks is a multiply-high whose magic number is checked over the whole grid once.
-					const size_t lanes_all = (size_t)S * mcsp;
-					if (lanes_all + 64 < (1ull << 31)) {
-						if (h->slim_magic_for != mcsp || h->slim_magic_upto < lanes_all + 64) {
-							const uint32_t M = (uint32_t)(0x100000000ull / (uint32_t)mcsp) + 1u;
-							bool ok = true;
-							for (uint64_t g = 0; g < lanes_all + 64 && ok; g++) ok = (uint32_t)((g * M) >> 32) == (uint32_t)(g / (uint32_t)mcsp);
-							h->slim_magic_for = ok ? mcsp : -1; h->slim_magic = M; h->slim_magic_upto = lanes_all + 64;
-						}
-						if (h->slim_magic_for == mcsp) {
-							if (lanes_all + 64 > h->slim_plan_cap) {
-								if (h->d_slim_plan) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(hipFree(h->d_slim_plan)); }
-								h->d_slim_plan = nullptr; h->slim_plan_cap = 0;
-								HIP_TRY(hipMalloc(&h->d_slim_plan, (lanes_all + 64) * sizeof(SlimPlan)));
-								h->slim_plan_cap = lanes_all + 64;
-							}
-							next_dst(&lpr_dst, &lpr_ds);
-							if (lpr_dst != final_dst) return -EFAULT;  // routing bug
-							const int vec16 = (uintptr_t)lpr_dst % 16 == 0 && lpr_ds % 8 == 0 && !h->opt.lpr_scalar_stores;
-							const unsigned gw = (unsigned)((lanes_all + 63) / 64);
-							k_lpr_slim_plan<<<gw, 64, 0, q>>>(cur, cur_stride, T, cnt, S, c.deemph_a, mcsp, Ls, lpr_dst, lpr_ds, c.rate_out, c.rate_out2,
-							                                 sin, sout, cnt_dst, h->d_slim_plan);
-#define RTLFM_LPR_SLIM(MM) k_deemph_lpr_slim<MM><<<gw, 64, 0, q>>>(cur, cur_stride, S, st, mcsp, h->slim_magic, Ws, lpr_dst, lpr_ds, c.rate_out, c.rate_out2, \
-							sin, sout, vec16, h->d_slim_plan, h->opt.lpr_slim_prio)
-							if (M == 2) RTLFM_LPR_SLIM(2); else if (M == 1) RTLFM_LPR_SLIM(1); else RTLFM_LPR_SLIM(0);
-#undef RTLFM_LPR_SLIM
-							RTLFM_DBG_SYNC("one pass (lpr, slim)");
-							return 0;
-						}
-					}
-				}
-				if ((size_t)mcsp > (size_t)h->lpr_chunks_cap) {
-					if (h->d_lpr_chunks) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(hipFree(h->d_lpr_chunks)); }
-					h->d_lpr_chunks = nullptr; h->lpr_chunks_cap = 0;
-					HIP_TRY(hipMalloc(&h->d_lpr_chunks, (size_t)S * mcsp * sizeof(LprChunk)));
-					h->lpr_chunks_cap = mcsp;
-				}
-				next_dst(&lpr_dst, &lpr_ds);
-				if (lpr_dst != final_dst) return -EFAULT;  // routing bug
-				// outputs leave in 64-byte pieces through LDS (2; any row alignment), else in 16-byte groups where the rows allow
-				// it (1), else one by one (staged_kernels.h, LprSink)
-				int lpr_vec = (uintptr_t)lpr_dst % 16 == 0 && lpr_ds % 8 == 0 && !h->opt.lpr_scalar_stores;
-				if (h->opt.lpr_ring && !h->opt.lpr_scalar_stores) lpr_vec = 2;
-				const int nthr = h->opt.lpr_threads;
-				const size_t lpr_lds = lpr_vec == 2 ? (size_t)nthr * kLprRingStride * sizeof(int16_t) : 0;
-				// a workgroup owns whole streams: 256 / chunks of them, or one with a loop over its chunks
-				const int spw = mcsp >= nthr ? 1 : nthr / mcsp;
-				const unsigned gsp = (unsigned)((S + spw - 1) / spw);
-#define RTLFM_SPEC_LPR(MM) k_deemph_spec_lpr<MM><<<gsp, nthr, lpr_lds, q>>>(cur, cur_stride, T, cnt, S, st, mcsp, Ls, Ws, lpr_dst, lpr_ds, \
-				c.rate_out, c.rate_out2, sin, sout, h->d_lpr_chunks, lpr_vec, cnt_dst)
-				if (M == 2) RTLFM_SPEC_LPR(2); else if (M == 1) RTLFM_SPEC_LPR(1); else RTLFM_SPEC_LPR(0);
-#undef RTLFM_SPEC_LPR
-				RTLFM_DBG_SYNC("one pass (lpr)");
-				return 0;
-			}
-			// the four passes, for every stream
-			// chunk length: each of the passes A1 and C is one chunk long in time; a chunk must be
-			// long enough for the interval to contract (~100 samples) and, normally, to merge
-			const int L = T >= 8192 ? 1024 : 512;
-			const int mc = T / L + 2;
-			if ((size_t)mc > (size_t)h->deemph_chunks) {
-				if (h->d_deemph_tab) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(hipFree(h->d_deemph_tab)); HIP_TRY(hipFree(h->d_deemph_inc)); }
-				h->d_deemph_tab = nullptr; h->d_deemph_inc = nullptr; h->deemph_chunks = 0;
-				HIP_TRY(hipMalloc(&h->d_deemph_tab, (size_t)S * mc * sizeof(DeemphChunk)));
-				HIP_TRY(hipMalloc(&h->d_deemph_inc, (size_t)S * mc * sizeof(uint32_t)));
-				h->deemph_chunks = mc;
-			}
-			if (fuse_lpr && (size_t)mc > (size_t)h->lpr_chunks_cap) {
-				if (h->d_lpr_chunks) { HIP_TRY(hipStreamSynchronize(q)); HIP_TRY(hipFree(h->d_lpr_chunks)); }
-				h->d_lpr_chunks = nullptr; h->lpr_chunks_cap = 0;
-				HIP_TRY(hipMalloc(&h->d_lpr_chunks, (size_t)S * mc * sizeof(LprChunk)));
-				h->lpr_chunks_cap = mc;
-			}
-			const int mcs = mc;
-			if (fuse_lpr) next_dst(&lpr_dst, &lpr_ds);
-			const int lpr_vec = fuse_lpr && (uintptr_t)lpr_dst % 16 == 0 && lpr_ds % 8 == 0 && !h->opt.lpr_scalar_stores;
-			int lpc = 8;  // lanes per chunk in pass A2: the contracted interval (<= 2a + 2 states) must fit
-			while (lpc < 2 * c.deemph_a + 3) lpc *= 2;
-			const size_t per_wave = 64 / lpc;
-			const unsigned ga = (unsigned)(((size_t)S * mcs + per_wave - 1) / per_wave), gc = (unsigned)(((size_t)S * mcs + 63) / 64);
-#define RTLFM_DEEMPH_SCAN(MM)                                                                                       \
-	do {                                                                                                            \
-		k_deemph_scan_a1<MM><<<gc, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, mcs, L, lpc, h->d_deemph_tab);        \
-		RTLFM_DBG_SYNC("a1");                                                                                          \
-		k_deemph_scan_a2<MM><<<ga, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, mcs, L, lpc, h->d_deemph_tab);        \
-		RTLFM_DBG_SYNC("a2");                                                                                          \
-		k_deemph_scan_b<MM><<<gc, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, mcs, L, h->d_deemph_tab,               \
-		                                       h->d_deemph_inc, sin, sout);                                         \
-		RTLFM_DBG_SYNC("b");                                                                                           \
-		if (fuse_lpr) {                                                                                              \
-			k_deemph_scan_c_lpr<MM><<<gc, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, mcs, L, h->d_deemph_inc, lpr_dst, \
-			                                           lpr_ds, c.rate_out, c.rate_out2, sin, sout, h->d_lpr_chunks, lpr_vec); \
-			k_lpr_fixup<<<gc, 64, 0, q>>>(cur, cur_stride, T, cnt, S, mcs, L, h->d_lpr_chunks, lpr_dst, lpr_ds,        \
-			                              c.rate_out, c.rate_out2, sin, sout, h->d_cnt2);                            \
-		} else {                                                                                                     \
-			k_deemph_scan_c<MM><<<gc, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, mcs, L, h->d_deemph_inc, sout);      \
-		}                                                                                                            \
-		RTLFM_DBG_SYNC("c");                                                                                           \
-	} while (0)
-			if (M == 2) RTLFM_DEEMPH_SCAN(2);
-			else if (M == 1) RTLFM_DEEMPH_SCAN(1);
-			else RTLFM_DEEMPH_SCAN(0);
-#undef RTLFM_DEEMPH_SCAN
-		} else if (M == 2) k_deemph<2><<<grid, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, sin, sout);
-		else if (M == 1) k_deemph<1><<<grid, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, sin, sout);
-		else k_deemph<0><<<grid, 64, 0, q>>>(cur, cur_stride, T, cnt, S, st, sin, sout);
+	int32_t *cnt_dst = d_out_len ? d_out_len : h->d_cnt2;  // where a one-kernel tail leaves the counts
+	int e = 0;
+	switch (form) {
+	case Deemph::none: break;
+	case Deemph::identity: k_deemph_identity<<<grid_for(S, 64), 64, 0, r.q>>>(r.cur, r.cur_stride, r.T, r.cnt, S, r.sout); break;
+	case Deemph::sequential: tail_deemph_sequential(r, f); break;
+	case Deemph::spec: e = tail_deemph_spec(r, f); break;
+	case Deemph::spec_lpr: e = tail_deemph_spec_lpr(r, f, cnt_dst); break;
+	case Deemph::spec_arb: e = tail_deemph_spec_arb(r, f, cnt_dst); break;
+	case Deemph::four_pass: e = tail_deemph_four_pass(r, f, false); break;
+	case Deemph::four_pass_lpr: e = tail_deemph_four_pass(r, f, true); break;
 	}
+	if (e < 0) return e;
 	if (tp.adc) {
 		// dc_block_audio_filter (src/rtl_fm.c:1028-1041): sums per buffer, then the smoothing recurrence and the subtraction
-		// in one launch (staged_kernels.h, k_adc_smooth_apply); option adc_separate: round 4's three kernels
-		k_adc_sums<<<S * nblocks, 256, 0, q>>>(cur, cur_stride, Nblk, D, nblocks, sin, h->d_adc_sums);
-		if (!h->opt.adc_separate) {
-			k_adc_smooth_apply<<<S * nblocks, 256, (size_t)(nblocks + 1) * sizeof(int32_t), q>>>(cur, cur_stride, Nblk, D, nblocks, c.adc_block_const,
-			                                                                                  h->d_adc_sums, sin, sout);
-		} else {
-			k_adc_smooth<<<grid_for(S, 64), 64, 0, q>>>(h->d_adc_sums, Nblk, D, nblocks, S, c.adc_block_const, sin,
-			                                           sout, h->d_adc_avg);
-			k_adc_apply<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, cur_stride, Nblk, D, nblocks, S, T, sin,
-			                                                  h->d_adc_avg);
-		}
+		// in one launch (staged_kernels.h, k_adc_smooth_apply)
+		k_adc_sums<<<S * nblocks, 256, 0, r.q>>>(r.cur, r.cur_stride, r.Nblk, r.D, nblocks, r.sin, h->d_adc_sums);
+		k_adc_smooth_apply<<<S * nblocks, 256, (size_t)(nblocks + 1) * sizeof(int32_t), r.q>>>(r.cur, r.cur_stride, r.Nblk, r.D, nblocks,
+		                                                                                    c.adc_block_const, h->d_adc_sums, r.sin, r.sout);
 	}
-	if (tp.lpr && fuse_lpr) {
-		cur = lpr_dst; cur_stride = lpr_ds;
-		if (d_out_len)
-			HIP_TRY(hipMemcpyAsync(d_out_len, h->d_cnt2, S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-		return 0;
-	}
-	if (tp.lpr) {
-		int16_t *d; size_t ds;
-		next_dst(&d, &ds);
-		int maxout = (int)(((long long)c.rate_out - 1 + (long long)T * c.rate_out2) / c.rate_out);
-		k_low_pass_real<<<grid_for((size_t)S * (maxout + 1)), 256, 0, q>>>(
-		    cur, cur_stride, d, ds, T, cnt, S, c.rate_out, c.rate_out2, sin, sout, h->d_cnt2);
-		cur = d; cur_stride = ds;
-		if (d_out_len)
-			HIP_TRY(hipMemcpyAsync(d_out_len, h->d_cnt2, S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-		return 0;
-	}
-	if (tp.arb) {
+	const bool resampled = whole_tail(form) || form == Deemph::four_pass_lpr;
+	if (tp.lpr && !resampled) {
+		r.out_of_place();
+		const int maxout = (int)(((long long)c.rate_out - 1 + (long long)r.T * c.rate_out2) / c.rate_out);
+		k_low_pass_real<<<grid_for((size_t)S * (maxout + 1)), 256, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, r.T, r.cnt, S, c.rate_out,
+		                                                                   c.rate_out2, r.sin, r.sout, h->d_cnt2);
+		r.arrived();
+	} else if (tp.arb && !resampled) {
 		// arbitrary_resample per buffer on whatever result_len it has (src/rtl_fm.c:1168-1177, 1270)
-		int16_t *d; size_t ds;
-		next_dst(&d, &ds);
-		const int nlo = Nblk / D, nhi = (Nblk % D) ? nlo + 1 : nlo;
+		r.out_of_place();
+		const int nlo = r.Nblk / r.D, nhi = (r.Nblk % r.D) ? nlo + 1 : nlo;
 		const int l2lo = (int)((long long)nlo * c.rate_out2 / c.rate_out);
 		const int l2hi = (int)((long long)nhi * c.rate_out2 / c.rate_out);
 		const bool any_up = nlo < l2lo || nhi < l2hi, any_down = !(nlo < l2lo) || !(nhi < l2hi);
-		const ArbPlan ap{Nblk, D, nlo, l2lo, (int)((long long)(nlo + 1) * c.rate_out2 / c.rate_out)};
+		const ArbPlan ap{r.Nblk, r.D, nlo, l2lo, (int)((long long)(nlo + 1) * c.rate_out2 / c.rate_out)};
 		if (any_up)
-			k_arb_upsample<<<grid_for((size_t)S * nblocks * l2hi), 256, 0, q>>>(
-			    cur, cur_stride, d, ds, ap, l2hi, nblocks, S, sin, h->d_cnt2);
+			k_arb_upsample<<<grid_for((size_t)S * nblocks * l2hi), 256, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, ap, l2hi, nblocks, S, r.sin,
+			                                                                     h->d_cnt2);
 		if (any_down)
-			k_arb_downsample<<<grid_for((size_t)S * nblocks, 64), 64, 0, q>>>(
-			    cur, cur_stride, d, ds, ap, nblocks, S, sin, h->d_cnt2);
-		cur = d; cur_stride = ds;
-		if (cur != final_dst) return -EFAULT;  // routing bug
-		if (d_out_len)
-			HIP_TRY(hipMemcpyAsync(d_out_len, h->d_cnt2, S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-		return 0;
+			k_arb_downsample<<<grid_for((size_t)S * nblocks, 64), 64, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, ap, nblocks, S, r.sin, h->d_cnt2);
+		r.arrived();
 	}
-	if (cur != final_dst) return -EFAULT;  // routing bug
-	if (d_out_len) {
-		if (varcnt)
-			HIP_TRY(hipMemcpyAsync(d_out_len, h->d_cnt[par], S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-		else
-			k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, T);
-	}
+	if (r.cur != final_dst) return -EFAULT;  // routing bug
+	if (!d_out_len || whole_tail(form)) return 0;
+	if (tp.lpr || tp.arb)
+		HIP_TRY(hipMemcpyAsync(d_out_len, h->d_cnt2, S * sizeof(int32_t), hipMemcpyDeviceToDevice, r.q));
+	else if (varcnt)
+		HIP_TRY(hipMemcpyAsync(d_out_len, h->d_cnt[par], S * sizeof(int32_t), hipMemcpyDeviceToDevice, r.q));
+	else
+		k_fill_cnt<<<grid_for(S, 64), 64, 0, r.q>>>(d_out_len, S, r.T);
 	return 0;
 }
+
 
 // -M raw: two int16 per decimated sample - of the counts the front end left (`cnt`), or of T everywhere
 static int raw_out_len(rtlfm_gpu *h, int32_t *d_out_len, const int32_t *cnt, int T)
@@ -3126,7 +3095,6 @@ static rtlfm_gpu make_view(rtlfm_gpu *h, int s0, int ns, uint32_t block_len)
 	v.d_sq_sums = h->d_sq_sums + s0 * cb * 2;
 	v.d_adc_sums = h->d_adc_sums + s0 * cb;
 	v.d_rdc_avg = h->d_rdc_avg + s0 * cb;
-	v.d_adc_avg = h->d_adc_avg + s0 * cb;
 	if (h->bufA) { v.bufA = h->bufA + (size_t)s0 * h->xstride; v.bufB = h->bufB + (size_t)s0 * h->xstride; }
 	if (h->deepA) v.deepA = h->deepA + (size_t)s0 * h->deep_stride;
 	if (h->deepB) v.deepB = h->deepB + (size_t)s0 * h->deep_stride;

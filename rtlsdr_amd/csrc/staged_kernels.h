@@ -1674,215 +1674,6 @@ k_deemph_spec_lpr(int16_t *R, size_t rstride, int T, const int32_t *__restrict__
 	}
 }
 
-// ---- -M wbfm's tail where it takes no wave slot from the front end (round 6) -----------------------------------
-// k_deemph_spec_lpr above is 146 registers per lane in 256-thread workgroups.  Beside the NEXT step's front end - four
-// waves of k_boxcar_scan per SIMD, 120 registers each - one of its waves only fits where a front-end wave has left, a
-// workgroup only where four have left at once, and every wave of the tail that runs displaces a whole wave of a front end
-// whose speed is the number of tiles it has in flight: a step cost front end + 0.27 ms (LAB.md I.1, I.19; round 6: I.21).
-// But 4 x 120 registers leave 32 of a SIMD's 512, a wave slot (eight per SIMD) and 13 KB of the CU's LDS unused.  This
-// kernel is the same arithmetic made to fit THERE: at most 32 registers, no LDS, one-wave workgroups, no barrier - a fifth
-// wave beside four front-end waves that costs them issue cycles and memory bandwidth, not a slot.
-// What had to go for that:
-//   * the chunk records and the finishing pass behind a workgroup barrier.  low_pass_real's accumulator is empty right
-//     behind every emission (src/rtl_fm.c:755-775), and where the emissions fall is a closed form of the carried phase: a
-//     lane's stretch runs from the last emission at or before its chunk's first sample to the last one at or before the
-//     chunk's end, so every output belongs to exactly one lane and nothing is put together afterwards.  The few samples in
-//     front of the chunk (fewer than fast / slow + 1) come out of the settle walk, which has to have met by then;
-//   * the walk's sixteen 16-byte groups in flight: one group is walked while the next is loaded;
-//   * the 64-byte output pieces through LDS: outputs leave in 16-byte groups from four registers (rows 16-byte aligned),
-//     the odd ones at a stretch's ends one by one;
-//   * the redo of a stream that cannot settle (silence: the two extreme walks stop a / 2 either side of the input) by its
-//     workgroup: the lane walks from the stream's carried state to its own stretch instead - every lane of such a stream
-//     does, so a silent stream costs up to chunks / 2 times the walk, and is as slow as its last lane (as before);
-//   * a carried state outside its range (filter state beyond int16, resampler phase outside [0, fast): only
-//     rtlfm_gpu_state_set can do that): the stream's first lane runs the reference's two loops over the whole run.
-struct SlimSink {
-	int16_t *bof;  // the output row advanced to the stretch's first 16-byte group boundary: output m lives at bof[m - first_full]
-	int mrel;      // m - first_full (negative in front of the boundary: those outputs leave one by one)
-	int phi;
-	uint32_t acc, p0, p1, p2, p3;  // the accumulator; the last eight outputs, oldest in the low half of p0
-	__device__ __forceinline__ void init(int16_t *bo, int m, int phi_, uint32_t acc_, bool vec)
-	{
-		const int first_full = vec ? ((m + 7) & ~7) : (1 << 30);
-		bof = bo + first_full; mrel = m - first_full; phi = phi_; acc = acc_; p0 = p1 = p2 = p3 = 0;
-	}
-	__device__ __forceinline__ void put(int y, int sl, int fa, const ConstDiv &cdiv)
-	{
-		acc += (uint32_t)y;
-		phi += sl;
-		if (phi >= fa) {
-			const uint32_t q = (uint32_t)cdiv((int)acc);
-			p0 = __builtin_amdgcn_alignbit(p1, p0, 16);
-			p1 = __builtin_amdgcn_alignbit(p2, p1, 16);
-			p2 = __builtin_amdgcn_alignbit(p3, p2, 16);
-			p3 = (p3 >> 16) | (q << 16);
-			if (mrel < 0) bof[mrel] = (int16_t)q;
-			mrel++;
-			if ((mrel & 7) == 0 && mrel > 0) *reinterpret_cast<uint4 *>(bof + mrel - 8) = make_uint4(p0, p1, p2, p3);
-			phi -= fa;
-			acc = 0;
-		}
-	}
-	__device__ __forceinline__ void finish()
-	{
-		const int nrem = mrel & 7;
-		if (mrel - nrem < 0) return;  // written one by one already
-		const uint32_t p[4] = {p0, p1, p2, p3};
-#pragma unroll
-		for (int j = 0; j < 8; j++)
-			if (j >= 8 - nrem) bof[mrel - 8 + j] = (int16_t)(p[j >> 1] >> (16 * (j & 1)));
-	}
-};
-
-// `count` samples at p through the filter from the biased state v: one 16-byte group walked while the next is loaded.
-// PAIR: two states (the settle walk's extremes), nothing emitted; else the filtered samples go into the sink.
-template <int MAGIC, bool PAIR>
-__device__ __forceinline__ void slim_walk(const int16_t *p, int count, uint32_t &v, uint32_t &v2, const DeemphStep &ds,
-                                          SlimSink &sink, int sl, int fa, const ConstDiv &cdiv)
-{
-	auto one = [&](uint32_t xb) {
-		v = ds.step<MAGIC>(xb, v);
-		if (PAIR) v2 = ds.step<MAGIC>(xb, v2);
-		else sink.put((int)(int16_t)(uint16_t)(v ^ 0x8000u), sl, fa, cdiv);
-	};
-	for (; count > 0 && (((uintptr_t)p) & 15); count--, p++) one((uint32_t)(uint16_t)*p ^ 0x8000u);
-	if (count >= 8) {
-		uint4 cur = *reinterpret_cast<const uint4 *>(p);
-		for (; count >= 8; count -= 8) {
-			p += 8;
-			const uint4 nxt = *reinterpret_cast<const uint4 *>(count >= 16 ? p : p - 8);
-			one((cur.x ^ 0x80008000u) & 0xffffu); one((cur.x ^ 0x80008000u) >> 16);
-			one((cur.y ^ 0x80008000u) & 0xffffu); one((cur.y ^ 0x80008000u) >> 16);
-			one((cur.z ^ 0x80008000u) & 0xffffu); one((cur.z ^ 0x80008000u) >> 16);
-			one((cur.w ^ 0x80008000u) & 0xffffu); one((cur.w ^ 0x80008000u) >> 16);
-			cur = nxt;
-		}
-	}
-	for (; count > 0; count--, p++) one((uint32_t)(uint16_t)*p ^ 0x8000u);
-}
-
-// What a lane of k_deemph_lpr_slim is to do, worked out by k_lpr_slim_plan in front of it (the 64-bit divisions of the
-// closed forms cost forty registers; the walk itself must fit 32): samples [j0, j0 + count) of its stream into the
-// resampler, the first output being m0 at phase phi0.  count bit 30: the stream's last chunk (it leaves the carried
-// state); count < 0: nothing to do (no such chunk, or a stream the plan kernel has done itself).
-struct SlimPlan { int32_t j0, count, m0, phi0; };
-constexpr int kSlimLast = 1 << 30;
-
-// One lane per (stream, chunk).  Outputs emitted before sample i: m(i) = floor((p0 + i slow) / fast); the accumulator is
-// empty at the first sample j with m(j) == m(i): j = ceil((m(i) fast - p0) / slow) - that is where a lane's stretch begins
-// and where its predecessor's ends.  The run's totals (count of outputs, phase left) are closed forms too and are written
-// here.  A stream whose carried state no run of the chain produces (filter state beyond int16, resampler phase outside
-// [0, fast): only rtlfm_gpu_state_set can do that) is done here, by its first lane, with the reference's two loops
-// (src/rtl_fm.c:1011-1026, 755-775).
-__global__ void __launch_bounds__(64)
-k_lpr_slim_plan(const int16_t *__restrict__ R, size_t rstride, int T, const int32_t *__restrict__ cnt, int nstreams, int a,
-                int max_chunks, int L, int16_t *__restrict__ B, size_t bstride, int fast, int slow,
-                const state_t *__restrict__ sin, state_t *__restrict__ sout, int32_t *__restrict__ cnt_out, SlimPlan *__restrict__ plan)
-{
-	const uint32_t g = blockIdx.x * 64u + threadIdx.x;
-	const int s = (int)(g / (uint32_t)max_chunks);
-	const int c = (int)(g - (uint32_t)s * (uint32_t)max_chunks);
-	if (s >= nstreams) return;
-	SlimPlan out{0, -1, 0, 0};
-	const int n = cnt ? cnt[s] : T;
-	const int16_t *r = R + (size_t)s * rstride;
-	const int head = (int)(((16 - ((uintptr_t)r & 15)) & 15) >> 1);
-	const int nc = deemph_chunks(n, head, L);
-	const int carried = sin[s].deemph_avg;
-	const long long p0 = sin[s].prev_lpr_index;
-	if ((uint32_t)(carried + 32768) > 65535u || p0 < 0 || p0 >= fast) {
-		plan[g] = out;
-		if (c != 0) return;
-		int16_t *bo = B + (size_t)s * bstride;
-		int avg = carried, now = sin[s].now_lpr, i2 = 0;
-		long long idx = p0;
-		const int half = a / 2, div = fast / slow;
-		for (int i = 0; i < n; i++) {
-			const int d = r[i] - avg;
-			avg += d > 0 ? (d + half) / a : (d - half) / a;
-			now = (int)((uint32_t)now + (uint32_t)(int)(int16_t)avg);
-			idx += slow;
-			if (idx < fast) continue;
-			bo[i2++] = (int16_t)(now / div);
-			idx -= fast;
-			now = 0;
-		}
-		sout[s].deemph_avg = avg; sout[s].now_lpr = now; sout[s].prev_lpr_index = (int)idx;
-		if (cnt_out) cnt_out[s] = i2;
-		return;
-	}
-	if (c < nc) {
-		int begin, end;
-		deemph_chunk_range(c, n, head, L, begin, end);
-		auto stretch_start = [&](int i, int &mi) -> int {
-			const long long idx = p0 + (long long)i * slow;
-			mi = (int)floor_div_pos(idx, fast);
-			if (mi == 0) return 0;
-			const long long need = (long long)mi * fast - p0;  // > 0
-			return (int)floor_div_pos(need + slow - 1, slow);
-		};
-		int m0 = 0, m1 = 0;
-		const int j0 = c == 0 ? 0 : stretch_start(begin, m0);
-		const int j1 = c == nc - 1 ? n : stretch_start(end, m1);
-		if (c == 0) m0 = 0;
-		out.j0 = j0; out.count = (j1 - j0) | (c == nc - 1 ? kSlimLast : 0);
-		out.m0 = m0; out.phi0 = (int)(p0 + (long long)j0 * slow - (long long)m0 * fast);
-		if (c == nc - 1) {
-			int E, phase;
-			lpr_totals(p0, n, slow, fast, E, phase);
-			sout[s].prev_lpr_index = phase;
-			if (cnt_out) cnt_out[s] = E;
-		}
-	}
-	plan[g] = out;
-}
-
-template <int MAGIC>
-__global__ void __launch_bounds__(64)
-k_deemph_lpr_slim(const int16_t *__restrict__ R, size_t rstride, int nstreams, DeemphStep ds, int max_chunks, uint32_t chunks_magic,
-                  int W, int16_t *__restrict__ B, size_t bstride, int fast, int slow, const state_t *__restrict__ sin,
-                  state_t *__restrict__ sout, int vec, const SlimPlan *__restrict__ plan, int prio)
-{
-	// the front end's waves run at priorities 2 / 1 / 0 by their progress when a tail follows and leave 3 to the tail
-	// (fused_kernel.h, ProgressPrio): a lane's walk is one dependent chain, and at the lowest priority it got an issue slot
-	// in five - the tail then outlasted the front end it ran beside (LAB.md I.22)
-	if (prio >= 3) __builtin_amdgcn_s_setprio(3);
-	else if (prio == 2) __builtin_amdgcn_s_setprio(2);
-	else if (prio == 1) __builtin_amdgcn_s_setprio(1);
-	else __builtin_amdgcn_s_setprio(0);
-	const uint32_t g = blockIdx.x * 64u + threadIdx.x;
-	const int s = (int)__umulhi(g, chunks_magic);  // g / max_chunks (the host checked the magic number over the grid)
-	if (s >= nstreams) return;
-	const SlimPlan pl = plan[g];
-	if (pl.count < 0) return;
-	const int16_t *r = R + (size_t)s * rstride;
-	const ConstDiv cdiv(fast / slow);
-	SlimSink sink;
-	const int carried = sin[s].deemph_avg;
-	// the filter's state at j0
-	uint32_t v = (uint32_t)(carried + 32768), v2 = v;
-	if (pl.j0 > 0) {
-		bool settled = false;
-		if (pl.j0 > W) {
-			v = 0; v2 = 65535;
-			slim_walk<MAGIC, true>(r + pl.j0 - W, W, v, v2, ds, sink, slow, fast, cdiv);
-			settled = v == v2;
-		}
-		if (!settled) {
-			// close to the run's start, or a stretch of the stream the filter does not forget over: from the carried state
-			v = (uint32_t)(carried + 32768); v2 = v;
-			slim_walk<MAGIC, true>(r, pl.j0, v, v2, ds, sink, slow, fast, cdiv);
-		}
-	}
-	sink.init(B + (size_t)s * bstride, pl.m0, pl.phi0, pl.m0 == 0 && pl.j0 == 0 ? (uint32_t)sin[s].now_lpr : 0u, vec != 0);
-	slim_walk<MAGIC, false>(r + pl.j0, pl.count & (kSlimLast - 1), v, v2, ds, sink, slow, fast, cdiv);
-	sink.finish();
-	if (pl.count & kSlimLast) {
-		sout[s].deemph_avg = (int)v - 32768;
-		sout[s].now_lpr = (int)sink.acc;
-	}
-}
-
 // ---- deemph_filter alone, in one pass (round 5) ---------------------------------------------------------------
 // `rtl_fm -M fm -s 24k -E deemp` - the everyday narrow-band line - ends in deemph_filter with nothing behind it, and took
 // the four passes of the time-parallel form (A1, A2, B, C: the run read three times, written once, 0.77 ms of kernel time
@@ -2067,46 +1858,11 @@ k_adc_sums(const int16_t *__restrict__ R, size_t rstride, int N, int D, int nblo
 	__syncthreads();
 	if (threadIdx.x == 0) sums[sb] = red[0] + red[1] + red[2] + red[3];
 }
-// ... the smoothing recurrence sequentially per stream ...
-__global__ void k_adc_smooth(const long long *__restrict__ sums, int N, int D, int nblocks, int nstreams,
-                             int k, const state_t *__restrict__ sin, state_t *__restrict__ sout,
-                             int32_t *__restrict__ avg)
-{
-	RTLFM_GRID_STRIDE(s, nstreams) {
-		int prev = sin[s].dc_avg;
-		const int p0 = D > 1 ? sin[s].prev_index : 0;
-		for (int b = 0; b < nblocks; b++) {
-			const int len = dec_block_begin(b + 1, N, D, p0) - dec_block_begin(b, N, D, p0);
-			int m = (int)(sums[s * nblocks + b] / len);
-			m = (m + prev * k) / (k + 1);
-			avg[s * nblocks + b] = m;
-			prev = m;
-		}
-		sout[s].dc_avg = prev;
-	}
-}
-// ... and the subtraction (T = upper bound of the per-stream count).
-__global__ void __launch_bounds__(256)
-k_adc_apply(int16_t *__restrict__ R, size_t rstride, int N, int D, int nblocks, int nstreams, int T,
-            const state_t *__restrict__ sin, const int32_t *__restrict__ avg)
-{
-	const size_t total = (size_t)nstreams * T;
-	RTLFM_GRID_STRIDE(g, total) {
-		const int t = (int)(g % T);
-		const size_t s = g / T;
-		const int p0 = D > 1 ? sin[s].prev_index : 0;
-		const int b = dec_block_of(t, N, D, p0);
-		if (b >= nblocks) continue;
-		int16_t *r = R + s * rstride + t;
-		*r = (int16_t)(*r - avg[s * nblocks + b]);
-	}
-}
 
-// Round 5: the smoothing and the subtraction in ONE launch behind the sums, a workgroup per (stream, buffer).  The
+// ... then the smoothing and the subtraction in ONE launch behind the sums, a workgroup per (stream, buffer).  The
 // recurrence avg_b = (mean_b + k avg_{b-1}) / (k + 1) over a stream's buffers is two integer operations per buffer, so
-// every workgroup simply runs it from the carried dc_avg up to its own buffer (k_adc_smooth did that in a launch of its
-// own, one lane per stream), and the subtraction knows its buffer's extent instead of finding every sample's buffer with a
-// 64-bit division (k_adc_apply).  The last buffer's workgroup leaves dc_avg.  Same integers.
+// every workgroup simply runs it from the carried dc_avg up to its own buffer, and the subtraction knows its buffer's
+// extent.  The last buffer's workgroup leaves dc_avg.
 // (A first form - one workgroup per stream doing all three steps - was SLOWER at 256 streams x 64 buffers: 256 workgroups
 // do not fill the GPU; rtl_fm -M am -s 12k -E dc 0.82 -> 0.90 ms per step.)
 __global__ void __launch_bounds__(256)
@@ -2322,10 +2078,7 @@ __device__ __forceinline__ void arb_upsample_wave(const int16_t *a, int16_t *bo,
 // One workgroup of `wpw` waves per stream; wave w takes the spans w, w + wpw, ... of its stream, each wave with an
 // LDS region of its own (the span's traffic is wave-private: wave barriers, no workgroup barrier inside the loop).
 constexpr int kSpecArbMaxWaves = 8;
-// (i, frac) of one output as one 16-byte entry (k_deemph_arb_span; the host fills it beside tab_i / tab_frac)
-struct alignas(16) ArbTab { double frac; int32_t i; int32_t pad; };
 constexpr int kArbTabGap = 64;  // tab_i: i of every output, a gap, then k_deemph_spec_arb's padded offset 2 i + 16 (i >> 5) - 2
-static_assert(sizeof(ArbTab) == 16, "one 16-byte load per output");
 // (A/B builds, tools/build_variant.sh arb64 -DRTLFM_ARB_WAVES8: the kernel held to 64 registers so that TWO of its waves fit
 // the hole one front-end wave leaves on a SIMD - LAB.md I.28)
 #ifndef RTLFM_ARB_LOOP
@@ -2564,178 +2317,6 @@ k_deemph_spec_arb(int16_t *R, size_t rstride, int T, int nstreams, DeemphStep ds
 #endif
 	}
 	if (__any(unsettled) && lane == 0) wg_unsettled = 1;
-	}  // spans of this wave
-	// ---- anybody who could not settle (or a state outside int16): the reference's sequential loop, by wave 0 ------
-	__syncthreads();
-	if (wave != 0 || !(plain || wg_unsettled)) return;
-	if (lane == 0) {
-		// deemph_filter (src/rtl_fm.c:1011-1026) over the run, in place
-		if (plain) sout[s].deemph_avg = deemph_plain(r, T, carried, (int)ds.a);
-		else sout[s].deemph_avg = (int)deemph_walk<MAGIC, true>(r, T, (uint32_t)(carried + 32768), ds) - 32768;
-	}
-	__threadfence_block();
-	wave_sync();
-	for (int b = 0; b < nblocks; b++)
-		arb_upsample_wave(r + (size_t)b * N, B + s * bstride + (size_t)b * len2, N, len2, lane);
-}
-
-// ---- round 5: the same tail at half the instructions (k_deemph_spec_arb above stays as the cross-check, option
-// "arb_span" = 0).  profiles/r04_pmc_c3_k_deemph_spec_arb.txt counted 65 lane-operations per demodulated sample on 1 / 64
-// of the data - 16 % of config 3's step, and the step pays a tail's WORK in full.  Where they went and
-// what is different here:
-//   * the resampler's two samples per output came out of a padded chunk array: shift, multiply, mask and add per look-up,
-//     twice per output.  The span lies LINEAR in LDS here (sample k at y[k - (k0 - W)]): one address per output, the two
-//     samples at offsets -2 and 0.  The lane-per-chunk walks then read and write 16 bytes at a lane stride of 2 C bytes,
-//     four-way conflicted - eight LDS instructions per lane and chunk, against the hundreds of VALU ones saved;
-//   * (i, frac) of an output as ONE 16-byte table entry (one load, one pointer to advance) instead of two arrays;
-//   * a = 2 (16 and 24 kHz) takes the four-instruction step (DeemphStep::step<3>) instead of six;
-//   * the settle window grows in steps of 32 samples whatever the chunk length C is, so C = 64 halves the settling per
-//     sample (two walks over 32 samples per chunk of 64).
-constexpr int kArbSettle = 32;  // samples per settling step
-
-template <int MAGIC, int C>
-__global__ void __launch_bounds__(64 * kSpecArbMaxWaves)
-k_deemph_arb_span(int16_t *R, size_t rstride, int T, int nstreams, DeemphStep ds, int W, int spans,
-                  int N, int len2, int nblocks, const ArbTab *__restrict__ tab,
-                  int16_t *__restrict__ B, size_t bstride,
-                  const state_t *__restrict__ sin, state_t *__restrict__ sout, size_t lds_per_wave,
-                  int32_t *__restrict__ cnt_out)
-{
-#if RTLFM_TAIL_PRIO >= 0
-	__builtin_amdgcn_s_setprio(RTLFM_TAIL_PRIO);
-#endif
-	static_assert(C % kArbSettle == 0, "the settling steps end at the chunk's first sample");
-	extern __shared__ uint4 arb_lds[];
-	__shared__ int wg_unsettled;
-	const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6, wpw = (int)blockDim.x >> 6;
-	int16_t *y = reinterpret_cast<int16_t *>(reinterpret_cast<char *>(arb_lds) + (size_t)wave * lds_per_wave);
-	const size_t s = blockIdx.x;
-	constexpr int span = 64 * C;
-	int16_t *r = R + s * rstride;
-	const int carried = sin[s].deemph_avg;
-	if (threadIdx.x == 0) {
-		wg_unsettled = 0;
-		if (cnt_out) cnt_out[s] = nblocks * len2;
-	}
-	__syncthreads();
-	const bool plain = (uint32_t)(carried + 32768) > 65535u;  // no biased form: the reference's loop below
-	auto wave_sync = [&]() {
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-	};
-	auto walk8 = [&](const uint4 &q4, uint32_t &lo, uint32_t &hi) {
-		const uint32_t w4[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-		for (int i = 0; i < 4; i++) {
-			const uint32_t b2 = w4[i] ^ 0x80008000u;
-			lo = ds.step<MAGIC>(b2 & 0xffffu, lo); hi = ds.step<MAGIC>(b2 & 0xffffu, hi);
-			lo = ds.step<MAGIC>(b2 >> 16, lo); hi = ds.step<MAGIC>(b2 >> 16, hi);
-		}
-	};
-	for (int sp = wave; sp < spans && !plain; sp += wpw) {
-		const int k0 = sp * span, k1 = min(k0 + span, T);
-		const int kbase = k0 - W;  // y[p] = sample kbase + p
-		bool unsettled = false;
-		wave_sync();  // the span before is done with this wave's LDS region
-		// samples [k0 - W, k0 + span), zero outside the run: coalesced 16-byte loads, linear in LDS
-		for (int g = lane; g < (W + span) / 8; g += 64) {
-			const int k = kbase + g * 8;
-			uint4 v = make_uint4(0, 0, 0, 0);
-			if (k >= 0 && k + 8 <= T) v = *reinterpret_cast<const uint4 *>(r + k);
-			else if (k + 8 > 0 && k < T) {
-				uint32_t t[4] = {0, 0, 0, 0};
-				for (int j = 0; j < 8; j++)
-					if (k + j >= 0 && k + j < T) t[j >> 1] |= (uint32_t)(uint16_t)r[k + j] << (16 * (j & 1));
-				v = make_uint4(t[0], t[1], t[2], t[3]);
-			}
-			*reinterpret_cast<uint4 *>(y + g * 8) = v;
-		}
-		wave_sync();
-		const int begin = k0 + lane * C, end = min(begin + C, T);
-		uint32_t v = (uint32_t)(carried + 32768);
-		{
-			// both extreme states over the samples before the chunk: where they have met, that is the state, whatever came
-			// earlier (k_deemph_spec_arb).  32 samples first, more only while some lane of the wave is undecided.
-			const bool mine = begin > 0 && begin < T;
-			uint32_t lo = 0, hi = 65535;
-			const int steps_max = W / kArbSettle;
-			for (int nw = 1;; nw = nw * 2 < steps_max ? nw * 2 : steps_max) {
-				lo = 0; hi = 65535;
-				if (begin < nw * kArbSettle) lo = hi = v;  // the run starts inside the window: from the carried state, over the samples there are
-				for (int b = nw; b >= 1; b--) {
-					const int st = begin - b * kArbSettle;
-					if (st < 0) continue;
-					const uint4 *wp = reinterpret_cast<const uint4 *>(y + (st - kbase));
-#pragma unroll
-					for (int g = 0; g < kArbSettle / 8; g++) walk8(wp[g], lo, hi);
-				}
-				if (nw >= steps_max || !__any(mine && lo != hi)) break;
-			}
-			if (mine) {
-				unsettled = lo != hi;  // what this workgroup writes for the stream is replaced afterwards
-				v = lo;
-			}
-		}
-		wave_sync();  // every lane has read what it settles on: the chunks may be filtered in place
-		if (lane == 0) y[W - 1] = (int16_t)(uint16_t)(v ^ 0x8000u);  // the filtered sample before the span
-		if (begin < T) {
-			int16_t *cp = y + W + lane * C;
-			const int cntc = end - begin;
-			int k = 0;
-			for (; k + 8 <= cntc; k += 8) {
-				uint4 q4 = *reinterpret_cast<uint4 *>(cp + k);
-				uint32_t w4[4] = {q4.x, q4.y, q4.z, q4.w};
-#pragma unroll
-				for (int i = 0; i < 4; i++) {
-					const uint32_t b2 = w4[i] ^ 0x80008000u;
-					v = ds.step<MAGIC>(b2 & 0xffffu, v);
-					const uint32_t l16 = v;
-					v = ds.step<MAGIC>(b2 >> 16, v);
-					w4[i] = ((l16 & 0xffffu) | (v << 16)) ^ 0x80008000u;
-				}
-				*reinterpret_cast<uint4 *>(cp + k) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-			}
-			for (; k < cntc; k++) {
-				v = ds.step<MAGIC>((uint32_t)(uint16_t)cp[k] ^ 0x8000u, v);
-				cp[k] = (int16_t)(uint16_t)(v ^ 0x8000u);
-			}
-			if (end == T) sout[s].deemph_avg = (int)v - 32768;
-		}
-		wave_sync();
-		// arbitrary_upsample (src/rtl_fm.c:1114-1135) of the buffers that intersect the span: output j of a buffer from the
-		// filtered samples i - 1 and i, (i, frac) as the reference's loop holds them when it writes buf2[j] (the host walks
-		// that loop once per (len1, len2): rtlfm_hip.hip)
-		for (int b = k0 / N; b <= (k1 - 1) / N; b++) {
-			const int base = b * N;
-			const int ia = max(k0, base) - base, ib = min(k1, base + N) - base;
-			const int j0 = arb_first_output(ia, N, len2), j1 = arb_first_output(ib, N, len2);
-			int16_t *bo = B + s * bstride + (size_t)b * len2;
-			const int16_t *yb = y + (base - kbase);  // yb[i] = filtered sample i of buffer b
-			// The table entries of the NEXT four outputs of the lane travel while these four are computed: a tail wave beside
-			// the front end costs the step the wave slot it holds, not its instructions, and with one dependent
-			// trip to L2 per output (44 per span and lane) the wave spent most of its life waiting.
-			constexpr int PF = 4;
-			ArbTab cur[PF], nxt[PF];
-			int j = j0 + lane;
-#pragma unroll
-			for (int u = 0; u < PF; u++) cur[u] = tab[min(j + 64 * u, len2 - 1)];
-			for (; j < j1; j += 64 * PF) {
-#pragma unroll
-				for (int u = 0; u < PF; u++) nxt[u] = tab[min(j + 64 * (PF + u), len2 - 1)];
-#pragma unroll
-				for (int u = 0; u < PF; u++) {
-					const int ju = j + 64 * u;
-					if (ju < j1) {
-						const int16_t *pp = yb + cur[u].i;
-						bo[ju] = (int16_t)((double)pp[-1] * (1 - cur[u].frac) + (double)pp[0] * cur[u].frac);
-					}
-				}
-#pragma unroll
-				for (int u = 0; u < PF; u++) cur[u] = nxt[u];
-			}
-		}
-		if (__any(unsettled) && lane == 0) wg_unsettled = 1;
 	}  // spans of this wave
 	// ---- anybody who could not settle (or a state outside int16): the reference's sequential loop, by wave 0 ------
 	__syncthreads();

@@ -629,15 +629,14 @@ def test_fifth_order_on_buffers_its_passes_do_not_divide(oracle_lib, front, L):
 @pytest.mark.parametrize("L,nb,ns", [(16384, 9, 5), (262144, 3, 2), (512 * 23, 6, 3)])
 def test_dc_block_audio_in_one_launch(oracle_lib, ov, L, nb, ns):
     """dc_block_audio_filter (-E dc, src/rtl_fm.c:1028-1041) as the sums + ONE kernel for the smoothing recurrence and the
-    subtraction (k_adc_smooth_apply: a workgroup per buffer runs the recurrence up to its own buffer) and as round 4's three
-    kernels (adc_separate = 1):
-    the oracle's output and carried dc_avg either way, behind boxcars that do not divide the buffer, deemph in front of it,
+    subtraction (k_adc_smooth_apply: a workgroup per buffer runs the recurrence up to its own buffer):
+    the oracle's output and carried dc_avg, behind boxcars that do not divide the buffer, deemph in front of it,
     low_pass_real behind it, runs split over launches."""
     cfg = make_cfg(ov, L, nb)
     amp = 20.0 if ov.get("custom_atan") == 1 else 50.0
     iq = synth.fm_iq_u8(ns, L // 2 * nb, seed=L + nb, fs=1.008e6, dev_hz=3e3, amplitude=amp)
     want, want_len, wst = oracle_lib.run_batch(cfg, iq, nthreads=2)
-    for splits, opts in ((None, None), ([(0, 1), (1, nb)], None), (None, dict(adc_separate=1))):
+    for splits, opts in ((None, None), ([(0, 1), (1, nb)], None)):
         outs, sts, used = gpu_run(cfg, iq, path=0, splits=splits, options=opts)
         for s_ in range(ns):
             assert len(outs[s_]) == want_len[s_], (ov, L, splits, opts, s_)
@@ -689,6 +688,11 @@ def test_options_by_name():
         assert e.value.code == -2  # -ENOENT
         with pytest.raises(capi.RtlfmError):
             g.set_option("fused_waves", 0)
+        # the A/B forms that lost and went (LAB.md I.1, I.22) took their options with them
+        for gone in ("lpr_slim", "lpr_slim_chunk", "lpr_slim_prio", "arb_span", "arb_chunk", "adc_separate"):
+            with pytest.raises(capi.RtlfmError) as e:
+                g.set_option(gone, 1)
+            assert e.value.code == -2, gone
 
 
 @pytest.mark.parametrize("engine", ENGINES)
@@ -1139,6 +1143,21 @@ def test_deemph_time_parallel(oracle_lib, a, front):
         o = o.cpu().numpy(); n = n.cpu().numpy()
         for s in range(ns):
             assert np.array_equal(o[s, :n[s]], want[s, :want_len[s]]), ("injected", a, s)
+            assert g.state_get(s).deemph_avg == wst[s].deemph_avg
+    # ... and into rows that do not share the work buffer's alignment - a view shifted by two int16, four bytes off a 16-byte
+    # boundary, with a stride of 8 n + 2 (the least the library takes: rows of whole dwords): the one-pass kernel's
+    # fall-back (the sequential filter in place, then a copy)
+    with GpuDemod(c2, ns, 0) as g:
+        for s in range(ns):
+            g.state_set(s, st_copy[s])
+        cap = g.result_cap(nb)
+        full = torch.zeros((ns, ((cap + 9) & ~7) + 2), dtype=torch.int16, device="cuda")
+        view = full[:, 2:2 + cap]
+        assert view.data_ptr() % 16 == 4 and view.stride(0) % 8 == 2
+        o, n = g.run_torch(torch.from_numpy(iq).cuda(), out=view); g.sync()
+        o = o.cpu().numpy(); n = n.cpu().numpy()
+        for s in range(ns):
+            assert np.array_equal(o[s, :n[s]], want[s, :want_len[s]]), ("shifted rows", a, s)
             assert g.state_get(s).deemph_avg == wst[s].deemph_avg
 
 
@@ -1848,28 +1867,14 @@ def test_deemph_replay_feeds_low_pass_real(oracle_lib, a, rates, scalar):
 
 
 @pytest.mark.parametrize("opts", [dict(lpr_chunk=256), dict(lpr_chunk=5440), dict(deemph_four_pass=1),
-                                  dict(deemph_four_pass=1, lpr_chunk=256), dict(lpr_separate=1), dict(lpr_slim=0),
+                                  dict(deemph_four_pass=1, lpr_chunk=256), dict(lpr_separate=1),
                                   dict(lpr_ring=0), dict(lpr_scalar_stores=1), dict(lpr_threads=64), dict(lpr_threads=192),
                                   dict(lpr_threads=128, lpr_chunk=256)])
 def test_lpr_tail_options(oracle_lib, opts):
-    """The same tail under its options: round 5's one-pass kernel (k_deemph_spec_lpr, `lpr_slim = 0`) with chunk lengths below
+    """The same tail under its options: the one-pass kernel (k_deemph_spec_lpr, the default) with chunk lengths below
     and above the four-pass route's own chunk (the chunk tables are sized per route) and its three ways of storing, the four
     passes instead of the one-pass kernel, low_pass_real as a kernel of its own."""
     _lpr_tail_case(oracle_lib, 13, (170000, 32000), opts)
-
-
-@pytest.mark.parametrize("a,rates", [(13, (170000, 32000)), (2, (48000, 11025)), (30, (240000, 96000)), (9, (170000, 169999))])
-@pytest.mark.parametrize("chunk", [256, 680, 6120, 100000])
-def test_lpr_slim_tail(oracle_lib, a, rates, chunk):
-    """Round 6's form of -M wbfm's tail (k_lpr_slim_plan + k_deemph_lpr_slim: 32 registers, no LDS, every lane a stretch of
-    its stream between two emissions of low_pass_real, nothing put together afterwards) over chunk lengths from far below
-    the settling window (every lane then walks from the stream's carried state) to longer than the run (one lane per
-    stream), with what _lpr_tail_case holds: carried accumulators and phases, a filter state outside int16 and a resampler
-    phase outside [0, fast) (the plan kernel's own loops), a silent stream and one that falls silent (lanes that cannot
-    settle), runs split over launches, rows stored in 16-byte groups and one by one."""
-    _lpr_tail_case(oracle_lib, a, rates, dict(lpr_slim=1, lpr_slim_chunk=chunk), weird_phase=True)
-    if chunk == 680:
-        _lpr_tail_case(oracle_lib, a, rates, dict(lpr_slim=1, lpr_slim_chunk=chunk, lpr_scalar_stores=1))
 
 
 def test_lpr_chunk_range():
@@ -1889,7 +1894,7 @@ def test_lpr_chunk_range():
         assert g.get_option("lpr_threads") == 256 and g.get_option("arb_waves") == 0 and g.get_option("arb_serial") == -1
 
 
-def _lpr_tail_case(oracle_lib, a, rates, options, weird_phase=False):
+def _lpr_tail_case(oracle_lib, a, rates, options):
     from rtlsdr_amd.demod import GpuDemod
     L, nb, ns = 32768, 6, 6
     ov = dict(downsample=6, custom_atan=1, deemph=1, deemph_a=a, rate_out=rates[0], rate_out2=rates[1],
@@ -1904,9 +1909,6 @@ def _lpr_tail_case(oracle_lib, a, rates, options, weird_phase=False):
         st0[s].prev_lpr_index = (s * 7919) % rates[0]
         st0[s].deemph_avg = 123 * s
     st0[ns - 1].deemph_avg = 90000
-    if weird_phase:
-        st0[3].prev_lpr_index = rates[0] + 12345  # what no run of the chain leaves behind: an emission on every sample until it is back in range
-        st0[4].prev_lpr_index = -777
     st_copy = [capi.RtlfmStreamState.from_buffer_copy(bytes(st0[s])) for s in range(ns)]
     want, want_len, wst = oracle_lib.run_batch(cfg, iq, states=st0, nthreads=2)
     for splits in (None, [(0, 2), (2, 3), (3, 6)]):
@@ -1953,10 +1955,8 @@ def test_deemph_feeds_arbitrary_upsample(oracle_lib, passes, L, nb, a, rates):
     st0[ns - 1].deemph_avg = -70000
     st_copy = [capi.RtlfmStreamState.from_buffer_copy(bytes(st0[s])) for s in range(ns)]
     want, want_len, wst = oracle_lib.run_batch(cfg, iq, states=st0, nthreads=2)
-    # arb_span: round 5's form of the kernel (k_deemph_arb_span: the span linear in LDS), with 32 and 64 samples per lane
     # arb_waves: the spans of a stream dealt to 1 .. 8 waves (default: as many as make about 16384 waves of all streams)
-    for splits, options in ((None, {}), ([(0, 1), (1, nb)], {}), (None, dict(arb_span=1)), ([(0, 1), (1, nb)], dict(arb_span=1, arb_chunk=64)),
-                            (None, dict(arb_span=1, arb_chunk=64)), (None, dict(arb_waves=1)), ([(0, 1), (1, nb)], dict(arb_waves=3)),
+    for splits, options in ((None, {}), ([(0, 1), (1, nb)], {}), (None, dict(arb_waves=1)), ([(0, 1), (1, nb)], dict(arb_waves=3)),
                             (None, dict(arb_waves=8)),
                             # arb_serial: this tail on the front end's stream (what handles of 2048 streams and more do by themselves)
                             ([(0, 1), (1, nb)], dict(arb_serial=1)), (None, dict(arb_serial=0))):
