@@ -165,6 +165,27 @@ int rtlfm_gpu_destroy(rtlfm_gpu *h);
  * concurrently with rtlfm_gpu_run(): the ring has two halves, and a callback never waits for a
  * transfer or a kernel.  -ENOSPC when max_blocks buffers are already queued for the stream, -EBUSY while
  * the stream has a slot open between rtlfm_gpu_acquire() and rtlfm_gpu_commit() (one producer per stream).
+ *
+ * The ring and channels.  The ring's INPUT side - the pinned staging rows, their device copies, the counts - has one row
+ * per stream.  While channels are on (rtlfm_gpu_set_channels) every call of the ring is refused with -ENOTSUP, unless the
+ * handle's option source_ring is 1 (rtlfm_gpu_set_option; default 0): then the input side has one row per SOURCE,
+ * rows = nstreams / per_source, and
+ *   - `stream` of rtlfm_gpu_push / _acquire / _commit is the source's index in [0, rows), anything else -EINVAL;
+ *   - rtlfm_gpu_run / _run_begin want the same number of buffers from every source (-EAGAIN otherwise) and buffer k of
+ *     the run of ONE length on every source: pos is one counter per handle.  Lengths that differ between the sources
+ *     are -ERANGE; nothing is taken, and rtlfm_gpu_reset empties the ring.  Short buffers whose lengths agree are run
+ *     buffer by buffer through the channel front ends, each of which takes every length the ring accepts;
+ *   - a run copies rows rows to the device and is one rtlfm_gpu_run_device on them: pos advances and the source
+ *     history changes over once per run, ring runs and rtlfm_gpu_run_device calls may alternate on one handle, and
+ *     rtlfm_gpu_channels_tell counts both;
+ *   - the RESULT side stays per stream (= per channel): rtlfm_gpu_fetch / _fetch_all / _fetch_all_prev,
+ *     rtlfm_gpu_levels*.
+ * At 64 sources x 64 channels with 4 x 262144-byte buffers the ring pins 2 x 64 MiB instead of 2 x 4 GiB.  With
+ * channels off the option changes nothing: rows = streams.  The option itself: -EINVAL for anything but 0 / 1; -EBUSY,
+ * changing nothing, while a run is begun, a slot is open or buffers are queued.  rtlfm_gpu_set_channels with the option
+ * on says -EBUSY while buffers are queued; otherwise both rebuild the input side at once for the new number of rows
+ * (a failed allocation there is tried again by the next call of the ring).  Results of runs before such a call STAY
+ * fetchable: the result side is not touched.  The mute, the statistics, the gate and the snapshots stay refused.
  */
 int rtlfm_gpu_push(rtlfm_gpu *h, int stream, const uint8_t *iq, uint32_t len);
 
@@ -408,9 +429,11 @@ int rtlfm_gpu_load(rtlfm_gpu *h, const char *path);
  *     every channel's decimated IQ (k_channel_boxcar; rtlfm_gpu_last_path says 2), everything else through the staged
  *     kernels behind k_channel_mix (1); rtlfm_gpu_set_path(1) forces the latter, 2 with fifth_order passes is -ENOTSUP.
  * What reads or owns per-STREAM input rows, or would lose pos, is refused with -ENOTSUP and changes nothing while
- * channels are on: rtlfm_gpu_push / _acquire / _commit / _run / _run_begin (the ring), the options input_stats,
+ * channels are on: rtlfm_gpu_push / _acquire / _commit / _run / _run_begin (the ring) unless the option source_ring
+ * gives the ring a row per source ("The ring and channels" at rtlfm_gpu_push), the options input_stats,
  * input_health and squelch_gate, rtlfm_gpu_mute, rtlfm_gpu_save / _load / _state_move; and rtlfm_gpu_set_channels itself
- * on a handle with cfg.dc_block_raw or one of those options on (-EBUSY with a run begun, a ring slot open or a mute owed).
+ * on a handle with cfg.dc_block_raw or one of those options on (-EBUSY with a run begun, a ring slot open or a mute owed,
+ * and - option source_ring on - with buffers queued in the ring, whose rows it would change).
  * rtlfm_gpu_channels_seek / _tell: set / read pos (a caller that resumes a recording sets where it is).
  */
 uint32_t rtlfm_channel_step(int32_t shift_hz, uint32_t capture_rate);

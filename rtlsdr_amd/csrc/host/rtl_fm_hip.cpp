@@ -61,6 +61,22 @@
 // Not with -S, -C or -O agc=2: those host engines carry state of their own (hop position and settle counters, the
 // monitor's cycles, the AGC's index and counters) that the snapshot does not hold.
 //
+// -X file (not a reference letter): channels.  Line i of the file is the list of channel frequencies of source i, in -S's
+// grammar (blanks, tabs or commas, a:b:step ranges, k / M / G; blank lines and lines that start with '#' are skipped), and
+// every line stands for the same number K of channels: n lines with -N n, one without.  Source i is tuned to its -f AS
+// GIVEN - no capture_rate / 4 offset, no +16 kHz under -M wbfm: the library's NCO mixers take the rotation's place, channel
+// c of source i with the step rtlfm_channel_step(channel_freq - f_i, capture_rate) (include/rtlfm_hip.h,
+// rtlfm_gpu_set_channels), and a channel further than capture_rate / 2 from its source's -f is refused.  The rate plan is
+// optimal_settings()' as under -N; -m chooses the capture rate.  ONE handle of n x K streams with the library's option
+// source_ring, so that the ring has a row per SOURCE: handle stream s = channel s % K of source s / K writes the file
+// with %d = s; -H, -L ("stream s:") and -l work per stream as under -N without the device gate.  -x ntaps puts the channel
+// filter rtlfm_channel_lowpass(ntaps, 0.4 / D, D) in the boxcar's place (not with -F: the filter stands where the boxcar
+// stands; where its taps do not fit an int16 - fewer taps than D needs - the same filter at D / 2^k and shift 14 - k).  The demod thread pushes the same number of buffers for every source and run (run_channels below); the
+// streams run in lockstep on ONE sample counter, and no handle is shrunk (the library refuses state_move with channels):
+// a source's short last buffer is completed with bytes 127 - which mix to 0 at every phase - to the full length and
+// demodulated, a source that has ended is fed buffers of bytes 127 and its K files receive nothing more, until the last
+// source ends.  Not with -S, -C, -K, -R, -Z, -O agc=2 or -E rdc: each needs what the library refuses while channels are on.
+//
 // Not restated (out of scope): the command file's own hop (its 2 x 3 200 000 byte mute, the DC-filter reset, -B), and
 // -t negative (terminate on squelch).
 #include <getopt.h>
@@ -507,6 +523,9 @@ struct Multi {
 	std::vector<rtlfm_stream_state> kept;
 	std::vector<int> live;                   // handle stream k -> source, as the demod thread left it
 	std::vector<rtlfm_stream_state> states;  // one rtlfm_gpu_state_get_all: -l without a device gate, -K
+	// -X: K channels per source; chan[s] = what handle stream s owns (its file, wave header, -L counters), index = s
+	int chan_per = 0;
+	std::vector<Source> chan;
 };
 
 // the options a handle of this tool runs with besides its configuration
@@ -907,7 +926,7 @@ void output_thread_multi(Multi *m)
 			m->out_q.pop_front();
 		}
 		for (size_t k = 0; k < o.who.size(); k++) {
-			Source &s = m->src[o.who[k]];
+			Source &s = m->chan_per ? m->chan[o.who[k]] : m->src[o.who[k]];  // (-X: who = the handle's streams)
 			const size_t n = (size_t)o.lens[k];
 			if (!n) continue;
 			fwrite(o.pcm.data() + k * o.stride, 2, n, s.file);
@@ -915,7 +934,7 @@ void output_thread_multi(Multi *m)
 			s.samples_out += n;
 		}
 	}
-	for (Source &s : m->src) fflush(s.file);
+	for (Source &s : m->chan_per ? m->chan : m->src) fflush(s.file);
 }
 
 // everything after option parsing for n > 1 (main has refused what -N does not allow)
@@ -1095,6 +1114,239 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 	return ret;
 }
 
+// ---- -X: K channels per source, one handle of n x K streams over the library's source-indexed ring ------------------
+//
+// The device side is -N's: on_buffer_multi / dongle_thread_multi, a host queue per source.  The demod thread takes
+// b = min(what every live queue holds, max_blocks) buffers from every live source and pushes them with the SOURCE's index
+// (option source_ring); a short buffer - a file's last - is completed with bytes 127 to the full length, and a source
+// that has ended is fed b buffers of bytes 127, so that every source has one length per buffer index and the handle's one
+// sample counter holds for all.  The streams of an ended source write nothing more.  The run ends with the last source.
+void demod_thread_channels(Multi *m)
+{
+	const int n = (int)m->src.size(), K = m->chan_per, S = n * K;
+	const size_t stride = ((size_t)rtlfm_result_cap(&m->cfg) * m->cfg.max_blocks + 16 + 63) / 64 * 64;
+	const uint32_t L = m->cfg.block_len;
+	const std::vector<uint8_t> silence(L, 127);
+	std::vector<int> who((size_t)S);
+	for (int s = 0; s < S; s++) who[(size_t)s] = s;
+	std::vector<char> ended((size_t)n, 0);
+	for (;;) {
+		int b = m->cfg.max_blocks, live = 0;
+		{
+			std::unique_lock<std::mutex> g(m->m);
+			m->cv_work.wait(g, [&] {
+				if (m->failed) return true;
+				for (int i = 0; i < n; i++)
+					if (!ended[(size_t)i] && m->src[(size_t)i].q.empty() && !m->src[(size_t)i].eof) return false;
+				return true;
+			});
+			if (m->failed) break;
+			for (int i = 0; i < n; i++) {
+				Source &s = m->src[(size_t)i];
+				if (!ended[(size_t)i] && s.q.empty()) ended[(size_t)i] = 1;  // an empty queue here means the source has ended
+				if (ended[(size_t)i]) continue;
+				live++;
+				b = std::min(b, (int)s.q.size());
+			}
+			for (int i = 0; i < n; i++) {
+				Source &s = m->src[(size_t)i];
+				if (ended[(size_t)i]) continue;
+				for (int j = 0; j < b; j++) {
+					s.taken.push_back(std::move(s.q.front()));
+					s.q.pop_front();
+				}
+				s.cv_room.notify_all();
+			}
+		}
+		if (!live) break;
+		int r = 0;
+		for (int i = 0; i < n && r == 0; i++) {
+			if (ended[(size_t)i]) {
+				for (int j = 0; j < b && r == 0; j++) r = rtlfm_gpu_push(m->gpu, i, silence.data(), L);
+				continue;
+			}
+			for (std::vector<uint8_t> &buf : m->src[(size_t)i].taken) {
+				if (buf.size() < L) buf.resize(L, 127);  // the source's short last buffer, completed
+				if ((r = rtlfm_gpu_push(m->gpu, i, buf.data(), L)) < 0) break;
+			}
+		}
+		int ran = 0;
+		if (r == 0) r = rtlfm_gpu_run_begin(m->gpu, &ran);
+		if (r == 0 && ran != b) r = -EPROTO;
+		if (r == 0) r = rtlfm_gpu_run_end(m->gpu);
+		RunOut o;
+		o.stride = stride;
+		o.pcm.resize((size_t)S * stride);
+		o.lens.resize((size_t)S);
+		o.who = who;
+		if (r == 0) r = rtlfm_gpu_fetch_all(m->gpu, o.pcm.data(), stride, o.lens.data());
+		if (r < 0) {
+			std::lock_guard<std::mutex> g(m->m);
+			fail_multi(m, "rtlfm_gpu_push/run/fetch_all", r);
+			break;
+		}
+		for (int s = 0; s < S; s++)
+			if (ended[(size_t)(s / K)]) o.lens[(size_t)s] = 0;
+		if (m->print_levels)
+			for (int s = 0; s < S; s++)
+				if (!ended[(size_t)(s / K)]) levels_multi(m, m->chan[(size_t)s], s);
+		if (m->cfg.squelch_level) {
+			// demod_thread's squelch rule per stream, as demod_thread_multi applies it without the device gate (max_blocks is 1)
+			m->states.resize((size_t)S);
+			int got = 0;
+			bool clamped = false;
+			if (rtlfm_gpu_state_get_all(m->gpu, m->states.data(), S, &got) == 0) {
+				for (int s = 0; s < S; s++) {
+					rtlfm_stream_state &st = m->states[(size_t)s];
+					if (st.squelch_hits <= m->conseq_squelch) continue;
+					clamped |= st.squelch_hits != m->conseq_squelch + 1;
+					st.squelch_hits = m->conseq_squelch + 1;
+					if (!ended[(size_t)(s / K)]) m->chan[(size_t)s].blocks_squelched++;
+					o.lens[(size_t)s] = 0;
+				}
+				if (clamped) rtlfm_gpu_state_set_all(m->gpu, m->states.data(), S);
+			}
+		}
+		std::lock_guard<std::mutex> g(m->m);
+		for (Source &s : m->src) {
+			for (std::vector<uint8_t> &buf : s.taken) s.spare.push_back(std::move(buf));
+			s.taken.clear();
+		}
+		m->out_q.push_back(std::move(o));
+		m->cv_out.notify_one();
+	}
+	std::lock_guard<std::mutex> g(m->m);
+	m->out_done = true;
+	m->cv_out.notify_all();
+}
+
+// everything after option parsing for -X (main has refused what -X does not allow): freqs[i] = source i's -f as given,
+// chan_freqs[i] = its K channel frequencies, each within capture_rate / 2 of freqs[i]
+int run_channels(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<uint32_t> &freqs,
+                 const std::vector<std::vector<uint32_t>> &chan_freqs, uint32_t capture_rate, int gain, int ppm,
+                 const std::string &pattern, bool write_wav, int verbosity, int conseq_squelch, int print_levels,
+                 const char *opt_string, int agc, int ntaps)
+{
+	Multi m;
+	m.cfg = planned;
+	rtlfm_cfg &c = m.cfg;
+	const int K = (int)chan_freqs[0].size(), S = n * K;
+	m.chan_per = K;
+	m.depth = 2 * c.max_blocks;
+	m.verbosity = verbosity;
+	m.conseq_squelch = conseq_squelch;
+	m.print_levels = print_levels;
+	m.src = std::vector<Source>((size_t)n);
+	m.chan = std::vector<Source>((size_t)S);
+	const uint32_t count = rtlsdr_get_device_count();
+	if (count == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE or RTLSDR_FILE_LIST).\n"); return 1; }
+	if ((uint64_t)dev_index + (uint64_t)n > count) {
+		fprintf(stderr, "-d %d with %d sources needs devices %d .. %d, and there are %u.\n", dev_index, n, dev_index, dev_index + n - 1, count);
+		return 1;
+	}
+	int ret = 0;
+	for (int i = 0; i < n && !ret; i++) {
+		Source &s = m.src[(size_t)i];
+		s.index = i;
+		s.m = &m;
+		s.user_freq = s.capture_freq = freqs[(size_t)i];  // as given: the mixers take the rotation's place
+		if (rtlsdr_open(&s.dev, (uint32_t)(dev_index + i)) < 0) {
+			fprintf(stderr, "Failed to open rtlsdr device #%d.\n", dev_index + i);
+			ret = 1;
+			break;
+		}
+		if (gain == -100) rtlsdr_set_tuner_gain_mode(s.dev, 0);
+		else { rtlsdr_set_tuner_gain_mode(s.dev, 1); rtlsdr_set_tuner_gain(s.dev, gain); }
+		if (opt_string) rtlsdr_set_opt_string(s.dev, opt_string, verbosity);
+		if (agc >= 0) rtlsdr_set_tuner_gain_mode(s.dev, agc);
+		rtlsdr_set_freq_correction_ppb(s.dev, ppm * 1000);
+		rtlsdr_set_offset_tuning(s.dev, c.offset_tuning);
+		rtlsdr_set_center_freq(s.dev, s.capture_freq);
+		if (rtlsdr_set_sample_rate(s.dev, capture_rate) < 0 && i == 0)
+			fprintf(stderr, "WARNING: capture rate %u Hz is outside what an RTL2832 can do.\n", capture_rate);
+		fprintf(stderr, "source %d: device #%d, tuned to %u Hz, streams %d .. %d.\n", i, dev_index + i, s.capture_freq, i * K, i * K + K - 1);
+	}
+	if (!ret) {
+		fprintf(stderr, "%d sources x %d channels = %d streams.\nOversampling input by: %ix.\nSampling at %u S/s.\nOutput at %u Hz.\n", n, K, S,
+		        c.downsample, capture_rate, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out));
+		std::vector<uint32_t> steps((size_t)S);
+		for (int s = 0; s < S; s++) {
+			const uint32_t cf = chan_freqs[(size_t)(s / K)][(size_t)(s % K)];
+			steps[(size_t)s] = rtlfm_channel_step((int32_t)((int64_t)cf - (int64_t)freqs[(size_t)(s / K)]), capture_rate);
+			if (verbosity) fprintf(stderr, "stream %d: source %d, %u Hz, step %u\n", s, s / K, cf, steps[(size_t)s]);
+		}
+		const char *what = "rtlfm_gpu_create";
+		int r = rtlfm_gpu_create(&c, S, 0, &m.gpu);
+		if (r == 0) { what = "option source_ring"; r = rtlfm_gpu_set_option(m.gpu, "source_ring", 1); }
+		if (r == 0) { what = "rtlfm_gpu_set_channels"; r = rtlfm_gpu_set_channels(m.gpu, K, steps.data()); }
+		if (r == 0 && ntaps > 0) {
+			// the cutoff the benchmarks use: 0.4 of the output rate, in cycles per capture sample
+			std::vector<int16_t> taps((size_t)ntaps);
+			int shift = 0;
+			what = "rtlfm_channel_lowpass";
+			// (-ERANGE: fewer taps than the gain D needs at shift 14 - a tap beyond an int16, a short filter at a large D.  The
+			// same filter at half the scale and one bit less shift has the same DC gain, as long as D stays whole.)
+			int gain = c.downsample, less = 0;
+			r = rtlfm_channel_lowpass(ntaps, 0.4 / c.downsample, gain, taps.data(), &shift);
+			while (r == -ERANGE && gain % 2 == 0 && less < 14) {
+				gain /= 2;
+				less++;
+				r = rtlfm_channel_lowpass(ntaps, 0.4 / c.downsample, gain, taps.data(), &shift);
+			}
+			shift -= less;
+			if (r == 0 && (less || verbosity)) fprintf(stderr, "-x %d: gain %d at shift %d\n", ntaps, gain, shift);
+			if (r == 0) { what = "rtlfm_gpu_set_channel_filter"; r = rtlfm_gpu_set_channel_filter(m.gpu, taps.data(), ntaps, shift); }
+		}
+		if (r < 0) {
+			fprintf(stderr, "%s: %s\n", what, rtlfm_gpu_strerror(r));
+			ret = 2;
+		}
+	}
+	const size_t at = pattern.find("%d");
+	for (int s = 0; s < S && !ret; s++) {
+		Source &ch = m.chan[(size_t)s];
+		ch.index = s;
+		ch.user_freq = chan_freqs[(size_t)(s / K)][(size_t)(s % K)];
+		const std::string name = at == std::string::npos ? pattern : pattern.substr(0, at) + std::to_string(s) + pattern.substr(at + 2);
+		ch.file = fopen(name.c_str(), "wb");
+		if (!ch.file) { fprintf(stderr, "Failed to open %s\n", name.c_str()); ret = 1; break; }
+		if (write_wav)
+			rtlamd_wave_write_header(&ch.wave, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out), ch.user_freq, 16,
+			                         c.mode == RTLFM_MODE_RAW ? 2 : 1, ch.file);
+	}
+	if (!ret) {
+		for (Source &s : m.src) rtlsdr_reset_buffer(s.dev);
+		std::thread t_out(output_thread_multi, &m), t_demod(demod_thread_channels, &m);
+		std::vector<std::thread> t_dongle;
+		for (Source &s : m.src) t_dongle.emplace_back(dongle_thread_multi, &s);
+		for (std::thread &t : t_dongle) t.join();
+		t_demod.join();
+		t_out.join();
+		uint64_t in = 0, out = 0, sq = 0;
+		for (Source &s : m.src) in += s.blocks_in;
+		for (Source &ch : m.chan) {
+			out += ch.samples_out;
+			sq += ch.blocks_squelched;
+		}
+		fprintf(stderr, "%llu buffers in, %llu samples out, %llu buffers held back by the squelch%s\n", (unsigned long long)in,
+		        (unsigned long long)out, (unsigned long long)sq, m.failed ? " (FAILED)" : "");
+		if (verbosity)
+			for (Source &ch : m.chan)
+				fprintf(stderr, "stream %d: %llu samples out, %llu buffers held back by the squelch\n", ch.index,
+				        (unsigned long long)ch.samples_out, (unsigned long long)ch.blocks_squelched);
+		if (m.failed) ret = 3;
+	}
+	for (Source &ch : m.chan)
+		if (ch.file) {
+			if (write_wav) rtlamd_wave_finalize(&ch.wave, ch.file);
+			fclose(ch.file);
+		}
+	for (Source &s : m.src)
+		if (s.dev) rtlsdr_close(s.dev);
+	if (m.gpu) rtlfm_gpu_destroy(m.gpu);
+	return ret;
+}
+
 // -R: the file against what the command line plans, before a device is opened: 0, or the exit status (2) behind the
 // library's text.  The handle checks the same again when it loads the file (rtlfm_gpu_load).
 int check_resume(const char *path, const rtlfm_cfg &planned, int nstreams)
@@ -1127,6 +1379,11 @@ void usage()
 	        "\t       adcrms lines add the ADC statistics of the raw bytes; sets -M raw; -v prints every event]\n"
 	        "\t[-S scan_file  scanning: line i of the file is the frequency list of source i (-N n, or one source): frequencies\n"
 	        "\t       and a:b:step ranges; needs -l; a source whose squelch holds a buffer hops to its next frequency; not with -C]\n"
+	        "\t[-X channel_file  channels: line i of the file is the list of channel frequencies of source i (-N n, or one source), in\n"
+	        "\t       -S's grammar, the same number K on every line; source i's centre frequency is its -f as given and its K channels are mixed\n"
+	        "\t       down on the GPU; stream s = channel s %% K of source s / K writes the file with %%d = s; not with -S -C -K -R -Z,\n"
+	        "\t       -O agc=2 or -E rdc]\n"
+	        "\t[-x ntaps  with -X: a windowed-sinc channel filter of ntaps taps (cutoff 0.4 of the output rate) in the boxcar's place; not with -F]\n"
 	        "\t[-K file  keep: write every stream's carried filter state to file at exit (with -N n: n records, in source order)]\n"
 	        "\t[-R file  resume: load such a file before the first buffer - it must hold as many records as there are sources and\n"
 	        "\t       come from the same -M / -s / -r / -F / -A / -E / -l / -W ... plan, else exit 2; the output continues as if the tool had\n"
@@ -1165,11 +1422,13 @@ int main(int argc, char **argv)
 	bool have_freq = false, write_wav = false, wb_mode = false;
 	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
 	const char *cmd_file = nullptr, *opt_string = nullptr, *scan_file = nullptr, *keep_file = nullptr, *resume_file = nullptr;
+	const char *chan_file = nullptr;  // -X
+	int chan_taps = -1;               // -x; -1: not given
 	int agc = -1;  // -O agc=<n>; -1: not given
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
-	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:K:R:")) != -1) {
+	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:K:R:X:x:")) != -1) {
 		switch (opt) {
 		case 'd': dev_index = atoi(optarg); break;
 		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
@@ -1178,6 +1437,8 @@ int main(int argc, char **argv)
 		case 'S': scan_file = optarg; break;
 		case 'K': keep_file = optarg; break;
 		case 'R': resume_file = optarg; break;
+		case 'X': chan_file = optarg; break;
+		case 'x': chan_taps = atoi(optarg); break;
 		case 'O':
 			opt_string = optarg;
 			agc = opt_string_agc(optarg);
@@ -1243,6 +1504,31 @@ int main(int argc, char **argv)
 		case 'Z': a.zero_copy = true; break;
 		case 'v': a.verbosity++; break;
 		default: usage();
+		}
+	}
+	if (chan_taps != -1 && !chan_file) {
+		fprintf(stderr, "-x (taps of the channel filter) needs -X (the channel file): the filter acts on channels only.\n");
+		return 1;
+	}
+	if (chan_file) {
+		// everything -X refuses for what it is combined with is refused here, before a device is opened or a handle created:
+		// each of these needs what the library refuses while channels are on (include/rtlfm_hip.h, rtlfm_gpu_set_channels)
+		const char *with = nullptr, *why = nullptr;
+		if (scan_file) { with = "-S (scan lists)"; why = "a hop needs the hop mute and the squelch gate, which read per-stream input rows"; }
+		else if (cmd_file) { with = "-C (command file)"; why = "the monitor needs the option input_stats, which reads per-stream input rows"; }
+		else if (keep_file) { with = "-K (keep)"; why = "a snapshot does not hold the channels' sample counter"; }
+		else if (resume_file) { with = "-R (resume)"; why = "a snapshot does not hold the channels' sample counter"; }
+		else if (a.zero_copy) { with = "-Z (zero-copy)"; why = "the ring is filled from the sources' host queues, in lockstep"; }
+		else if (agc == 2) { with = "-O agc=2 (software AGC)"; why = "it needs the option input_health, which reads per-stream input rows"; }
+		else if (c.dc_block_raw) { with = "-E rdc (raw DC block)"; why = "it rides on the rotation's kernel, whose place the mixers take"; }
+		else if (chan_taps != -1 && fifth) { with = "-x (channel filter) with -F (fifth-order low pass)"; why = "the channel filter stands in the boxcar's place, and -F leaves no boxcar"; }
+		if (with) {
+			fprintf(stderr, "-X (channel file) does not go with %s: %s.\n", with, why);
+			return 1;
+		}
+		if (chan_taps != -1 && (chan_taps < 1 || chan_taps > RTLFM_CHANNEL_MAX_TAPS)) {
+			fprintf(stderr, "-x %d with -X: the channel filter takes 1 .. %d taps.\n", chan_taps, RTLFM_CHANNEL_MAX_TAPS);
+			return 1;
 		}
 	}
 	if ((keep_file || resume_file) && (scan_file || cmd_file || agc == 2)) {
@@ -1320,6 +1606,85 @@ int main(int argc, char **argv)
 	const char *filename = optind < argc ? argv[optind] : "-";
 
 	if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
+	if (chan_file) {
+		// -X: the file, the names and the plan, all before a device is opened or a GPU handle created
+		std::vector<std::vector<uint32_t>> chan_freqs;
+		std::vector<int> chan_lineno;
+		FILE *xf = fopen(chan_file, "r");
+		if (!xf) { fprintf(stderr, "-X %s: cannot open the channel file\n", chan_file); return 1; }
+		char line[65536];
+		int lineno = 0;
+		while (fgets(line, sizeof(line), xf)) {
+			lineno++;
+			const char *t = line;
+			while (*t == ' ' || *t == '\t') t++;
+			if (*t == '#' || *t == '\n' || *t == '\r' || !*t) continue;
+			int nf = 0;
+			int pr = rtlfm_scan_parse_list(t, nullptr, 0, &nf);
+			std::vector<uint32_t> fl((size_t)(nf > 0 ? nf : 0));
+			if (pr == -ENOBUFS) pr = rtlfm_scan_parse_list(t, fl.data(), nf, &nf);
+			if (pr < 0) { fclose(xf); fprintf(stderr, "-X %s: line %d is no frequency list\n", chan_file, lineno); return 1; }
+			chan_freqs.push_back(std::move(fl));
+			chan_lineno.push_back(lineno);
+		}
+		fclose(xf);
+		if ((int)chan_freqs.size() != nstreams) {
+			fprintf(stderr, "-X %s holds %zu lists, -N %d needs exactly %d: line i of the file is the channel list of source i.\n", chan_file,
+			        chan_freqs.size(), nstreams, nstreams);
+			return 1;
+		}
+		for (size_t i = 1; i < chan_freqs.size(); i++)
+			if (chan_freqs[i].size() != chan_freqs[0].size()) {
+				fprintf(stderr, "-X %s: line %d stands for %zu channels and line %d for %zu; every source needs the same number of channels "
+				        "(-N sources share one handle).\n", chan_file, chan_lineno[i], chan_freqs[i].size(), chan_lineno[0], chan_freqs[0].size());
+				return 1;
+			}
+		const size_t total = chan_freqs.size() * chan_freqs[0].size();
+		if (freqs.size() != 1 && freqs.size() != (size_t)nstreams) {
+			fprintf(stderr, "-X with -N %d: give -f once (every source) or %d times (one per source), not %zu times.\n", nstreams, nstreams,
+			        freqs.size());
+			return 1;
+		}
+		if (freqs.size() == 1) freqs.assign((size_t)nstreams, freqs[0]);
+		const std::string pattern(filename);
+		const size_t at = pattern.find("%d");
+		if (total > 1 && (at == std::string::npos || pattern.find("%d", at + 2) != std::string::npos)) {
+			fprintf(stderr, "-X with %zu streams: the filename must hold exactly one %%d (the stream index), e.g. out_%%d.raw.\n", total);
+			return 1;
+		}
+		if (pattern == "-" || (total == 1 && at != std::string::npos && pattern.find("%d", at + 2) != std::string::npos)) {
+			fprintf(stderr, "-X: no stdout and at most one %%d; name the files, e.g. out_%%d.raw.\n");
+			return 1;
+		}
+		if (c.deemph) c.deemph_a = rtlfm_deemph_a(c.rate_out, time_constant);
+		// one plan for all sources, as under -N; a source's capture frequency is its -f as given (no capture_rate / 4 offset,
+		// no +16 kHz under -M wbfm)
+		rtlfm_cfg planned = c;
+		uint32_t capture_rate = 0;
+		for (int i = 0; i < nstreams; i++) {
+			rtlfm_cfg ci = c;
+			uint32_t cr = 0;
+			rtlfm_optimal_settings(&ci, freqs[(size_t)i], rate_in, min_capture, fifth, edge, nullptr, &cr);
+			if (i == 0) {
+				planned = ci;
+				capture_rate = cr;
+			} else if (memcmp(&ci, &planned, sizeof(ci)) != 0 || cr != capture_rate) {
+				fprintf(stderr, "-X: the rate plan for %u Hz differs from the one for %u Hz; one handle needs one plan.\n", freqs[(size_t)i], freqs[0]);
+				return 1;
+			}
+		}
+		for (size_t i = 0; i < chan_freqs.size(); i++)
+			for (size_t k = 0; k < chan_freqs[i].size(); k++) {
+				const int64_t off = (int64_t)chan_freqs[i][k] - (int64_t)freqs[i];
+				if (2 * (off < 0 ? -off : off) > (int64_t)capture_rate) {
+					fprintf(stderr, "-X %s: line %d, entry %zu: %u Hz is further than capture_rate / 2 = %u Hz from the -f of source %zu, %u Hz.\n",
+					        chan_file, chan_lineno[i], k + 1, chan_freqs[i][k], capture_rate / 2, i, freqs[i]);
+					return 1;
+				}
+			}
+		return run_channels(planned, nstreams, dev_index, freqs, chan_freqs, capture_rate, gain, ppm, pattern, write_wav, a.verbosity,
+		                    conseq_squelch, a.print_levels, opt_string, agc, chan_taps > 0 ? chan_taps : 0);
+	}
 	int r_resume = 0;
 	if (nstreams > 1 || cmd_file || scan_file) {
 		// everything -N refuses is refused here, before a device is opened or a GPU handle created

@@ -176,6 +176,7 @@ struct rtlfm_gpu {
 		int squelch_gate = 0;  // 1: k_scan_gate at the end of every run (rtlfm_gpu_gate)
 		int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
 		int verify_twice = 0;  // debug: every run_device runs twice - into a shadow output, then into the caller's - and the two are compared on the device
+		int source_ring = 0;   // 1: while channels are on the ring's input side has one row per SOURCE (ring_rows) and the ring calls are open
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
 	int16_t *vt_out = nullptr;
@@ -347,6 +348,15 @@ static long placement_held_mb(rtlfm_gpu *h);
 static void ingest_destroy(rtlfm_gpu *h);
 static void ingest_reset(rtlfm_gpu *h);
 static bool ingest_busy(rtlfm_gpu *h);
+static bool ingest_queued(rtlfm_gpu *h);
+static int ingest_resize(rtlfm_gpu *h);
+
+// Rows of the ring's input side (h_stage, d_in, h_len, pushed, open_slot): one per stream - or, with option source_ring
+// and channels on, one per source.  The result side is per stream whatever this says.
+static inline int ring_rows(const rtlfm_gpu *h)
+{
+	return h->opt.source_ring && h->chan_per > 0 ? h->nstreams / h->chan_per : h->nstreams;
+}
 
 // everything the handle has launched: the front end's stream, then the audio tail's
 static hipError_t sync_all(rtlfm_gpu *h)
@@ -779,6 +789,7 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	if (!h || per_source < 0) return -EINVAL;
 	if (per_source > 0 && (!steps || h->nstreams % per_source)) return -EINVAL;
 	if (ingest_busy(h) || h->mute_streams > 0) return -EBUSY;
+	if (h->opt.source_ring && ingest_queued(h)) return -EBUSY;  // (queued buffers lie in rows of the old count)
 	if (per_source > 0 && (h->cfg.dc_block_raw || h->opt.input_stats || h->opt.input_health || h->opt.squelch_gate)) return -ENOTSUP;
 	HIP_TRY(hipSetDevice(h->device));
 	HIP_TRY(sync_all(h));
@@ -797,7 +808,9 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	h->chan_per = per_source;
 	h->chan_pos = 0;
 	h->bank_K = 0;  // (the bank's bins belong to the old per_source)
-	return ensure_history(h);
+	const int r = ensure_history(h);
+	if (r < 0) return r;
+	return ingest_resize(h);  // (option source_ring: the ring's input side for the new number of sources)
 }
 
 extern "C" int rtlfm_gpu_channels_seek(rtlfm_gpu *h, uint64_t pos)
@@ -1068,6 +1081,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"input_stats", &h->opt.input_stats}, {"input_stats_nt", &h->opt.input_stats_nt},
 		{"input_health", &h->opt.input_health},
 		{"squelch_gate", &h->opt.squelch_gate}, {"conseq_squelch", &h->opt.conseq_squelch},
+		{"source_ring", &h->opt.source_ring},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -1123,6 +1137,13 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 		}
 	}
 	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
+	if (!strcmp(name, "source_ring")) {
+		// the ring's rows change with it while channels are on: only on a ring that holds nothing and is in the middle of nothing
+		if (value != 0 && value != 1) return -EINVAL;
+		if (ingest_busy(h) || ingest_queued(h)) return -EBUSY;
+		h->opt.source_ring = (int)value;
+		return ingest_resize(h);
+	}
 	if (!strcmp(name, "arb_waves") && (value < 0 || value > kSpecArbMaxWaves)) return -EINVAL;
 	if (!strcmp(name, "lpr_threads") && (value < 64 || value > kSpecLprThreads || value % 64)) return -EINVAL;
 	if (!strcmp(name, "arb_serial")) {
@@ -2177,6 +2198,42 @@ struct ChanRun {
 	channel::Frame f;        // (segs, tiles_per_seg, ntiles: the front end's own)
 };
 
+// What the channel front ends allocate at first use, sized from the handle's own buffer length: a view of the handle on a
+// shorter buffer (run_ragged) must find them there - it is a copy and must not allocate.  The decimated IQ; on path 1 the
+// filter's mixed samples and the bank's sums.
+static int ensure_chan_iq(rtlfm_gpu *h)
+{
+	if (h->chan_iq) return 0;
+	h->chan_stride = (((size_t)h->cap_blocks * (h->cfg.block_len / 2)) / h->cfg.downsample + 1 + 16 + 3) & ~(size_t)3;  // rows start on 16-byte lines
+	HIP_TRY(hipMalloc(&h->chan_iq, (size_t)h->nstreams * h->chan_stride * sizeof(uint32_t)));
+	return 0;
+}
+static int ensure_chan_fir_x(rtlfm_gpu *h)
+{
+	if (h->chan_fir_x) return 0;
+	h->chan_fir_xstride = (size_t)chanfir::kHaloMax + (size_t)h->cap_blocks * (h->cfg.block_len / 2);
+	HIP_TRY(hipMalloc(&h->chan_fir_x, (size_t)h->nstreams * h->chan_fir_xstride * sizeof(uint32_t)));
+	return 0;
+}
+static int ensure_bank_v(rtlfm_gpu *h, size_t vneed /* 0: the most a run of this handle can need */)
+{
+	const size_t nsrc = (size_t)(h->nstreams / h->chan_per);
+	const size_t most = (nsrc * ((size_t)h->cap_blocks * (h->cfg.block_len / 2) / h->cfg.downsample + 1)) << h->bank_m;
+	if (h->bank_v && h->bank_v_dwords >= (vneed ? vneed : most)) return 0;
+	if (h->bank_v) { hipFree(h->bank_v); h->bank_v = nullptr; h->bank_v_dwords = 0; }
+	HIP_TRY(hipMalloc(&h->bank_v, most * sizeof(uint32_t)));
+	h->bank_v_dwords = most;
+	return 0;
+}
+// ... all of them, for the front end and the path the handle is set to, before the first view is made
+static int ensure_channel_buffers(rtlfm_gpu *h)
+{
+	int r = ensure_chan_iq(h);
+	if (r < 0 || h->path != 1) return r;
+	if (h->bank_K > 0) return ensure_bank_v(h, 0);
+	return h->fir_ntaps > 0 ? ensure_chan_fir_x(h) : 0;
+}
+
 static int chan_run_prepare(rtlfm_gpu *h, bool box, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
                             size_t out_stride, ChanRun &cr)
 {
@@ -2193,12 +2250,9 @@ static int chan_run_prepare(rtlfm_gpu *h, bool box, const uint8_t *d_iq, size_t 
 	// -M raw without the squelch behind the boxcar: what the launch leaves IS the output and goes straight into the caller's
 	// rows, as run_boxfused_emit's (a row the launch writes has one spare dword behind its last possible output: channel_kernel.h)
 	cr.raw_direct = box && c.mode == RTLFM_MODE_RAW && !c.squelch_level && !c.report_levels && out_stride / 2 >= (size_t)cr.Tin / cr.D + 2;
-	if (!cr.raw_direct && !h->chan_iq) {
-		h->chan_stride = (((size_t)h->cap_blocks * cr.N0) / cr.D + 1 + 16 + 3) & ~(size_t)3;  // rows start on 16-byte lines
-		HIP_TRY(hipMalloc(&h->chan_iq, (size_t)S * h->chan_stride * sizeof(uint32_t)));
-	}
-	cr.tp = plan_tail(h, nblocks);
 	int r;
+	if (!cr.raw_direct && (r = ensure_chan_iq(h)) < 0) return r;
+	cr.tp = plan_tail(h, nblocks);
 	if (!cr.raw_direct && cr.tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
 	cr.target_waves = cr.tp.any() ? h->fws.target_waves_tail : h->fws.target_waves;
 	cr.dcnt = h->d_cnt[h->step & 1];
@@ -2256,10 +2310,8 @@ static int launch_channel_fir(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		return 0;
 	}
 	constexpr int halo = chanfir::kHaloMax;
-	if (!h->chan_fir_x) {
-		h->chan_fir_xstride = (size_t)halo + (size_t)h->cap_blocks * cr.N0;
-		HIP_TRY(hipMalloc(&h->chan_fir_x, (size_t)S * h->chan_fir_xstride * sizeof(uint32_t)));
-	}
+	int r = ensure_chan_fir_x(h);
+	if (r < 0) return r;
 	// (the history's last `halo` samples: rows channel::kHist * 2 bytes apart, one buffer of halo * 2 bytes each)
 	channel::k_channel_mix<<<grid_for((size_t)S * (halo / 8)), 256, 0, q>>>(
 		cr.hist_in + (size_t)(channel::kHist - halo) * 2, (size_t)channel::kHist * 2, (uint32_t)halo * 2, 1, S, h->chan_per, h->d_chan_steps,
@@ -2298,12 +2350,8 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		return 0;
 	}
 	const size_t vneed = ((size_t)cr.nsrc * cr.maxout) << h->bank_m;
-	if (h->bank_v_dwords < vneed) {
-		if (h->bank_v) { hipFree(h->bank_v); h->bank_v = nullptr; h->bank_v_dwords = 0; }
-		const size_t most = ((size_t)cr.nsrc * ((size_t)h->cap_blocks * cr.N0 / cr.D + 1)) << h->bank_m;
-		HIP_TRY(hipMalloc(&h->bank_v, most * sizeof(uint32_t)));
-		h->bank_v_dwords = most;
-	}
+	int r = ensure_bank_v(h, vneed);
+	if (r < 0) return r;
 	chanbank::k_bank_sums<<<grid_for(vneed), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
 	                                                     h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.Tin, cr.D, cr.maxout,
 	                                                     cr.sin, h->bank_v);
@@ -2772,8 +2820,14 @@ extern "C" int rtlfm_gpu_mute_device(int device, uint8_t *d_iq, size_t stream_st
 // throughout).  Full buffers take the batched path; a run that holds a short buffer goes buffer
 // by buffer, each contiguous range of streams with the same length through a view of the handle
 // configured for that length (the chain's carried state makes this exact, and rare).
+//
+// Rows.  The input side - h_stage, d_in, h_len, pushed, open_slot - has ring_rows() rows: one per stream, or one per
+// SOURCE with option source_ring while channels are on (the `stream` of push / acquire / commit is then the source).  The
+// result side is per stream throughout.  set_channels and the option rebuild the input side when the count changes
+// (ingest_resize), on a ring that holds nothing; results of earlier runs stay where they are.
 struct Ingest {
-	uint8_t *h_stage[2] = {nullptr, nullptr};   // pinned, [stream][cap_blocks][block_len]
+	int rows = 0;                               // of the input side, as built (0: a rebuild failed; ingest_ensure tries again)
+	uint8_t *h_stage[2] = {nullptr, nullptr};   // pinned, [row][cap_blocks][block_len]
 	uint8_t *d_in[2] = {nullptr, nullptr};
 	std::vector<uint32_t> h_len[2];             // bytes in each slot
 	std::unique_ptr<std::atomic<int>[]> pushed[2];
@@ -2837,22 +2891,46 @@ static void ingest_free(Ingest *in)
 	delete in;
 }
 
-static int ingest_build(rtlfm_gpu *h, Ingest *in)
+// the input side, for the rows there are now
+static void ingest_free_input(Ingest *in)
 {
-	const size_t S = (size_t)h->nstreams;
-	const size_t bytes = S * h->cap_blocks * h->cfg.block_len;
-	HIP_TRY(hipSetDevice(h->device));
-	in->ostride = ((size_t)rtlfm_result_cap(&h->cfg) * h->cap_blocks + 16 + 63) & ~(size_t)63;
-	HIP_TRY(rtl_pool::stream_get(h->device, 0, &in->copy_stream));
+	for (int k = 0; k < 2; k++) {
+		if (in->h_stage[k]) hipHostFree(in->h_stage[k]);
+		if (in->d_in[k]) hipFree(in->d_in[k]);
+		in->h_stage[k] = nullptr; in->d_in[k] = nullptr;
+	}
+	in->rows = 0;
+}
+static int ingest_build_input(rtlfm_gpu *h, Ingest *in)
+{
+	const size_t R = (size_t)ring_rows(h);
+	const size_t bytes = R * h->cap_blocks * h->cfg.block_len;
 	for (int k = 0; k < 2; k++) {
 		HIP_TRY(hipHostMalloc(&in->h_stage[k], bytes, hipHostMallocDefault));
 		HIP_TRY(hipMalloc(&in->d_in[k], bytes));
+		in->h_len[k].assign(R * h->cap_blocks, 0);
+		in->pushed[k].reset(new std::atomic<int>[R]);
+		for (size_t s = 0; s < R; s++) in->pushed[k][s].store(0);
+	}
+	in->open_slot.reset(new std::atomic<int>[R]);
+	for (size_t s = 0; s < R; s++) in->open_slot[s].store(0);
+	in->rows = (int)R;
+	return 0;
+}
+
+static int ingest_build(rtlfm_gpu *h, Ingest *in)
+{
+	const size_t S = (size_t)h->nstreams;
+	HIP_TRY(hipSetDevice(h->device));
+	in->ostride = ((size_t)rtlfm_result_cap(&h->cfg) * h->cap_blocks + 16 + 63) & ~(size_t)63;
+	HIP_TRY(rtl_pool::stream_get(h->device, 0, &in->copy_stream));
+	int rb = ingest_build_input(h, in);
+	if (rb < 0) return rb;
+	const size_t bytes = (size_t)in->rows * h->cap_blocks * h->cfg.block_len;
+	for (int k = 0; k < 2; k++) {
 		HIP_TRY(hipMalloc(&in->d_result_len[k], S * sizeof(int32_t)));
 		HIP_TRY(hipEventCreateWithFlags(&in->ev_h2d[k], hipEventDisableTiming));
 		HIP_TRY(hipEventCreateWithFlags(&in->ev_run[k], hipEventDisableTiming));
-		in->h_len[k].assign(S * h->cap_blocks, 0);
-		in->pushed[k].reset(new std::atomic<int>[S]);
-		for (size_t s = 0; s < S; s++) in->pushed[k][s].store(0);
 	}
 	{
 		// the results away from the input they are demodulated from (rtlfm_gpu_malloc_apart_ex; plain memory when the
@@ -2913,18 +2991,39 @@ static int ingest_build(rtlfm_gpu *h, Ingest *in)
 			}
 		}
 	}
-	in->open_slot.reset(new std::atomic<int>[S]);
-	for (size_t s = 0; s < S; s++) in->open_slot[s].store(0);
 	return 0;
+}
+
+// The row count has changed (rtlfm_gpu_set_channels, option source_ring): the input side once more, for the rows there are
+// now.  The callers have found the ring idle and empty; what is in flight on the device is waited for.  The result side,
+// `last` and `prev` stay: results of earlier runs remain fetchable.  (The results were placed against the old d_in:
+// option ring_apart speaks of the ring as first built.)
+static int ingest_resize_locked(rtlfm_gpu *h, Ingest *in)
+{
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	HIP_TRY(hipStreamSynchronize(in->copy_stream));
+	std::unique_lock<std::shared_mutex> g(in->mu);
+	ingest_free_input(in);
+	in->h2d_pending[0] = in->h2d_pending[1] = false;
+	return ingest_build_input(h, in);
+}
+static int ingest_resize(rtlfm_gpu *h)
+{
+	Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE);
+	if (!in || in->rows == ring_rows(h)) return 0;
+	std::lock_guard<std::mutex> g(g_ingest_alloc_mu);
+	return ingest_resize_locked(h, in);
 }
 
 // the ring is built by whoever comes first (callbacks of many streams may arrive at once) and
 // published only when it is complete
 static int ingest_ensure(rtlfm_gpu *h)
 {
-	if (__atomic_load_n(&h->ing, __ATOMIC_ACQUIRE)) return 0;
+	if (Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE))
+		if (in->rows == ring_rows(h)) return 0;
 	std::lock_guard<std::mutex> g(g_ingest_alloc_mu);
-	if (h->ing) return 0;
+	if (h->ing) return h->ing->rows == ring_rows(h) ? 0 : ingest_resize_locked(h, h->ing);  // (a rebuild that failed in the setter)
 	Ingest *in = new Ingest();
 	int r = ingest_build(h, in);
 	if (r < 0) {
@@ -2947,8 +3046,8 @@ static void ingest_reset(rtlfm_gpu *h)
 	if (!in) return;
 	std::unique_lock<std::shared_mutex> g(in->mu);
 	for (int k = 0; k < 2; k++)
-		for (int s = 0; s < h->nstreams; s++) in->pushed[k][s].store(0);
-	for (int s = 0; s < h->nstreams; s++) in->open_slot[s].store(0);
+		for (int s = 0; s < in->rows; s++) in->pushed[k][s].store(0);
+	for (int s = 0; s < in->rows; s++) in->open_slot[s].store(0);
 	in->last = -1;
 	in->prev = -1;
 	in->pending_f = -1;
@@ -2962,15 +3061,26 @@ static bool ingest_busy(rtlfm_gpu *h)
 	if (!in) return false;
 	std::shared_lock<std::shared_mutex> g(in->mu);
 	if (in->pending_f >= 0) return true;
-	for (int s = 0; s < h->nstreams; s++)
+	for (int s = 0; s < in->rows; s++)
 		if (in->open_slot[s].load(std::memory_order_acquire)) return true;
+	return false;
+}
+
+// buffers wait in the filling half
+static bool ingest_queued(rtlfm_gpu *h)
+{
+	Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE);
+	if (!in) return false;
+	std::shared_lock<std::shared_mutex> g(in->mu);
+	for (int s = 0; s < in->rows; s++)
+		if (in->pushed[in->fill][s].load(std::memory_order_acquire) > 0) return true;
 	return false;
 }
 
 extern "C" int rtlfm_gpu_push(rtlfm_gpu *h, int stream, const uint8_t *iq, uint32_t len)
 {
-	if (!h || !iq || stream < 0 || stream >= h->nstreams) return -EINVAL;
-	if (h->chan_per > 0) return -ENOTSUP;  // (channels: the ring's rows are per stream)
+	if (!h || !iq || stream < 0 || stream >= ring_rows(h)) return -EINVAL;  // (option source_ring with channels: the SOURCE)
+	if (h->chan_per > 0 && !h->opt.source_ring) return -ENOTSUP;  // (channels: the ring's rows are per stream)
 	// actual_length of a bulk transfer: whole 512-byte USB packets, at most the buffer
 	if (len == 0 || len > h->cfg.block_len || len % 512) return -EINVAL;
 	if (len != h->cfg.block_len) {
@@ -3009,8 +3119,8 @@ extern "C" int rtlfm_gpu_push(rtlfm_gpu *h, int stream, const uint8_t *iq, uint3
 // writes the samples there, and commits the length.  No memcpy between the producer and the H2D copy.
 extern "C" int rtlfm_gpu_acquire(rtlfm_gpu *h, int stream, uint8_t **buf, uint32_t *cap)
 {
-	if (!h || !buf || stream < 0 || stream >= h->nstreams) return -EINVAL;
-	if (h->chan_per > 0) return -ENOTSUP;
+	if (!h || !buf || stream < 0 || stream >= ring_rows(h)) return -EINVAL;
+	if (h->chan_per > 0 && !h->opt.source_ring) return -ENOTSUP;
 	int r = ingest_ensure(h);
 	if (r < 0) return r;
 	Ingest *in = h->ing;
@@ -3027,10 +3137,10 @@ extern "C" int rtlfm_gpu_acquire(rtlfm_gpu *h, int stream, uint8_t **buf, uint32
 
 extern "C" int rtlfm_gpu_commit(rtlfm_gpu *h, int stream, uint32_t len)
 {
-	if (!h || stream < 0 || stream >= h->nstreams) return -EINVAL;
-	if (h->chan_per > 0) return -ENOTSUP;
+	if (!h || stream < 0 || stream >= ring_rows(h)) return -EINVAL;
+	if (h->chan_per > 0 && !h->opt.source_ring) return -ENOTSUP;
 	Ingest *in = h->ing;
-	if (!in) return -EINVAL;
+	if (!in || in->rows != ring_rows(h)) return -EINVAL;
 	std::shared_lock<std::shared_mutex> g(in->mu);
 	const int o = in->open_slot[stream].load(std::memory_order_acquire);
 	if (!o) return -EINVAL;
@@ -3113,6 +3223,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	if (h->opt.input_stats && (r = ensure_input_stats(h)) < 0) return r;
 	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
 	if (h->opt.squelch_gate && (r = ensure_gate(h)) < 0) return r;
+	if (h->chan_per > 0 && (r = ensure_channel_buffers(h)) < 0) return r;
 	if (!in->d_tmp) {
 		HIP_TRY(hipMalloc(&in->d_tmp, (size_t)S * in->ostride * sizeof(int16_t)));
 		HIP_TRY(hipMalloc(&in->d_tmp_len, (size_t)S * sizeof(int32_t)));
@@ -3130,7 +3241,26 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 		// every range of this buffer reads st[cur] and writes the next copy; the rotation advances once
 		const int cur = h->st_cur;
 		const unsigned step = h->step;
-		for (int s0 = 0; s0 < S;) {
+		if (h->chan_per > 0) {
+			// Channels (option source_ring): rtlfm_gpu_run_begin has found buffer j of one length on every source, so ONE view of
+			// the whole handle runs it.  The view is a copy: what a channel run advances on it - pos, the history's current
+			// copy - goes back to the handle here, once per buffer; the rotation advances below as for every ragged run.
+			const uint32_t len = in->h_len[f][j];
+			rtlfm_cfg c = h->cfg;
+			c.block_len = len;
+			c.max_blocks = 1;
+			if ((r = validate_cfg(&c)) < 0) return r;
+			rtlfm_gpu v = make_view(h, 0, S, len);
+			v.st_cur = cur;
+			v.step = step;
+			r = run_device_impl(&v, in->d_in[f] + (size_t)j * h->cfg.block_len, stride, 1, in->d_tmp, in->ostride, in->d_tmp_len);
+			h->fws = v.fws;
+			h->last_path = v.last_path;
+			if (r < 0) return r;
+			h->chan_pos = v.chan_pos;
+			h->src_hist_cur = v.src_hist_cur;
+		}
+		for (int s0 = 0; s0 < S && h->chan_per == 0;) {
 			const uint32_t len = in->h_len[f][(size_t)s0 * h->cap_blocks + j];
 			int s1 = s0 + 1;
 			while (s1 < S && in->h_len[f][(size_t)s1 * h->cap_blocks + j] == len) s1++;
@@ -3214,13 +3344,13 @@ static int apply_mute(rtlfm_gpu *h, Ingest *in, int f, int nb)
 extern "C" int rtlfm_gpu_run_begin(rtlfm_gpu *h, int *taken)
 {
 	if (!h) return -EINVAL;
-	if (h->chan_per > 0) return -ENOTSUP;  // (so rtlfm_gpu_run: it begins here)
+	if (h->chan_per > 0 && !h->opt.source_ring) return -ENOTSUP;  // (so rtlfm_gpu_run: it begins here)
 	int r = ingest_ensure(h);
 	if (r < 0) return r;
 	Ingest *in = h->ing;
 	if (in->pending_f >= 0) return -EBUSY;  // a begun run has not been ended
 	HIP_TRY(hipSetDevice(h->device));
-	const int S = h->nstreams;
+	const int S = in->rows;  // (option source_ring with channels: the sources)
 	const uint32_t L = h->cfg.block_len;
 	int f, nb;
 	bool ragged = false;
@@ -3243,6 +3373,12 @@ extern "C" int rtlfm_gpu_run_begin(rtlfm_gpu *h, int *taken)
 		for (int s = 0; s < S && !ragged; s++)
 			for (int j = 0; j < nb; j++)
 				if (in->h_len[f][(size_t)s * h->cap_blocks + j] != L) { ragged = true; break; }
+		// channels: pos is ONE counter per handle, so buffer j must have one length on every source.  Nothing is taken; the
+		// caller empties the ring (rtlfm_gpu_reset).
+		if (ragged && h->chan_per > 0)
+			for (int s = 1; s < S; s++)
+				for (int j = 0; j < nb; j++)
+					if (in->h_len[f][(size_t)s * h->cap_blocks + j] != in->h_len[f][j]) return -ERANGE;
 		for (int s = 0; s < S; s++) in->pushed[f ^ 1][s].store(0);
 		in->fill = f ^ 1;
 	}
@@ -3257,7 +3393,7 @@ extern "C" int rtlfm_gpu_run_end(rtlfm_gpu *h)
 	Ingest *in = h->ing;
 	if (in->pending_f < 0) return -EINVAL;  // nothing begun
 	HIP_TRY(hipSetDevice(h->device));
-	const int S = h->nstreams;
+	const int S = in->rows;  // input rows: the run's results are per stream (run_device_impl, run_ragged)
 	const uint32_t L = h->cfg.block_len;
 	const size_t stride = (size_t)h->cap_blocks * L;
 	const int f = in->pending_f, nb = in->pending_nb;

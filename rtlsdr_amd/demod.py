@@ -57,8 +57,22 @@ class GpuDemod:
             pass
 
     # -- the callback boundary ---------------------------------------------
+    @property
+    def sources(self) -> int:
+        """Rows of the ring's input side - what ``stream`` of ``rtlsdr_callback`` counts: the streams, or, with the option
+        ``source_ring`` while channels are on, the wideband sources (``nstreams // per_source``).  Results are per stream
+        (= per channel) either way."""
+        if self._per_source and self.get_option("source_ring"):
+            return self.nstreams // self._per_source
+        return self.nstreams
+
     def rtlsdr_callback(self, buf, stream: int = 0):
-        """What rtlsdr_read_async's callback does with (buf, len, ctx)."""
+        """What rtlsdr_read_async's callback does with (buf, len, ctx).  ``stream`` is the row of the ring: the stream,
+        or - channels on, option ``source_ring`` set - the SOURCE in ``range(self.sources)``; ``full_demod`` then turns
+        every source's queued buffers into all of its channels, and ``fetch*`` hand back one row per stream.  Every
+        source must have delivered the same number of buffers, and buffer k the same length on every source
+        (``-ERANGE`` otherwise: the channels share one sample counter).  Without ``source_ring`` the ring is refused
+        while channels are on (``-ENOTSUP``)."""
         a = np.ascontiguousarray(buf, dtype=np.uint8)
         check(self.lib.rtlfm_gpu_push(self._h, stream, a.ctypes.data, a.size), "rtlfm_gpu_push")
 
@@ -70,7 +84,8 @@ class GpuDemod:
     run = full_demod
 
     def run_begin(self) -> int:
-        """rtlfm_gpu_run_begin: take what the ring's filling half holds and flip the halves; returns buffers per stream taken."""
+        """rtlfm_gpu_run_begin: take what the ring's filling half holds and flip the halves; returns buffers per stream
+        (per source over the source ring) taken."""
         n = C.c_int()
         check(self.lib.rtlfm_gpu_run_begin(self._h, C.byref(n)), "rtlfm_gpu_run_begin")
         return n.value
