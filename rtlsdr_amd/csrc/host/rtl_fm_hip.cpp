@@ -71,7 +71,8 @@
 // source_ring, so that the ring has a row per SOURCE: handle stream s = channel s % K of source s / K writes the file
 // with %d = s; -H, -L ("stream s:") and -l work per stream as under -N without the device gate.  -x ntaps puts the channel
 // filter rtlfm_channel_lowpass(ntaps, 0.4 / D, D) in the boxcar's place (not with -F: the filter stands where the boxcar
-// stands; where its taps do not fit an int16 - fewer taps than D needs - the same filter at D / 2^k and shift 14 - k).  The demod thread pushes the same number of buffers for every source and run (run_channels below); the
+// stands; where its taps do not fit an int16 - fewer taps than D needs - the same filter at D / 2^k and shift 14 - k).
+// The demod thread pushes the same number of buffers for every source and run (demod_thread_channels below); the
 // streams run in lockstep on ONE sample counter, and no handle is shrunk (the library refuses state_move with channels):
 // a source's short last buffer is completed with bytes 127 - which mix to 0 at every phase - to the full length and
 // demodulated, a source that has ended is fed buffers of bytes 127 and its K files receive nothing more, until the last
@@ -79,6 +80,14 @@
 //
 // Not restated (out of scope): the command file's own hop (its 2 x 3 200 000 byte mute, the DC-filter reset, -B), and
 // -t negative (terminate on squelch).
+//
+// How the file is laid out.  main fills ONE Settings from the command line and hands it, const, to the mode that runs:
+// run_single (one source: Plumbing, next_slot, on_buffer, demod_thread - the callback pushes or commits straight into the
+// ring, which is what -Z and stdout need), run_multi (-N, -C, -S) or run_channels (-X).  What the modes share exists
+// once: open_source (a device and its tuner calls), Sink (an output file with its wave header, its counters and its -L
+// bookkeeping), print_level (the -L line), hold_back (demod_thread_fn's rule from the carried state), squelch_gate_on and
+// handle_setup (what a handle gets after it is created), read_list_file (-S and -X), plan_one / plan_for_all (the rate
+// plan), summary (the closing lines), and for the two modes with host queues take_batch, run_and_fetch, deliver and fail.
 #include <getopt.h>
 #include <pthread.h>
 #include <spawn.h>
@@ -94,6 +103,7 @@
 #include <cstring>
 #include <deque>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -122,6 +132,222 @@ double atofs(const char *s)
 		}
 	}
 	return atof(t.c_str()) * mul;
+}
+
+// everything main parses; the modes read it and change nothing
+struct Settings {
+	rtlfm_cfg cfg;              // what the handle is created with: the command line's, then plan_for_all's
+	uint32_t capture_rate = 0;  // ... and the capture rate of that plan
+	int rate_in = 24000, min_capture = 1000000, fifth = 0, edge = 0, time_constant = 75;  // what the plan is asked with
+	int gain = -100, ppm = 0, dev_index = 0, verbosity = 0;
+	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
+	int print_levels = 0;     // -L (src/rtl_fm.c:1757-1759)
+	bool write_wav = false, wb_mode = false;
+	bool zero_copy = false;  // -Z: the device layer reads straight into the pinned staging ring
+	const char *filename = "-", *cmd_file = nullptr, *scan_file = nullptr, *keep_file = nullptr, *resume_file = nullptr;
+	const char *chan_file = nullptr, *opt_string = nullptr;
+	int agc = -1;        // -O agc=<n>; -1: not given
+	int chan_taps = -1;  // -x; -1: not given
+};
+
+unsigned out_rate(const rtlfm_cfg &c) { return (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out); }
+
+// optimal_settings() (src/rtl_fm.c:1407-1445) for one frequency, asked with what the command line gave
+void plan_one(const Settings &st, uint32_t freq, rtlfm_cfg *cfg, uint32_t *capture_freq, uint32_t *capture_rate)
+{
+	rtlfm_optimal_settings(cfg, freq, st.rate_in, st.min_capture, st.fifth, st.edge, capture_freq, capture_rate);
+}
+
+// One plan for all sources (deemph_a, src/rtl_fm.c:1929-1934, and optimal_settings(), which must not depend on the
+// frequency for what this CLI accepts) into st.cfg / st.capture_rate, each source's capture frequency into capture_freqs
+// where the caller wants them: 0, or the index of the first source whose plan differs from source 0's (st is then as it was)
+int plan_for_all(Settings &st, const std::vector<uint32_t> &freqs, std::vector<uint32_t> *capture_freqs)
+{
+	rtlfm_cfg c = st.cfg, planned = c;
+	if (c.deemph) c.deemph_a = rtlfm_deemph_a(c.rate_out, st.time_constant);
+	if (capture_freqs) capture_freqs->assign(freqs.size(), 0);
+	uint32_t capture_rate = 0;
+	for (size_t i = 0; i < freqs.size(); i++) {
+		rtlfm_cfg ci = c;
+		uint32_t cr = 0;
+		plan_one(st, freqs[i], &ci, capture_freqs ? &(*capture_freqs)[i] : nullptr, &cr);
+		if (i == 0) {
+			planned = ci;
+			capture_rate = cr;
+		} else if (memcmp(&ci, &planned, sizeof(ci)) != 0 || cr != capture_rate) {
+			return (int)i;
+		}
+	}
+	st.cfg = planned;
+	st.capture_rate = capture_rate;
+	return 0;
+}
+
+// A file of frequency lists (-S, -X): one list per line in rtlfm_scan_parse_list's grammar, blank lines and lines that
+// start with '#' skipped.  0, -ENOENT (cannot open it) or -EINVAL with *bad_line = the line that is no list
+int read_list_file(const char *path, std::vector<std::vector<uint32_t>> &lists, std::vector<int> *linenos, int *bad_line)
+{
+	FILE *f = fopen(path, "r");
+	if (!f) return -ENOENT;
+	char line[65536];
+	int lineno = 0, r = 0;
+	while (r == 0 && fgets(line, sizeof(line), f)) {
+		lineno++;
+		const char *t = line;
+		while (*t == ' ' || *t == '\t') t++;
+		if (*t == '#' || *t == '\n' || *t == '\r' || !*t) continue;
+		int nf = 0;
+		int pr = rtlfm_scan_parse_list(t, nullptr, 0, &nf);
+		std::vector<uint32_t> fl((size_t)(nf > 0 ? nf : 0));
+		if (pr == -ENOBUFS) pr = rtlfm_scan_parse_list(t, fl.data(), nf, &nf);
+		if (pr < 0) {
+			*bad_line = lineno;
+			r = -EINVAL;
+			break;
+		}
+		lists.push_back(std::move(fl));
+		if (linenos) linenos->push_back(lineno);
+	}
+	fclose(f);
+	return r;
+}
+
+// Device dev_index + i, open and set up as the reference's main does it (src/rtl_fm.c:1945-1985): gain, the -O string, ppm,
+// offset tuning, frequency, rate.  nullptr behind the message when it cannot be opened.  The caller says where it is tuned.
+rtlsdr_dev_t *open_source(const Settings &st, int i, int gain, uint32_t capture_freq)
+{
+	rtlsdr_dev_t *dev = nullptr;
+	if (rtlsdr_open(&dev, (uint32_t)(st.dev_index + i)) < 0) {
+		fprintf(stderr, "Failed to open rtlsdr device #%d.\n", st.dev_index + i);
+		return nullptr;
+	}
+	if (gain == -100) rtlsdr_set_tuner_gain_mode(dev, 0);
+	else { rtlsdr_set_tuner_gain_mode(dev, 1); rtlsdr_set_tuner_gain(dev, gain); }
+	if (st.opt_string) rtlsdr_set_opt_string(dev, st.opt_string, st.verbosity);
+	if (st.agc >= 0) rtlsdr_set_tuner_gain_mode(dev, st.agc);  // the string's agc=<tuner_gain_mode>, src/librtlsdr.c:3166-3171
+	rtlsdr_set_freq_correction_ppb(dev, st.ppm * 1000);
+	rtlsdr_set_offset_tuning(dev, st.cfg.offset_tuning);
+	rtlsdr_set_center_freq(dev, capture_freq);
+	if (rtlsdr_set_sample_rate(dev, st.capture_rate) < 0 && i == 0)
+		fprintf(stderr, "WARNING: capture rate %u Hz is outside what an RTL2832 can do.\n", st.capture_rate);
+	return dev;
+}
+
+// One output: the file, its wave header, what went into it and what the squelch held back, and its -L bookkeeping
+// (src/rtl_fm.c:109-113, 1217-1237).  index = the %d of the file's name and the i of "stream i: "; -1 = the one output
+// of a single source, whose name is taken as it is ('-' = stdout) and whose lines carry no prefix.
+struct Sink {
+	FILE *file = nullptr;
+	rtlamd_wave wave{};
+	int index = -1;
+	uint32_t user_freq = 0;  // dongle.userFreq, src/rtl_fm.c:1440
+	uint64_t samples_out = 0, blocks_squelched = 0;
+	int print_level_no = 1, level_max = 0, level_max_max = 0;
+	double level_sum = 0.0;
+
+	bool open(const Settings &st, int idx, uint32_t freq)
+	{
+		index = idx;
+		user_freq = freq;
+		std::string name(st.filename);
+		const size_t at = name.find("%d");
+		if (idx >= 0 && at != std::string::npos) name = name.substr(0, at) + std::to_string(idx) + name.substr(at + 2);
+		file = idx < 0 && name == "-" ? stdout : fopen(name.c_str(), "wb");
+		if (!file) {
+			fprintf(stderr, "Failed to open %s\n", name.c_str());
+			return false;
+		}
+		if (st.write_wav)  // src/rtl_fm.c:1990-1995; nothing on stdout
+			rtlamd_wave_write_header(&wave, out_rate(st.cfg), freq, 16, st.cfg.mode == RTLFM_MODE_RAW ? 2 : 1, file);
+		return true;
+	}
+	void write(const int16_t *pcm, size_t n)
+	{
+		fwrite(pcm, 2, n, file);           // src/rtl_fm.c:1400
+		wave.data_size += 2 * (uint32_t)n;  // waveDataSize, :1401
+		samples_out += n;
+	}
+	void close()
+	{
+		if (!file || file == stdout) return;
+		rtlamd_wave_finalize(&wave, file);  // src/rtl_fm.c:2041-2045; nothing where no header was written
+		fclose(file);
+		file = nullptr;
+	}
+};
+
+// -L: full_demod()'s level printing, src/rtl_fm.c:1217-1237, on the rms() the GPU layer kept for handle stream k
+void print_level(Sink &s, rtlfm_gpu *gpu, int k, const Settings &st)
+{
+	int32_t sr = 0;
+	int nl = 0;
+	if (rtlfm_gpu_levels(gpu, k, &sr, 1, &nl) != 0 || nl != 1) return;
+	--s.print_level_no;
+	if (sr < 0) return;
+	s.level_sum += sr;
+	if (s.level_max < sr) s.level_max = sr;
+	if (s.level_max_max < sr) s.level_max_max = sr;
+	if (s.print_level_no) return;
+	s.print_level_no = st.print_levels;
+	const double avg_rms = s.level_sum / st.print_levels;
+	const std::string prefix = s.index < 0 ? "" : "stream " + std::to_string(s.index) + ": ";
+	fprintf(stderr, "%s%.3f kHz, %.1f avg rms, %d max rms, %d max max rms, %d squelch rms, %d rms, %.1f dB rms level, %.2f dB avg rms level\n",
+	        prefix.c_str(), s.user_freq / 1000.0, avg_rms, s.level_max, s.level_max_max, st.cfg.squelch_level, (int)sr,
+	        20.0 * log10(1E-10 + sr), 20.0 * log10(1E-10 + avg_rms));
+	s.level_max = 0;
+	s.level_sum = 0;
+}
+
+// -l without a device gate: demod_thread_fn()'s rule (src/rtl_fm.c:1366-1370) from the carried state, after a run of one
+// buffer per stream.  While a stream's squelch has been closed for more than conseq_squelch buffers its buffer does not go
+// to the output thread - on_held(k) -, and the counter is held one above the limit ("hair trigger").  squelch_hits starts
+// at 11 (:1615): silence until it first opens.  Every stream's state in one copy, and one copy back only in a run that
+// clamped a counter.
+template <class F>
+void hold_back(rtlfm_gpu *gpu, int nstreams, int conseq_squelch, std::vector<rtlfm_stream_state> &states, F on_held)
+{
+	states.resize((size_t)nstreams);
+	int got = 0;
+	bool clamped = false;
+	if (rtlfm_gpu_state_get_all(gpu, states.data(), nstreams, &got) != 0) return;
+	for (int k = 0; k < nstreams; k++) {
+		rtlfm_stream_state &s = states[(size_t)k];
+		if (s.squelch_hits <= conseq_squelch) continue;
+		clamped |= s.squelch_hits != conseq_squelch + 1;
+		s.squelch_hits = conseq_squelch + 1;
+		on_held(k);
+	}
+	if (clamped) rtlfm_gpu_state_set_all(gpu, states.data(), nstreams);
+}
+
+// -l on the device: the same rule as the handle's squelch gate, where the configuration has one.  -ENOTSUP (behind a
+// resampler) is no error unless the caller needs the gate (-S does): *on = false then, and hold_back applies the rule.
+int squelch_gate_on(rtlfm_gpu *gpu, int conseq_squelch, bool needed, bool *on)
+{
+	int r = rtlfm_gpu_set_option(gpu, "conseq_squelch", conseq_squelch);
+	if (r == 0) r = rtlfm_gpu_set_option(gpu, "squelch_gate", 1);
+	*on = r == 0;
+	return r == -ENOTSUP && !needed ? 0 : r;
+}
+
+// the closing lines: the totals of the n outputs of sources that gave in_all buffers, and with `each` a line per output -
+// with its source's buffers where an output is a source's (in_each), without them where sources fan out into channels (-X)
+void summary(const Sink *out, size_t n, uint64_t in_all, const uint64_t *in_each, bool failed, bool each)
+{
+	auto buffers = [](uint64_t b) { return std::to_string(b) + " buffers in, "; };
+	auto line = [](const std::string &head, uint64_t samples, uint64_t held, const char *tail) {
+		fprintf(stderr, "%s%llu samples out, %llu buffers held back by the squelch%s\n", head.c_str(), (unsigned long long)samples,
+		        (unsigned long long)held, tail);
+	};
+	uint64_t samples = 0, held = 0;
+	for (size_t s = 0; s < n; s++) {
+		samples += out[s].samples_out;
+		held += out[s].blocks_squelched;
+	}
+	line(buffers(in_all), samples, held, failed ? " (FAILED)" : "");
+	for (size_t s = 0; each && s < n; s++)
+		line("stream " + std::to_string(out[s].index) + ": " + (in_each ? buffers(in_each[s]) : ""), out[s].samples_out,
+		     out[s].blocks_squelched, "");
 }
 
 struct Plumbing {
@@ -237,26 +463,41 @@ int opt_string_agc(const char *opts)
 	return agc;
 }
 
+// What a handle gets after rtlfm_gpu_create, each with its message: -O agc=2 (the option input_health and the engine for
+// `devs`), -R, and -l's device gate (*use_gate; `gate_needed` as squelch_gate_on's).  false = exit status 2
+bool handle_setup(rtlfm_gpu *gpu, const Settings &st, const std::vector<rtlsdr_dev_t *> &devs, Health *hl, bool gate_needed, bool *use_gate)
+{
+	int r = 0;
+	if (st.agc == 2) {
+		r = rtlfm_gpu_set_option(gpu, "input_health", 1);
+		if (r == 0) r = health_create(hl, devs, st.cfg.max_blocks, st.verbosity);
+		if (r < 0) { fprintf(stderr, "rtlfm_agc_create: %s\n", rtlfm_gpu_strerror(r)); return false; }
+	}
+	if (st.resume_file && (r = rtlfm_gpu_load(gpu, st.resume_file)) < 0) {
+		fprintf(stderr, "-R %s: %s\n", st.resume_file, rtlfm_gpu_strerror(r));
+		return false;
+	}
+	if (st.cfg.squelch_level && (r = squelch_gate_on(gpu, st.conseq_squelch, gate_needed, use_gate)) < 0) {
+		fprintf(stderr, "squelch_gate: %s\n", rtlfm_gpu_strerror(r));
+		return false;
+	}
+	return true;
+}
+
+// ---- one source: the callback pushes or commits straight into the ring -------------------------------------
+
 struct App {
-	rtlfm_cfg cfg;
+	const Settings &st;
 	rtlfm_gpu *gpu = nullptr;
 	rtlsdr_dev_t *dev = nullptr;
 	Plumbing p;
-	FILE *file = nullptr;
-	rtlamd_wave wave{};
-	int verbosity = 0;
-	int conseq_squelch = 10;
-	// -L (src/rtl_fm.c:109-113, 1217-1237)
-	int print_levels = 0, print_level_no = 1, level_max = 0, level_max_max = 0;
-	double level_sum = 0.0;
-	uint32_t user_freq = 0;
-	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
-	bool use_gate = false;             // -l through the device's squelch gate (rtlfm_gpu_gate)
-	const char *keep_file = nullptr;   // -K: the snapshot written at exit
-	bool zero_copy = false;            // -Z: the device layer reads straight into the pinned staging ring
-	unsigned char *open_slot = nullptr;  // the slot the device layer is filling (rtlfm_gpu_acquire)
-	Health hl;                         // -O agc=2
-	std::deque<uint32_t> in_lens;      // ... the lengths of the buffers in the ring, oldest first (under p.m)
+	Sink out;
+	uint64_t blocks_in = 0;
+	bool use_gate = false;               // -l through the device's squelch gate (rtlfm_gpu_gate)
+	unsigned char *open_slot = nullptr;  // -Z: the slot the device layer is filling (rtlfm_gpu_acquire)
+	Health hl;                           // -O agc=2
+	std::deque<uint32_t> in_lens;        // ... the lengths of the buffers in the ring, oldest first (under p.m)
+	explicit App(const Settings &s) : st(s) {}
 };
 
 // -Z: where the device layer reads its next buffer to (rtlamd_file_set_buffer_source): a slot of the GPU
@@ -270,7 +511,7 @@ int next_slot(void *ctx, unsigned char **buf, uint32_t *cap)
 	// the demod thread would hardly ever find the ring closed and committed buffers would sit there.
 	std::unique_lock<std::mutex> g(a->p.m);
 	for (;;) {
-		a->p.cv_room.wait(g, [&] { return (!a->p.want_run && a->p.queued < a->cfg.max_blocks) || a->p.failed; });
+		a->p.cv_room.wait(g, [&] { return (!a->p.want_run && a->p.queued < a->st.cfg.max_blocks) || a->p.failed; });
 		if (a->p.failed) return -1;
 		uint8_t *p = nullptr;
 		int r = rtlfm_gpu_acquire(a->gpu, 0, &p, cap);
@@ -310,7 +551,7 @@ void on_buffer(unsigned char *buf, uint32_t len, void *ctx)
 	// is then exactly what the ring holds when rtlfm_gpu_run() takes it
 	std::unique_lock<std::mutex> g(a->p.m);
 	for (;;) {
-		a->p.cv_room.wait(g, [&] { return (!a->p.want_run && a->p.queued < a->cfg.max_blocks) || a->p.failed; });
+		a->p.cv_room.wait(g, [&] { return (!a->p.want_run && a->p.queued < a->st.cfg.max_blocks) || a->p.failed; });
 		if (a->p.failed) return;
 		int r = rtlfm_gpu_push(a->gpu, 0, buf, len);
 		if (r == 0) break;
@@ -331,8 +572,8 @@ void on_buffer(unsigned char *buf, uint32_t len, void *ctx)
 
 void dongle_thread(App *a)
 {
-	if (a->zero_copy) rtlamd_file_set_buffer_source(a->dev, next_slot, a);
-	rtlsdr_read_async(a->dev, on_buffer, a, 0, a->cfg.block_len);
+	if (a->st.zero_copy) rtlamd_file_set_buffer_source(a->dev, next_slot, a);
+	rtlsdr_read_async(a->dev, on_buffer, a, 0, a->st.cfg.block_len);
 	std::lock_guard<std::mutex> g(a->p.m);
 	a->p.eof = true;
 	a->p.cv_work.notify_all();
@@ -340,7 +581,9 @@ void dongle_thread(App *a)
 
 void demod_thread(App *a)
 {
-	const int cap = rtlfm_result_cap(&a->cfg) * a->cfg.max_blocks + 16;
+	const rtlfm_cfg &c = a->st.cfg;
+	const int cap = rtlfm_result_cap(&c) * c.max_blocks + 16;
+	std::vector<rtlfm_stream_state> states;
 	for (;;) {
 		int taken = 0;
 		{
@@ -374,7 +617,7 @@ void demod_thread(App *a)
 		std::vector<int16_t> pcm((size_t)cap);
 		int n = 0;
 		if (r == 0) r = rtlfm_gpu_fetch(a->gpu, 0, pcm.data(), cap, &n);
-		if (r == 0 && a->hl.agc) r = health_step(&a->hl, a->gpu, a->cfg.max_blocks, {0}, run_lens);
+		if (r == 0 && a->hl.agc) r = health_step(&a->hl, a->gpu, c.max_blocks, {0}, run_lens);
 		if (r < 0) {
 			fprintf(stderr, "rtlfm_gpu_run/fetch: %s\n", rtlfm_gpu_strerror(r));
 			std::lock_guard<std::mutex> g(a->p.m);
@@ -384,51 +627,19 @@ void demod_thread(App *a)
 			break;
 		}
 		pcm.resize((size_t)n);
-		if (a->print_levels) {
-			// full_demod()'s level printing, src/rtl_fm.c:1217-1237, on the rms() the GPU layer kept
-			int32_t sr = 0;
-			int nl = 0;
-			if (rtlfm_gpu_levels(a->gpu, 0, &sr, 1, &nl) == 0 && nl == 1) {
-				--a->print_level_no;
-				if (sr >= 0) {
-					a->level_sum += sr;
-					if (a->level_max < sr) a->level_max = sr;
-					if (a->level_max_max < sr) a->level_max_max = sr;
-					if (!a->print_level_no) {
-						a->print_level_no = a->print_levels;
-						const double avg_rms = a->level_sum / a->print_levels;
-						fprintf(stderr, "%.3f kHz, %.1f avg rms, %d max rms, %d max max rms, %d squelch rms, %d rms, %.1f dB rms level, %.2f dB avg rms level\n",
-						        a->user_freq / 1000.0, avg_rms, a->level_max, a->level_max_max, a->cfg.squelch_level, (int)sr,
-						        20.0 * log10(1E-10 + sr), 20.0 * log10(1E-10 + avg_rms));
-						a->level_max = 0;
-						a->level_sum = 0;
-					}
-				}
-			}
-		}
+		if (a->st.print_levels) print_level(a->out, a->gpu, 0, a->st);
+		bool held = false;
 		if (a->use_gate) {
-			// the same rule, applied on the device: a held buffer comes back with no samples and its record says so
+			// the rule applied on the device: a held buffer comes back with no samples and its record says so
 			rtlfm_gate_rec g1;
 			int ng = 0;
-			if (rtlfm_gpu_gate(a->gpu, 0, &g1, 1, &ng) == 0 && ng == 1 && !g1.emit) {
-				a->blocks_squelched++;
-				continue;
-			}
-		} else if (a->cfg.squelch_level) {
-			// demod_thread_fn(), src/rtl_fm.c:1366-1370: while the squelch has been closed for more than
-			// conseq_squelch buffers nothing goes to the output thread, and the counter is held one above
-			// the limit ("hair trigger").  squelch_hits starts at 11 (:1615): silence until it first opens.
-			// One read of the state per run, and a write only when the counter was clamped.
-			rtlfm_stream_state st;
-			int ns = 0;
-			if (rtlfm_gpu_state_get_all(a->gpu, &st, 1, &ns) == 0 && st.squelch_hits > a->conseq_squelch) {
-				if (st.squelch_hits != a->conseq_squelch + 1) {
-					st.squelch_hits = a->conseq_squelch + 1;
-					rtlfm_gpu_state_set_all(a->gpu, &st, 1);
-				}
-				a->blocks_squelched++;
-				continue;
-			}
+			held = rtlfm_gpu_gate(a->gpu, 0, &g1, 1, &ng) == 0 && ng == 1 && !g1.emit;
+		} else if (c.squelch_level) {
+			hold_back(a->gpu, 1, a->st.conseq_squelch, states, [&](int) { held = true; });
+		}
+		if (held) {
+			a->out.blocks_squelched++;
+			continue;
 		}
 		std::lock_guard<std::mutex> g(a->p.m);
 		a->p.out_q.push_back(std::move(pcm));
@@ -450,11 +661,46 @@ void output_thread(App *a)
 			pcm = std::move(a->p.out_q.front());
 			a->p.out_q.pop_front();
 		}
-		fwrite(pcm.data(), 2, pcm.size(), a->file);  // src/rtl_fm.c:1400
-		a->wave.data_size += 2 * (uint32_t)pcm.size();  // waveDataSize, :1401
-		a->samples_out += pcm.size();
+		a->out.write(pcm.data(), pcm.size());
 	}
-	fflush(a->file);
+	fflush(a->out.file);
+}
+
+// everything after option parsing for one source; freq = where the user tunes it (+16 kHz under -M wbfm)
+int run_single(const Settings &st, uint32_t freq, uint32_t capture_freq)
+{
+	App a(st);
+	const rtlfm_cfg &c = st.cfg;
+	if (rtlsdr_get_device_count() == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE).\n"); return 1; }
+	if (!(a.dev = open_source(st, 0, st.gain, capture_freq))) return 1;
+	fprintf(stderr, "Tuned to %u Hz.\nOversampling input by: %ix.\nSampling at %u S/s.\nOutput at %u Hz.\n", capture_freq,
+	        c.downsample, st.capture_rate, out_rate(c));
+	if (st.verbosity)
+		fprintf(stderr, "downsample_passes = %d, downsample = %d, deemph_a = %d, buffer = %u B\n", c.downsample_passes,
+		        c.downsample, c.deemph_a, c.block_len);
+	int r = rtlfm_gpu_create(&c, 1, 0, &a.gpu);
+	if (r < 0) { fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r)); return 2; }
+	if (!handle_setup(a.gpu, st, {a.dev}, &a.hl, false, &a.use_gate)) return 2;
+	if (!a.out.open(st, -1, freq)) return 1;
+	rtlsdr_reset_buffer(a.dev);
+
+	std::thread t_out(output_thread, &a), t_demod(demod_thread, &a), t_dongle(dongle_thread, &a);
+	t_dongle.join();
+	t_demod.join();
+	t_out.join();
+	a.out.close();
+	summary(&a.out, 1, a.blocks_in, nullptr, a.p.failed, false);
+	if (a.hl.agc) {
+		health_report(&a.hl);
+		rtlfm_agc_destroy(a.hl.agc);
+	}
+	if (st.keep_file && !a.p.failed && (r = rtlfm_gpu_save(a.gpu, st.keep_file)) < 0) {  // behind the last run
+		fprintf(stderr, "-K %s: %s\n", st.keep_file, rtlfm_gpu_strerror(r));
+		a.p.failed = true;
+	}
+	rtlfm_gpu_destroy(a.gpu);
+	rtlsdr_close(a.dev);
+	return a.p.failed ? 3 : 0;
 }
 
 // ---- -N n: devices d .. d+n-1 as streams 0 .. n-1 of one handle ----------------------------------------
@@ -471,11 +717,7 @@ void output_thread(App *a)
 struct Multi;
 
 struct Source {
-	int index = 0;                            // stream index: output file, %d, "stream i:"
 	rtlsdr_dev_t *dev = nullptr;
-	uint32_t user_freq = 0, capture_freq = 0;
-	FILE *file = nullptr;
-	rtlamd_wave wave{};
 	Multi *m = nullptr;
 	std::deque<std::vector<uint8_t>> q;       // buffers copied by the callback, not yet taken by a run
 	std::vector<std::vector<uint8_t>> spare;  // taken buffers come back here, so a callback hardly ever allocates
@@ -483,25 +725,22 @@ struct Source {
 	int copying = 0;                          // callbacks copying into a reserved place of the queue
 	bool eof = false;
 	std::condition_variable cv_room;
-	// -L (src/rtl_fm.c:109-113, 1217-1237), per stream
-	int print_level_no = 1, level_max = 0, level_max_max = 0;
-	double level_sum = 0.0;
-	uint64_t blocks_in = 0, samples_out = 0, blocks_squelched = 0;
+	uint64_t blocks_in = 0;
 };
 
 struct RunOut {
 	std::vector<int16_t> pcm;  // handle stream k at k * stride
 	std::vector<int32_t> lens;
-	std::vector<int> who;      // handle stream k -> source
+	std::vector<int> who;      // handle stream k -> output
 	size_t stride = 0;
 };
 
 struct Multi {
-	rtlfm_cfg cfg;
+	const Settings &st;
 	rtlfm_gpu *gpu = nullptr;
 	std::vector<Source> src;
+	std::vector<Sink> out;  // -N: out[i] is source i's; -X: out[s] is handle stream s's, channel s % K of source s / K
 	int depth = 0;
-	int verbosity = 0, conseq_squelch = 10, print_levels = 0;
 	std::mutex m;
 	std::condition_variable cv_work, cv_out;
 	bool failed = false, out_done = false;
@@ -516,32 +755,28 @@ struct Multi {
 	// -S: the hop engine, list i = source i
 	rtlfm_scan *scan = nullptr;
 	std::vector<rtlfm_gate_rec> gate_recs;
-	bool wb_mode = false;
-	int rate_in = 0, min_capture = 0, fifth = 0, edge = 0;  // what optimal_settings() is asked with for a hop
 	// -K: record i = source i.  A source that leaves the batch leaves its record here (shrink); the others' are read at exit
-	const char *keep_file = nullptr;
 	std::vector<rtlfm_stream_state> kept;
 	std::vector<int> live;                   // handle stream k -> source, as the demod thread left it
 	std::vector<rtlfm_stream_state> states;  // one rtlfm_gpu_state_get_all: -l without a device gate, -K
-	// -X: K channels per source; chan[s] = what handle stream s owns (its file, wave header, -L counters), index = s
-	int chan_per = 0;
-	std::vector<Source> chan;
+	int chan_per = 0;                        // -X: K channels per source
+	explicit Multi(const Settings &s, size_t sources, size_t outputs) : st(s), src(sources), out(outputs), depth(2 * s.cfg.max_blocks) {}
 };
 
-// the options a handle of this tool runs with besides its configuration
+// the options a handle of this tool runs with besides its configuration (shrink: what the first handle was given)
 int handle_options(Multi *m, rtlfm_gpu *h)
 {
 	int r = 0;
+	bool on = false;
 	if (m->mon) r = rtlfm_gpu_set_option(h, "input_stats", 1);
 	if (r == 0 && m->hl.agc) r = rtlfm_gpu_set_option(h, "input_health", 1);
-	if (r == 0 && m->use_gate) r = rtlfm_gpu_set_option(h, "conseq_squelch", m->conseq_squelch);
-	if (r == 0 && m->use_gate) r = rtlfm_gpu_set_option(h, "squelch_gate", 1);
+	if (r == 0 && m->use_gate) r = squelch_gate_on(h, m->st.conseq_squelch, true, &on);
 	return r;
 }
 
-// with m->m held
-void fail_multi(Multi *m, const char *what, int r)
+void fail(Multi *m, const char *what, int r)
 {
+	std::lock_guard<std::mutex> g(m->m);
 	fprintf(stderr, "%s: %s\n", what, rtlfm_gpu_strerror(r));
 	m->failed = true;
 	for (Source &s : m->src) {
@@ -578,10 +813,74 @@ void on_buffer_multi(unsigned char *buf, uint32_t len, void *ctx)
 
 void dongle_thread_multi(Source *s)
 {
-	rtlsdr_read_async(s->dev, on_buffer_multi, s, 0, s->m->cfg.block_len);
+	rtlsdr_read_async(s->dev, on_buffer_multi, s, 0, s->m->st.cfg.block_len);
 	std::lock_guard<std::mutex> g(s->m->m);
 	s->eof = true;  // after the last callback: the queue holds everything the source gave
 	s->m->cv_work.notify_one();
+}
+
+// Taking a batch: wait until every source in `live` has a buffer or has ended; the ones that have ended (an empty queue
+// then) leave `live`; from each of the others b = min(what every queue holds, max_blocks) buffers go to its `taken`, and
+// its callback is woken.  Returns b, or 0 when the run has failed or no source is left.
+int take_batch(Multi *m, std::vector<int> &live)
+{
+	std::unique_lock<std::mutex> g(m->m);
+	m->cv_work.wait(g, [&] {
+		if (m->failed) return true;
+		for (int i : live)
+			if (m->src[(size_t)i].q.empty() && !m->src[(size_t)i].eof) return false;
+		return true;
+	});
+	if (m->failed) return 0;
+	live.erase(std::remove_if(live.begin(), live.end(), [&](int i) { return m->src[(size_t)i].q.empty(); }), live.end());
+	if (live.empty()) return 0;
+	int b = m->st.cfg.max_blocks;
+	for (int i : live) b = std::min(b, (int)m->src[(size_t)i].q.size());
+	for (int i : live) {
+		Source &s = m->src[(size_t)i];
+		for (int j = 0; j < b; j++) {
+			s.taken.push_back(std::move(s.q.front()));
+			s.q.pop_front();
+		}
+		s.cv_room.notify_all();
+	}
+	return b;
+}
+
+// The run behind the pushes (r = what they returned) of b buffers per ring row, and the PCM of the handle's who.size()
+// streams, stream k for output who[k].  false behind fail().
+bool run_and_fetch(Multi *m, int r, int b, const std::vector<int> &who, RunOut &o)
+{
+	int ran = 0;
+	if (r == 0) r = rtlfm_gpu_run_begin(m->gpu, &ran);
+	if (r == 0 && ran != b) r = -EPROTO;
+	if (r == 0) r = rtlfm_gpu_run_end(m->gpu);
+	o.stride = ((size_t)rtlfm_result_cap(&m->st.cfg) * m->st.cfg.max_blocks + 16 + 63) / 64 * 64;
+	o.pcm.resize(who.size() * o.stride);
+	o.lens.resize(who.size());
+	o.who = who;
+	if (r == 0) r = rtlfm_gpu_fetch_all(m->gpu, o.pcm.data(), o.stride, o.lens.data());
+	if (r < 0) fail(m, "rtlfm_gpu_push/run/fetch_all", r);
+	return r == 0;
+}
+
+// a run's PCM to the output thread, and what the run pushed back to the callbacks' spare buffers
+void deliver(Multi *m, RunOut &o)
+{
+	std::lock_guard<std::mutex> g(m->m);
+	for (Source &s : m->src) {
+		for (std::vector<uint8_t> &buf : s.taken) s.spare.push_back(std::move(buf));
+		s.taken.clear();
+	}
+	m->out_q.push_back(std::move(o));
+	m->cv_out.notify_one();
+}
+
+void demod_done(Multi *m)
+{
+	std::lock_guard<std::mutex> g(m->m);
+	m->out_done = true;
+	m->cv_out.notify_all();
 }
 
 // -K: the records of the handle's streams (stream k = source live[k]) into m->kept - with `stay`, only those of the
@@ -602,9 +901,9 @@ int keep_states(Multi *m, const std::vector<int> &live, const std::vector<int> *
 int shrink(Multi *m, const std::vector<int> &live, const std::vector<int> &stay)
 {
 	int r = 0;
-	if (m->keep_file && (r = keep_states(m, live, &stay)) < 0) return r;  // in front of the regroup: what the leaving sources carried
+	if (m->st.keep_file && (r = keep_states(m, live, &stay)) < 0) return r;  // in front of the regroup: what the leaving sources carried
 	rtlfm_gpu *nh = nullptr;
-	r = rtlfm_gpu_create(&m->cfg, (int)stay.size(), 0, &nh);
+	r = rtlfm_gpu_create(&m->st.cfg, (int)stay.size(), 0, &nh);
 	if (r < 0) return r;
 	std::vector<int32_t> map;
 	for (size_t i = 0, k = 0; i < live.size() && k < stay.size(); i++) {
@@ -621,27 +920,6 @@ int shrink(Multi *m, const std::vector<int> &live, const std::vector<int> &stay)
 	rtlfm_gpu_destroy(m->gpu);
 	m->gpu = nh;
 	return 0;
-}
-
-void levels_multi(Multi *m, Source &s, int k)
-{
-	// as demod_thread's -L block, per stream
-	int32_t sr = 0;
-	int nl = 0;
-	if (rtlfm_gpu_levels(m->gpu, k, &sr, 1, &nl) != 0 || nl != 1) return;
-	--s.print_level_no;
-	if (sr < 0) return;
-	s.level_sum += sr;
-	if (s.level_max < sr) s.level_max = sr;
-	if (s.level_max_max < sr) s.level_max_max = sr;
-	if (s.print_level_no) return;
-	s.print_level_no = m->print_levels;
-	const double avg_rms = s.level_sum / m->print_levels;
-	fprintf(stderr, "stream %d: %.3f kHz, %.1f avg rms, %d max rms, %d max max rms, %d squelch rms, %d rms, %.1f dB rms level, %.2f dB avg rms level\n",
-	        s.index, s.user_freq / 1000.0, avg_rms, s.level_max, s.level_max_max, m->cfg.squelch_level, (int)sr,
-	        20.0 * log10(1E-10 + sr), 20.0 * log10(1E-10 + avg_rms));
-	s.level_max = 0;
-	s.level_sum = 0;
 }
 
 // -C: a fired event's command, in the background and without a shell: argv[0] = the command, the arguments split at
@@ -688,7 +966,7 @@ int monitor_step(Multi *m, const std::vector<int> &live)
 	if (live.size() == m->src.size()) {
 		r = rtlfm_monitor_update(m->mon, m->gpu);
 	} else {
-		const int cap = m->cfg.max_blocks;
+		const int cap = m->st.cfg.max_blocks;
 		std::vector<int32_t> lv(live.size() * (size_t)cap);
 		std::vector<rtlfm_input_stat> st(live.size() * (size_t)cap);
 		int n = 0, ns = 0;
@@ -705,7 +983,7 @@ int monitor_step(Multi *m, const std::vector<int> &live)
 		for (int i = 0; i < n; i++) {
 			const rtlfm_monitor_rule &rule = m->rules[(size_t)ev[i].stream];
 			m->events++;
-			if (m->verbosity) {
+			if (m->st.verbosity) {
 				char line[512];
 				rtlfm_monitor_format_event(&rule, &ev[i], line, sizeof(line));
 				fprintf(stderr, "stream %d: %s\n", ev[i].stream, line);
@@ -724,15 +1002,14 @@ int monitor_step(Multi *m, const std::vector<int> &live)
 // and leaves a mute for the source's next buffer.  Stream k of the handle is source live[k].
 int gate_step(Multi *m, const std::vector<int> &live)
 {
-	const int cap = m->cfg.max_blocks;
+	const int cap = m->st.cfg.max_blocks;
 	m->gate_recs.resize(live.size() * (size_t)cap);
 	int n = 0;
 	int r = rtlfm_gpu_gate_all(m->gpu, m->gate_recs.data(), cap, &n);
 	if (r < 0) return r;
 	for (size_t k = 0; k < live.size(); k++) {
-		Source &s = m->src[(size_t)live[k]];
 		for (int b = 0; b < n; b++)
-			if (!m->gate_recs[k * (size_t)cap + b].emit) s.blocks_squelched++;
+			if (!m->gate_recs[k * (size_t)cap + b].emit) m->out[(size_t)live[k]].blocks_squelched++;
 		if (m->scan && (r = rtlfm_scan_feed(m->scan, live[k], m->gate_recs.data() + k * (size_t)cap, n)) < 0) return r;
 	}
 	if (!m->scan) return 0;
@@ -741,16 +1018,15 @@ int gate_step(Multi *m, const std::vector<int> &live)
 		int ne = 0;
 		if ((r = rtlfm_scan_events(m->scan, ev, 64, &ne)) < 0) return r;
 		for (int e = 0; e < ne; e++) {
-			Source &s = m->src[(size_t)ev[e].stream];
-			const uint32_t f_new = ev[e].freq + (m->wb_mode ? 16000u : 0u);  // src/rtl_fm.c:1455-1460
-			rtlfm_cfg ci = m->cfg;
+			Sink &o = m->out[(size_t)ev[e].stream];
+			const uint32_t f_new = ev[e].freq + (m->st.wb_mode ? 16000u : 0u);  // src/rtl_fm.c:1455-1460
+			rtlfm_cfg ci = m->st.cfg;
 			uint32_t cf = 0;
-			rtlfm_optimal_settings(&ci, f_new, m->rate_in, m->min_capture, m->fifth, m->edge, &cf, nullptr);
-			rtlsdr_set_center_freq(s.dev, cf);  // :1506
-			if (m->verbosity)
-				fprintf(stderr, "stream %d: hop %u -> %u at buffer %lld\n", ev[e].stream, s.user_freq, f_new, (long long)ev[e].buffer_serial);
-			s.user_freq = f_new;
-			s.capture_freq = cf;
+			plan_one(m->st, f_new, &ci, &cf, nullptr);
+			rtlsdr_set_center_freq(m->src[(size_t)ev[e].stream].dev, cf);  // :1506
+			if (m->st.verbosity)
+				fprintf(stderr, "stream %d: hop %u -> %u at buffer %lld\n", ev[e].stream, o.user_freq, f_new, (long long)ev[e].buffer_serial);
+			o.user_freq = f_new;
 		}
 		if (ne < 64) break;
 	}
@@ -767,7 +1043,7 @@ int gate_step(Multi *m, const std::vector<int> &live)
 
 void demod_thread_multi(Multi *m)
 {
-	const size_t stride = ((size_t)rtlfm_result_cap(&m->cfg) * m->cfg.max_blocks + 16 + 63) / 64 * 64;
+	const rtlfm_cfg &c = m->st.cfg;
 	std::vector<int> live;
 	for (size_t i = 0; i < m->src.size(); i++) live.push_back((int)i);
 	// -vv: where this thread's time goes (waiting for the slowest source, the copy into the ring, run + fetch, the
@@ -777,39 +1053,17 @@ void demod_thread_multi(Multi *m)
 	uint64_t runs = 0;
 	auto since = [](clk::time_point t0) { return std::chrono::duration<double>(clk::now() - t0).count(); };
 	for (;;) {
-		std::vector<int> stay;
-		int b = m->cfg.max_blocks;
 		clk::time_point t0 = clk::now();
-		{
-			std::unique_lock<std::mutex> g(m->m);
-			m->cv_work.wait(g, [&] {
-				if (m->failed) return true;
-				for (int i : live)
-					if (m->src[i].q.empty() && !m->src[i].eof) return false;
-				return true;
-			});
-			if (m->failed) break;
-			for (int i : live)
-				if (!m->src[i].q.empty()) stay.push_back(i);  // an empty queue here means the source has ended
-			for (int i : stay) b = std::min(b, (int)m->src[i].q.size());
-			for (int i : stay) {
-				Source &s = m->src[i];
-				for (int j = 0; j < b; j++) {
-					s.taken.push_back(std::move(s.q.front()));
-					s.q.pop_front();
-				}
-				s.cv_room.notify_all();
-			}
-		}
-		if (stay.empty()) break;
+		std::vector<int> stay = live;
+		const int b = take_batch(m, stay);
+		if (!b) break;
 		if (stay.size() != live.size()) {
 			int r = shrink(m, live, stay);
 			if (r < 0) {
-				std::lock_guard<std::mutex> g(m->m);
-				fail_multi(m, "rtlfm_gpu_create / rtlfm_gpu_state_move", r);
+				fail(m, "rtlfm_gpu_create / rtlfm_gpu_state_move", r);
 				break;
 			}
-			if (m->verbosity)
+			if (m->st.verbosity)
 				fprintf(stderr, "%zu of %zu streams go on (the others' sources have ended)\n", stay.size(), m->src.size());
 			live = stay;
 		}
@@ -837,81 +1091,43 @@ void demod_thread_multi(Multi *m)
 		for (int e : err) if (e < 0 && r == 0) r = e;
 		t_push += since(t0);
 		t0 = clk::now();
-		int ran = 0;
-		if (r == 0) r = rtlfm_gpu_run_begin(m->gpu, &ran);
-		if (r == 0 && ran != b) r = -EPROTO;
-		if (r == 0) r = rtlfm_gpu_run_end(m->gpu);
 		RunOut o;
-		o.stride = stride;
-		o.pcm.resize(ns * stride);
-		o.lens.resize(ns);
-		o.who = live;
-		if (r == 0) r = rtlfm_gpu_fetch_all(m->gpu, o.pcm.data(), stride, o.lens.data());
-		if (r < 0) {
-			std::lock_guard<std::mutex> g(m->m);
-			fail_multi(m, "rtlfm_gpu_push/run/fetch_all", r);
-			break;
-		}
+		if (!run_and_fetch(m, r, b, live, o)) break;
 		if (m->hl.agc) {
 			std::vector<std::vector<uint32_t>> lens(ns);
 			for (size_t k = 0; k < ns; k++)
 				for (const std::vector<uint8_t> &buf : m->src[live[k]].taken) lens[k].push_back((uint32_t)buf.size());
-			if ((r = health_step(&m->hl, m->gpu, m->cfg.max_blocks, live, lens)) < 0) {
-				std::lock_guard<std::mutex> g(m->m);
-				fail_multi(m, "rtlfm_gpu_input_health_all / rtlfm_agc_feed", r);
+			if ((r = health_step(&m->hl, m->gpu, c.max_blocks, live, lens)) < 0) {
+				fail(m, "rtlfm_gpu_input_health_all / rtlfm_agc_feed", r);
 				break;
 			}
 		}
 		if (m->mon && (r = monitor_step(m, live)) < 0) {
-			std::lock_guard<std::mutex> g(m->m);
-			fail_multi(m, "rtlfm_monitor_update / feed", r);
+			fail(m, "rtlfm_monitor_update / feed", r);
 			break;
 		}
 		if (m->use_gate && (r = gate_step(m, live)) < 0) {
-			std::lock_guard<std::mutex> g(m->m);
-			fail_multi(m, "rtlfm_gpu_gate_all / rtlfm_scan_feed / rtlfm_gpu_mute", r);
+			fail(m, "rtlfm_gpu_gate_all / rtlfm_scan_feed / rtlfm_gpu_mute", r);
 			break;
 		}
 		t_run += since(t0);
 		t0 = clk::now();
 		runs++;
-		if (m->print_levels)
-			for (size_t k = 0; k < ns; k++) levels_multi(m, m->src[live[k]], (int)k);
-		if (m->cfg.squelch_level && !m->use_gate) {
-			// demod_thread's squelch rule (src/rtl_fm.c:1366-1370), per stream; max_blocks is 1 here.  Every stream's state in
-			// one copy, and one copy back only in a run that clamped a counter
-			m->states.resize(ns);
-			int got = 0;
-			bool clamped = false;
-			if (rtlfm_gpu_state_get_all(m->gpu, m->states.data(), (int)ns, &got) == 0) {
-				for (size_t k = 0; k < ns; k++) {
-					rtlfm_stream_state &st = m->states[k];
-					if (st.squelch_hits <= m->conseq_squelch) continue;
-					clamped |= st.squelch_hits != m->conseq_squelch + 1;
-					st.squelch_hits = m->conseq_squelch + 1;
-					m->src[live[k]].blocks_squelched++;
-					o.lens[k] = 0;
-				}
-				if (clamped) rtlfm_gpu_state_set_all(m->gpu, m->states.data(), (int)ns);
-			}
-		}
+		if (m->st.print_levels)
+			for (size_t k = 0; k < ns; k++) print_level(m->out[(size_t)live[k]], m->gpu, (int)k, m->st);
+		if (c.squelch_level && !m->use_gate)  // max_blocks is 1 here
+			hold_back(m->gpu, (int)ns, m->st.conseq_squelch, m->states, [&](int k) {
+				m->out[(size_t)live[(size_t)k]].blocks_squelched++;
+				o.lens[(size_t)k] = 0;
+			});
 		t_per_stream += since(t0);
-		std::lock_guard<std::mutex> g(m->m);
-		for (int i : live) {
-			Source &s = m->src[i];
-			for (std::vector<uint8_t> &buf : s.taken) s.spare.push_back(std::move(buf));
-			s.taken.clear();
-		}
-		m->out_q.push_back(std::move(o));
-		m->cv_out.notify_one();
+		deliver(m, o);
 	}
 	m->live = live;
-	if (m->verbosity >= 2)
+	if (m->st.verbosity >= 2)
 		fprintf(stderr, "demod thread: %llu runs; %.3f s waiting for buffers, %.3f s pushing, %.3f s run + fetch_all, %.3f s -l / -L\n",
 		        (unsigned long long)runs, t_wait, t_push, t_run, t_per_stream);
-	std::lock_guard<std::mutex> g(m->m);
-	m->out_done = true;
-	m->cv_out.notify_all();
+	demod_done(m);
 }
 
 void output_thread_multi(Multi *m)
@@ -925,72 +1141,69 @@ void output_thread_multi(Multi *m)
 			o = std::move(m->out_q.front());
 			m->out_q.pop_front();
 		}
-		for (size_t k = 0; k < o.who.size(); k++) {
-			Source &s = m->chan_per ? m->chan[o.who[k]] : m->src[o.who[k]];  // (-X: who = the handle's streams)
-			const size_t n = (size_t)o.lens[k];
-			if (!n) continue;
-			fwrite(o.pcm.data() + k * o.stride, 2, n, s.file);
-			s.wave.data_size += 2 * (uint32_t)n;
-			s.samples_out += n;
-		}
+		for (size_t k = 0; k < o.who.size(); k++)
+			if (o.lens[k]) m->out[(size_t)o.who[k]].write(o.pcm.data() + k * o.stride, (size_t)o.lens[k]);
 	}
-	for (Source &s : m->chan_per ? m->chan : m->src) fflush(s.file);
+	for (Sink &s : m->out) fflush(s.file);
 }
 
-// everything after option parsing for n > 1 (main has refused what -N does not allow)
-int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<uint32_t> &freqs,
-              const std::vector<uint32_t> &capture_freqs, uint32_t capture_rate, int gain, int ppm, const std::string &pattern,
-              bool write_wav, int verbosity, int conseq_squelch, int print_levels, const std::vector<rtlfm_monitor_rule> &rules,
-              const char *opt_string, int agc, const std::vector<std::vector<uint32_t>> &scan_lists, bool wb_mode, int rate_in,
-              int min_capture, int fifth, int edge, const char *keep_file, const char *resume_file)
+// devices dev_index .. dev_index + n - 1 exist?  `asked` is how the caller's message names what wants them
+bool devices_there(const Settings &st, int n, const std::string &asked)
 {
-	Multi m;
-	m.keep_file = keep_file;
-	m.kept.resize((size_t)n);
-	m.wb_mode = wb_mode; m.rate_in = rate_in; m.min_capture = min_capture; m.fifth = fifth; m.edge = edge;
-	m.rules = rules;
-	m.cfg = planned;
-	rtlfm_cfg &c = m.cfg;
-	m.depth = 2 * c.max_blocks;
-	m.verbosity = verbosity;
-	m.conseq_squelch = conseq_squelch;
-	m.print_levels = print_levels;
-	m.src = std::vector<Source>((size_t)n);
 	const uint32_t count = rtlsdr_get_device_count();
-	if (count == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE or RTLSDR_FILE_LIST).\n"); return 1; }
-	if ((uint64_t)dev_index + (uint64_t)n > count) {
-		fprintf(stderr, "-d %d -N %d needs devices %d .. %d, and there are %u.\n", dev_index, n, dev_index, dev_index + n - 1, count);
-		return 1;
+	if (count == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE or RTLSDR_FILE_LIST).\n"); return false; }
+	if ((uint64_t)st.dev_index + (uint64_t)n > count) {
+		fprintf(stderr, "-d %d %s needs devices %d .. %d, and there are %u.\n", st.dev_index, asked.c_str(), st.dev_index,
+		        st.dev_index + n - 1, count);
+		return false;
 	}
+	return true;
+}
+
+// the output thread, the mode's demod thread and a dongle thread per source, until the last source has ended
+void run_threads(Multi *m, void (*demod)(Multi *))
+{
+	for (Source &s : m->src) rtlsdr_reset_buffer(s.dev);
+	std::thread t_out(output_thread_multi, m), t_demod(demod, m);
+	std::vector<std::thread> t_dongle;
+	for (Source &s : m->src) t_dongle.emplace_back(dongle_thread_multi, &s);
+	for (std::thread &t : t_dongle) t.join();
+	t_demod.join();
+	t_out.join();
+}
+
+void close_all(Multi *m)
+{
+	for (Sink &s : m->out) s.close();
+	for (Source &s : m->src)
+		if (s.dev) rtlsdr_close(s.dev);
+	if (m->gpu) rtlfm_gpu_destroy(m->gpu);
+}
+
+// everything after option parsing for -N, -C and -S (main has refused what they do not allow): source i is tuned to
+// capture_freqs[i] for the user's freqs[i]; rules (-C) and scan_lists (-S) are empty or hold one entry per source
+int run_multi(const Settings &st, const std::vector<uint32_t> &freqs, const std::vector<uint32_t> &capture_freqs,
+              const std::vector<rtlfm_monitor_rule> &rules, const std::vector<std::vector<uint32_t>> &scan_lists)
+{
+	const int n = (int)freqs.size();
+	const rtlfm_cfg &c = st.cfg;
+	Multi m(st, (size_t)n, (size_t)n);
+	m.kept.resize((size_t)n);
+	m.rules = rules;
+	if (!devices_there(st, n, "-N " + std::to_string(n))) return 1;
 	int ret = 0;
 	for (int i = 0; i < n && !ret; i++) {
-		Source &s = m.src[i];
-		s.index = i;
+		Source &s = m.src[(size_t)i];
 		s.m = &m;
-		s.user_freq = freqs[i];
-		s.capture_freq = capture_freqs[i];
-		if (rtlsdr_open(&s.dev, (uint32_t)(dev_index + i)) < 0) {
-			fprintf(stderr, "Failed to open rtlsdr device #%d.\n", dev_index + i);
-			ret = 1;
-			break;
-		}
-		const int g_i = rules.empty() ? gain : rules[(size_t)i].gain;  // -C: each source's gain from its line
-		if (g_i == -100) rtlsdr_set_tuner_gain_mode(s.dev, 0);
-		else { rtlsdr_set_tuner_gain_mode(s.dev, 1); rtlsdr_set_tuner_gain(s.dev, g_i); }
-		if (opt_string) rtlsdr_set_opt_string(s.dev, opt_string, verbosity);
-		if (agc >= 0) rtlsdr_set_tuner_gain_mode(s.dev, agc);  // the string's agc=<tuner_gain_mode>, src/librtlsdr.c:3166-3171
-		rtlsdr_set_freq_correction_ppb(s.dev, ppm * 1000);
-		rtlsdr_set_offset_tuning(s.dev, c.offset_tuning);
-		rtlsdr_set_center_freq(s.dev, s.capture_freq);
-		if (rtlsdr_set_sample_rate(s.dev, capture_rate) < 0 && i == 0)
-			fprintf(stderr, "WARNING: capture rate %u Hz is outside what an RTL2832 can do.\n", capture_rate);
-		if (verbosity || i == 0 || capture_freqs[i] != capture_freqs[0])
-			fprintf(stderr, "stream %d: device #%d, tuned to %u Hz.\n", i, dev_index + i, s.capture_freq);
+		s.dev = open_source(st, i, rules.empty() ? st.gain : rules[(size_t)i].gain, capture_freqs[(size_t)i]);  // -C: each source's gain from its line
+		if (!s.dev) ret = 1;
+		else if (st.verbosity || i == 0 || capture_freqs[(size_t)i] != capture_freqs[0])
+			fprintf(stderr, "stream %d: device #%d, tuned to %u Hz.\n", i, st.dev_index + i, capture_freqs[(size_t)i]);
 	}
 	if (!ret) {
 		fprintf(stderr, "%d streams.\nOversampling input by: %ix.\nSampling at %u S/s.\nOutput at %u Hz.\n", n, c.downsample,
-		        capture_rate, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out));
-		if (verbosity)
+		        st.capture_rate, out_rate(c));
+		if (st.verbosity)
 			fprintf(stderr, "downsample_passes = %d, downsample = %d, deemph_a = %d, buffer = %u B, host queue = %d buffers per stream\n",
 			        c.downsample_passes, c.downsample, c.deemph_a, c.block_len, m.depth);
 		int r = rtlfm_gpu_create(&c, n, 0, &m.gpu);
@@ -998,35 +1211,14 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 			fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r));
 			ret = 2;
 		}
-		if (!ret && agc == 2) {
-			std::vector<rtlsdr_dev_t *> devs;
-			for (Source &s : m.src) devs.push_back(s.dev);
-			r = rtlfm_gpu_set_option(m.gpu, "input_health", 1);
-			if (r == 0) r = health_create(&m.hl, devs, c.max_blocks, verbosity);
-			if (r < 0) {
-				fprintf(stderr, "rtlfm_agc_create: %s\n", rtlfm_gpu_strerror(r));
-				ret = 2;
-			}
-		}
+		std::vector<rtlsdr_dev_t *> devs;
+		for (Source &s : m.src) devs.push_back(s.dev);
+		if (!ret && !handle_setup(m.gpu, st, devs, &m.hl, !scan_lists.empty(), &m.use_gate)) ret = 2;
 		if (!ret && !rules.empty()) {
 			r = rtlfm_gpu_set_option(m.gpu, "input_stats", 1);
 			if (r == 0) r = rtlfm_monitor_create(n, rules.data(), &m.mon);
 			if (r < 0) {
 				fprintf(stderr, "rtlfm_monitor_create: %s\n", rtlfm_gpu_strerror(r));
-				ret = 2;
-			}
-		}
-		if (!ret && resume_file && (r = rtlfm_gpu_load(m.gpu, resume_file)) < 0) {
-			fprintf(stderr, "-R %s: %s\n", resume_file, rtlfm_gpu_strerror(r));
-			ret = 2;
-		}
-		if (!ret && c.squelch_level) {
-			// -l: demod_thread_fn's rule on the device where the configuration has a gate (not behind a resampler)
-			r = rtlfm_gpu_set_option(m.gpu, "conseq_squelch", conseq_squelch);
-			if (r == 0) r = rtlfm_gpu_set_option(m.gpu, "squelch_gate", 1);
-			m.use_gate = r == 0;
-			if (r < 0 && (r != -ENOTSUP || !scan_lists.empty())) {
-				fprintf(stderr, "squelch_gate: %s\n", rtlfm_gpu_strerror(r));
 				ret = 2;
 			}
 		}
@@ -1040,43 +1232,20 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 			}
 		}
 	}
-	const size_t at = pattern.find("%d");
-	for (int i = 0; i < n && !ret; i++) {
-		Source &s = m.src[i];
-		const std::string name = at == std::string::npos ? pattern : pattern.substr(0, at) + std::to_string(i) + pattern.substr(at + 2);
-		s.file = fopen(name.c_str(), "wb");
-		if (!s.file) { fprintf(stderr, "Failed to open %s\n", name.c_str()); ret = 1; break; }
-		if (write_wav)
-			rtlamd_wave_write_header(&s.wave, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out), s.user_freq, 16,
-			                         c.mode == RTLFM_MODE_RAW ? 2 : 1, s.file);
-		rtlsdr_reset_buffer(s.dev);
-	}
+	for (int i = 0; i < n && !ret; i++)
+		if (!m.out[(size_t)i].open(st, i, freqs[(size_t)i])) ret = 1;
 	if (!ret) {
-		std::thread t_out(output_thread_multi, &m), t_demod(demod_thread_multi, &m);
-		std::vector<std::thread> t_dongle;
-		for (Source &s : m.src) t_dongle.emplace_back(dongle_thread_multi, &s);
-		for (std::thread &t : t_dongle) t.join();
-		t_demod.join();
-		t_out.join();
-		uint64_t in = 0, out = 0, sq = 0;
-		for (Source &s : m.src) {
-			in += s.blocks_in;
-			out += s.samples_out;
-			sq += s.blocks_squelched;
-		}
-		fprintf(stderr, "%llu buffers in, %llu samples out, %llu buffers held back by the squelch%s\n", (unsigned long long)in,
-		        (unsigned long long)out, (unsigned long long)sq, m.failed ? " (FAILED)" : "");
-		if (verbosity)
-			for (Source &s : m.src)
-				fprintf(stderr, "stream %d: %llu buffers in, %llu samples out, %llu buffers held back by the squelch\n", s.index,
-				        (unsigned long long)s.blocks_in, (unsigned long long)s.samples_out, (unsigned long long)s.blocks_squelched);
+		run_threads(&m, demod_thread_multi);
+		std::vector<uint64_t> in;
+		for (Source &s : m.src) in.push_back(s.blocks_in);
+		summary(m.out.data(), m.out.size(), std::accumulate(in.begin(), in.end(), (uint64_t)0), in.data(), m.failed, st.verbosity > 0);
 		if (m.mon) {
 			fprintf(stderr, "%llu monitor events, %llu fired\n", (unsigned long long)m.events, (unsigned long long)m.fired);
 			// the scan statistics of src/rtl_fm.c:2033-2040, one line per command-file line that reported a level
 			for (int i = 0; i < n; i++) {
-				rtlfm_monitor_stat st;
-				if (rtlfm_monitor_stats(m.mon, i, &st) == 0 && st.count > 0)
-					fprintf(stderr, "%u, %.1f, %.2f, %.1f\n", rules[(size_t)i].freq, st.min_level, st.sum_levels / st.count, st.max_level);
+				rtlfm_monitor_stat ms;
+				if (rtlfm_monitor_stats(m.mon, i, &ms) == 0 && ms.count > 0)
+					fprintf(stderr, "%u, %.1f, %.2f, %.1f\n", rules[(size_t)i].freq, ms.min_level, ms.sum_levels / ms.count, ms.max_level);
 			}
 		}
 		if (m.hl.agc) health_report(&m.hl);
@@ -1086,15 +1255,15 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 				uint64_t hops = 0, held = 0;
 				rtlfm_scan_freq(m.scan, i, &f, nullptr, &hops, nullptr, &held);
 				fprintf(stderr, "stream %d: %llu hops, %llu buffers held, last on %u Hz\n", i, (unsigned long long)hops,
-				        (unsigned long long)held, f + (wb_mode ? 16000u : 0u));
+				        (unsigned long long)held, f + (st.wb_mode ? 16000u : 0u));
 			}
 		if (m.failed) ret = 3;
-		if (!ret && keep_file) {
+		if (!ret && st.keep_file) {
 			// behind the last run: the sources that were in the batch to the end, beside the records the others left
 			int r = keep_states(&m, m.live, nullptr);
-			if (r == 0) r = rtlfm_snapshot_write(keep_file, &c, n, m.kept.data(), nullptr);
+			if (r == 0) r = rtlfm_snapshot_write(st.keep_file, &c, n, m.kept.data(), nullptr);
 			if (r < 0) {
-				fprintf(stderr, "-K %s: %s\n", keep_file, rtlfm_gpu_strerror(r));
+				fprintf(stderr, "-K %s: %s\n", st.keep_file, rtlfm_gpu_strerror(r));
 				ret = 3;
 			}
 		}
@@ -1103,62 +1272,32 @@ int run_multi(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<
 	if (m.hl.agc) rtlfm_agc_destroy(m.hl.agc);
 	for (pid_t pid : m.children) waitpid(pid, nullptr, 0);  // the triggered commands run in the background; none outlives the tool
 	if (m.mon) rtlfm_monitor_destroy(m.mon);
-	for (Source &s : m.src) {
-		if (s.file) {
-			if (write_wav) rtlamd_wave_finalize(&s.wave, s.file);
-			fclose(s.file);
-		}
-		if (s.dev) rtlsdr_close(s.dev);
-	}
-	if (m.gpu) rtlfm_gpu_destroy(m.gpu);
+	close_all(&m);
 	return ret;
 }
 
 // ---- -X: K channels per source, one handle of n x K streams over the library's source-indexed ring ------------------
 //
 // The device side is -N's: on_buffer_multi / dongle_thread_multi, a host queue per source.  The demod thread takes
-// b = min(what every live queue holds, max_blocks) buffers from every live source and pushes them with the SOURCE's index
-// (option source_ring); a short buffer - a file's last - is completed with bytes 127 to the full length, and a source
-// that has ended is fed b buffers of bytes 127, so that every source has one length per buffer index and the handle's one
-// sample counter holds for all.  The streams of an ended source write nothing more.  The run ends with the last source.
+// b = min(what every live queue holds, max_blocks) buffers from every live source (take_batch) and pushes them with the
+// SOURCE's index (option source_ring); a short buffer - a file's last - is completed with bytes 127 to the full length, and
+// a source that has ended is fed b buffers of bytes 127, so that every source has one length per buffer index and the
+// handle's one sample counter holds for all.  The streams of an ended source write nothing more and count nothing more.
+// The run ends with the last source.
 void demod_thread_channels(Multi *m)
 {
 	const int n = (int)m->src.size(), K = m->chan_per, S = n * K;
-	const size_t stride = ((size_t)rtlfm_result_cap(&m->cfg) * m->cfg.max_blocks + 16 + 63) / 64 * 64;
-	const uint32_t L = m->cfg.block_len;
+	const uint32_t L = m->st.cfg.block_len;
 	const std::vector<uint8_t> silence(L, 127);
-	std::vector<int> who((size_t)S);
+	std::vector<int> who((size_t)S), live((size_t)n);
 	for (int s = 0; s < S; s++) who[(size_t)s] = s;
+	for (int i = 0; i < n; i++) live[(size_t)i] = i;
 	std::vector<char> ended((size_t)n, 0);
 	for (;;) {
-		int b = m->cfg.max_blocks, live = 0;
-		{
-			std::unique_lock<std::mutex> g(m->m);
-			m->cv_work.wait(g, [&] {
-				if (m->failed) return true;
-				for (int i = 0; i < n; i++)
-					if (!ended[(size_t)i] && m->src[(size_t)i].q.empty() && !m->src[(size_t)i].eof) return false;
-				return true;
-			});
-			if (m->failed) break;
-			for (int i = 0; i < n; i++) {
-				Source &s = m->src[(size_t)i];
-				if (!ended[(size_t)i] && s.q.empty()) ended[(size_t)i] = 1;  // an empty queue here means the source has ended
-				if (ended[(size_t)i]) continue;
-				live++;
-				b = std::min(b, (int)s.q.size());
-			}
-			for (int i = 0; i < n; i++) {
-				Source &s = m->src[(size_t)i];
-				if (ended[(size_t)i]) continue;
-				for (int j = 0; j < b; j++) {
-					s.taken.push_back(std::move(s.q.front()));
-					s.q.pop_front();
-				}
-				s.cv_room.notify_all();
-			}
-		}
-		if (!live) break;
+		const int b = take_batch(m, live);
+		if (!b) break;
+		std::fill(ended.begin(), ended.end(), 1);
+		for (int i : live) ended[(size_t)i] = 0;
 		int r = 0;
 		for (int i = 0; i < n && r == 0; i++) {
 			if (ended[(size_t)i]) {
@@ -1170,110 +1309,48 @@ void demod_thread_channels(Multi *m)
 				if ((r = rtlfm_gpu_push(m->gpu, i, buf.data(), L)) < 0) break;
 			}
 		}
-		int ran = 0;
-		if (r == 0) r = rtlfm_gpu_run_begin(m->gpu, &ran);
-		if (r == 0 && ran != b) r = -EPROTO;
-		if (r == 0) r = rtlfm_gpu_run_end(m->gpu);
 		RunOut o;
-		o.stride = stride;
-		o.pcm.resize((size_t)S * stride);
-		o.lens.resize((size_t)S);
-		o.who = who;
-		if (r == 0) r = rtlfm_gpu_fetch_all(m->gpu, o.pcm.data(), stride, o.lens.data());
-		if (r < 0) {
-			std::lock_guard<std::mutex> g(m->m);
-			fail_multi(m, "rtlfm_gpu_push/run/fetch_all", r);
-			break;
-		}
+		if (!run_and_fetch(m, r, b, who, o)) break;
 		for (int s = 0; s < S; s++)
 			if (ended[(size_t)(s / K)]) o.lens[(size_t)s] = 0;
-		if (m->print_levels)
+		if (m->st.print_levels)
 			for (int s = 0; s < S; s++)
-				if (!ended[(size_t)(s / K)]) levels_multi(m, m->chan[(size_t)s], s);
-		if (m->cfg.squelch_level) {
-			// demod_thread's squelch rule per stream, as demod_thread_multi applies it without the device gate (max_blocks is 1)
-			m->states.resize((size_t)S);
-			int got = 0;
-			bool clamped = false;
-			if (rtlfm_gpu_state_get_all(m->gpu, m->states.data(), S, &got) == 0) {
-				for (int s = 0; s < S; s++) {
-					rtlfm_stream_state &st = m->states[(size_t)s];
-					if (st.squelch_hits <= m->conseq_squelch) continue;
-					clamped |= st.squelch_hits != m->conseq_squelch + 1;
-					st.squelch_hits = m->conseq_squelch + 1;
-					if (!ended[(size_t)(s / K)]) m->chan[(size_t)s].blocks_squelched++;
-					o.lens[(size_t)s] = 0;
-				}
-				if (clamped) rtlfm_gpu_state_set_all(m->gpu, m->states.data(), S);
-			}
-		}
-		std::lock_guard<std::mutex> g(m->m);
-		for (Source &s : m->src) {
-			for (std::vector<uint8_t> &buf : s.taken) s.spare.push_back(std::move(buf));
-			s.taken.clear();
-		}
-		m->out_q.push_back(std::move(o));
-		m->cv_out.notify_one();
+				if (!ended[(size_t)(s / K)]) print_level(m->out[(size_t)s], m->gpu, s, m->st);
+		if (m->st.cfg.squelch_level)  // as -N without the device gate; max_blocks is 1
+			hold_back(m->gpu, S, m->st.conseq_squelch, m->states, [&](int s) {
+				if (!ended[(size_t)(s / K)]) m->out[(size_t)s].blocks_squelched++;
+				o.lens[(size_t)s] = 0;
+			});
+		deliver(m, o);
 	}
-	std::lock_guard<std::mutex> g(m->m);
-	m->out_done = true;
-	m->cv_out.notify_all();
+	demod_done(m);
 }
 
 // everything after option parsing for -X (main has refused what -X does not allow): freqs[i] = source i's -f as given,
 // chan_freqs[i] = its K channel frequencies, each within capture_rate / 2 of freqs[i]
-int run_channels(const rtlfm_cfg &planned, int n, int dev_index, const std::vector<uint32_t> &freqs,
-                 const std::vector<std::vector<uint32_t>> &chan_freqs, uint32_t capture_rate, int gain, int ppm,
-                 const std::string &pattern, bool write_wav, int verbosity, int conseq_squelch, int print_levels,
-                 const char *opt_string, int agc, int ntaps)
+int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const std::vector<std::vector<uint32_t>> &chan_freqs)
 {
-	Multi m;
-	m.cfg = planned;
-	rtlfm_cfg &c = m.cfg;
-	const int K = (int)chan_freqs[0].size(), S = n * K;
+	const rtlfm_cfg &c = st.cfg;
+	const int n = (int)freqs.size(), K = (int)chan_freqs[0].size(), S = n * K, ntaps = st.chan_taps > 0 ? st.chan_taps : 0;
+	Multi m(st, (size_t)n, (size_t)S);
 	m.chan_per = K;
-	m.depth = 2 * c.max_blocks;
-	m.verbosity = verbosity;
-	m.conseq_squelch = conseq_squelch;
-	m.print_levels = print_levels;
-	m.src = std::vector<Source>((size_t)n);
-	m.chan = std::vector<Source>((size_t)S);
-	const uint32_t count = rtlsdr_get_device_count();
-	if (count == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE or RTLSDR_FILE_LIST).\n"); return 1; }
-	if ((uint64_t)dev_index + (uint64_t)n > count) {
-		fprintf(stderr, "-d %d with %d sources needs devices %d .. %d, and there are %u.\n", dev_index, n, dev_index, dev_index + n - 1, count);
-		return 1;
-	}
+	if (!devices_there(st, n, "with " + std::to_string(n) + " sources")) return 1;
 	int ret = 0;
 	for (int i = 0; i < n && !ret; i++) {
 		Source &s = m.src[(size_t)i];
-		s.index = i;
 		s.m = &m;
-		s.user_freq = s.capture_freq = freqs[(size_t)i];  // as given: the mixers take the rotation's place
-		if (rtlsdr_open(&s.dev, (uint32_t)(dev_index + i)) < 0) {
-			fprintf(stderr, "Failed to open rtlsdr device #%d.\n", dev_index + i);
-			ret = 1;
-			break;
-		}
-		if (gain == -100) rtlsdr_set_tuner_gain_mode(s.dev, 0);
-		else { rtlsdr_set_tuner_gain_mode(s.dev, 1); rtlsdr_set_tuner_gain(s.dev, gain); }
-		if (opt_string) rtlsdr_set_opt_string(s.dev, opt_string, verbosity);
-		if (agc >= 0) rtlsdr_set_tuner_gain_mode(s.dev, agc);
-		rtlsdr_set_freq_correction_ppb(s.dev, ppm * 1000);
-		rtlsdr_set_offset_tuning(s.dev, c.offset_tuning);
-		rtlsdr_set_center_freq(s.dev, s.capture_freq);
-		if (rtlsdr_set_sample_rate(s.dev, capture_rate) < 0 && i == 0)
-			fprintf(stderr, "WARNING: capture rate %u Hz is outside what an RTL2832 can do.\n", capture_rate);
-		fprintf(stderr, "source %d: device #%d, tuned to %u Hz, streams %d .. %d.\n", i, dev_index + i, s.capture_freq, i * K, i * K + K - 1);
+		s.dev = open_source(st, i, st.gain, freqs[(size_t)i]);  // as given: the mixers take the rotation's place
+		if (!s.dev) ret = 1;
+		else fprintf(stderr, "source %d: device #%d, tuned to %u Hz, streams %d .. %d.\n", i, st.dev_index + i, freqs[(size_t)i], i * K, i * K + K - 1);
 	}
 	if (!ret) {
 		fprintf(stderr, "%d sources x %d channels = %d streams.\nOversampling input by: %ix.\nSampling at %u S/s.\nOutput at %u Hz.\n", n, K, S,
-		        c.downsample, capture_rate, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out));
+		        c.downsample, st.capture_rate, out_rate(c));
 		std::vector<uint32_t> steps((size_t)S);
 		for (int s = 0; s < S; s++) {
 			const uint32_t cf = chan_freqs[(size_t)(s / K)][(size_t)(s % K)];
-			steps[(size_t)s] = rtlfm_channel_step((int32_t)((int64_t)cf - (int64_t)freqs[(size_t)(s / K)]), capture_rate);
-			if (verbosity) fprintf(stderr, "stream %d: source %d, %u Hz, step %u\n", s, s / K, cf, steps[(size_t)s]);
+			steps[(size_t)s] = rtlfm_channel_step((int32_t)((int64_t)cf - (int64_t)freqs[(size_t)(s / K)]), st.capture_rate);
+			if (st.verbosity) fprintf(stderr, "stream %d: source %d, %u Hz, step %u\n", s, s / K, cf, steps[(size_t)s]);
 		}
 		const char *what = "rtlfm_gpu_create";
 		int r = rtlfm_gpu_create(&c, S, 0, &m.gpu);
@@ -1294,7 +1371,7 @@ int run_channels(const rtlfm_cfg &planned, int n, int dev_index, const std::vect
 				r = rtlfm_channel_lowpass(ntaps, 0.4 / c.downsample, gain, taps.data(), &shift);
 			}
 			shift -= less;
-			if (r == 0 && (less || verbosity)) fprintf(stderr, "-x %d: gain %d at shift %d\n", ntaps, gain, shift);
+			if (r == 0 && (less || st.verbosity)) fprintf(stderr, "-x %d: gain %d at shift %d\n", ntaps, gain, shift);
 			if (r == 0) { what = "rtlfm_gpu_set_channel_filter"; r = rtlfm_gpu_set_channel_filter(m.gpu, taps.data(), ntaps, shift); }
 		}
 		if (r < 0) {
@@ -1302,48 +1379,16 @@ int run_channels(const rtlfm_cfg &planned, int n, int dev_index, const std::vect
 			ret = 2;
 		}
 	}
-	const size_t at = pattern.find("%d");
-	for (int s = 0; s < S && !ret; s++) {
-		Source &ch = m.chan[(size_t)s];
-		ch.index = s;
-		ch.user_freq = chan_freqs[(size_t)(s / K)][(size_t)(s % K)];
-		const std::string name = at == std::string::npos ? pattern : pattern.substr(0, at) + std::to_string(s) + pattern.substr(at + 2);
-		ch.file = fopen(name.c_str(), "wb");
-		if (!ch.file) { fprintf(stderr, "Failed to open %s\n", name.c_str()); ret = 1; break; }
-		if (write_wav)
-			rtlamd_wave_write_header(&ch.wave, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out), ch.user_freq, 16,
-			                         c.mode == RTLFM_MODE_RAW ? 2 : 1, ch.file);
-	}
+	for (int s = 0; s < S && !ret; s++)
+		if (!m.out[(size_t)s].open(st, s, chan_freqs[(size_t)(s / K)][(size_t)(s % K)])) ret = 1;
 	if (!ret) {
-		for (Source &s : m.src) rtlsdr_reset_buffer(s.dev);
-		std::thread t_out(output_thread_multi, &m), t_demod(demod_thread_channels, &m);
-		std::vector<std::thread> t_dongle;
-		for (Source &s : m.src) t_dongle.emplace_back(dongle_thread_multi, &s);
-		for (std::thread &t : t_dongle) t.join();
-		t_demod.join();
-		t_out.join();
-		uint64_t in = 0, out = 0, sq = 0;
+		run_threads(&m, demod_thread_channels);
+		uint64_t in = 0;
 		for (Source &s : m.src) in += s.blocks_in;
-		for (Source &ch : m.chan) {
-			out += ch.samples_out;
-			sq += ch.blocks_squelched;
-		}
-		fprintf(stderr, "%llu buffers in, %llu samples out, %llu buffers held back by the squelch%s\n", (unsigned long long)in,
-		        (unsigned long long)out, (unsigned long long)sq, m.failed ? " (FAILED)" : "");
-		if (verbosity)
-			for (Source &ch : m.chan)
-				fprintf(stderr, "stream %d: %llu samples out, %llu buffers held back by the squelch\n", ch.index,
-				        (unsigned long long)ch.samples_out, (unsigned long long)ch.blocks_squelched);
+		summary(m.out.data(), m.out.size(), in, nullptr, m.failed, st.verbosity > 0);
 		if (m.failed) ret = 3;
 	}
-	for (Source &ch : m.chan)
-		if (ch.file) {
-			if (write_wav) rtlamd_wave_finalize(&ch.wave, ch.file);
-			fclose(ch.file);
-		}
-	for (Source &s : m.src)
-		if (s.dev) rtlsdr_close(s.dev);
-	if (m.gpu) rtlfm_gpu_destroy(m.gpu);
+	close_all(&m);
 	return ret;
 }
 
@@ -1411,63 +1456,56 @@ void usage()
 
 int main(int argc, char **argv)
 {
-	App a;
-	rtlfm_cfg_default(&a.cfg);
-	rtlfm_cfg &c = a.cfg;
-	int rate_in = 24000, min_capture = 1000000, time_constant = 75;
-	int fifth = 0, edge = 0, dev_index = 0, gain = -100, ppm = 0;
+	Settings st;
+	rtlfm_cfg_default(&st.cfg);
+	rtlfm_cfg &c = st.cfg;
 	uint32_t freq = 0;
 	std::vector<uint32_t> freqs;  // every -f, in order (-N)
 	int nstreams = 1;
-	bool have_freq = false, write_wav = false, wb_mode = false;
-	int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
-	const char *cmd_file = nullptr, *opt_string = nullptr, *scan_file = nullptr, *keep_file = nullptr, *resume_file = nullptr;
-	const char *chan_file = nullptr;  // -X
-	int chan_taps = -1;               // -x; -1: not given
-	int agc = -1;  // -O agc=<n>; -1: not given
+	bool have_freq = false;
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
 	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:K:R:X:x:")) != -1) {
 		switch (opt) {
-		case 'd': dev_index = atoi(optarg); break;
+		case 'd': st.dev_index = atoi(optarg); break;
 		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
 		case 'N': nstreams = atoi(optarg); break;
-		case 'C': cmd_file = optarg; break;
-		case 'S': scan_file = optarg; break;
-		case 'K': keep_file = optarg; break;
-		case 'R': resume_file = optarg; break;
-		case 'X': chan_file = optarg; break;
-		case 'x': chan_taps = atoi(optarg); break;
+		case 'C': st.cmd_file = optarg; break;
+		case 'S': st.scan_file = optarg; break;
+		case 'K': st.keep_file = optarg; break;
+		case 'R': st.resume_file = optarg; break;
+		case 'X': st.chan_file = optarg; break;
+		case 'x': st.chan_taps = atoi(optarg); break;
 		case 'O':
-			opt_string = optarg;
-			agc = opt_string_agc(optarg);
-			if (agc == -2) {
+			st.opt_string = optarg;
+			st.agc = opt_string_agc(optarg);
+			if (st.agc == -2) {
 				fprintf(stderr, "-O %s: agc= takes 0 (hardware AGC), 1 (manual) or 2 (software AGC).\n", optarg);
 				return 1;
 			}
 			break;
-		case 'g': gain = (int)(atof(optarg) * 10); break;
-		case 'p': ppm = (int)atof(optarg); break;
-		case 'm': min_capture = (int)atofs(optarg); break;
+		case 'g': st.gain = (int)(atof(optarg) * 10); break;
+		case 'p': st.ppm = (int)atof(optarg); break;
+		case 'm': st.min_capture = (int)atofs(optarg); break;
 		case 'l': c.squelch_level = (int)atof(optarg); break;
-		case 'L': a.print_levels = (int)atof(optarg); break;  // src/rtl_fm.c:1757-1759
+		case 'L': st.print_levels = (int)atof(optarg); break;
 		case 't':  // src/rtl_fm.c:1774-1781 (a negative value also asks to terminate on squelch: not restated)
-			conseq_squelch = (int)atof(optarg);
-			if (conseq_squelch < 0) conseq_squelch = -conseq_squelch;
+			st.conseq_squelch = (int)atof(optarg);
+			if (st.conseq_squelch < 0) st.conseq_squelch = -st.conseq_squelch;
 			break;
-		case 's': rate_in = (int)atofs(optarg); c.rate_out = rate_in; break;
+		case 's': st.rate_in = (int)atofs(optarg); c.rate_out = st.rate_in; break;
 		case 'r': c.rate_out2 = (int)atofs(optarg); break;
 		case 'o': c.post_downsample = (int)atof(optarg); break;
 		case 'q': c.rdc_block_const = atoi(optarg); break;
 		case 'E':
-			if (!strcmp(optarg, "edge")) edge = 1;
+			if (!strcmp(optarg, "edge")) st.edge = 1;
 			if (!strcmp(optarg, "dc") || !strcmp(optarg, "adc")) c.dc_block_audio = 1;
 			if (!strcmp(optarg, "rdc")) c.dc_block_raw = 1;
 			if (!strcmp(optarg, "deemp")) c.deemph = 1;
 			if (!strcmp(optarg, "offset")) c.offset_tuning = 1;
 			break;
-		case 'F': fifth = 1; c.comp_fir_size = atoi(optarg); break;
+		case 'F': st.fifth = 1; c.comp_fir_size = atoi(optarg); break;
 		case 'A':
 			if (!strcmp(optarg, "std")) c.custom_atan = RTLFM_ATAN_STD;
 			if (!strcmp(optarg, "fast")) c.custom_atan = RTLFM_ATAN_FAST;
@@ -1482,17 +1520,17 @@ int main(int argc, char **argv)
 			if (!strcmp(optarg, "wbfm") || !strcmp(optarg, "wfm")) {
 				// the preset of src/rtl_fm.c:1831-1840
 				c.mode = RTLFM_MODE_FM;
-				rate_in = 170000; c.rate_out = 170000; c.rate_out2 = 32000;
+				st.rate_in = 170000; c.rate_out = 170000; c.rate_out2 = 32000;
 				c.custom_atan = RTLFM_ATAN_FAST;
 				c.deemph = 1;
 				c.squelch_level = 0;
-				wb_mode = true;
+				st.wb_mode = true;
 			}
 			break;
 		case 'c':
-			if (!strcmp(optarg, "us")) time_constant = 75;
-			else if (!strcmp(optarg, "eu")) time_constant = 50;
-			else time_constant = (int)atof(optarg);
+			if (!strcmp(optarg, "us")) st.time_constant = 75;
+			else if (!strcmp(optarg, "eu")) st.time_constant = 50;
+			else st.time_constant = (int)atof(optarg);
 			break;
 		case 'W': {
 			long v = 512L * atoi(optarg);
@@ -1500,68 +1538,55 @@ int main(int argc, char **argv)
 			c.block_len = (uint32_t)v;
 			break;
 		}
-		case 'H': write_wav = true; break;
-		case 'Z': a.zero_copy = true; break;
-		case 'v': a.verbosity++; break;
+		case 'H': st.write_wav = true; break;
+		case 'Z': st.zero_copy = true; break;
+		case 'v': st.verbosity++; break;
 		default: usage();
 		}
 	}
-	if (chan_taps != -1 && !chan_file) {
+	if (st.chan_taps != -1 && !st.chan_file) {
 		fprintf(stderr, "-x (taps of the channel filter) needs -X (the channel file): the filter acts on channels only.\n");
 		return 1;
 	}
-	if (chan_file) {
+	if (st.chan_file) {
 		// everything -X refuses for what it is combined with is refused here, before a device is opened or a handle created:
 		// each of these needs what the library refuses while channels are on (include/rtlfm_hip.h, rtlfm_gpu_set_channels)
 		const char *with = nullptr, *why = nullptr;
-		if (scan_file) { with = "-S (scan lists)"; why = "a hop needs the hop mute and the squelch gate, which read per-stream input rows"; }
-		else if (cmd_file) { with = "-C (command file)"; why = "the monitor needs the option input_stats, which reads per-stream input rows"; }
-		else if (keep_file) { with = "-K (keep)"; why = "a snapshot does not hold the channels' sample counter"; }
-		else if (resume_file) { with = "-R (resume)"; why = "a snapshot does not hold the channels' sample counter"; }
-		else if (a.zero_copy) { with = "-Z (zero-copy)"; why = "the ring is filled from the sources' host queues, in lockstep"; }
-		else if (agc == 2) { with = "-O agc=2 (software AGC)"; why = "it needs the option input_health, which reads per-stream input rows"; }
+		if (st.scan_file) { with = "-S (scan lists)"; why = "a hop needs the hop mute and the squelch gate, which read per-stream input rows"; }
+		else if (st.cmd_file) { with = "-C (command file)"; why = "the monitor needs the option input_stats, which reads per-stream input rows"; }
+		else if (st.keep_file) { with = "-K (keep)"; why = "a snapshot does not hold the channels' sample counter"; }
+		else if (st.resume_file) { with = "-R (resume)"; why = "a snapshot does not hold the channels' sample counter"; }
+		else if (st.zero_copy) { with = "-Z (zero-copy)"; why = "the ring is filled from the sources' host queues, in lockstep"; }
+		else if (st.agc == 2) { with = "-O agc=2 (software AGC)"; why = "it needs the option input_health, which reads per-stream input rows"; }
 		else if (c.dc_block_raw) { with = "-E rdc (raw DC block)"; why = "it rides on the rotation's kernel, whose place the mixers take"; }
-		else if (chan_taps != -1 && fifth) { with = "-x (channel filter) with -F (fifth-order low pass)"; why = "the channel filter stands in the boxcar's place, and -F leaves no boxcar"; }
+		else if (st.chan_taps != -1 && st.fifth) { with = "-x (channel filter) with -F (fifth-order low pass)"; why = "the channel filter stands in the boxcar's place, and -F leaves no boxcar"; }
 		if (with) {
 			fprintf(stderr, "-X (channel file) does not go with %s: %s.\n", with, why);
 			return 1;
 		}
-		if (chan_taps != -1 && (chan_taps < 1 || chan_taps > RTLFM_CHANNEL_MAX_TAPS)) {
-			fprintf(stderr, "-x %d with -X: the channel filter takes 1 .. %d taps.\n", chan_taps, RTLFM_CHANNEL_MAX_TAPS);
+		if (st.chan_taps != -1 && (st.chan_taps < 1 || st.chan_taps > RTLFM_CHANNEL_MAX_TAPS)) {
+			fprintf(stderr, "-x %d with -X: the channel filter takes 1 .. %d taps.\n", st.chan_taps, RTLFM_CHANNEL_MAX_TAPS);
 			return 1;
 		}
 	}
-	if ((keep_file || resume_file) && (scan_file || cmd_file || agc == 2)) {
+	if ((st.keep_file || st.resume_file) && (st.scan_file || st.cmd_file || st.agc == 2)) {
 		// before a device is opened: the hop engine, the monitor and the software AGC carry state of their own
 		fprintf(stderr, "-K / -R (keep / resume the carried state) do not go with -S, -C or -O agc=2: those engines carry state of "
 		                "their own that the snapshot does not hold.\n");
 		return 1;
 	}
+	int bad_line = 0;
 	std::vector<std::vector<uint32_t>> scan_lists;
-	if (scan_file) {
+	if (st.scan_file) {
 		// everything -S refuses is refused here, before a device is opened
 		if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
-		if (cmd_file) { fprintf(stderr, "-S (scan lists) and -C (command file) exclude each other.\n"); usage(); }
+		if (st.cmd_file) { fprintf(stderr, "-S (scan lists) and -C (command file) exclude each other.\n"); usage(); }
 		if (!c.squelch_level) { fprintf(stderr, "Please specify a squelch level.  Required for scanning multiple frequencies.\n"); return 1; }  // src/rtl_fm.c:1693
-		FILE *sf = fopen(scan_file, "r");
-		if (!sf) { fprintf(stderr, "-S %s: cannot open the scan file\n", scan_file); usage(); }
-		char line[65536];
-		int lineno = 0;
-		while (fgets(line, sizeof(line), sf)) {
-			lineno++;
-			const char *t = line;
-			while (*t == ' ' || *t == '\t') t++;
-			if (*t == '#' || *t == '\n' || *t == '\r' || !*t) continue;
-			int nf = 0;
-			int pr = rtlfm_scan_parse_list(t, nullptr, 0, &nf);
-			std::vector<uint32_t> fl((size_t)(nf > 0 ? nf : 0));
-			if (pr == -ENOBUFS) pr = rtlfm_scan_parse_list(t, fl.data(), nf, &nf);
-			if (pr < 0) { fclose(sf); fprintf(stderr, "-S %s: line %d is no frequency list\n", scan_file, lineno); usage(); }
-			scan_lists.push_back(std::move(fl));
-		}
-		fclose(sf);
+		const int lr = read_list_file(st.scan_file, scan_lists, nullptr, &bad_line);
+		if (lr == -ENOENT) { fprintf(stderr, "-S %s: cannot open the scan file\n", st.scan_file); usage(); }
+		if (lr < 0) { fprintf(stderr, "-S %s: line %d is no frequency list\n", st.scan_file, bad_line); usage(); }
 		if ((int)scan_lists.size() != nstreams) {
-			fprintf(stderr, "-S %s holds %zu lists, -N %d needs exactly %d: line i of the file is the list of source i.\n", scan_file,
+			fprintf(stderr, "-S %s holds %zu lists, -N %d needs exactly %d: line i of the file is the list of source i.\n", st.scan_file,
 			        scan_lists.size(), nstreams, nstreams);
 			usage();
 		}
@@ -1572,19 +1597,19 @@ int main(int argc, char **argv)
 		}
 	}
 	std::vector<rtlfm_monitor_rule> rules;
-	if (cmd_file) {
+	if (st.cmd_file) {
 		// src/rtl_fm.c:1738-1741: the command file implies -M raw; here its lines are the -N sources, in order
 		if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
 		rules.resize((size_t)nstreams);
 		int found = 0;
-		const int pr = rtlfm_monitor_parse_file(cmd_file, rules.data(), nstreams, &found, nullptr, nullptr);
+		const int pr = rtlfm_monitor_parse_file(st.cmd_file, rules.data(), nstreams, &found, nullptr, nullptr);
 		if (pr < 0 && pr != -ENOBUFS) {
-			fprintf(stderr, "-C %s: %s\n", cmd_file, pr == -ENOENT ? "cannot open the command file" : "no valid measurement line");
+			fprintf(stderr, "-C %s: %s\n", st.cmd_file, pr == -ENOENT ? "cannot open the command file" : "no valid measurement line");
 			usage();
 		}
 		if (found != nstreams) {
 			fprintf(stderr, "-C %s holds %d measurement lines, -N %d needs exactly %d: line i of the file is watched by source i.\n",
-			        cmd_file, found, nstreams, nstreams);
+			        st.cmd_file, found, nstreams, nstreams);
 			usage();
 		}
 		c.mode = RTLFM_MODE_RAW;
@@ -1594,49 +1619,35 @@ int main(int argc, char **argv)
 		for (const rtlfm_monitor_rule &r : rules) freqs.push_back(r.freq);
 		freq = freqs[0];
 		have_freq = true;
-		wb_mode = false;
+		st.wb_mode = false;
 	}
 	if (!have_freq) { fprintf(stderr, "Please specify a frequency.\n"); return 1; }
-	if (wb_mode) freq += 16000;  // controller_thread_fn(), src/rtl_fm.c:1455-1460: "wbfm: adding 16000 Hz to every input frequency"
-	a.conseq_squelch = conseq_squelch;
-	if (c.squelch_level) c.max_blocks = 1;  // the squelch rule below is the reference's per-buffer rule
-	if (a.print_levels > 0) { c.report_levels = 1; c.max_blocks = 1; }
-	a.user_freq = freq;  // dongle.userFreq, src/rtl_fm.c:1440
-	rate_in *= c.post_downsample;  // src/rtl_fm.c:1886
-	const char *filename = optind < argc ? argv[optind] : "-";
+	if (st.wb_mode) freq += 16000;  // controller_thread_fn(), src/rtl_fm.c:1455-1460: "wbfm: adding 16000 Hz to every input frequency"
+	if (c.squelch_level) c.max_blocks = 1;  // the squelch rule (hold_back) is the reference's per-buffer rule
+	if (st.print_levels > 0) { c.report_levels = 1; c.max_blocks = 1; }
+	st.rate_in *= c.post_downsample;  // src/rtl_fm.c:1886
+	if (optind < argc) st.filename = argv[optind];
+	const std::string pattern(st.filename);
+	const size_t at = pattern.find("%d");
+	const bool two = at != std::string::npos && pattern.find("%d", at + 2) != std::string::npos;  // more than one %d
 
 	if (nstreams < 1) { fprintf(stderr, "-N wants a number of streams >= 1.\n"); usage(); }
-	if (chan_file) {
+	if (st.chan_file) {
 		// -X: the file, the names and the plan, all before a device is opened or a GPU handle created
 		std::vector<std::vector<uint32_t>> chan_freqs;
 		std::vector<int> chan_lineno;
-		FILE *xf = fopen(chan_file, "r");
-		if (!xf) { fprintf(stderr, "-X %s: cannot open the channel file\n", chan_file); return 1; }
-		char line[65536];
-		int lineno = 0;
-		while (fgets(line, sizeof(line), xf)) {
-			lineno++;
-			const char *t = line;
-			while (*t == ' ' || *t == '\t') t++;
-			if (*t == '#' || *t == '\n' || *t == '\r' || !*t) continue;
-			int nf = 0;
-			int pr = rtlfm_scan_parse_list(t, nullptr, 0, &nf);
-			std::vector<uint32_t> fl((size_t)(nf > 0 ? nf : 0));
-			if (pr == -ENOBUFS) pr = rtlfm_scan_parse_list(t, fl.data(), nf, &nf);
-			if (pr < 0) { fclose(xf); fprintf(stderr, "-X %s: line %d is no frequency list\n", chan_file, lineno); return 1; }
-			chan_freqs.push_back(std::move(fl));
-			chan_lineno.push_back(lineno);
-		}
-		fclose(xf);
+		const int lr = read_list_file(st.chan_file, chan_freqs, &chan_lineno, &bad_line);
+		if (lr == -ENOENT) { fprintf(stderr, "-X %s: cannot open the channel file\n", st.chan_file); return 1; }
+		if (lr < 0) { fprintf(stderr, "-X %s: line %d is no frequency list\n", st.chan_file, bad_line); return 1; }
 		if ((int)chan_freqs.size() != nstreams) {
-			fprintf(stderr, "-X %s holds %zu lists, -N %d needs exactly %d: line i of the file is the channel list of source i.\n", chan_file,
+			fprintf(stderr, "-X %s holds %zu lists, -N %d needs exactly %d: line i of the file is the channel list of source i.\n", st.chan_file,
 			        chan_freqs.size(), nstreams, nstreams);
 			return 1;
 		}
 		for (size_t i = 1; i < chan_freqs.size(); i++)
 			if (chan_freqs[i].size() != chan_freqs[0].size()) {
 				fprintf(stderr, "-X %s: line %d stands for %zu channels and line %d for %zu; every source needs the same number of channels "
-				        "(-N sources share one handle).\n", chan_file, chan_lineno[i], chan_freqs[i].size(), chan_lineno[0], chan_freqs[0].size());
+				        "(-N sources share one handle).\n", st.chan_file, chan_lineno[i], chan_freqs[i].size(), chan_lineno[0], chan_freqs[0].size());
 				return 1;
 			}
 		const size_t total = chan_freqs.size() * chan_freqs[0].size();
@@ -1646,164 +1657,66 @@ int main(int argc, char **argv)
 			return 1;
 		}
 		if (freqs.size() == 1) freqs.assign((size_t)nstreams, freqs[0]);
-		const std::string pattern(filename);
-		const size_t at = pattern.find("%d");
-		if (total > 1 && (at == std::string::npos || pattern.find("%d", at + 2) != std::string::npos)) {
+		if (total > 1 && (at == std::string::npos || two)) {
 			fprintf(stderr, "-X with %zu streams: the filename must hold exactly one %%d (the stream index), e.g. out_%%d.raw.\n", total);
 			return 1;
 		}
-		if (pattern == "-" || (total == 1 && at != std::string::npos && pattern.find("%d", at + 2) != std::string::npos)) {
+		if (pattern == "-" || (total == 1 && two)) {
 			fprintf(stderr, "-X: no stdout and at most one %%d; name the files, e.g. out_%%d.raw.\n");
 			return 1;
 		}
-		if (c.deemph) c.deemph_a = rtlfm_deemph_a(c.rate_out, time_constant);
 		// one plan for all sources, as under -N; a source's capture frequency is its -f as given (no capture_rate / 4 offset,
 		// no +16 kHz under -M wbfm)
-		rtlfm_cfg planned = c;
-		uint32_t capture_rate = 0;
-		for (int i = 0; i < nstreams; i++) {
-			rtlfm_cfg ci = c;
-			uint32_t cr = 0;
-			rtlfm_optimal_settings(&ci, freqs[(size_t)i], rate_in, min_capture, fifth, edge, nullptr, &cr);
-			if (i == 0) {
-				planned = ci;
-				capture_rate = cr;
-			} else if (memcmp(&ci, &planned, sizeof(ci)) != 0 || cr != capture_rate) {
-				fprintf(stderr, "-X: the rate plan for %u Hz differs from the one for %u Hz; one handle needs one plan.\n", freqs[(size_t)i], freqs[0]);
-				return 1;
-			}
+		if (const int i = plan_for_all(st, freqs, nullptr)) {
+			fprintf(stderr, "-X: the rate plan for %u Hz differs from the one for %u Hz; one handle needs one plan.\n", freqs[(size_t)i], freqs[0]);
+			return 1;
 		}
 		for (size_t i = 0; i < chan_freqs.size(); i++)
 			for (size_t k = 0; k < chan_freqs[i].size(); k++) {
 				const int64_t off = (int64_t)chan_freqs[i][k] - (int64_t)freqs[i];
-				if (2 * (off < 0 ? -off : off) > (int64_t)capture_rate) {
+				if (2 * (off < 0 ? -off : off) > (int64_t)st.capture_rate) {
 					fprintf(stderr, "-X %s: line %d, entry %zu: %u Hz is further than capture_rate / 2 = %u Hz from the -f of source %zu, %u Hz.\n",
-					        chan_file, chan_lineno[i], k + 1, chan_freqs[i][k], capture_rate / 2, i, freqs[i]);
+					        st.chan_file, chan_lineno[i], k + 1, chan_freqs[i][k], st.capture_rate / 2, i, freqs[i]);
 					return 1;
 				}
 			}
-		return run_channels(planned, nstreams, dev_index, freqs, chan_freqs, capture_rate, gain, ppm, pattern, write_wav, a.verbosity,
-		                    conseq_squelch, a.print_levels, opt_string, agc, chan_taps > 0 ? chan_taps : 0);
+		return run_channels(st, freqs, chan_freqs);
 	}
-	int r_resume = 0;
-	if (nstreams > 1 || cmd_file || scan_file) {
+	const bool multi = nstreams > 1 || st.cmd_file || st.scan_file;
+	if (multi) {
 		// everything -N refuses is refused here, before a device is opened or a GPU handle created
-		const std::string pattern(filename);
-		const size_t at = pattern.find("%d");
 		if (freqs.size() != 1 && freqs.size() != (size_t)nstreams) {
 			fprintf(stderr, "-N %d: give -f once (every device) or %d times (one per device), not %zu times.\n", nstreams,
 			        nstreams, freqs.size());
 			usage();
 		}
 		if (pattern == "-") { fprintf(stderr, "-N %d: no stdout; name the files, e.g. out_%%d.raw.\n", nstreams); usage(); }
-		if (nstreams == 1 && scan_file && at == std::string::npos) {
+		if (nstreams == 1 && st.scan_file && at == std::string::npos) {
 			// one source: the name as it is
-		} else if (at == std::string::npos || pattern.find("%d", at + 2) != std::string::npos) {
+		} else if (at == std::string::npos || two) {
 			fprintf(stderr, "-N %d: the filename must hold exactly one %%d (the stream index), e.g. out_%%d.raw.\n", nstreams);
 			usage();
 		}
-		if (a.zero_copy) {
+		if (st.zero_copy) {
 			// -Z writes a device's buffer straight into the ring, but with -N the ring is filled from the host
 			// queues (run_multi): there is no slot a device could own
 			fprintf(stderr, "-Z (zero-copy) works with one stream only, not with -N %d.\n", nstreams);
 			usage();
 		}
 		if (freqs.size() == 1) freqs.assign((size_t)nstreams, freqs[0]);
-		if (wb_mode)
+		if (st.wb_mode)
 			for (uint32_t &f : freqs) f += 16000;  // the -M wbfm rule above, for every device
-		if (c.deemph) c.deemph_a = rtlfm_deemph_a(c.rate_out, time_constant);
-		// one plan for all streams: optimal_settings() must not depend on the frequency for what this CLI accepts
-		rtlfm_cfg planned = c;
-		std::vector<uint32_t> capture_freqs((size_t)nstreams);
-		uint32_t capture_rate = 0;
-		for (int i = 0; i < nstreams; i++) {
-			rtlfm_cfg ci = c;
-			uint32_t cr = 0;
-			rtlfm_optimal_settings(&ci, freqs[i], rate_in, min_capture, fifth, edge, &capture_freqs[i], &cr);
-			if (i == 0) {
-				planned = ci;
-				capture_rate = cr;
-			} else if (memcmp(&ci, &planned, sizeof(ci)) != 0 || cr != capture_rate) {
-				fprintf(stderr, "-N: the rate plan for %u Hz differs from the one for %u Hz; one handle needs one plan.\n",
-				        freqs[i], freqs[0]);
-				return 1;
-			}
-		}
-		if (resume_file && (r_resume = check_resume(resume_file, planned, nstreams)) != 0) return r_resume;
-		return run_multi(planned, nstreams, dev_index, freqs, capture_freqs, capture_rate, gain, ppm, pattern, write_wav,
-		                 a.verbosity, conseq_squelch, a.print_levels, rules, opt_string, agc, scan_lists, wb_mode, rate_in, min_capture,
-		                 fifth, edge, keep_file, resume_file);
+	} else {
+		freqs.assign(1, freq);  // one source: the last -f
 	}
-
-	if (resume_file) {
-		// the plan the handle will be created with, before a device is opened (optimal_settings() and deemph_a are host arithmetic)
-		rtlfm_cfg planned = c;
-		if (planned.deemph) planned.deemph_a = rtlfm_deemph_a(planned.rate_out, time_constant);
-		rtlfm_optimal_settings(&planned, freq, rate_in, min_capture, fifth, edge, nullptr, nullptr);
-		if ((r_resume = check_resume(resume_file, planned, 1)) != 0) return r_resume;
+	// the plan the handle will be created with, and -R's file against it, before a device is opened (optimal_settings() and
+	// deemph_a are host arithmetic)
+	std::vector<uint32_t> capture_freqs;
+	if (const int i = plan_for_all(st, freqs, &capture_freqs)) {
+		fprintf(stderr, "-N: the rate plan for %u Hz differs from the one for %u Hz; one handle needs one plan.\n", freqs[(size_t)i], freqs[0]);
+		return 1;
 	}
-	if (rtlsdr_get_device_count() == 0) { fprintf(stderr, "No supported devices found (set RTLSDR_FILE).\n"); return 1; }
-	if (rtlsdr_open(&a.dev, (uint32_t)dev_index) < 0) { fprintf(stderr, "Failed to open rtlsdr device #%d.\n", dev_index); return 1; }
-	if (c.deemph) c.deemph_a = rtlfm_deemph_a(c.rate_out, time_constant);
-	uint32_t capture_freq = 0, capture_rate = 0;
-	rtlfm_optimal_settings(&c, freq, rate_in, min_capture, fifth, edge, &capture_freq, &capture_rate);
-	if (gain == -100) rtlsdr_set_tuner_gain_mode(a.dev, 0);
-	else { rtlsdr_set_tuner_gain_mode(a.dev, 1); rtlsdr_set_tuner_gain(a.dev, gain); }
-	if (opt_string) rtlsdr_set_opt_string(a.dev, opt_string, a.verbosity);
-	if (agc >= 0) rtlsdr_set_tuner_gain_mode(a.dev, agc);  // the string's agc=<tuner_gain_mode>, src/librtlsdr.c:3166-3171
-	rtlsdr_set_freq_correction_ppb(a.dev, ppm * 1000);
-	rtlsdr_set_offset_tuning(a.dev, c.offset_tuning);
-	rtlsdr_set_center_freq(a.dev, capture_freq);
-	if (rtlsdr_set_sample_rate(a.dev, capture_rate) < 0)
-		fprintf(stderr, "WARNING: capture rate %u Hz is outside what an RTL2832 can do.\n", capture_rate);
-	fprintf(stderr, "Tuned to %u Hz.\nOversampling input by: %ix.\nSampling at %u S/s.\nOutput at %u Hz.\n", capture_freq,
-	        c.downsample, capture_rate, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out));
-	if (a.verbosity)
-		fprintf(stderr, "downsample_passes = %d, downsample = %d, deemph_a = %d, buffer = %u B\n", c.downsample_passes,
-		        c.downsample, c.deemph_a, c.block_len);
-
-	int r = rtlfm_gpu_create(&c, 1, 0, &a.gpu);
-	if (r < 0) { fprintf(stderr, "rtlfm_gpu_create: %s\n", rtlfm_gpu_strerror(r)); return 2; }
-	if (resume_file && (r = rtlfm_gpu_load(a.gpu, resume_file)) < 0) { fprintf(stderr, "-R %s: %s\n", resume_file, rtlfm_gpu_strerror(r)); return 2; }
-	a.keep_file = keep_file;
-	if (c.squelch_level) {
-		// -l: demod_thread_fn's rule on the device where the configuration has a gate (not behind a resampler)
-		r = rtlfm_gpu_set_option(a.gpu, "conseq_squelch", conseq_squelch);
-		if (r == 0) r = rtlfm_gpu_set_option(a.gpu, "squelch_gate", 1);
-		a.use_gate = r == 0;
-		if (r < 0 && r != -ENOTSUP) { fprintf(stderr, "squelch_gate: %s\n", rtlfm_gpu_strerror(r)); return 2; }
-	}
-	if (agc == 2) {
-		r = rtlfm_gpu_set_option(a.gpu, "input_health", 1);
-		if (r == 0) r = health_create(&a.hl, {a.dev}, c.max_blocks, a.verbosity);
-		if (r < 0) { fprintf(stderr, "rtlfm_agc_create: %s\n", rtlfm_gpu_strerror(r)); return 2; }
-	}
-	a.file = !strcmp(filename, "-") ? stdout : fopen(filename, "wb");
-	if (!a.file) { fprintf(stderr, "Failed to open %s\n", filename); return 1; }
-	if (write_wav && a.file != stdout)  // src/rtl_fm.c:1990-1995
-		rtlamd_wave_write_header(&a.wave, (unsigned)(c.rate_out2 > 0 ? c.rate_out2 : c.rate_out), freq, 16,
-		                         c.mode == RTLFM_MODE_RAW ? 2 : 1, a.file);
-	rtlsdr_reset_buffer(a.dev);
-
-	std::thread t_out(output_thread, &a), t_demod(demod_thread, &a), t_dongle(dongle_thread, &a);
-	t_dongle.join();
-	t_demod.join();
-	t_out.join();
-	if (a.file != stdout) {
-		if (write_wav) rtlamd_wave_finalize(&a.wave, a.file);  // src/rtl_fm.c:2041-2045
-		fclose(a.file);
-	}
-	fprintf(stderr, "%llu buffers in, %llu samples out, %llu buffers held back by the squelch%s\n", (unsigned long long)a.blocks_in,
-	        (unsigned long long)a.samples_out, (unsigned long long)a.blocks_squelched, a.p.failed ? " (FAILED)" : "");
-	if (a.hl.agc) {
-		health_report(&a.hl);
-		rtlfm_agc_destroy(a.hl.agc);
-	}
-	if (a.keep_file && !a.p.failed && (r = rtlfm_gpu_save(a.gpu, a.keep_file)) < 0) {  // behind the last run
-		fprintf(stderr, "-K %s: %s\n", a.keep_file, rtlfm_gpu_strerror(r));
-		a.p.failed = true;
-	}
-	rtlfm_gpu_destroy(a.gpu);
-	rtlsdr_close(a.dev);
-	return a.p.failed ? 3 : 0;
+	if (st.resume_file)
+		if (const int r = check_resume(st.resume_file, c, nstreams)) return r;
+	return multi ? run_multi(st, freqs, capture_freqs, rules, scan_lists) : run_single(st, freq, capture_freqs[0]);
 }

@@ -164,3 +164,84 @@ def test_squelch_holds_back_per_channel(oracle_lib, tmp_path):
         assert_row_cfg(out_file(tmp_path, c), want, cfg, f"channel {c}")
     assert 8 < helds[0] < nb - 8 and helds[1] == nb, helds
     assert f"{nb} buffers in" in r.stderr and f"{sum(helds)} buffers held back" in r.stderr
+
+
+def keyed_carriers(nb, L, rate, windows, seed):
+    """nb buffers of L bytes: noise of one LSB and, for each (offset Hz, first, last) of windows, an FM carrier of amplitude 40
+    at that offset from the centre in buffers first .. last-1."""
+    n = np.arange(nb * L // 2, dtype=np.float64)
+    sig = np.zeros(n.size, dtype=np.complex128)
+    for off, first, last in windows:
+        on = ((n >= first * L // 2) & (n < last * L // 2)).astype(np.float64)
+        sig += 40.0 * on * np.exp(1j * (2 * np.pi * off * n / rate + (2500.0 / 1000.0) * np.sin(2 * np.pi * 1000.0 * n / rate)))
+    rng = np.random.default_rng(seed)
+    src = np.empty(nb * L, dtype=np.uint8)
+    src[0::2] = np.rint(127 + sig.real + rng.integers(-1, 2, n.size)).astype(np.uint8)
+    src[1::2] = np.rint(127 + sig.imag + rng.integers(-1, 2, n.size)).astype(np.uint8)
+    return src
+
+
+def held_back_per_channel(oracle_lib, cfg, rate, src, offsets, L, t):
+    """demod_thread_fn's rule (src/rtl_fm.c:1366-1370) over each channel's own buffers of one source: [(PCM, buffers held)]."""
+    steps = [cm.step_from_hz(off, rate) for off in offsets]
+    by = cm.mixed_bytes(src[None, :], steps, len(steps), 0)
+    ocfg = cm.copy_cfg(cfg, offset_tuning=1)
+    lib = oracle_lib.oracle()
+    scratch = np.zeros(L, dtype=np.int16)
+    res = []
+    for c in range(len(steps)):
+        st = oracle_lib.new_states(1)[0]
+        want, held = [np.zeros(0, dtype=np.int16)], 0
+        for b in range(src.size // L):
+            k = lib.orc_block(C.byref(ocfg), C.byref(st), np.ascontiguousarray(by[c, b * L:(b + 1) * L]), L, scratch)
+            if st.squelch_hits > t:
+                st.squelch_hits = t + 1
+                held += 1
+                continue
+            want.append(scratch[:k].copy())
+        res.append((np.concatenate(want), held))
+    return res
+
+
+OFFSETS = (96000, -192000)
+
+
+def squelch_two_sources_case(oracle_lib):
+    """-s 24k -l 100 -t 3 -W 4, two sources x two channels 96 kHz above and 192 kHz below each -f: (cfg, rate, L, t, captures).
+    Source 0, 9 buffers: carriers in buffers 2 .. 3 and 4 .. 6; source 1, 4 buffers: carriers in 1 .. 2 and 2 .. 3.  A
+    channel is silent until its carrier comes (squelch_hits starts at 11) and again from the fourth buffer the squelch finds
+    closed; the buffer behind a carrier still opens it (the boxcar's sum across the boundary).  By the oracle the four
+    streams hold 3 (buffers 0, 1, 8), 4 (0 .. 3), 1 and 2 buffers."""
+    L, t = 2048, 3
+    cfg, rate = plan(oracle_lib, 24000, rate_out=24000, squelch_level=100, block_len=L)
+    assert rate == 1008000
+    return cfg, rate, L, t, [keyed_carriers(9, L, rate, ((OFFSETS[0], 2, 4), (OFFSETS[1], 4, 7)), 7),
+                             keyed_carriers(4, L, rate, ((OFFSETS[0], 1, 3), (OFFSETS[1], 2, 4)), 8)]
+
+
+def test_squelch_per_channel_when_a_source_ends(oracle_lib, tmp_path):
+    """-N 2 -X, two channels each, -l 100 -t 3: source 1 ends after 4 of source 0's 9 buffers and is fed bytes 127 from
+    then on.  Its two files stop growing and its counters stop - each is the hold-back rule over its channel's 4 buffers -,
+    and the files and counts of source 0 are the rule over its own 9 buffers."""
+    cfg, rate, L, t, data = squelch_two_sources_case(oracle_lib)
+    f_src = (100000000, 200000000)
+    (tmp_path / "chan.txt").write_text("".join(" ".join(str(f + off) for off in OFFSETS) + "\n" for f in f_src))
+    srcs = []
+    for i, x in enumerate(data):
+        p = tmp_path / f"in_{i}.bin"
+        x.tofile(p)
+        srcs.append(p)
+    r = run_cli(tmp_path, srcs, ["-N", "2", "-f", "100M", "-f", "200M", "-X", str(tmp_path / "chan.txt"), "-s", "24k", "-l", "100", "-t", str(t),
+                                 "-W", "4", "-v", str(tmp_path / "out_%d.raw")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    total, samples = 0, 0
+    for i, x in enumerate(data):
+        nb = x.size // L
+        for c, (want, held) in enumerate(held_back_per_channel(oracle_lib, cfg, rate, x, OFFSETS, L, t)):
+            s = 2 * i + c
+            total += held
+            samples += want.size
+            assert 0 < held < nb and want.size > 0, (s, held)
+            assert f"stream {s}: {want.size} samples out, {held} buffers held back" in r.stderr, (s, held, r.stderr[-1500:])
+            assert_row_cfg(out_file(tmp_path, s), want, cfg, f"source {i} channel {c}")
+    assert f"13 buffers in, {samples} samples out, {total} buffers held back by the squelch" in r.stderr, r.stderr[-1500:]

@@ -191,6 +191,67 @@ def test_squelch_per_stream(oracle_lib, tmp_path):
     assert f"{n * nb} buffers in, " in r.stderr and f"{total_held} buffers held back" in r.stderr
 
 
+def _keyed(seed, L, nb, first, last, fs):
+    """nb buffers of L bytes: noise of one LSB, and an FM signal in buffers first .. last-1."""
+    sig = synth.fm_iq_u8(1, L // 2 * nb, fs=fs, dev_hz=2.5e3, amplitude=60.0, seed=seed)[0].reshape(nb, L)
+    quiet = synth.fm_iq_u8(1, L // 2 * nb, fs=fs, dev_hz=2.5e3, amplitude=0.0, noise_lsb=1, seed=seed + 1)[0].reshape(nb, L)
+    return np.concatenate([quiet[:first], sig[first:last], quiet[last:]]).ravel()
+
+
+def _held_back(oracle_lib, cfg, iq, L, t):
+    """demod_thread_fn's rule (src/rtl_fm.c:1366-1370) over the oracle's per-buffer outputs: (the PCM, buffers held)."""
+    lib = oracle_lib.oracle()
+    st = oracle_lib.new_states(1)[0]
+    scratch = np.zeros(L, dtype=np.int16)
+    want, held = [np.zeros(0, dtype=np.int16)], 0
+    for b in range(iq.size // L):
+        k = lib.orc_block(C.byref(cfg), C.byref(st), np.ascontiguousarray(iq[b * L:(b + 1) * L]), L, scratch)
+        if st.squelch_hits > t:
+            st.squelch_hits = t + 1
+            held += 1
+            continue
+        want.append(scratch[:k].copy())
+    return np.concatenate(want), held
+
+
+def squelch_behind_resampler_case(oracle_lib):
+    """-s 96k -r 32k -A fast -l 40 -t 3 -W 4 (/11 at 1 056 000 S/s, which does not divide a buffer's 1024 samples; rtl_fm's
+    low_pass_real wants -r below -s): (cfg, L, t, the two captures).  Source 0: 9 buffers, signal in 2 and 3; source 1: 4
+    buffers, signal in 1 and 2.  A stream is silent until its signal comes (squelch_hits starts at 11) and again from the
+    fourth buffer the squelch finds closed: by the oracle, source 0 holds 4 of its 9 buffers and source 1 one of its 4."""
+    L, t = 2048, 3
+    cfg = RtlfmCfg.default(rate_out=96000, rate_out2=32000, custom_atan=ATAN_FAST, squelch_level=40, block_len=L)
+    cf, cr = C.c_uint32(), C.c_uint32()
+    oracle_lib.oracle().orc_optimal_settings(C.byref(cfg), 100000000, 96000, 1000000, 0, 0, C.byref(cf), C.byref(cr))
+    assert cr.value == 1056000 and cfg.downsample == 11
+    return cfg, L, t, [_keyed(31, L, 9, 2, 4, 1.056e6), _keyed(41, L, 4, 1, 3, 1.056e6)]
+
+
+def test_squelch_behind_a_resampler_across_a_shrink(oracle_lib, tmp_path):
+    """-N 2 -l 40 -t 3 -r 32k: behind the resampler the handle has no squelch gate (-ENOTSUP), so the hold-back rule runs
+    from the carried state (rtlfm_gpu_state_get_all / _set_all), stream k of the handle for source live[k].  Source 1 ends
+    after 4 of source 0's 9 buffers: the rule goes on over source 0 on the handle it moved to."""
+    cfg, L, t, iq = squelch_behind_resampler_case(oracle_lib)
+    srcs = []
+    for i, x in enumerate(iq):
+        p = tmp_path / f"in_{i}.bin"
+        x.tofile(p)
+        srcs.append(p)
+    r = _run(tmp_path, srcs, ["-N", "2", "-v", "-f", "100M", "-s", "96k", "-r", "32k", "-A", "fast", "-l", "40", "-t", str(t), "-W", "4",
+                              str(tmp_path / "out_%d.raw")])
+    assert r.returncode == 0, r.stderr[-1500:]
+    assert "1 of 2 streams go on" in r.stderr, r.stderr[-1500:]
+    total = 0
+    for i, x in enumerate(iq):
+        nb = x.size // L
+        want, held = _held_back(oracle_lib, cfg, x, L, t)
+        total += held
+        assert 0 < held < nb and want.size > 0, (i, held)
+        assert f"stream {i}: {nb} buffers in, {want.size} samples out, {held} buffers held back" in r.stderr, (i, held, r.stderr[-1500:])
+        _close(cfg, np.fromfile(tmp_path / f"out_{i}.raw", dtype=np.int16), want, i)
+    assert "13 buffers in, " in r.stderr and f" samples out, {total} buffers held back by the squelch" in r.stderr
+
+
 def test_levels_per_stream(oracle_lib, tmp_path):
     """-L with 4 streams, each tuned to its own -f: every stream's level lines (prefixed 'stream i: ') are
     full_demod()'s bookkeeping over that stream's rms() values."""
