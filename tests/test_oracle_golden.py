@@ -192,6 +192,80 @@ def test_oracle_vs_live_reference_on_buffers_the_passes_do_not_divide(oracle_lib
     assert gu.state_dict(st) == gu.state_dict(rst), (kind, passes, L)
 
 
+FULL_SCALE_FRONTS = [(f"p{p}{'fir' if fir else ''}", dict(downsample=1 << p, downsample_passes=p, comp_fir_size=fir))
+                     for p in (1, 2, 3, 4, 5, 6, 7, 8, 10) for fir in (0, 9)] + \
+                    [(f"box{D}", dict(downsample=D, downsample_passes=0)) for D in (1, 2, 5, 6, 10, 64, 84, 255, 256, 257, 334, 1000)]
+FULL_SCALE_BACKS = [
+    ("std", dict(custom_atan=capi.ATAN_STD)), ("fast", dict(custom_atan=capi.ATAN_FAST)), ("lut", dict(custom_atan=capi.ATAN_LUT)),
+    ("am", dict(mode=capi.MODE_AM)), ("usb", dict(mode=capi.MODE_USB)), ("lsb", dict(mode=capi.MODE_LSB)), ("raw", dict(mode=capi.MODE_RAW)),
+    ("fast_deemph13", dict(custom_atan=capi.ATAN_FAST, deemph=1, deemph_a=13)),
+    ("lut_dc", dict(custom_atan=capi.ATAN_LUT, dc_block_audio=1)), ("lut_rdc", dict(custom_atan=capi.ATAN_LUT, dc_block_raw=1)),
+    ("lut_offset", dict(custom_atan=capi.ATAN_LUT, offset_tuning=1)), ("lut_squelch50", dict(custom_atan=capi.ATAN_LUT, squelch_level=50)),
+    ("std_lpr_48000_11025", dict(custom_atan=capi.ATAN_STD, rate_out=48000, rate_out2=11025, resampler=capi.RESAMPLE_LOW_PASS_REAL)),
+    ("lut_arb_16000_22050", dict(custom_atan=capi.ATAN_LUT, rate_out=16000, rate_out2=22050, resampler=capi.RESAMPLE_ARBITRARY)),
+    ("am_dc", dict(mode=capi.MODE_AM, dc_block_audio=1)),
+]
+
+
+def _full_scale_inputs(n):
+    """Bytes that drive every stage to its int16 / int32 limits: (name, uint8 [n])."""
+    rng = np.random.default_rng(255)
+    at = np.arange(n)
+    return [("random", rng.integers(0, 256, n, dtype=np.uint8)),
+            ("alternating", np.where(at % 2 == 0, 255, 0).astype(np.uint8)),  # I = +128, Q = -127 throughout
+            ("corners", rng.choice(np.array([0, 1, 127, 128, 254, 255], np.uint8), n)),
+            ("square64", np.where(at // 32 % 2 == 0, 255, 0).astype(np.uint8))]  # 16 samples at one corner, 16 at the opposite
+
+
+@pytest.mark.parametrize("front,fov", FULL_SCALE_FRONTS, ids=[f for f, _ in FULL_SCALE_FRONTS])
+def test_oracle_vs_live_reference_at_full_scale(oracle_lib, front, fov):
+    """The restatement against the reference's own full_demod() where the GPU suite trusts it most and the other
+    comparisons here never go: full-scale bytes, at which the boxcar's int16 store, fifth_order, generic_fir,
+    polar_disc_fast's 4096 * (x -/+ |y|), am_demod's (int16_t)sqrt above 32767 and polar_disc_lut's index all wrap.
+    Every front end of the grid behind every discriminator, mode and audio stage, four inputs: every output sample and
+    the complete carried state, exact (`-A std` shares the libm).  This is what pins the oracle's spelling of those
+    wraps to the reference's (gcc) behaviour.  The record keeps a SHA-256 of each output, its length and the state;
+    with the live reference the arrays themselves are compared, so a failure names the first sample."""
+    import hashlib
+    po = oracle_lib
+    L = 16384
+    while (L // 2) >> fov["downsample_passes"] < 8:
+        L *= 2
+    inputs = _full_scale_inputs(3 * L)
+    live = po.have_reference()
+    names, mine, theirs = [], [], []
+    for iname, iq in inputs:
+        for bname, bov in FULL_SCALE_BACKS:
+            what = f"{front}/{bname}/{iname}"
+            cfg = make_cfg(dict(fov, **bov), L)
+            got, st = po.run_stream(cfg, iq)
+            names.append(what)
+            mine.append((hashlib.sha256(got.tobytes()).digest(), len(got), st))
+            if not live:
+                continue
+            ref = po.Reference()
+            try:
+                want, rst = ref.run_stream(cfg, iq)
+            finally:
+                ref.close()
+            assert len(got) == len(want), (what, len(got), len(want))
+            bad = np.flatnonzero(got != want)
+            assert bad.size == 0, f"{what}: {bad.size} of {len(got)} samples differ, first at {bad[0]}: oracle {got[bad[0]]}, reference {want[bad[0]]}"
+            assert gu.state_dict(st) == gu.state_dict(rst), what
+            theirs.append((hashlib.sha256(want.tobytes()).digest(), len(want), rst))
+    rec = rr.result(live, f"oracle_golden/full_scale/{front}",
+                    lambda: {"sha256": np.frombuffer(b"".join(t[0] for t in theirs), np.uint8).reshape(-1, 32),
+                             "len": np.array([t[1] for t in theirs], np.int32),
+                             "state": np.frombuffer(b"".join(bytes(t[2]) for t in theirs), np.uint8).reshape(len(theirs), -1)},
+                    (L, names) + tuple(iq for _, iq in inputs))
+    assert len(rec["len"]) == len(names) == len(FULL_SCALE_BACKS) * 4
+    for i, what in enumerate(names):
+        sha, n, st = mine[i]
+        assert n == int(rec["len"][i]), (what, n, int(rec["len"][i]))
+        assert sha == rec["sha256"][i].tobytes(), f"{what}: the output differs from the reference's recorded one"
+        assert gu.state_dict(st) == gu.state_dict(capi.RtlfmStreamState.from_buffer_copy(rec["state"][i].tobytes())), what
+
+
 def test_batch_threads_equal_serial(oracle_lib):
     ov, sig = CASES[1][1], CASES[1][2]
     cfg = make_cfg(ov, 2048)

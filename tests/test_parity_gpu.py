@@ -252,8 +252,9 @@ def test_fused_fullscale_random_bytes(oracle_lib, engine):
 def test_fullscale_random_bytes_std_and_fast_end_to_end(oracle_lib, front, atan):
     """Full-scale random bytes through the one-launch front ends WITH `-A std` and `-A fast`, end to
     end: at this amplitude polar_disc_fast's 4096 * (x -/+ |y|) wraps in 32 bits (src/rtl_fm.c:851-872;
-    the oracle spells the wrap out as the gcc build of the reference behaves, pinned per function by
-    test_fast_atan2_against_oracle) and the conjugate products of polar_discriminant reach 2 * 2^30.
+    the oracle spells the wrap out as the gcc build of the reference behaves - pinned to the reference itself by
+    test_oracle_vs_live_reference_at_full_scale, tests/test_oracle_golden.py; test_fast_atan2_against_oracle compares
+    the kernel's function with the oracle's) and the conjugate products of polar_discriminant reach 2 * 2^30.
     k_fused / k_boxcar_scan must agree sample for sample, and so must the carried state."""
     if front.startswith("box"):
         D = int(front[3:])
