@@ -350,6 +350,56 @@ int rtlfm_gpu_mute(rtlfm_gpu *h, int stream, uint32_t nbytes);
 int rtlfm_gpu_mute_device(int device, uint8_t *d_iq, size_t stream_stride, int nstreams, size_t row_bytes,
                           const uint32_t *mute_bytes, void *hip_stream);
 
+/*
+ * Packed results (csrc/pack_kernel.h): fetch what the streams hold, not max(lens) x nstreams.
+ *
+ * rtlfm_gpu_fetch_all / _fetch_all_prev copy a rectangle as wide as the longest row.  With the option "pack_results"
+ * at 1 or 2 every ring run (rtlfm_gpu_run / _run_end) ends with two more launches on the handle's stream - k_pack_plan
+ * and k_pack_copy, behind the run's last kernel, behind its audio tail where it left one and behind the squelch gate
+ * where that is on (under verify_twice once, behind the comparison) - which write every stream's row, one behind the
+ * other, into a packed buffer of the ring half the run used, and an index of it.  Both are allocated on first use,
+ * sized for the worst case, and freed with the handle or when the option goes back to 0.  The pack is read-only towards
+ * the run: rows, lengths, levels and the carried state are not written, and rtlfm_gpu_fetch / _fetch_all /
+ * _fetch_all_prev return what they return without it.  With 0 (default) nothing is launched and nothing allocated.
+ *
+ *   rtlfm_packed_row   offset: where the row starts, in int16 from the start of the packed buffer, always a multiple
+ *                      of 8 (a 16-byte boundary; an empty row: where the next one starts); len: its samples; held: buffers
+ *                      of this run the rule left out (mode 2; 0 in mode 1).  The elements between a row's last sample and
+ *                      the next row's start are 0: the packed form of a run is the same byte for byte every time.
+ *
+ *   mode 1   a row's packed length is its result length (what rtlfm_gpu_fetch_all writes to lens): every
+ *            configuration, every path, ragged runs, with or without "squelch_gate", with channels on.
+ *   mode 2   additionally every buffer the reference's demod thread would not hand to its output thread is left out
+ *            (demod_thread_fn, src/rtl_fm.c:1366-1370: held while squelch_hits > conseq_squelch, the counter then kept at
+ *            conseq_squelch + 1).  The counter moves as full_demod() moves it (:1206-1213: a level below the squelch
+ *            adds one, any other zeroes it, a negative level changes nothing), so "hits > conseq" holds for exactly the
+ *            same buffers whether or not the CARRIED counter was ever clamped: the walk starts from the squelch_hits
+ *            the run started from and clamps a local copy only.  It reads the run's levels (rtlfm_gpu_levels),
+ *            cfg.squelch_level and the option "conseq_squelch"; buffer b's extent in its row is the one the squelch of
+ *            that run used (the gate's).  This is the squelch gate's output without its writes: allowed with channels
+ *            on, with every channel front end and on both paths, where "squelch_gate" is refused.
+ *            Refused, the option then staying what it was: -EINVAL without a squelch (cfg.squelch_level == 0) and while
+ *            "squelch_gate" is on (and "squelch_gate" while mode 2 is on: the rows would already be compacted);
+ *            -ENOTSUP behind a resampler, post_downsample > 1 or a buffer the fifth_order passes do not divide (as
+ *            "squelch_gate").  A ragged run in mode 2: -ENOTSUP from rtlfm_gpu_run_begin, nothing is taken.
+ *   Setting the option: -EBUSY while a run is begun and not ended; -EINVAL for values other than 0, 1, 2.
+ *
+ * rtlfm_gpu_fetch_packed / _fetch_packed_prev wait exactly as rtlfm_gpu_fetch_all / _fetch_all_prev do (_prev for that
+ * run only), copy the index (nstreams records) and then *total int16 in ONE transfer.  *total is the sum of the rows'
+ * lengths each rounded up to 8.  -ENODATA when that run was not packed (the option was off when it ran); -ENOBUFS with
+ * *total set when cap < *total (out is then untouched; rows has been written); -EAGAIN as their unpacked twins.
+ *
+ * rtlfm_gpu_pack_device: the mode-1 operator without a handle, as the other *_device entry points asynchronous on
+ * hip_stream (NULL = the default stream).  Row s is d_lens[s] (negative: 0) int16 at d_rows + s * stride, any int16
+ * alignment; d_packed is 16-byte aligned and holds cap int16; d_index [nstreams]; *d_total is always the full need, also
+ * when it exceeds cap - nothing at or beyond cap is then written, and the caller sees the need from the total.
+ */
+typedef struct { uint64_t offset; int32_t len; int32_t held; } rtlfm_packed_row;   /* 16 bytes */
+int rtlfm_gpu_fetch_packed(rtlfm_gpu *h, int16_t *out, size_t cap, rtlfm_packed_row *rows /* [nstreams] */, size_t *total);
+int rtlfm_gpu_fetch_packed_prev(rtlfm_gpu *h, int16_t *out, size_t cap, rtlfm_packed_row *rows, size_t *total);
+int rtlfm_gpu_pack_device(int device, const int16_t *d_rows, size_t stride, const int32_t *d_lens, int nstreams,
+                          int16_t *d_packed, size_t cap, rtlfm_packed_row *d_index, uint64_t *d_total, void *hip_stream);
+
 int rtlfm_gpu_state_get(rtlfm_gpu *h, int stream, rtlfm_stream_state *st);
 int rtlfm_gpu_state_set(rtlfm_gpu *h, int stream, const rtlfm_stream_state *st);
 /* demod_init() values for every stream. */
@@ -632,7 +682,10 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        allocated; anything but 0 / 1 -EINVAL).  Needs cfg.squelch_level != 0 (-EINVAL); -ENOTSUP with a
  *                        resampler (rate_out2 > 0), post_downsample > 1, or a buffer the fifth_order passes do not divide
  *   conseq_squelch       the demod thread's limit (default 10, demod_init, src/rtl_fm.c:1613; < 0 -EINVAL)
+ *   pack_results         0 (default) / 1 / 2: every ring run also leaves its results packed (see rtlfm_gpu_fetch_packed)
  * Read-only (rtlfm_gpu_get_option):
+ *   pack_us              device time of the last run's two pack launches in microseconds (waits for them); -1 when that
+ *                        run was not packed or rtlfm_gpu_timing_enable was off
  *   verify_runs         runs executed under verify_twice so far, and
  *   verify_mismatches    ... how many of them differed between their two executions
  *   block_len            the buffer length the handle was created with

@@ -158,6 +158,16 @@ class RtlfmGateRec(C.Structure):
 GATE_REC_DTYPE = [("hits_after", "<i4"), ("emit", "u1"), ("pad", "u1", (3,))]
 
 
+class RtlfmPackedRow(C.Structure):
+    """``rtlfm_packed_row`` — where one stream's row lies in a packed result buffer (include/rtlfm_hip.h)."""
+
+    _fields_ = [("offset", C.c_uint64), ("len", C.c_int32), ("held", C.c_int32)]
+
+
+# ... as a numpy dtype (GpuDemod.fetch_packed and pack_device return arrays of it)
+PACKED_ROW = [("offset", "<u8"), ("len", "<i4"), ("held", "<i4")]
+
+
 class RtlfmScanEvent(C.Structure):
     """``rtlfm_scan_event`` — one hop of a stream (include/rtlfm_scan.h)."""
 
@@ -305,6 +315,10 @@ _SIGNATURES = [
     ("rtlfm_gpu_gate_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_mute", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     ("rtlfm_gpu_mute_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("rtlfm_gpu_fetch_packed", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, _P(C.c_size_t)]),
+    ("rtlfm_gpu_fetch_packed_prev", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, _P(C.c_size_t)]),
+    ("rtlfm_gpu_pack_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     ("rtlfm_gpu_state_get", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_state_set", C.c_int, [C.c_void_p, C.c_int, _P(RtlfmStreamState)]),
     ("rtlfm_gpu_reset", C.c_int, [C.c_void_p]),

@@ -49,7 +49,9 @@
 // output is a deterministic function of the input files.  -v prints every hop, the hop counts are printed at exit.
 //
 // -l / -t hold the output back as demod_thread_fn does (:1366-1370): on the device (squelch_gate / conseq_squelch) where
-// the configuration has a gate, else per stream through the carried state.  -L prints full_demod()'s level lines.
+// the configuration has a gate, else per stream through the carried state.  Behind the device gate under -N, and under -X
+// (where the library refuses the gate: there the rule itself runs as option pack_results 2), only what the squelch let
+// through comes back from the device (rtlfm_gpu_fetch_packed).  -L prints full_demod()'s level lines.
 //
 // -K file / -R file (not reference letters): keep and resume.  -K writes every stream's carried state (the persisting
 // fields of struct demod_state, src/rtl_fm.c:172-208; include/rtlfm_snapshot.h) at exit, behind the last run; -R loads
@@ -69,7 +71,8 @@
 // rtlfm_gpu_set_channels), and a channel further than capture_rate / 2 from its source's -f is refused.  The rate plan is
 // optimal_settings()' as under -N; -m chooses the capture rate.  ONE handle of n x K streams with the library's option
 // source_ring, so that the ring has a row per SOURCE: handle stream s = channel s % K of source s / K writes the file
-// with %d = s; -H, -L ("stream s:") and -l work per stream as under -N without the device gate.  -x ntaps puts the channel
+// with %d = s; -H, -L ("stream s:") and -l work per stream (-l: the library's option pack_results 2 applies the rule and
+// counts what it held; hold_back only where that is refused, behind a resampler).  -x ntaps puts the channel
 // filter rtlfm_channel_lowpass(ntaps, 0.4 / D, D) in the boxcar's place (not with -F: the filter stands where the boxcar
 // stands; where its taps do not fit an int16 - fewer taps than D needs - the same filter at D / 2^k and shift 14 - k).
 // The demod thread pushes the same number of buffers for every source and run (demod_thread_channels below); the
@@ -729,10 +732,12 @@ struct Source {
 };
 
 struct RunOut {
-	std::vector<int16_t> pcm;  // handle stream k at k * stride
+	std::vector<int16_t> pcm;  // handle stream k at k * stride - or, fetched packed, at at[k]
 	std::vector<int32_t> lens;
 	std::vector<int> who;      // handle stream k -> output
 	size_t stride = 0;
+	std::vector<size_t> at;    // rtlfm_gpu_fetch_packed: where stream k's samples start (empty: rows of `stride`)
+	std::vector<int32_t> held; // ... and how many of its buffers the rule left out (option pack_results 2)
 };
 
 struct Multi {
@@ -760,6 +765,7 @@ struct Multi {
 	std::vector<int> live;                   // handle stream k -> source, as the demod thread left it
 	std::vector<rtlfm_stream_state> states;  // one rtlfm_gpu_state_get_all: -l without a device gate, -K
 	int chan_per = 0;                        // -X: K channels per source
+	bool packed = false;                     // the handle runs with option pack_results: rtlfm_gpu_fetch_packed brings the PCM
 	explicit Multi(const Settings &s, size_t sources, size_t outputs) : st(s), src(sources), out(outputs), depth(2 * s.cfg.max_blocks) {}
 };
 
@@ -771,6 +777,9 @@ int handle_options(Multi *m, rtlfm_gpu *h)
 	if (m->mon) r = rtlfm_gpu_set_option(h, "input_stats", 1);
 	if (r == 0 && m->hl.agc) r = rtlfm_gpu_set_option(h, "input_health", 1);
 	if (r == 0 && m->use_gate) r = squelch_gate_on(h, m->st.conseq_squelch, true, &on);
+	// behind the gate most rows are short or empty: only what they hold comes back (rtlfm_gpu_fetch_packed)
+	if (r == 0 && m->use_gate) r = rtlfm_gpu_set_option(h, "pack_results", 1);
+	if (r == 0 && m->use_gate) m->packed = true;
 	return r;
 }
 
@@ -859,8 +868,21 @@ bool run_and_fetch(Multi *m, int r, int b, const std::vector<int> &who, RunOut &
 	o.pcm.resize(who.size() * o.stride);
 	o.lens.resize(who.size());
 	o.who = who;
-	if (r == 0) r = rtlfm_gpu_fetch_all(m->gpu, o.pcm.data(), o.stride, o.lens.data());
-	if (r < 0) fail(m, "rtlfm_gpu_push/run/fetch_all", r);
+	if (r == 0 && m->packed) {
+		std::vector<rtlfm_packed_row> rows(who.size());
+		size_t total = 0;
+		r = rtlfm_gpu_fetch_packed(m->gpu, o.pcm.data(), o.pcm.size(), rows.data(), &total);
+		o.at.resize(who.size());
+		o.held.resize(who.size());
+		for (size_t k = 0; k < who.size() && r == 0; k++) {
+			o.at[k] = (size_t)rows[k].offset;
+			o.lens[k] = rows[k].len;
+			o.held[k] = rows[k].held;
+		}
+	} else if (r == 0) {
+		r = rtlfm_gpu_fetch_all(m->gpu, o.pcm.data(), o.stride, o.lens.data());
+	}
+	if (r < 0) fail(m, "rtlfm_gpu_push/run/fetch", r);
 	return r == 0;
 }
 
@@ -1142,7 +1164,7 @@ void output_thread_multi(Multi *m)
 			m->out_q.pop_front();
 		}
 		for (size_t k = 0; k < o.who.size(); k++)
-			if (o.lens[k]) m->out[(size_t)o.who[k]].write(o.pcm.data() + k * o.stride, (size_t)o.lens[k]);
+			if (o.lens[k]) m->out[(size_t)o.who[k]].write(o.pcm.data() + (o.at.empty() ? k * o.stride : o.at[k]), (size_t)o.lens[k]);
 	}
 	for (Sink &s : m->out) fflush(s.file);
 }
@@ -1316,7 +1338,10 @@ void demod_thread_channels(Multi *m)
 		if (m->st.print_levels)
 			for (int s = 0; s < S; s++)
 				if (!ended[(size_t)(s / K)]) print_level(m->out[(size_t)s], m->gpu, s, m->st);
-		if (m->st.cfg.squelch_level)  // as -N without the device gate; max_blocks is 1
+		if (m->packed) {  // -l: the rule ran on the device (pack_results 2), a held buffer has left no samples; max_blocks is 1
+			for (int s = 0; s < S; s++)
+				if (!ended[(size_t)(s / K)]) m->out[(size_t)s].blocks_squelched += (uint64_t)o.held[(size_t)s];
+		} else if (m->st.cfg.squelch_level)  // (a configuration pack_results 2 does not take) as -N without the device gate
 			hold_back(m->gpu, S, m->st.conseq_squelch, m->states, [&](int s) {
 				if (!ended[(size_t)(s / K)]) m->out[(size_t)s].blocks_squelched++;
 				o.lens[(size_t)s] = 0;
@@ -1356,6 +1381,15 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 		int r = rtlfm_gpu_create(&c, S, 0, &m.gpu);
 		if (r == 0) { what = "option source_ring"; r = rtlfm_gpu_set_option(m.gpu, "source_ring", 1); }
 		if (r == 0) { what = "rtlfm_gpu_set_channels"; r = rtlfm_gpu_set_channels(m.gpu, K, steps.data()); }
+		if (r == 0 && c.squelch_level) {
+			// -l: demod_thread_fn's rule on the device, and only what it let through comes back.  (-ENOTSUP, behind a
+			// resampler: the rule from the carried state after every run, hold_back.)
+			what = "option pack_results";
+			r = rtlfm_gpu_set_option(m.gpu, "conseq_squelch", st.conseq_squelch);
+			if (r == 0) r = rtlfm_gpu_set_option(m.gpu, "pack_results", 2);
+			m.packed = r == 0;
+			if (r == -ENOTSUP) r = 0;
+		}
 		if (r == 0 && ntaps > 0) {
 			// the cutoff the benchmarks use: 0.4 of the output rate, in cycles per capture sample
 			std::vector<int16_t> taps((size_t)ntaps);

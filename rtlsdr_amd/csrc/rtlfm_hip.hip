@@ -30,6 +30,7 @@
 #include "input_stats_kernel.h"
 #include "input_health_kernel.h"
 #include "scan_kernel.h"
+#include "pack_kernel.h"
 #include "state_kernel.h"
 #include "channel_kernel.h"
 #include "channel_fir_kernel.h"
@@ -177,6 +178,7 @@ struct rtlfm_gpu {
 		int conseq_squelch = 10;  // demod_init(), src/rtl_fm.c:1613
 		int verify_twice = 0;  // debug: every run_device runs twice - into a shadow output, then into the caller's - and the two are compared on the device
 		int source_ring = 0;   // 1: while channels are on the ring's input side has one row per SOURCE (ring_rows) and the ring calls are open
+		int pack_results = 0;  // 1 / 2: every ring run ends with k_pack_plan + k_pack_copy (pack_kernel.h; rtlfm_gpu_fetch_packed)
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
 	int16_t *vt_out = nullptr;
@@ -350,6 +352,8 @@ static void ingest_reset(rtlfm_gpu *h);
 static bool ingest_busy(rtlfm_gpu *h);
 static bool ingest_queued(rtlfm_gpu *h);
 static int ingest_resize(rtlfm_gpu *h);
+static int ingest_pack_free(rtlfm_gpu *h);
+static int ingest_pack_us(rtlfm_gpu *h, long *us);
 
 // Rows of the ring's input side (h_stage, d_in, h_len, pushed, open_slot): one per stream - or, with option source_ring
 // and channels on, one per source.  The result side is per stream whatever this says.
@@ -1081,7 +1085,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"input_stats", &h->opt.input_stats}, {"input_stats_nt", &h->opt.input_stats_nt},
 		{"input_health", &h->opt.input_health},
 		{"squelch_gate", &h->opt.squelch_gate}, {"conseq_squelch", &h->opt.conseq_squelch},
-		{"source_ring", &h->opt.source_ring},
+		{"source_ring", &h->opt.source_ring}, {"pack_results", &h->opt.pack_results},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -1134,7 +1138,19 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 		if (value == 1) {
 			const int g = gate_supported(h->cfg);
 			if (g < 0) return g;
+			if (h->opt.pack_results == 2) return -EINVAL;  // mode 2 reads uncompacted rows
 		}
+	}
+	if (!strcmp(name, "pack_results")) {
+		if (value < 0 || value > 2) return -EINVAL;
+		if (value == 2) {
+			const int g = gate_supported(h->cfg);  // the rule needs what the gate needs ...
+			if (g < 0) return g;
+			if (h->opt.squelch_gate) return -EINVAL;  // ... but not the gate's rows: they are compacted already
+		}
+		if (ingest_busy(h)) return -EBUSY;
+		h->opt.pack_results = (int)value;
+		return value == 0 ? ingest_pack_free(h) : 0;
 	}
 	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
 	if (!strcmp(name, "source_ring")) {
@@ -1175,6 +1191,7 @@ extern "C" int rtlfm_gpu_get_option(rtlfm_gpu *h, const char *name, long *value)
 	if (!strcmp(name, "verify_mismatches")) { *value = h->vt_mismatches; return 0; }  // verify_twice: runs whose two executions differed
 	if (!strcmp(name, "verify_runs")) { *value = h->vt_runs; return 0; }
 	if (!strcmp(name, "block_len")) { *value = (long)h->cfg.block_len; return 0; }  // what the handle was created with
+	if (!strcmp(name, "pack_us")) return ingest_pack_us(h, value);
 	// debugging (tests/test_soak_gpu.py): the host addresses of the runtime objects the handle owns - a hipStream_t / hipEvent_t
 	// IS the address of the runtime's object, which the runtime frees when the handle is destroyed
 	if (!strcmp(name, "dbg_own_stream")) { *value = (long)(uintptr_t)h->own_stream; return 0; }
@@ -2852,6 +2869,15 @@ struct Ingest {
 	bool mirror_valid = false;
 	int16_t *d_tmp = nullptr;                   // ragged runs: one buffer's results before they are appended
 	int32_t *d_tmp_len = nullptr;
+	// packed results (option pack_results; pack_kernel.h): per half, allocated by the first packed run
+	int16_t *d_packed[2] = {nullptr, nullptr};  // [packed_cap] int16: every row rounded up to 8, the worst case
+	rtlfm_packed_row *d_pack_index[2] = {nullptr, nullptr};  // [nstreams]
+	unsigned long long *d_pack_total[2] = {nullptr, nullptr};
+	int32_t *d_piece_off = nullptr;             // mode 2: [nstreams][cap_blocks], k_pack_plan's to k_pack_copy (one: both on the handle's stream)
+	size_t packed_cap = 0;
+	int pack_mode[2] = {0, 0};                  // how the half's run was packed (0: it was not)
+	hipEvent_t ev_pack[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // around the two launches while timing is on
+	bool pack_timed[2] = {false, false};
 };
 
 static std::mutex g_ingest_alloc_mu;
@@ -2873,6 +2899,45 @@ static long placement_held_mb(rtlfm_gpu *h)
 	return (long)(b >> 20);
 }
 
+static void pack_free(Ingest *in)
+{
+	for (int k = 0; k < 2; k++) {
+		for (void *p : {(void *)in->d_packed[k], (void *)in->d_pack_index[k], (void *)in->d_pack_total[k]})
+			if (p) hipFree(p);
+		for (hipEvent_t &e : in->ev_pack[k])
+			if (e) { hipEventDestroy(e); e = nullptr; }
+		in->d_packed[k] = nullptr; in->d_pack_index[k] = nullptr; in->d_pack_total[k] = nullptr;
+		in->pack_mode[k] = 0; in->pack_timed[k] = false;
+	}
+	if (in->d_piece_off) hipFree(in->d_piece_off);
+	in->d_piece_off = nullptr;
+	in->packed_cap = 0;
+}
+
+// option pack_results back to 0: what the pack allocated goes, behind whatever still reads or writes it
+static int ingest_pack_free(rtlfm_gpu *h)
+{
+	Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE);
+	if (!in || !in->d_packed[0]) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	pack_free(in);
+	return 0;
+}
+
+static int ingest_pack_us(rtlfm_gpu *h, long *us)
+{
+	Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE);
+	*us = -1;
+	if (!in || in->last < 0 || !in->pack_mode[in->last] || !in->pack_timed[in->last]) return 0;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(hipEventSynchronize(in->ev_pack[in->last][1]));
+	float ms = 0;
+	HIP_TRY(hipEventElapsedTime(&ms, in->ev_pack[in->last][0], in->ev_pack[in->last][1]));
+	*us = (long)(ms * 1000.0f + 0.5f);
+	return 0;
+}
+
 static void ingest_free(Ingest *in)
 {
 	if (!in) return;
@@ -2888,6 +2953,7 @@ static void ingest_free(Ingest *in)
 	if (in->h_result_len) hipHostFree(in->h_result_len);
 	if (in->d_tmp) hipFree(in->d_tmp);
 	if (in->d_tmp_len) hipFree(in->d_tmp_len);
+	pack_free(in);
 	delete in;
 }
 
@@ -3337,6 +3403,60 @@ static int apply_mute(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	return timing_end(h, ev);
 }
 
+// Option pack_results: the two launches of pack_kernel.h behind a ring run that has just been queued (the rotation has
+// moved on: the state copy the run STARTED from is two copies on, and stays as it is until the run after next writes it -
+// queued behind this).  On the handle's stream, behind the run's audio tail where that went to its own stream, as
+// launch_gate waits for it; under verify_twice behind the comparison, once.  Reads the half's rows and lengths, the run's
+// levels and that state copy; writes the half's packed buffer, index and total, and d_piece_off.
+static int ring_pack(rtlfm_gpu *h, Ingest *in, int f, int nb)
+{
+	const rtlfm_cfg &c = h->cfg;
+	const size_t S = (size_t)h->nstreams;
+	const int mode = h->opt.pack_results;
+	if (mode == 2 && gate_supported(c) < 0) return -ENOTSUP;
+	if (!in->d_packed[0]) {
+		for (int k = 0; k < 2; k++) {
+			HIP_TRY(hipMalloc(&in->d_packed[k], S * in->ostride * sizeof(int16_t)));  // (ostride is a multiple of 64)
+			HIP_TRY(hipMalloc(&in->d_pack_index[k], S * sizeof(rtlfm_packed_row)));
+			HIP_TRY(hipMalloc(&in->d_pack_total[k], sizeof(unsigned long long)));
+		}
+		in->packed_cap = S * in->ostride;
+	}
+	if (mode == 2 && !in->d_piece_off) HIP_TRY(hipMalloc(&in->d_piece_off, S * h->cap_blocks * sizeof(int32_t)));
+	const int par = (int)((h->step - 1) & 1);
+	if (h->tail_pending[par]) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_tail[par], 0));
+	pack::PlanParams pp{};
+	pp.mode = mode; pp.S = (int)S;
+	pp.lens = in->d_result_len[f];
+	pp.levels = h->d_levels;
+	pp.sin = h->st[(h->st_cur + 2) % 3];
+	pp.piece_off = in->d_piece_off;
+	pp.nblocks = nb;
+	pp.N = c.downsample_passes > 0 ? (int)((c.block_len / 2) >> c.downsample_passes) : (int)(c.block_len / 2);  // (as launch_gate)
+	pp.D = c.downsample_passes > 0 ? 1 : c.downsample;
+	pp.mul = c.mode == RTLFM_MODE_RAW ? 2 : 1;
+	pp.level = c.squelch_level; pp.conseq = h->opt.conseq_squelch;
+	pp.index = in->d_pack_index[f]; pp.total = in->d_pack_total[f];
+	pack::CopyParams cp{};
+	cp.mode = mode;
+	cp.R = in->d_result[f]; cp.rstride = in->ostride;
+	cp.packed = in->d_packed[f]; cp.cap = in->packed_cap;
+	cp.index = pp.index; cp.sin = pp.sin; cp.piece_off = pp.piece_off;
+	cp.nblocks = nb; cp.N = pp.N; cp.D = pp.D; cp.mul = pp.mul;
+	const size_t most = mode == 2 ? (size_t)pp.mul * (pp.N / pp.D + 1) : in->ostride;
+	in->pack_timed[f] = h->timing;
+	if (h->timing) {
+		for (hipEvent_t &e : in->ev_pack[f])
+			if (!e) HIP_TRY(hipEventCreate(&e));
+		HIP_TRY(hipEventRecord(in->ev_pack[f][0], h->stream));
+	}
+	const int r = pack::launch_pack(pp, cp, most, h->stream);
+	if (r < 0) return r;
+	if (h->timing) HIP_TRY(hipEventRecord(in->ev_pack[f][1], h->stream));
+	in->pack_mode[f] = mode;
+	return 0;
+}
+
 // rtlfm_gpu_run() in two steps, for a caller that gates its producers around the flip only (host/rtl_fm_hip.cpp): _begin
 // takes what the ring's filling half holds - every stream the same number of buffers, no slot open - and flips the
 // halves, which is all that must exclude the producers; _end queues the H2D copy and the kernels.  Between the two the
@@ -3379,6 +3499,8 @@ extern "C" int rtlfm_gpu_run_begin(rtlfm_gpu *h, int *taken)
 			for (int s = 1; s < S; s++)
 				for (int j = 0; j < nb; j++)
 					if (in->h_len[f][(size_t)s * h->cap_blocks + j] != in->h_len[f][j]) return -ERANGE;
+		// pack_results 2 knows a buffer's extent from the handle's buffer length: a ragged run is not taken either
+		if (ragged && h->opt.pack_results == 2) return -ENOTSUP;
 		for (int s = 0; s < S; s++) in->pushed[f ^ 1][s].store(0);
 		in->fill = f ^ 1;
 	}
@@ -3417,6 +3539,8 @@ extern "C" int rtlfm_gpu_run_end(rtlfm_gpu *h)
 	if (ragged) r = run_ragged(h, in, f, nb);
 	else r = run_device_impl(h, in->d_in[f], stride, nb, in->d_result[f], in->ostride, in->d_result_len[f]);
 	if (r < 0) return r;
+	in->pack_mode[f] = 0;
+	if (h->opt.pack_results && (r = ring_pack(h, in, f, nb)) < 0) return r;
 	HIP_TRY(hipEventRecord(in->ev_run[f], h->stream));
 	in->run_pending[f] = true;
 	in->tail_par[f] = (int)((h->step - 1) & 1);
@@ -3476,6 +3600,56 @@ extern "C" int rtlfm_gpu_fetch_all(rtlfm_gpu *h, int16_t *out, size_t out_stride
 		HIP_TRY(hipMemcpy2D(out, out_stride * sizeof(int16_t), in->d_result[f], in->ostride * sizeof(int16_t),
 		                    (size_t)mx * sizeof(int16_t), S, hipMemcpyDeviceToHost));
 	return 0;
+}
+
+// The packed form of the last run (prev: of the run before it), waited for as rtlfm_gpu_fetch_all (_prev) waits: the
+// index, then the rows in one transfer.  The total is the end of the last row.
+static int fetch_packed(rtlfm_gpu *h, bool prev, int16_t *out, size_t cap, rtlfm_packed_row *rows, size_t *total)
+{
+	if (!h || !rows || !total || (!out && cap)) return -EINVAL;
+	Ingest *in = h->ing;
+	if (!in || (prev ? in->prev < 0 || in->prev == in->last : in->last < 0)) return -EAGAIN;
+	const int f = prev ? in->prev : in->last;
+	if (!in->pack_mode[f] || !in->d_packed[f]) return -ENODATA;
+	HIP_TRY(hipSetDevice(h->device));
+	if (prev) {
+		HIP_TRY(hipEventSynchronize(in->ev_run[f]));  // (recorded behind the pack, which waited for the run's tail)
+	} else {
+		HIP_TRY(sync_all(h));
+	}
+	const size_t S = (size_t)h->nstreams;
+	HIP_TRY(hipMemcpy(rows, in->d_pack_index[f], S * sizeof(rtlfm_packed_row), hipMemcpyDeviceToHost));
+	const size_t need = (size_t)rows[S - 1].offset + (((size_t)rows[S - 1].len + 7) & ~(size_t)7);
+	*total = need;
+	if (need > cap) return -ENOBUFS;
+	if (need > 0) HIP_TRY(hipMemcpy(out, in->d_packed[f], need * sizeof(int16_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_fetch_packed(rtlfm_gpu *h, int16_t *out, size_t cap, rtlfm_packed_row *rows, size_t *total)
+{
+	return fetch_packed(h, false, out, cap, rows, total);
+}
+
+extern "C" int rtlfm_gpu_fetch_packed_prev(rtlfm_gpu *h, int16_t *out, size_t cap, rtlfm_packed_row *rows, size_t *total)
+{
+	return fetch_packed(h, true, out, cap, rows, total);
+}
+
+extern "C" int rtlfm_gpu_pack_device(int device, const int16_t *d_rows, size_t stride, const int32_t *d_lens, int nstreams,
+                                     int16_t *d_packed, size_t cap, rtlfm_packed_row *d_index, uint64_t *d_total, void *hip_stream)
+{
+	if (!d_rows || !d_lens || !d_packed || !d_index || !d_total || nstreams < 1) return -EINVAL;
+	if (((uintptr_t)d_rows & 1) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_index & 7) || ((uintptr_t)d_total & 7)) return -EINVAL;
+	int count = 0;
+	if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return -ENODEV;
+	HIP_TRY(hipSetDevice(device));
+	pack::PlanParams pp{};
+	pp.mode = 1; pp.S = nstreams; pp.lens = d_lens;
+	pp.index = d_index; pp.total = reinterpret_cast<unsigned long long *>(d_total);
+	pack::CopyParams cp{};
+	cp.mode = 1; cp.R = d_rows; cp.rstride = stride; cp.packed = d_packed; cp.cap = cap; cp.index = d_index;
+	return pack::launch_pack(pp, cp, stride, (hipStream_t)hip_stream);
 }
 
 extern "C" int rtlfm_gpu_fetch(rtlfm_gpu *h, int stream, int16_t *out, int cap, int *n)
@@ -3653,26 +3827,28 @@ extern "C" const char *rtlfm_gpu_strerror(int err)
 {
 	switch (err) {
 	case 0: return "ok";
-	case -EINVAL: return "invalid argument or configuration";
+	case -EINVAL: return "invalid argument, option value or configuration";
 	case -ENODEV: return "no usable HIP device (there is no CPU fallback)";
 	case -ENOMEM: return "out of device memory";
 	case -ENOSPC: return "max_blocks already queued for this stream";
 	case -EAGAIN: return "streams have unequal / zero queued blocks, or a producer still holds an acquired slot";
 	case -EBUSY: return "the stream's previous slot is still open (rtlfm_gpu_acquire without rtlfm_gpu_commit), or rtlfm_gpu_run_device while "
 	                    "a rtlfm_gpu_mute count is pending (it never writes its input), or rtlfm_gpu_state_move while a handle has a run "
-	                    "begun and not ended or a ring slot open";
+	                    "begun and not ended or a ring slot open, or the options source_ring / pack_results set in such a moment";
 	case -EXDEV: return "rtlfm_gpu_state_move: the handles are on different devices (use rtlfm_gpu_state_get_all / _set_all)";
 	case -ERANGE: return "the snapshot holds another number of streams than the handle";
 	case -EMEDIUMTYPE: return "the snapshot was saved under another configuration (a rtlfm_cfg field other than max_blocks / report_levels differs)";
 	case -EILSEQ: return "the snapshot file is damaged or no snapshot (magic, version, sizes, length or checksum)";
-	case -ENOTSUP: return "configuration not supported on this path; squelch_gate: not behind a resampler (rate_out2 > 0), "
-	                      "post_downsample > 1 or a buffer the fifth_order passes do not divide";
+	case -ENOTSUP: return "configuration not supported on this path; squelch_gate and pack_results 2: not behind a resampler "
+	                      "(rate_out2 > 0), post_downsample > 1 or a buffer the fifth_order passes do not divide; pack_results 2: "
+	                      "not on a run that holds a short buffer";
 	case -EDOM: return "outside the reference's own domain: a boxcar longer than the buffer (fm_demod reads lowpassed[-2]), low_pass_simple on a "
 	                   "count its step does not divide (src/rtl_fm.c:740), or rate_out2 > rate_out with low_pass_real (division by zero, :769)";
 	case -E2BIG: return "more blocks than cfg.max_blocks";
 	case -ENOBUFS: return "output buffer too small";
 	case -EIO: return "HIP runtime error";
-	case -ENODATA: return "no clock stamps recorded (rtlfm_gpu_clock_probe, fused fifth_order path only)";
+	case -ENODATA: return "no clock stamps recorded (rtlfm_gpu_clock_probe, fused fifth_order path only); no records of this kind "
+	                      "(the option was off); rtlfm_gpu_fetch_packed: that run was not packed (option pack_results was 0)";
 	default: return strerror(-err);
 	}
 }

@@ -82,6 +82,18 @@ __device__ __forceinline__ void move_down(int16_t *dst, const int16_t *src, int 
 	}
 }
 
+// The rule for one buffer (k_scan_gate, and k_pack_plan of pack_kernel.h): the counter moves as full_demod() moves it on the
+// buffer's rms() `sr` - a negative level changes nothing -, the buffer is held while hits > conseq, and a held buffer
+// leaves the counter at conseq + 1.  Clamping does not change a decision: a counter above conseq stays above it until a
+// level at or above the squelch zeroes it, clamped or not.  Returns whether the buffer is emitted.
+__device__ __forceinline__ bool gate_step(int &hits, int sr, int level, int conseq)
+{
+	if (sr >= 0) hits = sr < level ? hits + 1 : 0;       // src/rtl_fm.c:1206-1213
+	const bool hold = hits > conseq;                      // :1366
+	if (hold) hits = conseq + 1;                          // :1368
+	return !hold;
+}
+
 __global__ void __launch_bounds__(kGateThreads) k_scan_gate(GateParams p)
 {
 	__shared__ uint8_t emit[kGateChunk];
@@ -98,12 +110,9 @@ __global__ void __launch_bounds__(kGateThreads) k_scan_gate(GateParams p)
 		if (tid == 0) {
 			int hits = carry_hits;
 			for (int b = c0; b < c1; b++) {
-				const int sr = p.levels[s * p.nblocks + b];
-				if (sr >= 0) hits = sr < p.level ? hits + 1 : 0;       // src/rtl_fm.c:1206-1213
-				const bool hold = hits > p.conseq;                      // :1366
-				if (hold) hits = p.conseq + 1;                          // :1368
+				const bool emitted = gate_step(hits, p.levels[s * p.nblocks + b], p.level, p.conseq);
 				rtlfm_gate_rec r;
-				r.hits_after = hits; r.emit = hold ? 0 : 1; r.pad[0] = r.pad[1] = r.pad[2] = 0;
+				r.hits_after = hits; r.emit = emitted ? 1 : 0; r.pad[0] = r.pad[1] = r.pad[2] = 0;
 				p.recs[s * p.rec_stride + b] = r;
 				emit[b - c0] = r.emit;
 			}

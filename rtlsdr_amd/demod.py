@@ -117,6 +117,20 @@ class GpuDemod:
         check(self.lib.rtlfm_gpu_fetch_all_prev(self._h, out.ctypes.data, cap, lens.ctypes.data), "rtlfm_gpu_fetch_all_prev")
         return out, lens
 
+    def fetch_packed(self, prev: bool = False):
+        """rtlfm_gpu_fetch_packed (``prev``: _fetch_packed_prev): ``(packed int16 [total], index)`` of a run made with the
+        option ``pack_results`` at 1 or 2 - ``index`` a record array (``capi.PACKED_ROW``: offset, len, held) per stream,
+        stream s's samples ``packed[offset : offset + len]``.  One small copy for the index, one for the samples."""
+        fn = self.lib.rtlfm_gpu_fetch_packed_prev if prev else self.lib.rtlfm_gpu_fetch_packed
+        index = np.zeros(self.nstreams, dtype=capi.PACKED_ROW)
+        total = C.c_size_t()
+        # room for the worst case (every row full, rounded up to 8): pages the copy does not reach are never touched
+        cap = capi.load().rtlfm_result_cap(C.byref(self.cfg)) * max(1, self.cfg.max_blocks) + 16
+        out = np.empty(self.nstreams * ((cap + 7) & ~7), dtype=np.int16)
+        check(fn(self._h, out.ctypes.data, out.size, index.ctypes.data, C.byref(total)),
+              "rtlfm_gpu_fetch_packed_prev" if prev else "rtlfm_gpu_fetch_packed")
+        return out[:total.value], index
+
     # -- device-resident form ------------------------------------------------
     def result_cap(self, nblocks: int) -> int:
         c = self.lib.rtlfm_result_cap(C.byref(self.cfg)) * nblocks + 16
@@ -397,6 +411,16 @@ def optimal_settings(cfg: RtlfmCfg, freq: int, rate_in: int, min_capture_rate: i
 
 def deemph_a(rate_out: int, time_constant_us: int = 75) -> int:
     return capi.load().rtlfm_deemph_a(rate_out, time_constant_us)
+
+
+def pack_device(d_rows_ptr: int, stride: int, d_lens_ptr: int, nstreams: int, d_packed_ptr: int, cap: int, d_index_ptr: int,
+                d_total_ptr: int, device: int = 0, hip_stream_ptr: int = 0):
+    """rtlfm_gpu_pack_device: row s - ``lens[s]`` int16 at ``d_rows + s * stride``, any int16 alignment - behind the rows
+    before it in ``d_packed`` (16-byte aligned, ``cap`` int16), each row starting on a multiple of 8; the index
+    (``capi.PACKED_ROW`` [nstreams]) and the total need (uint64, also where it exceeds ``cap``) on the device.
+    Asynchronous on ``hip_stream_ptr`` (0: the default stream).  All pointers are device addresses."""
+    check(capi.load().rtlfm_gpu_pack_device(int(device), d_rows_ptr, int(stride), d_lens_ptr, int(nstreams), d_packed_ptr, int(cap),
+                                            d_index_ptr, d_total_ptr, hip_stream_ptr or None), "rtlfm_gpu_pack_device")
 
 
 def channel_step(shift_hz: int, capture_rate: int) -> int:
