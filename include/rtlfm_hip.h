@@ -598,6 +598,49 @@ int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bins /* [per_
                                int shift);
 int rtlfm_gpu_get_channel_bank(rtlfm_gpu *h, int *K, int32_t *bins, int bins_cap, int16_t *taps, int taps_cap, int *ntaps, int *shift);
 
+/*
+ * The bank's survey and per-source bins: a few demodulator SLOTS per source that follow the activity (DESIGN.md section
+ * 8.5, "Survey and slots"; include/rtlfm_slots.h has the allocator that turns one into the other).
+ *
+ * Per output instant the bank computes all K bins of a source and keeps the per_source the caller selected.  With the
+ * option "bank_survey" at 1 a run the bank takes also leaves, for source a with E_a the frames the run emitted (the count
+ * written to the source's channels),
+ *   frames[a]   = E_a
+ *   power[a][k] = sum over f < E_a of Yi[f][k]^2 + Yq[f][k]^2        (uint64; one term reaches 2^31)
+ * Y being the int16 pair fix_fft leaves for bin k at frame f: all K bins, selected or not, whatever bins says.  Integers,
+ * the same on both paths.  Path 2: k_channel_bank_survey - k_channel_bank's body with, per tile, the 256 lanes over (bin,
+ * group of frames) adding the results up out of LDS in 64-bit registers, and per segment one [K] partial stored - and
+ * k_bank_survey_reduce, which adds the segments and writes frames; both inside the front end's timed pair.  Path 1:
+ * k_bank_power_plain, one lane per (source, bin), behind the cross-check's kernels.  No atomics; a run without frames
+ * leaves zeros.  Two sets of buffers rotate as the ring's halves do, allocated by the first surveyed run and freed when
+ * the option returns to 0 (which waits for the handle) or with the handle.  Under verify_twice a survey is one
+ * execution's.  A ring run that holds short buffers is not surveyed.  With the option at 0 (default) no kernel, path,
+ * result or allocation differs.  Anything but 0 / 1 -EINVAL; -EBUSY while a run is begun and not ended; it may be set with
+ * the bank or channels off and acts only on runs the bank takes.
+ * rtlfm_gpu_bank_survey (_prev): power [sources][K] (cap: elements), frames [sources] and *K of the last run (of the run
+ * before it), waited for as rtlfm_gpu_fetch_all (_prev) wait - _prev for that run only, not the one started since; for
+ * runs through rtlfm_gpu_run_device just the same.  -ENODATA when that run carried no survey (option off, bank off, no
+ * run yet); -ENOBUFS when cap is too small, *K written all the same.
+ *
+ * rtlfm_gpu_set_channel_bins: bins [sources][per_source], each in [0, K) - channel c of source a becomes bin
+ * bins[a][c] of the bank that is set.  Nothing else changes: pos, the history, the taps and every stream's carried record
+ * stay (as retuning a dongle keeps demod_state).  The call does not wait for the device: the new bins travel through a
+ * rotation of pinned buffers on the handle's stream, so runs already queued use the old bins and later runs the new.
+ * -EINVAL without a bank, for NULL, or for a bin outside [0, K); -EBUSY while a run is begun and not ended; a refused call
+ * changes nothing.  rtlfm_gpu_set_channel_bank afterwards is its shared list again; it and rtlfm_gpu_set_channels drop the
+ * per-source bins.  rtlfm_gpu_get_channel_bins: [sources][per_source] as they rule now (the shared list repeated where no
+ * per-source bins are set); -ENOBUFS where cap < sources * per_source.  rtlfm_gpu_get_channel_bank keeps returning
+ * per_source bins: source 0's.
+ *
+ * The loop: run r -> rtlfm_gpu_bank_survey -> rtlfm_slots_step -> rtlfm_gpu_set_channel_bins -> run
+ * r + 1.  A decision made from run r's survey acts on run r + 1 (r + 2 through _prev): a transmission's first buffer is
+ * lost.
+ */
+int rtlfm_gpu_bank_survey(rtlfm_gpu *h, uint64_t *power, size_t cap, int32_t *frames, int *K);
+int rtlfm_gpu_bank_survey_prev(rtlfm_gpu *h, uint64_t *power, size_t cap, int32_t *frames, int *K);
+int rtlfm_gpu_set_channel_bins(rtlfm_gpu *h, const int32_t *bins /* [sources][per_source] */);
+int rtlfm_gpu_get_channel_bins(rtlfm_gpu *h, int32_t *bins, int cap);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,
@@ -683,6 +726,8 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        resampler (rate_out2 > 0), post_downsample > 1, or a buffer the fifth_order passes do not divide
  *   conseq_squelch       the demod thread's limit (default 10, demod_init, src/rtl_fm.c:1613; < 0 -EINVAL)
  *   pack_results         0 (default) / 1 / 2: every ring run also leaves its results packed (see rtlfm_gpu_fetch_packed)
+ *   bank_survey          0 (default) / 1: every run the channel bank takes also leaves every bin's power (see
+ *                        rtlfm_gpu_bank_survey)
  * Read-only (rtlfm_gpu_get_option):
  *   pack_us              device time of the last run's two pack launches in microseconds (waits for them); -1 when that
  *                        run was not packed or rtlfm_gpu_timing_enable was off

@@ -14,7 +14,7 @@ OUT = os.path.join(CSRC, "librtlfm_hip.so")
 # entries hold device code; FUSED_UNIT names the one that holds the k_fused instances - today the whole rtl_fm library -
 # for the prefetch lint, which reads that unit's assembly (first: it compiles longest).
 FUSED_UNIT = "rtlfm_hip.hip"
-SOURCES = [FUSED_UNIT, "rtlpower_hip.hip", "rtlfm_place.hip", "monitor.cpp", "agc.cpp", "scan.cpp", "snapshot.cpp"]
+SOURCES = [FUSED_UNIT, "rtlpower_hip.hip", "rtlfm_place.hip", "monitor.cpp", "agc.cpp", "scan.cpp", "snapshot.cpp", "slots.cpp"]
 DEVICE_UNITS = [s for s in SOURCES if s.endswith(".hip")]
 ARCH = "gfx950"
 

@@ -178,6 +178,22 @@ class RtlfmScanEvent(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad_"}
 
 
+class RtlfmSlotsCfg(C.Structure):
+    """``rtlfm_slots_cfg`` (include/rtlfm_slots.h)."""
+
+    _fields_ = [("open_level", C.c_uint64), ("close_level", C.c_uint64), ("hang", C.c_int32), ("park", C.c_int32),
+                ("mask", C.c_void_p)]
+
+
+class RtlfmSlotsEvent(C.Structure):
+    """``rtlfm_slots_event`` — one change of a slot's bin; an idle slot is bin -1 (include/rtlfm_slots.h)."""
+
+    _fields_ = [("source", C.c_int32), ("slot", C.c_int32), ("old_bin", C.c_int32), ("new_bin", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class RtlfmAgcEvent(C.Structure):
     """``rtlfm_agc_event`` — one change of a stream's gain index (include/rtlfm_agc.h)."""
 
@@ -340,6 +356,10 @@ _SIGNATURES = [
     ("rtlfm_gpu_set_channel_bank", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("rtlfm_gpu_get_channel_bank", C.c_int,
      [C.c_void_p, _P(C.c_int), C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int), _P(C.c_int)]),
+    ("rtlfm_gpu_bank_survey", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, _P(C.c_int)]),
+    ("rtlfm_gpu_bank_survey_prev", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, _P(C.c_int)]),
+    ("rtlfm_gpu_set_channel_bins", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_gpu_get_channel_bins", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     ("rtlfm_gpu_sync", C.c_int, [C.c_void_p]),
     ("rtlfm_gpu_set_stream", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtlfm_gpu_wait_for", C.c_int, [C.c_void_p, C.c_void_p]),
@@ -464,6 +484,17 @@ _SCAN_SIGNATURES = [
 ]
 DECLARED_SCAN_SYMBOLS = [s[0] for s in _SCAN_SIGNATURES]
 
+# ... and include/rtlfm_slots.h (the channel bank's slot allocator; host code inside the same library)
+_SLOTS_SIGNATURES = [
+    ("rtlfm_slots_create", C.c_int, [C.c_int, C.c_int, C.c_int, _P(RtlfmSlotsCfg), _P(C.c_void_p)]),
+    ("rtlfm_slots_destroy", C.c_int, [C.c_void_p]),
+    ("rtlfm_slots_step", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rtlfm_slots_bins", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_slots_idle", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_slots_events", C.c_int, [C.c_void_p, _P(RtlfmSlotsEvent), C.c_int, _P(C.c_int)]),
+]
+DECLARED_SLOTS_SYMBOLS = [s[0] for s in _SLOTS_SIGNATURES]
+
 # ... and include/rtlfm_snapshot.h (the snapshot file of rtlfm_gpu_save / _load; host code inside the same library)
 _SNAPSHOT_SIGNATURES = [
     ("rtlfm_snapshot_write", C.c_int, [C.c_char_p, _P(RtlfmCfg), C.c_int, C.c_void_p, C.c_void_p]),
@@ -505,7 +536,8 @@ def load(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, res, args in _SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES + _SNAPSHOT_SIGNATURES:
+    for name, res, args in (_SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES + _SNAPSHOT_SIGNATURES
+                            + _SLOTS_SIGNATURES):
         if path is not None and not hasattr(lib, name):
             continue  # an explicitly named other build (A/B against an earlier revision) may predate a symbol
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported

@@ -21,6 +21,11 @@
 //                    runs the log2 K stages over its batch of max(128, K) points (128 / K frames, or one frame with two
 //                    butterflies per lane), leaves the last stage's results in LDS as [bin][frame], and the workgroup
 //                    hands every selected bin's row its stretch of frames as one contiguous piece.
+//   k_channel_bank_survey, k_bank_survey_reduce
+//                    option bank_survey (rtlfm_gpu_bank_survey): the same body, which also adds up every bin's Yi^2 + Yq^2
+//                    over the segment's frames out of the [bin][frame] results, and the sum over the segments.
+//   k_bank_power_plain
+//                    the survey's cross-check: one lane per (source, bin) over the cross-check's transforms.
 //   k_bank_sums, k_bank_fft, k_bank_scatter
 //                    the cross-check: one lane per (frame, residue) forms v in memory, one lane per frame runs fix_fft in
 //                    the reference's own loop order with FIX_MPY spelled out, a scatter and channel::k_source_history
@@ -55,18 +60,21 @@ struct Geometry {
 	int Ls;     // int16 per residue row of the staged samples (even, its half odd)
 	int Fs;     // dwords per bin row of the results (odd)
 	int batch;  // points per wave and turn
+	int extra;  // dwords behind the results: the survey's sums of the segment's end, or none
 	size_t lds; // bytes
 };
 
 inline size_t lds_of(const Geometry &g)
 {
-	return 4 * ((size_t)g.K + (size_t)g.K * g.Qp + (size_t)g.K * g.Ls + (size_t)kWaves * g.batch + (size_t)g.K * g.Fs);
+	return 4 * ((size_t)g.K + (size_t)g.K * g.Qp + (size_t)g.K * g.Ls + (size_t)kWaves * g.batch + (size_t)g.K * g.Fs + (size_t)g.extra);
 }
 
-inline Geometry geometry(int m, int ntaps, int D)
+// survey: with room behind the results for k_channel_bank_survey's 256 64-bit sums (F shrinks where that needs it)
+inline Geometry geometry(int m, int ntaps, int D, bool survey = false)
 {
 	Geometry g{};
 	g.m = m; g.K = 1 << m;
+	g.extra = survey ? 2 * kWaves * 64 : 0;
 	g.Q = (ntaps + g.K - 1) / g.K;
 	g.Qp = (g.Q + 2) & ~1;
 	if (!((g.Qp / 2) & 1)) g.Qp += 2;
@@ -109,8 +117,10 @@ struct BankParams {
 	uint8_t *hist_out;        // the same behind it (another buffer)
 	const uint32_t *taps2;    // branch_taps(), as dwords
 	const uint32_t *tw;       // [K] fix_fft's twiddles per stage, doubled and packed (fix_fft_butterfly.h)
-	const int32_t *bins;      // [per_source]
+	const int32_t *bins;      // [per_source], or [sources][per_source] with bins_stride = per_source (rtlfm_gpu_set_channel_bins)
 	int m, Q, Qp, lead, F, Ls, Fs, shift;
+	int bins_stride;          // 0: one list for every source
+	unsigned long long *survey;  // k_channel_bank_survey: [sources][segs][K] partial sums
 };
 
 // One complex sample of the source as a dword (I | Q << 8): run sample g, the history in front of the run, or silence.
@@ -121,8 +131,14 @@ __device__ __forceinline__ uint32_t sample_at(const uint8_t *row, const uint8_t 
 	              : (uint32_t)*reinterpret_cast<const uint16_t *>(hold + (size_t)(kHist + g) * 2);
 }
 
-// Grid: source * segs + seg.  Dynamic LDS: Geometry::lds.
-__global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p)
+// The body of k_channel_bank and k_channel_bank_survey.  SURVEY: every bin's power over the frames of the workgroup's segment
+// as well (rtlfm_gpu_bank_survey): a lane owns bin tid % K and, per tile, the frames [c len, (c + 1) len) with c = tid / K -
+// len = K below 32 bins (one pass covers 256 frames), else the tile's frames shared out among the 256 / K lanes of a bin.
+// The rows of s_out are an odd number of dwords apart, so the 32 lanes of a half wave - min(K, 32) bins, the frame groups
+// a multiple of K apart where K < 32 - read 32 different banks whatever Fs is.  The lane keeps its sum in a 64-bit
+// register over all tiles; at the segment's end the lanes of a bin inside a wave add up by shuffles, the waves through LDS.
+template <bool SURVEY>
+__device__ __forceinline__ void bank_body(const BankParams &p)
 {
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 	const int m = p.m, K = 1 << m, Km = K - 1;
@@ -138,6 +154,7 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 	const int seg = (int)(blockIdx.x % (unsigned)p.f.segs);
 	const size_t src = (size_t)(blockIdx.x / (unsigned)p.f.segs);
 	const size_t s0 = src * (size_t)p.f.per_source;
+	const int32_t *bins = p.bins + src * (size_t)p.bins_stride;
 
 	for (int i = tid; i < K; i += kWaves * 64) s_tw[i] = p.tw[i];
 	for (int i = tid; i < K * p.Qp; i += kWaves * 64) s_taps[i] = p.taps2[i];
@@ -154,6 +171,9 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 	int16_t *hI = reinterpret_cast<int16_t *>(s_I), *hQ = reinterpret_cast<int16_t *>(s_Q);
 	uint32_t *wk = s_work + wave * batch;
 	const int gf = batch >> m;  // frames per batch
+	unsigned long long sv_acc = 0;
+	const int sv_bin = tid & Km, sv_c = tid >> m;
+	const int sv_len = K < 32 ? K : (p.F + (kWaves * 64 >> m) - 1) / (kWaves * 64 >> m);
 
 	for (int t = t_begin; t < t_end; t++) {
 		const int k0 = t * p.F;
@@ -223,13 +243,60 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p
 		// every selected bin's row receives the tile's frames as one contiguous piece: consecutive lanes, consecutive dwords
 		for (int x = tid; x < p.f.per_source * nf; x += kWaves * 64) {
 			const int c = x / nf, f = x - c * nf;
-			p.f.Y[(s0 + (size_t)c) * p.f.ystride + (size_t)(k0 + f)] = s_out[p.bins[c] * p.Fs + f];
+			p.f.Y[(s0 + (size_t)c) * p.f.ystride + (size_t)(k0 + f)] = s_out[bins[c] * p.Fs + f];
+		}
+		if constexpr (SURVEY) {
+			const uint32_t *ro = s_out + sv_bin * p.Fs;
+			const int f1 = min(min(nf, sc.E - k0), (sv_c + 1) * sv_len);  // (sc.E: what frames says - a broken record's count may be smaller than E)
+			for (int f = sv_c * sv_len; f < f1; f++) {
+				const iq16 y = unpack_iq(ro[f]);
+				sv_acc += (uint32_t)(y.i * y.i) + (uint32_t)(y.q * y.q);  // (at most 2^31: a dword; the sum is 64 bits from the first addition)
+			}
+		}
+	}
+	if constexpr (SURVEY) {
+		// (also of a segment that owns no frame, and of a run with none: zeros, never what an earlier run left)
+		for (int off = K; off < 64; off <<= 1) {
+			const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)sv_acc, off, 64);
+			const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(sv_acc >> 32), off, 64);
+			sv_acc += (unsigned long long)hi << 32 | lo;
+		}
+		unsigned long long *s_fin = reinterpret_cast<unsigned long long *>(s_out + ((K * p.Fs + 1) & ~1));  // [256]
+		s_fin[tid] = sv_acc;
+		__syncthreads();
+		const int stride = K < 64 ? 64 : K;
+		for (int b = tid; b < K; b += kWaves * 64) {
+			unsigned long long sum = 0;
+			for (int at = b; at < kWaves * 64; at += stride) sum += s_fin[at];
+			p.survey[(src * (size_t)p.f.segs + (size_t)seg) * (size_t)K + (size_t)b] = sum;
 		}
 	}
 	if (seg == p.f.segs - 1) {
 		for (int c = tid; c < p.f.per_source; c += kWaves * 64) channel::leave_schedule(p.f.sout, p.f.cnt, s0 + c, sc);
 		for (int u = tid; u < kHist / 8; u += kWaves * 64)
 			reinterpret_cast<uint4 *>(p.hist_out + src * (size_t)(kHist * 2))[u] = channel::history_piece(row, hold, p.f.T, u);
+	}
+}
+
+// Grid: source * segs + seg.  Dynamic LDS: Geometry::lds.
+__global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p) { bank_body<false>(p); }
+
+// ... the same with the survey's partial sums, [source][seg][K], stored at the segment's end (Geometry of survey = true)
+__global__ void __launch_bounds__(kWaves * 64) k_channel_bank_survey(const BankParams p) { bank_body<true>(p); }
+
+// The segments' partial sums into power [source][K], and the frames the run emitted for the source into frames [source]:
+// one lane per (source, bin).
+__global__ void __launch_bounds__(256)
+k_bank_survey_reduce(const unsigned long long *__restrict__ partial, int segs, int m, int nsources, int per_source, int T, int D,
+                     const state_t *__restrict__ sin, unsigned long long *__restrict__ power, int32_t *__restrict__ frames)
+{
+	RTLFM_GRID_STRIDE(g, (size_t)nsources << m) {
+		const size_t src = g >> m;
+		const size_t b = g & (((size_t)1 << m) - 1);
+		unsigned long long sum = 0;
+		for (int sg = 0; sg < segs; sg++) sum += partial[((src * (size_t)segs + (size_t)sg) << m) + b];
+		power[g] = sum;
+		if (b == 0) frames[src] = channel::schedule(sin[src * per_source].prev_index, T, D).E;
 	}
 }
 
@@ -305,7 +372,7 @@ k_bank_fft(uint32_t *__restrict__ V, const int16_t *__restrict__ sine, int m, in
 }
 
 __global__ void __launch_bounds__(256)
-k_bank_scatter(const uint32_t *__restrict__ V, const int32_t *__restrict__ bins, int m, int nstreams, int per_source, int T, int D,
+k_bank_scatter(const uint32_t *__restrict__ V, const int32_t *__restrict__ bins, size_t bins_stride, int m, int nstreams, int per_source, int T, int D,
                int maxout, uint32_t *__restrict__ Y, size_t ystride, int32_t *__restrict__ cnt, const state_t *__restrict__ sin,
                state_t *__restrict__ sout)
 {
@@ -317,7 +384,27 @@ k_bank_scatter(const uint32_t *__restrict__ V, const int32_t *__restrict__ bins,
 		const channel::Schedule sc = channel::schedule(sin[src * per_source].prev_index, T, D);
 		if (k == 0) channel::leave_schedule(sout, cnt, s, sc);
 		if (k >= min((T + sc.p0c) / D, maxout)) continue;
-		Y[s * ystride + k] = V[(((src * (size_t)maxout) + k) << m) + bins[c]];
+		Y[s * ystride + k] = V[(((src * (size_t)maxout) + k) << m) + bins[src * bins_stride + c]];
+	}
+}
+
+// The survey's cross-check: one lane per (source, bin) walks the transforms in V frame by frame.
+__global__ void __launch_bounds__(256)
+k_bank_power_plain(const uint32_t *__restrict__ V, int m, int nsources, int per_source, int T, int D, int maxout,
+                   const state_t *__restrict__ sin, unsigned long long *__restrict__ power, int32_t *__restrict__ frames)
+{
+	RTLFM_GRID_STRIDE(g, (size_t)nsources << m) {
+		const size_t src = g >> m;
+		const size_t b = g & (((size_t)1 << m) - 1);
+		const channel::Schedule sc = channel::schedule(sin[src * per_source].prev_index, T, D);
+		const int E = min(min((T + sc.p0c) / D, maxout), sc.E);  // (the frames written, and no more than frames says)
+		unsigned long long sum = 0;
+		for (int k = 0; k < E; k++) {
+			const iq16 y = unpack_iq(V[(((src * (size_t)maxout) + k) << m) + b]);
+			sum += (uint32_t)(y.i * y.i) + (uint32_t)(y.q * y.q);
+		}
+		power[g] = sum;
+		if (b == 0) frames[src] = sc.E;
 	}
 }
 

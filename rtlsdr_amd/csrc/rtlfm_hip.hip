@@ -142,6 +142,32 @@ struct rtlfm_gpu {
 	int32_t *d_bank_bins = nullptr;        // [chan_per]
 	uint32_t *bank_v = nullptr;            // path 1: [sources][maxout][K] sums, transformed in place
 	size_t bank_v_dwords = 0;
+	// per-source bins (rtlfm_gpu_set_channel_bins): while set they rule in d_bank_bins' place, chan_per apart per source.
+	// The setter copies through a rotation of pinned buffers on the handle's stream and waits for nothing but a buffer
+	// whose own copy, kBinStages calls ago, has not left yet.
+	static constexpr int kBinStages = 4;
+	std::vector<int32_t> bank_bins_ps;     // [sources][chan_per]; empty: the shared list
+	int32_t *d_bank_bins_ps = nullptr;
+	size_t bank_bins_ps_cap = 0;
+	int32_t *h_bins_stage[kBinStages] = {nullptr, nullptr, nullptr, nullptr};
+	hipEvent_t ev_bins_stage[kBinStages] = {nullptr, nullptr, nullptr, nullptr};
+	size_t bins_stage_cap = 0;
+	int bins_stage_next = 0;
+	// the survey (option bank_survey; rtlfm_gpu_bank_survey): two sets in rotation, as the ring's halves rotate - a surveyed
+	// run writes the set the last surveyed run did not; allocated by the first surveyed run
+	struct Survey {
+		unsigned long long *d_power[2] = {nullptr, nullptr};  // [sources][K]
+		int32_t *d_frames[2] = {nullptr, nullptr};            // [sources]
+		hipEvent_t ev[2] = {nullptr, nullptr};                // behind the set's last launch
+		size_t cap = 0;                                       // elements of d_power[k]
+		int cap_srcs = 0;
+		unsigned long long *d_partial = nullptr;              // k_channel_bank_survey's: [sources][segs][K]
+		size_t partial_cap = 0;
+		int K[2] = {0, 0}, nsrc[2] = {0, 0};                  // what the set holds
+		int last = -1, prev = -1;                             // the set of the last run and of the run before it; -1: that run carried none
+		int writing = -1;                                     // the set the run being launched writes
+		int next = 0;
+	} sv;
 	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
 	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
 	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
@@ -179,6 +205,7 @@ struct rtlfm_gpu {
 		int verify_twice = 0;  // debug: every run_device runs twice - into a shadow output, then into the caller's - and the two are compared on the device
 		int source_ring = 0;   // 1: while channels are on the ring's input side has one row per SOURCE (ring_rows) and the ring calls are open
 		int pack_results = 0;  // 1 / 2: every ring run ends with k_pack_plan + k_pack_copy (pack_kernel.h; rtlfm_gpu_fetch_packed)
+		int bank_survey = 0;   // 1: a run the bank takes leaves every bin's power as well (k_channel_bank_survey; rtlfm_gpu_bank_survey)
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
 	int16_t *vt_out = nullptr;
@@ -354,6 +381,7 @@ static bool ingest_queued(rtlfm_gpu *h);
 static int ingest_resize(rtlfm_gpu *h);
 static int ingest_pack_free(rtlfm_gpu *h);
 static int ingest_pack_us(rtlfm_gpu *h, long *us);
+static int survey_free(rtlfm_gpu *h, bool wait);
 
 // Rows of the ring's input side (h_stage, d_in, h_len, pushed, open_slot): one per stream - or, with option source_ring
 // and channels on, one per source.  The result side is per stream whatever this says.
@@ -561,9 +589,14 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_istats, h->d_ihealth,
 	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq,
 	                h->d_src_hist[0], h->d_src_hist[1], h->d_fir_taps, h->d_fir_taps8, h->chan_fir_x,
-	                h->d_bank_taps, h->d_bank_taps2, h->d_bank_tw, h->d_bank_sine, h->d_bank_bins, h->bank_v};
+	                h->d_bank_taps, h->d_bank_taps2, h->d_bank_tw, h->d_bank_sine, h->d_bank_bins, h->bank_v, h->d_bank_bins_ps};
 	for (void *p : ptrs)
 		if (p) hipFree(p);
+	(void)survey_free(h, false);
+	for (int k = 0; k < rtlfm_gpu::kBinStages; k++) {
+		if (h->h_bins_stage[k]) hipHostFree(h->h_bins_stage[k]);
+		if (h->ev_bins_stage[k]) hipEventDestroy(h->ev_bins_stage[k]);
+	}
 	delete[] h->mute_left;
 	h->fws.release();
 	ingest_destroy(h);
@@ -812,6 +845,7 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	h->chan_per = per_source;
 	h->chan_pos = 0;
 	h->bank_K = 0;  // (the bank's bins belong to the old per_source)
+	h->bank_bins_ps.clear();
 	const int r = ensure_history(h);
 	if (r < 0) return r;
 	return ingest_resize(h);  // (option source_ring: the ring's input side for the new number of sources)
@@ -938,6 +972,7 @@ extern "C" int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bi
 	HIP_TRY(sync_all(h));
 	if (K == 0) {
 		h->bank_K = 0;
+		h->bank_bins_ps.clear();
 		return history_clear(h);
 	}
 	int m = 0;
@@ -967,6 +1002,7 @@ extern "C" int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bi
 	if ((r = bank_upload(&h->d_bank_bins, b.data(), b.size())) < 0) return r;
 	h->bank_taps.assign(taps, taps + ntaps);
 	h->bank_bins = b;
+	h->bank_bins_ps.clear();  // (the shared list again)
 	h->bank_m = m; h->bank_K = K; h->bank_ntaps = ntaps; h->bank_shift = shift;
 	return ensure_history(h);
 }
@@ -980,8 +1016,50 @@ extern "C" int rtlfm_gpu_get_channel_bank(rtlfm_gpu *h, int *K, int32_t *bins, i
 	*shift = h->bank_K ? h->bank_shift : 0;
 	if (!h->bank_K) return 0;
 	if ((int)h->bank_bins.size() > bins_cap || h->bank_ntaps > taps_cap) return -ENOBUFS;
-	memcpy(bins, h->bank_bins.data(), h->bank_bins.size() * sizeof(int32_t));
+	// (per-source bins set: source 0's)
+	memcpy(bins, h->bank_bins_ps.empty() ? h->bank_bins.data() : h->bank_bins_ps.data(), h->bank_bins.size() * sizeof(int32_t));
 	memcpy(taps, h->bank_taps.data(), (size_t)h->bank_ntaps * sizeof(int16_t));
+	return 0;
+}
+
+// Per-source bins for the bank that is set: nothing else moves - pos, the history, the taps, every stream's record - and
+// nothing is waited for but a staging buffer whose own copy has not left yet.  The copy is ordered on the handle's stream:
+// runs queued before the call read the old bins, runs after it the new.
+extern "C" int rtlfm_gpu_set_channel_bins(rtlfm_gpu *h, const int32_t *bins)
+{
+	if (!h || !bins || h->bank_K <= 0 || h->chan_per <= 0) return -EINVAL;
+	const size_t n = (size_t)h->nstreams;  // sources * per_source
+	for (size_t i = 0; i < n; i++)
+		if (bins[i] < 0 || bins[i] >= h->bank_K) return -EINVAL;
+	if (ingest_busy(h)) return -EBUSY;
+	HIP_TRY(hipSetDevice(h->device));
+	if (h->bank_bins_ps_cap < n) {
+		HIP_TRY(hipMalloc(&h->d_bank_bins_ps, n * sizeof(int32_t)));  // (the first call: a handle's stream count never changes)
+		h->bank_bins_ps_cap = n;
+	}
+	if (h->bins_stage_cap < n) {
+		for (int k = 0; k < rtlfm_gpu::kBinStages; k++) {
+			HIP_TRY(hipHostMalloc(&h->h_bins_stage[k], n * sizeof(int32_t), hipHostMallocDefault));
+			HIP_TRY(hipEventCreateWithFlags(&h->ev_bins_stage[k], hipEventDisableTiming));
+		}
+		h->bins_stage_cap = n;
+	}
+	const int k = h->bins_stage_next;
+	HIP_TRY(hipEventSynchronize(h->ev_bins_stage[k]));  // (an event never recorded is complete)
+	memcpy(h->h_bins_stage[k], bins, n * sizeof(int32_t));
+	HIP_TRY(hipMemcpyAsync(h->d_bank_bins_ps, h->h_bins_stage[k], n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(hipEventRecord(h->ev_bins_stage[k], h->stream));
+	h->bins_stage_next = (k + 1) % rtlfm_gpu::kBinStages;
+	h->bank_bins_ps.assign(bins, bins + n);
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_get_channel_bins(rtlfm_gpu *h, int32_t *bins, int cap)
+{
+	if (!h || !bins || cap < 0 || h->bank_K <= 0 || h->chan_per <= 0) return -EINVAL;
+	if (cap < h->nstreams) return -ENOBUFS;
+	for (int s = 0; s < h->nstreams; s++)
+		bins[s] = h->bank_bins_ps.empty() ? h->bank_bins[(size_t)(s % h->chan_per)] : h->bank_bins_ps[(size_t)s];
 	return 0;
 }
 
@@ -1085,7 +1163,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"input_stats", &h->opt.input_stats}, {"input_stats_nt", &h->opt.input_stats_nt},
 		{"input_health", &h->opt.input_health},
 		{"squelch_gate", &h->opt.squelch_gate}, {"conseq_squelch", &h->opt.conseq_squelch},
-		{"source_ring", &h->opt.source_ring}, {"pack_results", &h->opt.pack_results},
+		{"source_ring", &h->opt.source_ring}, {"pack_results", &h->opt.pack_results}, {"bank_survey", &h->opt.bank_survey},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -1151,6 +1229,12 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 		if (ingest_busy(h)) return -EBUSY;
 		h->opt.pack_results = (int)value;
 		return value == 0 ? ingest_pack_free(h) : 0;
+	}
+	if (!strcmp(name, "bank_survey")) {
+		if (value != 0 && value != 1) return -EINVAL;
+		if (ingest_busy(h)) return -EBUSY;
+		h->opt.bank_survey = (int)value;
+		return value == 0 ? survey_free(h, true) : 0;
 	}
 	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
 	if (!strcmp(name, "source_ring")) {
@@ -2350,12 +2434,16 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 {
 	const int S = h->nstreams;
 	hipStream_t q = h->stream;
+	const bool ps = !h->bank_bins_ps.empty();
+	const int32_t *bins = ps ? h->d_bank_bins_ps : h->d_bank_bins;
+	const int bins_stride = ps ? h->chan_per : 0;
+	const int sv = h->sv.writing;  // -1: no survey (run_device_impl)
 	if (fused_path) {
-		const chanbank::Geometry g = chanbank::geometry(h->bank_m, h->bank_ntaps, cr.D);
+		const chanbank::Geometry g = chanbank::geometry(h->bank_m, h->bank_ntaps, cr.D, sv >= 0);
 		chanbank::BankParams p{};
 		p.f = cr.f;
 		p.hist_in = cr.hist_in; p.hist_out = cr.hist_out;
-		p.taps2 = h->d_bank_taps2; p.tw = h->d_bank_tw; p.bins = h->d_bank_bins;
+		p.taps2 = h->d_bank_taps2; p.tw = h->d_bank_tw; p.bins = bins; p.bins_stride = bins_stride;
 		p.m = g.m; p.Q = g.Q; p.Qp = g.Qp; p.lead = g.lead; p.F = g.F; p.Ls = g.Ls; p.Fs = g.Fs; p.shift = h->bank_shift;
 		p.f.ntiles = (cr.maxout + g.F - 1) / g.F;
 		// (frames are independent: every D goes with every segmentation - D = 1 for the plan; one workgroup per source and segment)
@@ -2363,7 +2451,21 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		              &p.f.tiles_per_seg);
 		const size_t grid = (size_t)cr.nsrc * p.f.segs;
 		if (grid > 0x7fffffffu) return -E2BIG;
-		chanbank::k_channel_bank<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+		if (sv < 0) {
+			chanbank::k_channel_bank<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+			return 0;
+		}
+		const size_t need = (grid << h->bank_m);
+		if (h->sv.partial_cap < need) {
+			if (h->sv.d_partial) { hipFree(h->sv.d_partial); h->sv.d_partial = nullptr; h->sv.partial_cap = 0; }  // (waits for what reads it)
+			HIP_TRY(hipMalloc(&h->sv.d_partial, need * sizeof(unsigned long long)));
+			h->sv.partial_cap = need;
+		}
+		p.survey = h->sv.d_partial;
+		chanbank::k_channel_bank_survey<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+		chanbank::k_bank_survey_reduce<<<grid_for((size_t)cr.nsrc << h->bank_m), 256, 0, q>>>(h->sv.d_partial, p.f.segs, h->bank_m, cr.nsrc,
+		                                                                                   h->chan_per, cr.Tin, cr.D, cr.sin, h->sv.d_power[sv],
+		                                                                                   h->sv.d_frames[sv]);
 		return 0;
 	}
 	const size_t vneed = ((size_t)cr.nsrc * cr.maxout) << h->bank_m;
@@ -2374,8 +2476,11 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 	                                                     cr.sin, h->bank_v);
 	chanbank::k_bank_fft<<<grid_for((size_t)cr.nsrc * cr.maxout), 256, 0, q>>>(h->bank_v, h->d_bank_sine, h->bank_m, cr.nsrc, h->chan_per, cr.Tin,
 	                                                                          cr.D, cr.maxout, cr.sin);
-	chanbank::k_bank_scatter<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->bank_v, h->d_bank_bins, h->bank_m, S, h->chan_per, cr.Tin, cr.D,
-	                                                                        cr.maxout, h->chan_iq, h->chan_stride, cr.dcnt, cr.sin, cr.sout);
+	chanbank::k_bank_scatter<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->bank_v, bins, (size_t)bins_stride, h->bank_m, S, h->chan_per, cr.Tin,
+	                                                                        cr.D, cr.maxout, h->chan_iq, h->chan_stride, cr.dcnt, cr.sin, cr.sout);
+	if (sv >= 0)
+		chanbank::k_bank_power_plain<<<grid_for((size_t)cr.nsrc << h->bank_m), 256, 0, q>>>(h->bank_v, h->bank_m, cr.nsrc, h->chan_per, cr.Tin, cr.D,
+		                                                                                 cr.maxout, cr.sin, h->sv.d_power[sv], h->sv.d_frames[sv]);
 	channel::k_source_history<<<grid_for((size_t)cr.nsrc * (channel::kHist / 8)), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, cr.hist_out,
 	                                                                                        cr.nsrc, cr.Tin);
 	return 0;
@@ -2633,6 +2738,86 @@ static int run_device_verified(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
                            int16_t *d_out, size_t out_stride, int32_t *d_out_len);
 
+// ---- the survey's two sets (option bank_survey) ----
+
+static int survey_free(rtlfm_gpu *h, bool wait)
+{
+	rtlfm_gpu::Survey &sv = h->sv;
+	if (wait && sv.d_power[0]) {
+		HIP_TRY(hipSetDevice(h->device));
+		HIP_TRY(sync_all(h));
+	}
+	for (int k = 0; k < 2; k++) {
+		if (sv.d_power[k]) hipFree(sv.d_power[k]);
+		if (sv.d_frames[k]) hipFree(sv.d_frames[k]);
+		if (sv.ev[k]) hipEventDestroy(sv.ev[k]);
+	}
+	if (sv.d_partial) hipFree(sv.d_partial);
+	sv = rtlfm_gpu::Survey{};
+	return 0;
+}
+
+// the sets, for the sources and the K there are now (grown behind whatever still reads them: what they held is gone)
+static int survey_ensure(rtlfm_gpu *h)
+{
+	rtlfm_gpu::Survey &sv = h->sv;
+	const int nsrc = h->nstreams / h->chan_per;
+	const size_t need = (size_t)nsrc * h->bank_K;
+	if (sv.d_power[0] && sv.cap >= need && sv.cap_srcs >= nsrc) return 0;
+	int r = survey_free(h, true);
+	if (r < 0) return r;
+	for (int k = 0; k < 2; k++) {
+		HIP_TRY(hipMalloc(&sv.d_power[k], need * sizeof(unsigned long long)));
+		HIP_TRY(hipMalloc(&sv.d_frames[k], (size_t)nsrc * sizeof(int32_t)));
+		HIP_TRY(hipEventCreateWithFlags(&sv.ev[k], hipEventDisableTiming));
+	}
+	sv.cap = need; sv.cap_srcs = nsrc;
+	return 0;
+}
+
+// a run has been queued: `wrote` is the set it wrote, or -1
+static void survey_advance(rtlfm_gpu *h, int wrote)
+{
+	rtlfm_gpu::Survey &sv = h->sv;
+	sv.prev = sv.last;
+	sv.last = wrote;
+	if (wrote >= 0) {
+		sv.K[wrote] = h->bank_K;
+		sv.nsrc[wrote] = h->nstreams / h->chan_per;
+		sv.next = wrote ^ 1;
+	}
+}
+
+static int survey_fetch(rtlfm_gpu *h, bool prev, uint64_t *power, size_t cap, int32_t *frames, int *K)
+{
+	if (!h || !K || !frames || (!power && cap)) return -EINVAL;
+	const rtlfm_gpu::Survey &sv = h->sv;
+	const int k = prev ? sv.prev : sv.last;
+	if (k < 0 || !sv.d_power[k]) return -ENODATA;
+	*K = sv.K[k];  // (written even where power does not fit)
+	const size_t n = (size_t)sv.nsrc[k] * sv.K[k];
+	if (cap < n) return -ENOBUFS;
+	HIP_TRY(hipSetDevice(h->device));
+	if (prev) {
+		HIP_TRY(hipEventSynchronize(sv.ev[k]));  // (that run's own event: not the run started since)
+	} else {
+		HIP_TRY(sync_all(h));
+	}
+	HIP_TRY(hipMemcpy(power, sv.d_power[k], n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(frames, sv.d_frames[k], (size_t)sv.nsrc[k] * sizeof(int32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_bank_survey(rtlfm_gpu *h, uint64_t *power, size_t cap, int32_t *frames, int *K)
+{
+	return survey_fetch(h, false, power, cap, frames, K);
+}
+
+extern "C" int rtlfm_gpu_bank_survey_prev(rtlfm_gpu *h, uint64_t *power, size_t cap, int32_t *frames, int *K)
+{
+	return survey_fetch(h, true, power, cap, frames, K);
+}
+
 extern "C" int rtlfm_gpu_run_device(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
                                     int16_t *d_out, size_t out_stride, int32_t *d_out_len)
 {
@@ -2653,9 +2838,21 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		const int g = ensure_gate(h);
 		if (g < 0) return g;
 	}
+	// the survey: of every run the bank takes while the option is on (both executions of a verified run write the same set:
+	// each stores, neither adds)
+	const bool surveyed = h->opt.bank_survey && h->chan_per > 0 && h->bank_K > 0;
+	if (surveyed) {
+		const int e = survey_ensure(h);
+		if (e < 0) return e;
+		h->sv.writing = h->sv.next;
+	}
 	const int r = h->opt.verify_twice ? run_device_verified(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
 	                                  : run_device_once(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
+	const int wrote = h->sv.writing;
+	h->sv.writing = -1;
 	if (r < 0) return r;
+	survey_advance(h, wrote);
+	if (wrote >= 0) HIP_TRY(hipEventRecord(h->sv.ev[wrote], h->stream));
 	h->st_cur = (h->st_cur + 1) % 3;
 	h->step++;
 	if (h->chan_per > 0) h->chan_pos += (uint64_t)nblocks * (h->cfg.block_len / 2);  // (once per run, also under verify_twice)
@@ -3257,6 +3454,7 @@ static rtlfm_gpu make_view(rtlfm_gpu *h, int s0, int ns, uint32_t block_len)
 	v.opt.input_health = 0;  // ... and the health records
 	v.mute_streams = 0;      // rtlfm_gpu_run_end has applied the mute to the whole run's input
 	v.opt.verify_twice = 0;  // views must not allocate (the shadow rows): ragged runs are not verified
+	v.opt.bank_survey = 0;   // ... nor surveyed: a survey is one run's, a view runs one buffer (run_ragged says so on the handle)
 	v.ev_pending.clear(); v.ev_free.clear();
 	const size_t cb = (size_t)h->cap_blocks;
 	for (int k = 0; k < 3; k++) v.st[k] = h->st[k] + s0;
@@ -3358,6 +3556,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	h->stats_nblocks = h->opt.input_stats ? nb : 0;
 	h->health_nblocks = h->opt.input_health ? nb : 0;
 	h->gate_nblocks = h->opt.squelch_gate ? nb : 0;
+	survey_advance(h, -1);  // (a run of short buffers carries no survey: rtlfm_gpu_bank_survey says -ENODATA)
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -3848,7 +4047,8 @@ extern "C" const char *rtlfm_gpu_strerror(int err)
 	case -ENOBUFS: return "output buffer too small";
 	case -EIO: return "HIP runtime error";
 	case -ENODATA: return "no clock stamps recorded (rtlfm_gpu_clock_probe, fused fifth_order path only); no records of this kind "
-	                      "(the option was off); rtlfm_gpu_fetch_packed: that run was not packed (option pack_results was 0)";
+	                      "(the option was off); rtlfm_gpu_fetch_packed: that run was not packed (option pack_results was 0); "
+	                      "rtlfm_gpu_bank_survey: that run carried no survey (option bank_survey off, no bank, or no run yet)";
 	default: return strerror(-err);
 	}
 }

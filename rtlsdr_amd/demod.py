@@ -306,6 +306,38 @@ class GpuDemod:
                                                   C.byref(sh)), "rtlfm_gpu_get_channel_bank")
         return K.value, (bins[:self._per_source].copy() if K.value else bins[:0].copy()), taps[:n.value].copy(), sh.value
 
+    def bank_survey(self, prev: bool = False):
+        """rtlfm_gpu_bank_survey (``prev``: _bank_survey_prev): ``(power uint64 [sources, K], frames int32 [sources])`` of
+        a run the bank took with the option ``bank_survey`` at 1 - every bin's summed ``Yi^2 + Yq^2`` over the frames the
+        run emitted, selected or not.  ``RtlfmError`` with -ENODATA where that run carried none."""
+        fn = self.lib.rtlfm_gpu_bank_survey_prev if prev else self.lib.rtlfm_gpu_bank_survey
+        what = "rtlfm_gpu_bank_survey_prev" if prev else "rtlfm_gpu_bank_survey"
+        nsrc = self.nstreams // self._per_source if self._per_source else self.nstreams
+        K = C.c_int()
+        frames = np.zeros(nsrc, dtype=np.int32)
+        r = fn(self._h, None, 0, frames.ctypes.data, C.byref(K))  # (the size first: K is written with -ENOBUFS)
+        if r < 0 and r != -105:
+            check(r, what)
+        power = np.zeros((nsrc, max(K.value, 1)), dtype=np.uint64)
+        check(fn(self._h, power.ctypes.data, power.size, frames.ctypes.data, C.byref(K)), what)
+        return power[:, :K.value], frames
+
+    def set_channel_bins(self, bins):
+        """rtlfm_gpu_set_channel_bins: ``bins`` int32 [sources, per_source] - channel c of source a becomes bin
+        ``bins[a][c]`` of the bank that is set.  Nothing else changes, nothing is waited for: runs already queued use the
+        old bins, later ones the new."""
+        b = np.ascontiguousarray(bins, dtype=np.int32)
+        if not self._per_source or b.size != self.nstreams:
+            raise ValueError(f"bins: [sources, per_source] = {self.nstreams} entries, not {b.shape}")
+        check(self.lib.rtlfm_gpu_set_channel_bins(self._h, b.ctypes.data), "rtlfm_gpu_set_channel_bins")
+
+    def channel_bins(self) -> np.ndarray:
+        """rtlfm_gpu_get_channel_bins: int32 [sources, per_source] as they rule now."""
+        per = max(self._per_source, 1)
+        out = np.zeros((self.nstreams // per, per), dtype=np.int32)
+        check(self.lib.rtlfm_gpu_get_channel_bins(self._h, out.ctypes.data, out.size), "rtlfm_gpu_get_channel_bins")
+        return out
+
     # -- state & plumbing ------------------------------------------------------
     def state_get(self, stream: int = 0) -> RtlfmStreamState:
         st = RtlfmStreamState()
