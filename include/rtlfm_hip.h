@@ -823,6 +823,11 @@ int rtlfm_gpu_selftest_fast_atan2(int device, const int32_t *yx, int n, int32_t 
  * divides by fast / slow (src/rtl_fm.c:769): the magic-number form of staged_kernels.h */
 int rtlfm_gpu_selftest_const_div(int device, const int32_t *nd, int n, int32_t *q);
 
+/* What the library's handles hold right now, process-wide (rtlfm_gpu and rtlpower_gpu alike): kind 0 device
+ * allocations, 1 pinned host allocations, 2 events; -EINVAL for any other kind.  For leak checks: the figures after
+ * destroying a handle equal those from before creating it. */
+long rtlfm_debug_live(int kind);
+
 /*
  * rotate_90 on raw u8 IQ (src/rtl_fm.c:437-447, NEG_U8(x) = 255 - x, :375-392): sample n
  * times (+j)^n, in place on device memory, len bytes (a multiple of 8, 16-byte aligned

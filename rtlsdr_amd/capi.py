@@ -378,6 +378,7 @@ _SIGNATURES = [
     ("rtlfm_gpu_selftest_atan2", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     ("rtlfm_gpu_selftest_fast_atan2", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     ("rtlfm_gpu_selftest_const_div", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    ("rtlfm_debug_live", C.c_long, [C.c_int]),
     ("rtlfm_gpu_rotate_90_u8", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("rtlfm_gpu_malloc", C.c_int, [C.c_int, C.c_size_t, _P(C.c_void_p)]),
     ("rtlfm_gpu_malloc_apart", C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, _P(C.c_void_p), _P(C.c_int)]),

@@ -864,12 +864,7 @@ inline int launch(fused::Workspace &ws, const rtlfm_cfg &c, int nstreams, const 
 	if (sp.nlist) memcpy(p.seg_start, sp.start, sizeof(int) * (size_t)(sp.nlist + 1));
 	const int waves = nstreams * sp.segs;
 #ifdef RTLFM_BOX_PHASES
-	if (ws.want_stamps) {
-		if (ws.stamp_waves < waves) { if (ws.stamps) hipFree(ws.stamps); ws.stamps = nullptr; ws.stamp_waves = 0; if (hipMalloc(&ws.stamps, (size_t)waves * 32 * 2) != hipSuccess) return -ENOMEM; ws.stamp_waves = waves; }
-		p.stamps = ws.stamps + (size_t)(ws.stamp_seq & 1) * ws.stamp_waves * 4;
-		ws.stamp_seq++;
-		ws.stamp_last = waves;
-	}
+	if (ws.want_stamps) OWN_TRY(fused::stamps_for(ws, waves, q, &p.stamps));
 #endif
 	const bool std_fm = c.custom_atan == RTLFM_ATAN_STD && c.mode == RTLFM_MODE_FM;
 	p.has_first = (p.D & 1) ? 1 : 0;

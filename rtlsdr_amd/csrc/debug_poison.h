@@ -8,24 +8,9 @@
 // per allocation / launch.  Include AFTER <hip/hip_runtime.h> and before any code that allocates.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <cstdlib>
+#include "device_own.h"  // poison_on(), and the allocation half: DevBuf and the hipMalloc macro
 
 namespace rtl_debug {
-
-inline bool poison_on()
-{
-	static const bool on = [] { const char *e = getenv("RTLFM_POISON"); return e && *e && *e != '0'; }();
-	return on;
-}
-
-inline hipError_t poison_malloc(void **p, size_t n)
-{
-	const hipError_t e = (hipMalloc)(p, n);  // (the parentheses keep the macro below out of this call)
-	if (e == hipSuccess && n && poison_on()) {
-		if ((hipMemset)(*p, 0xA5, n) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) return hipErrorUnknown;
-	}
-	return e;
-}
 
 // one workgroup per wave slot's share of the LDS: 16 waves x 10 KiB cover a CU's 160 KiB
 static __global__ void __launch_bounds__(64) k_poison_lds()
@@ -44,5 +29,3 @@ inline void poison_lds(hipStream_t q)
 }
 
 }  // namespace rtl_debug
-
-#define hipMalloc(p, n) ::rtl_debug::poison_malloc((void **)(p), (n))

@@ -43,6 +43,7 @@
 #include <type_traits>
 
 #include "dsp_device.h"
+#include "device_own.h"
 
 namespace rtlfm {
 namespace fused {
@@ -1364,14 +1365,14 @@ __global__ void __launch_bounds__(64, (P == 1 ? 2 : P == 2 ? 3 : RTLFM_FUSED_WAV
 }
 
 struct Workspace {
-	unsigned long long *stamps = nullptr;
-	int stamp_waves = 0;                          // capacity of stamps[]
+	DevBuf<unsigned long long> stamps;            // two halves of stamp_waves() waves, four stamps a wave
+	int stamp_waves() const { return (int)(stamps.capacity() / 8); }
 	int stamp_last = 0;                           // waves of the last launch that stamped
 	unsigned stamp_seq = 0;                       // stamped launches so far: they alternate between the two halves of stamps[]
 	// the half the last (back = 0) or the one before the last (back = 1) stamped launch wrote
-	const unsigned long long *stamp_half(int back) const { return stamps + (size_t)((stamp_seq + 1 + back) & 1) * stamp_waves * 4; }
-	uint32_t *mfma_taps[2] = {nullptr, nullptr};  // [rotate]
-	uint8_t *dummy_tile = nullptr;
+	const unsigned long long *stamp_half(int back) const { return stamps + (size_t)((stamp_seq + 1 + back) & 1) * stamp_waves() * 4; }
+	DevBuf<uint32_t> mfma_taps[2];                // [rotate]
+	DevBuf<uint8_t> dummy_tile;
 	int pass0_engine = -1;                        // 0 = v_dot4 (VALU), 1 = int8 MFMA; -1 = the compiled default (see launch)
 	bool want_stamps = false;                     // rtlfm_gpu_clock_probe(): every wave leaves its clock stamps
 	// segmentation (rtlfm_gpu_set_option: fused_waves, fused_min_tiles, fused_tiles_per_seg)
@@ -1396,14 +1397,6 @@ struct Workspace {
 	int fused_store = -1;                         // k_fused's PCM stores with 1-3 passes: -1 by the launch's output size, 0 plain, 1 non-temporal
 	int box_store = -1;                           // k_boxcar_scan's output stores: -1 by the launch's output size, 0 plain, 1 whole lines + nt
 	int debug = 0;                                // fused_debug: 2 = clock stamps per launch (+16: only on timing_read), 4 = reload a cached tile, 32 = stamp HW_ID / XCC_ID instead of the shader clock
-	void release()
-	{
-		if (stamps) hipFree(stamps);
-		stamps = nullptr;
-		for (auto &t : mfma_taps) { if (t) hipFree(t); t = nullptr; }
-		if (dummy_tile) hipFree(dummy_tile);
-		dummy_tile = nullptr;
-	}
 };
 
 // How a run of `total_tiles` tiles per stream is cut into segments (one wave each).  Every segment
@@ -1510,13 +1503,35 @@ inline bool supported_sq(const rtlfm_cfg &c)
 inline int ensure_dummy_tile(Workspace &ws)
 {
 	if (ws.dummy_tile) return 0;
-	if (hipMalloc(&ws.dummy_tile, kTileBytes) != hipSuccess) return -ENOMEM;
+	OWN_TRY(ws.dummy_tile.alloc(kTileBytes));
 	// hipMemset of device memory returns before the fill has run (it is a kernel on the null stream), and the handle's
 	// own stream is non-blocking: without the wait a first launch could read the tile before it is filled - the
 	// boxcar front end's partial last tile (-W n) then summed garbage behind the run's end into (now_r, now_j).
 	// Found by the extended sweep with four test processes sharing the GPU, where the fill was late often enough.
 	if (hipMemset(ws.dummy_tile, 0x7f, kTileBytes) != hipSuccess) return -EIO;
 	if (hipStreamSynchronize(nullptr) != hipSuccess) return -EIO;
+	return 0;
+}
+
+// pass 0's int8 MFMA tap table for this rotation
+inline int ensure_mfma_taps(Workspace &ws, int rotate)
+{
+	DevBuf<uint32_t> &t = ws.mfma_taps[rotate];
+	if (t) return 0;
+	uint32_t host[256];
+	make_mfma_taps(rotate != 0, host);
+	OWN_TRY(t.alloc(256));
+	return hipMemcpy(t, host, sizeof(host), hipMemcpyHostToDevice) == hipSuccess ? 0 : -EIO;
+}
+
+// Room for the clock stamps of a launch of `waves` waves (stamped launches alternate between two halves), and the half
+// this launch writes.  k_fused's and k_boxcar_scan's.
+inline int stamps_for(Workspace &ws, int waves, hipStream_t q, unsigned long long **half)
+{
+	OWN_TRY(ws.stamps.grow((size_t)waves * 8, q));
+	*half = ws.stamps + (size_t)(ws.stamp_seq & 1) * ws.stamp_waves() * 4;
+	ws.stamp_seq++;
+	ws.stamp_last = waves;
 	return 0;
 }
 
@@ -1590,14 +1605,8 @@ inline int launch(Workspace &ws, const rtlfm_cfg &c, int nstreams, const uint8_t
 	const int engine = effective_engine(ws);
 	if (rdc_avg && engine != 1) return -ENOTSUP;
 	if (engine == 1) {
-		uint32_t *&t = ws.mfma_taps[p.rotate];
-		if (!t) {
-			uint32_t host[256];
-			make_mfma_taps(p.rotate != 0, host);
-			if (hipMalloc(&t, sizeof(host)) != hipSuccess) return -ENOMEM;
-			if (hipMemcpy(t, host, sizeof(host), hipMemcpyHostToDevice) != hipSuccess) return -EIO;
-		}
-		p.mfma_taps = t;
+		OWN_TRY(ensure_mfma_taps(ws, p.rotate));
+		p.mfma_taps = ws.mfma_taps[p.rotate];
 	}
 	p.debug = ws.debug | (ws.tail_follows ? 128 : 0);
 	if (!emit_iq && c.downsample_passes <= 3) {
@@ -1614,12 +1623,7 @@ inline int launch(Workspace &ws, const rtlfm_cfg &c, int nstreams, const uint8_t
 	p.segs = sp.segs; p.tiles_per_seg = sp.tiles_per_seg; p.nlist = sp.nlist;
 	if (sp.nlist) memcpy(p.seg_start, sp.start, sizeof(int) * (size_t)(sp.nlist + 1));
 	const int waves = nstreams * sp.segs;
-	if (p.debug & 2) {
-		if (ws.stamp_waves < waves) { if (ws.stamps) hipFree(ws.stamps); ws.stamps = nullptr; ws.stamp_waves = 0; if (hipMalloc(&ws.stamps, (size_t)waves * 32 * 2) != hipSuccess) return -ENOMEM; ws.stamp_waves = waves; }
-		p.stamps = ws.stamps + (size_t)(ws.stamp_seq & 1) * ws.stamp_waves * 4;
-		ws.stamp_seq++;
-		ws.stamp_last = waves;
-	}
+	if (p.debug & 2) OWN_TRY(stamps_for(ws, waves, q, &p.stamps));
 	if (emit_iq) p.variant = RTLFM_ATAN_FAST;  // the emit path lives in the run-time-discriminator kernels
 	if (emit_iq && c.downsample_passes > kMaxP) return launch_one<6, false>(p, waves, q);  // the rest is staged
 	const bool fir = c.comp_fir_size == 9;

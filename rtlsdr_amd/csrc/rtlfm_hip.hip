@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/rtlfm_hip.h"
+#include "device_own.h"
 #include "debug_poison.h"
 #include "stream_pool.h"
 #include "staged_kernels.h"
@@ -55,7 +56,7 @@ struct rtlfm_gpu {
 	int device = 0;
 	hipStream_t own_stream = nullptr;
 	hipStream_t stream = nullptr;
-	hipEvent_t ev_wait = nullptr, ev_release = nullptr;  // rtlfm_gpu_wait_for / _release_to
+	Event ev_wait, ev_release;  // rtlfm_gpu_wait_for / _release_to
 	int path = 0, last_path = 0;
 
 	// geometry
@@ -64,114 +65,105 @@ struct rtlfm_gpu {
 	int cap_blocks = 0;
 
 	// device memory
-	uint32_t *bufA = nullptr, *bufB = nullptr;
+	DevBuf<uint32_t> bufA, bufB;
 	// demodulated samples on their way through the audio tail: [step parity][ping / pong], tstride
 	// int16 per stream.  Two sets, because the tail of step k runs on its own stream while the front
 	// end of step k + 1 already fills the other set.
-	int16_t *res[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-	bool res_one_block = false;  // res[0][0] and res[1][0] are ONE placed allocation (res[1][0] points into it)
+	DevBuf<int16_t> res[2][2];  // (placed: res[0][0] owns ONE block for both parities and res[1][0] is an alias into it)
 	size_t tstride = 0;
-	int32_t *d_cnt[2] = {nullptr, nullptr}, *d_cnt2 = nullptr;  // d_cnt: per step parity
-	DeemphChunk *d_deemph_tab = nullptr;  // time-parallel deemph (k_deemph_scan_*): [nstreams][deemph_chunks]
-	uint32_t *d_deemph_inc = nullptr;
-	LprChunk *d_lpr_chunks = nullptr;     // low_pass_real folded into the replay pass: [nstreams][deemph_chunks]
-	int32_t *d_arb_i = nullptr;           // k_deemph_spec_arb: (i, frac) of every output of a buffer, [arb_len2]
-	double *d_arb_frac = nullptr;
+	DevBuf<int32_t> d_cnt[2], d_cnt2;  // d_cnt: per step parity
+	DevBuf<DeemphChunk> d_deemph_tab;  // time-parallel deemph (k_deemph_scan_*): [nstreams][chunks]
+	DevBuf<uint32_t> d_deemph_inc;
+	DevBuf<LprChunk> d_lpr_chunks;     // low_pass_real folded into the replay pass: [nstreams][chunks]
+	DevBuf<int32_t> d_arb_i;              // k_deemph_spec_arb: (i, frac) of every output of a buffer, [arb_len2]
+	DevBuf<double> d_arb_frac;
 	int arb_len2 = 0, arb_len1 = 0;
-	int deemph_chunks = 0;   // capacity of d_deemph_tab / d_deemph_inc, chunks per stream
-	int lpr_chunks_cap = 0;  // ... of d_lpr_chunks
-	uint32_t *deepA = nullptr, *deepB = nullptr;  // /64 IQ work buffers of the 7..10-pass path
+	DevBuf<uint32_t> deepA, deepB;  // /64 IQ work buffers of the 7..10-pass path
 	size_t deep_stride = 0;
 	// Carried state, three copies in rotation: step k reads st[cur] and writes st[(cur + 1) % 3].
 	// The tail of step k (own stream) still reads st[cur] / writes the tail's fields of the next copy
 	// while the front end of step k + 1 reads that copy and writes the third one.
-	state_t *st[3] = {nullptr, nullptr, nullptr};
+	DevBuf<state_t> st[3];
 	int st_cur = 0;
 	unsigned step = 0;                      // parity selects res[] / d_cnt[] / the events
 	hipStream_t tail_stream = nullptr;
 	int tail_priority = 0;
 	int tail_prio_value = 0;                // the HIP priority tail_stream was taken from the pool with
-	hipEvent_t ev_front[2] = {nullptr, nullptr}, ev_tail[2] = {nullptr, nullptr};
+	Event ev_front[2], ev_tail[2];
 	bool tail_pending[2] = {false, false};  // ev_tail[p] has been recorded and not yet waited for
 	bool tail_overlap = true;
 	bool tail_serial_asked = false;         // option tail_serial: never overlap, whatever the stream
-	int32_t *d_lut = nullptr;
-	int32_t *d_mute = nullptr;        // [nstreams*cap_blocks]
-	int32_t *d_levels = nullptr;      // [nstreams*cap_blocks] rms() per buffer of the last run
+	DevBuf<int32_t> d_lut;
+	DevBuf<int32_t> d_mute;           // [nstreams*cap_blocks]
+	DevBuf<int32_t> d_levels;         // [nstreams*cap_blocks] rms() per buffer of the last run
 	int last_nblocks = 0;
-	rtlfm_input_stat *d_istats = nullptr;  // [nstreams*cap_blocks] ADC statistics of the raw bytes (option input_stats), allocated on first use
+	DevBuf<rtlfm_input_stat> d_istats;     // [nstreams*cap_blocks] ADC statistics of the raw bytes (option input_stats), allocated on first use
 	int stats_nblocks = 0;                 // buffers of the last run that have records ([stream][stats_nblocks])
-	rtlfm_input_health *d_ihealth = nullptr;  // the same for option input_health
+	DevBuf<rtlfm_input_health> d_ihealth;  // the same for option input_health
 	int health_nblocks = 0;
 	// scanning (scan_kernel.h): the gate's records of the last run, allocated on first use, and the hop mute's counts
-	rtlfm_gate_rec *d_gate = nullptr;      // [nstreams*cap_blocks]
+	DevBuf<rtlfm_gate_rec> d_gate;    // [nstreams*cap_blocks]
 	int gate_nblocks = 0;
 	size_t gate_rec_off = 0;               // stream-range views (ragged runs) write buffer j of the run: [stream][gate_rec_stride] + j
 	int gate_rec_stride = 0;               // 0: the run's own buffer count
-	uint32_t *mute_left = nullptr;         // host, [nstreams]: bytes rtlfm_gpu_mute still owes each stream; allocated by the first call
+	std::shared_ptr<uint32_t[]> mute_left; // host, [nstreams]: bytes rtlfm_gpu_mute still owes each stream; allocated by the first call (a view's copy shares it)
 	int mute_streams = 0;                  // streams with a count pending
-	scan::MuteEntry *d_mute_entries = nullptr;
-	size_t mute_entries_cap = 0;
-	int32_t *d_move_map = nullptr;         // [nstreams]: rtlfm_gpu_state_move's map on the device, allocated by the first move into this handle
+	DevBuf<scan::MuteEntry> d_mute_entries;
+	DevBuf<int32_t> d_move_map;            // [nstreams]: rtlfm_gpu_state_move's map on the device, allocated by the first move into this handle
 	// channels (channel_kernel.h; rtlfm_gpu_set_channels): stream s = channel s % chan_per of source s / chan_per
 	int chan_per = 0;                      // 0: off
 	uint64_t chan_pos = 0;                 // complex samples consumed since set_channels / reset / seek: ONE counter, the streams run in lockstep
-	uint32_t *d_chan_steps = nullptr;      // [nstreams]
-	uint32_t *d_chan_table = nullptr;      // [channel::kTableSize], uploaded by the first set_channels
-	uint32_t *chan_iq = nullptr;           // what a channel front end leaves for the back half: [nstreams][chan_stride] decimated IQ
+	DevBuf<uint32_t> d_chan_steps;         // [nstreams]
+	DevBuf<uint32_t> d_chan_table;         // [channel::kTableSize], uploaded by the first set_channels
+	DevBuf<uint32_t> chan_iq;              // what a channel front end leaves for the back half: [nstreams][chan_stride] decimated IQ
 	size_t chan_stride = 0;
 	// the source history of the filter and the bank (channel_kernel.h, kHist): [src_hist_srcs][channel::kHist * 2] raw bytes,
 	// every SOURCE's last samples; a run reads [src_hist_cur] and writes the other
-	uint8_t *d_src_hist[2] = {nullptr, nullptr};
+	DevBuf<uint8_t> d_src_hist[2];
 	int src_hist_cur = 0, src_hist_srcs = 0;
 	// the channel filter (channel_fir_kernel.h; rtlfm_gpu_set_channel_filter): acts while channels are on
 	int fir_ntaps = 0, fir_shift = 0;      // 0 taps: none, the boxcar
 	std::vector<int16_t> fir_taps;         // what the getter hands back
-	int16_t *d_fir_taps = nullptr;         // [ntaps], k_channel_fir_plain's
-	uint32_t *d_fir_taps8 = nullptr;       // chanfir::shifted_taps(), k_channel_fir's
-	uint32_t *chan_fir_x = nullptr;        // path 1: k_channel_mix's samples of the history's end and the run, [nstreams][chan_fir_xstride]
+	DevBuf<int16_t> d_fir_taps;            // [ntaps], k_channel_fir_plain's
+	DevBuf<uint32_t> d_fir_taps8;          // chanfir::shifted_taps(), k_channel_fir's
+	DevBuf<uint32_t> chan_fir_x;           // path 1: k_channel_mix's samples of the history's end and the run, [nstreams][chan_fir_xstride]
 	size_t chan_fir_xstride = 0;
 	// the channel bank (channel_bank_kernel.h; rtlfm_gpu_set_channel_bank): while on it takes the mixer paths' place
 	int bank_m = 0, bank_K = 0, bank_ntaps = 0, bank_shift = 0;  // K == 0: none
 	std::vector<int16_t> bank_taps;        // what the getter hands back
 	std::vector<int32_t> bank_bins;        // [chan_per]
-	int16_t *d_bank_taps = nullptr;        // [ntaps], k_bank_sums'
-	uint32_t *d_bank_taps2 = nullptr;      // chanbank::branch_taps(), k_channel_bank's
-	uint32_t *d_bank_tw = nullptr;         // [K] twiddles per stage, doubled and packed
-	int16_t *d_bank_sine = nullptr;        // [3 K / 4] sine_table(m), k_bank_fft's
-	int32_t *d_bank_bins = nullptr;        // [chan_per]
-	uint32_t *bank_v = nullptr;            // path 1: [sources][maxout][K] sums, transformed in place
-	size_t bank_v_dwords = 0;
+	DevBuf<int16_t> d_bank_taps;           // [ntaps], k_bank_sums'
+	DevBuf<uint32_t> d_bank_taps2;         // chanbank::branch_taps(), k_channel_bank's
+	DevBuf<uint32_t> d_bank_tw;            // [K] twiddles per stage, doubled and packed
+	DevBuf<int16_t> d_bank_sine;           // [3 K / 4] sine_table(m), k_bank_fft's
+	DevBuf<int32_t> d_bank_bins;           // [chan_per]
+	DevBuf<uint32_t> bank_v;               // path 1: [sources][maxout][K] sums, transformed in place
 	// per-source bins (rtlfm_gpu_set_channel_bins): while set they rule in d_bank_bins' place, chan_per apart per source.
 	// The setter copies through a rotation of pinned buffers on the handle's stream and waits for nothing but a buffer
 	// whose own copy, kBinStages calls ago, has not left yet.
 	static constexpr int kBinStages = 4;
 	std::vector<int32_t> bank_bins_ps;     // [sources][chan_per]; empty: the shared list
-	int32_t *d_bank_bins_ps = nullptr;
-	size_t bank_bins_ps_cap = 0;
-	int32_t *h_bins_stage[kBinStages] = {nullptr, nullptr, nullptr, nullptr};
-	hipEvent_t ev_bins_stage[kBinStages] = {nullptr, nullptr, nullptr, nullptr};
-	size_t bins_stage_cap = 0;
+	DevBuf<int32_t> d_bank_bins_ps;
+	PinnedBuf<int32_t> h_bins_stage[kBinStages];
+	Event ev_bins_stage[kBinStages];
 	int bins_stage_next = 0;
 	// the survey (option bank_survey; rtlfm_gpu_bank_survey): two sets in rotation, as the ring's halves rotate - a surveyed
 	// run writes the set the last surveyed run did not; allocated by the first surveyed run
 	struct Survey {
-		unsigned long long *d_power[2] = {nullptr, nullptr};  // [sources][K]
-		int32_t *d_frames[2] = {nullptr, nullptr};            // [sources]
-		hipEvent_t ev[2] = {nullptr, nullptr};                // behind the set's last launch
-		size_t cap = 0;                                       // elements of d_power[k]
+		DevBuf<unsigned long long> d_power[2];                // [sources][K]
+		DevBuf<int32_t> d_frames[2];                          // [sources]
+		Event ev[2];                                          // behind the set's last launch
 		int cap_srcs = 0;
-		unsigned long long *d_partial = nullptr;              // k_channel_bank_survey's: [sources][segs][K]
-		size_t partial_cap = 0;
+		DevBuf<unsigned long long> d_partial;                 // k_channel_bank_survey's: [sources][segs][K]
 		int K[2] = {0, 0}, nsrc[2] = {0, 0};                  // what the set holds
 		int last = -1, prev = -1;                             // the set of the last run and of the run before it; -1: that run carried none
 		int writing = -1;                                     // the set the run being launched writes
 		int next = 0;
 	} sv;
-	long long *d_sums = nullptr;      // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
-	long long *d_adc_sums = nullptr;  // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
-	uint32_t *d_sq_sums = nullptr;    // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
-	int2 *d_rdc_avg = nullptr;        // [nstreams*cap_blocks]
+	DevBuf<long long> d_sums;         // [nstreams*cap_blocks*2]  dc_block_raw (front end's stream)
+	DevBuf<long long> d_adc_sums;     // [nstreams*cap_blocks]    dc_block_audio (the tail's stream)
+	DevBuf<uint32_t> d_sq_sums;       // [nstreams*cap_blocks*2]  rms()'s sums taken by the boxcar front end (SQ kernels)
+	DevBuf<int2> d_rdc_avg;           // [nstreams*cap_blocks]
 	struct Ingest *ing = nullptr;     // the callback side (push / run / fetch), allocated on first use
 	bool no_deemph_scan = false;      // stream-range views (ragged runs) keep to the sequential filter
 	// placement of the write streams (rtlfm_gpu_malloc_apart_ex): what the searches found and what they cost
@@ -208,18 +200,17 @@ struct rtlfm_gpu {
 		int bank_survey = 0;   // 1: a run the bank takes leaves every bin's power as well (k_channel_bank_survey; rtlfm_gpu_bank_survey)
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
-	int16_t *vt_out = nullptr;
-	size_t vt_out_cap = 0;        // int16 elements
-	int32_t *vt_len = nullptr, *vt_len2 = nullptr;
-	state_t *vt_state = nullptr;
-	rtlfm_gate_rec *vt_gate = nullptr;     // the first execution's gate records
-	unsigned long long *vt_cnt = nullptr;  // [4]: differing PCM dwords, differing lengths, differing state dwords, first differing (stream << 32 | index) + 1
+	DevBuf<int16_t> vt_out;
+	DevBuf<int32_t> vt_len, vt_len2;
+	DevBuf<state_t> vt_state;
+	DevBuf<rtlfm_gate_rec> vt_gate;        // the first execution's gate records
+	DevBuf<unsigned long long> vt_cnt;     // [4]: differing PCM dwords, differing lengths, differing state dwords, first differing (stream << 32 | index) + 1
 	long vt_mismatches = 0, vt_runs = 0;
 
 	// timing of the decimating front end
 	bool timing = false;
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_free;
+	std::vector<std::pair<Event, Event>> ev_pending;
+	std::vector<std::pair<Event, Event>> ev_free;
 };
 
 // ------------------------------------------------------------ host planner ----
@@ -439,11 +430,11 @@ static int create_body(rtlfm_gpu *h)
 	HIP_TRY(rtl_pool::stream_get(h->device, 0, &h->own_stream));  // (from the process-wide pool: stream_pool.h)
 	h->stream = h->own_stream;
 	const size_t S = (size_t)nstreams;
-	for (int k = 0; k < 3; k++) HIP_TRY(hipMalloc(&h->st[k], S * sizeof(state_t)));
+	for (int k = 0; k < 3; k++) OWN_TRY(h->st[k].alloc(S));
 	for (int k = 0; k < 2; k++) {
-		HIP_TRY(hipMalloc(&h->d_cnt[k], S * sizeof(int32_t)));
-		HIP_TRY(hipEventCreateWithFlags(&h->ev_front[k], hipEventDisableTiming));
-		HIP_TRY(hipEventCreateWithFlags(&h->ev_tail[k], hipEventDisableTiming));
+		OWN_TRY(h->d_cnt[k].alloc(S));
+		OWN_TRY(h->ev_front[k].create(hipEventDisableTiming));
+		OWN_TRY(h->ev_tail[k].create(hipEventDisableTiming));
 	}
 	// (default priority: the highest and the lowest one were both tried - round 3: highest 1 % slower; round 4,
 	// three alternations on one box: c3 0.883 / 0.881 / 0.883 ms, wbfm 1.381 / 1.381 / 1.379 for default / lowest /
@@ -468,20 +459,20 @@ static int create_body(rtlfm_gpu *h)
 		                                              : (cfg->downsample > 1 ? n0 / cfg->downsample + 1 : n0);
 		h->tstride = ((size_t)h->cap_blocks * per + 64 + 63) & ~(size_t)63;
 	}
-	HIP_TRY(hipMalloc(&h->d_cnt2, S * sizeof(int32_t)));
-	HIP_TRY(hipMalloc(&h->d_mute, S * h->cap_blocks * sizeof(int32_t)));
-	HIP_TRY(hipMalloc(&h->d_levels, S * h->cap_blocks * sizeof(int32_t)));
-	HIP_TRY(hipMalloc(&h->d_sums, S * h->cap_blocks * 2 * sizeof(long long)));
-	HIP_TRY(hipMalloc(&h->d_adc_sums, S * h->cap_blocks * sizeof(long long)));
-	HIP_TRY(hipMalloc(&h->d_rdc_avg, (S * h->cap_blocks + 32) * sizeof(int2)));  // (+ slack: k_boxcar_scan reads kRdcMany entries from a tile's first buffer on)
-	HIP_TRY(hipMalloc(&h->d_sq_sums, S * h->cap_blocks * 2 * sizeof(uint32_t)));
+	OWN_TRY(h->d_cnt2.alloc(S));
+	OWN_TRY(h->d_mute.alloc(S * h->cap_blocks));
+	OWN_TRY(h->d_levels.alloc(S * h->cap_blocks));
+	OWN_TRY(h->d_sums.alloc(S * h->cap_blocks * 2));
+	OWN_TRY(h->d_adc_sums.alloc(S * h->cap_blocks));
+	OWN_TRY(h->d_rdc_avg.alloc(S * h->cap_blocks + 32));  // (+ slack: k_boxcar_scan reads kRdcMany entries from a tile's first buffer on)
+	OWN_TRY(h->d_sq_sums.alloc(S * h->cap_blocks * 2));
 	if (cfg->custom_atan == RTLFM_ATAN_LUT) {
 		// atan_lut_init(), src/rtl_fm.c:881-892 — built with the host libm, as
 		// the reference builds it
 		std::vector<int32_t> lut(131072);
 		for (int i = 0; i < 131072; i++)
 			lut[i] = (int32_t)(atan((double)i / 256.0) / 3.14159 * 16384.0);
-		HIP_TRY(hipMalloc(&h->d_lut, lut.size() * sizeof(int32_t)));
+		OWN_TRY(h->d_lut.alloc(lut.size()));
 		HIP_TRY(hipMemcpy(h->d_lut, lut.data(), lut.size() * sizeof(int32_t), hipMemcpyHostToDevice));
 	}
 	int r = options_from_env(h);
@@ -492,11 +483,8 @@ static int create_body(rtlfm_gpu *h)
 static int ensure_work_buffers(rtlfm_gpu *h)
 {
 	const size_t S = (size_t)h->nstreams;
-	if (!h->bufA) {
-		HIP_TRY(hipMalloc(&h->bufA, S * h->xstride * sizeof(uint32_t)));
-		HIP_TRY(hipMalloc(&h->bufB, S * h->xstride * sizeof(uint32_t)));
-	}
-	return 0;
+	OWN_TRY(h->bufA.alloc(S * h->xstride));
+	return h->bufB.alloc(S * h->xstride);
 }
 // the decimated IQ a front end in emit mode leaves for the staged kernels: /2^level behind fifth_order passes
 // (run_fused_emit), 1 / D (+ 1 per buffer) behind the boxcar (run_boxfused_emit)
@@ -524,15 +512,15 @@ static int ensure_deep_buffers(rtlfm_gpu *h, const uint8_t *d_iq = nullptr, size
 		void *q = nullptr; int apart = 0; double ms = 0; size_t walked = 0;
 		int r = rtlfm_gpu_malloc_apart_ex(h->device, bytes, d_iq, iq_bytes, (size_t)h->place.budget_gb << 30, &q, &apart, &ms, &walked);
 		if (r < 0) return r;
-		h->deepA = static_cast<uint32_t *>(q);
+		OWN_TRY(h->deepA.adopt(q, bytes / sizeof(uint32_t)));
 		h->place.search_ms += ms;
 		if (walked > h->place.walked_peak) h->place.walked_peak = walked;
 		h->place.deep_apart = apart;
 	} else {
-		HIP_TRY(hipMalloc(&h->deepA, bytes));
+		OWN_TRY(h->deepA.alloc(bytes / sizeof(uint32_t)));
 		h->place.deep_apart = 0;
 	}
-	if (fifth) HIP_TRY(hipMalloc(&h->deepB, bytes));
+	if (fifth) OWN_TRY(h->deepB.alloc(bytes / sizeof(uint32_t)));
 	return 0;
 }
 // d_iq / iq_bytes: the input the first run streams from - the buffers the front end writes the demodulated
@@ -548,20 +536,19 @@ static int ensure_res_buffers(rtlfm_gpu *h, const uint8_t *d_iq = nullptr, size_
 		const size_t one = (S * h->tstride * sizeof(int16_t) + 255) & ~(size_t)255;
 		int apart = 0;
 		if (search) {
-			// the two buffers the front end writes (one per step parity) as ONE placed block: one search, and a
-			// candidate that had to be larger than the request (rtlfm_gpu_malloc_apart_ex) is shared by both
+			// the two buffers the front end writes (one per step parity) as ONE placed block, the second an alias into it:
+			// one search, and a candidate that had to be larger than the request (rtlfm_gpu_malloc_apart_ex) is shared by both
 			void *q = nullptr; double ms = 0; size_t walked = 0;
 			int r = rtlfm_gpu_malloc_apart_ex(h->device, 2 * one, d_iq, iq_bytes, (size_t)h->place.budget_gb << 30, &q, &apart, &ms, &walked);
 			if (r < 0) return r;
 			h->place.search_ms += ms;
 			if (walked > h->place.walked_peak) h->place.walked_peak = walked;
-			h->res[0][0] = (int16_t *)q;
-			h->res[1][0] = (int16_t *)((char *)q + one);
-			h->res_one_block = true;
+			OWN_TRY(h->res[0][0].adopt(q, 2 * one / sizeof(int16_t)));
+			h->res[1][0] = h->res[0][0].alias(one / sizeof(int16_t));
 		} else {
-			for (int p = 0; p < 2; p++) HIP_TRY(hipMalloc(&h->res[p][0], one));
+			for (int p = 0; p < 2; p++) OWN_TRY(h->res[p][0].alloc(one / sizeof(int16_t)));
 		}
-		for (int p = 0; p < 2; p++) HIP_TRY(hipMalloc(&h->res[p][1], one));
+		for (int p = 0; p < 2; p++) OWN_TRY(h->res[p][1].alloc(one / sizeof(int16_t)));
 		h->place.res_apart = apart;
 	}
 	return 0;
@@ -579,26 +566,6 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	hipSetDevice(h->device);
 	if (h->stream) hipStreamSynchronize(h->stream);
 	if (h->tail_stream) hipStreamSynchronize(h->tail_stream);
-	for (hipEvent_t e : {h->ev_wait, h->ev_release, h->ev_front[0], h->ev_front[1], h->ev_tail[0], h->ev_tail[1]})
-		if (e) hipEventDestroy(e);
-	for (auto &p : h->ev_pending) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-	for (auto &p : h->ev_free) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
-	void *ptrs[] = {h->d_arb_i, h->d_arb_frac, h->d_deemph_tab, h->d_deemph_inc, h->d_lpr_chunks, h->deepA, h->deepB, h->bufA, h->bufB, h->res[0][0], h->res[0][1], h->res_one_block ? nullptr : (void *)h->res[1][0], h->res[1][1],
-	                h->d_cnt[0], h->d_cnt[1], h->d_cnt2,
-	                h->st[0], h->st[1], h->st[2], h->d_lut, h->d_mute, h->d_levels, h->d_sq_sums, h->d_sums, h->d_adc_sums, h->d_rdc_avg,
-	                h->vt_out, h->vt_len, h->vt_len2, h->vt_state, h->vt_cnt, h->d_istats, h->d_ihealth,
-	                h->d_gate, h->vt_gate, h->d_mute_entries, h->d_move_map, h->d_chan_steps, h->d_chan_table, h->chan_iq,
-	                h->d_src_hist[0], h->d_src_hist[1], h->d_fir_taps, h->d_fir_taps8, h->chan_fir_x,
-	                h->d_bank_taps, h->d_bank_taps2, h->d_bank_tw, h->d_bank_sine, h->d_bank_bins, h->bank_v, h->d_bank_bins_ps};
-	for (void *p : ptrs)
-		if (p) hipFree(p);
-	(void)survey_free(h, false);
-	for (int k = 0; k < rtlfm_gpu::kBinStages; k++) {
-		if (h->h_bins_stage[k]) hipHostFree(h->h_bins_stage[k]);
-		if (h->ev_bins_stage[k]) hipEventDestroy(h->ev_bins_stage[k]);
-	}
-	delete[] h->mute_left;
-	h->fws.release();
 	ingest_destroy(h);
 	// The streams go back to the process-wide pool, never to hipStreamDestroy (stream_pool.h: the runtime releases a freed
 	// object of a destroyed stream once more, later, in whoever's memory it has become - LAB.md I.21).
@@ -634,8 +601,7 @@ static int ensure_history(rtlfm_gpu *h)
 	if (h->src_hist_srcs < nsrc) {
 		h->src_hist_srcs = 0;  // (until both copies are there: chan_run_prepare refuses a run without them)
 		for (int i = 0; i < 2; i++) {
-			if (h->d_src_hist[i]) { hipFree(h->d_src_hist[i]); h->d_src_hist[i] = nullptr; }
-			HIP_TRY(hipMalloc(&h->d_src_hist[i], (size_t)nsrc * channel::kHist * 2));
+			OWN_TRY(h->d_src_hist[i].grow((size_t)nsrc * channel::kHist * 2, h->stream));
 		}
 		h->src_hist_srcs = nsrc;
 	}
@@ -702,7 +668,7 @@ static int set_mutes(rtlfm_gpu *h, const uint32_t *mutes)
 	for (int s = 0; s < h->nstreams; s++) any |= mutes[s] != 0;
 	if (!h->mute_left) {
 		if (!any) return 0;
-		h->mute_left = new (std::nothrow) uint32_t[(size_t)h->nstreams]();
+		h->mute_left.reset(new (std::nothrow) uint32_t[(size_t)h->nstreams]());
 		if (!h->mute_left) return -ENOMEM;
 	}
 	h->mute_streams = 0;
@@ -736,7 +702,7 @@ extern "C" int rtlfm_gpu_state_move(rtlfm_gpu *dst, rtlfm_gpu *src, const int32_
 		for (int k = 0; k < n; k++)
 			if (map[k] >= 0) mutes[(size_t)k] = src->mute_left[map[k]];
 	HIP_TRY(hipSetDevice(dst->device));
-	if (!dst->d_move_map) HIP_TRY(hipMalloc(&dst->d_move_map, (size_t)n * sizeof(int32_t)));
+	OWN_TRY(dst->d_move_map.alloc((size_t)n));
 	HIP_TRY(sync_all(src));
 	if (src != dst) HIP_TRY(sync_all(dst));
 	HIP_TRY(hipMemcpy(dst->d_move_map, map, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -773,7 +739,7 @@ extern "C" int rtlfm_gpu_save(rtlfm_gpu *h, const char *path)
 	int n = 0;
 	const int r = rtlfm_gpu_state_get_all(h, st.data(), h->nstreams, &n);
 	if (r < 0) return r;
-	if (h->mute_left) memcpy(mutes.data(), h->mute_left, mutes.size() * sizeof(uint32_t));
+	if (h->mute_left) memcpy(mutes.data(), h->mute_left.get(), mutes.size() * sizeof(uint32_t));
 	return rtlfm_snapshot_write(path, &h->cfg, h->nstreams, st.data(), mutes.data());
 }
 
@@ -834,12 +800,12 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 		if (!h->d_chan_table) {
 			std::vector<int16_t> tab(2 * channel::kTableSize);
 			channel::build_table(tab.data());  // (int16 cos, int16 sin = the kernels' packed dword)
-			uint32_t *d = nullptr;
-			HIP_TRY(hipMalloc(&d, channel::kTableSize * sizeof(uint32_t)));
-			if (hipMemcpy(d, tab.data(), channel::kTableSize * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) { hipFree(d); return -EIO; }
-			h->d_chan_table = d;
+			DevBuf<uint32_t> d;
+			OWN_TRY(d.alloc(channel::kTableSize));
+			if (hipMemcpy(d, tab.data(), channel::kTableSize * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return -EIO;
+			h->d_chan_table = std::move(d);
 		}
-		if (!h->d_chan_steps) HIP_TRY(hipMalloc(&h->d_chan_steps, (size_t)h->nstreams * sizeof(uint32_t)));
+		OWN_TRY(h->d_chan_steps.alloc((size_t)h->nstreams));
 		HIP_TRY(hipMemcpy(h->d_chan_steps, steps, (size_t)h->nstreams * sizeof(uint32_t), hipMemcpyHostToDevice));
 	}
 	h->chan_per = per_source;
@@ -910,9 +876,8 @@ extern "C" int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, i
 	HIP_TRY(hipSetDevice(h->device));
 	HIP_TRY(sync_all(h));
 	if (ntaps > 0) {
-		if (!h->d_fir_taps) HIP_TRY(hipMalloc(&h->d_fir_taps, RTLFM_CHANNEL_MAX_TAPS * sizeof(int16_t)));
-		if (!h->d_fir_taps8)
-			HIP_TRY(hipMalloc(&h->d_fir_taps8, (size_t)chanfir::kGroup * chanfir::padded_taps(RTLFM_CHANNEL_MAX_TAPS) * sizeof(int16_t)));
+		OWN_TRY(h->d_fir_taps.alloc(RTLFM_CHANNEL_MAX_TAPS));
+		OWN_TRY(h->d_fir_taps8.alloc((size_t)chanfir::kGroup * chanfir::padded_taps(RTLFM_CHANNEL_MAX_TAPS) * sizeof(int16_t) / sizeof(uint32_t)));
 		std::vector<int16_t> t8((size_t)chanfir::kGroup * chanfir::padded_taps(ntaps));
 		chanfir::shifted_taps(taps, ntaps, t8.data());
 		HIP_TRY(hipMemcpy(h->d_fir_taps, taps, (size_t)ntaps * sizeof(int16_t), hipMemcpyHostToDevice));
@@ -945,11 +910,11 @@ extern "C" int rtlfm_channel_bank_check(int K, const int16_t *taps, int ntaps, i
 }
 
 template <typename T>
-static int bank_upload(T **dst, const T *src, size_t n)
+static int bank_upload(DevBuf<T> &dst, const T *src, size_t n)
 {
-	if (*dst) { hipFree(*dst); *dst = nullptr; }
-	HIP_TRY(hipMalloc(dst, n * sizeof(T)));
-	HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+	dst.reset();  // (the handle is idle: the caller has waited for it)
+	OWN_TRY(dst.alloc(n));
+	HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice));
 	return 0;
 }
 
@@ -995,11 +960,11 @@ extern "C" int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bi
 			tw[(size_t)(1 << st) - 1 + q] = (uint32_t)(uint16_t)(wr * 2) | ((uint32_t)(uint16_t)(wi * 2) << 16);
 		}
 	int r;
-	if ((r = bank_upload(&h->d_bank_taps, taps, (size_t)ntaps)) < 0) return r;
-	if ((r = bank_upload(&h->d_bank_taps2, reinterpret_cast<const uint32_t *>(t2.data()), t2.size() / 2)) < 0) return r;
-	if ((r = bank_upload(&h->d_bank_tw, tw.data(), tw.size())) < 0) return r;
-	if ((r = bank_upload(&h->d_bank_sine, sine.data(), sine.size())) < 0) return r;
-	if ((r = bank_upload(&h->d_bank_bins, b.data(), b.size())) < 0) return r;
+	if ((r = bank_upload(h->d_bank_taps, taps, (size_t)ntaps)) < 0) return r;
+	if ((r = bank_upload(h->d_bank_taps2, reinterpret_cast<const uint32_t *>(t2.data()), t2.size() / 2)) < 0) return r;
+	if ((r = bank_upload(h->d_bank_tw, tw.data(), tw.size())) < 0) return r;
+	if ((r = bank_upload(h->d_bank_sine, sine.data(), sine.size())) < 0) return r;
+	if ((r = bank_upload(h->d_bank_bins, b.data(), b.size())) < 0) return r;
 	h->bank_taps.assign(taps, taps + ntaps);
 	h->bank_bins = b;
 	h->bank_bins_ps.clear();  // (the shared list again)
@@ -1033,16 +998,10 @@ extern "C" int rtlfm_gpu_set_channel_bins(rtlfm_gpu *h, const int32_t *bins)
 		if (bins[i] < 0 || bins[i] >= h->bank_K) return -EINVAL;
 	if (ingest_busy(h)) return -EBUSY;
 	HIP_TRY(hipSetDevice(h->device));
-	if (h->bank_bins_ps_cap < n) {
-		HIP_TRY(hipMalloc(&h->d_bank_bins_ps, n * sizeof(int32_t)));  // (the first call: a handle's stream count never changes)
-		h->bank_bins_ps_cap = n;
-	}
-	if (h->bins_stage_cap < n) {
-		for (int k = 0; k < rtlfm_gpu::kBinStages; k++) {
-			HIP_TRY(hipHostMalloc(&h->h_bins_stage[k], n * sizeof(int32_t), hipHostMallocDefault));
-			HIP_TRY(hipEventCreateWithFlags(&h->ev_bins_stage[k], hipEventDisableTiming));
-		}
-		h->bins_stage_cap = n;
+	OWN_TRY(h->d_bank_bins_ps.alloc(n));  // (the first call: a handle's stream count never changes)
+	for (int k = 0; k < rtlfm_gpu::kBinStages; k++) {
+		OWN_TRY(h->h_bins_stage[k].alloc(n));
+		OWN_TRY(h->ev_bins_stage[k].create(hipEventDisableTiming));
 	}
 	const int k = h->bins_stage_next;
 	HIP_TRY(hipEventSynchronize(h->ev_bins_stage[k]));  // (an event never recorded is complete)
@@ -1107,7 +1066,7 @@ extern "C" int rtlfm_gpu_wait_for(rtlfm_gpu *h, void *producer_stream)
 	if (!h) return -EINVAL;
 	if ((hipStream_t)producer_stream == h->stream) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	if (!h->ev_wait) HIP_TRY(hipEventCreateWithFlags(&h->ev_wait, hipEventDisableTiming));
+	OWN_TRY(h->ev_wait.create(hipEventDisableTiming));
 	HIP_TRY(hipEventRecord(h->ev_wait, (hipStream_t)producer_stream));
 	HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_wait, 0));
 	return 0;
@@ -1118,7 +1077,7 @@ extern "C" int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream)
 	if (!h) return -EINVAL;
 	if ((hipStream_t)consumer_stream == h->stream) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	if (!h->ev_release) HIP_TRY(hipEventCreateWithFlags(&h->ev_release, hipEventDisableTiming));
+	OWN_TRY(h->ev_release.create(hipEventDisableTiming));
 	HIP_TRY(hipEventRecord(h->ev_release, h->stream));
 	HIP_TRY(hipStreamWaitEvent((hipStream_t)consumer_stream, h->ev_release, 0));
 	for (int p = 0; p < 2; p++)  // and for the audio tails still running on their own stream
@@ -1338,7 +1297,7 @@ extern "C" int rtlfm_gpu_timing_read(rtlfm_gpu *h, double *front_ms, int *launch
 		HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
 		total += ms;
 		n++;
-		h->ev_free.push_back(p);
+		h->ev_free.push_back(std::move(p));
 	}
 	h->ev_pending.clear();
 	if (front_ms) *front_ms = total;
@@ -1346,24 +1305,24 @@ extern "C" int rtlfm_gpu_timing_read(rtlfm_gpu *h, double *front_ms, int *launch
 	return 0;
 }
 
-static int timing_begin(rtlfm_gpu *h, std::pair<hipEvent_t, hipEvent_t> &ev)
+static int timing_begin(rtlfm_gpu *h, std::pair<Event, Event> &ev)
 {
 	if (!h->timing) return 0;
 	if (!h->ev_free.empty()) {
-		ev = h->ev_free.back();
+		ev = std::move(h->ev_free.back());
 		h->ev_free.pop_back();
 	} else {
-		HIP_TRY(hipEventCreate(&ev.first));
-		HIP_TRY(hipEventCreate(&ev.second));
+		OWN_TRY(ev.first.create());
+		OWN_TRY(ev.second.create());
 	}
 	HIP_TRY(hipEventRecord(ev.first, h->stream));
 	return 0;
 }
-static int timing_end(rtlfm_gpu *h, std::pair<hipEvent_t, hipEvent_t> &ev)
+static int timing_end(rtlfm_gpu *h, std::pair<Event, Event> &ev)
 {
 	if (!h->timing) return 0;
 	HIP_TRY(hipEventRecord(ev.second, h->stream));
-	h->ev_pending.push_back(ev);
+	h->ev_pending.push_back(std::move(ev));
 	return 0;
 }
 
@@ -1500,7 +1459,7 @@ struct TailRun {
 	int16_t *dst; size_t dst_stride;  // where the out-of-place stage at hand writes (out_of_place() ... arrived())
 	void out_of_place()
 	{
-		int16_t *const *res = h->res[h->step & 1];
+		const DevBuf<int16_t> *res = h->res[h->step & 1];
 		dst = --remaining_oop == 0 ? final_dst : cur == res[0] ? res[1] : res[0];
 		dst_stride = remaining_oop == 0 ? final_stride : h->tstride;
 	}
@@ -1533,28 +1492,6 @@ static Deemph deemph_route(const TailPlan &tp, const DeemphForm &f, const TailRu
 			return Deemph::spec_arb;
 	}
 	return tp.lpr && !tp.adc && !h->opt.lpr_separate ? Deemph::four_pass_lpr : Deemph::four_pass;
-}
-
-// Scratch that is sized by the run.  What may still be reading the old blocks has finished before they are freed, and the
-// caller's key to them says "none" from before this call until every allocation (and copy) behind it has succeeded: a
-// failure half way leaves no key beside freed or short memory.
-struct Scratch { void **p; size_t bytes; };
-static int replace_scratch(hipStream_t q, std::initializer_list<Scratch> blocks)
-{
-	for (const Scratch &b : blocks)
-		if (*b.p) { HIP_TRY(hipStreamSynchronize(q)); break; }
-	for (const Scratch &b : blocks)
-		if (*b.p) { HIP_TRY(hipFree(*b.p)); *b.p = nullptr; }
-	for (const Scratch &b : blocks) HIP_TRY(hipMalloc(b.p, b.bytes));
-	return 0;
-}
-static int grow_scratch(hipStream_t q, int *cap, int need, std::initializer_list<Scratch> blocks)
-{
-	if (need <= *cap) return 0;
-	*cap = 0;
-	const int e = replace_scratch(q, blocks);
-	if (e == 0) *cap = need;
-	return e;
 }
 
 // Samples per lane of a one-pass kernel: `want` where the run fills the GPU that way (-M wbfm at 1024 streams: 64 K lanes);
@@ -1616,9 +1553,10 @@ static int arb_tables(rtlfm_gpu *h, hipStream_t q, int Nblk, int arb_l2)
 		if (tick > arb_l2) { tick -= arb_l2; i++; }
 		if (i >= Nblk) { i = Nblk - 1; tick = arb_l2; }
 	}
-	h->arb_len2 = 0; h->arb_len1 = 0;  // (the tables of another geometry may still be in use: replace_scratch waits)
-	const int e = replace_scratch(q, {{(void **)&h->d_arb_i, ti.size() * sizeof(int32_t)}, {(void **)&h->d_arb_frac, tf.size() * sizeof(double)}});
-	if (e < 0) return e;
+	h->arb_len2 = 0; h->arb_len1 = 0;  // (no key to the tables until both hold the new geometry)
+	if (h->d_arb_i) HIP_TRY(hipStreamSynchronize(q));  // (the tables of another geometry may still be in use)
+	OWN_TRY(h->d_arb_i.grow(ti.size(), q));
+	OWN_TRY(h->d_arb_frac.grow(tf.size(), q));
 	HIP_TRY(hipMemcpy(h->d_arb_i, ti.data(), ti.size() * sizeof(int32_t), hipMemcpyHostToDevice));
 	HIP_TRY(hipMemcpy(h->d_arb_frac, tf.data(), tf.size() * sizeof(double), hipMemcpyHostToDevice));
 	h->arb_len2 = arb_l2; h->arb_len1 = Nblk;
@@ -1682,8 +1620,7 @@ static int tail_deemph_spec_lpr(TailRun &r, const DeemphForm &f, int32_t *cnt_ds
 		if (per <= Lwant) Ls = (int)(per * ((Lwant + per / 2) / per));
 		mcsp = T / Ls + 2;
 	}
-	const int e = grow_scratch(r.q, &h->lpr_chunks_cap, mcsp, {{(void **)&h->d_lpr_chunks, (size_t)r.S * mcsp * sizeof(LprChunk)}});
-	if (e < 0) return e;
+	OWN_TRY(h->d_lpr_chunks.grow((size_t)r.S * mcsp, r.q));
 	r.out_of_place();
 	// outputs leave in 64-byte pieces through LDS (2; any row alignment), else in 16-byte groups where the rows allow
 	// it (1), else one by one (staged_kernels.h, LprSink)
@@ -1712,10 +1649,9 @@ static int tail_deemph_four_pass(TailRun &r, const DeemphForm &f, bool fuse_lpr)
 	// long enough for the interval to contract (~100 samples) and, normally, to merge
 	const int L = T >= 8192 ? 1024 : 512;
 	const int mc = T / L + 2;
-	int e = grow_scratch(r.q, &h->deemph_chunks, mc, {{(void **)&h->d_deemph_tab, (size_t)S * mc * sizeof(DeemphChunk)},
-	                                                  {(void **)&h->d_deemph_inc, (size_t)S * mc * sizeof(uint32_t)}});
-	if (e == 0 && fuse_lpr) e = grow_scratch(r.q, &h->lpr_chunks_cap, mc, {{(void **)&h->d_lpr_chunks, (size_t)S * mc * sizeof(LprChunk)}});
-	if (e < 0) return e;
+	OWN_TRY(h->d_deemph_tab.grow((size_t)S * mc, r.q));
+	OWN_TRY(h->d_deemph_inc.grow((size_t)S * mc, r.q));
+	if (fuse_lpr) OWN_TRY(h->d_lpr_chunks.grow((size_t)S * mc, r.q));
 	if (fuse_lpr) r.out_of_place();
 	const int lpr_vec = fuse_lpr && (uintptr_t)r.dst % 16 == 0 && r.dst_stride % 8 == 0 && !h->opt.lpr_scalar_stores;
 	int lpc = 8;  // lanes per chunk in pass A2: the contracted interval (<= 2a + 2 states) must fit
@@ -1943,7 +1879,7 @@ static int run_staged(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, i
 	if (r < 0) return r;
 	const state_t *sin = h->st[h->st_cur];
 	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 
 	r = timing_begin(h, ev);
 	if (r < 0) return r;
@@ -2084,7 +2020,7 @@ static int run_fused(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, in
 	}
 	int16_t *dd; size_t dds;
 	tail_route(h, tp, d_out, out_stride, &dd, &dds);
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	int r = timing_begin(h, ev);
 	if (r < 0) return r;
 	const int2 *rdc = rdc_prepass(h, d_iq, stream_stride, nblocks);
@@ -2143,7 +2079,7 @@ static int run_fused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_strid
 		int r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
 		if (r < 0) return r;
 	}
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	int r = timing_begin(h, ev);
 	if (r < 0) return r;
 	h->fws.tail_follows = !raw_direct;  // kernels follow on this stream and, with a tail, on the tail's (as run_boxfused_emit)
@@ -2217,7 +2153,7 @@ static int run_boxfused(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride,
 	}
 	int16_t *dd; size_t dds;
 	tail_route(h, tp, d_out, out_stride, &dd, &dds);
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	int r = timing_begin(h, ev);
 	if (r < 0) return r;
 	const bool sq = c.squelch_level || c.report_levels;  // the front end takes rms()'s sums, k_squelch_apply decides (boxcar_kernel.h, SQ)
@@ -2261,7 +2197,7 @@ static int run_boxfused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_st
 		r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
 		if (r < 0) return r;
 	}
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	r = timing_begin(h, ev);
 	if (r < 0) return r;
 	h->fws.tail_follows = !raw_direct;  // kernels follow on this stream and, with a tail, on the tail's
@@ -2300,31 +2236,26 @@ struct ChanRun {
 };
 
 // What the channel front ends allocate at first use, sized from the handle's own buffer length: a view of the handle on a
-// shorter buffer (run_ragged) must find them there - it is a copy and must not allocate.  The decimated IQ; on path 1 the
+// shorter buffer (run_ragged) must find them there - it is a copy and cannot allocate (device_own.h).  The decimated IQ; on path 1 the
 // filter's mixed samples and the bank's sums.
 static int ensure_chan_iq(rtlfm_gpu *h)
 {
 	if (h->chan_iq) return 0;
 	h->chan_stride = (((size_t)h->cap_blocks * (h->cfg.block_len / 2)) / h->cfg.downsample + 1 + 16 + 3) & ~(size_t)3;  // rows start on 16-byte lines
-	HIP_TRY(hipMalloc(&h->chan_iq, (size_t)h->nstreams * h->chan_stride * sizeof(uint32_t)));
-	return 0;
+	return h->chan_iq.alloc((size_t)h->nstreams * h->chan_stride);
 }
 static int ensure_chan_fir_x(rtlfm_gpu *h)
 {
 	if (h->chan_fir_x) return 0;
 	h->chan_fir_xstride = (size_t)chanfir::kHaloMax + (size_t)h->cap_blocks * (h->cfg.block_len / 2);
-	HIP_TRY(hipMalloc(&h->chan_fir_x, (size_t)h->nstreams * h->chan_fir_xstride * sizeof(uint32_t)));
-	return 0;
+	return h->chan_fir_x.alloc((size_t)h->nstreams * h->chan_fir_xstride);
 }
 static int ensure_bank_v(rtlfm_gpu *h, size_t vneed /* 0: the most a run of this handle can need */)
 {
 	const size_t nsrc = (size_t)(h->nstreams / h->chan_per);
 	const size_t most = (nsrc * ((size_t)h->cap_blocks * (h->cfg.block_len / 2) / h->cfg.downsample + 1)) << h->bank_m;
-	if (h->bank_v && h->bank_v_dwords >= (vneed ? vneed : most)) return 0;
-	if (h->bank_v) { hipFree(h->bank_v); h->bank_v = nullptr; h->bank_v_dwords = 0; }
-	HIP_TRY(hipMalloc(&h->bank_v, most * sizeof(uint32_t)));
-	h->bank_v_dwords = most;
-	return 0;
+	if (h->bank_v.capacity() >= (vneed ? vneed : most)) return 0;
+	return h->bank_v.grow(most, h->stream);
 }
 // ... all of them, for the front end and the path the handle is set to, before the first view is made
 static int ensure_channel_buffers(rtlfm_gpu *h)
@@ -2456,11 +2387,7 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 			return 0;
 		}
 		const size_t need = (grid << h->bank_m);
-		if (h->sv.partial_cap < need) {
-			if (h->sv.d_partial) { hipFree(h->sv.d_partial); h->sv.d_partial = nullptr; h->sv.partial_cap = 0; }  // (waits for what reads it)
-			HIP_TRY(hipMalloc(&h->sv.d_partial, need * sizeof(unsigned long long)));
-			h->sv.partial_cap = need;
-		}
+		OWN_TRY(h->sv.d_partial.grow(need, q));  // (waits for what reads it)
 		p.survey = h->sv.d_partial;
 		chanbank::k_channel_bank_survey<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
 		chanbank::k_bank_survey_reduce<<<grid_for((size_t)cr.nsrc << h->bank_m), 256, 0, q>>>(h->sv.d_partial, p.f.segs, h->bank_m, cr.nsrc,
@@ -2496,7 +2423,7 @@ static int run_channels(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size
 	ChanRun cr;
 	int r = chan_run_prepare(h, !bank && !fir, d_iq, stream_stride, nblocks, d_out, out_stride, cr);
 	if (r < 0) return r;
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	if ((r = timing_begin(h, ev)) < 0) return r;
 	r = bank ? launch_channel_bank(h, fused_path, cr) : fir ? launch_channel_fir(h, fused_path, cr) : launch_channel_boxcar(h, cr);
 	if (r < 0) return r;
@@ -2508,16 +2435,12 @@ static int run_channels(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size
 
 static int ensure_input_stats(rtlfm_gpu *h)
 {
-	if (!h->d_istats)
-		HIP_TRY(hipMalloc(&h->d_istats, (size_t)h->nstreams * h->cap_blocks * sizeof(rtlfm_input_stat)));
-	return 0;
+	return h->d_istats.alloc((size_t)h->nstreams * h->cap_blocks);
 }
 
 static int ensure_input_health(rtlfm_gpu *h)
 {
-	if (!h->d_ihealth)
-		HIP_TRY(hipMalloc(&h->d_ihealth, (size_t)h->nstreams * h->cap_blocks * sizeof(rtlfm_input_health)));
-	return 0;
+	return h->d_ihealth.alloc((size_t)h->nstreams * h->cap_blocks);
 }
 
 // The raw-byte readers in front of a run's front end: with input_health on, k_input_health, which takes the statistics
@@ -2537,9 +2460,7 @@ static int launch_input_readers(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream
 
 static int ensure_gate(rtlfm_gpu *h)
 {
-	if (!h->d_gate)
-		HIP_TRY(hipMalloc(&h->d_gate, (size_t)h->nstreams * h->cap_blocks * sizeof(rtlfm_gate_rec)));
-	return 0;
+	return h->d_gate.alloc((size_t)h->nstreams * h->cap_blocks);
 }
 
 // The squelch gate, the last launch of a run (option squelch_gate): on the handle's stream, behind the audio tail wherever
@@ -2564,7 +2485,7 @@ static int launch_gate(rtlfm_gpu *h, int nblocks, int16_t *d_out, size_t out_str
 	p.D = c.downsample_passes > 0 ? 1 : c.downsample;
 	p.mul = c.mode == RTLFM_MODE_RAW ? 2 : 1;
 	p.level = c.squelch_level; p.conseq = h->opt.conseq_squelch;
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	int r = timing_begin(h, ev);
 	if (r < 0) return r;
 	if ((r = scan::launch_gate(p, h->nstreams, h->stream)) < 0) return r;
@@ -2674,18 +2595,11 @@ static int run_device_verified(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 {
 	const size_t S = (size_t)h->nstreams;
 	const size_t need = S * out_stride;
-	if (h->vt_out_cap < need) {
-		if (h->vt_out) hipFree(h->vt_out);
-		h->vt_out = nullptr; h->vt_out_cap = 0;
-		HIP_TRY(hipMalloc(&h->vt_out, need * sizeof(int16_t)));
-		h->vt_out_cap = need;
-	}
-	if (!h->vt_len) {
-		HIP_TRY(hipMalloc(&h->vt_len, S * sizeof(int32_t)));
-		HIP_TRY(hipMalloc(&h->vt_len2, S * sizeof(int32_t)));
-		HIP_TRY(hipMalloc(&h->vt_state, S * sizeof(state_t)));
-		HIP_TRY(hipMalloc(&h->vt_cnt, 4 * sizeof(unsigned long long)));
-	}
+	OWN_TRY(h->vt_out.grow(need, h->stream));
+	OWN_TRY(h->vt_len.alloc(S));
+	OWN_TRY(h->vt_len2.alloc(S));
+	OWN_TRY(h->vt_state.alloc(S));
+	OWN_TRY(h->vt_cnt.alloc(4));
 	state_t *sout = h->st[(h->st_cur + 1) % 3];
 	int r = run_device_once(h, d_iq, stream_stride, nblocks, h->vt_out, out_stride, h->vt_len);
 	if (r < 0) return r;
@@ -2695,7 +2609,7 @@ static int run_device_verified(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 	// and the comparison reported state words that had never differed: one red run of the suite in round 6)
 	HIP_TRY(hipMemcpyAsync(h->vt_state, sout, S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
 	if (h->opt.squelch_gate) {
-		if (!h->vt_gate) HIP_TRY(hipMalloc(&h->vt_gate, S * h->cap_blocks * sizeof(rtlfm_gate_rec)));
+		OWN_TRY(h->vt_gate.alloc(S * h->cap_blocks));
 		HIP_TRY(hipMemcpyAsync(h->vt_gate, h->d_gate, S * nblocks * sizeof(rtlfm_gate_rec), hipMemcpyDeviceToDevice, h->stream));
 	}
 	HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2714,12 +2628,12 @@ static int run_device_verified(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 	HIP_TRY(hipMemcpy(h->vt_cnt, init, sizeof(init), hipMemcpyHostToDevice));
 	k_verify_rows<<<(unsigned)S, 256, 0, h->stream>>>(h->vt_out, d_out, out_stride, h->vt_len, len2, (int)S, h->vt_cnt);
 	const size_t nw = S * sizeof(state_t) / 4;
-	k_verify_words<<<(unsigned)((nw + 255) / 256), 256, 0, h->stream>>>(reinterpret_cast<const uint32_t *>(h->vt_state),
+	k_verify_words<<<(unsigned)((nw + 255) / 256), 256, 0, h->stream>>>(reinterpret_cast<const uint32_t *>(h->vt_state.get()),
 	                                                                  reinterpret_cast<const uint32_t *>(sout), nw, h->vt_cnt);
 	if (h->opt.squelch_gate) {  // the gate's records count with the state words
 		const size_t gw = S * nblocks * sizeof(rtlfm_gate_rec) / 4;
-		k_verify_words<<<(unsigned)((gw + 255) / 256), 256, 0, h->stream>>>(reinterpret_cast<const uint32_t *>(h->vt_gate),
-		                                                                  reinterpret_cast<const uint32_t *>(h->d_gate), gw, h->vt_cnt);
+		k_verify_words<<<(unsigned)((gw + 255) / 256), 256, 0, h->stream>>>(reinterpret_cast<const uint32_t *>(h->vt_gate.get()),
+		                                                                  reinterpret_cast<const uint32_t *>(h->d_gate.get()), gw, h->vt_cnt);
 	}
 	unsigned long long got[4];
 	HIP_TRY(hipMemcpyAsync(got, h->vt_cnt, sizeof(got), hipMemcpyDeviceToHost, h->stream));
@@ -2747,13 +2661,7 @@ static int survey_free(rtlfm_gpu *h, bool wait)
 		HIP_TRY(hipSetDevice(h->device));
 		HIP_TRY(sync_all(h));
 	}
-	for (int k = 0; k < 2; k++) {
-		if (sv.d_power[k]) hipFree(sv.d_power[k]);
-		if (sv.d_frames[k]) hipFree(sv.d_frames[k]);
-		if (sv.ev[k]) hipEventDestroy(sv.ev[k]);
-	}
-	if (sv.d_partial) hipFree(sv.d_partial);
-	sv = rtlfm_gpu::Survey{};
+	sv = rtlfm_gpu::Survey{};  // (the sets go with it)
 	return 0;
 }
 
@@ -2763,15 +2671,15 @@ static int survey_ensure(rtlfm_gpu *h)
 	rtlfm_gpu::Survey &sv = h->sv;
 	const int nsrc = h->nstreams / h->chan_per;
 	const size_t need = (size_t)nsrc * h->bank_K;
-	if (sv.d_power[0] && sv.cap >= need && sv.cap_srcs >= nsrc) return 0;
+	if (sv.d_power[0] && sv.d_power[0].capacity() >= need && sv.cap_srcs >= nsrc) return 0;
 	int r = survey_free(h, true);
 	if (r < 0) return r;
 	for (int k = 0; k < 2; k++) {
-		HIP_TRY(hipMalloc(&sv.d_power[k], need * sizeof(unsigned long long)));
-		HIP_TRY(hipMalloc(&sv.d_frames[k], (size_t)nsrc * sizeof(int32_t)));
-		HIP_TRY(hipEventCreateWithFlags(&sv.ev[k], hipEventDisableTiming));
+		OWN_TRY(sv.d_power[k].alloc(need));
+		OWN_TRY(sv.d_frames[k].alloc((size_t)nsrc));
+		OWN_TRY(sv.ev[k].create(hipEventDisableTiming));
 	}
-	sv.cap = need; sv.cap_srcs = nsrc;
+	sv.cap_srcs = nsrc;
 	return 0;
 }
 
@@ -2868,7 +2776,7 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 // `cap` records.  One contract for all of them, rtlfm_gpu_levels': bad arguments, then "not enabled", then the count -
 // written even where it does not fit -, then the copy.
 template <class Rec>
-static int fetch_records(rtlfm_gpu *h, Rec *rtlfm_gpu::*recs, int rtlfm_gpu::*count_of, bool (*enabled)(const rtlfm_gpu *),
+static int fetch_records(rtlfm_gpu *h, DevBuf<Rec> rtlfm_gpu::*recs, int rtlfm_gpu::*count_of, bool (*enabled)(const rtlfm_gpu *),
                          bool all, int stream, Rec *out, int cap, int *n)
 {
 	if (!h || !out || !n || (!all && (stream < 0 || stream >= h->nstreams))) return -EINVAL;
@@ -2978,7 +2886,7 @@ extern "C" int rtlfm_gpu_mute(rtlfm_gpu *h, int stream, uint32_t nbytes)
 	if (h->chan_per > 0) return -ENOTSUP;  // (channels: the mute counts a stream's own input bytes)
 	if (!h->mute_left) {
 		if (!nbytes) return 0;
-		h->mute_left = new (std::nothrow) uint32_t[(size_t)h->nstreams]();
+		h->mute_left.reset(new (std::nothrow) uint32_t[(size_t)h->nstreams]());
 		if (!h->mute_left) return -ENOMEM;
 	}
 	h->mute_streams += (nbytes ? 1 : 0) - (h->mute_left[stream] ? 1 : 0);
@@ -3004,12 +2912,11 @@ extern "C" int rtlfm_gpu_mute_device(int device, uint8_t *d_iq, size_t stream_st
 	}
 	if (ent.empty()) return 0;
 	hipStream_t q = (hipStream_t)hip_stream;
-	scan::MuteEntry *d_ent = nullptr;
-	HIP_TRY(hipMalloc(&d_ent, ent.size() * sizeof(scan::MuteEntry)));
+	DevBuf<scan::MuteEntry> d_ent;
+	OWN_TRY(d_ent.alloc(ent.size()));
 	hipError_t e = hipMemcpy(d_ent, ent.data(), ent.size() * sizeof(scan::MuteEntry), hipMemcpyHostToDevice);
 	int r = e == hipSuccess ? scan::launch_mute(d_iq, d_ent, (int)ent.size(), mx, q) : -EIO;
-	if (hipStreamSynchronize(q) != hipSuccess) r = -EIO;  // the entries are freed below
-	(void)hipFree(d_ent);
+	if (hipStreamSynchronize(q) != hipSuccess) r = -EIO;  // the entries go when this returns
 	return r;
 }
 
@@ -3041,19 +2948,20 @@ extern "C" int rtlfm_gpu_mute_device(int device, uint8_t *d_iq, size_t stream_st
 // (ingest_resize), on a ring that holds nothing; results of earlier runs stay where they are.
 struct Ingest {
 	int rows = 0;                               // of the input side, as built (0: a rebuild failed; ingest_ensure tries again)
-	uint8_t *h_stage[2] = {nullptr, nullptr};   // pinned, [row][cap_blocks][block_len]
-	uint8_t *d_in[2] = {nullptr, nullptr};
+	struct Input {                              // what a change of the row count replaces (ingest_resize_locked), as one
+		PinnedBuf<uint8_t> h_stage[2];          // pinned, [row][cap_blocks][block_len]
+		DevBuf<uint8_t> d_in[2];
+	} inp;
 	std::vector<uint32_t> h_len[2];             // bytes in each slot
 	std::unique_ptr<std::atomic<int>[]> pushed[2];
 	std::unique_ptr<std::atomic<int>[]> open_slot;  // [stream] 1 + half while a slot is out between acquire and commit
 	int fill = 0;                               // guarded by mu (shared: read, exclusive: flip)
 	std::shared_mutex mu;
 	hipStream_t copy_stream = nullptr;
-	hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_run[2] = {nullptr, nullptr};
+	Event ev_h2d[2], ev_run[2];
 	bool h2d_pending[2] = {false, false}, run_pending[2] = {false, false};
-	int16_t *d_result[2] = {nullptr, nullptr};  // ostride int16 per stream
-	bool result_one_block = false;              // d_result[1] points into d_result[0]'s allocation
-	int32_t *d_result_len[2] = {nullptr, nullptr};
+	DevBuf<int16_t> d_result[2];                // ostride int16 per stream; [1] is an alias into [0]'s block unless it had to be placed apart
+	DevBuf<int32_t> d_result_len[2];
 	size_t ostride = 0;
 	int pending_f = -1, pending_nb = 0;         // rtlfm_gpu_run_begin() has flipped the halves, _end() has not run yet
 	bool pending_ragged = false;
@@ -3061,20 +2969,22 @@ struct Ingest {
 	int prev = -1;                              // ... and of the run before it (rtlfm_gpu_fetch_all_prev)
 	int tail_par[2] = {0, 0};                   // per half: step parity of its run, and whether that run left an audio tail
 	bool tail_any[2] = {false, false};          // on the tail stream (ev_tail[parity])
-	int16_t *h_result = nullptr;                // pinned mirror of the last run's results (per-stream fetch)
-	int32_t *h_result_len = nullptr;
+	PinnedBuf<int16_t> h_result;                // pinned mirror of the last run's results (per-stream fetch)
+	PinnedBuf<int32_t> h_result_len;
 	bool mirror_valid = false;
-	int16_t *d_tmp = nullptr;                   // ragged runs: one buffer's results before they are appended
-	int32_t *d_tmp_len = nullptr;
-	// packed results (option pack_results; pack_kernel.h): per half, allocated by the first packed run
-	int16_t *d_packed[2] = {nullptr, nullptr};  // [packed_cap] int16: every row rounded up to 8, the worst case
-	rtlfm_packed_row *d_pack_index[2] = {nullptr, nullptr};  // [nstreams]
-	unsigned long long *d_pack_total[2] = {nullptr, nullptr};
-	int32_t *d_piece_off = nullptr;             // mode 2: [nstreams][cap_blocks], k_pack_plan's to k_pack_copy (one: both on the handle's stream)
-	size_t packed_cap = 0;
-	int pack_mode[2] = {0, 0};                  // how the half's run was packed (0: it was not)
-	hipEvent_t ev_pack[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};  // around the two launches while timing is on
-	bool pack_timed[2] = {false, false};
+	DevBuf<int16_t> d_tmp;                      // ragged runs: one buffer's results before they are appended
+	DevBuf<int32_t> d_tmp_len;
+	// packed results (option pack_results; pack_kernel.h): per half, allocated by the first packed run; the option back
+	// at 0 drops them as one (ingest_pack_free)
+	struct Pack {
+		DevBuf<int16_t> d_packed[2];                // every row rounded up to 8, the worst case
+		DevBuf<rtlfm_packed_row> d_pack_index[2];   // [nstreams]
+		DevBuf<unsigned long long> d_pack_total[2];
+		DevBuf<int32_t> d_piece_off;                // mode 2: [nstreams][cap_blocks], k_pack_plan's to k_pack_copy (one: both on the handle's stream)
+		int pack_mode[2] = {0, 0};                  // how the half's run was packed (0: it was not)
+		Event ev_pack[2][2];                        // around the two launches while timing is on
+		bool pack_timed[2] = {false, false};
+	} pk;
 };
 
 static std::mutex g_ingest_alloc_mu;
@@ -3090,35 +3000,20 @@ static size_t alloc_size(const void *p)
 }
 static long placement_held_mb(rtlfm_gpu *h)
 {
-	size_t b = alloc_size(h->res[0][0]) + (h->res_one_block ? 0 : alloc_size(h->res[1][0])) + alloc_size(h->deepA);
+	size_t b = alloc_size(h->res[0][0]) + (h->res[1][0].is_alias() ? 0 : alloc_size(h->res[1][0])) + alloc_size(h->deepA);
 	if (Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE))
-		b += alloc_size(in->d_result[0]) + (in->result_one_block ? 0 : alloc_size(in->d_result[1]));
+		b += alloc_size(in->d_result[0]) + (in->d_result[1].is_alias() ? 0 : alloc_size(in->d_result[1]));
 	return (long)(b >> 20);
-}
-
-static void pack_free(Ingest *in)
-{
-	for (int k = 0; k < 2; k++) {
-		for (void *p : {(void *)in->d_packed[k], (void *)in->d_pack_index[k], (void *)in->d_pack_total[k]})
-			if (p) hipFree(p);
-		for (hipEvent_t &e : in->ev_pack[k])
-			if (e) { hipEventDestroy(e); e = nullptr; }
-		in->d_packed[k] = nullptr; in->d_pack_index[k] = nullptr; in->d_pack_total[k] = nullptr;
-		in->pack_mode[k] = 0; in->pack_timed[k] = false;
-	}
-	if (in->d_piece_off) hipFree(in->d_piece_off);
-	in->d_piece_off = nullptr;
-	in->packed_cap = 0;
 }
 
 // option pack_results back to 0: what the pack allocated goes, behind whatever still reads or writes it
 static int ingest_pack_free(rtlfm_gpu *h)
 {
 	Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE);
-	if (!in || !in->d_packed[0]) return 0;
+	if (!in || !in->pk.d_packed[0]) return 0;
 	HIP_TRY(hipSetDevice(h->device));
 	HIP_TRY(sync_all(h));
-	pack_free(in);
+	in->pk = Ingest::Pack{};
 	return 0;
 }
 
@@ -3126,11 +3021,11 @@ static int ingest_pack_us(rtlfm_gpu *h, long *us)
 {
 	Ingest *in = __atomic_load_n(&h->ing, __ATOMIC_ACQUIRE);
 	*us = -1;
-	if (!in || in->last < 0 || !in->pack_mode[in->last] || !in->pack_timed[in->last]) return 0;
+	if (!in || in->last < 0 || !in->pk.pack_mode[in->last] || !in->pk.pack_timed[in->last]) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	HIP_TRY(hipEventSynchronize(in->ev_pack[in->last][1]));
+	HIP_TRY(hipEventSynchronize(in->pk.ev_pack[in->last][1]));
 	float ms = 0;
-	HIP_TRY(hipEventElapsedTime(&ms, in->ev_pack[in->last][0], in->ev_pack[in->last][1]));
+	HIP_TRY(hipEventElapsedTime(&ms, in->pk.ev_pack[in->last][0], in->pk.ev_pack[in->last][1]));
 	*us = (long)(ms * 1000.0f + 0.5f);
 	return 0;
 }
@@ -3139,38 +3034,17 @@ static void ingest_free(Ingest *in)
 {
 	if (!in) return;
 	if (in->copy_stream) { int dev_ = 0; (void)hipGetDevice(&dev_); rtl_pool::stream_put(dev_, 0, in->copy_stream); }
-	for (int k = 0; k < 2; k++) {
-		if (in->h_stage[k]) hipHostFree(in->h_stage[k]);
-		for (void *p : {(void *)in->d_in[k], k == 1 && in->result_one_block ? nullptr : (void *)in->d_result[k], (void *)in->d_result_len[k]})
-			if (p) hipFree(p);
-		for (hipEvent_t e : {in->ev_h2d[k], in->ev_run[k]})
-			if (e) hipEventDestroy(e);
-	}
-	if (in->h_result) hipHostFree(in->h_result);
-	if (in->h_result_len) hipHostFree(in->h_result_len);
-	if (in->d_tmp) hipFree(in->d_tmp);
-	if (in->d_tmp_len) hipFree(in->d_tmp_len);
-	pack_free(in);
 	delete in;
 }
 
 // the input side, for the rows there are now
-static void ingest_free_input(Ingest *in)
-{
-	for (int k = 0; k < 2; k++) {
-		if (in->h_stage[k]) hipHostFree(in->h_stage[k]);
-		if (in->d_in[k]) hipFree(in->d_in[k]);
-		in->h_stage[k] = nullptr; in->d_in[k] = nullptr;
-	}
-	in->rows = 0;
-}
 static int ingest_build_input(rtlfm_gpu *h, Ingest *in)
 {
 	const size_t R = (size_t)ring_rows(h);
 	const size_t bytes = R * h->cap_blocks * h->cfg.block_len;
 	for (int k = 0; k < 2; k++) {
-		HIP_TRY(hipHostMalloc(&in->h_stage[k], bytes, hipHostMallocDefault));
-		HIP_TRY(hipMalloc(&in->d_in[k], bytes));
+		OWN_TRY(in->inp.h_stage[k].alloc(bytes));
+		OWN_TRY(in->inp.d_in[k].alloc(bytes));
 		in->h_len[k].assign(R * h->cap_blocks, 0);
 		in->pushed[k].reset(new std::atomic<int>[R]);
 		for (size_t s = 0; s < R; s++) in->pushed[k][s].store(0);
@@ -3191,9 +3065,9 @@ static int ingest_build(rtlfm_gpu *h, Ingest *in)
 	if (rb < 0) return rb;
 	const size_t bytes = (size_t)in->rows * h->cap_blocks * h->cfg.block_len;
 	for (int k = 0; k < 2; k++) {
-		HIP_TRY(hipMalloc(&in->d_result_len[k], S * sizeof(int32_t)));
-		HIP_TRY(hipEventCreateWithFlags(&in->ev_h2d[k], hipEventDisableTiming));
-		HIP_TRY(hipEventCreateWithFlags(&in->ev_run[k], hipEventDisableTiming));
+		OWN_TRY(in->d_result_len[k].alloc(S));
+		OWN_TRY(in->ev_h2d[k].create(hipEventDisableTiming));
+		OWN_TRY(in->ev_run[k].create(hipEventDisableTiming));
 	}
 	{
 		// the results away from the input they are demodulated from (rtlfm_gpu_malloc_apart_ex; plain memory when the
@@ -3202,10 +3076,13 @@ static int ingest_build(rtlfm_gpu *h, Ingest *in)
 		// says whether it is, and only if not the second half gets a block and a search of its own.
 		const size_t one = (S * in->ostride * sizeof(int16_t) + 255) & ~(size_t)255;
 		const size_t budget = (size_t)h->place.budget_gb << 30;
-		void *p = nullptr;
+		const size_t one_elems = one / sizeof(int16_t);
+		void *q = nullptr;
+		DevBuf<int16_t> p;
 		int apart = 0; double ms = 0; size_t walked = 0;
-		int r = rtlfm_gpu_malloc_apart_ex(h->device, 2 * one, in->d_in[0], bytes, budget, &p, &apart, &ms, &walked);
+		int r = rtlfm_gpu_malloc_apart_ex(h->device, 2 * one, in->inp.d_in[0], bytes, budget, &q, &apart, &ms, &walked);
 		if (r < 0) return r;
+		OWN_TRY(p.adopt(q, 2 * one_elems));
 		h->place.search_ms += ms;
 		if (walked > h->place.walked_peak) h->place.walked_peak = walked;
 		h->place.ring_tries = 1;
@@ -3214,42 +3091,39 @@ static int ingest_build(rtlfm_gpu *h, Ingest *in)
 			// runs on for more than 16 GB).  Here the handle owns the OTHER side as well: the ring's device inputs move - new ones
 			// are allocated while the old ones are still held, so that they come from somewhere else - and the search runs once
 			// more against them.  One retry; whatever it finds is what the ring gets.
-			void *n0 = nullptr, *n1 = nullptr;
-			if (hipMalloc(&n0, bytes) == hipSuccess && hipMalloc(&n1, bytes) == hipSuccess) {
-				(void)hipFree(p);
-				p = nullptr;
+			DevBuf<uint8_t> n0, n1;
+			if (n0.alloc(bytes, true) == 0 && n1.alloc(bytes, true) == 0) {  // (quietly: without them there is simply no retry)
+				p.reset();
 				int apart2 = 0;
-				r = rtlfm_gpu_malloc_apart_ex(h->device, 2 * one, n0, bytes, budget, &p, &apart2, &ms, &walked);
-				if (r < 0) { (void)hipFree(n0); (void)hipFree(n1); return r; }
+				r = rtlfm_gpu_malloc_apart_ex(h->device, 2 * one, n0, bytes, budget, &q, &apart2, &ms, &walked);
+				if (r < 0) return r;
+				OWN_TRY(p.adopt(q, 2 * one_elems));
 				h->place.search_ms += ms;
 				if (walked > h->place.walked_peak) h->place.walked_peak = walked;
 				h->place.ring_tries = 2;
-				(void)hipFree(in->d_in[0]); (void)hipFree(in->d_in[1]);
-				in->d_in[0] = (uint8_t *)n0; in->d_in[1] = (uint8_t *)n1;
+				in->inp.d_in[0] = std::move(n0); in->inp.d_in[1] = std::move(n1);
 				apart = apart2;
 			} else {
-				if (n0) (void)hipFree(n0);
 				(void)hipGetLastError();
 			}
 		}
-		in->d_result[0] = (int16_t *)p;
-		in->d_result[1] = (int16_t *)((char *)p + one);
-		in->result_one_block = true;
+		in->d_result[0] = std::move(p);
+		in->d_result[1] = in->d_result[0].alias(one_elems);
 		h->place.ring_apart = apart;
 		if (apart) {
 			double rd = 0, rw = 0;
 			const auto t0 = std::chrono::steady_clock::now();
-			const int both = rtlfm_gpu_placement_probe(h->device, in->d_in[1], bytes, in->d_result[1], one, &rd, &rw);
+			const int both = rtlfm_gpu_placement_probe(h->device, in->inp.d_in[1], bytes, in->d_result[1], one, &rd, &rw);
 			h->place.search_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 			if (both < 0) return both;
 			if (!both) {
 				void *p2 = nullptr; int apart2 = 0;
-				r = rtlfm_gpu_malloc_apart_ex(h->device, one, in->d_in[1], bytes, budget, &p2, &apart2, &ms, &walked);
+				r = rtlfm_gpu_malloc_apart_ex(h->device, one, in->inp.d_in[1], bytes, budget, &p2, &apart2, &ms, &walked);
 				if (r < 0) return r;
 				h->place.search_ms += ms;
 				if (walked > h->place.walked_peak) h->place.walked_peak = walked;
-				in->d_result[1] = (int16_t *)p2;
-				in->result_one_block = false;
+				in->d_result[1].reset();  // (the alias goes: an owner of its own)
+				OWN_TRY(in->d_result[1].adopt(p2, one_elems));
 				h->place.ring_apart = apart2;
 			}
 		}
@@ -3267,7 +3141,8 @@ static int ingest_resize_locked(rtlfm_gpu *h, Ingest *in)
 	HIP_TRY(sync_all(h));
 	HIP_TRY(hipStreamSynchronize(in->copy_stream));
 	std::unique_lock<std::shared_mutex> g(in->mu);
-	ingest_free_input(in);
+	in->inp = Ingest::Input{};
+	in->rows = 0;
 	in->h2d_pending[0] = in->h2d_pending[1] = false;
 	return ingest_build_input(h, in);
 }
@@ -3370,7 +3245,7 @@ extern "C" int rtlfm_gpu_push(rtlfm_gpu *h, int stream, const uint8_t *iq, uint3
 		return -ENOSPC;
 	}
 	const size_t at = (size_t)stream * h->cap_blocks + slot;
-	memcpy(in->h_stage[f] + at * h->cfg.block_len, iq, len);
+	memcpy(in->inp.h_stage[f] + at * h->cfg.block_len, iq, len);
 	in->h_len[f][at] = len;
 	return 0;
 }
@@ -3393,7 +3268,7 @@ extern "C" int rtlfm_gpu_acquire(rtlfm_gpu *h, int stream, uint8_t **buf, uint32
 	const int slot = in->pushed[f][stream].load(std::memory_order_acquire);
 	if (slot >= h->cap_blocks) return -ENOSPC;
 	in->open_slot[stream].store(1 + f, std::memory_order_release);
-	*buf = in->h_stage[f] + ((size_t)stream * h->cap_blocks + slot) * h->cfg.block_len;
+	*buf = in->inp.h_stage[f] + ((size_t)stream * h->cap_blocks + slot) * h->cfg.block_len;
 	if (cap) *cap = h->cfg.block_len;
 	return 0;
 }
@@ -3440,7 +3315,8 @@ __global__ void k_append_results(int16_t *dst, size_t dstride, int32_t *dst_len,
 }
 
 // A view of the handle on streams [s0, s0 + ns) with another buffer length: same device buffers,
-// per-stream pointers shifted, everything on the handle's stream (no tail overlap, no timing).
+// per-stream pointers shifted, everything on the handle's stream (no tail overlap, no timing).  The copy is all aliases
+// (device_own.h): it owns nothing, frees nothing, and an allocation through it fails with -EINVAL.
 static rtlfm_gpu make_view(rtlfm_gpu *h, int s0, int ns, uint32_t block_len)
 {
 	rtlfm_gpu v = *h;
@@ -3453,26 +3329,34 @@ static rtlfm_gpu make_view(rtlfm_gpu *h, int s0, int ns, uint32_t block_len)
 	v.opt.input_stats = 0;   // run_ragged takes the statistics itself, into the run's own rows
 	v.opt.input_health = 0;  // ... and the health records
 	v.mute_streams = 0;      // rtlfm_gpu_run_end has applied the mute to the whole run's input
-	v.opt.verify_twice = 0;  // views must not allocate (the shadow rows): ragged runs are not verified
+	v.opt.verify_twice = 0;  // (the shadow rows are sized by the run: a view cannot grow them) ragged runs are not verified
 	v.opt.bank_survey = 0;   // ... nor surveyed: a survey is one run's, a view runs one buffer (run_ragged says so on the handle)
 	v.ev_pending.clear(); v.ev_free.clear();
 	const size_t cb = (size_t)h->cap_blocks;
-	for (int k = 0; k < 3; k++) v.st[k] = h->st[k] + s0;
+	for (int k = 0; k < 3; k++) v.st[k] = h->st[k].alias(s0);
 	for (int k = 0; k < 2; k++) {
-		v.d_cnt[k] = h->d_cnt[k] + s0;
-		for (int j = 0; j < 2; j++) v.res[k][j] = h->res[k][j] ? h->res[k][j] + (size_t)s0 * h->tstride : nullptr;
+		v.d_cnt[k] = h->d_cnt[k].alias(s0);
+		for (int j = 0; j < 2; j++) v.res[k][j] = h->res[k][j].alias((size_t)s0 * h->tstride);
 	}
-	v.d_cnt2 = h->d_cnt2 + s0;
-	v.d_mute = h->d_mute + s0 * cb;
-	v.d_levels = h->d_levels + s0 * cb;
-	v.d_sums = h->d_sums + s0 * cb * 2;
-	v.d_sq_sums = h->d_sq_sums + s0 * cb * 2;
-	v.d_adc_sums = h->d_adc_sums + s0 * cb;
-	v.d_rdc_avg = h->d_rdc_avg + s0 * cb;
-	if (h->bufA) { v.bufA = h->bufA + (size_t)s0 * h->xstride; v.bufB = h->bufB + (size_t)s0 * h->xstride; }
-	if (h->deepA) v.deepA = h->deepA + (size_t)s0 * h->deep_stride;
-	if (h->deepB) v.deepB = h->deepB + (size_t)s0 * h->deep_stride;
+	v.d_cnt2 = h->d_cnt2.alias(s0);
+	v.d_mute = h->d_mute.alias(s0 * cb);
+	v.d_levels = h->d_levels.alias(s0 * cb);
+	v.d_sums = h->d_sums.alias(s0 * cb * 2);
+	v.d_sq_sums = h->d_sq_sums.alias(s0 * cb * 2);
+	v.d_adc_sums = h->d_adc_sums.alias(s0 * cb);
+	v.d_rdc_avg = h->d_rdc_avg.alias(s0 * cb);
+	v.bufA = h->bufA.alias((size_t)s0 * h->xstride); v.bufB = h->bufB.alias((size_t)s0 * h->xstride);
+	v.deepA = h->deepA.alias((size_t)s0 * h->deep_stride);
+	v.deepB = h->deepB.alias((size_t)s0 * h->deep_stride);
 	return v;
+}
+
+// what a view's run advanced that belongs to the handle (the view itself owned nothing)
+static void view_done(rtlfm_gpu *h, const rtlfm_gpu &v)
+{
+	h->fws.stamp_seq = v.fws.stamp_seq;
+	h->fws.stamp_last = v.fws.stamp_last;
+	h->last_path = v.last_path;
 }
 
 // a run that holds short buffers: buffer by buffer, ranges of streams with equal length
@@ -3481,17 +3365,24 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	const int S = h->nstreams;
 	const size_t stride = (size_t)h->cap_blocks * h->cfg.block_len;
 	int r;
-	// views must not allocate: everything any path may need exists before the first one is made
+	// A view cannot allocate (device_own.h: it holds aliases): everything any path may need exists before the first one is
+	// made - the front ends' workspace too: the dummy tile, k_fused's pass-0 tap table for the handle's rotation where the
+	// engine is the MFMA one, and, while waves leave clock stamps, room for the most waves a one-buffer launch can have.
 	if ((r = ensure_work_buffers(h)) < 0 || (r = ensure_res_buffers(h)) < 0 || (r = ensure_deep_buffers(h)) < 0) return r;
-	if (fused::ensure_dummy_tile(h->fws)) return -ENOMEM;
+	if ((r = fused::ensure_dummy_tile(h->fws)) < 0) return r;
+	if (h->cfg.downsample_passes > 0 && fused::effective_engine(h->fws) == 1 &&  // (k_fused's: fifth_order passes only)
+	    (r = fused::ensure_mfma_taps(h->fws, h->cfg.offset_tuning ? 0 : 1)) < 0)
+		return r;
+	if (h->fws.want_stamps || (h->fws.debug & 2)) {
+		const size_t tiles = (h->cfg.block_len + fused::kTileBytes - 1) / fused::kTileBytes;  // (a segment is a tile at least)
+		if ((r = h->fws.stamps.grow((size_t)S * tiles * 8, h->stream)) < 0) return r;
+	}
 	if (h->opt.input_stats && (r = ensure_input_stats(h)) < 0) return r;
 	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
 	if (h->opt.squelch_gate && (r = ensure_gate(h)) < 0) return r;
 	if (h->chan_per > 0 && (r = ensure_channel_buffers(h)) < 0) return r;
-	if (!in->d_tmp) {
-		HIP_TRY(hipMalloc(&in->d_tmp, (size_t)S * in->ostride * sizeof(int16_t)));
-		HIP_TRY(hipMalloc(&in->d_tmp_len, (size_t)S * sizeof(int32_t)));
-	}
+	OWN_TRY(in->d_tmp.alloc((size_t)S * in->ostride));
+	OWN_TRY(in->d_tmp_len.alloc((size_t)S));
 	// The views run their audio tail on the handle's main stream: the tails of the two previous
 	// (batched) steps may still be running on the tail stream, writing the state copy and the res[]
 	// sets the views are about to read.  Order the main stream behind both, on the handle itself.
@@ -3517,9 +3408,8 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 			rtlfm_gpu v = make_view(h, 0, S, len);
 			v.st_cur = cur;
 			v.step = step;
-			r = run_device_impl(&v, in->d_in[f] + (size_t)j * h->cfg.block_len, stride, 1, in->d_tmp, in->ostride, in->d_tmp_len);
-			h->fws = v.fws;
-			h->last_path = v.last_path;
+			r = run_device_impl(&v, in->inp.d_in[f] + (size_t)j * h->cfg.block_len, stride, 1, in->d_tmp, in->ostride, in->d_tmp_len);
+			view_done(h, v);
 			if (r < 0) return r;
 			h->chan_pos = v.chan_pos;
 			h->src_hist_cur = v.src_hist_cur;
@@ -3533,7 +3423,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 			c.max_blocks = 1;
 			if ((r = validate_cfg(&c)) < 0) return r;
 			// each buffer's statistics over its own length, filed as [stream][nb] like a batched run's
-			if ((r = launch_input_readers(h, in->d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, len, 1, s1 - s0,
+			if ((r = launch_input_readers(h, in->inp.d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, len, 1, s1 - s0,
 			                              (size_t)s0 * nb + j, nb)) < 0)
 				return r;
 			rtlfm_gpu v = make_view(h, s0, s1 - s0, len);
@@ -3541,10 +3431,9 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 			v.step = step;
 			v.gate_rec_off = (size_t)s0 * nb + j;  // the gate's records filed as [stream][nb] like a batched run's
 			v.gate_rec_stride = nb;
-			r = run_device_impl(&v, in->d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, 1,
+			r = run_device_impl(&v, in->inp.d_in[f] + (size_t)s0 * stride + (size_t)j * h->cfg.block_len, stride, 1,
 			                         in->d_tmp + (size_t)s0 * in->ostride, in->ostride, in->d_tmp_len + s0);
-			h->fws = v.fws;  // lazily created tap tables / probe buffers belong to the handle
-			h->last_path = v.last_path;
+			view_done(h, v);
 			if (r < 0) return r;
 			s0 = s1;
 		}
@@ -3584,21 +3473,15 @@ static int apply_mute(rtlfm_gpu *h, Ingest *in, int f, int nb)
 		if (!left) h->mute_streams--;
 	}
 	if (ent.empty()) return 0;
-	if (h->mute_entries_cap < ent.size()) {
-		if (h->d_mute_entries) HIP_TRY(hipFree(h->d_mute_entries));
-		h->d_mute_entries = nullptr; h->mute_entries_cap = 0;
-		const size_t cap = (size_t)h->nstreams * h->cap_blocks;
-		HIP_TRY(hipMalloc(&h->d_mute_entries, cap * sizeof(scan::MuteEntry)));
-		h->mute_entries_cap = cap;
-	}
+	OWN_TRY(h->d_mute_entries.grow((size_t)h->nstreams * h->cap_blocks, h->stream));  // (the most a run can have)
 	// (a blocking copy: the entries are on the device before the launch is queued, and an earlier run's launch that read
 	// the same array has been waited for by it)
 	HIP_TRY(hipStreamSynchronize(h->stream));
 	HIP_TRY(hipMemcpy(h->d_mute_entries, ent.data(), ent.size() * sizeof(scan::MuteEntry), hipMemcpyHostToDevice));
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	int r = timing_begin(h, ev);
 	if (r < 0) return r;
-	if ((r = scan::launch_mute(in->d_in[f], h->d_mute_entries, (int)ent.size(), mx, h->stream)) < 0) return r;
+	if ((r = scan::launch_mute(in->inp.d_in[f], h->d_mute_entries, (int)ent.size(), mx, h->stream)) < 0) return r;
 	return timing_end(h, ev);
 }
 
@@ -3613,15 +3496,12 @@ static int ring_pack(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	const size_t S = (size_t)h->nstreams;
 	const int mode = h->opt.pack_results;
 	if (mode == 2 && gate_supported(c) < 0) return -ENOTSUP;
-	if (!in->d_packed[0]) {
-		for (int k = 0; k < 2; k++) {
-			HIP_TRY(hipMalloc(&in->d_packed[k], S * in->ostride * sizeof(int16_t)));  // (ostride is a multiple of 64)
-			HIP_TRY(hipMalloc(&in->d_pack_index[k], S * sizeof(rtlfm_packed_row)));
-			HIP_TRY(hipMalloc(&in->d_pack_total[k], sizeof(unsigned long long)));
-		}
-		in->packed_cap = S * in->ostride;
+	for (int k = 0; k < 2; k++) {
+		OWN_TRY(in->pk.d_packed[k].alloc(S * in->ostride));  // (ostride is a multiple of 64)
+		OWN_TRY(in->pk.d_pack_index[k].alloc(S));
+		OWN_TRY(in->pk.d_pack_total[k].alloc(1));
 	}
-	if (mode == 2 && !in->d_piece_off) HIP_TRY(hipMalloc(&in->d_piece_off, S * h->cap_blocks * sizeof(int32_t)));
+	if (mode == 2) OWN_TRY(in->pk.d_piece_off.alloc(S * h->cap_blocks));
 	const int par = (int)((h->step - 1) & 1);
 	if (h->tail_pending[par]) HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_tail[par], 0));
 	pack::PlanParams pp{};
@@ -3629,30 +3509,29 @@ static int ring_pack(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	pp.lens = in->d_result_len[f];
 	pp.levels = h->d_levels;
 	pp.sin = h->st[(h->st_cur + 2) % 3];
-	pp.piece_off = in->d_piece_off;
+	pp.piece_off = in->pk.d_piece_off;
 	pp.nblocks = nb;
 	pp.N = c.downsample_passes > 0 ? (int)((c.block_len / 2) >> c.downsample_passes) : (int)(c.block_len / 2);  // (as launch_gate)
 	pp.D = c.downsample_passes > 0 ? 1 : c.downsample;
 	pp.mul = c.mode == RTLFM_MODE_RAW ? 2 : 1;
 	pp.level = c.squelch_level; pp.conseq = h->opt.conseq_squelch;
-	pp.index = in->d_pack_index[f]; pp.total = in->d_pack_total[f];
+	pp.index = in->pk.d_pack_index[f]; pp.total = in->pk.d_pack_total[f];
 	pack::CopyParams cp{};
 	cp.mode = mode;
 	cp.R = in->d_result[f]; cp.rstride = in->ostride;
-	cp.packed = in->d_packed[f]; cp.cap = in->packed_cap;
+	cp.packed = in->pk.d_packed[f]; cp.cap = in->pk.d_packed[f].capacity();
 	cp.index = pp.index; cp.sin = pp.sin; cp.piece_off = pp.piece_off;
 	cp.nblocks = nb; cp.N = pp.N; cp.D = pp.D; cp.mul = pp.mul;
 	const size_t most = mode == 2 ? (size_t)pp.mul * (pp.N / pp.D + 1) : in->ostride;
-	in->pack_timed[f] = h->timing;
+	in->pk.pack_timed[f] = h->timing;
 	if (h->timing) {
-		for (hipEvent_t &e : in->ev_pack[f])
-			if (!e) HIP_TRY(hipEventCreate(&e));
-		HIP_TRY(hipEventRecord(in->ev_pack[f][0], h->stream));
+		for (Event &e : in->pk.ev_pack[f]) OWN_TRY(e.create());
+		HIP_TRY(hipEventRecord(in->pk.ev_pack[f][0], h->stream));
 	}
 	const int r = pack::launch_pack(pp, cp, most, h->stream);
 	if (r < 0) return r;
-	if (h->timing) HIP_TRY(hipEventRecord(in->ev_pack[f][1], h->stream));
-	in->pack_mode[f] = mode;
+	if (h->timing) HIP_TRY(hipEventRecord(in->pk.ev_pack[f][1], h->stream));
+	in->pk.pack_mode[f] = mode;
 	return 0;
 }
 
@@ -3727,18 +3606,18 @@ extern "C" int rtlfm_gpu_run_end(rtlfm_gpu *h)
 		in->run_pending[f] = false;
 	}
 	if (nb == h->cap_blocks)
-		HIP_TRY(hipMemcpyAsync(in->d_in[f], in->h_stage[f], stride * S, hipMemcpyHostToDevice, in->copy_stream));
+		HIP_TRY(hipMemcpyAsync(in->inp.d_in[f], in->inp.h_stage[f], stride * S, hipMemcpyHostToDevice, in->copy_stream));
 	else
-		HIP_TRY(hipMemcpy2DAsync(in->d_in[f], stride, in->h_stage[f], stride, (size_t)nb * L, S, hipMemcpyHostToDevice,
+		HIP_TRY(hipMemcpy2DAsync(in->inp.d_in[f], stride, in->inp.h_stage[f], stride, (size_t)nb * L, S, hipMemcpyHostToDevice,
 		                         in->copy_stream));
 	HIP_TRY(hipEventRecord(in->ev_h2d[f], in->copy_stream));
 	in->h2d_pending[f] = true;
 	HIP_TRY(hipStreamWaitEvent(h->stream, in->ev_h2d[f], 0));
 	if (h->mute_streams > 0 && (r = apply_mute(h, in, f, nb)) < 0) return r;
 	if (ragged) r = run_ragged(h, in, f, nb);
-	else r = run_device_impl(h, in->d_in[f], stride, nb, in->d_result[f], in->ostride, in->d_result_len[f]);
+	else r = run_device_impl(h, in->inp.d_in[f], stride, nb, in->d_result[f], in->ostride, in->d_result_len[f]);
 	if (r < 0) return r;
-	in->pack_mode[f] = 0;
+	in->pk.pack_mode[f] = 0;
 	if (h->opt.pack_results && (r = ring_pack(h, in, f, nb)) < 0) return r;
 	HIP_TRY(hipEventRecord(in->ev_run[f], h->stream));
 	in->run_pending[f] = true;
@@ -3809,7 +3688,7 @@ static int fetch_packed(rtlfm_gpu *h, bool prev, int16_t *out, size_t cap, rtlfm
 	Ingest *in = h->ing;
 	if (!in || (prev ? in->prev < 0 || in->prev == in->last : in->last < 0)) return -EAGAIN;
 	const int f = prev ? in->prev : in->last;
-	if (!in->pack_mode[f] || !in->d_packed[f]) return -ENODATA;
+	if (!in->pk.pack_mode[f] || !in->pk.d_packed[f]) return -ENODATA;
 	HIP_TRY(hipSetDevice(h->device));
 	if (prev) {
 		HIP_TRY(hipEventSynchronize(in->ev_run[f]));  // (recorded behind the pack, which waited for the run's tail)
@@ -3817,11 +3696,11 @@ static int fetch_packed(rtlfm_gpu *h, bool prev, int16_t *out, size_t cap, rtlfm
 		HIP_TRY(sync_all(h));
 	}
 	const size_t S = (size_t)h->nstreams;
-	HIP_TRY(hipMemcpy(rows, in->d_pack_index[f], S * sizeof(rtlfm_packed_row), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(rows, in->pk.d_pack_index[f], S * sizeof(rtlfm_packed_row), hipMemcpyDeviceToHost));
 	const size_t need = (size_t)rows[S - 1].offset + (((size_t)rows[S - 1].len + 7) & ~(size_t)7);
 	*total = need;
 	if (need > cap) return -ENOBUFS;
-	if (need > 0) HIP_TRY(hipMemcpy(out, in->d_packed[f], need * sizeof(int16_t), hipMemcpyDeviceToHost));
+	if (need > 0) HIP_TRY(hipMemcpy(out, in->pk.d_packed[f], need * sizeof(int16_t), hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -3859,10 +3738,8 @@ extern "C" int rtlfm_gpu_fetch(rtlfm_gpu *h, int stream, int16_t *out, int cap, 
 	HIP_TRY(hipSetDevice(h->device));
 	if (!in->mirror_valid) {
 		// one transfer for all streams, then every per-stream fetch is a host copy
-		if (!in->h_result) {
-			HIP_TRY(hipHostMalloc(&in->h_result, (size_t)h->nstreams * in->ostride * sizeof(int16_t), hipHostMallocDefault));
-			HIP_TRY(hipHostMalloc(&in->h_result_len, (size_t)h->nstreams * sizeof(int32_t), hipHostMallocDefault));
-		}
+		OWN_TRY(in->h_result.alloc((size_t)h->nstreams * in->ostride));
+		OWN_TRY(in->h_result_len.alloc((size_t)h->nstreams));
 		int r = rtlfm_gpu_fetch_all(h, in->h_result, in->ostride, in->h_result_len);
 		if (r < 0) return r;
 		in->mirror_valid = true;
@@ -3872,6 +3749,11 @@ extern "C" int rtlfm_gpu_fetch(rtlfm_gpu *h, int stream, int16_t *out, int cap, 
 	if (len > cap) return -ENOBUFS;
 	if (len > 0) memcpy(out, in->h_result + (size_t)stream * in->ostride, (size_t)len * sizeof(int16_t));
 	return 0;
+}
+
+extern "C" long rtlfm_debug_live(int kind)
+{
+	return kind >= 0 && kind <= 2 ? rtl_own::live(kind).load() : -EINVAL;
 }
 
 __global__ void k_selftest_atan2(const int32_t *yx, int n, int32_t *a, int32_t *b)
@@ -3901,14 +3783,13 @@ extern "C" int rtlfm_gpu_selftest_const_div(int device, const int32_t *nd, int n
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return -ENODEV;
 	HIP_TRY(hipSetDevice(device));
-	int32_t *d_in = nullptr, *d_q = nullptr;
-	HIP_TRY(hipMalloc(&d_in, (size_t)n * 8));
-	HIP_TRY(hipMalloc(&d_q, (size_t)n * 4));
+	DevBuf<int32_t> d_in, d_q;
+	OWN_TRY(d_in.alloc((size_t)n * 2));
+	OWN_TRY(d_q.alloc((size_t)n));
 	HIP_TRY(hipMemcpy(d_in, nd, (size_t)n * 8, hipMemcpyHostToDevice));
 	k_selftest_const_div<<<grid_for((size_t)n), 256>>>(d_in, n, d_q);
 	HIP_TRY(hipDeviceSynchronize());
 	HIP_TRY(hipMemcpy(q, d_q, (size_t)n * 4, hipMemcpyDeviceToHost));
-	hipFree(d_in); hipFree(d_q);
 	return 0;
 }
 
@@ -3918,14 +3799,13 @@ extern "C" int rtlfm_gpu_selftest_fast_atan2(int device, const int32_t *yx, int 
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return -ENODEV;
 	HIP_TRY(hipSetDevice(device));
-	int32_t *d_in = nullptr, *d_a = nullptr;
-	HIP_TRY(hipMalloc(&d_in, (size_t)n * 8));
-	HIP_TRY(hipMalloc(&d_a, (size_t)n * 4));
+	DevBuf<int32_t> d_in, d_a;
+	OWN_TRY(d_in.alloc((size_t)n * 2));
+	OWN_TRY(d_a.alloc((size_t)n));
 	HIP_TRY(hipMemcpy(d_in, yx, (size_t)n * 8, hipMemcpyHostToDevice));
 	k_selftest_fast_atan2<<<grid_for((size_t)n), 256>>>(d_in, n, d_a);
 	HIP_TRY(hipDeviceSynchronize());
 	HIP_TRY(hipMemcpy(q14, d_a, (size_t)n * 4, hipMemcpyDeviceToHost));
-	hipFree(d_in); hipFree(d_a);
 	return 0;
 }
 
@@ -3935,16 +3815,15 @@ extern "C" int rtlfm_gpu_selftest_atan2(int device, const int32_t *yx, int n, in
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return -ENODEV;
 	HIP_TRY(hipSetDevice(device));
-	int32_t *d_in = nullptr, *d_a = nullptr, *d_b = nullptr;
-	HIP_TRY(hipMalloc(&d_in, (size_t)n * 8));
-	HIP_TRY(hipMalloc(&d_a, (size_t)n * 4));
-	HIP_TRY(hipMalloc(&d_b, (size_t)n * 4));
+	DevBuf<int32_t> d_in, d_a, d_b;
+	OWN_TRY(d_in.alloc((size_t)n * 2));
+	OWN_TRY(d_a.alloc((size_t)n));
+	OWN_TRY(d_b.alloc((size_t)n));
 	HIP_TRY(hipMemcpy(d_in, yx, (size_t)n * 8, hipMemcpyHostToDevice));
-	k_selftest_atan2<<<grid_for((size_t)n), 256>>>(d_in, n, q14 ? d_a : nullptr, q14_libm ? d_b : nullptr);
+	k_selftest_atan2<<<grid_for((size_t)n), 256>>>(d_in, n, q14 ? d_a.get() : nullptr, q14_libm ? d_b.get() : nullptr);
 	HIP_TRY(hipDeviceSynchronize());
 	if (q14) HIP_TRY(hipMemcpy(q14, d_a, (size_t)n * 4, hipMemcpyDeviceToHost));
 	if (q14_libm) HIP_TRY(hipMemcpy(q14_libm, d_b, (size_t)n * 4, hipMemcpyDeviceToHost));
-	hipFree(d_in); hipFree(d_a); hipFree(d_b);
 	return 0;
 }
 

@@ -46,19 +46,13 @@ using namespace rtlfm;
 namespace {
 
 struct ProbeRig {
-	uint32_t *sink = nullptr;
-	hipEvent_t a = nullptr, b = nullptr;
+	DevBuf<uint32_t> sink;
+	Event a, b;
 	int init()
 	{
-		if (hipMalloc(&sink, (size_t)8192 * 256) != hipSuccess) return -ENOMEM;
-		if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return -EIO;
-		return 0;
-	}
-	~ProbeRig()
-	{
-		if (a) hipEventDestroy(a);
-		if (b) hipEventDestroy(b);
-		if (sink) hipFree(sink);
+		OWN_TRY(sink.alloc((size_t)8192 * 64));
+		OWN_TRY(a.create());
+		return b.create();
 	}
 	// ms per launch: `region` bytes of `in` streamed by 8192 waves, W bytes stored per lane and tile into `out`
 	// (region / 8192 * 64 * W / 8192 ... = region * W / 128 bytes in all)
@@ -340,22 +334,24 @@ extern "C" int rtlfm_gpu_bw_probe(int device, size_t bytes, int write_div, int r
 	for (int w : {2, 4, 8, 16})
 		if (fabs(128.0 / write_div - w) < fabs(128.0 / write_div - W)) W = w;
 	const size_t wbytes = total / 128 * W + 4096;
-	uint8_t *d_in = nullptr, *d_near = nullptr;
-	void *d_far = nullptr;
+	DevBuf<uint8_t> d_in, d_far;
+	uint8_t *d_near = nullptr;
+	void *far = nullptr;
 	ProbeRig rig;
 	int rc = rig.init();
 	if (rc < 0) return rc;
 	do {
 		// input and the co-located output in ONE allocation: the same quarter by construction
-		if (hipMalloc(&d_in, total + wbytes) != hipSuccess) { rc = -ENOMEM; break; }
+		if ((rc = d_in.alloc(total + wbytes)) < 0) break;
 		d_near = d_in + total;
 		if (hipMemset(d_in, 0x5a, total) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) { rc = -EIO; break; }
 		int apart = 0;
 		// (a measurement, not a service path: the walk may be long)
-		if ((rc = rtlfm_gpu_malloc_apart_ex(device, wbytes, d_in, total, (size_t)150 << 30, &d_far, &apart, nullptr, nullptr)) < 0) break;
+		if ((rc = rtlfm_gpu_malloc_apart_ex(device, wbytes, d_in, total, (size_t)150 << 30, &far, &apart, nullptr, nullptr)) < 0) break;
+		if ((rc = d_far.adopt(far, wbytes)) < 0) break;
 		float ms[3] = {0, 0, 0};
 		if ((rc = rig.run(d_in, total, nullptr, 0, reps, &ms[0])) < 0) break;
-		if ((rc = rig.run(d_in, total, (uint8_t *)d_far, W, reps, &ms[1])) < 0) break;
+		if ((rc = rig.run(d_in, total, d_far, W, reps, &ms[1])) < 0) break;
 		if ((rc = rig.run(d_in, total, d_near, W, reps, &ms[2])) < 0) break;
 		const double moved = (double)total * (1.0 + W / 128.0);
 		if (read_gbs) *read_gbs = (double)total / (ms[0] * 1e-3) / 1e9;
@@ -364,8 +360,6 @@ extern "C" int rtlfm_gpu_bw_probe(int device, size_t bytes, int write_div, int r
 		if (write_fraction) *write_fraction = W / 128.0;
 		rc = apart;  // 1: the "apart" figure really is a quarter away
 	} while (0);
-	if (d_in) hipFree(d_in);
-	if (d_far) hipFree(d_far);
 	return rc;
 }
 

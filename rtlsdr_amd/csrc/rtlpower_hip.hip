@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/rtlpower_hip.h"
+#define OWN_UNIT "rtlpower_hip"
 #include "debug_poison.h"
 #include "stream_pool.h"
 #include "power_kernels.h"
@@ -33,29 +34,28 @@ struct rtlpower_gpu {
 	rtlpower_cfg cfg;
 	int nstreams = 0, device = 0;
 	hipStream_t own_stream = nullptr, stream = nullptr;
-	hipEvent_t ev_wait = nullptr, ev_release = nullptr;
+	Event ev_wait, ev_release;
 	int N = 1, len_dec = 0, chunks = 0, dec_elems = 0;
 	bool decimates = false;
-	int32_t *d_window = nullptr;
-	uint16_t *d_window16 = nullptr;  // the low halves (k_power_scan_big multiplies in 16 bits)
-	uint32_t *d_tw = nullptr;
-	long long *d_avg = nullptr;
-	int32_t *d_samples = nullptr;
-	int16_t *d_decA = nullptr, *d_decB = nullptr;
-	size_t dec_cap_reads = 0;
-	uint8_t *d_one = nullptr;  // landing zone of rtlpower_gpu_scan()
+	DevBuf<int32_t> d_window;
+	DevBuf<uint16_t> d_window16;  // the low halves (k_power_scan_big multiplies in 16 bits)
+	DevBuf<uint32_t> d_tw;
+	DevBuf<long long> d_avg;
+	DevBuf<int32_t> d_samples;
+	DevBuf<int16_t> d_decA, d_decB;
+	DevBuf<uint8_t> d_one;  // landing zone of rtlpower_gpu_scan()
 	bool timing = false;
 	int groups = 0;  // option "groups": workgroups per stream of the FFT kernel (0 = automatic)
 	bool staged = false;                   // bin_e 15 .. 21 or more points per read than a workgroup's LDS holds: transform in HBM
-	uint32_t *d_work = nullptr; int2 *d_ave = nullptr;
+	DevBuf<uint32_t> d_work; DevBuf<int2> d_ave;
 	// one undecimated frame per read, bin_e > 14: the window comb by comb, the batch's bytes likewise, the averages' partial sums
-	uint16_t *d_window16T = nullptr; uint8_t *d_tbuf = nullptr; int2 *d_part = nullptr; bool attr_comb = false;
+	DevBuf<uint16_t> d_window16T; DevBuf<uint8_t> d_tbuf; DevBuf<int2> d_part; bool attr_comb = false;
 	int scan_frames = 1;  // option "scan_frames": 0 = k_power_scan also where k_power_scan_frames applies (A/B, tests)
 	bool attr_frames = false;
 	// decimated scans (a range below 1 MHz, src/rtl_power.c:466-480) in two launches: k_power_downsample_iq (-F) or
 	// k_power_boxcar into packed int16 pairs, k_power_scan_frames<13, true> on them
 	int dec_fast = 1;     // option "dec_fast": 0 = the general kernels (one launch per pass, k_power_scan) also where these apply
-	uint32_t *d_dec32 = nullptr; size_t dec32_cap = 0;  // dwords
+	DevBuf<uint32_t> d_dec32;
 	bool attr_frames16 = false;
 	int last_kernel = 0;  // option "last_kernel" (read-only): which transform kernel the last scan took (RTLPOWER_KERNEL_*)
 	int staged_fast = 1;  // option "staged_fast": 0 = the general kernels also where the fast ones apply (A/B, tests)
@@ -68,29 +68,30 @@ struct rtlpower_gpu {
 	struct Pipe {
 		hipStream_t aux = nullptr;
 		int aux_prio = 0;  // the HIP priority aux was taken from the stream pool with
-		hipEvent_t start = nullptr, prep[2] = {nullptr, nullptr}, scanned[2] = {nullptr, nullptr}, done = nullptr;
+		Event start, prep[2], scanned[2], done;
 	} pipe;
 	bool work_two = false;  // d_work / d_ave / d_tbuf / d_part hold two batches
 	size_t work_reads = 0;                 // reads the work buffer holds per stream
 	bool attr_lds = false;
 	bool want_stamps = false;              // rtlpower_gpu_clock_probe
-	unsigned long long *d_stamps = nullptr;
-	int stamp_cap = 0, stamp_last = 0;     // workgroups the buffer holds / of the last stamped launch
+	DevBuf<unsigned long long> d_stamps;   // four per workgroup
+	int stamp_last = 0;                    // workgroups of the last stamped launch
 	bool attr_set = false, attr_big = false;  // the kernels' dynamic-LDS limits are raised on this handle's device
-	std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending, ev_free;
+	std::vector<std::pair<Event, Event>> ev_pending, ev_free;
 	// rtlpower_gpu_report (power_report_kernel.h): one device block - doubt counter, doubt list, samples, values - and its
 	// pinned mirror, both allocated by the first report; `arrived` is the kernel's per-stream counter
-	uint8_t *d_rep = nullptr, *h_rep = nullptr;
-	uint32_t *d_arrived = nullptr;
-	hipEvent_t ev_rep = nullptr;
+	DevBuf<uint8_t> d_rep;
+	PinnedBuf<uint8_t> h_rep;
+	DevBuf<uint32_t> d_arrived;
+	Event ev_rep;
 	int rep_outn = 0;            // values per stream of the last report (the kept bins and the trailing value)
 	double rep_rate = 0;
 	bool rep_issued = false, rep_resolved = false;
 	int rep_status = 0;          // what resolving found (0, -EOVERFLOW, -EIO)
 	long rep_doubts = 0;         // option "report_doubts" (read-only)
 	long rep_guard_ppm = 1;      // option "report_guard_ppm": the guard in millionths of a hundredth of a dB (tests widen it)
-	uint8_t *d_in = nullptr; size_t in_cap = 0;  // landing zone of rtlpower_gpu_scan_host()
-	hipEvent_t ev_in = nullptr;
+	DevBuf<uint8_t> d_in;  // landing zone of rtlpower_gpu_scan_host()
+	Event ev_in;
 };
 
 // the window functions, src/rtl_power.c:329-408
@@ -414,23 +415,23 @@ static int power_create_body(rtlpower_gpu *h)
 	HIP_TRY(rtl_pool::stream_get(h->device, 0, &h->own_stream));  // (from the process-wide pool: stream_pool.h)
 	h->stream = h->own_stream;
 	const size_t S = (size_t)nstreams;
-	HIP_TRY(hipMalloc(&h->d_avg, S * h->N * sizeof(long long)));
-	HIP_TRY(hipMalloc(&h->d_samples, S * sizeof(int32_t)));
+	OWN_TRY(h->d_avg.alloc(S * h->N));
+	OWN_TRY(h->d_samples.alloc(S));
 	if (cfg->bin_e > 0) {
 		std::vector<int32_t> w((size_t)h->N);
 		rtlpower_window_coefs(cfg->window, h->N, w.data());
-		HIP_TRY(hipMalloc(&h->d_window, w.size() * sizeof(int32_t)));
+		OWN_TRY(h->d_window.alloc(w.size()));
 		HIP_TRY(hipMemcpy(h->d_window, w.data(), w.size() * sizeof(int32_t), hipMemcpyHostToDevice));
 		std::vector<uint16_t> w16(w.size());
 		for (size_t i = 0; i < w.size(); i++) w16[i] = (uint16_t)(uint32_t)w[i];
-		HIP_TRY(hipMalloc(&h->d_window16, w16.size() * sizeof(uint16_t)));
+		OWN_TRY(h->d_window16.alloc(w16.size()));
 		HIP_TRY(hipMemcpy(h->d_window16, w16.data(), w16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
 		if (cfg->bin_e > 14) {
 			// comb b of the frame = the points k << c | b: k_power_scan_big<14, true> reads its coefficients as it reads a read's
 			const int cc = cfg->bin_e - 14;
 			std::vector<uint16_t> wt(w16.size());
 			for (size_t j = 0; j < w16.size(); j++) wt[((j & (((size_t)1 << cc) - 1)) << 14) | (j >> cc)] = w16[j];
-			HIP_TRY(hipMalloc(&h->d_window16T, wt.size() * sizeof(uint16_t)));
+			OWN_TRY(h->d_window16T.alloc(wt.size()));
 			HIP_TRY(hipMemcpy(h->d_window16T, wt.data(), wt.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
 		}
 		// sine_table(), src/rtl_power.c:247-261, regrouped per FFT stage: stage s uses
@@ -451,7 +452,7 @@ static int power_create_body(rtlpower_gpu *h)
 				tw[(size_t)(1 << st) - 1 + m] = (uint32_t)(uint16_t)(wr * 2) | ((uint32_t)(uint16_t)(wi * 2) << 16);
 			}
 		}
-		HIP_TRY(hipMalloc(&h->d_tw, tw.size() * sizeof(uint32_t)));
+		OWN_TRY(h->d_tw.alloc(tw.size()));
 		HIP_TRY(hipMemcpy(h->d_tw, tw.data(), tw.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
 	}
 	return rtlpower_gpu_clear(h);
@@ -462,19 +463,7 @@ extern "C" int rtlpower_gpu_destroy(rtlpower_gpu *h)
 	if (!h) return -EINVAL;
 	(void)hipSetDevice(h->device);
 	if (h->stream) (void)hipStreamSynchronize(h->stream);
-	for (hipEvent_t e : {h->ev_wait, h->ev_release})
-		if (e) (void)hipEventDestroy(e);
-	for (auto &p : h->ev_pending) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-	for (auto &p : h->ev_free) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-	if (h->h_rep) (void)hipHostFree(h->h_rep);
-	for (hipEvent_t e : {h->ev_rep, h->ev_in})
-		if (e) (void)hipEventDestroy(e);
-	void *ptrs[] = {h->d_rep, h->d_arrived, h->d_in, h->d_window, h->d_window16, h->d_tw, h->d_avg, h->d_samples, h->d_decA, h->d_decB, h->d_one, h->d_stamps, h->d_work, h->d_ave, h->d_window16T, h->d_tbuf, h->d_part, h->d_dec32};
-	for (void *p : ptrs)
-		if (p) (void)hipFree(p);
 	if (h->pipe.aux) (void)hipStreamSynchronize(h->pipe.aux);
-	for (hipEvent_t e : {h->pipe.start, h->pipe.prep[0], h->pipe.prep[1], h->pipe.scanned[0], h->pipe.scanned[1], h->pipe.done})
-		if (e) (void)hipEventDestroy(e);
 	// back to the pool, never destroyed (stream_pool.h)
 	rtl_pool::stream_put(h->device, h->pipe.aux_prio, h->pipe.aux);
 	rtl_pool::stream_put(h->device, 0, h->own_stream);
@@ -513,7 +502,7 @@ extern "C" int rtlpower_gpu_wait_for(rtlpower_gpu *h, void *producer_stream)
 	if (!h) return -EINVAL;
 	if ((hipStream_t)producer_stream == h->stream) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	if (!h->ev_wait) HIP_TRY(hipEventCreateWithFlags(&h->ev_wait, hipEventDisableTiming));
+	OWN_TRY(h->ev_wait.create(hipEventDisableTiming));
 	HIP_TRY(hipEventRecord(h->ev_wait, (hipStream_t)producer_stream));
 	HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_wait, 0));
 	return 0;
@@ -524,7 +513,7 @@ extern "C" int rtlpower_gpu_release_to(rtlpower_gpu *h, void *consumer_stream)
 	if (!h) return -EINVAL;
 	if ((hipStream_t)consumer_stream == h->stream) return 0;
 	HIP_TRY(hipSetDevice(h->device));
-	if (!h->ev_release) HIP_TRY(hipEventCreateWithFlags(&h->ev_release, hipEventDisableTiming));
+	OWN_TRY(h->ev_release.create(hipEventDisableTiming));
 	HIP_TRY(hipEventRecord(h->ev_release, h->stream));
 	HIP_TRY(hipStreamWaitEvent((hipStream_t)consumer_stream, h->ev_release, 0));
 	return 0;
@@ -638,7 +627,7 @@ extern "C" int rtlpower_gpu_timing_read(rtlpower_gpu *h, double *ms, int *launch
 		float t = 0;
 		HIP_TRY(hipEventElapsedTime(&t, p.first, p.second));
 		total += t; n++;
-		h->ev_free.push_back(p);
+		h->ev_free.push_back(std::move(p));
 	}
 	h->ev_pending.clear();
 	if (ms) *ms = total;
@@ -678,17 +667,11 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 		const bool by_boxcar = c.boxcar && c.downsample > 1 && (int)(c.buf_len / 2) == Pr * c.downsample;
 		if (h->dec_fast && h->decimates && !h->staged && pow2 && aligned && c.bin_e >= 3 && h->N <= Pr && (by_fifth || by_boxcar)) {
 			const size_t need = (size_t)S * nreads * Pr;
-			if (h->dec32_cap < need) {
-				HIP_TRY(hipStreamSynchronize(q));
-				if (h->d_dec32) (void)hipFree(h->d_dec32);
-				h->d_dec32 = nullptr; h->dec32_cap = 0;
-				HIP_TRY(hipMalloc(&h->d_dec32, need * sizeof(uint32_t)));
-				h->dec32_cap = need;
-			}
-			std::pair<hipEvent_t, hipEvent_t> ev;
+			OWN_TRY(h->d_dec32.grow(need, q));
+			std::pair<Event, Event> ev;
 			if (h->timing) {
-				if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); }
-				else { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
+				if (!h->ev_free.empty()) { ev = std::move(h->ev_free.back()); h->ev_free.pop_back(); }
+				else { OWN_TRY(ev.first.create()); OWN_TRY(ev.second.create()); }
 				HIP_TRY(hipEventRecord(ev.first, q));
 			}
 			if (by_fifth) {
@@ -710,7 +693,7 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 				}
 			} else {
 				k_power_boxcar<<<grid_for((size_t)S * nreads * Pr), 256, 0, q>>>(
-				    d_iq, stream_stride, nreads, (int)c.buf_len, c.downsample, S, reinterpret_cast<int16_t *>(h->d_dec32),
+				    d_iq, stream_stride, nreads, (int)c.buf_len, c.downsample, S, reinterpret_cast<int16_t *>(h->d_dec32.get()),
 				    (size_t)nreads * 2 * Pr, (size_t)2 * Pr, Pr);
 			}
 			ScanParams p{};
@@ -736,7 +719,7 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 			HIP_TRY(hipGetLastError());
 			if (h->timing) {
 				HIP_TRY(hipEventRecord(ev.second, q));
-				h->ev_pending.push_back(ev);
+				h->ev_pending.push_back(std::move(ev));
 			}
 			return 0;
 		}
@@ -746,12 +729,8 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 	if (h->decimates) {
 		drs = (size_t)c.buf_len;  // elements reserved per read
 		dss = drs * nreads;
-		if (h->dec_cap_reads < (size_t)nreads) {
-			if (h->d_decA) { (void)hipFree(h->d_decA); (void)hipFree(h->d_decB); h->d_decA = h->d_decB = nullptr; }
-			HIP_TRY(hipMalloc(&h->d_decA, (size_t)S * dss * sizeof(int16_t)));
-			HIP_TRY(hipMalloc(&h->d_decB, (size_t)S * dss * sizeof(int16_t)));
-			h->dec_cap_reads = nreads;
-		}
+		OWN_TRY(h->d_decA.grow((size_t)S * dss, q));
+		OWN_TRY(h->d_decB.grow((size_t)S * dss, q));
 		int16_t *cur = h->d_decA, *oth = h->d_decB;
 		if (c.boxcar) {
 			const int out_cplx = h->dec_elems / 2;
@@ -796,15 +775,14 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 		if (h->work_reads < batch || (two && !h->work_two)) {
 			HIP_TRY(hipStreamSynchronize(q));
 			if (h->pipe.aux) HIP_TRY(hipStreamSynchronize(h->pipe.aux));
-			if (h->d_work) { (void)hipFree(h->d_work); (void)hipFree(h->d_ave); h->d_work = nullptr; h->d_ave = nullptr; }
-			if (h->d_tbuf) { (void)hipFree(h->d_tbuf); (void)hipFree(h->d_part); h->d_tbuf = nullptr; h->d_part = nullptr; }
+			h->d_work.reset(); h->d_ave.reset(); h->d_tbuf.reset(); h->d_part.reset();
 			h->work_reads = 0; h->work_two = false;
 			const size_t sets = two ? 2 : 1;
-			HIP_TRY(hipMalloc(&h->d_work, sets * S * batch * M * sizeof(uint32_t)));
-			HIP_TRY(hipMalloc(&h->d_ave, sets * S * batch * sizeof(int2)));
+			OWN_TRY(h->d_work.alloc(sets * S * batch * M));
+			OWN_TRY(h->d_ave.alloc(sets * S * batch));
 			if (fast_shape) {
-				HIP_TRY(hipMalloc(&h->d_tbuf, sets * S * batch * M * 2));
-				HIP_TRY(hipMalloc(&h->d_part, sets * S * batch * (M / 8192) * sizeof(int2)));
+				OWN_TRY(h->d_tbuf.alloc(sets * S * batch * M * 2));
+				OWN_TRY(h->d_part.alloc(sets * S * batch * (M / 8192)));
 			}
 			h->work_reads = batch; h->work_two = two;
 		}
@@ -823,10 +801,10 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 			                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
 			h->attr_lds = true;
 		}
-		std::pair<hipEvent_t, hipEvent_t> ev;
+		std::pair<Event, Event> ev;
 		if (h->timing) {
-			if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); }
-			else { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
+			if (!h->ev_free.empty()) { ev = std::move(h->ev_free.back()); h->ev_free.pop_back(); }
+			else { OWN_TRY(ev.first.create()); OWN_TRY(ev.second.create()); }
 			HIP_TRY(hipEventRecord(ev.first, q));
 		}
 		const bool piped = fast && two && h->work_two && (h->staged_pipe == 2 || (size_t)nreads > batch);
@@ -835,8 +813,8 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 			HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
 			HIP_TRY(rtl_pool::stream_get(h->device, lo, &h->pipe.aux));  // (a priority of its own: a hardware queue of its own)
 			h->pipe.aux_prio = lo;
-			for (hipEvent_t *e : {&h->pipe.start, &h->pipe.prep[0], &h->pipe.prep[1], &h->pipe.scanned[0], &h->pipe.scanned[1], &h->pipe.done})
-				HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+			for (Event *e : {&h->pipe.start, &h->pipe.prep[0], &h->pipe.prep[1], &h->pipe.scanned[0], &h->pipe.scanned[1], &h->pipe.done})
+				OWN_TRY(e->create(hipEventDisableTiming));
 		}
 		hipStream_t qa = piped ? h->pipe.aux : q;  // where the byte-moving kernels go
 		// the sets of work buffers (piped: batch k uses set k & 1; the handle's allocation holds work_reads reads per set)
@@ -919,7 +897,7 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 		HIP_TRY(hipGetLastError());
 		if (h->timing) {
 			HIP_TRY(hipEventRecord(ev.second, q));
-			h->ev_pending.push_back(ev);
+			h->ev_pending.push_back(std::move(ev));
 		}
 		return 0;
 	}
@@ -937,10 +915,10 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 		                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
 		h->attr_set = true;
 	}
-	std::pair<hipEvent_t, hipEvent_t> ev;
+	std::pair<Event, Event> ev;
 	if (h->timing) {
-		if (!h->ev_free.empty()) { ev = h->ev_free.back(); h->ev_free.pop_back(); }
-		else { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
+		if (!h->ev_free.empty()) { ev = std::move(h->ev_free.back()); h->ev_free.pop_back(); }
+		else { OWN_TRY(ev.first.create()); OWN_TRY(ev.second.create()); }
 		HIP_TRY(hipEventRecord(ev.first, q));
 	}
 	const bool big = !dec && h->chunks == 1 && h->len_dec == 2 * h->N && (c.bin_e == 13 || c.bin_e == 14) &&
@@ -964,12 +942,7 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 	}
 	const unsigned grid = (unsigned)S * (unsigned)p.groups;
 	if (big && h->want_stamps) {
-		if (h->stamp_cap < (int)grid) {
-			if (h->d_stamps) (void)hipFree(h->d_stamps);
-			h->d_stamps = nullptr; h->stamp_cap = 0;
-			HIP_TRY(hipMalloc(&h->d_stamps, (size_t)grid * 32));
-			h->stamp_cap = (int)grid;
-		}
+		OWN_TRY(h->d_stamps.grow((size_t)grid * 4, q));
 		HIP_TRY(hipMemsetAsync(h->d_stamps, 0, (size_t)grid * 32, q));
 		p.stamps = h->d_stamps;
 		h->stamp_last = (int)grid;
@@ -995,7 +968,7 @@ extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, si
 	HIP_TRY(hipGetLastError());
 	if (h->timing) {
 		HIP_TRY(hipEventRecord(ev.second, q));
-		h->ev_pending.push_back(ev);
+		h->ev_pending.push_back(std::move(ev));
 	}
 	return 0;
 }
@@ -1006,31 +979,29 @@ extern "C" int rtlpower_gpu_scan(rtlpower_gpu *h, int stream, const uint8_t *buf
 	// through a one-stream view of the handle
 	if (!h || !buf || stream < 0 || stream >= h->nstreams || len != h->cfg.buf_len) return -EINVAL;
 	HIP_TRY(hipSetDevice(h->device));
-	if (!h->d_one) HIP_TRY(hipMalloc(&h->d_one, h->cfg.buf_len));
+	OWN_TRY(h->d_one.alloc(h->cfg.buf_len));
 	HIP_TRY(hipMemcpyAsync(h->d_one, buf, len, hipMemcpyHostToDevice, h->stream));
-	rtlpower_gpu view = *h;  // shallow: same device buffers, shifted to this stream
+	// A copy: aliases of the handle's device buffers (device_own.h), shifted to this stream.  Its work buffers - sized by the
+	// scan - are its own: reset() leaves empty owners, and what the scan allocates into them goes with the view, at the end
+	// of this function: behind the synchronisation, also when that failed.
+	rtlpower_gpu view = *h;
 	view.nstreams = 1;
-	view.d_avg = h->d_avg + (size_t)stream * h->N;
-	view.d_samples = h->d_samples + stream;
-	view.d_decA = view.d_decB = nullptr; view.dec_cap_reads = 0;
-	view.d_work = nullptr; view.d_ave = nullptr; view.work_reads = 0; view.work_two = false;
-	view.d_tbuf = nullptr; view.d_part = nullptr;
-	view.d_dec32 = nullptr; view.dec32_cap = 0;
-	view.want_stamps = false;  // (the stamp buffer would be the view's: one leak per scan, and nothing for rtlpower_gpu_clock_read to find)
+	view.d_avg = h->d_avg.alias((size_t)stream * h->N);
+	view.d_samples = h->d_samples.alias(stream);
+	view.d_decA.reset(); view.d_decB.reset();
+	view.d_work.reset(); view.d_ave.reset(); view.work_reads = 0; view.work_two = false;
+	view.d_tbuf.reset(); view.d_part.reset();
+	view.d_dec32.reset();
+	if (!h->pipe.aux) view.pipe = rtlpower_gpu::Pipe{};  // (an owner's: whoever needs it first creates it)
+	view.want_stamps = false;  // (the stamp buffer would be the view's: nothing for rtlpower_gpu_clock_read to find)
 	view.ev_pending.clear(); view.ev_free.clear(); view.timing = false;
 	int r = rtlpower_gpu_scan_device(&view, h->d_one, h->cfg.buf_len, 1);
 	// what the view learnt about this device stays learnt (the kernels' dynamic-LDS limits are raised once per handle)
 	h->attr_set = view.attr_set; h->attr_big = view.attr_big; h->attr_lds = view.attr_lds; h->attr_comb = view.attr_comb;
 	h->attr_frames = view.attr_frames; h->attr_frames16 = view.attr_frames16;
 	h->last_kernel = view.last_kernel;
-	h->pipe = view.pipe;  // (created by whoever needed it first)
-	const hipError_t e = hipStreamSynchronize(h->stream);
-	if (view.d_decA) { (void)hipFree(view.d_decA); (void)hipFree(view.d_decB); }  // also when the sync failed
-	if (view.d_work) { (void)hipFree(view.d_work); (void)hipFree(view.d_ave); }
-	if (view.d_tbuf) { (void)hipFree(view.d_tbuf); (void)hipFree(view.d_part); }
-	if (view.d_dec32) (void)hipFree(view.d_dec32);
-	if (e != hipSuccess) return -EIO;
-	return r;
+	if (!h->pipe.aux && view.pipe.aux) h->pipe = std::move(view.pipe);
+	return hipStreamSynchronize(h->stream) == hipSuccess ? r : -EIO;
 }
 
 extern "C" int rtlpower_gpu_fetch(rtlpower_gpu *h, int stream, int64_t *avg, int32_t *samples)
@@ -1064,14 +1035,8 @@ extern "C" int rtlpower_gpu_scan_host(rtlpower_gpu *h, const uint8_t *iq, size_t
 	HIP_TRY(hipSetDevice(h->device));
 	const size_t pitch = (row + 15) & ~(size_t)15;
 	const size_t need = pitch * (size_t)h->nstreams;
-	if (h->in_cap < need) {
-		HIP_TRY(hipStreamSynchronize(h->stream));  // an earlier scan may still read the old buffer
-		if (h->d_in) (void)hipFree(h->d_in);
-		h->d_in = nullptr; h->in_cap = 0;
-		HIP_TRY(hipMalloc(&h->d_in, need));
-		h->in_cap = need;
-	}
-	if (!h->ev_in) HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+	OWN_TRY(h->d_in.grow(need, h->stream));  // (behind an earlier scan that may still read the old buffer)
+	OWN_TRY(h->ev_in.create(hipEventDisableTiming));
 	HIP_TRY(hipMemcpy2DAsync(h->d_in, pitch, iq, stream_stride, row, (size_t)h->nstreams, hipMemcpyHostToDevice, h->stream));
 	HIP_TRY(hipEventRecord(h->ev_in, h->stream));
 	const int r = rtlpower_gpu_scan_device(h, h->d_in, pitch, nreads);
@@ -1097,15 +1062,11 @@ extern "C" int rtlpower_gpu_report(rtlpower_gpu *h, double rate, double crop, in
 	const size_t vals_at = rep_values_at(S);
 	if (!h->ev_rep) {  // first use: sized for crop 0.  ev_rep is created last; a first use that failed half way starts over
 		const size_t bytes = vals_at + (size_t)S * ((size_t)h->N + 1) * sizeof(uint32_t);
-		if (h->h_rep) (void)hipHostFree(h->h_rep);
-		if (h->d_arrived) (void)hipFree(h->d_arrived);
-		if (h->d_rep) (void)hipFree(h->d_rep);
-		h->h_rep = nullptr; h->d_arrived = nullptr; h->d_rep = nullptr;
-		HIP_TRY(hipMalloc(&h->d_rep, bytes));
-		HIP_TRY(hipMalloc(&h->d_arrived, (size_t)S * sizeof(uint32_t)));
+		OWN_TRY(h->d_rep.alloc(bytes));
+		OWN_TRY(h->d_arrived.alloc((size_t)S));
 		HIP_TRY(hipMemset(h->d_arrived, 0, (size_t)S * sizeof(uint32_t)));
-		HIP_TRY(hipHostMalloc(&h->h_rep, bytes, hipHostMallocDefault));
-		HIP_TRY(hipEventCreateWithFlags(&h->ev_rep, hipEventDisableTiming));
+		OWN_TRY(h->h_rep.alloc(bytes));
+		OWN_TRY(h->ev_rep.create(hipEventDisableTiming));
 	}
 	if (h->rep_issued) HIP_TRY(hipEventSynchronize(h->ev_rep));  // the last report's copy has left the pinned block
 	hipStream_t q = h->stream;
@@ -1122,7 +1083,7 @@ extern "C" int rtlpower_gpu_report(rtlpower_gpu *h, double rate, double crop, in
 	p.seg = ((h->N + groups - 1) / groups + kReportThreads - 1) / kReportThreads * kReportThreads;
 	p.groups = (h->N + p.seg - 1) / p.seg;
 	p.rate = rate; p.guard = (double)h->rep_guard_ppm * 1e-6;
-	p.doubt_count = reinterpret_cast<uint32_t *>(h->d_rep);
+	p.doubt_count = reinterpret_cast<uint32_t *>(h->d_rep.get());
 	p.doubts = reinterpret_cast<ReportDoubt *>(h->d_rep + kRepDoubtsAt); p.doubt_cap = kDoubtCap;
 	p.out_samples = reinterpret_cast<int32_t *>(h->d_rep + kRepSamplesAt);
 	p.out = reinterpret_cast<uint32_t *>(h->d_rep + vals_at);
@@ -1144,7 +1105,7 @@ static int report_wait(rtlpower_gpu *h)
 	if (h->rep_resolved) return h->rep_status;
 	HIP_TRY(hipSetDevice(h->device));
 	HIP_TRY(hipEventSynchronize(h->ev_rep));
-	const uint32_t count = *reinterpret_cast<const uint32_t *>(h->h_rep);
+	const uint32_t count = *reinterpret_cast<const uint32_t *>(h->h_rep.get());
 	h->rep_doubts = (long)count;
 	h->rep_resolved = true;
 	if (count > kDoubtCap) {
