@@ -117,7 +117,8 @@ int rtlpower_window_coefs(int window, int length, int32_t *out);
  * what frequency_range() can plan (src/rtl_power.c:483-486): up to 2^14 points per read the transform lives in a
  * workgroup's LDS, beyond that (bin_e 15 ... 21, or more frames per read) the same stages run over a work buffer in HBM.
  * Outside scanner()'s own domain - a trailing FFT frame that reaches past the read,
- * where the reference transforms whatever its static fft_buf still holds (src/rtl_power.c:695) - is refused. */
+ * where the reference transforms whatever its static fft_buf still holds (src/rtl_power.c:695) - is refused, and so is
+ * a read of fewer than two values after decimation, where its remove_dc() divides by zero (:590, :692-693). */
 int rtlpower_cfg_validate(const rtlpower_cfg *cfg);
 int rtlpower_gpu_create(const rtlpower_cfg *cfg, int nstreams, int device, rtlpower_gpu **out);
 int rtlpower_gpu_destroy(rtlpower_gpu *h);
@@ -182,6 +183,8 @@ int rtlpower_gpu_release_to(rtlpower_gpu *h, void *consumer_stream);
  * rounding boundary, in millionths of a hundredth of a dB, below which the report kernel does not decide. */
 int rtlpower_gpu_set_option(rtlpower_gpu *h, const char *name, long value);
 int rtlpower_gpu_get_option(rtlpower_gpu *h, const char *name, long *value);
+/* What "last_kernel" reads.  A scan with bin_e == 0 (rms_power) runs no transform and leaves "last_kernel" untouched:
+ * RTLPOWER_KERNEL_NONE on a handle that has scanned nothing else. */
 enum rtlpower_kernel {
 	RTLPOWER_KERNEL_NONE = 0,
 	RTLPOWER_KERNEL_GENERAL = 1,      /* k_power_scan: any shape one workgroup's LDS holds */
@@ -191,6 +194,19 @@ enum rtlpower_kernel {
 	RTLPOWER_KERNEL_STAGED = 5,       /* transforms through HBM, the general kernels */
 	RTLPOWER_KERNEL_STAGED_FAST = 6   /* ... rtl_power's own fine-bin shape */
 };
+/* The options that steer a scan, as set_option names them; their defaults are 0, 1, 1, 0, 0, 1. */
+typedef struct rtlpower_route_opts {
+	int32_t groups, dec_fast, staged_fast, staged_pipe, staged_batch, scan_frames;
+} rtlpower_route_opts;
+/*
+ * Which transform rtlpower_gpu_scan_device() takes for `nreads` reads of `nstreams` streams at this stream stride and
+ * input address (its low four bits are all that matter), without a handle and without a GPU: the plan the scan itself
+ * makes, so "last_kernel" after that scan reads the same.  opts == NULL: the defaults.  Returns one of
+ * RTLPOWER_KERNEL_* - RTLPOWER_KERNEL_NONE for bin_e == 0 -, the error of rtlpower_cfg_validate(), or -EINVAL for
+ * arguments the scan refuses.  "groups", "staged_batch" and "staged_pipe" shape the launches, never the route.
+ */
+int rtlpower_scan_route(const rtlpower_cfg *cfg, int nstreams, int nreads, size_t stream_stride, unsigned addr_low_bits,
+                        const rtlpower_route_opts *opts);
 /* HIP-event timing of the FFT kernel, as rtlfm_gpu_timing_*. */
 int rtlpower_gpu_timing_enable(rtlpower_gpu *h, int on);
 int rtlpower_gpu_timing_read(rtlpower_gpu *h, double *ms, int *launches);

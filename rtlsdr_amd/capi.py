@@ -407,6 +407,22 @@ class RtlpowerPlan(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RtlpowerRouteOpts(C.Structure):
+    """``rtlpower_route_opts`` — the options that steer a scan, with their defaults."""
+
+    _fields_ = [("groups", C.c_int32), ("dec_fast", C.c_int32), ("staged_fast", C.c_int32), ("staged_pipe", C.c_int32),
+                ("staged_batch", C.c_int32), ("scan_frames", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw) -> "RtlpowerRouteOpts":
+        o = cls(groups=0, dec_fast=1, staged_fast=1, staged_pipe=0, staged_batch=0, scan_frames=1)
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        return o
+
+
 # ... and include/rtlpower_hip.h
 _POWER_SIGNATURES = [
     ("rtlpower_frequency_range", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int, _P(RtlpowerPlan)]),
@@ -438,6 +454,7 @@ _POWER_SIGNATURES = [
     ("rtlpower_gpu_report", C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
     ("rtlpower_gpu_report_fetch", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int), _P(C.c_int32)]),
     ("rtlpower_gpu_report_fetch_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("rtlpower_scan_route", C.c_int, [_P(RtlpowerCfg), C.c_int, C.c_int, C.c_size_t, C.c_uint, _P(RtlpowerRouteOpts)]),
 ]
 CENTI_SIGN, CENTI_INF, CENTI_NAN = 0x80000000, 0x7FFFFFFF, 0x7FFFFFFE  # RTLPOWER_CENTI_* (include/rtlpower_hip.h)
 _SIGNATURES = _SIGNATURES + _POWER_SIGNATURES

@@ -30,13 +30,20 @@ using namespace rtlpower;
 		}                                                                                     \
 	} while (0)
 
-struct rtlpower_gpu {
+// What a configuration fixes about its scans (scan_geometry): a handle's from create on
+struct ScanGeom {
+	int N = 1, len_dec = 0, chunks = 0, dec_elems = 0;
+	bool decimates = false;
+	bool staged = false;  // bin_e 15 .. 21 or more points per read than a workgroup's LDS holds: transform in HBM
+};
+
+static const rtlpower_route_opts kRouteDefaults = {0, 1, 1, 0, 0, 1};
+
+struct rtlpower_gpu : ScanGeom {
 	rtlpower_cfg cfg;
 	int nstreams = 0, device = 0;
 	hipStream_t own_stream = nullptr, stream = nullptr;
 	Event ev_wait, ev_release;
-	int N = 1, len_dec = 0, chunks = 0, dec_elems = 0;
-	bool decimates = false;
 	DevBuf<int32_t> d_window;
 	DevBuf<uint16_t> d_window16;  // the low halves (k_power_scan_big multiplies in 16 bits)
 	DevBuf<uint32_t> d_tw;
@@ -45,26 +52,21 @@ struct rtlpower_gpu {
 	DevBuf<int16_t> d_decA, d_decB;
 	DevBuf<uint8_t> d_one;  // landing zone of rtlpower_gpu_scan()
 	bool timing = false;
-	int groups = 0;  // option "groups": workgroups per stream of the FFT kernel (0 = automatic)
-	bool staged = false;                   // bin_e 15 .. 21 or more points per read than a workgroup's LDS holds: transform in HBM
+	// the options a scan's plan reads (kOptions; what each does: include/rtlpower_hip.h, plan_scan)
+	rtlpower_route_opts opt = kRouteDefaults;
+	int last_kernel = 0;  // option "last_kernel" (read-only): which transform kernel the last scan took (RTLPOWER_KERNEL_*)
+	unsigned lds_raised = 0;  // raise_lds: the kernels whose dynamic-LDS limit is raised on this handle's device (kLds*)
 	DevBuf<uint32_t> d_work; DevBuf<int2> d_ave;
 	// one undecimated frame per read, bin_e > 14: the window comb by comb, the batch's bytes likewise, the averages' partial sums
-	DevBuf<uint16_t> d_window16T; DevBuf<uint8_t> d_tbuf; DevBuf<int2> d_part; bool attr_comb = false;
-	int scan_frames = 1;  // option "scan_frames": 0 = k_power_scan also where k_power_scan_frames applies (A/B, tests)
-	bool attr_frames = false;
+	DevBuf<uint16_t> d_window16T; DevBuf<uint8_t> d_tbuf; DevBuf<int2> d_part;
 	// decimated scans (a range below 1 MHz, src/rtl_power.c:466-480) in two launches: k_power_downsample_iq (-F) or
 	// k_power_boxcar into packed int16 pairs, k_power_scan_frames<13, true> on them
-	int dec_fast = 1;     // option "dec_fast": 0 = the general kernels (one launch per pass, k_power_scan) also where these apply
 	DevBuf<uint32_t> d_dec32;
-	bool attr_frames16 = false;
-	int last_kernel = 0;  // option "last_kernel" (read-only): which transform kernel the last scan took (RTLPOWER_KERNEL_*)
-	int staged_fast = 1;  // option "staged_fast": 0 = the general kernels also where the fast ones apply (A/B, tests)
-	// Fine bins (one frame per read beyond 16384 points), round 5: the batches of a scan as a two-stream pipeline.  The
-	// transform in LDS (k_power_scan_big<14, true>: issue-bound, 71 registers, one workgroup per CU) runs on the handle's
-	// stream; what only moves bytes - the comb gather of the NEXT batch, the passes over HBM and the accumulation of the
-	// one BEFORE - runs beside it on `aux` (their waves fit next to the transform's on every CU).  Two sets of work buffers.
-	int staged_pipe = 0;  // option "staged_pipe": 0 (default) = one batch after the other on one stream, 1 = the pipeline from 2^18 bins on, 2 = wherever it applies
-	int staged_batch = 0; // option "staged_batch": reads per batch, 0 = by the work buffer's size (tests: several batches of a small scan)
+	// Fine bins (one frame per read beyond 16384 points), round 5: the batches of a scan as a two-stream pipeline (option
+	// "staged_pipe").  The transform in LDS (k_power_scan_big<14, true>: issue-bound, 71 registers, one workgroup per CU)
+	// runs on the handle's stream; what only moves bytes - the comb gather of the NEXT batch, the passes over HBM and the
+	// accumulation of the one BEFORE - runs beside it on `aux` (their waves fit next to the transform's on every CU).  Two
+	// sets of work buffers.
 	struct Pipe {
 		hipStream_t aux = nullptr;
 		int aux_prio = 0;  // the HIP priority aux was taken from the stream pool with
@@ -72,11 +74,9 @@ struct rtlpower_gpu {
 	} pipe;
 	bool work_two = false;  // d_work / d_ave / d_tbuf / d_part hold two batches
 	size_t work_reads = 0;                 // reads the work buffer holds per stream
-	bool attr_lds = false;
 	bool want_stamps = false;              // rtlpower_gpu_clock_probe
 	DevBuf<unsigned long long> d_stamps;   // four per workgroup
 	int stamp_last = 0;                    // workgroups of the last stamped launch
-	bool attr_set = false, attr_big = false;  // the kernels' dynamic-LDS limits are raised on this handle's device
 	std::vector<std::pair<Event, Event>> ev_pending, ev_free;
 	// rtlpower_gpu_report (power_report_kernel.h): one device block - doubt counter, doubt list, samples, values - and its
 	// pinned mirror, both allocated by the first report; `arrived` is the kernel's per-stream counter
@@ -89,7 +89,7 @@ struct rtlpower_gpu {
 	bool rep_issued = false, rep_resolved = false;
 	int rep_status = 0;          // what resolving found (0, -EOVERFLOW, -EIO)
 	long rep_doubts = 0;         // option "report_doubts" (read-only)
-	long rep_guard_ppm = 1;      // option "report_guard_ppm": the guard in millionths of a hundredth of a dB (tests widen it)
+	int rep_guard_ppm = 1;       // option "report_guard_ppm": the guard in millionths of a hundredth of a dB (tests widen it)
 	DevBuf<uint8_t> d_in;  // landing zone of rtlpower_gpu_scan_host()
 	Event ev_in;
 };
@@ -344,6 +344,8 @@ static int validate(const rtlpower_cfg *c)
 	if (c->buf_len < 16 || c->buf_len % 4 || c->buf_len > (1u << 26)) return -EINVAL;
 	if (c->downsample < 1) return -EINVAL;
 	if (c->comp_fir_size != 0 && c->comp_fir_size != 9) return -EINVAL;
+	// remove_dc() divides by buf_len / ds and by one less (src/rtl_power.c:590, :692-693): the reference stops there
+	if (c->bin_e > 0 && c->buf_len / (uint32_t)c->downsample < 2) return -EINVAL;
 	if (!c->boxcar && c->downsample_passes) {
 		if (c->downsample_passes < 1 || c->downsample_passes > 10) return -EINVAL;
 		if (c->downsample != (1 << c->downsample_passes)) return -EINVAL;
@@ -371,6 +373,23 @@ static int validate(const rtlpower_cfg *c)
 extern "C" int rtlpower_cfg_validate(const rtlpower_cfg *cfg) { return cfg ? validate(cfg) : -EINVAL; }
 
 static int power_create_body(rtlpower_gpu *h);
+
+static ScanGeom scan_geometry(const rtlpower_cfg &c)
+{
+	ScanGeom g;
+	g.N = 1 << c.bin_e;
+	const int ds = c.downsample;
+	g.decimates = (c.boxcar && ds > 1) || (!c.boxcar && c.downsample_passes > 0);
+	g.len_dec = (int)c.buf_len / ds;  // what remove_dc() and the chunk loop are given (:692-696)
+	if (c.bin_e > 0) {
+		g.chunks = (g.len_dec + 2 * g.N - 1) / (2 * g.N);
+		// what one workgroup's LDS cannot hold goes through the work buffer in HBM (power_kernels.h, k_power_fft_*)
+		g.staged = c.bin_e > 14 || (long long)g.chunks * g.N > kMaxPoints;
+		if (c.boxcar && ds > 1) g.dec_elems = 2 * (((int)c.buf_len / 2 + ds - 1) / ds);
+		else if (g.decimates) g.dec_elems = (int)c.buf_len >> c.downsample_passes;
+	}
+	return g;
+}
 
 extern "C" int rtlpower_gpu_create(const rtlpower_cfg *cfg, int nstreams, int device, rtlpower_gpu **out)
 {
@@ -401,17 +420,7 @@ static int power_create_body(rtlpower_gpu *h)
 {
 	const rtlpower_cfg *cfg = &h->cfg;
 	const int nstreams = h->nstreams;
-	h->N = 1 << cfg->bin_e;
-	const int ds = cfg->downsample;
-	h->decimates = (cfg->boxcar && ds > 1) || (!cfg->boxcar && cfg->downsample_passes > 0);
-	h->len_dec = (int)cfg->buf_len / ds;  // what remove_dc() and the chunk loop are given (:692-696)
-	if (cfg->bin_e > 0) {
-		h->chunks = (h->len_dec + 2 * h->N - 1) / (2 * h->N);
-		// what one workgroup's LDS cannot hold goes through the work buffer in HBM (power_kernels.h, k_power_fft_*)
-		h->staged = cfg->bin_e > 14 || (long long)h->chunks * h->N > kMaxPoints;
-		if (cfg->boxcar && ds > 1) h->dec_elems = 2 * (((int)cfg->buf_len / 2 + ds - 1) / ds);
-		else if (h->decimates) h->dec_elems = (int)cfg->buf_len >> cfg->downsample_passes;
-	}
+	static_cast<ScanGeom &>(*h) = scan_geometry(*cfg);
 	HIP_TRY(rtl_pool::stream_get(h->device, 0, &h->own_stream));  // (from the process-wide pool: stream_pool.h)
 	h->stream = h->own_stream;
 	const size_t S = (size_t)nstreams;
@@ -519,62 +528,55 @@ extern "C" int rtlpower_gpu_release_to(rtlpower_gpu *h, void *consumer_stream)
 	return 0;
 }
 
+// The options by name: one table for set_option and get_option.  A flag stores value != 0; a read-only name is unknown
+// to set_option; "report_doubts" has no slot, its read waits for the report.
+#define OPT_SLOT(field) [](rtlpower_gpu *h) -> int * { return &h->field; }
+static const struct Option {
+	const char *name;
+	int *(*slot)(rtlpower_gpu *);
+	long min, max;
+	bool flag, read_only;
+} kOptions[] = {
+	{"groups", OPT_SLOT(opt.groups), 0, INT32_MAX, false, false},  // workgroups per stream of the FFT kernel (0 = automatic)
+	{"staged_fast", OPT_SLOT(opt.staged_fast), 0, 1, true, false},
+	{"dec_fast", OPT_SLOT(opt.dec_fast), 0, 1, true, false},
+	{"staged_pipe", OPT_SLOT(opt.staged_pipe), 0, 2, false, false},
+	{"staged_batch", OPT_SLOT(opt.staged_batch), 0, 1 << 20, false, false},  // reads per batch, 0 = by the work buffer's size
+	{"scan_frames", OPT_SLOT(opt.scan_frames), 0, 1, true, false},
+	{"report_guard_ppm", OPT_SLOT(rep_guard_ppm), 1, 500000, false, false},
+	{"last_kernel", OPT_SLOT(last_kernel), 0, 0, false, true},
+	{"report_doubts", nullptr, 0, 0, false, true},
+};
+#undef OPT_SLOT
+
+static const Option *find_option(const char *name)
+{
+	for (const Option &o : kOptions)
+		if (!strcmp(name, o.name)) return &o;
+	return nullptr;
+}
+
 extern "C" int rtlpower_gpu_set_option(rtlpower_gpu *h, const char *name, long value)
 {
 	if (!h || !name) return -EINVAL;
-	if (!strcmp(name, "groups")) {
-		if (value < 0) return -EINVAL;
-		h->groups = (int)value;
-		return 0;
-	}
-	if (!strcmp(name, "staged_fast")) {
-		h->staged_fast = value != 0;
-		return 0;
-	}
-	if (!strcmp(name, "dec_fast")) {
-		h->dec_fast = value != 0;
-		return 0;
-	}
-	if (!strcmp(name, "staged_pipe")) {
-		if (value < 0 || value > 2) return -EINVAL;
-		h->staged_pipe = (int)value;
-		return 0;
-	}
-	if (!strcmp(name, "staged_batch")) {
-		if (value < 0 || value > (1 << 20)) return -EINVAL;
-		h->staged_batch = (int)value;
-		return 0;
-	}
-	if (!strcmp(name, "scan_frames")) {
-		h->scan_frames = value != 0;
-		return 0;
-	}
-	if (!strcmp(name, "report_guard_ppm")) {
-		if (value < 1 || value > 500000) return -EINVAL;
-		h->rep_guard_ppm = value;
-		return 0;
-	}
-	return -ENOENT;
+	const Option *o = find_option(name);
+	if (!o || o->read_only) return -ENOENT;
+	if (o->flag) value = value != 0;
+	if (value < o->min || value > o->max) return -EINVAL;
+	*o->slot(h) = (int)value;
+	return 0;
 }
 
 extern "C" int rtlpower_gpu_get_option(rtlpower_gpu *h, const char *name, long *value)
 {
 	if (!h || !name || !value) return -EINVAL;
-	if (!strcmp(name, "groups")) { *value = h->groups; return 0; }
-	if (!strcmp(name, "staged_fast")) { *value = h->staged_fast; return 0; }
-	if (!strcmp(name, "dec_fast")) { *value = h->dec_fast; return 0; }
-	if (!strcmp(name, "staged_pipe")) { *value = h->staged_pipe; return 0; }
-	if (!strcmp(name, "staged_batch")) { *value = h->staged_batch; return 0; }
-	if (!strcmp(name, "scan_frames")) { *value = h->scan_frames; return 0; }
-	if (!strcmp(name, "last_kernel")) { *value = h->last_kernel; return 0; }
-	if (!strcmp(name, "report_guard_ppm")) { *value = h->rep_guard_ppm; return 0; }
-	if (!strcmp(name, "report_doubts")) {
-		if (!h->rep_issued) { *value = 0; return 0; }
-		const int r = report_wait(h);
-		*value = h->rep_doubts;
-		return r == -EOVERFLOW ? 0 : r;  // (an overflowing report still says how many bins it was handed)
-	}
-	return -ENOENT;
+	const Option *o = find_option(name);
+	if (!o) return -ENOENT;
+	if (o->slot) { *value = *o->slot(h); return 0; }
+	if (!h->rep_issued) { *value = 0; return 0; }
+	const int r = report_wait(h);
+	*value = h->rep_doubts;
+	return r == -EOVERFLOW ? 0 : r;  // (an overflowing report still says how many bins it was handed)
 }
 
 // The shader clock the FFT kernel's workgroups actually ran at (k_power_scan_big stamps s_memtime and the
@@ -643,334 +645,460 @@ static inline int grid_for(size_t work, int block = 256, int cap = 256 * 16)
 	return (int)g;
 }
 
+// ---- a scan: its plan, made once (host only), and one launcher per route -----------
+
+struct ScanPlan {
+	int route = RTLPOWER_KERNEL_NONE;  // which launcher, as "last_kernel" names it; NONE: rms_power (bin_e == 0)
+	// DECIMATED: points of a decimated read (2^dec_e of them) and what decimates
+	int Pr = 0, dec_e = 0;
+	bool by_fifth = false, by_boxcar = false;
+	// STAGED / STAGED_FAST: reads per batch; fast_shape: the work buffers include the fast kernels'; two: two sets of
+	// them; piped: the batches as the two-stream pipeline
+	bool fast_shape = false, fast = false, two = false, piped = false;
+	size_t batch = 0;
+	// GENERAL / BIG / FRAMES, and DECIMATED's transform: points a workgroup holds, workgroups per stream, the grid
+	bool big = false, frames = false;
+	int M = 0, groups = 0;
+	unsigned grid = 0;
+};
+
+// Workgroups per stream of an in-LDS transform: enough for the 256 CUs (a large-FFT workgroup fills a CU's LDS, the small
+// ones share) - a stream's reads are split when there are few streams (power_kernels.h) - or what option "groups" says,
+// and never more than `most`, the units of work a stream has
+static int groups_per_stream(int S, int option, int most)
+{
+	int groups = option > 0 ? option : (512 + S - 1) / S;
+	if (groups > most) groups = most;
+	return groups < 1 ? 1 : groups;
+}
+
+// Reads per batch of a staged scan: at most ~1 GiB of work buffer.  The pipeline holds two batches: half the points each,
+// and at least four batches where each still fills the GPU (measured, profiles/r05_power_big_pipe.txt: 2^19 .. 2^21 bins -
+// two passes over HBM per batch - 4-5 % faster in two sessions and 6 % slower in a third; 2^15 .. 2^17 1-3 % SLOWER: the
+// kernels do run at the same time, but beside the transform the accumulating pass takes three times as long as alone and
+// becomes the longer chain; a scan of one batch only pays for the events.  Not the default.)
+static size_t staged_batch_reads(const rtlpower_cfg &c, const ScanGeom &g, const rtlpower_route_opts &o, int S, int nreads, bool two)
+{
+	size_t batch = ((size_t)1 << (two ? 27 : 28)) / ((size_t)S * g.chunks * g.N);
+	if (batch < 1) batch = 1;
+	if (batch > (size_t)nreads) batch = (size_t)nreads;
+	if (two && ((size_t)nreads + batch - 1) / batch < 4) {
+		const size_t want = nreads < 4 ? (size_t)nreads : 4, b2 = ((size_t)nreads + want - 1) / want;
+		if (((size_t)S * b2) << (c.bin_e - 14) >= 2048) batch = b2;  // (eight combs per CU and batch: 512 made a one-stream scan of 2^21 bins 1.6 x slower)
+	}
+	if (o.staged_batch > 0 && (size_t)o.staged_batch < batch) batch = (size_t)o.staged_batch;
+	return batch;
+}
+
+// Which way `nreads` reads of S streams go, from the configuration, its geometry, the options and where the rows lie -
+// nothing else: not what a handle has allocated, not what it ran before.
+static ScanPlan plan_scan(const rtlpower_cfg &c, const ScanGeom &g, const rtlpower_route_opts &o, int S, int nreads,
+                          size_t stride, unsigned addr_low)
+{
+	ScanPlan p;
+	if (c.bin_e == 0) return p;
+	// the conditions the fast kernels share
+	const bool rows16 = !(stride & 15) && !(addr_low & 15) && !(c.buf_len & 15);  // rows take 16-byte loads
+	const bool one_frame = !g.decimates && g.chunks == 1 && g.len_dec == 2 * g.N;  // a read is exactly one undecimated frame
+	const bool whole = c.buf_len == (uint32_t)g.len_dec;  // ... and every byte of it (downsample > 1 without -F or boxcar divides len_dec only)
+	const int Pr = g.len_dec / 2;
+	const bool pow2_frames = Pr >= 512 && Pr <= 8192 && (Pr & (Pr - 1)) == 0 && g.len_dec == 2 * Pr;  // a decimated read is whole power-of-two frames
+	// a decimated scan whose reads are whole frames of at least 512 points: two launches (power_kernels.h)
+	const bool by_fifth = !c.boxcar && c.downsample_passes >= 1 && c.downsample_passes <= kDecMaxPasses &&
+	                      (int)((c.buf_len / 2) >> c.downsample_passes) == Pr;
+	const bool by_boxcar = c.boxcar && c.downsample > 1 && (long long)(c.buf_len / 2) == (long long)Pr * c.downsample;
+	if (o.dec_fast && g.decimates && !g.staged && pow2_frames && rows16 && c.bin_e >= 3 && g.N <= Pr && (by_fifth || by_boxcar)) {
+		p.route = RTLPOWER_KERNEL_DECIMATED;
+		p.Pr = Pr; p.by_fifth = by_fifth; p.by_boxcar = by_boxcar;
+		for (p.dec_e = 9; (1 << p.dec_e) < Pr; p.dec_e++) {}
+		p.M = 8192;  // k_power_scan_frames<13, true> transforms groups of M / Pr reads
+		p.groups = groups_per_stream(S, o.groups, (nreads + (p.M / Pr) - 1) / (p.M / Pr));
+	} else if (g.staged) {
+		// bin_e 15 .. 21 (or frames beyond one workgroup's LDS): the same stages over a work buffer in HBM, a batch of reads
+		// at a time.  rtl_power's own fine-bin shape - an undecimated read is exactly one frame - takes the kernels written for it
+		p.fast_shape = c.bin_e > 14 && !g.decimates && g.chunks == 1;
+		p.fast = o.staged_fast && p.fast_shape && one_frame && whole && rows16;
+		p.two = p.fast_shape && o.staged_fast && (o.staged_pipe == 2 || (o.staged_pipe == 1 && c.bin_e >= 18));
+		p.batch = staged_batch_reads(c, g, o, S, nreads, p.two);
+		p.piped = p.fast && p.two && (o.staged_pipe == 2 || (size_t)nreads > p.batch);
+		p.route = p.fast ? RTLPOWER_KERNEL_STAGED_FAST : RTLPOWER_KERNEL_STAGED;
+	} else {
+		// in one workgroup's LDS.  k_power_scan_big: one frame of 8192 / 16384 points per read; k_power_scan_frames: several
+		// frames per read (rtl_power's everyday shape: every scan below 8192 bins reads 16384 bytes), reads of exactly 8192
+		// or 16384 points; k_power_scan: anything
+		p.M = g.chunks * g.N;
+		p.big = one_frame && (c.bin_e == 13 || c.bin_e == 14) && rows16;
+		p.frames = o.scan_frames && !g.decimates && g.chunks > 1 && c.bin_e >= 3 && (p.M == 8192 || p.M == 16384) &&
+		           g.len_dec == 2 * p.M && whole && rows16;
+		p.route = p.big ? RTLPOWER_KERNEL_BIG : p.frames ? RTLPOWER_KERNEL_FRAMES : RTLPOWER_KERNEL_GENERAL;
+		p.groups = groups_per_stream(S, o.groups, nreads);
+	}
+	p.grid = (unsigned)S * (unsigned)p.groups;
+	return p;
+}
+
+extern "C" int rtlpower_scan_route(const rtlpower_cfg *cfg, int nstreams, int nreads, size_t stream_stride, unsigned addr_low_bits,
+                                   const rtlpower_route_opts *opts)
+{
+	if (!cfg || nstreams < 1 || nreads < 1) return -EINVAL;
+	const int v = validate(cfg);
+	if (v < 0) return v;
+	if (stream_stride < (size_t)nreads * cfg->buf_len) return -EINVAL;
+	return plan_scan(*cfg, scan_geometry(*cfg), opts ? *opts : kRouteDefaults, nstreams, nreads, stream_stride, addr_low_bits).route;
+}
+
+static int timing_begin(rtlpower_gpu *h, std::pair<Event, Event> &ev)
+{
+	if (!h->timing) return 0;
+	if (!h->ev_free.empty()) {
+		ev = std::move(h->ev_free.back());
+		h->ev_free.pop_back();
+	} else {
+		OWN_TRY(ev.first.create());
+		OWN_TRY(ev.second.create());
+	}
+	HIP_TRY(hipEventRecord(ev.first, h->stream));
+	return 0;
+}
+static int timing_end(rtlpower_gpu *h, std::pair<Event, Event> &ev)
+{
+	if (!h->timing) return 0;
+	HIP_TRY(hipEventRecord(ev.second, h->stream));
+	h->ev_pending.push_back(std::move(ev));
+	return 0;
+}
+
+// A kernel's dynamic-LDS limit, raised in front of its first launch: once per handle, not per process - the attribute
+// belongs to the device the handle lives on, and one process may hold handles on several
+enum : unsigned { kLdsScan = 1, kLdsBig13 = 2, kLdsBig14 = 4, kLdsFrames13 = 8, kLdsFrames14 = 16, kLdsFrames16 = 32, kLdsFft = 64, kLdsComb = 128 };
+template <class K> static int raise_lds(rtlpower_gpu *h, unsigned bit, K kernel)
+{
+	if (h->lds_raised & bit) return 0;
+	HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
+	h->lds_raised |= bit;
+	return 0;
+}
+
+struct ScanInput {  // stream s, read r at d_iq + s * stride + r * buf_len
+	const uint8_t *d_iq;
+	size_t stride;
+	int nreads;
+};
+struct Decimated {  // decimate_general's output: stream s, read r at dec + s * dss + r * drs (int16 elements)
+	const int16_t *dec = nullptr;
+	size_t dss = 0, drs = 0;
+};
+
+static int scan_rms(rtlpower_gpu *h, const ScanInput &in)
+{
+	k_power_rms<<<h->nstreams, 256, 0, h->stream>>>(in.d_iq, in.stride, in.nreads, (int)h->cfg.buf_len, h->cfg.peak_hold, h->d_avg, h->d_samples);
+	HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// k_power_downsample_iq (-F) or k_power_boxcar into packed int16 pairs, k_power_scan_frames<13, true> on them
+static int scan_decimated(rtlpower_gpu *h, const ScanPlan &pl, const ScanInput &in)
+{
+	const rtlpower_cfg &c = h->cfg;
+	const int S = h->nstreams, Pr = pl.Pr, nreads = in.nreads;
+	hipStream_t q = h->stream;
+	if (pl.by_fifth) {
+		DecimateParams dp{};
+		dp.iq8 = in.d_iq; dp.stride8 = in.stride; dp.nreads = nreads; dp.buf_len = (int)c.buf_len;
+		dp.passes = c.downsample_passes; dp.fir = c.comp_fir_size;
+		dp.out = h->d_dec32; dp.out_stream_stride = (size_t)nreads * Pr; dp.out_per_read = Pr;
+		dp.tile_out = kDecTileIn >> c.downsample_passes;
+		dp.tiles_per_read = (Pr + dp.tile_out - 1) / dp.tile_out;
+		dp.total_tiles = (size_t)S * nreads * dp.tiles_per_read;
+		const unsigned g = (unsigned)(dp.total_tiles < 256 * 20 ? dp.total_tiles : 256 * 20);
+		switch (c.downsample_passes) {
+		case 1: k_power_downsample_iq<1><<<g, 256, 0, q>>>(dp); break;
+		case 2: k_power_downsample_iq<2><<<g, 256, 0, q>>>(dp); break;
+		case 3: k_power_downsample_iq<3><<<g, 256, 0, q>>>(dp); break;
+		case 4: k_power_downsample_iq<4><<<g, 256, 0, q>>>(dp); break;
+		case 5: k_power_downsample_iq<5><<<g, 256, 0, q>>>(dp); break;
+		default: k_power_downsample_iq<6><<<g, 256, 0, q>>>(dp); break;
+		}
+	} else {
+		k_power_boxcar<<<grid_for((size_t)S * nreads * Pr), 256, 0, q>>>(
+		    in.d_iq, in.stride, nreads, (int)c.buf_len, c.downsample, S, reinterpret_cast<int16_t *>(h->d_dec32.get()),
+		    (size_t)nreads * 2 * Pr, (size_t)2 * Pr, Pr);
+	}
+	ScanParams p{};
+	p.dec32 = h->d_dec32; p.dec32_stream_stride = (size_t)nreads * Pr; p.dec_e = pl.dec_e;
+	p.nreads = nreads; p.bin_e = c.bin_e; p.ds = c.downsample; p.peak_hold = c.peak_hold;
+	p.window16 = h->d_window16; p.tw = h->d_tw; p.avg = h->d_avg; p.samples = h->d_samples;
+	p.groups = pl.groups;
+	OWN_TRY(raise_lds(h, kLdsFrames16, k_power_scan_frames<13, true>));
+	const size_t lds16 = ((size_t)skewed_size(pl.M) + (size_t)h->N) * 4;
+	hipLaunchKernelGGL((k_power_scan_frames<13, true>), dim3(pl.grid), dim3(kThreads), lds16, q, p);
+	return 0;
+}
+
+// The general decimation: the boxcar, or one launch per fifth_order pass and generic_fir, into int16 pairs
+static int decimate_general(rtlpower_gpu *h, const ScanInput &in, Decimated *out)
+{
+	const rtlpower_cfg &c = h->cfg;
+	const int S = h->nstreams, nreads = in.nreads;
+	hipStream_t q = h->stream;
+	const size_t drs = (size_t)c.buf_len, dss = drs * nreads;  // elements reserved per read, per stream
+	OWN_TRY(h->d_decA.grow((size_t)S * dss, q));
+	OWN_TRY(h->d_decB.grow((size_t)S * dss, q));
+	int16_t *cur = h->d_decA, *oth = h->d_decB;
+	if (c.boxcar) {
+		const int out_cplx = h->dec_elems / 2;
+		k_power_boxcar<<<grid_for((size_t)S * nreads * out_cplx), 256, 0, q>>>(
+		    in.d_iq, in.stride, nreads, (int)c.buf_len, c.downsample, S, cur, dss, drs, out_cplx);
+	} else {
+		for (int j = 0; j < c.downsample_passes; j++) {
+			const int length = (int)c.buf_len >> j;
+			k_power_fifth<<<grid_for((size_t)S * nreads * (length / 4)), 256, 0, q>>>(
+			    j == 0 ? in.d_iq : nullptr, in.stride, j == 0 ? nullptr : cur, dss, drs, nreads, (int)c.buf_len,
+			    length, S, j == 0 ? cur : oth, dss, drs);
+			if (j > 0) std::swap(cur, oth);
+		}
+		if (c.comp_fir_size == 9) {
+			const int cplx = ((int)c.buf_len >> c.downsample_passes) / 2;
+			k_power_fir9<<<grid_for((size_t)S * nreads * cplx), 256, 0, q>>>(cur, oth, dss, drs, nreads, cplx, S,
+			                                                               c.downsample_passes);
+			std::swap(cur, oth);
+		}
+	}
+	*out = Decimated{cur, dss, drs};
+	return 0;
+}
+
+// ---- the staged route: a batch of reads at a time through work buffers in HBM ----
+
+// Elements per set of the work buffers (piped: batch k uses set k & 1); the handle's allocation holds work_reads reads per set
+struct StagedSets {
+	size_t work, ave, tbuf, part;
+};
+static StagedSets staged_sets(const rtlpower_gpu *h, size_t reads)
+{
+	const size_t M = (size_t)h->chunks * h->N, n = (size_t)h->nstreams * reads;
+	return {n * M, n, n * M * 2, n * (M / 8192)};
+}
+
+// Work buffers for pl.batch reads per set: kept from scan to scan, allocated anew where a scan needs more
+static int staged_reserve(rtlpower_gpu *h, const ScanPlan &pl)
+{
+	if (h->work_reads >= pl.batch && (h->work_two || !pl.two)) return 0;
+	HIP_TRY(hipStreamSynchronize(h->stream));
+	if (h->pipe.aux) HIP_TRY(hipStreamSynchronize(h->pipe.aux));
+	h->d_work.reset(); h->d_ave.reset(); h->d_tbuf.reset(); h->d_part.reset();
+	h->work_reads = 0; h->work_two = false;
+	const StagedSets n = staged_sets(h, (pl.two ? 2 : 1) * pl.batch);
+	OWN_TRY(h->d_work.alloc(n.work));
+	OWN_TRY(h->d_ave.alloc(n.ave));
+	if (pl.fast_shape) {
+		OWN_TRY(h->d_tbuf.alloc(n.tbuf));
+		OWN_TRY(h->d_part.alloc(n.part));
+	}
+	h->work_reads = pl.batch; h->work_two = pl.two;
+	return 0;
+}
+
+static int pipe_create(rtlpower_gpu *h)
+{
+	if (h->pipe.aux) return 0;
+	int lo = 0, hi = 0;
+	HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+	HIP_TRY(rtl_pool::stream_get(h->device, lo, &h->pipe.aux));  // (a priority of its own: a hardware queue of its own)
+	h->pipe.aux_prio = lo;
+	for (Event *e : {&h->pipe.start, &h->pipe.prep[0], &h->pipe.prep[1], &h->pipe.scanned[0], &h->pipe.scanned[1], &h->pipe.done})
+		OWN_TRY(e->create(hipEventDisableTiming));
+	return 0;
+}
+
+// One batch: reads r0 .. r0 + nb - 1 of every stream, into and out of set `set` of the work buffers
+struct StagedBatch {
+	int r0, nb, set;
+	size_t frames;
+	StagedSets at;  // where the set begins in each buffer
+	StagedParams sp;
+};
+static StagedBatch staged_batch(rtlpower_gpu *h, const ScanPlan &pl, const ScanInput &in, const Decimated &d, int r0, int set)
+{
+	const rtlpower_cfg &c = h->cfg;
+	StagedBatch b{};
+	b.r0 = r0; b.nb = in.nreads - r0 < (int)pl.batch ? in.nreads - r0 : (int)pl.batch; b.set = set;
+	b.frames = (size_t)h->nstreams * b.nb * h->chunks;
+	const StagedSets n = staged_sets(h, h->work_reads);
+	b.at = {set * n.work, set * n.ave, set * n.tbuf, set * n.part};
+	StagedParams &sp = b.sp;
+	sp.iq8 = d.dec ? nullptr : in.d_iq + (size_t)r0 * c.buf_len; sp.stride8 = in.stride;
+	sp.dec = d.dec ? d.dec + (size_t)r0 * d.drs : nullptr; sp.dec_stream_stride = d.dss; sp.dec_read_stride = d.drs; sp.dec_elems = h->dec_elems;
+	sp.nreads = b.nb; sp.buf_len = (int)c.buf_len; sp.len_dec = h->len_dec; sp.bin_e = c.bin_e; sp.chunks = h->chunks;
+	sp.ds = c.downsample; sp.peak_hold = c.peak_hold; sp.window = h->d_window; sp.tw = h->d_tw;
+	sp.ave = h->d_ave + b.at.ave; sp.work = h->d_work + b.at.work; sp.avg = h->d_avg; sp.samples = h->d_samples; sp.nstreams = h->nstreams;
+	return b;
+}
+
+// the fast front: the comb gather and remove_dc's averages of a batch, on qa ...
+static void staged_comb(rtlpower_gpu *h, const StagedBatch &b, hipStream_t qa)
+{
+	const rtlpower_cfg &c = h->cfg;
+	const size_t frames = (size_t)h->nstreams * b.nb, tiles = frames << (c.bin_e - 13);
+	k_power_comb_bytes<<<grid_for(tiles, 1, 256 * 32), 256, 0, qa>>>(b.sp.iq8, b.sp.stride8, b.nb, (int)c.buf_len, c.bin_e, tiles,
+	                                                                   h->d_tbuf + b.at.tbuf, h->d_part + b.at.part);
+	k_power_dc_fin<<<grid_for(frames, 64), 64, 0, qa>>>(h->d_part + b.at.part, 1 << (c.bin_e - 13), h->len_dec, frames, b.sp.ave);
+}
+
+// ... and stages 0 .. 13 of every comb in LDS, on the handle's stream
+static void staged_transform(rtlpower_gpu *h, const StagedBatch &b)
+{
+	ScanParams cp{};
+	cp.iq8 = h->d_tbuf + b.at.tbuf; cp.window16 = h->d_window16T; cp.tw = h->d_tw; cp.ave = b.sp.ave; cp.work = b.sp.work;
+	cp.comb_c = h->cfg.bin_e - 14; cp.comb_blocks = b.frames << cp.comb_c;
+	const size_t lds_big = ((size_t)skewed_size(16384) + 16384) * 4;
+	const unsigned wgs = (unsigned)(cp.comb_blocks < 256 ? cp.comb_blocks : 256);
+	hipLaunchKernelGGL((k_power_scan_big<14, true>), dim3(wgs), dim3(kThreads), lds_big, h->stream, cp);
+}
+
+// the general front: remove_dc, the points to their places in the work buffer, the stages one workgroup's LDS holds
+static void staged_front_general(rtlpower_gpu *h, const StagedBatch &b)
+{
+	const rtlpower_cfg &c = h->cfg;
+	hipStream_t q = h->stream;
+	const size_t reads = (size_t)h->nstreams * b.nb;
+	k_power_dc<<<(unsigned)reads, 256, 0, q>>>(b.sp);
+	if (c.bin_e >= 12) k_power_place_tiled<<<grid_for(b.frames << (c.bin_e - 12), 1, 256 * 64), 256, 0, q>>>(b.sp);
+	else k_power_place<<<grid_for(reads * h->chunks * h->N, 256, 256 * 64), 256, 0, q>>>(b.sp);
+	const int eb = c.bin_e < 14 ? c.bin_e : 14;
+	const size_t lds = ((size_t)skewed_size(1 << eb) + ((size_t)1 << eb)) * 4, nblk = b.frames << (c.bin_e - eb);
+	hipLaunchKernelGGL(k_power_fft_lds, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(kThreads), lds, q, h->d_work, h->d_tw, eb, nblk);
+}
+
+// stages 14 .. bin_e - 1 over HBM on qa, three per pass; the last pass accumulates (k_power_fft_gl_acc)
+static void staged_back(rtlpower_gpu *h, const StagedBatch &b, hipStream_t qa)
+{
+	const rtlpower_cfg &c = h->cfg;
+	for (int st = 14; st < c.bin_e;) {
+		const int R = c.bin_e - st >= 3 ? 3 : c.bin_e - st;
+		if (st + R == c.bin_e) {
+			const int g = grid_for((size_t)h->nstreams << (c.bin_e - R), 256, 256 * 64);
+			if (R == 3) k_power_fft_gl_acc<3><<<g, 256, 0, qa>>>(b.sp, st);
+			else if (R == 2) k_power_fft_gl_acc<2><<<g, 256, 0, qa>>>(b.sp, st);
+			else k_power_fft_gl_acc<1><<<g, 256, 0, qa>>>(b.sp, st);
+		} else {
+			const int g = grid_for(b.frames << (c.bin_e - R), 256, 256 * 64);
+			k_power_fft_gl<3><<<g, 256, 0, qa>>>(b.sp.work, h->d_tw, c.bin_e, st, b.frames);
+		}
+		st += R;
+	}
+	if (c.bin_e <= 14) k_power_accum<<<grid_for((size_t)h->nstreams * h->N, 256, 256 * 64), 256, 0, h->stream>>>(b.sp);
+}
+
+static int scan_staged(rtlpower_gpu *h, const ScanPlan &pl, const ScanInput &in, const Decimated &d)
+{
+	hipStream_t q = h->stream;
+	if (pl.fast) OWN_TRY(raise_lds(h, kLdsComb, k_power_scan_big<14, true>));
+	OWN_TRY(raise_lds(h, kLdsFft, k_power_fft_lds));
+	if (pl.piped) OWN_TRY(pipe_create(h));
+	rtlpower_gpu::Pipe &pipe = h->pipe;
+	hipStream_t qa = pl.piped ? pipe.aux : q;  // where the kernels that only move bytes go
+	if (pl.piped) {
+		// aux starts behind what the caller has queued on q (the producer of d_iq, an earlier scan's accumulation)
+		HIP_TRY(hipEventRecord(pipe.start, q));
+		HIP_TRY(hipStreamWaitEvent(qa, pipe.start, 0));
+		staged_comb(h, staged_batch(h, pl, in, d, 0, 0), qa);
+		HIP_TRY(hipEventRecord(pipe.prep[0], qa));
+	}
+	for (int r0 = 0, kb = 0; r0 < in.nreads; r0 += (int)pl.batch, kb++) {
+		const int set = pl.piped ? (kb & 1) : 0, r1 = r0 + (int)pl.batch;
+		const StagedBatch b = staged_batch(h, pl, in, d, r0, set);
+		if (!pl.fast) {
+			staged_front_general(h, b);
+		} else if (!pl.piped) {
+			staged_comb(h, b, q);
+			staged_transform(h, b);
+		} else {
+			// this batch's combs and averages are there (and, aux being in order, the batch before the last has left this set)
+			HIP_TRY(hipStreamWaitEvent(q, pipe.prep[set], 0));
+			staged_transform(h, b);
+			HIP_TRY(hipEventRecord(pipe.scanned[set], q));
+			// beside this batch's transform: the next batch's combs into the other set (its last user, batch kb - 1's
+			// passes over HBM, is already queued on aux in front of them) ...
+			if (r1 < in.nreads) {
+				staged_comb(h, staged_batch(h, pl, in, d, r1, set ^ 1), qa);
+				HIP_TRY(hipEventRecord(pipe.prep[set ^ 1], qa));
+			}
+			// ... then, once the transform is through, this batch's stages beyond 13 and its accumulation
+			HIP_TRY(hipStreamWaitEvent(qa, pipe.scanned[set], 0));
+		}
+		staged_back(h, b, qa);
+	}
+	if (pl.piped) {  // the scan is complete on q when aux is through
+		HIP_TRY(hipEventRecord(pipe.done, qa));
+		HIP_TRY(hipStreamWaitEvent(q, pipe.done, 0));
+	}
+	return 0;
+}
+
+// ---- the routes in one workgroup's LDS: k_power_scan_big, k_power_scan_frames, k_power_scan ----
+
+static int scan_in_lds(rtlpower_gpu *h, const ScanPlan &pl, const ScanInput &in, const Decimated &d)
+{
+	const rtlpower_cfg &c = h->cfg;
+	hipStream_t q = h->stream;
+	ScanParams p{};
+	p.iq8 = d.dec ? nullptr : in.d_iq; p.stride8 = in.stride;
+	p.dec = d.dec; p.dec_stream_stride = d.dss; p.dec_read_stride = d.drs; p.dec_elems = h->dec_elems;
+	p.nreads = in.nreads; p.buf_len = (int)c.buf_len; p.len_dec = h->len_dec;
+	p.bin_e = c.bin_e; p.chunks = h->chunks; p.ds = c.downsample; p.peak_hold = c.peak_hold;
+	p.window = h->d_window; p.window16 = h->d_window16; p.tw = h->d_tw; p.avg = h->d_avg; p.samples = h->d_samples;
+	p.groups = pl.groups;
+	OWN_TRY(raise_lds(h, kLdsScan, k_power_scan));
+	if (pl.big) {
+		OWN_TRY(raise_lds(h, kLdsBig13, k_power_scan_big<13>));
+		OWN_TRY(raise_lds(h, kLdsBig14, k_power_scan_big<14>));
+	}
+	if (pl.big && h->want_stamps) {
+		OWN_TRY(h->d_stamps.grow((size_t)pl.grid * 4, q));
+		HIP_TRY(hipMemsetAsync(h->d_stamps, 0, (size_t)pl.grid * 32, q));
+		p.stamps = h->d_stamps;
+		h->stamp_last = (int)pl.grid;
+	}
+	if (pl.frames) {
+		OWN_TRY(raise_lds(h, kLdsFrames13, k_power_scan_frames<13>));
+		OWN_TRY(raise_lds(h, kLdsFrames14, k_power_scan_frames<14>));
+	}
+	const size_t lds = ((size_t)skewed_size(pl.M) + (size_t)h->N) * 4;
+	const dim3 grid(pl.grid), block(kThreads);
+	if (pl.big && c.bin_e == 14) hipLaunchKernelGGL(k_power_scan_big<14>, grid, block, lds, q, p);
+	else if (pl.big) hipLaunchKernelGGL(k_power_scan_big<13>, grid, block, lds, q, p);
+	else if (pl.frames && pl.M == 8192) hipLaunchKernelGGL(k_power_scan_frames<13>, grid, block, lds, q, p);
+	else if (pl.frames) hipLaunchKernelGGL(k_power_scan_frames<14>, grid, block, lds, q, p);
+	else hipLaunchKernelGGL(k_power_scan, grid, block, lds, q, p);
+	return 0;
+}
+
 extern "C" int rtlpower_gpu_scan_device(rtlpower_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nreads)
 {
 	if (!h || !d_iq || nreads < 1) return -EINVAL;
 	if (stream_stride < (size_t)nreads * h->cfg.buf_len) return -EINVAL;
 	HIP_TRY(hipSetDevice(h->device));
-	const rtlpower_cfg &c = h->cfg;
-	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	rtl_debug::poison_lds(q);  // RTLFM_POISON=1 only
-	if (c.bin_e == 0) {
-		k_power_rms<<<S, 256, 0, q>>>(d_iq, stream_stride, nreads, (int)c.buf_len, c.peak_hold, h->d_avg, h->d_samples);
-		HIP_TRY(hipGetLastError());
-		return 0;
-	}
-	// ---- a decimated scan whose reads are whole frames of at least 512 points: two launches (power_kernels.h) ----
-	{
-		const int Pr = h->len_dec / 2;  // points of a decimated read
-		const bool pow2 = Pr >= 512 && Pr <= 8192 && (Pr & (Pr - 1)) == 0 && h->len_dec == 2 * Pr;
-		const bool aligned = !(stream_stride & 15) && !((uintptr_t)d_iq & 15) && !(c.buf_len & 15);
-		const bool by_fifth = !c.boxcar && c.downsample_passes >= 1 && c.downsample_passes <= kDecMaxPasses &&
-		                      (int)((c.buf_len / 2) >> c.downsample_passes) == Pr;
-		const bool by_boxcar = c.boxcar && c.downsample > 1 && (int)(c.buf_len / 2) == Pr * c.downsample;
-		if (h->dec_fast && h->decimates && !h->staged && pow2 && aligned && c.bin_e >= 3 && h->N <= Pr && (by_fifth || by_boxcar)) {
-			const size_t need = (size_t)S * nreads * Pr;
-			OWN_TRY(h->d_dec32.grow(need, q));
-			std::pair<Event, Event> ev;
-			if (h->timing) {
-				if (!h->ev_free.empty()) { ev = std::move(h->ev_free.back()); h->ev_free.pop_back(); }
-				else { OWN_TRY(ev.first.create()); OWN_TRY(ev.second.create()); }
-				HIP_TRY(hipEventRecord(ev.first, q));
-			}
-			if (by_fifth) {
-				DecimateParams dp{};
-				dp.iq8 = d_iq; dp.stride8 = stream_stride; dp.nreads = nreads; dp.buf_len = (int)c.buf_len;
-				dp.passes = c.downsample_passes; dp.fir = c.comp_fir_size;
-				dp.out = h->d_dec32; dp.out_stream_stride = (size_t)nreads * Pr; dp.out_per_read = Pr;
-				dp.tile_out = kDecTileIn >> c.downsample_passes;
-				dp.tiles_per_read = (Pr + dp.tile_out - 1) / dp.tile_out;
-				dp.total_tiles = (size_t)S * nreads * dp.tiles_per_read;
-				const unsigned g = (unsigned)(dp.total_tiles < 256 * 20 ? dp.total_tiles : 256 * 20);
-				switch (c.downsample_passes) {
-				case 1: k_power_downsample_iq<1><<<g, 256, 0, q>>>(dp); break;
-				case 2: k_power_downsample_iq<2><<<g, 256, 0, q>>>(dp); break;
-				case 3: k_power_downsample_iq<3><<<g, 256, 0, q>>>(dp); break;
-				case 4: k_power_downsample_iq<4><<<g, 256, 0, q>>>(dp); break;
-				case 5: k_power_downsample_iq<5><<<g, 256, 0, q>>>(dp); break;
-				default: k_power_downsample_iq<6><<<g, 256, 0, q>>>(dp); break;
-				}
-			} else {
-				k_power_boxcar<<<grid_for((size_t)S * nreads * Pr), 256, 0, q>>>(
-				    d_iq, stream_stride, nreads, (int)c.buf_len, c.downsample, S, reinterpret_cast<int16_t *>(h->d_dec32.get()),
-				    (size_t)nreads * 2 * Pr, (size_t)2 * Pr, Pr);
-			}
-			ScanParams p{};
-			p.dec32 = h->d_dec32; p.dec32_stream_stride = (size_t)nreads * Pr;
-			for (p.dec_e = 9; (1 << p.dec_e) < Pr; p.dec_e++) {}
-			p.nreads = nreads; p.bin_e = c.bin_e; p.ds = c.downsample; p.peak_hold = c.peak_hold;
-			p.window16 = h->d_window16; p.tw = h->d_tw; p.avg = h->d_avg; p.samples = h->d_samples;
-			constexpr int M = 8192;
-			const int units = (nreads + (M / Pr) - 1) / (M / Pr);
-			int groups = (512 + S - 1) / S;
-			if (h->groups > 0) groups = h->groups;
-			if (groups > units) groups = units;
-			if (groups < 1) groups = 1;
-			p.groups = groups;
-			if (!h->attr_frames16) {
-				HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_scan_frames<13, true>),
-				                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-				h->attr_frames16 = true;
-			}
-			const size_t lds16 = ((size_t)skewed_size(M) + (size_t)h->N) * 4;
-			hipLaunchKernelGGL((k_power_scan_frames<13, true>), dim3((unsigned)S * (unsigned)groups), dim3(kThreads), lds16, q, p);
-			h->last_kernel = RTLPOWER_KERNEL_DECIMATED;
-			HIP_TRY(hipGetLastError());
-			if (h->timing) {
-				HIP_TRY(hipEventRecord(ev.second, q));
-				h->ev_pending.push_back(std::move(ev));
-			}
-			return 0;
-		}
-	}
-	const int16_t *dec = nullptr;
-	size_t dss = 0, drs = 0;
-	if (h->decimates) {
-		drs = (size_t)c.buf_len;  // elements reserved per read
-		dss = drs * nreads;
-		OWN_TRY(h->d_decA.grow((size_t)S * dss, q));
-		OWN_TRY(h->d_decB.grow((size_t)S * dss, q));
-		int16_t *cur = h->d_decA, *oth = h->d_decB;
-		if (c.boxcar) {
-			const int out_cplx = h->dec_elems / 2;
-			k_power_boxcar<<<grid_for((size_t)S * nreads * out_cplx), 256, 0, q>>>(
-			    d_iq, stream_stride, nreads, (int)c.buf_len, c.downsample, S, cur, dss, drs, out_cplx);
-		} else {
-			for (int j = 0; j < c.downsample_passes; j++) {
-				const int length = (int)c.buf_len >> j;
-				k_power_fifth<<<grid_for((size_t)S * nreads * (length / 4)), 256, 0, q>>>(
-				    j == 0 ? d_iq : nullptr, stream_stride, j == 0 ? nullptr : cur, dss, drs, nreads, (int)c.buf_len,
-				    length, S, j == 0 ? cur : oth, dss, drs);
-				if (j > 0) std::swap(cur, oth);
-			}
-			if (c.comp_fir_size == 9) {
-				const int cplx = ((int)c.buf_len >> c.downsample_passes) / 2;
-				k_power_fir9<<<grid_for((size_t)S * nreads * cplx), 256, 0, q>>>(cur, oth, dss, drs, nreads, cplx, S,
-				                                                               c.downsample_passes);
-				std::swap(cur, oth);
-			}
-		}
-		dec = cur;
-	}
-	if (h->staged) {
-		// bin_e 15 .. 21 (or frames beyond one workgroup's LDS): the same stages over a work buffer in HBM,
-		// a batch of reads at a time (at most ~1 GiB of work buffer)
-		const size_t M = (size_t)h->chunks * h->N;
-		const bool fast_shape = c.bin_e > 14 && !dec && h->chunks == 1;
-		// the pipeline holds two batches: half the points each, and at least four batches where each still fills the GPU
-		// (measured, profiles/r05_power_big_pipe.txt: 2^19 .. 2^21 bins - two passes over HBM per batch - 4-5 % faster in two
-		// sessions and 6 % slower in a third; 2^15 .. 2^17 1-3 % SLOWER: the kernels do run at the same time, but beside the
-		// transform the accumulating pass takes three times as long as alone and becomes the longer chain; a scan of one batch
-		// only pays for the events.  Not the default.)
-		const bool two = fast_shape && h->staged_fast && (h->staged_pipe == 2 || (h->staged_pipe == 1 && c.bin_e >= 18));
-		size_t batch = ((size_t)1 << (two ? 27 : 28)) / ((size_t)S * M);
-		if (batch < 1) batch = 1;
-		if (batch > (size_t)nreads) batch = (size_t)nreads;
-		if (two && ((size_t)nreads + batch - 1) / batch < 4) {
-			const size_t want = nreads < 4 ? (size_t)nreads : 4, b2 = ((size_t)nreads + want - 1) / want;
-			if (((size_t)S * b2) << (c.bin_e - 14) >= 2048) batch = b2;  // (eight combs per CU and batch: 512 made a one-stream scan of 2^21 bins 1.6 x slower)
-		}
-		if (h->staged_batch > 0 && (size_t)h->staged_batch < batch) batch = (size_t)h->staged_batch;
-		if (h->work_reads < batch || (two && !h->work_two)) {
-			HIP_TRY(hipStreamSynchronize(q));
-			if (h->pipe.aux) HIP_TRY(hipStreamSynchronize(h->pipe.aux));
-			h->d_work.reset(); h->d_ave.reset(); h->d_tbuf.reset(); h->d_part.reset();
-			h->work_reads = 0; h->work_two = false;
-			const size_t sets = two ? 2 : 1;
-			OWN_TRY(h->d_work.alloc(sets * S * batch * M));
-			OWN_TRY(h->d_ave.alloc(sets * S * batch));
-			if (fast_shape) {
-				OWN_TRY(h->d_tbuf.alloc(sets * S * batch * M * 2));
-				OWN_TRY(h->d_part.alloc(sets * S * batch * (M / 8192)));
-			}
-			h->work_reads = batch; h->work_two = two;
-		}
-		// rtl_power's own fine-bin shape - an undecimated read is exactly one frame - takes the kernels written for it
-		const bool fast = h->staged_fast && h->d_tbuf && c.bin_e > 14 && !dec && h->chunks == 1 && h->len_dec == 2 * h->N &&
-		                  c.buf_len == (uint32_t)(2 * h->N) && !(stream_stride & 15) && !((uintptr_t)d_iq & 15);
-		if (fast && !h->attr_comb) {
-			HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_scan_big<14, true>),
-			                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-			h->attr_comb = true;
-		}
-		const int eb = c.bin_e < 14 ? c.bin_e : 14;
-		const size_t lds = ((size_t)skewed_size(1 << eb) + ((size_t)1 << eb)) * 4;
-		if (!h->attr_lds) {
-			HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_fft_lds),
-			                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-			h->attr_lds = true;
-		}
-		std::pair<Event, Event> ev;
-		if (h->timing) {
-			if (!h->ev_free.empty()) { ev = std::move(h->ev_free.back()); h->ev_free.pop_back(); }
-			else { OWN_TRY(ev.first.create()); OWN_TRY(ev.second.create()); }
-			HIP_TRY(hipEventRecord(ev.first, q));
-		}
-		const bool piped = fast && two && h->work_two && (h->staged_pipe == 2 || (size_t)nreads > batch);
-		if (piped && !h->pipe.aux) {
-			int lo = 0, hi = 0;
-			HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-			HIP_TRY(rtl_pool::stream_get(h->device, lo, &h->pipe.aux));  // (a priority of its own: a hardware queue of its own)
-			h->pipe.aux_prio = lo;
-			for (Event *e : {&h->pipe.start, &h->pipe.prep[0], &h->pipe.prep[1], &h->pipe.scanned[0], &h->pipe.scanned[1], &h->pipe.done})
-				OWN_TRY(e->create(hipEventDisableTiming));
-		}
-		hipStream_t qa = piped ? h->pipe.aux : q;  // where the byte-moving kernels go
-		// the sets of work buffers (piped: batch k uses set k & 1; the handle's allocation holds work_reads reads per set)
-		const size_t set_work = (size_t)S * h->work_reads * M, set_ave = (size_t)S * h->work_reads;
-		const size_t set_tbuf = set_work * 2, set_part = (size_t)S * h->work_reads * (M / 8192);
-		auto comb_of = [&](int r0, int nb, int set) {  // the comb gather + remove_dc's averages of one batch, on qa
-			const size_t frames = (size_t)S * nb, tiles = frames << (c.bin_e - 13);
-			k_power_comb_bytes<<<grid_for(tiles, 1, 256 * 32), 256, 0, qa>>>(d_iq + (size_t)r0 * c.buf_len, stream_stride, nb, (int)c.buf_len, c.bin_e, tiles,
-			                                                                   h->d_tbuf + set * set_tbuf, h->d_part + set * set_part);
-			k_power_dc_fin<<<grid_for(frames, 64), 64, 0, qa>>>(h->d_part + set * set_part, 1 << (c.bin_e - 13), h->len_dec, frames, h->d_ave + set * set_ave);
-		};
-		if (piped && nreads > 0) {
-			// aux starts behind what the caller has queued on q (the producer of d_iq, an earlier scan's accumulation)
-			HIP_TRY(hipEventRecord(h->pipe.start, q));
-			HIP_TRY(hipStreamWaitEvent(qa, h->pipe.start, 0));
-			comb_of(0, nreads < (int)batch ? nreads : (int)batch, 0);
-			HIP_TRY(hipEventRecord(h->pipe.prep[0], qa));
-		}
-		int kb = 0;
-		for (int r0 = 0; r0 < nreads; r0 += (int)batch, kb++) {
-			const int nb = nreads - r0 < (int)batch ? nreads - r0 : (int)batch;
-			const int set = piped ? (kb & 1) : 0;
-			StagedParams sp{};
-			sp.iq8 = dec ? nullptr : d_iq + (size_t)r0 * c.buf_len; sp.stride8 = stream_stride;
-			sp.dec = dec ? dec + (size_t)r0 * drs : nullptr; sp.dec_stream_stride = dss; sp.dec_read_stride = drs; sp.dec_elems = h->dec_elems;
-			sp.nreads = nb; sp.buf_len = (int)c.buf_len; sp.len_dec = h->len_dec; sp.bin_e = c.bin_e; sp.chunks = h->chunks;
-			sp.ds = c.downsample; sp.peak_hold = c.peak_hold; sp.window = h->d_window; sp.tw = h->d_tw;
-			sp.ave = h->d_ave + set * set_ave; sp.work = h->d_work + set * set_work; sp.avg = h->d_avg; sp.samples = h->d_samples; sp.nstreams = S;
-			const size_t frames = (size_t)S * nb * h->chunks;
-			if (fast) {
-				if (!piped) comb_of(r0, nb, 0);
-				else HIP_TRY(hipStreamWaitEvent(q, h->pipe.prep[set], 0));  // this batch's combs and averages are there (and, aux being
-				                                                            // in order, the batch before the last has left this set)
-				ScanParams cp{};
-				cp.iq8 = h->d_tbuf + set * set_tbuf; cp.window16 = h->d_window16T; cp.tw = h->d_tw; cp.ave = sp.ave; cp.work = sp.work;
-				cp.comb_c = c.bin_e - 14; cp.comb_blocks = frames << cp.comb_c;
-				const size_t lds_big = ((size_t)skewed_size(16384) + 16384) * 4;
-				const unsigned wgs = (unsigned)(cp.comb_blocks < 256 ? cp.comb_blocks : 256);
-				hipLaunchKernelGGL((k_power_scan_big<14, true>), dim3(wgs), dim3(kThreads), lds_big, q, cp);
-				if (piped) {
-					HIP_TRY(hipEventRecord(h->pipe.scanned[set], q));
-					// beside this batch's transform: the next batch's combs into the other set (its last user, batch kb - 1's
-					// passes over HBM, is already queued on aux in front of them) ...
-					if (r0 + (int)batch < nreads) {
-						const int r1 = r0 + (int)batch, nb1 = nreads - r1 < (int)batch ? nreads - r1 : (int)batch;
-						comb_of(r1, nb1, set ^ 1);
-						HIP_TRY(hipEventRecord(h->pipe.prep[set ^ 1], qa));
-					}
-					// ... then, once the transform is through, this batch's stages beyond 13 and its accumulation
-					HIP_TRY(hipStreamWaitEvent(qa, h->pipe.scanned[set], 0));
-				}
-			} else {
-				k_power_dc<<<(unsigned)((size_t)S * nb), 256, 0, q>>>(sp);
-				if (c.bin_e >= 12) k_power_place_tiled<<<grid_for(frames << (c.bin_e - 12), 1, 256 * 64), 256, 0, q>>>(sp);
-				else k_power_place<<<grid_for((size_t)S * nb * M, 256, 256 * 64), 256, 0, q>>>(sp);
-				const size_t nblk = frames << (c.bin_e - eb);
-				hipLaunchKernelGGL(k_power_fft_lds, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(kThreads), lds, q, h->d_work, h->d_tw, eb, nblk);
-			}
-			// stages 14 .. bin_e - 1 over HBM, three per pass; the last pass accumulates (k_power_fft_gl_acc)
-			for (int st = 14; st < c.bin_e;) {
-				const int R = c.bin_e - st >= 3 ? 3 : c.bin_e - st;
-				if (st + R == c.bin_e) {
-					const int g = grid_for((size_t)S << (c.bin_e - R), 256, 256 * 64);
-					if (R == 3) k_power_fft_gl_acc<3><<<g, 256, 0, qa>>>(sp, st);
-					else if (R == 2) k_power_fft_gl_acc<2><<<g, 256, 0, qa>>>(sp, st);
-					else k_power_fft_gl_acc<1><<<g, 256, 0, qa>>>(sp, st);
-				} else {
-					const int g = grid_for(frames << (c.bin_e - R), 256, 256 * 64);
-					k_power_fft_gl<3><<<g, 256, 0, qa>>>(sp.work, h->d_tw, c.bin_e, st, frames);
-				}
-				st += R;
-			}
-			if (c.bin_e <= 14) k_power_accum<<<grid_for((size_t)S * h->N, 256, 256 * 64), 256, 0, q>>>(sp);
-			h->last_kernel = fast ? RTLPOWER_KERNEL_STAGED_FAST : RTLPOWER_KERNEL_STAGED;
-		}
-		if (piped) {  // the scan is complete on q when aux is through
-			HIP_TRY(hipEventRecord(h->pipe.done, qa));
-			HIP_TRY(hipStreamWaitEvent(q, h->pipe.done, 0));
-		}
-		HIP_TRY(hipGetLastError());
-		if (h->timing) {
-			HIP_TRY(hipEventRecord(ev.second, q));
-			h->ev_pending.push_back(std::move(ev));
-		}
-		return 0;
-	}
-	ScanParams p{};
-	p.iq8 = dec ? nullptr : d_iq; p.stride8 = stream_stride;
-	p.dec = dec; p.dec_stream_stride = dss; p.dec_read_stride = drs; p.dec_elems = h->dec_elems;
-	p.nreads = nreads; p.buf_len = (int)c.buf_len; p.len_dec = h->len_dec;
-	p.bin_e = c.bin_e; p.chunks = h->chunks; p.ds = c.downsample; p.peak_hold = c.peak_hold;
-	p.window = h->d_window; p.window16 = h->d_window16; p.tw = h->d_tw; p.avg = h->d_avg; p.samples = h->d_samples;
-	const size_t lds = ((size_t)skewed_size(h->chunks * h->N) + (size_t)h->N) * 4;
-	// per handle, not per process: the attribute belongs to the device the handle lives on, and one process
-	// may hold handles on several
-	if (!h->attr_set) {
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_scan),
-		                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-		h->attr_set = true;
-	}
+	const ScanInput in{d_iq, stream_stride, nreads};
+	const ScanPlan pl = plan_scan(h->cfg, *h, h->opt, h->nstreams, nreads, stream_stride, (unsigned)((uintptr_t)d_iq & 15));
+	rtl_debug::poison_lds(h->stream);  // RTLFM_POISON=1 only
+	if (pl.route == RTLPOWER_KERNEL_NONE) return scan_rms(h, in);  // (no timing, and last_kernel stays)
+	// outside the timed region: the general decimation and what the route allocates (growing waits for the stream)
+	Decimated dec;
+	if (pl.route == RTLPOWER_KERNEL_DECIMATED) OWN_TRY(h->d_dec32.grow((size_t)h->nstreams * nreads * pl.Pr, h->stream));
+	else if (h->decimates) OWN_TRY(decimate_general(h, in, &dec));
+	if (h->staged) OWN_TRY(staged_reserve(h, pl));
 	std::pair<Event, Event> ev;
-	if (h->timing) {
-		if (!h->ev_free.empty()) { ev = std::move(h->ev_free.back()); h->ev_free.pop_back(); }
-		else { OWN_TRY(ev.first.create()); OWN_TRY(ev.second.create()); }
-		HIP_TRY(hipEventRecord(ev.first, q));
+	OWN_TRY(timing_begin(h, ev));
+	switch (pl.route) {
+	case RTLPOWER_KERNEL_DECIMATED: OWN_TRY(scan_decimated(h, pl, in)); break;
+	case RTLPOWER_KERNEL_STAGED:
+	case RTLPOWER_KERNEL_STAGED_FAST: OWN_TRY(scan_staged(h, pl, in, dec)); break;
+	default: OWN_TRY(scan_in_lds(h, pl, in, dec));
 	}
-	const bool big = !dec && h->chunks == 1 && h->len_dec == 2 * h->N && (c.bin_e == 13 || c.bin_e == 14) &&
-	                 !(stream_stride & 15) && !((uintptr_t)d_iq & 15) && !(c.buf_len & 15);
-	if (big && !h->attr_big) {
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_scan_big<13>),
-		                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_scan_big<14>),
-		                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-		h->attr_big = true;
-	}
-	// enough workgroups for the 256 CUs (a large-FFT workgroup fills a CU's LDS, the small ones share):
-	// a stream's reads are split when there are few streams (power_kernels.h)
-	{
-		const int want = 512;
-		int groups = (want + S - 1) / S;
-		if (groups > nreads) groups = nreads;
-		if (groups < 1) groups = 1;
-		if (h->groups > 0) groups = h->groups < nreads ? h->groups : nreads;
-		p.groups = groups;
-	}
-	const unsigned grid = (unsigned)S * (unsigned)p.groups;
-	if (big && h->want_stamps) {
-		OWN_TRY(h->d_stamps.grow((size_t)grid * 4, q));
-		HIP_TRY(hipMemsetAsync(h->d_stamps, 0, (size_t)grid * 32, q));
-		p.stamps = h->d_stamps;
-		h->stamp_last = (int)grid;
-	}
-	// several frames per read (rtl_power's everyday shape: every scan below 8192 bins reads 16384 bytes): raw input,
-	// reads of exactly 8192 or 16384 points
-	const int M = h->chunks * h->N;
-	const bool frames = h->scan_frames && !dec && h->chunks > 1 && c.bin_e >= 3 && (M == 8192 || M == 16384) && h->len_dec == 2 * M &&
-	                    c.buf_len == (uint32_t)(2 * M) && !(stream_stride & 15) && !((uintptr_t)d_iq & 15);
-	if (frames && !h->attr_frames) {
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_scan_frames<13>),
-		                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-		HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_power_scan_frames<14>),
-		                            hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-		h->attr_frames = true;
-	}
-	if (big && c.bin_e == 14) hipLaunchKernelGGL(k_power_scan_big<14>, dim3(grid), dim3(kThreads), lds, q, p);
-	else if (big) hipLaunchKernelGGL(k_power_scan_big<13>, dim3(grid), dim3(kThreads), lds, q, p);
-	else if (frames && M == 8192) hipLaunchKernelGGL(k_power_scan_frames<13>, dim3(grid), dim3(kThreads), lds, q, p);
-	else if (frames) hipLaunchKernelGGL(k_power_scan_frames<14>, dim3(grid), dim3(kThreads), lds, q, p);
-	else hipLaunchKernelGGL(k_power_scan, dim3(grid), dim3(kThreads), lds, q, p);
-	h->last_kernel = big ? RTLPOWER_KERNEL_BIG : frames ? RTLPOWER_KERNEL_FRAMES : RTLPOWER_KERNEL_GENERAL;
+	h->last_kernel = pl.route;
 	HIP_TRY(hipGetLastError());
-	if (h->timing) {
-		HIP_TRY(hipEventRecord(ev.second, q));
-		h->ev_pending.push_back(std::move(ev));
-	}
-	return 0;
+	return timing_end(h, ev);
 }
 
 extern "C" int rtlpower_gpu_scan(rtlpower_gpu *h, int stream, const uint8_t *buf, uint32_t len)
@@ -997,8 +1125,7 @@ extern "C" int rtlpower_gpu_scan(rtlpower_gpu *h, int stream, const uint8_t *buf
 	view.ev_pending.clear(); view.ev_free.clear(); view.timing = false;
 	int r = rtlpower_gpu_scan_device(&view, h->d_one, h->cfg.buf_len, 1);
 	// what the view learnt about this device stays learnt (the kernels' dynamic-LDS limits are raised once per handle)
-	h->attr_set = view.attr_set; h->attr_big = view.attr_big; h->attr_lds = view.attr_lds; h->attr_comb = view.attr_comb;
-	h->attr_frames = view.attr_frames; h->attr_frames16 = view.attr_frames16;
+	h->lds_raised = view.lds_raised;
 	h->last_kernel = view.last_kernel;
 	if (!h->pipe.aux && view.pipe.aux) h->pipe = std::move(view.pipe);
 	return hipStreamSynchronize(h->stream) == hipSuccess ? r : -EIO;

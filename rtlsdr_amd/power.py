@@ -153,6 +153,17 @@ class GpuPower:
         return (mhz.value, span.value) if r == 0 else None
 
 
+def scan_route(cfg: RtlpowerCfg, nstreams: int, nreads: int, stream_stride: int | None = None, addr_low_bits: int = 0,
+               **options) -> int:
+    """``rtlpower_scan_route``: the transform (RTLPOWER_KERNEL_*, 0 for bin_e == 0) a scan of these rows takes - what
+    ``last_kernel`` reads after it -, from the scan's own plan (no GPU).  Contiguous rows by default; ``options`` as
+    ``set_option`` names them."""
+    if stream_stride is None:
+        stream_stride = nreads * int(cfg.buf_len)
+    return check(capi.load().rtlpower_scan_route(C.byref(cfg), nstreams, nreads, stream_stride, addr_low_bits,
+                                                 C.byref(capi.RtlpowerRouteOpts.default(**options))), "rtlpower_scan_route")
+
+
 def report_host(avg, samples: int, rate: float, bin_e: int, crop: float = 0.0) -> np.ndarray:
     """``rtlpower_report_host``: the values csv_dbm() prints, as sign + hundredths (no GPU; avg is left as it is)."""
     a = np.ascontiguousarray(avg, dtype=np.int64)

@@ -274,6 +274,38 @@ def test_power_one_frame_per_read_every_size(oracle_lib, bin_e):
                 assert n == wn[s] and np.array_equal(avg, want[s]), (bin_e, s, "stride")
 
 
+@pytest.mark.parametrize("kw,opts", [
+    (dict(bin_e=1, buf_len=16384), {}),
+    (dict(bin_e=5, buf_len=16384), {}),
+    (dict(bin_e=13, buf_len=16384), {}),
+    (dict(bin_e=9, downsample=4, downsample_passes=2, buf_len=16384), {}),
+    (dict(bin_e=15, buf_len=65536), {}),
+    (dict(bin_e=15, buf_len=65536), dict(staged_fast=0)),
+    (dict(bin_e=5, buf_len=16384), dict(scan_frames=0)),
+], ids=lambda v: "-".join(f"{k[:3]}{x}" for k, x in v.items()) or "defaults")
+def test_power_route_predicted_is_route_taken(kw, opts):
+    """rtlpower_scan_route - the scan's own plan, asked without a handle - against last_kernel after the scan it
+    predicts: the smallest shape of every transform family, on contiguous rows and then on the same rows at a stride 8
+    bytes longer, where no kernel that takes 16-byte loads may run."""
+    from rtlsdr_amd.power import GpuPower, scan_route
+    cfg = RtlpowerCfg.default(**kw)
+    L, nr, ns = int(cfg.buf_len), 3, 2
+    rows = torch.from_numpy(synth.random_u8(ns, L * nr, seed=60 + cfg.bin_e)).cuda()
+    wide = torch.zeros((ns, L * nr + 8), dtype=torch.uint8, device="cuda")
+    wide[:, :L * nr] = rows
+    with GpuPower(cfg, ns, 0) as g:
+        for k, v in opts.items():
+            g.set_option(k, v)
+        for d in (rows, wide):
+            want = scan_route(cfg, ns, nr, d.stride(0), d.data_ptr() & 15, **opts)
+            g.scan_device(d.data_ptr(), d.stride(0), nr)
+            g.sync()
+            print(f"route {kw} {opts} stride {d.stride(0)}: predicted {want}, taken {g.last_kernel}")
+            assert g.last_kernel == want, (kw, opts, d.stride(0), want, g.last_kernel)
+        assert want in (1, 5), (kw, opts, want)  # RTLPOWER_KERNEL_GENERAL, _STAGED
+        assert g.fetch(0)[1] == g.fetch(ns - 1)[1] > 0
+
+
 def test_power_clock_probe():
     """rtlpower_gpu_clock_probe: the large-FFT kernel's workgroups stamp the shader clock they ran at."""
     from rtlsdr_amd.power import GpuPower
