@@ -23,7 +23,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import reference_record as rr  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
 
-MODULES = ["tests/test_oracle_golden.py", "tests/test_power_oracle.py", "tests/test_capi_symbols.py", "tests/test_device_shim.py"]
+MODULES = ["tests/test_oracle_golden.py", "tests/test_power_oracle.py", "tests/test_capi_symbols.py", "tests/test_device_shim.py",
+           "tests/test_power_hard_cpu.py"]
 
 
 def main():
