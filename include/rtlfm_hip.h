@@ -641,6 +641,54 @@ int rtlfm_gpu_bank_survey_prev(rtlfm_gpu *h, uint64_t *power, size_t cap, int32_
 int rtlfm_gpu_set_channel_bins(rtlfm_gpu *h, const int32_t *bins /* [sources][per_source] */);
 int rtlfm_gpu_get_channel_bins(rtlfm_gpu *h, int32_t *bins, int cap);
 
+/*
+ * Option "source_dc": the raw DC block per SOURCE in front of the mixers and the bank ("Source DC").
+ *
+ * A capture has a DC spike at the frequency the dongle is tuned to; the reference takes it off with dc_block_raw_filter
+ * "BEFORE up-mixing" (src/rtl_fm.c:1043-1065, :1329-1332).  cfg.dc_block_raw stays refused while channels are on (it is a
+ * stream's filter); this option is the same recurrence for the source rows.  0 (default) / 1; it acts only on runs that
+ * channels take and may be set with channels off.  All of it is integers, one definition for every path:
+ *
+ * averages     a run has nblocks buffers of L bytes (cfg.block_len, or a ring view's own length: whole 512-byte packets, so
+ *              a buffer is a multiple of 256 complex samples).  For source a and buffer b, k = cfg.rdc_block_const:
+ *                  mI    = trunc(sum(I - 127) / (L / 2))                     (C division; likewise mQ)
+ *                  aI[b] = trunc((mI + aI[b-1] k) / (k + 1))                 (likewise aQ)
+ *                  aI[-1] = clamp(dc_avgI, -128, 128) of the record of the source's CHANNEL 0 (stream a * per_source)
+ *              - the recurrence of :1055-1058 with the carried value clamped on the way in, so that a broken record moves
+ *              values and never breaks a bound (as p0c does for prev_index): |a| <= 128 by induction.
+ * subtraction  every sample of buffer b enters every front end as x = I - 127 - aI[b], y = Q - 127 - aQ[b]: |x|, |y| <= 256.
+ *              The mixer, the boxcar, the filter and the bank are the existing definitions with this x, y; everything behind
+ *              the front end is the stream's chain unchanged (rms() keeps its DC fix: omitDCfix follows cfg.dc_block_raw = 0).
+ * record       after a run dc_avgI / dc_avgQ of EVERY channel's record of the source are a[nblocks - 1] (as the bank writes
+ *              prev_index); rtlfm_gpu_state_get / _set (_all) see them per channel.  verify_twice: both executions use
+ *              one set of averages and one history.
+ * history      the filter and the bank re-read up to 4096 samples in front of a run as raw bytes; those keep the x, y they
+ *              were consumed with: beside the byte history the handle carries, per source, what was subtracted from each
+ *              of its sixteen 256-sample pieces, in two copies that change over with the bytes.  Wherever the history is
+ *              cleared these are too (bytes 127 with a = 0: x = 0).  A run shorter than the history shifts whole pieces.
+ * switching    in either direction waits for the handle, clears the history (a sixth clearing call) and leaves every
+ *              record alone.
+ * refusals     each changes nothing.  -EINVAL: a value other than 0 / 1, or - setting 1 - cfg.rdc_block_const outside
+ *              0 ... 65535; -ENOTSUP on a handle with cfg.dc_block_raw; -EBUSY while a run is begun, a ring slot is open
+ *              or, with source_ring, buffers are queued; -ERANGE: setting 1 while a filter or bank is set that fails the
+ *              wider check below.
+ * bounds       with the option on |m| <= 362 instead of 182 ((256 (|c| + |s|) + 8192) >> 14 over the table) and the bank
+ *              sees |x| <= 256 instead of 128.  rtlfm_channel_filter_check_dc / rtlfm_channel_bank_check_dc (host only) are
+ *              the two checks with those factors; rtlfm_gpu_set_channel_filter / _bank apply them while the option is 1
+ *              (-ERANGE, nothing changed).  Mixed samples still fit the packed int16 the kernels keep in LDS.
+ * kernels      k_rdc_sums_wide / _small on the source rows (one more read of the source bytes) and k_source_dc_smooth,
+ *              inside the front end's timed pair, leave one list per source: what comes off the bytes of every 256-sample
+ *              piece of the history and of the run.  k_channel_boxcar<STAGE, true>, k_channel_fir<true>, k_channel_bank_dc (_survey_dc)
+ *              and, on path 1, k_channel_mix<true> and k_bank_sums<true> are the existing bodies reading it.  With the option at
+ *              0 no kernel, path, launch count, result or allocation differs.
+ */
+int rtlfm_channel_filter_check_dc(const int16_t *taps, int ntaps, int shift);
+/* Measurement only (tools/source_dc_bench.py): source_dc's pre-pass alone over d_iq's source rows, as one timed pair of
+ * rtlfm_gpu_timing_read.  Waits for the handle first; moves nothing a run carries.  -ENOTSUP with the option or channels
+ * off, -EBUSY while a run is begun, -EINVAL / -E2BIG as rtlfm_gpu_run_device. */
+int rtlfm_gpu_source_dc_prepass(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks);
+int rtlfm_channel_bank_check_dc(int K, const int16_t *taps, int ntaps, int shift);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,
@@ -728,6 +776,8 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *   pack_results         0 (default) / 1 / 2: every ring run also leaves its results packed (see rtlfm_gpu_fetch_packed)
  *   bank_survey          0 (default) / 1: every run the channel bank takes also leaves every bin's power (see
  *                        rtlfm_gpu_bank_survey)
+ *   source_dc            0 (default) / 1: runs that channels take subtract every source's smoothed buffer averages in front
+ *                        of the mixers and the bank (see "source_dc" above)
  * Read-only (rtlfm_gpu_get_option):
  *   pack_us              device time of the last run's two pack launches in microseconds (waits for them); -1 when that
  *                        run was not packed or rtlfm_gpu_timing_enable was off

@@ -353,6 +353,9 @@ _SIGNATURES = [
     ("rtlfm_gpu_set_channel_filter", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("rtlfm_gpu_get_channel_filter", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int), _P(C.c_int)]),
     ("rtlfm_channel_bank_check", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    ("rtlfm_channel_filter_check_dc", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("rtlfm_channel_bank_check_dc", C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    ("rtlfm_gpu_source_dc_prepass", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]),
     ("rtlfm_gpu_set_channel_bank", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     ("rtlfm_gpu_get_channel_bank", C.c_int,
      [C.c_void_p, _P(C.c_int), C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int), _P(C.c_int)]),

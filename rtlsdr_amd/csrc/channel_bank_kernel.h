@@ -121,7 +121,19 @@ struct BankParams {
 	int m, Q, Qp, lead, F, Ls, Fs, shift;
 	int bins_stride;          // 0: one list for every source
 	unsigned long long *survey;  // k_channel_bank_survey: [sources][segs][K] partial sums
+	const uint32_t *dc;       // the _dc kernels: the sources' lists of biases (option source_dc; channel_kernel.h), dc_stride dwords apart
+	size_t dc_stride;
 };
+
+// What comes off run sample g's bytes: 127, or - option source_dc - the bias of its piece.  Silence (sample_at) stays x = 0.
+template <bool DC>
+__device__ __forceinline__ channel::pk16 bias_at(const uint32_t *dcrow, int T, int g)
+{
+	if constexpr (DC) {
+		if (g < T && g >= -kHist) return channel::dc_bias(dcrow, g);
+	}
+	return (channel::pk16){127, 127};
+}
 
 // One complex sample of the source as a dword (I | Q << 8): run sample g, the history in front of the run, or silence.
 __device__ __forceinline__ uint32_t sample_at(const uint8_t *row, const uint8_t *hold, int T, int g)
@@ -137,7 +149,9 @@ __device__ __forceinline__ uint32_t sample_at(const uint8_t *row, const uint8_t 
 // The rows of s_out are an odd number of dwords apart, so the 32 lanes of a half wave - min(K, 32) bins, the frame groups
 // a multiple of K apart where K < 32 - read 32 different banks whatever Fs is.  The lane keeps its sum in a 64-bit
 // register over all tiles; at the segment's end the lanes of a bin inside a wave add up by shuffles, the waves through LDS.
-template <bool SURVEY>
+// DC (the _dc kernels; option source_dc): the bias of a sample's piece comes off in the staging loop in 127's place, so the
+// survey sees a bin 0 without the spike with no further change.
+template <bool SURVEY, bool DC>
 __device__ __forceinline__ void bank_body(const BankParams &p)
 {
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -161,6 +175,7 @@ __device__ __forceinline__ void bank_body(const BankParams &p)
 
 	const uint8_t *row = p.f.iq + src * p.f.src_stride;
 	const uint8_t *hold = p.hist_in + src * (size_t)(kHist * 2);
+	const uint32_t *dcrow = DC ? p.dc + src * p.dc_stride : nullptr;
 	const int D = p.f.D;
 	const int p0 = p.f.sin[s0].prev_index;         // one schedule per source: channel 0's
 	const channel::Schedule sc = channel::schedule(p0, p.f.T, D);
@@ -188,8 +203,9 @@ __device__ __forceinline__ void bank_body(const BankParams &p)
 			const uint32_t w = sample_at(row, hold, p.f.T, g0 + u);
 			const int up = u + base;
 			const int at = (up & Km) * p.Ls + (up >> m);
-			hI[at] = (int16_t)((int)(w & 0xffu) - 127);
-			hQ[at] = (int16_t)((int)(w >> 8) - 127);
+			const channel::pk16 bias = bias_at<DC>(dcrow, p.f.T, g0 + u);
+			hI[at] = (int16_t)((int)(w & 0xffu) - bias.x);
+			hQ[at] = (int16_t)((int)(w >> 8) - bias.y);
 		}
 		__syncthreads();
 		const int nb = (nf + gf - 1) / gf;
@@ -279,10 +295,12 @@ __device__ __forceinline__ void bank_body(const BankParams &p)
 }
 
 // Grid: source * segs + seg.  Dynamic LDS: Geometry::lds.
-__global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p) { bank_body<false>(p); }
+__global__ void __launch_bounds__(kWaves * 64) k_channel_bank(const BankParams p) { bank_body<false, false>(p); }
+__global__ void __launch_bounds__(kWaves * 64) k_channel_bank_dc(const BankParams p) { bank_body<false, true>(p); }
 
 // ... the same with the survey's partial sums, [source][seg][K], stored at the segment's end (Geometry of survey = true)
-__global__ void __launch_bounds__(kWaves * 64) k_channel_bank_survey(const BankParams p) { bank_body<true>(p); }
+__global__ void __launch_bounds__(kWaves * 64) k_channel_bank_survey(const BankParams p) { bank_body<true, false>(p); }
+__global__ void __launch_bounds__(kWaves * 64) k_channel_bank_survey_dc(const BankParams p) { bank_body<true, true>(p); }
 
 // The segments' partial sums into power [source][K], and the frames the run emitted for the source into frames [source]:
 // one lane per (source, bin).
@@ -302,10 +320,11 @@ k_bank_survey_reduce(const unsigned long long *__restrict__ partial, int segs, i
 
 // ---- the cross-check ----
 // V: [sources][maxout][K] the sums v, then in place their transforms.
+template <bool DC>
 __global__ void __launch_bounds__(256)
 k_bank_sums(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__restrict__ hist_in, const int16_t *__restrict__ taps,
             int ntaps, int m, int shift, uint32_t pos, int nsources, int per_source, int T, int D, int maxout,
-            const state_t *__restrict__ sin, uint32_t *__restrict__ V)
+            const state_t *__restrict__ sin, uint32_t *__restrict__ V, const uint32_t *__restrict__ dc, size_t dc_stride)
 {
 	const int K = 1 << m;
 	RTLFM_GRID_STRIDE(g, ((size_t)nsources * maxout) << m) {
@@ -321,8 +340,9 @@ k_bank_sums(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_t *__
 		int ai = 0, aq = 0;
 		for (int j = (int)((pos + (uint32_t)e - (uint32_t)r) & (uint32_t)(K - 1)); j < ntaps; j += K) {
 			const uint32_t w = sample_at(row, hold, T, e - j);
-			ai += (int)taps[j] * ((int)(w & 0xffu) - 127);
-			aq += (int)taps[j] * ((int)(w >> 8) - 127);
+			const channel::pk16 bias = bias_at<DC>(dc + src * dc_stride, T, e - j);
+			ai += (int)taps[j] * ((int)(w & 0xffu) - bias.x);
+			aq += (int)taps[j] * ((int)(w >> 8) - bias.y);
 		}
 		V[g] = channel::round_sat_pack(ai, aq, shift);
 	}

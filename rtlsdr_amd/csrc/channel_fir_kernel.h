@@ -71,10 +71,23 @@ struct FirParams {
 	const uint32_t *taps8;    // shifted_taps(), as dwords
 	int ntaps, nt8, halo, shift;
 	int groups;               // workgroups that share a source tile = ceil(per_source / kWaves)
+	const uint32_t *dc;       // k_channel_fir<true>: the sources' lists of biases (option source_dc; channel_kernel.h), dc_stride dwords apart
+	size_t dc_stride;
+	int dc_entries;           // ... and entries of a list: channel::kDcHist + T / 256
 };
 
 // Grid: ((source * segs) + seg) * groups + group; wave w = channel group * kWaves + w of the source (k_channel_boxcar's).
 // Dynamic LDS: lds_bytes(ntaps).
+// DC (k_channel_fir<true>; option source_dc; dynamic LDS: lds_bytes(ntaps) + kDcLds): the staged span covers several buffers
+// and reaches into the history, so the biases of its 256-sample pieces - nine at most - are staged with it, behind the
+// mixed samples, and a lane looks its dword's up there: the 64 lanes of a turn cover 128 samples, one or two entries, which
+// LDS hands to all of them at once.
+constexpr int kDcSlots = 16;
+constexpr size_t kDcLds = kDcSlots * sizeof(uint32_t);
+static_assert((kTile + kHaloMax) / channel::kDcPiece + 1 <= kDcSlots, "a span's pieces fit their slots");
+
+// (One kernel body for both forms, as channel::k_channel_mix.)
+template <bool DC>
 __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 {
 	extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -85,6 +98,7 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 	uint32_t *s_src = s_taps + kGroup * p.nt8 / 2;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	uint32_t *mI = s_src + span / 2 + wave * 2 * W, *mQ = mI + W;
+	[[maybe_unused]] uint32_t *s_dc = s_src + span / 2 + kWaves * 2 * W;  // (DC only)
 	const int group = (int)(blockIdx.x % (unsigned)p.groups);
 	const int sseg = (int)(blockIdx.x / (unsigned)p.groups);
 	const int seg = sseg % p.f.segs;
@@ -109,6 +123,11 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 	for (int t = t_begin; t < t_end; t++) {
 		const int g0 = t * kTile - p.halo;  // the run sample staged first (below 0: the history's)
 		__syncthreads();  // the source bytes of the tile before this one have been mixed by every wave
+		[[maybe_unused]] const int pc0 = (g0 + channel::kHist) >> channel::kDcShift;  // the list's entry of the span's first piece (halo <= kHist: >= 0)
+		if constexpr (DC) {
+			// (past the run's end the span holds bytes 127: nothing comes off them but 127)
+			if (tid < kDcSlots) s_dc[tid] = pc0 + tid < p.dc_entries ? p.dc[src * p.dc_stride + (size_t)(pc0 + tid)] : channel::kDcNone;
+		}
 		for (int u = tid; u < span / kGroup; u += kWaves * 64) {
 			const int g = g0 + u * kGroup;
 			uint4 v = make_uint4(0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu, 0x7f7f7f7fu);
@@ -123,8 +142,14 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 			const uint32_t w = s_src[i];
 			const uint32_t ph = (p.f.pos + (uint32_t)(g0 + 2 * i)) * step;
 			int i0, q0, i1, q1;
-			channel::mix(w, 0, s_table[ph >> channel::kPhaseShift], i0, q0);
-			channel::mix(w, 1, s_table[(ph + step) >> channel::kPhaseShift], i1, q1);
+			if constexpr (DC) {
+				const channel::pk16 bias = __builtin_bit_cast(channel::pk16, s_dc[((g0 + 2 * i + channel::kHist) >> channel::kDcShift) - pc0]);
+				channel::mix_bias(w, 0, s_table[ph >> channel::kPhaseShift], bias, i0, q0);
+				channel::mix_bias(w, 1, s_table[(ph + step) >> channel::kPhaseShift], bias, i1, q1);
+			} else {
+				channel::mix(w, 0, s_table[ph >> channel::kPhaseShift], i0, q0);
+				channel::mix(w, 1, s_table[(ph + step) >> channel::kPhaseShift], i1, q1);
+			}
 			mI[i] = pack_iq(i0, i1);
 			mQ[i] = pack_iq(q0, q1);
 		}
@@ -159,6 +184,7 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_fir(const FirParams p)
 			reinterpret_cast<uint4 *>(p.hist_out + src * (size_t)(channel::kHist * 2))[u] = channel::history_piece(row, hold, p.f.T, u);
 	}
 }
+
 
 // ---- the cross-check ----
 // X: [nstreams][xstride] mixed samples, the history's last kHaloMax in front of the run's T (k_channel_mix, twice).

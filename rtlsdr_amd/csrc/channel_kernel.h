@@ -14,6 +14,8 @@
 //                      a workgroup stages an 8 KiB tile of ONE source in LDS once, and each of its waves mixes and sums
 //                      it for another channel of that source.  Nothing at the capture rate goes back to memory.
 //   k_source_history   the cross-checks' copy of the carried source history (the one-launch kernels write it themselves).
+//   k_source_dc_smooth option source_dc: dc_block_raw_filter's averages per SOURCE and buffer, as the list of what comes off
+//                      every 256-sample piece in front of the mixers, the filter and the bank (the DC forms of the kernels).
 //
 // The channel filter (channel_fir_kernel.h) and the channel bank (channel_bank_kernel.h) stand in k_channel_boxcar's place
 // and share what is here: the launch frame, the output schedule, the rounding of a sum and the source history.
@@ -60,16 +62,21 @@ typedef short pk16 __attribute__((ext_vector_type(2)));
 // Sample `half` (0 / 1) of a source dword (bytes I0 Q0 I1 Q1) times e^(-j theta), cs = the table entry of theta:
 // (x, y) = (I - 127, Q - 127) as one packed pair, then I' = (x, y) . (c, s) and Q' = (y, x) . (c, -s), each one
 // v_dot2_i32_i16 with the rounding constant as its accumulator (the compiler keeps the wait states of its own dots).
-__device__ __forceinline__ void mix(uint32_t w, int half, uint32_t cs, int &i, int &q)
+// bias: what comes off the bytes - (127, 127), or with option source_dc (127 + aI, 127 + aQ) of the sample's buffer.
+__device__ __forceinline__ void mix_bias(uint32_t w, int half, uint32_t cs, pk16 bias, int &i, int &q)
 {
 	const uint32_t spread = __builtin_amdgcn_perm(0u, w, half ? 0x0c030c02u : 0x0c010c00u);  // I | Q << 16
-	const pk16 xy = __builtin_bit_cast(pk16, spread) - (pk16){127, 127};
+	const pk16 xy = __builtin_bit_cast(pk16, spread) - bias;
 	const uint32_t xyw = __builtin_bit_cast(uint32_t, xy);
 	const pk16 yx = __builtin_bit_cast(pk16, (xyw >> 16) | (xyw << 16));
 	const pk16 c_s = __builtin_bit_cast(pk16, cs);
 	const pk16 c_ms = c_s * (pk16){1, -1};
 	i = __builtin_amdgcn_sdot2(xy, c_s, 8192, false) >> 14;
 	q = __builtin_amdgcn_sdot2(yx, c_ms, 8192, false) >> 14;
+}
+__device__ __forceinline__ void mix(uint32_t w, int half, uint32_t cs, int &i, int &q)
+{
+	mix_bias(w, half, cs, (pk16){127, 127}, i, q);
 }
 
 // (one wave's LDS operations complete in the order it issues them: the fences are for the compiler)
@@ -147,12 +154,86 @@ k_source_history(const uint8_t *__restrict__ iq, size_t src_stride, const uint8_
 	}
 }
 
+// ------------------------------------------------------------------ source_dc ----
+// Option source_dc (include/rtlfm_hip.h): dc_block_raw_filter's averages (src/rtl_fm.c:1043-1065) per SOURCE and buffer,
+// taken off every sample in front of every front end.  What the front ends read is one list per source, a dword per
+// 256-sample piece - buffers are whole multiples of 256 samples, so a piece has one buffer and one pair -:
+//     dc[source][kDcHist + T / 256],   entry j = the piece that starts at run sample (j - kDcHist) * 256
+// the history's sixteen pieces in front, then the run's.  An entry is the BIAS of its piece, (127 + aI) | (127 + aQ) << 16
+// as two int16: what mix_bias() and the bank take off the bytes; kDcNone where nothing was subtracted (a = 0).  The list's
+// last kDcHist entries are the next run's history, whatever T is: a run shorter than the history shifts whole pieces.
+constexpr int kDcPiece = 256;
+constexpr int kDcShift = 8;
+constexpr int kDcHist = kHist / kDcPiece;
+constexpr uint32_t kDcNone = 0x007f007fu;
+static_assert(kHist % kDcPiece == 0 && (1 << kDcShift) == kDcPiece, "the history is whole pieces");
+
+// the bias of run sample g (>= -kHist) out of a source's list
+__device__ __forceinline__ pk16 dc_bias(const uint32_t *dcrow, int g)
+{
+	return __builtin_bit_cast(pk16, dcrow[(g + kHist) >> kDcShift]);
+}
+
+// k_rdc_smooth by source: the recurrence runs down one lane out of LDS as there.  The carried value is channel 0's,
+// clamped to [-128, 128] on the way in (a broken record moves values, never a bound: |a| <= 128 by induction); every
+// channel's record receives the last one.  Writes the source's list - the history's entries from hist_in (none: kDcNone),
+// the run's - and the next history's entries to hist_out (none: a run of the boxcar, which carries no history).
+__global__ void __launch_bounds__(64)
+k_source_dc_smooth(const long long *__restrict__ sums /* [source][b][2] */, uint32_t L, int nblocks, int nsources, int per_source, int k,
+                   const state_t *__restrict__ sin, state_t *__restrict__ sout, const uint32_t *__restrict__ hist_in,
+                   uint32_t *__restrict__ hist_out, uint32_t *__restrict__ dc, size_t dc_stride)
+{
+	const size_t src = blockIdx.x;
+	if (src >= (size_t)nsources) return;
+	const int lane = (int)threadIdx.x;
+	uint32_t *row = dc + src * dc_stride;
+	__shared__ int2 m[64];
+	__shared__ int2 last;
+	if (lane < kDcHist) row[lane] = hist_in ? hist_in[src * kDcHist + lane] : kDcNone;
+	const state_t &rec = sin[src * (size_t)per_source];
+	int pi = min(max(rec.dc_avgI, -128), 128), pq = min(max(rec.dc_avgQ, -128), 128);
+	const int pairs = (int)(L / 2), ppb = (int)(L / (2 * kDcPiece));
+	for (int base = 0; base < nblocks; base += 64) {
+		const int b = base + lane;
+		const int cnt = nblocks - base < 64 ? nblocks - base : 64;
+		if (b < nblocks)
+			m[lane] = make_int2((int)(sums[(src * nblocks + b) * 2] / pairs), (int)(sums[(src * nblocks + b) * 2 + 1] / pairs));
+		__syncthreads();
+		if (lane == 0) {
+			for (int t = 0; t < cnt; t++) {
+				const int2 v = m[t];
+				pi = sdiv_trunc(v.x + pi * k, k + 1);  // (|v| <= 128, |p| <= 128, k <= 65535: no overflow; k + 1 > 0)
+				pq = sdiv_trunc(v.y + pq * k, k + 1);
+				m[t] = make_int2(pi, pq);
+			}
+			last = make_int2(pi, pq);
+		}
+		__syncthreads();
+		for (int i = lane; i < cnt * ppb; i += 64) {
+			const int2 a = m[i / ppb];
+			row[kDcHist + (size_t)base * ppb + i] = (uint32_t)(uint16_t)(127 + a.x) | (uint32_t)(uint16_t)(127 + a.y) << 16;
+		}
+		__syncthreads();
+	}
+	// (the block's own stores, behind a barrier)
+	if (hist_out && lane < kDcHist) hist_out[src * kDcHist + lane] = row[(size_t)nblocks * ppb + lane];
+	for (int c = lane; c < per_source; c += 64) {
+		sout[src * (size_t)per_source + c].dc_avgI = last.x;
+		sout[src * (size_t)per_source + c].dc_avgQ = last.y;
+	}
+}
+
 // ---------------------------------------------------------------- k_channel_mix ----
 // One thread per 16 source bytes = 8 complex samples of one stream, as k_convert; the row read is the SOURCE's.
+// DC (k_channel_mix<true>; option source_dc): the bias of the thread's eight samples from entry dc_off + n / 256 of the
+// source's list - dc_off = kDcHist for a run, kDcHist - halo / 256 for the end of the history the filter's cross-check
+// mixes.  (The body stands in the kernel itself, for both forms: behind a call, even an inlined one, the compiler lays the
+// off form out differently from the kernel it was - profiles/source_dc_isa_compare.txt.)
+template <bool DC>
 __global__ void __launch_bounds__(256)
 k_channel_mix(const uint8_t *__restrict__ iq, size_t src_stride, uint32_t L, int nblocks, int nstreams, int per_source,
               const uint32_t *__restrict__ steps, const uint32_t *__restrict__ table, uint32_t pos,
-              uint32_t *__restrict__ X, size_t xstride)
+              uint32_t *__restrict__ X, size_t xstride, const uint32_t *__restrict__ dc, size_t dc_stride, int dc_off)
 {
 	__shared__ uint32_t s_table[kTableSize];
 	for (int i = threadIdx.x; i < kTableSize; i += blockDim.x) s_table[i] = table[i];
@@ -170,11 +251,14 @@ k_channel_mix(const uint8_t *__restrict__ iq, size_t src_stride, uint32_t L, int
 		const uint32_t step = steps[s];
 		const uint32_t n = (uint32_t)b * (L / 2) + (uint32_t)j * 8;  // sample of the run
 		uint32_t ph = (pos + n) * step;
+		[[maybe_unused]] pk16 bias;
+		if constexpr (DC) bias = __builtin_bit_cast(pk16, dc[src * dc_stride + (size_t)dc_off + (n >> kDcShift)]);
 		uint32_t o[8];
 #pragma unroll
 		for (int k = 0; k < 8; k++) {
 			int re, im;
-			mix(w[k >> 1], k & 1, s_table[ph >> kPhaseShift], re, im);
+			if constexpr (DC) mix_bias(w[k >> 1], k & 1, s_table[ph >> kPhaseShift], bias, re, im);
+			else mix(w[k >> 1], k & 1, s_table[ph >> kPhaseShift], re, im);
 			ph += step;
 			o[k] = pack_iq(re, im);
 		}
@@ -190,6 +274,8 @@ struct BoxParams {
 	const uint32_t *steps;    // [nstreams]
 	const uint32_t *table;    // [kTableSize]
 	int groups;               // workgroups that share a source tile = ceil(per_source / kWaves)
+	const uint32_t *dc;       // k_channel_boxcar<STAGE, true>: the sources' lists of biases (option source_dc), dc_stride dwords apart
+	size_t dc_stride;
 };
 
 // inclusive prefix sum over the wave's 64 lanes (wrapping)
@@ -216,7 +302,9 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v, int lane)
 // STAGE (D >= kStageMinD): a tile's outputs of a channel are gathered in LDS and leave as consecutive dwords of the whole
 // wave; without it every lane stores its own, 4 bytes wherever a boundary falls (at /10: 13 cache lines per store
 // instruction; LAB.md I.38).
-template <bool STAGE>
+// DC (option source_dc): a lane's 64 samples lie in one 256-sample piece, so one bias per lane and tile comes off them in
+// the mixer.  (One kernel body for both forms, as k_channel_mix.)
+template <bool STAGE, bool DC>
 __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams p)
 {
 	__shared__ uint32_t s_table[kTableSize];
@@ -277,6 +365,8 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 		if (a < p.f.T) {
 			int left = (int)(k0 + 1) * D - p0 - a;  // samples up to and including the one the next output ends behind
 			uint32_t ph = (p.f.pos + (uint32_t)a) * step;
+			[[maybe_unused]] pk16 bias;
+			if constexpr (DC) bias = dc_bias(p.dc + src * p.dc_stride, a);
 			const uint4 *rowp = reinterpret_cast<const uint4 *>(&s_tile[lane * kRowStride]);
 			for (int v = 0; v < kRowDwords / 4; v++) {
 				const uint4 raw = rowp[v];
@@ -290,7 +380,8 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 #pragma unroll
 				for (int j = 0; j < 8; j++) {
 					int re, im;
-					mix(w[j >> 1], j & 1, cs[j], re, im);
+					if constexpr (DC) mix_bias(w[j >> 1], j & 1, cs[j], bias, re, im);
+					else mix(w[j >> 1], j & 1, cs[j], re, im);
 					run_i += (uint32_t)re; run_q += (uint32_t)im;
 					if (--left == 0) {
 						// (the stretch's first output lacks what lay in front of the stretch: added below)
@@ -345,6 +436,7 @@ __global__ void __launch_bounds__(kWaves * 64) k_channel_boxcar(const BoxParams 
 		leave_schedule(p.f.sout, p.f.cnt, s, schedule(p0, p.f.T, D));
 	}
 }
+
 
 // segments per stream: enough waves to fill the GPU, no segment shorter than min_tiles (each but the first re-runs a tile)
 inline void plan(int nstreams, int ntiles, int D, int target_waves, int min_tiles, int tiles_per_seg, int *segs, int *tps)

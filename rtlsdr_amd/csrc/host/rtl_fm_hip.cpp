@@ -80,6 +80,8 @@
 // a source's short last buffer is completed with bytes 127 - which mix to 0 at every phase - to the full length and
 // demodulated, a source that has ended is fed buffers of bytes 127 and its K files receive nothing more, until the last
 // source ends.  Not with -S, -C, -K, -R, -Z, -O agc=2 or -E rdc: each needs what the library refuses while channels are on.
+// -E srcdc (with -X only, not with -E rdc) sets the library's option source_dc: every source's DC spike comes off in front of
+// the mixers.
 //
 // Not restated (out of scope): the command file's own hop (its 2 x 3 200 000 byte mute, the DC-filter reset, -B), and
 // -t negative (terminate on squelch).
@@ -149,6 +151,7 @@ struct Settings {
 	bool zero_copy = false;  // -Z: the device layer reads straight into the pinned staging ring
 	const char *filename = "-", *cmd_file = nullptr, *scan_file = nullptr, *keep_file = nullptr, *resume_file = nullptr;
 	const char *chan_file = nullptr, *opt_string = nullptr;
+	bool source_dc = false;  // -E srcdc: the library's option source_dc (with -X only)
 	int agc = -1;        // -O agc=<n>; -1: not given
 	int chan_taps = -1;  // -x; -1: not given
 };
@@ -1381,6 +1384,7 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 		int r = rtlfm_gpu_create(&c, S, 0, &m.gpu);
 		if (r == 0) { what = "option source_ring"; r = rtlfm_gpu_set_option(m.gpu, "source_ring", 1); }
 		if (r == 0) { what = "rtlfm_gpu_set_channels"; r = rtlfm_gpu_set_channels(m.gpu, K, steps.data()); }
+		if (r == 0 && st.source_dc) { what = "option source_dc"; r = rtlfm_gpu_set_option(m.gpu, "source_dc", 1); }
 		if (r == 0 && c.squelch_level) {
 			// -l: demod_thread_fn's rule on the device, and only what it let through comes back.  (-ENOTSUP, behind a
 			// resampler: the rule from the carried state after every run, hold_back.)
@@ -1461,7 +1465,7 @@ void usage()
 	        "\t[-X channel_file  channels: line i of the file is the list of channel frequencies of source i (-N n, or one source), in\n"
 	        "\t       -S's grammar, the same number K on every line; source i's centre frequency is its -f as given and its K channels are mixed\n"
 	        "\t       down on the GPU; stream s = channel s %% K of source s / K writes the file with %%d = s; not with -S -C -K -R -Z,\n"
-	        "\t       -O agc=2 or -E rdc]\n"
+	        "\t       -O agc=2 or -E rdc; -E srcdc takes every source's DC spike off in front of the mixers (-q sets its constant)]\n"
 	        "\t[-x ntaps  with -X: a windowed-sinc channel filter of ntaps taps (cutoff 0.4 of the output rate) in the boxcar's place; not with -F]\n"
 	        "\t[-K file  keep: write every stream's carried filter state to file at exit (with -N n: n records, in source order)]\n"
 	        "\t[-R file  resume: load such a file before the first buffer - it must hold as many records as there are sources and\n"
@@ -1472,7 +1476,7 @@ void usage()
 	        "\t[-m minimum_capture_rate Hz (default: 1m)]\n"
 	        "\t[-F fir_size (default: off)]  enables the fifth-order low pass; 0 or 9 (9 = droop compensation)\n"
 	        "\t[-A std/fast/lut choose atan math (default: std)]\n"
-	        "\t[-E enable_option]  edge, dc, rdc, deemp, offset\n"
+	        "\t[-E enable_option]  edge, dc, rdc, deemp, offset, srcdc (with -X only; not with rdc)\n"
 	        "\t[-c de-emphasis_time_constant in us: us (75), eu (50) or a number]\n"
 	        "\t[-o oversampling (default: 1)]  [-l squelch_level]  [-t squelch_delay (default: 10)]  [-q rdc_block_const]\n"
 	        "\t[-L N  prints levels every N calculations (with -N: per stream, as 'stream i: ...')]\n"
@@ -1536,6 +1540,7 @@ int main(int argc, char **argv)
 			if (!strcmp(optarg, "edge")) st.edge = 1;
 			if (!strcmp(optarg, "dc") || !strcmp(optarg, "adc")) c.dc_block_audio = 1;
 			if (!strcmp(optarg, "rdc")) c.dc_block_raw = 1;
+			if (!strcmp(optarg, "srcdc")) st.source_dc = true;
 			if (!strcmp(optarg, "deemp")) c.deemph = 1;
 			if (!strcmp(optarg, "offset")) c.offset_tuning = 1;
 			break;
@@ -1577,6 +1582,15 @@ int main(int argc, char **argv)
 		case 'v': st.verbosity++; break;
 		default: usage();
 		}
+	}
+	if (st.source_dc && c.dc_block_raw) {
+		fprintf(stderr, "-E srcdc (raw DC block per source, with -X) does not go with -E rdc (raw DC block per stream): choose one.\n");
+		return 1;
+	}
+	if (st.source_dc && !st.chan_file) {
+		fprintf(stderr, "-E srcdc (raw DC block per source) needs -X (the channel file): it acts in front of the channels' mixers only; "
+		                "without channels -E rdc is the raw DC block.\n");
+		return 1;
 	}
 	if (st.chan_taps != -1 && !st.chan_file) {
 		fprintf(stderr, "-x (taps of the channel filter) needs -X (the channel file): the filter acts on channels only.\n");

@@ -121,6 +121,12 @@ struct rtlfm_gpu {
 	// every SOURCE's last samples; a run reads [src_hist_cur] and writes the other
 	DevBuf<uint8_t> d_src_hist[2];
 	int src_hist_cur = 0, src_hist_srcs = 0;
+	// option source_dc (channel_kernel.h, k_source_dc_smooth): allocated when the option is first set, for as many sources as
+	// there are streams.  The history's biases change over with d_src_hist.
+	DevBuf<long long> d_sdc_sums;          // [sources][cap_blocks][2] k_rdc_sums_wide's, by source
+	DevBuf<uint32_t> d_sdc;                // [sources][sdc_stride] a run's list of biases: the history's pieces, then the run's
+	size_t sdc_stride = 0;
+	DevBuf<uint32_t> d_sdc_hist[2];        // [sources][channel::kDcHist]
 	// the channel filter (channel_fir_kernel.h; rtlfm_gpu_set_channel_filter): acts while channels are on
 	int fir_ntaps = 0, fir_shift = 0;      // 0 taps: none, the boxcar
 	std::vector<int16_t> fir_taps;         // what the getter hands back
@@ -198,6 +204,7 @@ struct rtlfm_gpu {
 		int source_ring = 0;   // 1: while channels are on the ring's input side has one row per SOURCE (ring_rows) and the ring calls are open
 		int pack_results = 0;  // 1 / 2: every ring run ends with k_pack_plan + k_pack_copy (pack_kernel.h; rtlfm_gpu_fetch_packed)
 		int bank_survey = 0;   // 1: a run the bank takes leaves every bin's power as well (k_channel_bank_survey; rtlfm_gpu_bank_survey)
+		int source_dc = 0;     // 1: runs that channels take subtract every source's smoothed buffer averages in front of the front end (k_source_dc_smooth)
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
 	DevBuf<int16_t> vt_out;
@@ -582,12 +589,28 @@ extern "C" int rtlfm_gpu_destroy(rtlfm_gpu *h)
 	return 0;
 }
 
+// Option source_dc: the sums, the lists of biases and the history's biases, for the most sources and the longest run the
+// handle can have (a view - run_ragged - cannot allocate).
+static int ensure_source_dc(rtlfm_gpu *h)
+{
+	const size_t S = (size_t)h->nstreams;
+	h->sdc_stride = (size_t)channel::kDcHist + (size_t)h->cap_blocks * (h->cfg.block_len / (2 * channel::kDcPiece));
+	OWN_TRY(h->d_sdc_sums.alloc(S * h->cap_blocks * 2));
+	OWN_TRY(h->d_sdc.alloc(S * h->sdc_stride));
+	for (int i = 0; i < 2; i++) OWN_TRY(h->d_sdc_hist[i].alloc(S * channel::kDcHist));
+	return 0;
+}
+
 // The source history - every source's carried bytes - back to 127: mixed zeros, m[n < 0] = 0 and x[n < 0] = 0.  On the
 // handle's stream: behind the runs already queued, in front of the next.
 static int history_clear(rtlfm_gpu *h)
 {
 	if (!h->d_src_hist[0]) return 0;
 	HIP_TRY(hipMemsetAsync(h->d_src_hist[h->src_hist_cur], 127, (size_t)h->src_hist_srcs * channel::kHist * 2, h->stream));
+	// (option source_dc: with them what was subtracted from them - nothing)
+	if (h->d_sdc_hist[0])
+		HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_sdc_hist[h->src_hist_cur].get(), (int)channel::kDcNone,
+		                          (size_t)h->nstreams * channel::kDcHist, h->stream));
 	return 0;
 }
 
@@ -837,6 +860,15 @@ extern "C" int rtlfm_channel_filter_check(const int16_t *taps, int ntaps, int sh
 	return 182 * sum + r <= 0x7fffffffll ? 0 : -ERANGE;  // |m| <= 182: the int32 sum and its rounding cannot overflow
 }
 
+extern "C" int rtlfm_channel_filter_check_dc(const int16_t *taps, int ntaps, int shift)
+{
+	if (!taps || ntaps < 1 || ntaps > RTLFM_CHANNEL_MAX_TAPS || shift < 0 || shift > 30) return -EINVAL;
+	long long sum = 0;
+	for (int j = 0; j < ntaps; j++) sum += taps[j] < 0 ? -(long long)taps[j] : (long long)taps[j];
+	const long long r = shift ? 1ll << (shift - 1) : 0;
+	return 362 * sum + r <= 0x7fffffffll ? 0 : -ERANGE;  // option source_dc: |x|, |y| <= 256, so |m| <= 362
+}
+
 extern "C" int rtlfm_channel_lowpass(int ntaps, double cutoff, int D, int16_t *taps, int *shift)
 {
 	if (!taps || !shift || ntaps < 1 || ntaps > RTLFM_CHANNEL_MAX_TAPS || D < 1 || !(cutoff > 0.0 && cutoff < 0.5)) return -EINVAL;
@@ -868,7 +900,8 @@ extern "C" int rtlfm_gpu_set_channel_filter(rtlfm_gpu *h, const int16_t *taps, i
 {
 	if (!h) return -EINVAL;
 	if (ntaps != 0) {
-		const int r = rtlfm_channel_filter_check(taps, ntaps, shift);
+		int r = rtlfm_channel_filter_check(taps, ntaps, shift);
+		if (r == 0 && h->opt.source_dc) r = rtlfm_channel_filter_check_dc(taps, ntaps, shift);
 		if (r < 0) return r;
 	}
 	if (h->cfg.downsample_passes > 0) return -ENOTSUP;  // (the filter takes the boxcar's place, not fifth_order's)
@@ -909,6 +942,20 @@ extern "C" int rtlfm_channel_bank_check(int K, const int16_t *taps, int ntaps, i
 	return 128 * most + r <= 0x7fffffffll ? 0 : -ERANGE;  // |x| <= 128: a branch's int32 sum and its rounding cannot overflow
 }
 
+extern "C" int rtlfm_channel_bank_check_dc(int K, const int16_t *taps, int ntaps, int shift)
+{
+	const int e = rtlfm_channel_bank_check(K, taps, ntaps, shift);
+	if (e != 0 && e != -ERANGE) return e;
+	long long most = 0;
+	for (int b = 0; b < K && b < ntaps; b++) {
+		long long sum = 0;
+		for (int j = b; j < ntaps; j += K) sum += taps[j] < 0 ? -(long long)taps[j] : (long long)taps[j];
+		if (sum > most) most = sum;
+	}
+	const long long r = shift ? 1ll << (shift - 1) : 0;
+	return 256 * most + r <= 0x7fffffffll ? 0 : -ERANGE;  // option source_dc: |x| <= 256
+}
+
 template <typename T>
 static int bank_upload(DevBuf<T> &dst, const T *src, size_t n)
 {
@@ -923,6 +970,7 @@ extern "C" int rtlfm_gpu_set_channel_bank(rtlfm_gpu *h, int K, const int32_t *bi
 	if (!h) return -EINVAL;
 	if (K != 0) {
 		int r = rtlfm_channel_bank_check(K, taps, ntaps, shift);
+		if (r == 0 && h->opt.source_dc) r = rtlfm_channel_bank_check_dc(K, taps, ntaps, shift);
 		if (r < 0) return r;
 	}
 	if (ingest_busy(h)) return -EBUSY;  // (a begun run means channels off: asked first, or it could never be the answer)
@@ -1123,6 +1171,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"input_health", &h->opt.input_health},
 		{"squelch_gate", &h->opt.squelch_gate}, {"conseq_squelch", &h->opt.conseq_squelch},
 		{"source_ring", &h->opt.source_ring}, {"pack_results", &h->opt.pack_results}, {"bank_survey", &h->opt.bank_survey},
+		{"source_dc", &h->opt.source_dc},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -1194,6 +1243,25 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 		if (ingest_busy(h)) return -EBUSY;
 		h->opt.bank_survey = (int)value;
 		return value == 0 ? survey_free(h, true) : 0;
+	}
+	if (!strcmp(name, "source_dc")) {
+		// (include/rtlfm_hip.h: every refusal leaves the handle as it was)
+		if (value != 0 && value != 1) return -EINVAL;
+		if (value == 1 && (h->cfg.rdc_block_const < 0 || h->cfg.rdc_block_const > 65535)) return -EINVAL;
+		if (h->cfg.dc_block_raw) return -ENOTSUP;
+		if (ingest_busy(h) || (h->opt.source_ring && ingest_queued(h))) return -EBUSY;
+		if (value == 1 && h->fir_ntaps > 0 && rtlfm_channel_filter_check_dc(h->fir_taps.data(), h->fir_ntaps, h->fir_shift) < 0) return -ERANGE;
+		if (value == 1 && h->bank_K > 0 &&
+		    rtlfm_channel_bank_check_dc(h->bank_K, h->bank_taps.data(), h->bank_ntaps, h->bank_shift) < 0)
+			return -ERANGE;
+		HIP_TRY(hipSetDevice(h->device));
+		HIP_TRY(sync_all(h));
+		if (value == 1) {
+			int r = ensure_source_dc(h);
+			if (r < 0) return r;
+		}
+		h->opt.source_dc = (int)value;
+		return history_clear(h);  // (the history belongs to the old rule; the records stay)
 	}
 	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
 	if (!strcmp(name, "source_ring")) {
@@ -1867,6 +1935,27 @@ static int run_irregular_rest(rtlfm_gpu *h, const uint32_t *cur, size_t xstride,
 	return run_tail(h, tp, dd, dds, T, false, nblocks, Nblk, 1, d_out, out_stride, d_out_len);
 }
 
+// Option source_dc's pre-pass, in front of a channel front end and inside its timed pair: every source's buffer sums
+// (k_rdc_sums_wide / _small on the source rows - one more read of the source bytes), then k_source_dc_smooth, which leaves
+// the run's list of biases in d_sdc, the averages in every channel's record of sout and - hist: a filter or a bank carries
+// a history - the next history's biases in the copy the run writes.
+static int launch_source_dc(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, const state_t *sin, state_t *sout, bool hist)
+{
+	const int nsrc = h->nstreams / h->chan_per;
+	const uint32_t L = h->cfg.block_len;
+	if (!h->d_sdc || !h->d_sdc_sums || !h->d_sdc_hist[0] || !h->d_sdc_hist[1]) return -EFAULT;
+	if ((size_t)channel::kDcHist + (size_t)nblocks * (L / (2 * channel::kDcPiece)) > h->sdc_stride) return -E2BIG;
+	const size_t total = (size_t)nsrc * nblocks;
+	if (L < 8192)
+		k_rdc_sums_small<<<(unsigned)((total + 3) / 4), 256, 0, h->stream>>>(d_iq, stream_stride, L, nblocks, total, h->d_sdc_sums);
+	else
+		k_rdc_sums_wide<<<(unsigned)total, 256, 0, h->stream>>>(d_iq, stream_stride, L, nblocks, h->d_sdc_sums);
+	channel::k_source_dc_smooth<<<(unsigned)nsrc, 64, 0, h->stream>>>(
+		h->d_sdc_sums, L, nblocks, nsrc, h->chan_per, h->cfg.rdc_block_const, sin, sout,
+		hist ? h->d_sdc_hist[h->src_hist_cur].get() : nullptr, hist ? h->d_sdc_hist[h->src_hist_cur ^ 1].get() : nullptr, h->d_sdc, h->sdc_stride);
+	return 0;
+}
+
 static int run_staged(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
                       size_t out_stride, int32_t *d_out_len)
 {
@@ -1891,10 +1980,16 @@ static int run_staged(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, i
 		                                           h->d_rdc_avg);
 		rdc = h->d_rdc_avg;
 	}
-	if (h->chan_per > 0)  // channels: the NCO mixer in rotate16_neg90's place, the source's row in the stream's
-		channel::k_channel_mix<<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S, h->chan_per,
-		                                                                               h->d_chan_steps, h->d_chan_table,
-		                                                                               (uint32_t)h->chan_pos, h->bufA, h->xstride);
+	if (h->chan_per > 0 && h->opt.source_dc) {  // ... behind option source_dc's pre-pass (no filter, no bank here: no history)
+		if ((r = launch_source_dc(h, d_iq, stream_stride, nblocks, sin, sout, false)) < 0) return r;
+		channel::k_channel_mix<true><<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S, h->chan_per,
+		                                                                                  h->d_chan_steps, h->d_chan_table,
+		                                                                                  (uint32_t)h->chan_pos, h->bufA, h->xstride, h->d_sdc,
+		                                                                                  h->sdc_stride, channel::kDcHist);
+	} else if (h->chan_per > 0)  // channels: the NCO mixer in rotate16_neg90's place, the source's row in the stream's
+		channel::k_channel_mix<false><<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S, h->chan_per,
+		                                                                                      h->d_chan_steps, h->d_chan_table,
+		                                                                                      (uint32_t)h->chan_pos, h->bufA, h->xstride, nullptr, 0, 0);
 	else
 		k_convert<<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S,
 		                                                                  h->bufA, h->xstride,
@@ -2314,8 +2409,14 @@ static int launch_channel_boxcar(rtlfm_gpu *h, const ChanRun &cr)
 	channel::plan(h->nstreams, p.f.ntiles, cr.D, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs, &p.f.tiles_per_seg);
 	const size_t grid = (size_t)cr.nsrc * p.f.segs * p.groups;
 	if (grid > 0x7fffffffu) return -E2BIG;
-	if (cr.D >= channel::kStageMinD) channel::k_channel_boxcar<true><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
-	else channel::k_channel_boxcar<false><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+	if (h->opt.source_dc) {
+		p.dc = h->d_sdc; p.dc_stride = h->sdc_stride;
+		if (cr.D >= channel::kStageMinD) channel::k_channel_boxcar<true, true><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+		else channel::k_channel_boxcar<false, true><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+		return 0;
+	}
+	if (cr.D >= channel::kStageMinD) channel::k_channel_boxcar<true, false><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+	else channel::k_channel_boxcar<false, false><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
 	return 0;
 }
 
@@ -2338,19 +2439,35 @@ static int launch_channel_fir(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		channel::plan(S, p.f.ntiles, 1, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs, &p.f.tiles_per_seg);
 		const size_t grid = (size_t)cr.nsrc * p.f.segs * p.groups;
 		if (grid > 0x7fffffffu) return -E2BIG;
-		chanfir::k_channel_fir<<<(unsigned)grid, chanfir::kWaves * 64, chanfir::lds_bytes(h->fir_ntaps), q>>>(p);
+		if (h->opt.source_dc) {
+			p.dc = h->d_sdc; p.dc_stride = h->sdc_stride; p.dc_entries = channel::kDcHist + cr.Tin / channel::kDcPiece;
+			chanfir::k_channel_fir<true><<<(unsigned)grid, chanfir::kWaves * 64, chanfir::lds_bytes(h->fir_ntaps) + chanfir::kDcLds, q>>>(p);
+			return 0;
+		}
+		chanfir::k_channel_fir<false><<<(unsigned)grid, chanfir::kWaves * 64, chanfir::lds_bytes(h->fir_ntaps), q>>>(p);
 		return 0;
 	}
 	constexpr int halo = chanfir::kHaloMax;
 	int r = ensure_chan_fir_x(h);
 	if (r < 0) return r;
+	if (h->opt.source_dc) {
+		// (the history's last `halo` samples are the list's entries kDcHist - halo / 256 ... kDcHist - 1)
+		channel::k_channel_mix<true><<<grid_for((size_t)S * (halo / 8)), 256, 0, q>>>(
+			cr.hist_in + (size_t)(channel::kHist - halo) * 2, (size_t)channel::kHist * 2, (uint32_t)halo * 2, 1, S, h->chan_per, h->d_chan_steps,
+			h->d_chan_table, (uint32_t)h->chan_pos - (uint32_t)halo, h->chan_fir_x, h->chan_fir_xstride, h->d_sdc, h->sdc_stride,
+			channel::kDcHist - halo / channel::kDcPiece);
+		channel::k_channel_mix<true><<<grid_for((size_t)S * cr.nblocks * (h->cfg.block_len / 16)), 256, 0, q>>>(
+			cr.f.iq, cr.f.src_stride, h->cfg.block_len, cr.nblocks, S, h->chan_per, h->d_chan_steps, h->d_chan_table, (uint32_t)h->chan_pos,
+			h->chan_fir_x + halo, h->chan_fir_xstride, h->d_sdc, h->sdc_stride, channel::kDcHist);
+	} else {
 	// (the history's last `halo` samples: rows channel::kHist * 2 bytes apart, one buffer of halo * 2 bytes each)
-	channel::k_channel_mix<<<grid_for((size_t)S * (halo / 8)), 256, 0, q>>>(
+	channel::k_channel_mix<false><<<grid_for((size_t)S * (halo / 8)), 256, 0, q>>>(
 		cr.hist_in + (size_t)(channel::kHist - halo) * 2, (size_t)channel::kHist * 2, (uint32_t)halo * 2, 1, S, h->chan_per, h->d_chan_steps,
-		h->d_chan_table, (uint32_t)h->chan_pos - (uint32_t)halo, h->chan_fir_x, h->chan_fir_xstride);
-	channel::k_channel_mix<<<grid_for((size_t)S * cr.nblocks * (h->cfg.block_len / 16)), 256, 0, q>>>(
+		h->d_chan_table, (uint32_t)h->chan_pos - (uint32_t)halo, h->chan_fir_x, h->chan_fir_xstride, nullptr, 0, 0);
+	channel::k_channel_mix<false><<<grid_for((size_t)S * cr.nblocks * (h->cfg.block_len / 16)), 256, 0, q>>>(
 		cr.f.iq, cr.f.src_stride, h->cfg.block_len, cr.nblocks, S, h->chan_per, h->d_chan_steps, h->d_chan_table, (uint32_t)h->chan_pos,
-		h->chan_fir_x + halo, h->chan_fir_xstride);
+		h->chan_fir_x + halo, h->chan_fir_xstride, nullptr, 0, 0);
+	}
 	chanfir::k_channel_fir_plain<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->chan_fir_x, h->chan_fir_xstride, S, cr.Tin, cr.D,
 	                                                                          h->d_fir_taps, h->fir_ntaps, h->fir_shift, cr.maxout, h->chan_iq,
 	                                                                          h->chan_stride, cr.dcnt, cr.sin, cr.sout);
@@ -2382,14 +2499,18 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		              &p.f.tiles_per_seg);
 		const size_t grid = (size_t)cr.nsrc * p.f.segs;
 		if (grid > 0x7fffffffu) return -E2BIG;
+		const bool dc = h->opt.source_dc != 0;
+		if (dc) { p.dc = h->d_sdc; p.dc_stride = h->sdc_stride; }
 		if (sv < 0) {
-			chanbank::k_channel_bank<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+			if (dc) chanbank::k_channel_bank_dc<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+			else chanbank::k_channel_bank<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
 			return 0;
 		}
 		const size_t need = (grid << h->bank_m);
 		OWN_TRY(h->sv.d_partial.grow(need, q));  // (waits for what reads it)
 		p.survey = h->sv.d_partial;
-		chanbank::k_channel_bank_survey<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+		if (dc) chanbank::k_channel_bank_survey_dc<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
+		else chanbank::k_channel_bank_survey<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
 		chanbank::k_bank_survey_reduce<<<grid_for((size_t)cr.nsrc << h->bank_m), 256, 0, q>>>(h->sv.d_partial, p.f.segs, h->bank_m, cr.nsrc,
 		                                                                                   h->chan_per, cr.Tin, cr.D, cr.sin, h->sv.d_power[sv],
 		                                                                                   h->sv.d_frames[sv]);
@@ -2398,9 +2519,14 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 	const size_t vneed = ((size_t)cr.nsrc * cr.maxout) << h->bank_m;
 	int r = ensure_bank_v(h, vneed);
 	if (r < 0) return r;
-	chanbank::k_bank_sums<<<grid_for(vneed), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
-	                                                     h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.Tin, cr.D, cr.maxout,
-	                                                     cr.sin, h->bank_v);
+	if (h->opt.source_dc)
+		chanbank::k_bank_sums<true><<<grid_for(vneed), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
+		                                                        h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.Tin, cr.D,
+		                                                        cr.maxout, cr.sin, h->bank_v, h->d_sdc, h->sdc_stride);
+	else
+		chanbank::k_bank_sums<false><<<grid_for(vneed), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
+		                                                            h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.Tin, cr.D,
+		                                                            cr.maxout, cr.sin, h->bank_v, nullptr, 0);
 	chanbank::k_bank_fft<<<grid_for((size_t)cr.nsrc * cr.maxout), 256, 0, q>>>(h->bank_v, h->d_bank_sine, h->bank_m, cr.nsrc, h->chan_per, cr.Tin,
 	                                                                          cr.D, cr.maxout, cr.sin);
 	chanbank::k_bank_scatter<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->bank_v, bins, (size_t)bins_stride, h->bank_m, S, h->chan_per, cr.Tin,
@@ -2425,12 +2551,34 @@ static int run_channels(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size
 	if (r < 0) return r;
 	std::pair<Event, Event> ev;
 	if ((r = timing_begin(h, ev)) < 0) return r;
+	if (h->opt.source_dc && (r = launch_source_dc(h, d_iq, stream_stride, nblocks, cr.sin, cr.sout, bank || fir)) < 0) return r;
 	r = bank ? launch_channel_bank(h, fused_path, cr) : fir ? launch_channel_fir(h, fused_path, cr) : launch_channel_boxcar(h, cr);
 	if (r < 0) return r;
 	if ((r = timing_end(h, ev)) < 0) return r;
 	const int32_t *cnt = cr.varcnt ? cr.dcnt : nullptr;
 	if (cr.raw_direct) return raw_out_len(h, d_out_len, cnt, cr.T);
 	return run_back_half(h, h->chan_iq, h->chan_stride, cr.T, cr.N0, cr.D, nblocks, cnt, cr.tp, d_out, out_stride, d_out_len);
+}
+
+// Option source_dc's pre-pass alone, as one timed pair (tools/source_dc_bench.py): the sums and the smoothing over d_iq's
+// source rows, into the handle's list.  Nothing a run carries moves: the records it writes are the next copy's, which every
+// run overwrites first, and no history is read or written.
+extern "C" int rtlfm_gpu_source_dc_prepass(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks)
+{
+	if (!h || !d_iq || nblocks < 1) return -EINVAL;
+	if (nblocks > h->cap_blocks) return -E2BIG;
+	if (((uintptr_t)d_iq & 15) || (stream_stride & 15) || stream_stride < (size_t)nblocks * h->cfg.block_len) return -EINVAL;
+	if (!h->opt.source_dc || h->chan_per <= 0) return -ENOTSUP;
+	if (ingest_busy(h)) return -EBUSY;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));  // (the next state copy may still be an audio tail's)
+	std::pair<Event, Event> ev;
+	int r = timing_begin(h, ev);
+	if (r < 0) return r;
+	if ((r = launch_source_dc(h, d_iq, stream_stride, nblocks, h->st[h->st_cur], h->st[(h->st_cur + 1) % 3], false)) < 0) return r;
+	if ((r = timing_end(h, ev)) < 0) return r;
+	HIP_TRY(hipGetLastError());
+	return 0;
 }
 
 static int ensure_input_stats(rtlfm_gpu *h)

@@ -21,7 +21,8 @@ class GpuDemod:
     """``nstreams`` independent rtl_fm demodulators sharing one configuration."""
 
     def __init__(self, cfg: RtlfmCfg, nstreams: int = 1, device: int = 0, lib_path: str | None = None,
-                 options: dict | None = None, squelch_gate: bool | None = None, conseq_squelch: int | None = None):
+                 options: dict | None = None, squelch_gate: bool | None = None, conseq_squelch: int | None = None,
+                 source_dc: bool | None = None):
         self.lib = capi.load(lib_path)  # lib_path: another build of the library (A/B measurements)
         self.cfg = cfg
         self.nstreams = nstreams
@@ -37,6 +38,9 @@ class GpuDemod:
             self.set_option("conseq_squelch", conseq_squelch)
         if squelch_gate is not None:
             self.set_option("squelch_gate", int(bool(squelch_gate)))
+        # the raw DC block per source in front of the channel front ends (include/rtlfm_hip.h, option source_dc)
+        if source_dc is not None:
+            self.set_option("source_dc", int(bool(source_dc)))
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
