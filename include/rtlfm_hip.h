@@ -141,8 +141,9 @@ int rtlfm_result_len(const rtlfm_cfg *cfg);
 /* Upper bound of output samples per block (always defined). */
 int rtlfm_result_cap(const rtlfm_cfg *cfg);
 
-/* What rtlfm_gpu_create() accepts, without a GPU: 0, or the error it would return (-EINVAL, or -EDOM
- * where the reference itself leaves its domain: see rtlfm_gpu_strerror). */
+/* What rtlfm_gpu_create() accepts, without a GPU: 0, or the error it would return (-EINVAL; -EDOM
+ * where the reference itself leaves its domain: see rtlfm_gpu_strerror; -E2BIG where max_blocks buffers of block_len
+ * bytes are more than 2^31 - 1 complex samples per stream - a run is counted in int). */
 int rtlfm_cfg_validate(const rtlfm_cfg *cfg);
 
 /* ---- the GPU layer ------------------------------------------------------ */
@@ -783,6 +784,9 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        run was not packed or rtlfm_gpu_timing_enable was off
  *   verify_runs         runs executed under verify_twice so far, and
  *   verify_mismatches    ... how many of them differed between their two executions
+ *   last_route           which front end the last run took, one of enum rtlfm_route below (0 before the first run; over the ring,
+ *                        the last view's of a run with short buffers), and
+ *   last_rest            ... what followed it, one of enum rtlfm_rest: the plan rtlfm_run_route() names for that run
  *   block_len            the buffer length the handle was created with
  *   ring_apart           1 / 0: the result buffers behind rtlfm_gpu_push() / _run() are / are not a quarter of the HBM
  *                        away from the ring's device input; -1 before the ring exists (it is built by the first push)
@@ -814,10 +818,72 @@ int rtlfm_gpu_get_option(rtlfm_gpu *h, const char *name, long *value);
 /* 0 = automatic, 1 = staged reference kernels, 2 = fused streaming kernel
  * (fails with -ENOTSUP at run time when the configuration has no fused
  * form); 3 / 4 = fused with the first decimation pass forced onto v_dot4 /
- * onto the int8 MFMA pipe (2 takes the compiled default).  For tests and A/B measurement. */
+ * onto the int8 MFMA pipe (2 takes the compiled default).  For tests and A/B measurement.
+ * Which kernels each value leads to for a given configuration: the route table of DESIGN.md 4.6a, rtlfm_run_route below. */
 int rtlfm_gpu_set_path(rtlfm_gpu *h, int path);
-/* Which path the last run took (1 or 2). */
+/* Which path the last run took (1 or 2): 2 where a one-launch front end ran, 1 where the staged kernels decimated.  The
+ * read-only options "last_route" and "last_rest" say which front end and what followed it (enum rtlfm_route / rtlfm_rest). */
 int rtlfm_gpu_last_path(rtlfm_gpu *h);
+
+/*
+ * A run's plan.  rtlfm_gpu_run_device() decides everything it can before its first launch - which front end, what
+ * follows it, where the carried state is copied - from the configuration, the buffer count, a handful of options and the
+ * alignment of the caller's rows, and from nothing else; rtlfm_run_route() makes the same plan without a handle and
+ * without a GPU.  What "last_route" reads (0 before the first run):
+ */
+enum rtlfm_route {
+	RTLFM_ROUTE_STAGED = 1,           /* k_convert, a kernel per pass (k_fifth ... / k_boxcar), the staged back half */
+	RTLFM_ROUTE_FUSED = 2,            /* k_fused from the bytes to the PCM */
+	RTLFM_ROUTE_FUSED_EMIT = 3,       /* k_fused leaves the decimated IQ (of the first six passes at most) */
+	RTLFM_ROUTE_BOXCAR = 4,           /* k_boxcar_scan from the bytes to the PCM */
+	RTLFM_ROUTE_BOXCAR_EMIT = 5,      /* k_boxcar_scan leaves the decimated IQ */
+	RTLFM_ROUTE_CHAN_MIX = 6,         /* channels: k_channel_mix, then as RTLFM_ROUTE_STAGED */
+	RTLFM_ROUTE_CHAN_BOXCAR = 7,      /* channels: k_channel_boxcar */
+	RTLFM_ROUTE_CHAN_FIR = 8,         /* channels, a filter set: k_channel_fir */
+	RTLFM_ROUTE_CHAN_FIR_PLAIN = 9,   /* ... its cross-check: k_channel_mix x 2, k_channel_fir_plain, k_source_history */
+	RTLFM_ROUTE_CHAN_BANK = 10,       /* channels, a bank set: k_channel_bank */
+	RTLFM_ROUTE_CHAN_BANK_PLAIN = 11  /* ... its cross-check: k_bank_sums, k_bank_fft, k_bank_scatter, k_source_history */
+};
+/* What follows the front end ("last_rest"). */
+enum rtlfm_rest {
+	RTLFM_REST_NONE = 0,        /* nothing: -M raw without a squelch, the front end wrote the caller's rows (and their lengths follow) */
+	RTLFM_REST_DEEP_DEMOD = 1,  /* k_deep_rest: passes 6 .., generic_fir and the demodulator in one launch; the audio tail */
+	RTLFM_REST_DEEP_IQ = 2,     /* k_deep_rest without the demodulator (a squelch, -L, -M raw); the back half */
+	RTLFM_REST_PER_PASS = 3,    /* a k_fifth per pass beyond the sixth, k_fir9; the back half */
+	RTLFM_REST_IRREGULAR = 4,   /* buffers the passes do not divide: k_fifth up to the first such pass, k_fifth_irregular; the audio tail */
+	RTLFM_REST_BACK_HALF = 5,   /* the back half: k_squelch_*, k_fm_demod / k_simple_demod, the audio tail */
+	RTLFM_REST_TAIL = 6         /* the front end demodulated: k_squelch_apply where it took rms()'s sums, the audio tail */
+};
+enum rtlfm_channels_kind { RTLFM_CHANNELS_OFF = 0, RTLFM_CHANNELS_MIXER = 1, RTLFM_CHANNELS_FILTER = 2, RTLFM_CHANNELS_BANK = 3 };
+/* What of a handle steers a run besides its configuration: rtlfm_gpu_set_path's 0 / 1 / 2, the options of these names, the
+ * flag of the ring's views of short buffers (they keep to the sequential deemph_filter), and what channels are on.  A
+ * fresh handle's values are 0, -1, 1, 1, 0, 0, -1, 0, 0. */
+typedef struct rtlfm_route_opts {
+	int32_t path, pass0_engine, squelch_fused, deep_rest, deemph_four_pass, deemph_sequential, arb_serial, no_deemph_scan, channels;
+} rtlfm_route_opts;
+typedef struct rtlfm_route_plan {
+	int32_t route, rest;         /* enum rtlfm_route, enum rtlfm_rest */
+	int32_t last_path;           /* what rtlfm_gpu_last_path() says afterwards */
+	int32_t sq_front;            /* 1: the front end takes rms()'s sums and k_squelch_apply follows it */
+	int32_t copy_state;          /* 1: the carried record is copied to the next one in front of the launches (else the front end does) */
+	int32_t tail_follows;        /* 1: the front end is cut into segments for a launch that kernels follow */
+	int32_t tail;                /* the audio tail's stages: 1 low_pass_simple, 2 deemph_filter, 4 dc_block_audio, 8 low_pass_real,
+	                                16 arbitrary_resample, 32 deemph_filter as the out-of-place one-pass kernel */
+	int32_t N0, Nblk, D, T;      /* complex samples per buffer; buffer b owns the outputs of Nblk inputs through a boxcar D
+	                                (fifth_order passes: Nblk outputs, D = 1); outputs of a stream's run (varcnt: at most) */
+	int32_t varcnt;              /* 1: the boxcar does not divide a buffer, per-stream counts */
+	int32_t level, first_irr;    /* passes the fused front end runs; the first pass handed a length it does not divide (none: the pass count) */
+} rtlfm_route_plan;
+/*
+ * The plan of a run of `nblocks` buffers on a handle of `nstreams` streams into rows whose first address has the low
+ * four bits `out_low_bits` and which lie `out_stride` int16 apart.  opts == NULL: a fresh handle's values.  *plan (may be
+ * NULL) is written whenever a route is returned.  Returns the route; -ENOTSUP where rtlfm_gpu_set_path(2) has no fused
+ * form to take (and for channels in a state their setters refuse); the error of rtlfm_cfg_validate(); -EINVAL / -E2BIG
+ * for arguments rtlfm_gpu_run_device() refuses.  The options that shape launches (fused_waves, fused_min_tiles,
+ * fused_tiles_per_seg, box_store, fused_store, lpr_*, arb_waves) are no inputs: they cannot change a route.
+ */
+int rtlfm_run_route(const rtlfm_cfg *cfg, int nstreams, int nblocks, unsigned out_low_bits, size_t out_stride,
+                    const rtlfm_route_opts *opts, rtlfm_route_plan *plan);
 
 /*
  * HIP-event timing of the decimating front-end kernel (the dominant kernel)

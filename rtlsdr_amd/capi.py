@@ -293,6 +293,40 @@ class RtlpowerCfg(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RtlfmRouteOpts(C.Structure):
+    """``rtlfm_route_opts`` - what of a handle steers a run's plan besides its configuration, with a fresh handle's values."""
+
+    _fields_ = [("path", C.c_int32), ("pass0_engine", C.c_int32), ("squelch_fused", C.c_int32), ("deep_rest", C.c_int32),
+                ("deemph_four_pass", C.c_int32), ("deemph_sequential", C.c_int32), ("arb_serial", C.c_int32),
+                ("no_deemph_scan", C.c_int32), ("channels", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw) -> "RtlfmRouteOpts":
+        o = cls(path=0, pass0_engine=-1, squelch_fused=1, deep_rest=1, deemph_four_pass=0, deemph_sequential=0, arb_serial=-1,
+                no_deemph_scan=0, channels=0)
+        for k, v in kw.items():
+            if not hasattr(o, k):
+                raise AttributeError(k)
+            setattr(o, k, v)
+        return o
+
+
+class RtlfmRoutePlan(C.Structure):
+    """``rtlfm_route_plan`` - a run's plan as rtlfm_run_route writes it."""
+
+    _fields_ = [(n, C.c_int32) for n in ("route", "rest", "last_path", "sq_front", "copy_state", "tail_follows", "tail", "N0", "Nblk", "D",
+                                         "T", "varcnt", "level", "first_irr")]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# enum rtlfm_route / rtlfm_rest / rtlfm_channels_kind (include/rtlfm_hip.h)
+(ROUTE_STAGED, ROUTE_FUSED, ROUTE_FUSED_EMIT, ROUTE_BOXCAR, ROUTE_BOXCAR_EMIT, ROUTE_CHAN_MIX, ROUTE_CHAN_BOXCAR, ROUTE_CHAN_FIR,
+ ROUTE_CHAN_FIR_PLAIN, ROUTE_CHAN_BANK, ROUTE_CHAN_BANK_PLAIN) = range(1, 12)
+REST_NONE, REST_DEEP_DEMOD, REST_DEEP_IQ, REST_PER_PASS, REST_IRREGULAR, REST_BACK_HALF, REST_TAIL = range(7)
+CHANNELS_OFF, CHANNELS_MIXER, CHANNELS_FILTER, CHANNELS_BANK = range(4)
+
 # Every symbol include/rtlfm_hip.h declares: (name, restype, argtypes)
 _P = C.POINTER
 _SIGNATURES = [
@@ -369,6 +403,7 @@ _SIGNATURES = [
     ("rtlfm_gpu_release_to", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rtlfm_gpu_set_path", C.c_int, [C.c_void_p, C.c_int]),
     ("rtlfm_gpu_last_path", C.c_int, [C.c_void_p]),
+    ("rtlfm_run_route", C.c_int, [_P(RtlfmCfg), C.c_int, C.c_int, C.c_uint, C.c_size_t, _P(RtlfmRouteOpts), _P(RtlfmRoutePlan)]),
     ("rtlfm_gpu_timing_enable", C.c_int, [C.c_void_p, C.c_int]),
     ("rtlfm_gpu_timing_read", C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_int)]),
     ("rtlfm_gpu_clock_probe", C.c_int, [C.c_void_p, C.c_int]),
@@ -559,8 +594,8 @@ def load(path: str | None = None) -> C.CDLL:
     lib = C.CDLL(p)
     for name, res, args in (_SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES + _SNAPSHOT_SIGNATURES
                             + _SLOTS_SIGNATURES):
-        if path is not None and not hasattr(lib, name):
-            continue  # an explicitly named other build (A/B against an earlier revision) may predate a symbol
+        if p != LIB_PATH and not hasattr(lib, name):
+            continue  # an explicitly named other build (`path` or RTLFM_HIP_LIB: A/B against an earlier revision) may predate a symbol
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

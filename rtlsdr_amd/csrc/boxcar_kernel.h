@@ -786,54 +786,7 @@ __global__ void __launch_bounds__(64) k_boxcar_partial32(const Params p)
 	p.sout[s].now_j = aj;
 }
 
-// the decimator itself: what both forms of the launch need
-inline bool supported_front(const rtlfm_cfg &c)
-{
-	// at least two outputs per 4096-sample tile: a wave that starts mid-stream takes its first
-	// "previous output" from its warm-up tile
-	// (downsample == 1, rtl_fm -s 1.2M: low_pass() hands every sample on - 4096 outputs per tile, the same kernel)
-	// (beyond /2047 - rtl_fm -s 400 - a tile completes two outputs at most and a mid-stream wave could not warm up on one
-	// tile: those runs take ONE wave per stream, launch(); round 6)
-	if (c.downsample_passes != 0 || c.downsample < 1) return false;
-	if (c.comp_fir_size) return false;
-	// -E rdc: any buffer size (round 6: a tile of buffers shorter than itself looks its averages up in a table in LDS);
-	// with the rotation the constant sums to zero over every four samples, with offset tuning - no rotation - it adds up
-	// linearly: one packed multiply-add per look-up
-	return true;  // else any buffer length (a multiple of 512 bytes): the run is one continuous sample stream here
-}
-
-// one launch from the bytes to the PCM
-inline bool supported(const rtlfm_cfg &c)
-{
-	if (c.mode != RTLFM_MODE_FM && c.mode != RTLFM_MODE_AM && c.mode != RTLFM_MODE_USB && c.mode != RTLFM_MODE_LSB)
-		return false;
-	if (c.squelch_level || c.report_levels) return false;
-	return supported_front(c);
-}
-
-// the power squelch / -L with the sums taken by the front end itself (SQ kernels) and k_squelch_apply behind it: one launch
-// over the input + a small one over the PCM, no emit mode.  Buffers of at least 8192 samples (a tile's outputs then
-// belong to two buffers at most); -M raw keeps the emit mode (the samples themselves are the output).
-inline bool supported_sq(const rtlfm_cfg &c)
-{
-	if (c.mode != RTLFM_MODE_FM && c.mode != RTLFM_MODE_AM && c.mode != RTLFM_MODE_USB && c.mode != RTLFM_MODE_LSB)
-		return false;
-	if (!c.squelch_level && !c.report_levels) return false;
-	if (c.block_len < 16384) return false;
-	// rms() looks at every step-th element once a buffer holds more than 32768 of them (src/rtl_fm.c:1090-1092): the sums
-	// taken here are over all of them
-	if (c.downsample < 1 || 2 * ((int)(c.block_len / 2) / c.downsample + 1) > 32768) return false;
-	return supported_front(c);
-}
-
-// emit mode: the launch stores the decimated IQ, and the squelch (src/rtl_fm.c:1204-1215), the -L levels
-// (:1217-1237) and mode_demod incl. -M raw (:1006-1009, 1256-1259) follow on 1 / D of the data
-inline bool supported_emit(const rtlfm_cfg &c)
-{
-	if (!supported_front(c)) return false;
-	return c.mode == RTLFM_MODE_RAW || c.squelch_level != 0 || c.report_levels != 0;
-}
-
+// (what each form of the launch covers - supported_front(), supported(), supported_sq(), supported_emit(): run_plan.h)
 inline int launch(fused::Workspace &ws, const rtlfm_cfg &c, int nstreams, const uint8_t *d_iq, size_t stream_stride,
                   int nblocks, int16_t *d_out, size_t out_stride, int32_t *d_cnt, const state_t *sin, state_t *sout,
                   hipStream_t q, uint32_t *emit_iq = nullptr, size_t emit_iq_stride = 0, const int2 *rdc_avg = nullptr,

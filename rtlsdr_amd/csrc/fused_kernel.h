@@ -44,17 +44,15 @@
 
 #include "dsp_device.h"
 #include "device_own.h"
+#include "run_plan.h"
 
 namespace rtlfm {
 namespace fused {
 
 using state_t = rtlfm_stream_state;
 
-constexpr int kLaneSamples = 64;
-constexpr int kTileSamples = 64 * kLaneSamples;  // 4096
-constexpr int kTileBytes = 2 * kTileSamples;     // 8192
+// (kLaneSamples, kTileSamples, kTileBytes, kMaxP: run_plan.h)
 constexpr int kPre = 16;                         // prefix entries of a linear ring
-constexpr int kMaxP = 6;
 constexpr int kMaxSegList = 128;
 
 #ifdef RTLFM_FUSED_MARKS  // analysis builds only: section markers in the .s
@@ -595,9 +593,7 @@ constexpr bool dpp_vgpr_carry()
 // lane-derived LDS addresses per tile - were built and measured with the wave count matched to the 4864
 // slots, tools/ab_engines.py --waves: no faster than four, and the recomputation costs 2-3 % with four.
 // DESIGN.md section 4.2a.)
-#ifndef RTLFM_PASS0_DEFAULT
-#define RTLFM_PASS0_DEFAULT 1  // 0: always v_dot4 on the VALU, 1: int8 MFMA where it is faster (RTLFM_PASS0=valu|mfma overrides)
-#endif
+// (RTLFM_PASS0_DEFAULT: run_plan.h)
 // Where the MFMA variant issues the next tile's loads: 0 = after the MFMA phase, 1 = after
 // pass 0's read-back and the deferred PCM store, 2 = after pass 1 (P >= 2 only).
 #ifndef RTLFM_MFMA_RELOAD_AT
@@ -1373,7 +1369,7 @@ struct Workspace {
 	const unsigned long long *stamp_half(int back) const { return stamps + (size_t)((stamp_seq + 1 + back) & 1) * stamp_waves() * 4; }
 	DevBuf<uint32_t> mfma_taps[2];                // [rotate]
 	DevBuf<uint8_t> dummy_tile;
-	int pass0_engine = -1;                        // 0 = v_dot4 (VALU), 1 = int8 MFMA; -1 = the compiled default (see launch)
+	int pass0_engine = plan::kRouteDefaults.pass0_engine;  // 0 = v_dot4 (VALU), 1 = int8 MFMA; -1 = the compiled default (see launch)
 	bool want_stamps = false;                     // rtlfm_gpu_clock_probe(): every wave leaves its clock stamps
 	// segmentation (rtlfm_gpu_set_option: fused_waves, fused_min_tiles, fused_tiles_per_seg)
 	int target_waves = 8192;                      // enough waves to fill the 4096 wave slots of 256 CUs twice
@@ -1389,7 +1385,7 @@ struct Workspace {
 	// 32768 / 40960, two alternations on one box; wbfm still 20480 (1.40 against 1.42-1.46 either side).
 	// 0 = as target_waves_tail (set together with it by fused_waves).
 	int target_waves_tail_fifth = 24576;
-	bool tail_follows = false;                    // set by the host per run (rtlfm_hip.hip: plan_tail)
+	bool tail_follows = false;                    // set by the host per run (run_plan.h: RunPlan::tail_follows)
 	int min_tiles = 8;                            // a segment pays one warm-up tile: at most 1/8 on top
 	bool plan_by_caller = false;                  // fused_waves / fused_min_tiles were set: the planner's own rules of thumb stand back
 	int tiles_per_seg = 0;                        // > 0: exactly this (tests)
@@ -1471,34 +1467,9 @@ inline SegPlan plan_segments(const Workspace &ws, int nstreams, int total_tiles,
 	return sp;
 }
 
-// the pass-0 engine a launch will use: the handle's choice, else the compiled default
-inline int effective_engine(const Workspace &ws)
-{
-	return ws.pass0_engine >= 0 ? ws.pass0_engine : (RTLFM_PASS0_DEFAULT ? 1 : 0);
-}
-
-// What the front end in emit mode plus staged kernels covers beyond supported(): 7..10 passes,
-// -M raw, and the squelch (rtlfm_hip.hip: run_fused_emit)
-// buffers that are not whole 8 KiB tiles (-W n) take the partial-tile kernels: MFMA engine
-inline bool needs_partial_tiles(const rtlfm_cfg &c) { return (c.block_len % kTileBytes) != 0; }
-
-inline bool supported_emit(const rtlfm_cfg &c)
-{
-	if (c.downsample_passes < 1 || c.downsample_passes > RTLFM_MAX_PASSES) return false;
-	return c.downsample_passes > kMaxP || c.mode == RTLFM_MODE_RAW || c.squelch_level != 0 || c.report_levels != 0;
-}
-
-// the power squelch / -L with rms()'s sums taken by the front end itself and k_squelch_apply behind it (as
-// boxfused::supported_sq): up to six passes, at most 32768 decimated elements per buffer (beyond that rms() looks at
-// every step-th element only, src/rtl_fm.c:1090-1092)
-inline bool supported_sq(const rtlfm_cfg &c)
-{
-	if (c.mode != RTLFM_MODE_FM && c.mode != RTLFM_MODE_AM && c.mode != RTLFM_MODE_USB && c.mode != RTLFM_MODE_LSB)
-		return false;
-	if (!c.squelch_level && !c.report_levels) return false;
-	if (c.downsample_passes < 1 || c.downsample_passes > kMaxP) return false;
-	return (c.block_len >> c.downsample_passes) <= 32768;
-}
+// the pass-0 engine a launch will use (run_plan.h, which also holds what each form of the launch covers: supported(),
+// supported_sq(), supported_emit(), needs_partial_tiles())
+inline int effective_engine(const Workspace &ws) { return effective_engine(ws.pass0_engine); }
 
 inline int ensure_dummy_tile(Workspace &ws)
 {
@@ -1533,17 +1504,6 @@ inline int stamps_for(Workspace &ws, int waves, hipStream_t q, unsigned long lon
 	ws.stamp_seq++;
 	ws.stamp_last = waves;
 	return 0;
-}
-
-inline bool supported(const rtlfm_cfg &c, int nblocks)
-{
-	if (c.mode != RTLFM_MODE_FM && c.mode != RTLFM_MODE_AM && c.mode != RTLFM_MODE_USB && c.mode != RTLFM_MODE_LSB)
-		return false;
-	if (c.downsample_passes < 1 || c.downsample_passes > kMaxP) return false;
-	if (c.squelch_level || c.report_levels) return false;
-	(void)nblocks;
-	// -E rdc: the RDC instantiations; -W n: the PT ones (both MFMA pass 0 only; rtlfm_hip.hip checks the engine)
-	return true;
 }
 
 template <int P, bool FIR9>

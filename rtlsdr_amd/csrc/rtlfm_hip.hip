@@ -25,6 +25,7 @@
 #include "device_own.h"
 #include "debug_poison.h"
 #include "stream_pool.h"
+#include "run_plan.h"
 #include "staged_kernels.h"
 #include "fused_kernel.h"
 #include "boxcar_kernel.h"
@@ -39,6 +40,7 @@
 #include "../../include/rtlfm_snapshot.h"
 
 using namespace rtlfm;
+using namespace rtlfm::plan;
 
 #define HIP_TRY(expr)                                                              \
 	do {                                                                           \
@@ -57,7 +59,8 @@ struct rtlfm_gpu {
 	hipStream_t own_stream = nullptr;
 	hipStream_t stream = nullptr;
 	Event ev_wait, ev_release;  // rtlfm_gpu_wait_for / _release_to
-	int path = 0, last_path = 0;
+	int path = kRouteDefaults.path, last_path = 0;
+	int last_route = 0, last_rest = 0;  // options "last_route" / "last_rest" (read-only): the plan the last run took (run_plan.h)
 
 	// geometry
 	size_t xstride = 0;   // dwords per stream in a work buffer
@@ -184,14 +187,15 @@ struct rtlfm_gpu {
 		size_t walked_peak = 0;         // most a search held in temporary allocations (bytes)
 	} place;
 	fused::Workspace fws;
-	// A/B switches (rtlfm_gpu_set_option); none of them changes a result
+	// A/B switches (rtlfm_gpu_set_option); none of them changes a result.  (Those that steer a run's plan start at
+	// kRouteDefaults' values, run_plan.h: rtlfm_run_route without options plans as a fresh handle runs.)
 	struct Options {
-		int deemph_sequential = 0, deemph_four_pass = 0, lpr_separate = 0, lpr_scalar_stores = 0, tail_sync = 0;
+		int deemph_sequential = kRouteDefaults.deemph_sequential, deemph_four_pass = kRouteDefaults.deemph_four_pass, lpr_separate = 0, lpr_scalar_stores = 0, tail_sync = 0;
 		int lpr_chunk = 5440;  // samples per lane of the one-pass deemph + low_pass_real kernel (round 5: 2720 -> 5440 with the outputs leaving through LDS)
-		int deep_rest = 1;     // 0: the passes beyond six, generic_fir and the demodulator as a launch each (round 4) instead of k_deep_rest
-		int squelch_fused = 1; // 0: the squelch / -L behind the boxcar through the emit mode and k_squelch_rms / _hits / _zero / k_fm_demod (round 4) also where the front end can take rms()'s sums itself
+		int deep_rest = kRouteDefaults.deep_rest;  // 0: the passes beyond six, generic_fir and the demodulator as a launch each (round 4) instead of k_deep_rest
+		int squelch_fused = kRouteDefaults.squelch_fused;  // 0: the squelch / -L behind the boxcar through the emit mode and k_squelch_rms / _hits / _zero / k_fm_demod (round 4) also where the front end can take rms()'s sums itself
 		int lpr_ring = 1;      // 0: the one-pass deemph + low_pass_real kernel's outputs leave in 16-byte groups from registers (round 3) instead of 64-byte pieces from LDS
-		int arb_serial = -1;   // deemph + arbitrary_upsample behind the front end on ITS stream: -1 = from 2048 streams on, 0 never, 1 always
+		int arb_serial = kRouteDefaults.arb_serial;  // deemph + arbitrary_upsample behind the front end on ITS stream: -1 = from 2048 streams on, 0 never, 1 always
 		int lpr_threads = 256; // lanes per workgroup of k_deemph_spec_lpr: 64, 128, 192 or 256
 		int arb_waves = 0;     // waves per stream of k_deemph_spec_arb: 0 = about 16384 waves in all, else 1 .. 8
 		int verify_inject = 0; // tests: the shadow execution's first sample of stream 0 is overwritten before the comparison (it must be noticed)
@@ -269,23 +273,7 @@ extern "C" int32_t rtlfm_deemph_a(int32_t rate_out, int32_t tc_us)
 	return (int32_t)round(1.0 / (1.0 - exp(-1.0 / (rate_out * tc))));
 }
 
-// the first fifth_order pass that is handed a length which is not a multiple of four elements (src/rtl_fm.c:1188-1191),
-// or downsample_passes if there is none; buffers are multiples of 512 bytes, so this is pass 8 or 9
-static int first_irregular_pass(const rtlfm_cfg &c)
-{
-	for (int p = 0; p < c.downsample_passes; p++)
-		if ((c.block_len >> p) % 4) return p;
-	return c.downsample_passes;
-}
-
-// per-block decimated complex samples, or -1 when the boxcar phase makes it vary
-static int dec_per_block(const rtlfm_cfg *c)
-{
-	int n0 = (int)(c->block_len / 2);
-	if (c->downsample_passes > 0) return n0 >> c->downsample_passes;
-	if (c->downsample <= 1) return n0;
-	return n0 % c->downsample == 0 ? n0 / c->downsample : -1;
-}
+// (first_irregular_pass, dec_per_block, validate_cfg: run_plan.h)
 
 extern "C" int rtlfm_result_len(const rtlfm_cfg *c)
 {
@@ -314,47 +302,6 @@ extern "C" int rtlfm_result_cap(const rtlfm_cfg *c)
 		if (up > n) n = (int)up;
 	}
 	return n + 2;
-}
-
-static int validate_cfg(const rtlfm_cfg *c)
-{
-	if (c->mode < RTLFM_MODE_FM || c->mode > RTLFM_MODE_RAW) return -EINVAL;
-	if (c->block_len < 512 || c->block_len > RTLFM_MAX_BLOCK_LEN || c->block_len % 512) return -EINVAL;
-	if (c->downsample_passes < 0 || c->downsample_passes > RTLFM_MAX_PASSES) return -EINVAL;
-	// (a buffer the passes do not divide - nine or ten passes, 512 n bytes with n odd / n % 4 != 0 - is something the
-	// reference runs, src/rtl_fm.c:1188-1191: the last passes then see lengths that are not multiples of four elements;
-	// k_fifth_irregular, staged_kernels.h)
-	if (c->downsample_passes == 0 && c->downsample < 1) return -EINVAL;
-	// a buffer shorter than the boxcar leaves low_pass() with lp_len == 0 and fm_demod() then reads
-	// lowpassed[-2] (src/rtl_fm.c:955-956): outside the reference's domain
-	if (c->downsample_passes == 0 && (uint32_t)c->downsample > c->block_len / 2) return -EDOM;
-	if (c->comp_fir_size != 0 && c->comp_fir_size != 9) return -EINVAL;
-	if (c->custom_atan < RTLFM_ATAN_STD || c->custom_atan > RTLFM_ATAN_LUT) return -EINVAL;
-	if (c->max_blocks < 1) return -EINVAL;
-	if (c->post_downsample < 1 || c->post_downsample > 16) return -EINVAL;
-	if (c->deemph && c->deemph_a < 1) return -EINVAL;
-	if (c->mode != RTLFM_MODE_RAW) {
-		int per = dec_per_block(c);
-		// low_pass_simple: "length must be multiple of step" (src/rtl_fm.c:740); otherwise the
-		// reference sums stale samples past result_len.  Behind a boxcar that does not divide the
-		// buffer the per-buffer count alternates, so no step > 1 can divide it every time.
-		if (c->post_downsample > 1 && (per < 0 || per % c->post_downsample)) return -EDOM;
-		if (c->rate_out2 > 0) {
-			if (c->rate_out <= 0) return -EINVAL;
-			if (c->resampler == RTLFM_RESAMPLE_LOW_PASS_REAL) {
-				// the reference divides by zero here (src/rtl_fm.c:769)
-				if (c->rate_out / c->rate_out2 == 0) return -EDOM;
-			} else if (c->resampler == RTLFM_RESAMPLE_ARBITRARY) {
-				// per < 0: the per-buffer count is n or n + 1 (boxcar not dividing the buffer)
-				int n = per < 0 ? (int)(c->block_len / 2) / c->downsample : per / c->post_downsample;
-				long long len2 = (long long)n * c->rate_out2 / c->rate_out;
-				if (len2 < 1 || n < 2) return -EINVAL;
-			} else {
-				return -EINVAL;
-			}
-		}
-	}
-	return 0;
 }
 
 extern "C" int rtlfm_cfg_validate(const rtlfm_cfg *cfg) { return cfg ? validate_cfg(cfg) : -EINVAL; }
@@ -1301,6 +1248,8 @@ extern "C" int rtlfm_gpu_get_option(rtlfm_gpu *h, const char *name, long *value)
 	if (!strcmp(name, "placement_held_mb")) { *value = placement_held_mb(h); return 0; }
 	if (!strcmp(name, "verify_mismatches")) { *value = h->vt_mismatches; return 0; }  // verify_twice: runs whose two executions differed
 	if (!strcmp(name, "verify_runs")) { *value = h->vt_runs; return 0; }
+	if (!strcmp(name, "last_route")) { *value = h->last_route; return 0; }  // the plan the last run took (enum rtlfm_route / rtlfm_rest)
+	if (!strcmp(name, "last_rest")) { *value = h->last_rest; return 0; }
 	if (!strcmp(name, "block_len")) { *value = (long)h->cfg.block_len; return 0; }  // what the handle was created with
 	if (!strcmp(name, "pack_us")) return ingest_pack_us(h, value);
 	// debugging (tests/test_soak_gpu.py): the host addresses of the runtime objects the handle owns - a hipStream_t / hipEvent_t
@@ -1409,40 +1358,10 @@ static inline int grid_for(size_t work, int block = 256, int cap = 256 * 16)
 // samples (uniform count T, or per-stream d_cnt when `varcnt`); the final
 // result is left in dst with dst_stride and its per-stream length in
 // d_out_len (may be NULL).
-struct TailPlan {
-	bool post, deemph, adc, lpr, arb;
-	bool deemph_spec;  // deemph_filter alone on a long run: the one-pass kernel, which works OUT of place (k_deemph_spec)
-	int oop() const { return (post ? 1 : 0) + (deemph_spec ? 1 : 0) + ((lpr || arb) ? 1 : 0); }
-	bool any() const { return post || deemph || adc || lpr || arb; }
-};
-// the time-parallel forms of deemph_filter apply: a long run, a divisor whose contracted interval fits a wave
-static bool deemph_scans(const rtlfm_gpu *h, int T)
-{
-	const rtlfm_cfg &c = h->cfg;
-	return T >= 2048 && c.deemph_a >= 2 && 2 * c.deemph_a + 2 <= kDeemphGap && !h->no_deemph_scan && !h->opt.deemph_sequential;
-}
-// nblocks: the buffers of the run (the plan depends on how long a stream's run is)
-static TailPlan plan_tail(const rtlfm_gpu *h, int nblocks)
-{
-	const rtlfm_cfg &c = h->cfg;
-	TailPlan t{};
-	if (c.mode == RTLFM_MODE_RAW) return t;
-	t.post = c.post_downsample > 1;
-	t.deemph = c.deemph != 0;
-	t.adc = c.dc_block_audio != 0;
-	t.lpr = c.rate_out2 > 0 && c.resampler == RTLFM_RESAMPLE_LOW_PASS_REAL;
-	t.arb = c.rate_out2 > 0 && c.resampler == RTLFM_RESAMPLE_ARBITRARY;
-	if (t.deemph && !t.lpr && !t.arb && !h->opt.deemph_four_pass) {
-		// the demodulated samples of a stream's run, as run_tail() will be told (an upper bound behind a boxcar that does not
-		// divide the buffer)
-		const long long n0 = c.block_len / 2;
-		long long T = c.downsample_passes > 0 ? (long long)nblocks * (n0 >> c.downsample_passes)
-		                                      : ((long long)nblocks * n0) / c.downsample + ((n0 % c.downsample) ? 1 : 0);
-		if (t.post) T /= c.post_downsample;
-		t.deemph_spec = T < (1ll << 30) && deemph_scans(h, (int)T);
-	}
-	return t;
-}
+// (TailPlan, plan_tail: run_plan.h - a run's plan holds it.)  What run_tail asks again while it runs:
+static rtlfm_route_opts route_opts(const rtlfm_gpu *h);
+static bool deemph_scans(const rtlfm_gpu *h, int T) { return plan::deemph_scans(h->cfg, route_opts(h), T); }
+static bool arb_tail_in_line(const rtlfm_gpu *h, const TailPlan &tp) { return plan::arb_tail_in_line(h->cfg, route_opts(h), h->nstreams, tp); }
 
 // Where mode_demod() should write so that the chain ends in `final`.
 static void tail_route(rtlfm_gpu *h, const TailPlan &tp, int16_t *final_dst, size_t final_stride,
@@ -1455,18 +1374,6 @@ static void tail_route(rtlfm_gpu *h, const TailPlan &tp, int16_t *final_dst, siz
 		*demod_dst = h->res[h->step & 1][0];
 		*demod_stride = h->tstride;
 	}
-}
-
-// Config 3's own tail (deemph + arbitrary_upsample: 16384 short waves that fill the GPU by themselves, 63 us alone) behind a
-// front end of thousands of streams is better off IN LINE, on the front end's stream: beside the next front end it takes
-// 1.5 % more of the step than behind this one, and a front end with nothing beside it runs best in few long segments
-// (the planner's no-tail target: another 3 %, LAB.md I.31).  A rule of the configuration and the stream count only - a
-// handle's tail never changes streams between runs.
-static bool arb_tail_in_line(const rtlfm_gpu *h, const TailPlan &tp)
-{
-	const rtlfm_cfg &c = h->cfg;
-	return tp.deemph && tp.arb && !tp.post && !tp.adc && !tp.lpr && c.rate_out2 > c.rate_out &&
-	       (h->opt.arb_serial > 0 || (h->opt.arb_serial < 0 && h->nstreams >= 2048));
 }
 
 // The form deemph_filter takes in a run, with the resampler where one kernel does both: decided ONCE, at the top of
@@ -1844,95 +1751,106 @@ static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_s
 }
 
 
-// -M raw: two int16 per decimated sample - of the counts the front end left (`cnt`), or of T everywhere
-static int raw_out_len(rtlfm_gpu *h, int32_t *d_out_len, const int32_t *cnt, int T)
+// One run as its launchers see it: the plan, the caller's arguments, and what each of them used to spell out for itself -
+// the stream, the two state copies, this step's counts, where mode_demod() writes (route_demod), the timed pair.
+struct RunFrame {
+	rtlfm_gpu *h;
+	const RunPlan &pl;
+	const uint8_t *d_iq; size_t stream_stride; int nblocks;
+	int16_t *d_out; size_t out_stride; int32_t *d_out_len;
+	hipStream_t q;
+	const state_t *sin; state_t *sout;
+	int32_t *dcnt;            // per-stream counts of a boxcar that does not divide the buffer (this step parity's)
+	int16_t *dd; size_t dds;  // where mode_demod() writes so that the audio tail ends in d_out
+	std::pair<Event, Event> ev;
+	size_t iq_bytes() const { return iq_extent(h, stream_stride, nblocks); }
+	const int32_t *cnt() const { return pl.g.varcnt ? dcnt : nullptr; }
+	// the audio tail's work buffers, a quarter of the HBM away from the first run's input where that matters
+	int ensure_res() { return pl.tp.any() ? ensure_res_buffers(h, d_iq, iq_bytes()) : 0; }
+	void route_demod() { tail_route(h, pl.tp, d_out, out_stride, &dd, &dds); }  // (behind ensure_res)
+	// the audio tail behind whatever demodulated into dd (run_tail: T, varcnt, Nblk, D as the front end left them)
+	int tail() { return run_tail(h, pl.tp, dd, dds, pl.g.T, pl.g.varcnt, nblocks, pl.g.Nblk, pl.g.D, d_out, out_stride, d_out_len); }
+};
+
+// -M raw: two int16 per decimated sample - of the counts the front end left, or of T everywhere
+static int raw_out_len(RunFrame &f)
 {
-	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	if (!d_out_len) return 0;
-	if (cnt) {
-		HIP_TRY(hipMemcpyAsync(d_out_len, cnt, S * sizeof(int32_t), hipMemcpyDeviceToDevice, q));
-		k_scale_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2, 1);
+	const int S = f.h->nstreams;
+	if (!f.d_out_len) return 0;
+	if (f.cnt()) {
+		HIP_TRY(hipMemcpyAsync(f.d_out_len, f.cnt(), S * sizeof(int32_t), hipMemcpyDeviceToDevice, f.q));
+		k_scale_cnt<<<grid_for(S, 64), 64, 0, f.q>>>(f.d_out_len, S, 2, 1);
 	} else {
-		k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 2 * T);
+		k_fill_cnt<<<grid_for(S, 64), 64, 0, f.q>>>(f.d_out_len, S, 2 * f.pl.g.T);
 	}
 	return 0;
 }
 
-// The back half of full_demod() behind every decimator that leaves IQ (run_staged, and the emit modes of both front
-// ends): the power squelch (src/rtl_fm.c:1204-1215) and -L levels, mode_demod incl. -M raw (:1256-1259), the audio tail.
-// `cur`: the decimated IQ, T samples per stream - or, with `cnt`, the per-stream counts of a boxcar that does not divide
-// the buffer (T is then their upper bound); buffer extents as run_tail's (Nblk, D).
-// d_iq / iq_bytes: run_staged, which has not allocated the tail's work buffers in front of its launches as the front ends do.
-static int run_back_half(rtlfm_gpu *h, uint32_t *cur, size_t xstride, int T, int Nblk, int D, int nblocks, const int32_t *cnt,
-                         const TailPlan &tp, int16_t *d_out, size_t out_stride, int32_t *d_out_len, const uint8_t *d_iq = nullptr,
-                         size_t iq_bytes = 0)
+// The back half of full_demod() behind every decimator that leaves IQ (run_staged, the emit modes of both front ends, the
+// channel front ends): the power squelch (src/rtl_fm.c:1204-1215) and -L levels, mode_demod incl. -M raw (:1256-1259), the
+// audio tail.  `cur`: the decimated IQ of the plan's geometry.
+// late_res: run_staged, which has not allocated the tail's work buffers in front of its launches as the front ends do - it
+// does so here, behind the squelch's kernels, where it always did.
+static int run_back_half(RunFrame &f, uint32_t *cur, size_t xstride, bool late_res = false)
 {
+	rtlfm_gpu *h = f.h;
 	const rtlfm_cfg &c = h->cfg;
-	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	if (c.squelch_level || c.report_levels)
-		k_squelch_rms<<<S * nblocks, 256, 0, q>>>(cur, xstride, Nblk, D, nblocks, sin, c.squelch_level,
+	const RunGeom &g = f.pl.g;
+	const int S = h->nstreams, nblocks = f.nblocks;
+	hipStream_t q = f.q;
+	if (wants_levels(c))
+		k_squelch_rms<<<S * nblocks, 256, 0, q>>>(cur, xstride, g.Nblk, g.D, nblocks, f.sin, c.squelch_level,
 		                                         c.dc_block_raw, h->d_mute, h->d_levels);
 	if (c.squelch_level) {
-		k_squelch_hits<<<grid_for(S, 64), 64, 0, q>>>(h->d_mute, nblocks, S, sin, sout);
-		k_squelch_zero<<<S * nblocks, 256, 0, q>>>(cur, xstride, Nblk, D, nblocks, S, T, sin,
+		k_squelch_hits<<<grid_for(S, 64), 64, 0, q>>>(h->d_mute, nblocks, S, f.sin, f.sout);
+		k_squelch_zero<<<S * nblocks, 256, 0, q>>>(cur, xstride, g.Nblk, g.D, nblocks, S, g.T, f.sin,
 		                                                     h->d_mute);
 	}
-	if (d_iq && tp.any()) {
-		const int r = ensure_res_buffers(h, d_iq, iq_bytes);
+	if (late_res) {
+		const int r = f.ensure_res();
 		if (r < 0) return r;
 	}
-	int16_t *dd; size_t dds;
-	tail_route(h, tp, d_out, out_stride, &dd, &dds);
+	f.route_demod();
 	if (c.mode == RTLFM_MODE_FM)
-		k_fm_demod<<<S * nblocks, 256, 0, q>>>(cur, xstride, dd, dds, T, S, Nblk, D, nblocks,
-		                                         c.custom_atan, h->d_lut, cnt, sin, sout);
+		k_fm_demod<<<S * nblocks, 256, 0, q>>>(cur, xstride, f.dd, f.dds, g.T, S, g.Nblk, g.D, nblocks,
+		                                         c.custom_atan, h->d_lut, f.cnt(), f.sin, f.sout);
 	else
-		k_simple_demod<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, xstride, dd, dds, T, S, c.mode,
-		                                                     c.output_scale, cnt);
-	if (c.mode == RTLFM_MODE_RAW) return raw_out_len(h, d_out_len, cnt, T);
-	return run_tail(h, tp, dd, dds, T, cnt != nullptr, nblocks, Nblk, D, d_out, out_stride, d_out_len);
+		k_simple_demod<<<grid_for((size_t)S * g.T), 256, 0, q>>>(cur, xstride, f.dd, f.dds, g.T, S, c.mode,
+		                                                     c.output_scale, f.cnt());
+	if (c.mode == RTLFM_MODE_RAW) return raw_out_len(f);
+	return f.tail();
 }
 
-// Passes first .. passes - 1 where `first` is handed a length that is not a multiple of four elements, and everything
-// up to mode_demod() behind them (staged_kernels.h, k_fifth_irregular); then the ordinary audio tail.  `cur` holds the
-// level in front of pass `first` (n_in samples per buffer, buffers back to back).
-static int run_irregular_rest(rtlfm_gpu *h, const uint32_t *cur, size_t xstride, int first, int nblocks, int16_t *d_out,
-                              size_t out_stride, int32_t *d_out_len, const uint8_t *d_iq, size_t iq_bytes)
+// REST_IRREGULAR.  Passes first_irr .. passes - 1 where first_irr is handed a length that is not a multiple of four
+// elements, and everything up to mode_demod() behind them (staged_kernels.h, k_fifth_irregular); then the ordinary audio
+// tail.  `cur` holds the level in front of that pass (n_in samples per buffer, buffers back to back).
+static int run_irregular_rest(RunFrame &f, const uint32_t *cur, size_t xstride)
 {
+	rtlfm_gpu *h = f.h;
 	const rtlfm_cfg &c = h->cfg;
-	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	TailPlan tp = plan_tail(h, nblocks);
-	if (tp.any()) {
-		int r = ensure_res_buffers(h, d_iq, iq_bytes);
-		if (r < 0) return r;
-	}
-	int16_t *dd; size_t dds;
-	tail_route(h, tp, d_out, out_stride, &dd, &dds);
+	const int S = h->nstreams, nblocks = f.nblocks, first = f.pl.g.first_irr;
+	int r = f.ensure_res();
+	if (r < 0) return r;
+	f.route_demod();
 	IrregularParams ip{};
-	ip.X = cur; ip.xstride = xstride; ip.n_in = (int)((c.block_len / 2) >> first); ip.nblocks = nblocks; ip.nstreams = S;
+	ip.X = cur; ip.xstride = xstride; ip.n_in = f.pl.g.N0 >> first; ip.nblocks = nblocks; ip.nstreams = S;
 	ip.first = first; ip.passes = c.downsample_passes; ip.lp_len = (int)(c.block_len >> c.downsample_passes);
 	ip.fir = c.comp_fir_size == 9 ? 1 : 0; ip.mode = c.mode; ip.variant = c.custom_atan; ip.output_scale = c.output_scale;
 	ip.squelch_level = c.squelch_level; ip.report_levels = c.report_levels; ip.omit_dc_fix = c.dc_block_raw;
-	ip.lut = h->d_lut; ip.R = dd; ip.rstride = dds;
-	ip.levels = (c.squelch_level || c.report_levels) ? h->d_levels : nullptr;
-	ip.sin = h->st[h->st_cur]; ip.sout = h->st[(h->st_cur + 1) % 3];
-	if (2 * ip.n_in + 8 > kIrregularMaxElems) return -ENOTSUP;
-	k_fifth_irregular<<<(unsigned)S, 64, 0, q>>>(ip);  // one wave per stream
+	ip.lut = h->d_lut; ip.R = f.dd; ip.rstride = f.dds;
+	ip.levels = wants_levels(c) ? h->d_levels : nullptr;
+	ip.sin = f.sin; ip.sout = f.sout;
+	if (2 * ip.n_in + 8 > kIrregularMaxElems) return -ENOTSUP;  // (never: pass 8 of RTLFM_MAX_BLOCK_LEN is handed 512 samples)
+	k_fifth_irregular<<<(unsigned)S, 64, 0, f.q>>>(ip);  // one wave per stream
 	if (c.mode == RTLFM_MODE_RAW) {
-		if (d_out_len) k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, nblocks * ip.lp_len);
+		if (f.d_out_len) k_fill_cnt<<<grid_for(S, 64), 64, 0, f.q>>>(f.d_out_len, S, nblocks * ip.lp_len);
 		return 0;
 	}
-	const int Nblk = ip.lp_len / 2, T = nblocks * Nblk;
-	if (T == 0) {  // every buffer is down to one element or none: fm_demod() has nothing to pair
-		if (d_out_len) k_fill_cnt<<<grid_for(S, 64), 64, 0, q>>>(d_out_len, S, 0);
+	if (f.pl.g.T == 0) {  // every buffer is down to one element or none: fm_demod() has nothing to pair
+		if (f.d_out_len) k_fill_cnt<<<grid_for(S, 64), 64, 0, f.q>>>(f.d_out_len, S, 0);
 		return 0;
 	}
-	return run_tail(h, tp, dd, dds, T, false, nblocks, Nblk, 1, d_out, out_stride, d_out_len);
+	return f.tail();
 }
 
 // Option source_dc's pre-pass, in front of a channel front end and inside its timed pair: every source's buffer sums
@@ -1956,21 +1874,24 @@ static int launch_source_dc(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_str
 	return 0;
 }
 
-static int run_staged(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                      size_t out_stride, int32_t *d_out_len)
+// ROUTE_STAGED and ROUTE_CHAN_MIX: a kernel per stage through the work buffers.  The timed pair holds the decimator with
+// its own raw-DC sums (k_rdc_sums / k_rdc_smooth, not the front ends' pre-pass); the tail's buffers are allocated behind
+// it, in the back half.
+static int run_staged(RunFrame &f)
 {
+	rtlfm_gpu *h = f.h;
 	const rtlfm_cfg &c = h->cfg;
-	const int S = h->nstreams;
+	const RunGeom &g = f.pl.g;
+	const int S = h->nstreams, nblocks = f.nblocks;
 	const uint32_t L = c.block_len;
-	const int N0 = (int)(L / 2);
-	hipStream_t q = h->stream;
+	const uint8_t *d_iq = f.d_iq;
+	const size_t stream_stride = f.stream_stride;
+	hipStream_t q = f.q;
+	const state_t *sin = f.sin;
+	state_t *sout = f.sout;
 	int r = ensure_work_buffers(h);
 	if (r < 0) return r;
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	std::pair<Event, Event> ev;
-
-	r = timing_begin(h, ev);
+	r = timing_begin(h, f.ev);
 	if (r < 0) return r;
 	// --- rtlsdr_callback: convert, raw DC block, rotate (src/rtl_fm.c:1326-1338)
 	const int2 *rdc = nullptr;
@@ -1996,46 +1917,31 @@ static int run_staged(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, i
 		                                                                  c.offset_tuning ? 0 : 1, rdc);
 	uint32_t *cur = h->bufA, *oth = h->bufB;
 	// --- decimation (src/rtl_fm.c:1187-1202)
-	int T;          // decimated complex samples per stream (upper bound if varcnt)
-	int Nblk, D;    // block geometry for "first output of a block" tests
-	bool varcnt = false;
 	if (c.downsample_passes > 0) {
-		const int first_irr = first_irregular_pass(c);
-		for (int p = 0; p < first_irr; p++) {
-			int N = N0 >> p;
+		for (int p = 0; p < g.first_irr; p++) {
+			int N = g.N0 >> p;
 			k_fifth<<<grid_for((size_t)S * nblocks * (N / 2)), 256, 0, q>>>(cur, oth, h->xstride, N, nblocks, S,
 			                                                              p, sin, sout);
 			std::swap(cur, oth);
 		}
-		if (first_irr < c.downsample_passes) {
-			r = timing_end(h, ev);
+		if (f.pl.rest == RTLFM_REST_IRREGULAR) {
+			r = timing_end(h, f.ev);
 			if (r < 0) return r;
-			return run_irregular_rest(h, cur, h->xstride, first_irr, nblocks, d_out, out_stride, d_out_len, d_iq,
-			                          iq_extent(h, stream_stride, nblocks));
+			return run_irregular_rest(f, cur, h->xstride);
 		}
-		Nblk = N0 >> c.downsample_passes;
-		D = 1;
-		T = nblocks * Nblk;
 		if (c.comp_fir_size == 9) {
-			k_fir9<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, oth, h->xstride, T, S, c.downsample_passes,
+			k_fir9<<<grid_for((size_t)S * g.T), 256, 0, q>>>(cur, oth, h->xstride, g.T, S, c.downsample_passes,
 			                                              sin, sout);
 			std::swap(cur, oth);
 		}
 	} else {
-		Nblk = N0;
-		D = c.downsample;
-		int Tin = nblocks * N0;
-		int maxout = Tin / D + 1;
-		k_boxcar<<<grid_for((size_t)S * (maxout + 1)), 256, 0, q>>>(cur, oth, h->xstride, Tin, S, D, sin, sout,
-		                                                          h->d_cnt[h->step & 1]);
+		k_boxcar<<<grid_for((size_t)S * (g.maxout + 1)), 256, 0, q>>>(cur, oth, h->xstride, g.Tin, S, g.D, sin, sout,
+		                                                          f.dcnt);
 		std::swap(cur, oth);
-		varcnt = (N0 % D) != 0;
-		T = varcnt ? maxout : Tin / D;
 	}
-	r = timing_end(h, ev);
+	r = timing_end(h, f.ev);
 	if (r < 0) return r;
-	return run_back_half(h, cur, h->xstride, T, Nblk, D, nblocks, varcnt ? h->d_cnt[h->step & 1] : nullptr, plan_tail(h, nblocks), d_out,
-	                     out_stride, d_out_len, d_iq, iq_extent(h, stream_stride, nblocks));
+	return run_back_half(f, cur, h->xstride, true);
 }
 
 
@@ -2100,40 +2006,49 @@ static const int2 *rdc_prepass(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_
 	return h->d_rdc_avg;
 }
 
-static int run_fused(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                     size_t out_stride, int32_t *d_out_len)
+// What the four launchers of k_fused and k_boxcar_scan share around their launch, in the one order all four had: the
+// buffers the plan asks for (what an emit mode writes, the audio tail's), then inside the timed pair the raw-DC pre-pass,
+// the cleared rms() sums where the front end takes them, the launch; behind the pair k_squelch_apply on those sums.
+// `launch(rdc)`: the front end itself, given the pre-pass's averages (or nullptr).
+template <class Launch>
+static int run_front_end(RunFrame &f, Launch &&launch)
 {
+	rtlfm_gpu *h = f.h;
 	const rtlfm_cfg &c = h->cfg;
+	const RunPlan &pl = f.pl;
 	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	TailPlan tp = plan_tail(h, nblocks);
-	if (tp.any()) {
-		int r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
-		if (r < 0) return r;
+	const bool emits = pl.route == RTLFM_ROUTE_FUSED_EMIT || pl.route == RTLFM_ROUTE_BOXCAR_EMIT;
+	int r;
+	if (pl.rest != RTLFM_REST_NONE) {  // (REST_NONE: the launch writes the caller's rows and nothing follows but their lengths)
+		if (emits && (r = ensure_deep_buffers(h, f.d_iq, f.iq_bytes())) < 0) return r;
+		if ((r = f.ensure_res()) < 0) return r;
 	}
-	int16_t *dd; size_t dds;
-	tail_route(h, tp, d_out, out_stride, &dd, &dds);
-	std::pair<Event, Event> ev;
-	int r = timing_begin(h, ev);
+	f.route_demod();
+	if ((r = timing_begin(h, f.ev)) < 0) return r;
+	h->fws.tail_follows = pl.tail_follows;
+	const int2 *rdc = rdc_prepass(h, f.d_iq, f.stream_stride, f.nblocks);  // -E rdc; in emit mode in front of -M raw, the squelch, 7-10 passes
+	if (pl.sq_front) HIP_TRY(hipMemsetAsync(h->d_sq_sums, 0, (size_t)S * f.nblocks * 2 * sizeof(uint32_t), f.q));
+	if ((r = launch(rdc)) < 0) return r;
+	if ((r = timing_end(h, f.ev)) < 0) return r;
+	if (pl.sq_front)  // the front end took rms()'s sums, k_squelch_apply decides (fused_kernel.h; boxcar_kernel.h, SQ)
+		k_squelch_apply<<<(unsigned)S, 256, (size_t)f.nblocks * sizeof(int32_t), f.q>>>(
+		    h->d_sq_sums, f.dd, f.dds, pl.g.Nblk, pl.g.D, f.nblocks, S, c.squelch_level, c.dc_block_raw, c.mode == RTLFM_MODE_FM ? 1 : 0,
+		    f.cnt(), pl.g.T, f.sin, f.sout, h->d_levels);
+	return 0;
+}
+// where an emit mode writes: the caller's rows (REST_NONE), else the handle's work buffer
+static uint32_t *emit_to(const RunFrame &f) { return f.pl.rest == RTLFM_REST_NONE ? reinterpret_cast<uint32_t *>(f.d_out) : f.h->deepA.get(); }
+static size_t emit_stride(const RunFrame &f) { return f.pl.rest == RTLFM_REST_NONE ? f.out_stride / 2 : f.h->deep_stride; }
+
+// ROUTE_FUSED: k_fused from the bytes to the PCM.
+static int run_fused(RunFrame &f)
+{
+	rtlfm_gpu *h = f.h;
+	int r = run_front_end(f, [&](const int2 *rdc) {
+		return fused::launch(h->fws, h->cfg, h->nstreams, f.d_iq, f.stream_stride, f.nblocks, f.dd, f.dds, f.sin, f.sout, h->d_lut, f.q, nullptr, 0,
+		                     rdc, f.pl.sq_front ? h->d_sq_sums.get() : nullptr);
+	});
 	if (r < 0) return r;
-	const int2 *rdc = rdc_prepass(h, d_iq, stream_stride, nblocks);
-	const bool sq = c.squelch_level || c.report_levels;  // the front end takes rms()'s sums, k_squelch_apply decides (fused_kernel.h)
-	// (a tail in line leaves the next front end alone: the plan of a front end that nothing runs beside)
-	h->fws.tail_follows = (tp.any() && !arb_tail_in_line(h, tp)) || sq;
-	if (sq) HIP_TRY(hipMemsetAsync(h->d_sq_sums, 0, (size_t)S * nblocks * 2 * sizeof(uint32_t), q));
-	r = fused::launch(h->fws, c, S, d_iq, stream_stride, nblocks, dd, dds, sin, sout, h->d_lut, q, nullptr, 0, rdc,
-	                  sq ? h->d_sq_sums : nullptr);
-	if (r < 0) return r;
-	r = timing_end(h, ev);
-	if (r < 0) return r;
-	if (sq) {
-		const int Nb = (int)((c.block_len / 2) >> c.downsample_passes);
-		k_squelch_apply<<<(unsigned)S, 256, (size_t)nblocks * sizeof(int32_t), q>>>(
-		    h->d_sq_sums, dd, dds, Nb, 1, nblocks, S, c.squelch_level, c.dc_block_raw, c.mode == RTLFM_MODE_FM ? 1 : 0, nullptr,
-		    nblocks * Nb, sin, sout, h->d_levels);
-	}
 	// bit 2 with bit 8: report the stamps of every launch (synchronises, so the GPU idles between
 	// launches and clocks up); bit 2 alone with bit 16: only when timing_read() asks, i.e. the last
 	// launch of an uninterrupted sequence
@@ -2141,187 +2056,116 @@ static int run_fused(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, in
 		int r2 = report_clock_stamps(h);
 		if (r2 < 0) return r2;
 	}
-	const int Nblk = (int)((c.block_len / 2) >> c.downsample_passes);
-	return run_tail(h, tp, dd, dds, nblocks * Nblk, false, nblocks, Nblk, 1, d_out, out_stride, d_out_len);
+	return f.tail();
 }
 
-// The fused front end in emit mode + staged kernels for what it does not do itself: with up to
+// REST_DEEP_DEMOD / REST_DEEP_IQ.  Seven and more passes on buffers they divide: the passes beyond six, generic_fir and
+// (without a squelch) the demodulator in ONE launch, a workgroup per (stream, buffer) in LDS (staged_kernels.h, k_deep_rest)
+static int rest_deep(RunFrame &f)
+{
+	rtlfm_gpu *h = f.h;
+	const rtlfm_cfg &c = h->cfg;
+	const RunGeom &g = f.pl.g;
+	const bool demod_here = f.pl.rest == RTLFM_REST_DEEP_DEMOD;
+	int kk[6];
+	deep_rest_tails(c.downsample_passes, c.comp_fir_size == 9, kk);
+	DeepRestParams dp{};
+	dp.X = h->deepA; dp.xstride = h->deep_stride; dp.n6 = g.N0 >> g.level; dp.nblocks = f.nblocks; dp.nstreams = h->nstreams;
+	dp.passes = c.downsample_passes;
+	dp.fir = c.comp_fir_size == 9 ? 1 : 0; dp.kt = kk[0];
+	dp.mode = c.mode; dp.variant = c.custom_atan; dp.output_scale = c.output_scale; dp.lut = h->d_lut;
+	dp.sin = f.sin; dp.sout = f.sout;
+	if (demod_here) { dp.R = f.dd; dp.rstride = f.dds; }
+	else { dp.Y = h->deepB; dp.ystride = h->deep_stride; }
+	const size_t lds_b = (size_t)2 * (kk[0] + dp.n6 + 8) * sizeof(uint32_t);
+	k_deep_rest<<<(unsigned)((size_t)h->nstreams * f.nblocks), 256, lds_b, f.q>>>(dp);
+	if (demod_here) return f.tail();
+	return run_back_half(f, h->deepB, h->deep_stride);  // the squelch, -L, -M raw on the final level
+}
+
+// REST_PER_PASS / REST_IRREGULAR behind six fused passes: a launch per remaining pass the buffers divide; then generic_fir
+// and the back half, or - nine or ten passes on buffers they do not divide - the reference's own loops from there.
+static int rest_passes(RunFrame &f)
+{
+	rtlfm_gpu *h = f.h;
+	const rtlfm_cfg &c = h->cfg;
+	const RunGeom &g = f.pl.g;
+	const int S = h->nstreams;
+	uint32_t *cur = h->deepA, *oth = h->deepB;
+	for (int p = g.level; p < g.first_irr; p++) {
+		const int N = g.N0 >> p;
+		k_fifth<<<grid_for((size_t)S * f.nblocks * (N / 2)), 256, 0, f.q>>>(cur, oth, h->deep_stride, N, f.nblocks, S, p, f.sin, f.sout);
+		std::swap(cur, oth);
+	}
+	if (f.pl.rest == RTLFM_REST_IRREGULAR) return run_irregular_rest(f, cur, h->deep_stride);
+	if (c.comp_fir_size == 9) {
+		k_fir9<<<grid_for((size_t)S * g.T), 256, 0, f.q>>>(cur, oth, h->deep_stride, g.T, S, c.downsample_passes, f.sin, f.sout);
+		std::swap(cur, oth);
+	}
+	return run_back_half(f, cur, h->deep_stride);
+}
+
+// ROUTE_FUSED_EMIT.  The fused front end in emit mode + staged kernels for what it does not do itself: with up to
 // six passes it emits the decimated, FIR-compensated IQ (what full_demod() hands on after
 // src/rtl_fm.c:1202); with 7..10 passes the /64 IQ, and the staged kernels run the remaining
 // passes and the FIR on 1/64 of the data.  Then, as in full_demod(): squelch (:1204-1215),
 // mode_demod incl. -M raw (:1256-1259), audio tail.  The work buffer has the staged path's
 // layout for that level (a stream's buffers back to back).
-static int run_fused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                          size_t out_stride, int32_t *d_out_len)
+static int run_fused_emit(RunFrame &f)
 {
-	const rtlfm_cfg &c = h->cfg;
-	const int S = h->nstreams;
-	const int N0 = (int)(c.block_len / 2);
-	const int level = c.downsample_passes < fused::kMaxP ? c.downsample_passes : fused::kMaxP;
-	hipStream_t q = h->stream;
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	// -M raw behind up to six passes, no squelch: the emitted IQ is the output, straight into the caller's rows where they
-	// take 16-byte stores (as run_boxfused_emit)
-	const bool raw_direct = c.mode == RTLFM_MODE_RAW && !c.squelch_level && !c.report_levels && c.downsample_passes <= fused::kMaxP &&
-	                        !((uintptr_t)d_out & 15) && !(out_stride & 7);
-	if (!raw_direct) {
-		int r0 = ensure_deep_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
-		if (r0 < 0) return r0;
-	}
-	TailPlan tp = plan_tail(h, nblocks);
-	if (tp.any() && !raw_direct) {  // (-M raw has no audio tail: full_demod returns behind raw_demod, src/rtl_fm.c:1257-1259)
-		int r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
-		if (r < 0) return r;
-	}
-	std::pair<Event, Event> ev;
-	int r = timing_begin(h, ev);
+	rtlfm_gpu *h = f.h;
+	int r = run_front_end(f, [&](const int2 *rdc) {
+		return fused::launch(h->fws, h->cfg, h->nstreams, f.d_iq, f.stream_stride, f.nblocks, nullptr, 0, f.sin, f.sout, h->d_lut, f.q, emit_to(f),
+		                     emit_stride(f), rdc);
+	});
 	if (r < 0) return r;
-	h->fws.tail_follows = !raw_direct;  // kernels follow on this stream and, with a tail, on the tail's (as run_boxfused_emit)
-	const int2 *rdc = rdc_prepass(h, d_iq, stream_stride, nblocks);  // -E rdc in front of -M raw, the squelch, 7-10 passes
-	r = fused::launch(h->fws, c, S, d_iq, stream_stride, nblocks, nullptr, 0, sin, sout, h->d_lut, q,
-	                  raw_direct ? reinterpret_cast<uint32_t *>(d_out) : h->deepA, raw_direct ? out_stride / 2 : h->deep_stride, rdc);
-	if (r < 0) return r;
-	r = timing_end(h, ev);
-	if (r < 0) return r;
-	if (raw_direct) return raw_out_len(h, d_out_len, nullptr, nblocks * (N0 >> c.downsample_passes));
-	uint32_t *cur = h->deepA, *oth = h->deepB;
-	const int first_irr = first_irregular_pass(c);
-	// seven and more passes on buffers they divide: the passes beyond six, generic_fir and (without a squelch) the
-	// demodulator in ONE launch, a workgroup per (stream, buffer) in LDS (staged_kernels.h, k_deep_rest)
-	if (c.downsample_passes > level && first_irr >= c.downsample_passes && h->opt.deep_rest) {
-		int kk[6];
-		deep_rest_tails(c.downsample_passes, c.comp_fir_size == 9, kk);
-		const int n6 = N0 >> level, nF = N0 >> c.downsample_passes;
-		if (n6 >= 2 * kk[0] && nF - kk[c.downsample_passes - level] >= 3) {
-			const bool demod_here = !c.squelch_level && !c.report_levels && c.mode != RTLFM_MODE_RAW;
-			DeepRestParams dp{};
-			dp.X = cur; dp.xstride = h->deep_stride; dp.n6 = n6; dp.nblocks = nblocks; dp.nstreams = S; dp.passes = c.downsample_passes;
-			dp.fir = c.comp_fir_size == 9 ? 1 : 0; dp.kt = kk[0];
-			dp.mode = c.mode; dp.variant = c.custom_atan; dp.output_scale = c.output_scale; dp.lut = h->d_lut;
-			dp.sin = sin; dp.sout = sout;
-			const int T2 = nblocks * nF;
-			int16_t *dd2; size_t dds2;
-			tail_route(h, tp, d_out, out_stride, &dd2, &dds2);
-			if (demod_here) { dp.R = dd2; dp.rstride = dds2; }
-			else { dp.Y = oth; dp.ystride = h->deep_stride; }
-			const size_t lds_b = (size_t)2 * (kk[0] + n6 + 8) * sizeof(uint32_t);
-			k_deep_rest<<<(unsigned)((size_t)S * nblocks), 256, lds_b, q>>>(dp);
-			if (demod_here) return run_tail(h, tp, dd2, dds2, T2, false, nblocks, nF, 1, d_out, out_stride, d_out_len);
-			std::swap(cur, oth);
-			// the squelch, -L, -M raw on the final level
-			return run_back_half(h, cur, h->deep_stride, T2, nF, 1, nblocks, nullptr, tp, d_out, out_stride, d_out_len);
-		}
+	switch (f.pl.rest) {
+	case RTLFM_REST_NONE: return raw_out_len(f);
+	case RTLFM_REST_DEEP_DEMOD:
+	case RTLFM_REST_DEEP_IQ: return rest_deep(f);
+	case RTLFM_REST_PER_PASS:
+	case RTLFM_REST_IRREGULAR: return rest_passes(f);
+	case RTLFM_REST_BACK_HALF: return run_back_half(f, h->deepA, h->deep_stride);
+	default: return -EFAULT;  // planning bug
 	}
-	for (int p = level; p < c.downsample_passes && p < first_irr; p++) {
-		const int N = N0 >> p;
-		k_fifth<<<grid_for((size_t)S * nblocks * (N / 2)), 256, 0, q>>>(cur, oth, h->deep_stride, N, nblocks, S, p,
-		                                                              sin, sout);
-		std::swap(cur, oth);
-	}
-	if (first_irr < c.downsample_passes)  // nine or ten passes on buffers they do not divide: the reference's own loops from here
-		return run_irregular_rest(h, cur, h->deep_stride, first_irr, nblocks, d_out, out_stride, d_out_len, d_iq,
-		                          iq_extent(h, stream_stride, nblocks));
-	const int Nblk = N0 >> c.downsample_passes;
-	const int T = nblocks * Nblk;
-	if (c.downsample_passes > level && c.comp_fir_size == 9) {
-		k_fir9<<<grid_for((size_t)S * T), 256, 0, q>>>(cur, oth, h->deep_stride, T, S, c.downsample_passes, sin, sout);
-		std::swap(cur, oth);
-	}
-	return run_back_half(h, cur, h->deep_stride, T, Nblk, 1, nblocks, nullptr, tp, d_out, out_stride, d_out_len);
 }
 
-// The boxcar (low_pass) front end in one launch; output counts may differ per buffer and
+// ROUTE_BOXCAR.  The boxcar (low_pass) front end in one launch; output counts may differ per buffer and
 // per stream (d_cnt), which the order-insensitive tail stages accept (run_tail, varcnt).
-static int run_boxfused(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                        size_t out_stride, int32_t *d_out_len)
+static int run_boxfused(RunFrame &f)
 {
-	const rtlfm_cfg &c = h->cfg;
-	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	TailPlan tp = plan_tail(h, nblocks);
-	if (tp.any()) {
-		int r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
-		if (r < 0) return r;
-	}
-	int16_t *dd; size_t dds;
-	tail_route(h, tp, d_out, out_stride, &dd, &dds);
-	std::pair<Event, Event> ev;
-	int r = timing_begin(h, ev);
-	if (r < 0) return r;
-	const bool sq = c.squelch_level || c.report_levels;  // the front end takes rms()'s sums, k_squelch_apply decides (boxcar_kernel.h, SQ)
-	h->fws.tail_follows = tp.any() || sq;
-	const int2 *rdc = rdc_prepass(h, d_iq, stream_stride, nblocks);
-	if (sq) HIP_TRY(hipMemsetAsync(h->d_sq_sums, 0, (size_t)S * nblocks * 2 * sizeof(uint32_t), q));
-	r = boxfused::launch(h->fws, c, S, d_iq, stream_stride, nblocks, dd, dds, h->d_cnt[h->step & 1], sin, sout, q, nullptr, 0, rdc,
-	                     sq ? h->d_sq_sums : nullptr);
-	if (r < 0) return r;
-	r = timing_end(h, ev);
-	if (r < 0) return r;
-	const int N0 = (int)(c.block_len / 2), D = c.downsample;
-	const int Tin = nblocks * N0;
-	const bool varcnt = (N0 % D) != 0;
-	const int T = varcnt ? Tin / D + 1 : Tin / D;
-	if (sq)
-		k_squelch_apply<<<(unsigned)S, 256, (size_t)nblocks * sizeof(int32_t), q>>>(
-		    h->d_sq_sums, dd, dds, N0, D, nblocks, S, c.squelch_level, c.dc_block_raw, c.mode == RTLFM_MODE_FM ? 1 : 0,
-		    varcnt ? h->d_cnt[h->step & 1] : nullptr, T, sin, sout, h->d_levels);
-	return run_tail(h, tp, dd, dds, T, varcnt, nblocks, N0, D, d_out, out_stride, d_out_len);
+	rtlfm_gpu *h = f.h;
+	int r = run_front_end(f, [&](const int2 *rdc) {
+		return boxfused::launch(h->fws, h->cfg, h->nstreams, f.d_iq, f.stream_stride, f.nblocks, f.dd, f.dds, f.dcnt, f.sin, f.sout, f.q, nullptr, 0,
+		                        rdc, f.pl.sq_front ? h->d_sq_sums.get() : nullptr);
+	});
+	return r < 0 ? r : f.tail();
 }
 
-// The boxcar front end in emit mode + staged kernels on 1 / D of the data, as full_demod() goes on behind
-// low_pass(): power squelch (src/rtl_fm.c:1204-1215), -L levels (:1217-1237), mode_demod incl. -M raw
+// ROUTE_BOXCAR_EMIT.  The boxcar front end in emit mode + staged kernels on 1 / D of the data, as full_demod() goes on
+// behind low_pass(): power squelch (src/rtl_fm.c:1204-1215), -L levels (:1217-1237), mode_demod incl. -M raw
 // (:1006-1009, 1256-1259), audio tail.  The everyday scanner line - rtl_fm -M fm -s 12k -l 50 - is this.
-static int run_boxfused_emit(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                             size_t out_stride, int32_t *d_out_len)
+// (REST_NONE, -M raw without the squelch: what the launch emits IS the output - raw_demod() copies lowpassed[],
+// src/rtl_fm.c:1002-1009 - and goes straight into the caller's rows; round 5: a copy kernel over 429 M samples cost more
+// than the decimator)
+static int run_boxfused_emit(RunFrame &f)
 {
-	const rtlfm_cfg &c = h->cfg;
-	const int S = h->nstreams;
-	hipStream_t q = h->stream;
-	const state_t *sin = h->st[h->st_cur];
-	state_t *sout = h->st[(h->st_cur + 1) % 3];
-	// -M raw without the squelch: what the launch emits IS the output (raw_demod() copies lowpassed[], src/rtl_fm.c:1002-1009)
-	// - it goes straight into the caller's rows (round 5; a copy kernel over 429 M samples cost more than the decimator)
-	const bool raw_direct = c.mode == RTLFM_MODE_RAW && !c.squelch_level && !c.report_levels;
-	int r = raw_direct ? 0 : ensure_deep_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
+	rtlfm_gpu *h = f.h;
+	int r = run_front_end(f, [&](const int2 *rdc) {
+		return boxfused::launch(h->fws, h->cfg, h->nstreams, f.d_iq, f.stream_stride, f.nblocks, nullptr, 0, f.dcnt, f.sin, f.sout, f.q, emit_to(f),
+		                        emit_stride(f), rdc);
+	});
 	if (r < 0) return r;
-	TailPlan tp = plan_tail(h, nblocks);
-	if (tp.any()) {
-		r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks));
-		if (r < 0) return r;
-	}
-	std::pair<Event, Event> ev;
-	r = timing_begin(h, ev);
-	if (r < 0) return r;
-	h->fws.tail_follows = !raw_direct;  // kernels follow on this stream and, with a tail, on the tail's
-	int32_t *dcnt = h->d_cnt[h->step & 1];
-	const int2 *rdc = rdc_prepass(h, d_iq, stream_stride, nblocks);
-	uint32_t *emit_to = raw_direct ? reinterpret_cast<uint32_t *>(d_out) : h->deepA;
-	const size_t emit_stride = raw_direct ? out_stride / 2 : h->deep_stride;
-	r = boxfused::launch(h->fws, c, S, d_iq, stream_stride, nblocks, nullptr, 0, dcnt, sin, sout, q, emit_to, emit_stride, rdc);
-	if (r < 0) return r;
-	r = timing_end(h, ev);
-	if (r < 0) return r;
-	const int N0 = (int)(c.block_len / 2), D = c.downsample;
-	const int Tin = nblocks * N0;
-	const bool varcnt = (N0 % D) != 0;
-	const int T = varcnt ? Tin / D + 1 : Tin / D;
-	if (raw_direct) return raw_out_len(h, d_out_len, varcnt ? dcnt : nullptr, T);
-	return run_back_half(h, h->deepA, h->deep_stride, T, N0, D, nblocks, varcnt ? dcnt : nullptr, tp, d_out, out_stride, d_out_len);
+	return f.pl.rest == RTLFM_REST_NONE ? raw_out_len(f) : run_back_half(f, h->deepA, h->deep_stride);
 }
 
 // Channels on.  One of three front ends takes the source bytes to every channel's decimated IQ (chan_iq), then full_demod()
-// goes on as behind low_pass() (run_back_half).  What the three share of a run:
+// goes on as behind low_pass() (run_back_half).  What the three share of a run beyond the plan's geometry (RunGeom: Tin
+// complex samples of the run, an output every D of them, maxout the most a run can have):
 struct ChanRun {
-	int N0, D, Tin;        // complex samples per buffer, outputs every D of them, complex samples of the run
-	bool varcnt;           // D does not divide a buffer: per-stream counts
-	int T, maxout, nsrc;   // outputs of a stream's run (with varcnt: at most), the most a run can have, sources
-	int nblocks;
-	TailPlan tp;
+	const RunGeom &g;
+	int nsrc, nblocks;
 	int target_waves;      // for channel::plan
-	bool raw_direct;       // the boxcar alone: the launch's rows ARE the output
 	int32_t *dcnt;
 	const state_t *sin;
 	state_t *sout;
@@ -2361,39 +2205,31 @@ static int ensure_channel_buffers(rtlfm_gpu *h)
 	return h->fir_ntaps > 0 ? ensure_chan_fir_x(h) : 0;
 }
 
-static int chan_run_prepare(rtlfm_gpu *h, bool box, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                            size_t out_stride, ChanRun &cr)
+// What the three front ends are handed (REST_NONE - the boxcar alone, -M raw without the squelch: the launch's rows ARE the
+// output, as run_boxfused_emit's)
+static int chan_run_prepare(RunFrame &rf, ChanRun &cr)
 {
-	const rtlfm_cfg &c = h->cfg;
-	const int S = h->nstreams;
-	cr.N0 = (int)(c.block_len / 2); cr.D = c.downsample;
-	cr.Tin = nblocks * cr.N0;
-	cr.varcnt = (cr.N0 % cr.D) != 0;
-	cr.T = cr.varcnt ? cr.Tin / cr.D + 1 : cr.Tin / cr.D;
-	cr.maxout = cr.Tin / cr.D + 1;
-	cr.nsrc = S / h->chan_per;
-	cr.nblocks = nblocks;
-	if (!box && h->src_hist_srcs < cr.nsrc) return -ENOMEM;  // (ensure_history failed in the setter, which said so)
-	// -M raw without the squelch behind the boxcar: what the launch leaves IS the output and goes straight into the caller's
-	// rows, as run_boxfused_emit's (a row the launch writes has one spare dword behind its last possible output: channel_kernel.h)
-	cr.raw_direct = box && c.mode == RTLFM_MODE_RAW && !c.squelch_level && !c.report_levels && out_stride / 2 >= (size_t)cr.Tin / cr.D + 2;
+	rtlfm_gpu *h = rf.h;
+	const RunGeom &g = rf.pl.g;
+	const bool direct = rf.pl.rest == RTLFM_REST_NONE;
+	cr.nsrc = h->nstreams / h->chan_per;
+	cr.nblocks = rf.nblocks;
+	if (rf.pl.route != RTLFM_ROUTE_CHAN_BOXCAR && h->src_hist_srcs < cr.nsrc) return -ENOMEM;  // (ensure_history failed in the setter, which said so)
 	int r;
-	if (!cr.raw_direct && (r = ensure_chan_iq(h)) < 0) return r;
-	cr.tp = plan_tail(h, nblocks);
-	if (!cr.raw_direct && cr.tp.any() && (r = ensure_res_buffers(h, d_iq, iq_extent(h, stream_stride, nblocks))) < 0) return r;
-	cr.target_waves = cr.tp.any() ? h->fws.target_waves_tail : h->fws.target_waves;
-	cr.dcnt = h->d_cnt[h->step & 1];
-	cr.sin = h->st[h->st_cur]; cr.sout = h->st[(h->st_cur + 1) % 3];
+	if (!direct && ((r = ensure_chan_iq(h)) < 0 || (r = rf.ensure_res()) < 0)) return r;
+	cr.target_waves = rf.pl.tp.any() ? h->fws.target_waves_tail : h->fws.target_waves;
+	cr.dcnt = rf.dcnt;
+	cr.sin = rf.sin; cr.sout = rf.sout;
 	cr.hist_in = h->d_src_hist[h->src_hist_cur]; cr.hist_out = h->d_src_hist[h->src_hist_cur ^ 1];
 	channel::Frame &f = cr.f;
 	f = channel::Frame{};
-	f.iq = d_iq; f.src_stride = stream_stride;
+	f.iq = rf.d_iq; f.src_stride = rf.stream_stride;
 	f.pos = (uint32_t)h->chan_pos;
-	f.T = cr.Tin; f.D = cr.D;
-	f.maxout = cr.maxout;
+	f.T = g.Tin; f.D = g.D;
+	f.maxout = g.maxout;
 	f.per_source = h->chan_per;
-	f.Y = cr.raw_direct ? reinterpret_cast<uint32_t *>(d_out) : h->chan_iq;
-	f.ystride = cr.raw_direct ? out_stride / 2 : h->chan_stride;
+	f.Y = direct ? reinterpret_cast<uint32_t *>(rf.d_out) : h->chan_iq.get();
+	f.ystride = direct ? rf.out_stride / 2 : h->chan_stride;
 	f.cnt = cr.dcnt; f.sin = cr.sin; f.sout = cr.sout;
 	return 0;
 }
@@ -2405,17 +2241,17 @@ static int launch_channel_boxcar(rtlfm_gpu *h, const ChanRun &cr)
 	p.f = cr.f;
 	p.steps = h->d_chan_steps; p.table = h->d_chan_table;
 	p.groups = (h->chan_per + channel::kWaves - 1) / channel::kWaves;
-	p.f.ntiles = (cr.Tin + channel::kTileSamples - 1) / channel::kTileSamples;
-	channel::plan(h->nstreams, p.f.ntiles, cr.D, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs, &p.f.tiles_per_seg);
+	p.f.ntiles = (cr.g.Tin + channel::kTileSamples - 1) / channel::kTileSamples;
+	channel::plan(h->nstreams, p.f.ntiles, cr.g.D, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs, &p.f.tiles_per_seg);
 	const size_t grid = (size_t)cr.nsrc * p.f.segs * p.groups;
 	if (grid > 0x7fffffffu) return -E2BIG;
 	if (h->opt.source_dc) {
 		p.dc = h->d_sdc; p.dc_stride = h->sdc_stride;
-		if (cr.D >= channel::kStageMinD) channel::k_channel_boxcar<true, true><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+		if (cr.g.D >= channel::kStageMinD) channel::k_channel_boxcar<true, true><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
 		else channel::k_channel_boxcar<false, true><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
 		return 0;
 	}
-	if (cr.D >= channel::kStageMinD) channel::k_channel_boxcar<true, false><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
+	if (cr.g.D >= channel::kStageMinD) channel::k_channel_boxcar<true, false><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
 	else channel::k_channel_boxcar<false, false><<<(unsigned)grid, channel::kWaves * 64, 0, h->stream>>>(p);
 	return 0;
 }
@@ -2434,13 +2270,13 @@ static int launch_channel_fir(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		p.steps = h->d_chan_steps; p.table = h->d_chan_table; p.taps8 = h->d_fir_taps8;
 		p.ntaps = h->fir_ntaps; p.nt8 = chanfir::padded_taps(h->fir_ntaps); p.halo = chanfir::halo_of(h->fir_ntaps); p.shift = h->fir_shift;
 		p.groups = (h->chan_per + chanfir::kWaves - 1) / chanfir::kWaves;
-		p.f.ntiles = (cr.Tin + chanfir::kTile - 1) / chanfir::kTile;
+		p.f.ntiles = (cr.g.Tin + chanfir::kTile - 1) / chanfir::kTile;
 		// (kMaxD's limit is the boxcar's warm-up tile; here every D goes with every segmentation: D = 1 for the plan)
 		channel::plan(S, p.f.ntiles, 1, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs, &p.f.tiles_per_seg);
 		const size_t grid = (size_t)cr.nsrc * p.f.segs * p.groups;
 		if (grid > 0x7fffffffu) return -E2BIG;
 		if (h->opt.source_dc) {
-			p.dc = h->d_sdc; p.dc_stride = h->sdc_stride; p.dc_entries = channel::kDcHist + cr.Tin / channel::kDcPiece;
+			p.dc = h->d_sdc; p.dc_stride = h->sdc_stride; p.dc_entries = channel::kDcHist + cr.g.Tin / channel::kDcPiece;
 			chanfir::k_channel_fir<true><<<(unsigned)grid, chanfir::kWaves * 64, chanfir::lds_bytes(h->fir_ntaps) + chanfir::kDcLds, q>>>(p);
 			return 0;
 		}
@@ -2468,11 +2304,11 @@ static int launch_channel_fir(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		cr.f.iq, cr.f.src_stride, h->cfg.block_len, cr.nblocks, S, h->chan_per, h->d_chan_steps, h->d_chan_table, (uint32_t)h->chan_pos,
 		h->chan_fir_x + halo, h->chan_fir_xstride, nullptr, 0, 0);
 	}
-	chanfir::k_channel_fir_plain<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->chan_fir_x, h->chan_fir_xstride, S, cr.Tin, cr.D,
-	                                                                          h->d_fir_taps, h->fir_ntaps, h->fir_shift, cr.maxout, h->chan_iq,
+	chanfir::k_channel_fir_plain<<<grid_for((size_t)S * cr.g.maxout), 256, 0, q>>>(h->chan_fir_x, h->chan_fir_xstride, S, cr.g.Tin, cr.g.D,
+	                                                                          h->d_fir_taps, h->fir_ntaps, h->fir_shift, cr.g.maxout, h->chan_iq,
 	                                                                          h->chan_stride, cr.dcnt, cr.sin, cr.sout);
 	channel::k_source_history<<<grid_for((size_t)cr.nsrc * (channel::kHist / 8)), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, cr.hist_out,
-	                                                                                        cr.nsrc, cr.Tin);
+	                                                                                        cr.nsrc, cr.g.Tin);
 	return 0;
 }
 
@@ -2487,13 +2323,13 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 	const int bins_stride = ps ? h->chan_per : 0;
 	const int sv = h->sv.writing;  // -1: no survey (run_device_impl)
 	if (fused_path) {
-		const chanbank::Geometry g = chanbank::geometry(h->bank_m, h->bank_ntaps, cr.D, sv >= 0);
+		const chanbank::Geometry g = chanbank::geometry(h->bank_m, h->bank_ntaps, cr.g.D, sv >= 0);
 		chanbank::BankParams p{};
 		p.f = cr.f;
 		p.hist_in = cr.hist_in; p.hist_out = cr.hist_out;
 		p.taps2 = h->d_bank_taps2; p.tw = h->d_bank_tw; p.bins = bins; p.bins_stride = bins_stride;
 		p.m = g.m; p.Q = g.Q; p.Qp = g.Qp; p.lead = g.lead; p.F = g.F; p.Ls = g.Ls; p.Fs = g.Fs; p.shift = h->bank_shift;
-		p.f.ntiles = (cr.maxout + g.F - 1) / g.F;
+		p.f.ntiles = (cr.g.maxout + g.F - 1) / g.F;
 		// (frames are independent: every D goes with every segmentation - D = 1 for the plan; one workgroup per source and segment)
 		channel::plan(cr.nsrc * chanbank::kWaves, p.f.ntiles, 1, cr.target_waves, h->fws.min_tiles, h->fws.tiles_per_seg, &p.f.segs,
 		              &p.f.tiles_per_seg);
@@ -2512,52 +2348,58 @@ static int launch_channel_bank(rtlfm_gpu *h, bool fused_path, const ChanRun &cr)
 		if (dc) chanbank::k_channel_bank_survey_dc<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
 		else chanbank::k_channel_bank_survey<<<(unsigned)grid, chanbank::kWaves * 64, g.lds, q>>>(p);
 		chanbank::k_bank_survey_reduce<<<grid_for((size_t)cr.nsrc << h->bank_m), 256, 0, q>>>(h->sv.d_partial, p.f.segs, h->bank_m, cr.nsrc,
-		                                                                                   h->chan_per, cr.Tin, cr.D, cr.sin, h->sv.d_power[sv],
+		                                                                                   h->chan_per, cr.g.Tin, cr.g.D, cr.sin, h->sv.d_power[sv],
 		                                                                                   h->sv.d_frames[sv]);
 		return 0;
 	}
-	const size_t vneed = ((size_t)cr.nsrc * cr.maxout) << h->bank_m;
+	const size_t vneed = ((size_t)cr.nsrc * cr.g.maxout) << h->bank_m;
 	int r = ensure_bank_v(h, vneed);
 	if (r < 0) return r;
 	if (h->opt.source_dc)
 		chanbank::k_bank_sums<true><<<grid_for(vneed), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
-		                                                        h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.Tin, cr.D,
-		                                                        cr.maxout, cr.sin, h->bank_v, h->d_sdc, h->sdc_stride);
+		                                                        h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.g.Tin, cr.g.D,
+		                                                        cr.g.maxout, cr.sin, h->bank_v, h->d_sdc, h->sdc_stride);
 	else
 		chanbank::k_bank_sums<false><<<grid_for(vneed), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, h->d_bank_taps, h->bank_ntaps, h->bank_m,
-		                                                            h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.Tin, cr.D,
-		                                                            cr.maxout, cr.sin, h->bank_v, nullptr, 0);
-	chanbank::k_bank_fft<<<grid_for((size_t)cr.nsrc * cr.maxout), 256, 0, q>>>(h->bank_v, h->d_bank_sine, h->bank_m, cr.nsrc, h->chan_per, cr.Tin,
-	                                                                          cr.D, cr.maxout, cr.sin);
-	chanbank::k_bank_scatter<<<grid_for((size_t)S * cr.maxout), 256, 0, q>>>(h->bank_v, bins, (size_t)bins_stride, h->bank_m, S, h->chan_per, cr.Tin,
-	                                                                        cr.D, cr.maxout, h->chan_iq, h->chan_stride, cr.dcnt, cr.sin, cr.sout);
+		                                                            h->bank_shift, (uint32_t)h->chan_pos, cr.nsrc, h->chan_per, cr.g.Tin, cr.g.D,
+		                                                            cr.g.maxout, cr.sin, h->bank_v, nullptr, 0);
+	chanbank::k_bank_fft<<<grid_for((size_t)cr.nsrc * cr.g.maxout), 256, 0, q>>>(h->bank_v, h->d_bank_sine, h->bank_m, cr.nsrc, h->chan_per, cr.g.Tin,
+	                                                                          cr.g.D, cr.g.maxout, cr.sin);
+	chanbank::k_bank_scatter<<<grid_for((size_t)S * cr.g.maxout), 256, 0, q>>>(h->bank_v, bins, (size_t)bins_stride, h->bank_m, S, h->chan_per, cr.g.Tin,
+	                                                                        cr.g.D, cr.g.maxout, h->chan_iq, h->chan_stride, cr.dcnt, cr.sin, cr.sout);
 	if (sv >= 0)
-		chanbank::k_bank_power_plain<<<grid_for((size_t)cr.nsrc << h->bank_m), 256, 0, q>>>(h->bank_v, h->bank_m, cr.nsrc, h->chan_per, cr.Tin, cr.D,
-		                                                                                 cr.maxout, cr.sin, h->sv.d_power[sv], h->sv.d_frames[sv]);
+		chanbank::k_bank_power_plain<<<grid_for((size_t)cr.nsrc << h->bank_m), 256, 0, q>>>(h->bank_v, h->bank_m, cr.nsrc, h->chan_per, cr.g.Tin, cr.g.D,
+		                                                                                 cr.g.maxout, cr.sin, h->sv.d_power[sv], h->sv.d_frames[sv]);
 	channel::k_source_history<<<grid_for((size_t)cr.nsrc * (channel::kHist / 8)), 256, 0, q>>>(cr.f.iq, cr.f.src_stride, cr.hist_in, cr.hist_out,
-	                                                                                        cr.nsrc, cr.Tin);
+	                                                                                        cr.nsrc, cr.g.Tin);
 	return 0;
 }
 
-// The channel front end of a run and what follows it.  The bank, while set, takes precedence over the filter, and the
-// filter over the boxcar; fused_path: the one-launch kernel, else the filter's or the bank's cross-check (the boxcar's is
-// run_staged behind k_channel_mix: not here).
-static int run_channels(rtlfm_gpu *h, bool fused_path, const uint8_t *d_iq, size_t stream_stride, int nblocks, int16_t *d_out,
-                        size_t out_stride, int32_t *d_out_len)
+// ROUTE_CHAN_BOXCAR / _FIR / _FIR_PLAIN / _BANK / _BANK_PLAIN: the channel front end of a run and what follows it.  (The
+// boxcar's cross-check is run_staged behind k_channel_mix, ROUTE_CHAN_MIX: not here.)  Option source_dc's pre-pass runs
+// inside the timed pair, as the front ends' raw-DC pre-pass does.
+static int run_channels(RunFrame &f)
 {
-	const bool bank = h->bank_K > 0, fir = !bank && h->fir_ntaps > 0;
-	ChanRun cr;
-	int r = chan_run_prepare(h, !bank && !fir, d_iq, stream_stride, nblocks, d_out, out_stride, cr);
+	rtlfm_gpu *h = f.h;
+	const int route = f.pl.route;
+	ChanRun cr{f.pl.g};
+	int r = chan_run_prepare(f, cr);
 	if (r < 0) return r;
-	std::pair<Event, Event> ev;
-	if ((r = timing_begin(h, ev)) < 0) return r;
-	if (h->opt.source_dc && (r = launch_source_dc(h, d_iq, stream_stride, nblocks, cr.sin, cr.sout, bank || fir)) < 0) return r;
-	r = bank ? launch_channel_bank(h, fused_path, cr) : fir ? launch_channel_fir(h, fused_path, cr) : launch_channel_boxcar(h, cr);
+	if ((r = timing_begin(h, f.ev)) < 0) return r;
+	if (h->opt.source_dc && (r = launch_source_dc(h, f.d_iq, f.stream_stride, f.nblocks, cr.sin, cr.sout, route != RTLFM_ROUTE_CHAN_BOXCAR)) < 0)
+		return r;
+	switch (route) {
+	case RTLFM_ROUTE_CHAN_BOXCAR: r = launch_channel_boxcar(h, cr); break;
+	case RTLFM_ROUTE_CHAN_FIR: r = launch_channel_fir(h, true, cr); break;
+	case RTLFM_ROUTE_CHAN_FIR_PLAIN: r = launch_channel_fir(h, false, cr); break;
+	case RTLFM_ROUTE_CHAN_BANK: r = launch_channel_bank(h, true, cr); break;
+	case RTLFM_ROUTE_CHAN_BANK_PLAIN: r = launch_channel_bank(h, false, cr); break;
+	default: return -EFAULT;  // planning bug
+	}
 	if (r < 0) return r;
-	if ((r = timing_end(h, ev)) < 0) return r;
-	const int32_t *cnt = cr.varcnt ? cr.dcnt : nullptr;
-	if (cr.raw_direct) return raw_out_len(h, d_out_len, cnt, cr.T);
-	return run_back_half(h, h->chan_iq, h->chan_stride, cr.T, cr.N0, cr.D, nblocks, cnt, cr.tp, d_out, out_stride, d_out_len);
+	if ((r = timing_end(h, f.ev)) < 0) return r;
+	if (f.pl.rest == RTLFM_REST_NONE) return raw_out_len(f);
+	return run_back_half(f, h->chan_iq, h->chan_stride);
 }
 
 // Option source_dc's pre-pass alone, as one timed pair (tools/source_dc_bench.py): the sums and the smoothing over d_iq's
@@ -2614,7 +2456,7 @@ static int ensure_gate(rtlfm_gpu *h)
 // The squelch gate, the last launch of a run (option squelch_gate): on the handle's stream, behind the audio tail wherever
 // that ran.  Reads this step's sin and the finished rows; writes the records, the clamped squelch_hits of sout and the
 // per-stream counts (d_cnt of this step and the caller's d_out_len).
-static int launch_gate(rtlfm_gpu *h, int nblocks, int16_t *d_out, size_t out_stride, int32_t *d_out_len)
+static int launch_gate(rtlfm_gpu *h, const RunGeom &g, int nblocks, int16_t *d_out, size_t out_stride, int32_t *d_out_len)
 {
 	const rtlfm_cfg &c = h->cfg;
 	if (gate_supported(c) < 0) return -ENOTSUP;  // (a short buffer of a ragged run may be one the passes do not divide)
@@ -2629,8 +2471,7 @@ static int launch_gate(rtlfm_gpu *h, int nblocks, int16_t *d_out, size_t out_str
 	p.rec_stride = h->gate_rec_stride ? h->gate_rec_stride : nblocks;
 	p.cnt = h->d_cnt[par]; p.cnt2 = d_out_len;
 	p.nblocks = nblocks;
-	p.N = c.downsample_passes > 0 ? (int)((c.block_len / 2) >> c.downsample_passes) : (int)(c.block_len / 2);
-	p.D = c.downsample_passes > 0 ? 1 : c.downsample;
+	p.N = g.Nblk; p.D = g.D;
 	p.mul = c.mode == RTLFM_MODE_RAW ? 2 : 1;
 	p.level = c.squelch_level; p.conseq = h->opt.conseq_squelch;
 	std::pair<Event, Event> ev;
@@ -2640,75 +2481,63 @@ static int launch_gate(rtlfm_gpu *h, int nblocks, int16_t *d_out, size_t out_str
 	return timing_end(h, ev);
 }
 
-// one execution of a run: everything rtlfm_gpu_run_device does except moving on to the next state copy / step
+// what of the handle steers a run's plan (rtlfm_route_opts): the bank, while set, takes precedence over the filter, and
+// the filter over the boxcar
+static rtlfm_route_opts route_opts(const rtlfm_gpu *h)
+{
+	const int channels = h->chan_per <= 0 ? RTLFM_CHANNELS_OFF
+	                     : h->bank_K > 0 ? RTLFM_CHANNELS_BANK : h->fir_ntaps > 0 ? RTLFM_CHANNELS_FILTER : RTLFM_CHANNELS_MIXER;
+	return rtlfm_route_opts{h->path, h->fws.pass0_engine, h->opt.squelch_fused, h->opt.deep_rest, h->opt.deemph_four_pass,
+	                        h->opt.deemph_sequential, h->opt.arb_serial, h->no_deemph_scan ? 1 : 0, channels};
+}
+
+extern "C" int rtlfm_run_route(const rtlfm_cfg *cfg, int nstreams, int nblocks, unsigned out_low_bits, size_t out_stride,
+                               const rtlfm_route_opts *opts, rtlfm_route_plan *plan)
+{
+	return run_route(cfg, nstreams, nblocks, out_low_bits, out_stride, opts, plan);
+}
+
+// one execution of a run: everything rtlfm_gpu_run_device does except moving on to the next state copy / step.
+// The plan (run_plan.h) decides what can be decided before the first launch; one launcher per route does the rest.
 static int run_device_once(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks,
                            int16_t *d_out, size_t out_stride, int32_t *d_out_len)
 {
 	rtl_debug::poison_lds(h->stream);  // RTLFM_POISON=1 only
 	const size_t S = (size_t)h->nstreams;
-	// the squelch / -L with rms()'s sums taken by the front end itself (round 5) comes before the emit mode
-	const bool fuse_sq = h->opt.squelch_fused && fused::supported_sq(h->cfg);
-	bool can_fuse = fused::supported(h->cfg, nblocks) || fuse_sq;
-	// the raw DC block rides on the MFMA pass 0, and only that engine has the partial-tile kernels (-W n)
-	const bool mfma_only = h->cfg.dc_block_raw || fused::needs_partial_tiles(h->cfg);
-	if (mfma_only && fused::effective_engine(h->fws) != 1) can_fuse = false;
-	if (can_fuse && plan_tail(h, nblocks).oop() == 0 && (((uintptr_t)d_out & 15) || (out_stride & 7)))
-		can_fuse = false;  // the fused kernel stores 16-byte vectors straight into d_out
-	const bool can_box = boxfused::supported(h->cfg) || (h->opt.squelch_fused && boxfused::supported_sq(h->cfg));
-	const bool can_box_emit = boxfused::supported_emit(h->cfg);
-	const bool can_deep = fused::supported_emit(h->cfg) && !(mfma_only && fused::effective_engine(h->fws) != 1);
+	const int par = (int)(h->step & 1);
 	int r;
-	{
-		// this step reuses the res[] / d_cnt[] set and the state copy the step before last handed to
-		// its audio tail
-		const int par = (int)(h->step & 1);
-		if (h->tail_pending[par]) {
-			HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_tail[par], 0));
-			h->tail_pending[par] = false;
-		}
+	// this step reuses the res[] / d_cnt[] set and the state copy the step before last handed to
+	// its audio tail
+	if (h->tail_pending[par]) {
+		HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_tail[par], 0));
+		h->tail_pending[par] = false;
 	}
-	if (h->chan_per > 0) {
-		// Channels on: the boxcar has the one-launch front end; every other decimator runs staged behind k_channel_mix.
-		// (Both leave the other fields of the record to the copy, as the staged kernels always do.)
-		const bool boxed = h->path != 1 && h->cfg.downsample_passes == 0;
-		if (h->path == 2 && !boxed) return -ENOTSUP;
-		HIP_TRY(hipMemcpyAsync(h->st[(h->st_cur + 1) % 3], h->st[h->st_cur], S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
-		// (a filter or a bank is only ever set on a handle without fifth_order passes: with one, both paths are its own)
-		r = boxed || h->bank_K > 0 || h->fir_ntaps > 0 ? run_channels(h, boxed, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len)
-		                                                 : run_staged(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
-		if (r < 0) return r;
-		h->last_path = boxed ? 2 : 1;
-		HIP_TRY(hipGetLastError());
-		return 0;
-	}
-	if (h->path == 2 && !can_fuse && !can_box && !can_box_emit && !can_deep) return -ENOTSUP;
+	const RunPlan pl = plan_run(h->cfg, h->nstreams, nblocks, route_opts(h), (unsigned)((uintptr_t)d_out & 15), out_stride);
+	if (pl.route < 0) return pl.route;
 	// the callback's ADC statistics (src/rtl_fm.c:1302-1324) come before the conversion: in front of whichever front end runs
+	// (channels on: the readers and the gate are off - rtlfm_gpu_set_channels and the options refuse each other)
 	if (h->opt.input_stats && (r = ensure_input_stats(h)) < 0) return r;
 	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
 	if ((r = launch_input_readers(h, d_iq, stream_stride, h->cfg.block_len, nblocks, (int)S, 0, nblocks)) < 0) return r;
-	// state is double-buffered: kernels read st[cur], write st[cur^1].  The staged kernels each
-	// update their own fields, so the record is copied first; the fused kernels copy it themselves.
-	if (!(h->path != 1 && (can_fuse || can_box || can_box_emit || can_deep)))
-		HIP_TRY(hipMemcpyAsync(h->st[(h->st_cur + 1) % 3], h->st[h->st_cur], S * sizeof(state_t),
-		                       hipMemcpyDeviceToDevice, h->stream));
-	if (h->path != 1 && can_box) {
-		r = run_boxfused(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
-		h->last_path = 2;
-	} else if (h->path != 1 && can_box_emit) {
-		r = run_boxfused_emit(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
-		h->last_path = 2;
-	} else if (h->path != 1 && can_deep && !(can_fuse && fuse_sq)) {
-		r = run_fused_emit(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
-		h->last_path = 2;
-	} else if (h->path != 1 && can_fuse) {
-		r = run_fused(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
-		h->last_path = 2;
-	} else {
-		r = run_staged(h, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len);
-		h->last_path = 1;
+	// state is double-buffered: kernels read st[cur], write the next copy.  The staged kernels and the channel front ends
+	// each update their own fields, so the record is copied first; k_fused and k_boxcar_scan copy it themselves.
+	state_t *sout = h->st[(h->st_cur + 1) % 3];
+	if (pl.copy_state) HIP_TRY(hipMemcpyAsync(sout, h->st[h->st_cur], S * sizeof(state_t), hipMemcpyDeviceToDevice, h->stream));
+	RunFrame f{h, pl, d_iq, stream_stride, nblocks, d_out, out_stride, d_out_len, h->stream, h->st[h->st_cur], sout, h->d_cnt[par]};
+	switch (pl.route) {
+	case RTLFM_ROUTE_STAGED:
+	case RTLFM_ROUTE_CHAN_MIX: r = run_staged(f); break;
+	case RTLFM_ROUTE_FUSED: r = run_fused(f); break;
+	case RTLFM_ROUTE_FUSED_EMIT: r = run_fused_emit(f); break;
+	case RTLFM_ROUTE_BOXCAR: r = run_boxfused(f); break;
+	case RTLFM_ROUTE_BOXCAR_EMIT: r = run_boxfused_emit(f); break;
+	default: r = run_channels(f); break;
 	}
 	if (r < 0) return r;
-	if (h->opt.squelch_gate && (r = launch_gate(h, nblocks, d_out, out_stride, d_out_len)) < 0) return r;
+	h->last_path = pl.last_path;
+	h->last_route = pl.route;
+	h->last_rest = pl.rest;
+	if (h->opt.squelch_gate && (r = launch_gate(h, pl.g, nblocks, d_out, out_stride, d_out_len)) < 0) return r;
 	HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -3505,6 +3334,8 @@ static void view_done(rtlfm_gpu *h, const rtlfm_gpu &v)
 	h->fws.stamp_seq = v.fws.stamp_seq;
 	h->fws.stamp_last = v.fws.stamp_last;
 	h->last_path = v.last_path;
+	h->last_route = v.last_route;
+	h->last_rest = v.last_rest;
 }
 
 // a run that holds short buffers: buffer by buffer, ranges of streams with equal length
@@ -4070,7 +3901,7 @@ extern "C" const char *rtlfm_gpu_strerror(int err)
 	                      "not on a run that holds a short buffer";
 	case -EDOM: return "outside the reference's own domain: a boxcar longer than the buffer (fm_demod reads lowpassed[-2]), low_pass_simple on a "
 	                   "count its step does not divide (src/rtl_fm.c:740), or rate_out2 > rate_out with low_pass_real (division by zero, :769)";
-	case -E2BIG: return "more blocks than cfg.max_blocks";
+	case -E2BIG: return "more blocks than cfg.max_blocks; a configuration whose max_blocks buffers exceed 2^31 - 1 complex samples per stream";
 	case -ENOBUFS: return "output buffer too small";
 	case -EIO: return "HIP runtime error";
 	case -ENODATA: return "no clock stamps recorded (rtlfm_gpu_clock_probe, fused fifth_order path only); no records of this kind "

@@ -17,6 +17,7 @@
 #pragma once
 
 #include "dsp_device.h"
+#include "run_plan.h"
 
 #include <type_traits>
 
@@ -636,16 +637,7 @@ struct DeepRestParams {
 	const int32_t *lut;
 	const state_t *sin; state_t *sout;
 };
-// tail lengths per level for `passes` (index 0 = level 6): what the next level, the filter and the demodulator reach back
-__host__ __device__ inline void deep_rest_tails(int passes, int fir, int k[6])
-{
-	const int L = passes - 6;
-	k[L] = fir ? 10 : 1;
-	for (int j = L - 1; j >= 0; j--) {
-		k[j] = 2 * k[j + 1] + 5;
-		if (k[j] < 6) k[j] = 6;
-	}
-}
+// (tail lengths per level for `passes`: deep_rest_tails(), run_plan.h)
 
 __global__ void __launch_bounds__(256) k_deep_rest(const DeepRestParams p)
 {
@@ -1079,7 +1071,7 @@ __global__ void k_deemph_identity(const int16_t *__restrict__ R, size_t rstride,
 //   C (one lane per chunk, all chunks at once): replay the chunk from its incoming state, writing.
 // Every step is the reference's integer step; chunks whose interval does not contract in time
 // (or a true state outside the tracked interval) are simply walked in B.
-constexpr int kDeemphGap = 62;  // candidates per chunk must fit a wave
+// (kDeemphGap = 62, run_plan.h: candidates per chunk must fit a wave)
 struct DeemphChunk {
 	int32_t lo;   // biased lower end after k samples
 	int32_t k;    // samples consumed before the table applies; -1: not contracted

@@ -31,6 +31,7 @@ class GpuDemod:
         check(self.lib.rtlfm_gpu_create(C.byref(cfg), nstreams, device, C.byref(h)), "rtlfm_gpu_create")
         self._h = h
         self._per_source = 0  # channels (set_channels): 0 = off
+        self._path = 0        # set_path
         for k, v in (options or {}).items():
             self.set_option(k, v)
         # the scanner's squelch gate (include/rtlfm_hip.h, rtlfm_gpu_gate): off unless asked for
@@ -409,10 +410,33 @@ class GpuDemod:
 
     def set_path(self, path: int):
         check(self.lib.rtlfm_gpu_set_path(self._h, path), "rtlfm_gpu_set_path")
+        self._path = min(path, 2)  # (3 / 4: path 2 with the pass-0 engine forced, which the option pass0_engine reads back)
 
     @property
     def last_path(self) -> int:
         return self.lib.rtlfm_gpu_last_path(self._h)
+
+    @property
+    def last_route(self) -> int:
+        """Which front end the last run took (``capi.ROUTE_*``, enum rtlfm_route); 0 before the first run."""
+        return self.get_option("last_route")
+
+    @property
+    def last_rest(self) -> int:
+        """What followed it (``capi.REST_*``, enum rtlfm_rest)."""
+        return self.get_option("last_rest")
+
+    def run_route(self, nblocks: int, d_out_ptr: int = 0, out_stride: int | None = None, no_deemph_scan: bool = False):
+        """The plan a run of ``nblocks`` buffers of this handle into rows at ``d_out_ptr``, ``out_stride`` int16 apart
+        (default: ``result_cap(nblocks)``), will take - ``run_route()`` below with the handle's configuration, its stream
+        count, its path and options as they are set now, and the channels that are on."""
+        o = {k: self.get_option(k) for k in ("pass0_engine", "squelch_fused", "deep_rest", "deemph_four_pass", "deemph_sequential", "arb_serial")}
+        channels = capi.CHANNELS_OFF
+        if self._per_source:
+            channels = (capi.CHANNELS_BANK if self.get_channel_bank()[0] else
+                        capi.CHANNELS_FILTER if self.channel_filter()[0].size else capi.CHANNELS_MIXER)
+        return run_route(self.cfg, self.nstreams, nblocks, d_out_ptr & 15, self.result_cap(nblocks) if out_stride is None else out_stride,
+                         path=self._path, no_deemph_scan=int(no_deemph_scan), channels=channels, **o)
 
     def timing_enable(self, on: bool = True):
         check(self.lib.rtlfm_gpu_timing_enable(self._h, int(on)), "rtlfm_gpu_timing_enable")
@@ -443,6 +467,20 @@ def optimal_settings(cfg: RtlfmCfg, freq: int, rate_in: int, min_capture_rate: i
                                              int(use_fifth_order), edge, C.byref(cf), C.byref(cr)),
           "rtlfm_optimal_settings")
     return cf.value, cr.value
+
+
+def run_route(cfg: RtlfmCfg, nstreams: int, nblocks: int, out_low_bits: int = 0, out_stride: int | None = None, **options):
+    """``rtlfm_run_route``: the plan (``capi.RtlfmRoutePlan``: route, rest, last_path, ...) a run of ``nblocks`` buffers of
+    ``nstreams`` streams takes - what ``last_route`` / ``last_rest`` / ``last_path`` read after it -, from the run's own
+    planner (no GPU).  ``out_low_bits``: the low four bits of the first row's address; ``out_stride``: int16 between rows
+    (default: ``GpuDemod.result_cap``'s).  ``options`` as ``capi.RtlfmRouteOpts``; RtlfmError where the run would be
+    refused (-ENOTSUP: ``path=2`` without a fused form)."""
+    if out_stride is None:
+        out_stride = (capi.load().rtlfm_result_cap(C.byref(cfg)) * nblocks + 16 + 63) & ~63
+    plan = capi.RtlfmRoutePlan()
+    check(capi.load().rtlfm_run_route(C.byref(cfg), nstreams, nblocks, out_low_bits, out_stride,
+                                      C.byref(capi.RtlfmRouteOpts.default(**options)), C.byref(plan)), "rtlfm_run_route")
+    return plan
 
 
 def deemph_a(rate_out: int, time_constant_us: int = 75) -> int:
