@@ -1504,6 +1504,7 @@ static int tail_deemph_spec(TailRun &r, const DeemphForm &f)
 		// (the plan promised an out-of-place stage and the run turned out otherwise - rows that do not share their
 		// alignment, a run that is shorter than planned: the sequential filter in place, then a copy)
 		tail_deemph_sequential(r, f);
+		r.stage_done("sequential");
 		HIP_TRY(hipMemcpy2DAsync(r.dst, r.dst_stride * sizeof(int16_t), r.cur, r.cur_stride * sizeof(int16_t), (size_t)r.T * sizeof(int16_t), r.S,
 		                         hipMemcpyDeviceToDevice, r.q));
 	}
@@ -1694,6 +1695,7 @@ static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_s
 		r.out_of_place();
 		r.T /= c.post_downsample;
 		k_post_downsample<<<grid_for((size_t)S * r.T), 256, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, r.T, S, c.post_downsample);
+		r.stage_done("post");
 		r.arrived();
 		r.Nblk = r.T / nblocks; r.D = 1;
 	}
@@ -1701,8 +1703,8 @@ static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_s
 	int e = 0;
 	switch (form) {
 	case Deemph::none: break;
-	case Deemph::identity: k_deemph_identity<<<grid_for(S, 64), 64, 0, r.q>>>(r.cur, r.cur_stride, r.T, r.cnt, S, r.sout); break;
-	case Deemph::sequential: tail_deemph_sequential(r, f); break;
+	case Deemph::identity: k_deemph_identity<<<grid_for(S, 64), 64, 0, r.q>>>(r.cur, r.cur_stride, r.T, r.cnt, S, r.sout); r.stage_done("identity"); break;
+	case Deemph::sequential: tail_deemph_sequential(r, f); r.stage_done("sequential"); break;
 	case Deemph::spec: e = tail_deemph_spec(r, f); break;
 	case Deemph::spec_lpr: e = tail_deemph_spec_lpr(r, f, cnt_dst); break;
 	case Deemph::spec_arb: e = tail_deemph_spec_arb(r, f, cnt_dst); break;
@@ -1716,6 +1718,7 @@ static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_s
 		k_adc_sums<<<S * nblocks, 256, 0, r.q>>>(r.cur, r.cur_stride, r.Nblk, r.D, nblocks, r.sin, h->d_adc_sums);
 		k_adc_smooth_apply<<<S * nblocks, 256, (size_t)(nblocks + 1) * sizeof(int32_t), r.q>>>(r.cur, r.cur_stride, r.Nblk, r.D, nblocks,
 		                                                                                    c.adc_block_const, h->d_adc_sums, r.sin, r.sout);
+		r.stage_done("adc");
 	}
 	const bool resampled = whole_tail(form) || form == Deemph::four_pass_lpr;
 	if (tp.lpr && !resampled) {
@@ -1723,6 +1726,7 @@ static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_s
 		const int maxout = (int)(((long long)c.rate_out - 1 + (long long)r.T * c.rate_out2) / c.rate_out);
 		k_low_pass_real<<<grid_for((size_t)S * (maxout + 1)), 256, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, r.T, r.cnt, S, c.rate_out,
 		                                                                   c.rate_out2, r.sin, r.sout, h->d_cnt2);
+		r.stage_done("lpr");
 		r.arrived();
 	} else if (tp.arb && !resampled) {
 		// arbitrary_resample per buffer on whatever result_len it has (src/rtl_fm.c:1168-1177, 1270)
@@ -1735,8 +1739,10 @@ static int run_tail(rtlfm_gpu *h, const TailPlan &tp, int16_t *cur, size_t cur_s
 		if (any_up)
 			k_arb_upsample<<<grid_for((size_t)S * nblocks * l2hi), 256, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, ap, l2hi, nblocks, S, r.sin,
 			                                                                     h->d_cnt2);
+		if (any_up) r.stage_done("arb up");
 		if (any_down)
 			k_arb_downsample<<<grid_for((size_t)S * nblocks, 64), 64, 0, r.q>>>(r.cur, r.cur_stride, r.dst, r.dst_stride, ap, nblocks, S, r.sin, h->d_cnt2);
+		if (any_down) r.stage_done("arb down");
 		r.arrived();
 	}
 	if (r.cur != final_dst) return -EFAULT;  // routing bug

@@ -186,8 +186,9 @@ inline int validate_cfg(const rtlfm_cfg *c)
 			} else if (c->resampler == RTLFM_RESAMPLE_ARBITRARY) {
 				// per < 0: the per-buffer count is n or n + 1 (boxcar not dividing the buffer)
 				int n = per < 0 ? (int)(c->block_len / 2) / c->downsample : per / c->post_downsample;
-				long long len2 = (long long)n * c->rate_out2 / c->rate_out;
-				if (len2 < 1 || n < 2) return -EINVAL;
+				// (a buffer of one sample: both resamplers read b1[1], src/rtl_fm.c:1121, 1148.  len2 == 0 - rate_out2 so small
+				// that n * rate_out2 / rate_out truncates to nothing - is a run of no output the reference makes: not refused)
+				if (n < 2) return -EINVAL;
 			} else {
 				return -EINVAL;
 			}

@@ -1440,6 +1440,30 @@ struct LprSink {
 	}
 };
 
+// low_pass_real exactly as the reference loops it (src/rtl_fm.c:762-773), for a carried prev_lpr_index outside [0, fast) -
+// rtlfm_gpu_state_set's alone.  From fast upwards the reference emits an output at EVERY input until the phase is back
+// below fast, and below zero it emits nothing for a while: the closed forms of the chunked kernels (output index and phase
+// at a chunk's start, lpr_totals) hold for neither, so such a stream is walked whole by one lane.  At most one output per
+// input: the row holds them.
+struct LprRefSink {
+	int16_t *bo;
+	int m;
+	long long phi;
+	int sl, fa, div;
+	uint32_t acc;
+	__device__ __forceinline__ void operator()(int y)
+	{
+		acc += (uint32_t)y;
+		phi += sl;
+		if (phi >= fa) {
+			bo[m++] = (int16_t)((int)acc / div);
+			phi -= fa;
+			acc = 0;
+		}
+	}
+};
+__device__ __forceinline__ bool lpr_phase_outside(long long p0, int fast) { return p0 < 0 || p0 >= fast; }
+
 template <int MAGIC>
 __global__ void __launch_bounds__(64)
 k_deemph_scan_c_lpr(const int16_t *__restrict__ R, size_t rstride, int T, const int32_t *__restrict__ cnt, int nstreams,
@@ -1458,8 +1482,22 @@ k_deemph_scan_c_lpr(const int16_t *__restrict__ R, size_t rstride, int T, const 
 	// a stream whose carried deemph state lay outside int16 was filtered in place by pass B (plain form)
 	const bool filter = incoming[s * max_chunks] != 0xffffffffu;
 	const long long p0 = sin[s].prev_lpr_index;
+	if (lpr_phase_outside(p0, fast)) {
+		// the stream's first lane walks the whole run (LprRefSink) and leaves the state; the count waits in its chunk
+		// record for k_lpr_fixup
+		if (c != 0) return;
+		LprRefSink ref{B + s * bstride, 0, p0, slow, fast, fast / slow, (uint32_t)sin[s].now_lpr};
+		const uint32_t v = deemph_walk_sink<MAGIC>(r, n, filter ? incoming[s * max_chunks] : 0u, ds, filter, ref);
+		if (filter) sout[s].deemph_avg = (int)v - 32768;
+		sout[s].now_lpr = (int)ref.acc;
+		sout[s].prev_lpr_index = (int)ref.phi;
+		LprChunk rec;
+		rec.head = 0; rec.tail = ref.acc; rec.mfirst = ref.m;
+		lc[s * max_chunks] = rec;
+		return;
+	}
 	const long long idx0 = p0 + (long long)begin * slow;
-	const int m0 = (p0 >= 0 && p0 < fast) ? (int)floor_div_pos(idx0, fast) : (int)(idx0 / fast);
+	const int m0 = (int)floor_div_pos(idx0, fast);
 	LprSink sink(B + s * bstride, m0, (int)(idx0 - (long long)m0 * fast), slow, fast, c == 0 ? (uint32_t)sin[s].now_lpr : 0u, vec != 0);
 	const uint32_t v = deemph_walk_sink<MAGIC>(r + begin, end - begin, filter ? incoming[s * max_chunks + c] : 0u, ds, filter, sink);
 	sink.finish();
@@ -1533,7 +1571,7 @@ __device__ __forceinline__ void deemph_walk_pair(const int16_t *r, int n, uint32
 __device__ __forceinline__ void lpr_totals(long long p0, int n, int slow, int fast, int &E, int &phase)
 {
 	const long long tot = p0 + (long long)n * slow;
-	E = (p0 >= 0 && p0 < fast) ? (int)floor_div_pos(tot, fast) : (int)(tot / fast);
+	E = (int)floor_div_pos(tot, fast);  // (p0 inside [0, fast): the callers send every other stream through LprRefSink)
 	phase = (int)(tot - (long long)E * fast);
 }
 
@@ -1576,7 +1614,7 @@ k_deemph_spec_lpr(int16_t *R, size_t rstride, int T, const int32_t *__restrict__
 	int n = 0, nc = 0, head = 0, carried = 0;
 	int16_t *r = nullptr;
 	long long p0 = 0;
-	bool plain = false;
+	bool plain = false, outside = false;
 	if (live) {
 		n = cnt ? cnt[s] : T;
 		r = R + s * rstride;
@@ -1585,14 +1623,15 @@ k_deemph_spec_lpr(int16_t *R, size_t rstride, int T, const int32_t *__restrict__
 		carried = sin[s].deemph_avg;
 		plain = (uint32_t)(carried + 32768) > 65535u;  // only rtlfm_gpu_state_set can do that
 		p0 = sin[s].prev_lpr_index;
+		outside = lpr_phase_outside(p0, fast);  // likewise
 	}
 	const int c_first = spw == 1 ? tid : tid - sl * max_chunks, c_step = spw == 1 ? nthreads : max_chunks;
-	if (live && !plain) {
+	if (live && !plain && !outside) {
 		for (int c = c_first; c < nc; c += c_step) {
 			int begin, end;
 			deemph_chunk_range(c, n, head, L, begin, end);
 			const long long idx0 = p0 + (long long)begin * slow;
-			const int m0 = (p0 >= 0 && p0 < fast) ? (int)floor_div_pos(idx0, fast) : (int)(idx0 / fast);
+			const int m0 = (int)floor_div_pos(idx0, fast);
 			LprSink sink(B + s * bstride, m0, (int)(idx0 - (long long)m0 * fast), slow, fast, c == 0 ? (uint32_t)sin[s].now_lpr : 0u, vec != 0, my_ring);
 			bool settled = true;
 			uint32_t v = (uint32_t)(carried + 32768);
@@ -1618,19 +1657,29 @@ k_deemph_spec_lpr(int16_t *R, size_t rstride, int T, const int32_t *__restrict__
 	__threadfence_block();  // the chunk records and outputs of this workgroup's lanes, for its finishing lanes
 	__syncthreads();
 	if (!live) return;
-	if (plain || unsettled[sl]) {
+	if (plain || outside || unsettled[sl]) {
 		if (c_first != 0) return;
 		// the reference's loop over the whole run, on the stream's first lane
+		auto filter_into = [&](auto &to) {
+			if (plain) {
+				sout[s].deemph_avg = deemph_plain(r, n, carried, (int)ds.a);
+				deemph_walk_sink<MAGIC>(r, n, 0u, ds, false, to);
+			} else {
+				sout[s].deemph_avg = (int)deemph_walk_sink<MAGIC>(r, n, (uint32_t)(carried + 32768), ds, true, to) - 32768;
+			}
+		};
+		if (outside) {
+			LprRefSink ref{B + s * bstride, 0, p0, slow, fast, fast / slow, (uint32_t)sin[s].now_lpr};
+			filter_into(ref);
+			sout[s].now_lpr = (int)ref.acc;
+			sout[s].prev_lpr_index = (int)ref.phi;
+			if (cnt_out) cnt_out[s] = ref.m;
+			return;
+		}
 		int E, phase;
 		lpr_totals(p0, n, slow, fast, E, phase);
-		const int m0 = (p0 >= 0 && p0 < fast) ? (int)floor_div_pos(p0, fast) : (int)(p0 / fast);
-		LprSink sink(B + s * bstride, m0, (int)(p0 - (long long)m0 * fast), slow, fast, (uint32_t)sin[s].now_lpr, vec != 0, my_ring);
-		if (plain) {
-			sout[s].deemph_avg = deemph_plain(r, n, carried, (int)ds.a);
-			deemph_walk_sink<MAGIC>(r, n, 0u, ds, false, sink);
-		} else {
-			sout[s].deemph_avg = (int)deemph_walk_sink<MAGIC>(r, n, (uint32_t)(carried + 32768), ds, true, sink) - 32768;
-		}
+		LprSink sink(B + s * bstride, 0, (int)p0, slow, fast, (uint32_t)sin[s].now_lpr, vec != 0, my_ring);
+		filter_into(sink);
 		sink.finish();
 		sout[s].now_lpr = (int)sink.out.tail;
 		sout[s].prev_lpr_index = phase;
@@ -1805,6 +1854,11 @@ k_lpr_fixup(const int16_t *__restrict__ R, size_t rstride, int T, const int32_t 
 	const int nc = deemph_chunks(n, head, L);
 	if (c >= nc) return;
 	const LprChunk *l0 = lc + s * max_chunks;
+	if (lpr_phase_outside(sin[s].prev_lpr_index, fast)) {
+		// k_deemph_scan_c_lpr's first lane walked the stream and left the state: only the count is to hand on
+		if (c == nc - 1) cnt_out[s] = l0[0].mfirst;
+		return;
+	}
 	const int div = fast / slow;
 	// what the chunks before c left in the accumulator since their last emission
 	auto carried = [&](int upto) {
@@ -1819,7 +1873,7 @@ k_lpr_fixup(const int16_t *__restrict__ R, size_t rstride, int T, const int32_t 
 	if (c == nc - 1) {
 		const long long p0 = sin[s].prev_lpr_index;
 		const long long tot = p0 + (long long)n * slow;
-		const int E = (p0 >= 0 && p0 < fast) ? (int)floor_div_pos(tot, fast) : (int)(tot / fast);
+		const int E = (int)floor_div_pos(tot, fast);
 		sout[s].now_lpr = (int)carried(c);
 		sout[s].prev_lpr_index = (int)(tot - (long long)E * fast);
 		cnt_out[s] = E;
@@ -1921,10 +1975,33 @@ k_low_pass_real(const int16_t *__restrict__ A, size_t astride, int16_t *__restri
 		// p0 < fast and n * slow < 2^31 * 2^20: everything below stays under 2^52 for any run the
 		// library accepts (p0 comes from the carried state: outside [0, fast) only if injected)
 		const bool fits = p0 >= 0 && p0 < fast;
+		if (!fits) {
+			// A phase outside [0, fast) - rtlfm_gpu_state_set's alone.  From fast upwards the reference emits an output at
+			// EVERY input until the phase is back below fast (one subtraction per input, src/rtl_fm.c:768-772): neither the
+			// closed form above nor the host's bound on the outputs holds, so the stream's thread 0 walks the reference's
+			// own loop (at most one output per input: n <= the row).
+			if (m != 0) continue;
+			const int16_t *a = A + s * astride;
+			uint32_t acc = (uint32_t)sin[s].now_lpr;
+			long long ph = p0;
+			int out = 0;
+			for (int k = 0; k < n; k++) {
+				acc += (uint32_t)(int)a[k];
+				ph += slow;
+				if (ph >= fast) {
+					B[s * bstride + out++] = (int16_t)((int)acc / div);
+					ph -= fast;
+					acc = 0;
+				}
+			}
+			sout[s].now_lpr = (int)acc;
+			sout[s].prev_lpr_index = (int)ph;
+			cnt_out[s] = out;
+			continue;
+		}
 		long long k = 0;  // inputs consumed once output m - 1 is out
 		if (m > 0) {
-			const long long need = (long long)m * fast - p0;
-			k = fits ? floor_div_pos(need + slow - 1, slow) : (need + slow - 1) / slow;
+			k = floor_div_pos((long long)m * fast - p0 + slow - 1, slow);
 			if (k > n) continue;  // output m - 1 does not exist
 		}
 		long long ph = p0 + k * slow - (long long)m * fast;  // the accumulator's phase before input k
@@ -2347,7 +2424,7 @@ __global__ void k_arb_downsample(const int16_t *__restrict__ A, size_t astride, 
 		while (j < len2) {
 			double frac = 1.0;
 			if (tick + len2 > len1) frac = (double)(len1 - tick) / (double)len2;
-			cur = (int16_t)(cur + (int16_t)((double)b1[src] * frac + carry));
+			cur = (int16_t)(cur + (int16_t)(int)((double)b1[src] * frac + carry));  // (through int: values up to +-65534 wrap)
 			carry = (double)b1[src] * (1.0 - frac);
 			tick += len2;
 			src++;

@@ -64,6 +64,41 @@ def test_cli_output_matches_oracle(oracle_lib, tmp_path, argv, plan, fs):
     assert d.max() <= (0 if exact_needed else 1) and (d != 0).mean() <= 1e-4, (argv, int(d.max()), int((d != 0).sum()))
 
 
+@pytest.mark.parametrize("argv,plan,rec", [
+    (["-M", "am", "-s", "24k", "-E", "dc"], (24000, 1000000, 0, dict(mode=MODE_AM, rate_out=24000, dc_block_audio=1)), "KEYED"),
+    (["-M", "usb", "-s", "24k", "-E", "deemp"], (24000, 1000000, 0, dict(mode=MODE_USB, rate_out=24000, deemph=1)), "FLIP"),
+])
+def test_cli_on_the_rail_streams(oracle_lib, tmp_path, argv, plan, rec):
+    """The tool's own path on audio beyond half of int16: -M am / -M usb with the planner's own output_scale on a carrier
+    at the rails (tests/tail_hard.py: keyed on and off, and with its phase reversed) - am_demod / usb_demod wrap, and
+    dc_block_audio_filter / deemph_filter behind them see samples over the whole of int16.  Bit-exact: integer stages, and
+    a square root that is correctly rounded on both sides."""
+    import tail_hard as th
+    _, cli = hipbuild.build_host()
+    rate_in, min_capture, fifth, ov = plan
+    cfg = RtlfmCfg.default(**ov)
+    cf, cr = C.c_uint32(), C.c_uint32()
+    oracle_lib.oracle().orc_optimal_settings(C.byref(cfg), 100000000, rate_in, min_capture, fifth, 0, C.byref(cf), C.byref(cr))
+    assert cfg.output_scale == (1 << 15) // (128 * cfg.downsample) > 1
+    if cfg.deemph:
+        cfg.deemph_a = oracle_lib.oracle().orc_deemph_a(cfg.rate_out, 75)
+    L, nb = int(cfg.block_len), 9
+    iq = th.stream(getattr(th, rec), L * nb)
+    info = th.model_tail(cfg, th.demodulated(oracle_lib, cfg, iq))[2]
+    assert info["peak"] > 24576 and (info["adc"] > 0 or info["max_d"] > 32768), dict(info)  # the tail does see such audio
+    src = tmp_path / "capture.bin"
+    iq.tofile(src)
+    out = tmp_path / "audio.raw"
+    r = subprocess.run([cli, "-f", "100M"] + argv + [str(out)], env=dict(os.environ, RTLSDR_FILE=str(src)), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-1500:]
+    assert f"Sampling at {cr.value} S/s" in r.stderr
+    got = np.fromfile(out, dtype=np.int16)
+    want, _ = oracle_lib.run_stream(cfg, iq)
+    assert got.shape == want.shape
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, (argv, bad.size, bad[:8], got[bad[:8]], want[bad[:8]])
+
+
 @pytest.mark.parametrize("zero_copy", [True, False])
 def test_cli_on_a_slow_rtl_tcp_source_loses_nothing(oracle_lib, tmp_path, zero_copy):
     """The dongle / demod hand-off under a source that dribbles (an rtl_tcp server that sends 3000 bytes at a time with

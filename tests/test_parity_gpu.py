@@ -920,26 +920,45 @@ def _skip_only_outside_reference_domain(oracle_lib, cfg, L, err):
     raise AssertionError(f"the library rejects a configuration the reference (the oracle pinned to it) runs: {err}")
 
 
-@pytest.mark.parametrize("seed", range(int(os.environ.get("RTLFM_SWEEP", "48"))))
+SWEEP_SEEDS = int(os.environ.get("RTLFM_SWEEP", "48"))
+SWEEP_W_SEEDS = int(os.environ.get("RTLFM_SWEEP_W", "24"))
+
+
+def sweep_draw(seed, any_size=False):
+    """What a seed of the two sweeps below draws before it touches the GPU: (ov, L, nb, ns, cfg, the generator as it stands).
+    Shared with tests/test_tail_hard_cpu.py, which says what audio these inputs hand the tail."""
+    rng = np.random.default_rng((19000 if any_size else 9000) + seed)
+    ov = _random_cfg(rng)
+    if any_size:
+        L, nb, ns = 512 * int(rng.integers(1, 80)), int(rng.integers(2, 7)), int(rng.choice([1, 3, 9]))
+    else:
+        L, nb, ns = int(rng.choice([8192, 16384, 16384, 32768, 4096, 24576])), int(rng.integers(2, 6)), int(rng.choice([1, 2, 5, 33]))
+    return ov, L, nb, ns, make_cfg(ov, L, nb), rng
+
+
+def sweep_input(ov, L, nb, ns, seed, any_size=False):
+    """... and its input."""
+    amp = 25.0 if ov["custom_atan"] == 1 and ov["mode"] == capi.MODE_FM else 55.0
+    if ov["custom_atan"] == 1 and ov["downsample_passes"] == 0:
+        amp = max(2.0, min(25.0, 500.0 / ov["downsample"]))
+    iq = synth.fm_iq_u8(ns, L // 2 * nb, seed=(17000 if any_size else 7000) + seed, fs=1.024e6, dev_hz=20e3, amplitude=amp)
+    if any_size and seed % 3 == 0:
+        iq[-1] = synth.random_u8(1, L * nb, seed=18000 + seed)[0]  # full-scale bytes: the int16 wraps
+    return iq
+
+
+@pytest.mark.parametrize("seed", range(SWEEP_SEEDS))
 def test_random_configurations_vs_oracle(oracle_lib, seed):
     """Seeded random configurations through the automatic path selection (fused fifth_order /
     fused boxcar / staged, + tail) and through the staged kernels only, against the oracle:
     same outputs, same carried state, also when the run is split into launches."""
     from rtlsdr_amd.demod import GpuDemod
-    rng = np.random.default_rng(9000 + seed)
-    ov = _random_cfg(rng)
-    L = int(rng.choice([8192, 16384, 16384, 32768, 4096, 24576]))
-    nb = int(rng.integers(2, 6))
-    ns = int(rng.choice([1, 2, 5, 33]))
-    cfg = make_cfg(ov, L, nb)
+    ov, L, nb, ns, cfg, rng = sweep_draw(seed)
     try:
         GpuDemod(cfg, ns, 0).close()
     except capi.RtlfmError as e:
         _skip_only_outside_reference_domain(oracle_lib, cfg, L, e)
-    amp = 25.0 if ov["custom_atan"] == 1 and ov["mode"] == capi.MODE_FM else 55.0
-    if ov["custom_atan"] == 1 and ov["downsample_passes"] == 0:
-        amp = max(2.0, min(25.0, 500.0 / ov["downsample"]))
-    iq = synth.fm_iq_u8(ns, L // 2 * nb, seed=7000 + seed, fs=1.024e6, dev_hz=20e3, amplitude=amp)
+    iq = sweep_input(ov, L, nb, ns, seed)
     want, want_len, wst = oracle_lib.run_batch(cfg, iq, nthreads=2)
     cut = int(rng.integers(1, nb))
     for path, splits in ((0, None), (0, [(0, cut), (cut, nb)]), (1, None)):
@@ -1009,27 +1028,17 @@ def test_handles_of_several_threads_do_not_meet(oracle_lib):
     assert not errors, errors
 
 
-@pytest.mark.parametrize("seed", range(int(os.environ.get("RTLFM_SWEEP_W", "24"))))
+@pytest.mark.parametrize("seed", range(SWEEP_W_SEEDS))
 def test_random_configurations_any_buffer_size(oracle_lib, seed):
     """The same sweep with -W n buffers (any 512 n bytes, src/rtl_fm.c:1869-1873): the partial tiles of the fifth_order
     front end (fused_kernel.h, PT), the continuous run of the boxcar one, the staged kernels and the tails behind them."""
     from rtlsdr_amd.demod import GpuDemod
-    rng = np.random.default_rng(19000 + seed)
-    ov = _random_cfg(rng)
-    L = 512 * int(rng.integers(1, 80))
-    nb = int(rng.integers(2, 7))
-    ns = int(rng.choice([1, 3, 9]))
-    cfg = make_cfg(ov, L, nb)
+    ov, L, nb, ns, cfg, rng = sweep_draw(seed, any_size=True)
     try:
         GpuDemod(cfg, ns, 0).close()
     except capi.RtlfmError as e:
         _skip_only_outside_reference_domain(oracle_lib, cfg, L, e)
-    amp = 25.0 if ov["custom_atan"] == 1 and ov["mode"] == capi.MODE_FM else 55.0
-    if ov["custom_atan"] == 1 and ov["downsample_passes"] == 0:
-        amp = max(2.0, min(25.0, 500.0 / ov["downsample"]))
-    iq = synth.fm_iq_u8(ns, L // 2 * nb, seed=17000 + seed, fs=1.024e6, dev_hz=20e3, amplitude=amp)
-    if seed % 3 == 0:
-        iq[-1] = synth.random_u8(1, L * nb, seed=18000 + seed)[0]  # full-scale bytes: the int16 wraps
+    iq = sweep_input(ov, L, nb, ns, seed, any_size=True)
     want, want_len, wst = oracle_lib.run_batch(cfg, iq, nthreads=2)
     cut = int(rng.integers(1, nb))
     for path, splits in ((0, None), (0, [(0, cut), (cut, nb)])):

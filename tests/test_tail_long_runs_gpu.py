@@ -46,22 +46,29 @@ def _cfg(rng):
     return ov, L
 
 
-@pytest.mark.parametrize("seed", range(NSEEDS))
-def test_long_run_tail_random(oracle_lib, seed):
-    from rtlsdr_amd.demod import GpuDemod
+def long_run_draw(seed):
+    """What a seed draws before it touches the GPU: (ov, L, nb, ns, cfg, iq as synthesised, the generator as it stands).
+    Shared with tests/test_tail_hard_cpu.py."""
     rng = np.random.default_rng(31000 + seed)
     ov, L = _cfg(rng)
     nb = int(rng.integers(2, 7))
     ns = int(rng.choice([3, 5, 9]))
     cfg = make_cfg(ov, L, nb)
-    try:
-        GpuDemod(cfg, ns, 0).close()
-    except capi.RtlfmError as e:
-        pytest.skip(f"rejected: {e} {ov}")
     amp = 20.0 if ov["custom_atan"] == 1 else 50.0
     if ov["custom_atan"] == 1 and ov["downsample_passes"] == 0:
         amp = max(2.0, min(20.0, 500.0 / ov["downsample"]))
     iq = synth.fm_iq_u8(ns, L // 2 * nb, seed=8100 + seed, fs=1.024e6, dev_hz=float(rng.choice([3e3, 20e3, 75e3])), amplitude=amp)
+    return ov, L, nb, ns, cfg, iq, rng
+
+
+@pytest.mark.parametrize("seed", range(NSEEDS))
+def test_long_run_tail_random(oracle_lib, seed):
+    from rtlsdr_amd.demod import GpuDemod
+    ov, L, nb, ns, cfg, iq, rng = long_run_draw(seed)
+    try:
+        GpuDemod(cfg, ns, 0).close()
+    except capi.RtlfmError as e:
+        pytest.skip(f"rejected: {e} {ov}")
     if rng.random() < 0.7:
         iq[1] = 127
     if rng.random() < 0.7:
