@@ -690,6 +690,42 @@ int rtlfm_channel_filter_check_dc(const int16_t *taps, int ntaps, int shift);
 int rtlfm_gpu_source_dc_prepass(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks);
 int rtlfm_channel_bank_check_dc(int K, const int16_t *taps, int ntaps, int shift);
 
+/*
+ * Options "source_stats" and "source_health": the ADC statistics and the input health per SOURCE (DESIGN.md section 8.5,
+ * "Source statistics and health").
+ *
+ * One wideband source feeds K channels, so its gain decides all K at once: an overloaded ADC spoils every channel, too
+ * little gain raises every channel's noise.  "input_stats" / "input_health" read per-STREAM input rows and stay refused
+ * while channels are on (-ENOTSUP, both ways round); these two are the same records for the source rows.  Each 0 (default)
+ * / 1; they act only on runs that channels take and may be set with channels off (as "source_dc").
+ *
+ * records      one rtlfm_input_stat and / or one rtlfm_input_health per (source, buffer) of the run, with exactly the
+ *              definitions at rtlfm_gpu_input_stats / rtlfm_gpu_input_health above (no new type), taken over the source's raw
+ *              bytes before anything else touches them: in front of source_dc's subtraction, the mixers, the filter and the
+ *              bank.  Integer and order-independent: bit-identical to the reference's loops.  They change no result: PCM,
+ *              lengths, state records and rtlfm_gpu_channels_tell are those of the run without them.
+ * which runs   rtlfm_gpu_run_device reads the caller's source rows; ring runs over "source_ring" read the handle's device
+ *              copy.  A ring run that holds short buffers files each buffer's record over its own length, [source][nb], as
+ *              the stream readers do per stream.  Under verify_twice the records are one execution's (both see the same bytes).
+ * fetch        rtlfm_gpu_source_stats / _health: the last run's records of `source`; _all: every source in one copy, source
+ *              a at out + a * cap.  The contract of rtlfm_gpu_levels / _all with sources for streams: -EINVAL for bad
+ *              arguments or a source outside [0, sources); -ENODATA while the option is off, before the first run, after
+ *              rtlfm_gpu_set_channels and while the last run was not one that channels took; -ENOBUFS, with *n written, when
+ *              cap is too small; *n = buffers of the last run.
+ * setting      -EINVAL for any value but 0 / 1, -EBUSY while a run is begun and not ended or a ring slot is open; a refused
+ *              call changes nothing.  Setting 0 frees nothing.  The records, [sources][max_blocks], are allocated by the first
+ *              run that needs them and regrown when rtlfm_gpu_set_channels makes the sources more.
+ * kernels      inside the front end's timed pair (rtlfm_gpu_timing_read shows what they cost).  With "source_dc" on the
+ *              source rows are read ONCE for all of it: k_source_prepass (csrc/source_prepass_kernel.h) leaves the sums
+ *              k_rdc_sums_wide / _small would and the records, built from the readers' own per-word functions.  With
+ *              "source_dc" off k_input_health (which takes the statistics along) or k_input_stats run over the source rows.
+ *              Loads as input_stats_nt.  With both options at 0 no kernel, path, launch count, result or allocation differs.
+ */
+int rtlfm_gpu_source_stats(rtlfm_gpu *h, int source, rtlfm_input_stat *out, int cap, int *n);
+int rtlfm_gpu_source_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int *n);
+int rtlfm_gpu_source_health(rtlfm_gpu *h, int source, rtlfm_input_health *out, int cap, int *n);
+int rtlfm_gpu_source_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,
@@ -779,6 +815,8 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        rtlfm_gpu_bank_survey)
  *   source_dc            0 (default) / 1: runs that channels take subtract every source's smoothed buffer averages in front
  *                        of the mixers and the bank (see "source_dc" above)
+ *   source_stats         0 (default) / 1: runs that channels take leave the ADC statistics of every source's raw bytes, and
+ *   source_health        ... the overload / high-level / continuity records (see "source_stats" above)
  * Read-only (rtlfm_gpu_get_option):
  *   pack_us              device time of the last run's two pack launches in microseconds (waits for them); -1 when that
  *                        run was not packed or rtlfm_gpu_timing_enable was off

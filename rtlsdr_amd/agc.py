@@ -56,7 +56,18 @@ class SoftAgc:
         check(self.lib.rtlfm_agc_feed(self._a, stream, r.ctypes.data, ln.ctypes.data, r.size), "rtlfm_agc_feed")
 
     def update(self, demod):
-        """Feed every stream from the last run of a ``GpuDemod`` (needs ``set_option("input_health", 1)``)."""
+        """Feed every stream from the last run of a ``GpuDemod`` (needs ``set_option("input_health", 1)``).  A demod with
+        channels on and the option ``source_health`` set feeds SOURCE i's records to input i instead: one input per wideband
+        source (``nstreams // per_source``), ``ValueError`` otherwise."""
+        per = getattr(demod, "_per_source", 0)
+        if per and demod.get_option("source_health"):
+            nsrc = demod.nstreams // per
+            if self.nstreams != nsrc:
+                raise ValueError(f"one input per source: the demod has {nsrc}, this engine {self.nstreams}")
+            recs = demod.source_health_all()
+            for i in range(nsrc):
+                self.feed(i, recs[i], int(demod.cfg.block_len))
+            return
         check(self.lib.rtlfm_agc_update(self._a, demod._h), "rtlfm_agc_update")
 
     def poll(self, cap: int = 1024) -> list[dict]:

@@ -361,6 +361,10 @@ _SIGNATURES = [
     ("rtlfm_gpu_input_health_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     ("rtlfm_gpu_input_health_stats_device", C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                       C.c_void_p]),
+    ("rtlfm_gpu_source_stats", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_source_stats_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_source_health", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_source_health_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_gate", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_gate_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_mute", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),

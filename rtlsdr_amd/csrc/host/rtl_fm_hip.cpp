@@ -82,6 +82,12 @@
 // source ends.  Not with -S, -C, -K, -R, -Z, -O agc=2 or -E rdc: each needs what the library refuses while channels are on.
 // -E srcdc (with -X only, not with -E rdc) sets the library's option source_dc: every source's DC spike comes off in front of
 // the mixers.
+// -E srcagc (with -X only, not with any agc= part in -O) is -O agc=2 for the SOURCES of -X: gain mode 2 on every device, the
+// library's option source_health (records of every source's raw bytes, in front of everything), the engine of
+// include/rtlfm_agc.h fed after every run with input i = source i, each source's last index applied to its device, and the
+// lines of -N -O agc=2 -v with "source %d:" where those say "stream %d:" (under -X a stream is a channel).  The engine is
+// fed the full length for a completed short last buffer - the record is over the completed buffer - and nothing for a
+// source that has ended: the bytes 127 it is fed must not ramp its gain.  The PCM files are those of the run without it.
 //
 // Not restated (out of scope): the command file's own hop (its 2 x 3 200 000 byte mute, the DC-filter reset, -B), and
 // -t negative (terminate on squelch).
@@ -152,6 +158,7 @@ struct Settings {
 	const char *filename = "-", *cmd_file = nullptr, *scan_file = nullptr, *keep_file = nullptr, *resume_file = nullptr;
 	const char *chan_file = nullptr, *opt_string = nullptr;
 	bool source_dc = false;  // -E srcdc: the library's option source_dc (with -X only)
+	bool source_agc = false; // -E srcagc: the software AGC per source (with -X only; not with agc= in -O)
 	int agc = -1;        // -O agc=<n>; -1: not given
 	int chan_taps = -1;  // -x; -1: not given
 };
@@ -231,6 +238,7 @@ rtlsdr_dev_t *open_source(const Settings &st, int i, int gain, uint32_t capture_
 	else { rtlsdr_set_tuner_gain_mode(dev, 1); rtlsdr_set_tuner_gain(dev, gain); }
 	if (st.opt_string) rtlsdr_set_opt_string(dev, st.opt_string, st.verbosity);
 	if (st.agc >= 0) rtlsdr_set_tuner_gain_mode(dev, st.agc);  // the string's agc=<tuner_gain_mode>, src/librtlsdr.c:3166-3171
+	if (st.source_agc) rtlsdr_set_tuner_gain_mode(dev, 2);     // -E srcagc: as agc=2 (main has refused the two together)
 	rtlsdr_set_freq_correction_ppb(dev, st.ppm * 1000);
 	rtlsdr_set_offset_tuning(dev, st.cfg.offset_tuning);
 	rtlsdr_set_center_freq(dev, capture_freq);
@@ -367,8 +375,9 @@ struct Plumbing {
 	bool out_done = false;
 };
 
-// -O agc=2: the software AGC and the overload report for every source (include/rtlfm_agc.h)
+// -O agc=2, and -E srcagc under -X: the software AGC and the overload report for every source (include/rtlfm_agc.h)
 struct Health {
+	bool by_source = false;               // -E srcagc: the records are the handle's per-SOURCE ones, row i = source i, and the lines say "source"
 	rtlfm_agc *agc = nullptr;
 	std::vector<rtlsdr_dev_t *> devs;
 	std::vector<std::vector<int>> gains;  // each source's gain table, tenths of a dB
@@ -399,22 +408,24 @@ int health_create(Health *hl, const std::vector<rtlsdr_dev_t *> &devs, int settl
 	return r;
 }
 
-// after a run: stream k of the handle is source live[k], whose buffers of this run were lens[k] bytes long
+// after a run: stream k of the handle is source live[k], whose buffers of this run were lens[k] bytes long.  (by_source:
+// the handle has a row of records for every source, live or not; only the live ones are fed.)
 int health_step(Health *hl, rtlfm_gpu *gpu, int cap, const std::vector<int> &live, const std::vector<std::vector<uint32_t>> &lens)
 {
-	hl->recs.resize(live.size() * (size_t)cap);
+	const char *noun = hl->by_source ? "source" : "stream";
+	hl->recs.resize((hl->by_source ? hl->devs.size() : live.size()) * (size_t)cap);
 	int n = 0;
-	int r = rtlfm_gpu_input_health_all(gpu, hl->recs.data(), cap, &n);
+	int r = hl->by_source ? rtlfm_gpu_source_health_all(gpu, hl->recs.data(), cap, &n) : rtlfm_gpu_input_health_all(gpu, hl->recs.data(), cap, &n);
 	if (r < 0) return r;
 	for (size_t k = 0; k < live.size(); k++) {
 		const int i = live[k];
 		if ((int)lens[k].size() != n) return -EPROTO;
-		const rtlfm_input_health *rec = hl->recs.data() + k * (size_t)cap;
+		const rtlfm_input_health *rec = hl->recs.data() + (hl->by_source ? (size_t)i : k) * (size_t)cap;
 		if ((r = rtlfm_agc_feed(hl->agc, i, rec, lens[k].data(), n)) < 0) return r;
 		for (int b = 0; b < n; b++) {
 			const int ov = 8000ll * rec[b].overload >= (long long)lens[k][(size_t)b] ? 1 : 0;  // src/rtl_tcp.c:243
 			if (ov != hl->overloaded[(size_t)i] && hl->verbosity)
-				fprintf(stderr, "stream %d: buffer %lld: overload %s\n", i, hl->serial[(size_t)i], ov ? "begins" : "ends");
+				fprintf(stderr, "%s %d: buffer %lld: overload %s\n", noun, i, hl->serial[(size_t)i], ov ? "begins" : "ends");
 			hl->overloaded[(size_t)i] = ov;
 			hl->serial[(size_t)i]++;
 		}
@@ -425,7 +436,7 @@ int health_step(Health *hl, rtlfm_gpu *gpu, int cap, const std::vector<int> &liv
 		if ((r = rtlfm_agc_poll(hl->agc, ev, 64, &ne)) < 0) return r;
 		if (hl->verbosity)
 			for (int e = 0; e < ne; e++)
-				fprintf(stderr, "stream %d: buffer %lld: gain index %d -> %d, gain %d (%s)\n", ev[e].stream, (long long)ev[e].buffer_serial,
+				fprintf(stderr, "%s %d: buffer %lld: gain index %d -> %d, gain %d (%s)\n", noun, ev[e].stream, (long long)ev[e].buffer_serial,
 				        ev[e].old_index, ev[e].new_index, hl->gains[(size_t)ev[e].stream][(size_t)ev[e].new_index],
 				        ev[e].overloaded ? "overload" : "low level");
 		if (ne < 64) break;
@@ -447,7 +458,7 @@ void health_report(Health *hl)
 		int32_t idx = 0;
 		uint64_t total = 0, dropped = 0;
 		rtlfm_agc_state(hl->agc, (int)i, &idx, nullptr, &total, &dropped);
-		fprintf(stderr, "stream %zu: final gain index %d, gain %d\n", i, idx, hl->gains[i][(size_t)idx]);
+		fprintf(stderr, "%s %zu: final gain index %d, gain %d\n", hl->by_source ? "source" : "stream", i, idx, hl->gains[i][(size_t)idx]);
 	}
 }
 
@@ -1336,6 +1347,13 @@ void demod_thread_channels(Multi *m)
 		}
 		RunOut o;
 		if (!run_and_fetch(m, r, b, who, o)) break;
+		if (m->hl.agc) {  // -E srcagc: every live source's b records, each over a full (completed) buffer; an ended source's are not fed
+			const std::vector<std::vector<uint32_t>> lens(live.size(), std::vector<uint32_t>((size_t)b, L));
+			if ((r = health_step(&m->hl, m->gpu, m->st.cfg.max_blocks, live, lens)) < 0) {
+				fail(m, "rtlfm_gpu_source_health_all / rtlfm_agc_feed", r);
+				break;
+			}
+		}
 		for (int s = 0; s < S; s++)
 			if (ended[(size_t)(s / K)]) o.lens[(size_t)s] = 0;
 		if (m->st.print_levels)
@@ -1385,6 +1403,15 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 		if (r == 0) { what = "option source_ring"; r = rtlfm_gpu_set_option(m.gpu, "source_ring", 1); }
 		if (r == 0) { what = "rtlfm_gpu_set_channels"; r = rtlfm_gpu_set_channels(m.gpu, K, steps.data()); }
 		if (r == 0 && st.source_dc) { what = "option source_dc"; r = rtlfm_gpu_set_option(m.gpu, "source_dc", 1); }
+		if (r == 0 && st.source_agc) {
+			// (settle = the buffers one run may take, as -O agc=2: they were captured before a change could act)
+			what = "option source_health";
+			r = rtlfm_gpu_set_option(m.gpu, "source_health", 1);
+			std::vector<rtlsdr_dev_t *> devs;
+			for (Source &s : m.src) devs.push_back(s.dev);
+			m.hl.by_source = true;
+			if (r == 0) { what = "rtlfm_agc_create"; r = health_create(&m.hl, devs, c.max_blocks, st.verbosity); }
+		}
 		if (r == 0 && c.squelch_level) {
 			// -l: demod_thread_fn's rule on the device, and only what it let through comes back.  (-ENOTSUP, behind a
 			// resampler: the rule from the carried state after every run, hold_back.)
@@ -1424,8 +1451,10 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 		uint64_t in = 0;
 		for (Source &s : m.src) in += s.blocks_in;
 		summary(m.out.data(), m.out.size(), in, nullptr, m.failed, st.verbosity > 0);
+		if (m.hl.agc) health_report(&m.hl);
 		if (m.failed) ret = 3;
 	}
+	if (m.hl.agc) rtlfm_agc_destroy(m.hl.agc);
 	close_all(&m);
 	return ret;
 }
@@ -1465,7 +1494,8 @@ void usage()
 	        "\t[-X channel_file  channels: line i of the file is the list of channel frequencies of source i (-N n, or one source), in\n"
 	        "\t       -S's grammar, the same number K on every line; source i's centre frequency is its -f as given and its K channels are mixed\n"
 	        "\t       down on the GPU; stream s = channel s %% K of source s / K writes the file with %%d = s; not with -S -C -K -R -Z,\n"
-	        "\t       -O agc=2 or -E rdc; -E srcdc takes every source's DC spike off in front of the mixers (-q sets its constant)]\n"
+	        "\t       -O agc=2 or -E rdc; -E srcdc takes every source's DC spike off in front of the mixers (-q sets its constant);\n"
+	        "\t       -E srcagc is the software AGC for every SOURCE from the GPU's records of its raw bytes (-v prints every change; not with agc= in -O)]\n"
 	        "\t[-x ntaps  with -X: a windowed-sinc channel filter of ntaps taps (cutoff 0.4 of the output rate) in the boxcar's place; not with -F]\n"
 	        "\t[-K file  keep: write every stream's carried filter state to file at exit (with -N n: n records, in source order)]\n"
 	        "\t[-R file  resume: load such a file before the first buffer - it must hold as many records as there are sources and\n"
@@ -1476,7 +1506,7 @@ void usage()
 	        "\t[-m minimum_capture_rate Hz (default: 1m)]\n"
 	        "\t[-F fir_size (default: off)]  enables the fifth-order low pass; 0 or 9 (9 = droop compensation)\n"
 	        "\t[-A std/fast/lut choose atan math (default: std)]\n"
-	        "\t[-E enable_option]  edge, dc, rdc, deemp, offset, srcdc (with -X only; not with rdc)\n"
+	        "\t[-E enable_option]  edge, dc, rdc, deemp, offset, srcdc (with -X only; not with rdc), srcagc (with -X only; not with agc= in -O)\n"
 	        "\t[-c de-emphasis_time_constant in us: us (75), eu (50) or a number]\n"
 	        "\t[-o oversampling (default: 1)]  [-l squelch_level]  [-t squelch_delay (default: 10)]  [-q rdc_block_const]\n"
 	        "\t[-L N  prints levels every N calculations (with -N: per stream, as 'stream i: ...')]\n"
@@ -1541,6 +1571,7 @@ int main(int argc, char **argv)
 			if (!strcmp(optarg, "dc") || !strcmp(optarg, "adc")) c.dc_block_audio = 1;
 			if (!strcmp(optarg, "rdc")) c.dc_block_raw = 1;
 			if (!strcmp(optarg, "srcdc")) st.source_dc = true;
+			if (!strcmp(optarg, "srcagc")) st.source_agc = true;
 			if (!strcmp(optarg, "deemp")) c.deemph = 1;
 			if (!strcmp(optarg, "offset")) c.offset_tuning = 1;
 			break;
@@ -1590,6 +1621,16 @@ int main(int argc, char **argv)
 	if (st.source_dc && !st.chan_file) {
 		fprintf(stderr, "-E srcdc (raw DC block per source) needs -X (the channel file): it acts in front of the channels' mixers only; "
 		                "without channels -E rdc is the raw DC block.\n");
+		return 1;
+	}
+	if (st.source_agc && !st.chan_file) {
+		fprintf(stderr, "-E srcagc (software AGC per source) needs -X (the channel file): it reads the records of the sources' raw bytes "
+		                "that only a handle with channels takes; without channels -O agc=2 is the software AGC.\n");
+		return 1;
+	}
+	if (st.source_agc && st.agc != -1) {
+		fprintf(stderr, "-E srcagc (software AGC per source, gain mode 2 on every device) does not go with agc=%d in -O: one of them "
+		                "sets the devices' gain mode.\n", st.agc);
 		return 1;
 	}
 	if (st.chan_taps != -1 && !st.chan_file) {

@@ -31,6 +31,7 @@
 #include "boxcar_kernel.h"
 #include "input_stats_kernel.h"
 #include "input_health_kernel.h"
+#include "source_prepass_kernel.h"
 #include "scan_kernel.h"
 #include "pack_kernel.h"
 #include "state_kernel.h"
@@ -130,6 +131,13 @@ struct rtlfm_gpu {
 	DevBuf<uint32_t> d_sdc;                // [sources][sdc_stride] a run's list of biases: the history's pieces, then the run's
 	size_t sdc_stride = 0;
 	DevBuf<uint32_t> d_sdc_hist[2];        // [sources][channel::kDcHist]
+	// options source_stats / source_health: the readers' records per (SOURCE, buffer) of a run that channels take, allocated
+	// on first use for the sources there are then and regrown when rtlfm_gpu_set_channels makes them more
+	DevBuf<rtlfm_input_stat> d_src_stats;      // [sources][cap_blocks]
+	DevBuf<rtlfm_input_health> d_src_health;
+	int src_stats_nblocks = 0, src_health_nblocks = 0;  // buffers of the last run that have records; 0: that run left none
+	size_t src_rec_off = 0;                    // a view (run_ragged) files buffer j of the run: [source][src_rec_stride] + j
+	int src_rec_stride = 0;                    // 0: the run's own buffer count
 	// the channel filter (channel_fir_kernel.h; rtlfm_gpu_set_channel_filter): acts while channels are on
 	int fir_ntaps = 0, fir_shift = 0;      // 0 taps: none, the boxcar
 	std::vector<int16_t> fir_taps;         // what the getter hands back
@@ -209,6 +217,8 @@ struct rtlfm_gpu {
 		int pack_results = 0;  // 1 / 2: every ring run ends with k_pack_plan + k_pack_copy (pack_kernel.h; rtlfm_gpu_fetch_packed)
 		int bank_survey = 0;   // 1: a run the bank takes leaves every bin's power as well (k_channel_bank_survey; rtlfm_gpu_bank_survey)
 		int source_dc = 0;     // 1: runs that channels take subtract every source's smoothed buffer averages in front of the front end (k_source_dc_smooth)
+		int source_stats = 0;  // 1: runs that channels take leave the ADC statistics of every source's raw bytes (rtlfm_gpu_source_stats)
+		int source_health = 0; // 1: ... and the health records (rtlfm_gpu_source_health)
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
 	DevBuf<int16_t> vt_out;
@@ -548,6 +558,20 @@ static int ensure_source_dc(rtlfm_gpu *h)
 	return 0;
 }
 
+// Options source_stats / source_health: the records of whichever is on, [sources][cap_blocks] for the sources there are now
+// (a view - run_ragged - cannot allocate: the handle's run does, before the first view).  Allocated on first use, regrown
+// - never shrunk - when there are more sources than they were sized for (DevBuf::grow waits for the handle's stream first);
+// what they held is gone then, and the callers have said so (src_*_nblocks = 0) or are about to overwrite it.
+static int ensure_source_records(rtlfm_gpu *h)
+{
+	if (h->chan_per <= 0 || (!h->opt.source_stats && !h->opt.source_health)) return 0;
+	const int nsrc = h->nstreams / h->chan_per;
+	const size_t need = (size_t)nsrc * h->cap_blocks;
+	if (h->opt.source_stats) OWN_TRY(h->d_src_stats.grow(need, h->stream));
+	if (h->opt.source_health) OWN_TRY(h->d_src_health.grow(need, h->stream));
+	return 0;
+}
+
 // The source history - every source's carried bytes - back to 127: mixed zeros, m[n < 0] = 0 and x[n < 0] = 0.  On the
 // handle's stream: behind the runs already queued, in front of the next.
 static int history_clear(rtlfm_gpu *h)
@@ -782,8 +806,10 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	h->chan_pos = 0;
 	h->bank_K = 0;  // (the bank's bins belong to the old per_source)
 	h->bank_bins_ps.clear();
-	const int r = ensure_history(h);
+	h->src_stats_nblocks = h->src_health_nblocks = 0;  // (options source_stats / source_health: records of the old rows)
+	int r = ensure_history(h);
 	if (r < 0) return r;
+	if ((r = ensure_source_records(h)) < 0) return r;
 	return ingest_resize(h);  // (option source_ring: the ring's input side for the new number of sources)
 }
 
@@ -1119,6 +1145,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"squelch_gate", &h->opt.squelch_gate}, {"conseq_squelch", &h->opt.conseq_squelch},
 		{"source_ring", &h->opt.source_ring}, {"pack_results", &h->opt.pack_results}, {"bank_survey", &h->opt.bank_survey},
 		{"source_dc", &h->opt.source_dc},
+		{"source_stats", &h->opt.source_stats}, {"source_health", &h->opt.source_health},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -1209,6 +1236,14 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 		}
 		h->opt.source_dc = (int)value;
 		return history_clear(h);  // (the history belongs to the old rule; the records stay)
+	}
+	if (!strcmp(name, "source_stats") || !strcmp(name, "source_health")) {
+		// (they read source rows and act only on runs that channels take: free to set with channels off.  Setting 0 frees
+		// nothing; the records are allocated by the first run that needs them)
+		if (value != 0 && value != 1) return -EINVAL;
+		if (ingest_busy(h)) return -EBUSY;
+		*slot = (int)value;
+		return 0;
 	}
 	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
 	if (!strcmp(name, "source_ring")) {
@@ -1859,18 +1894,28 @@ static int run_irregular_rest(RunFrame &f, const uint32_t *cur, size_t xstride)
 	return f.tail();
 }
 
+// Options source_stats / source_health: where this run's records go (a view files single buffers into the run's rows)
+static rtlfm_input_stat *source_stats_out(const rtlfm_gpu *h) { return h->opt.source_stats ? h->d_src_stats + h->src_rec_off : nullptr; }
+static rtlfm_input_health *source_health_out(const rtlfm_gpu *h) { return h->opt.source_health ? h->d_src_health + h->src_rec_off : nullptr; }
+
 // Option source_dc's pre-pass, in front of a channel front end and inside its timed pair: every source's buffer sums
 // (k_rdc_sums_wide / _small on the source rows - one more read of the source bytes), then k_source_dc_smooth, which leaves
 // the run's list of biases in d_sdc, the averages in every channel's record of sout and - hist: a filter or a bank carries
-// a history - the next history's biases in the copy the run writes.
-static int launch_source_dc(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, const state_t *sin, state_t *sout, bool hist)
+// a history - the next history's biases in the copy the run writes.  records: k_source_prepass in k_rdc_sums_*'s place,
+// which leaves the same sums and the records of options source_stats / source_health from the same read.
+static int launch_source_dc(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, const state_t *sin, state_t *sout, bool hist,
+                            bool records)
 {
 	const int nsrc = h->nstreams / h->chan_per;
 	const uint32_t L = h->cfg.block_len;
 	if (!h->d_sdc || !h->d_sdc_sums || !h->d_sdc_hist[0] || !h->d_sdc_hist[1]) return -EFAULT;
 	if ((size_t)channel::kDcHist + (size_t)nblocks * (L / (2 * channel::kDcPiece)) > h->sdc_stride) return -E2BIG;
 	const size_t total = (size_t)nsrc * nblocks;
-	if (L < 8192)
+	if (records) {
+		const int r = sprepass::launch(d_iq, stream_stride, L, nblocks, nsrc, h->d_sdc_sums, source_health_out(h), source_stats_out(h),
+		                               h->src_rec_stride ? h->src_rec_stride : nblocks, h->opt.input_stats_nt != 0, h->stream);
+		if (r < 0) return r;
+	} else if (L < 8192)
 		k_rdc_sums_small<<<(unsigned)((total + 3) / 4), 256, 0, h->stream>>>(d_iq, stream_stride, L, nblocks, total, h->d_sdc_sums);
 	else
 		k_rdc_sums_wide<<<(unsigned)total, 256, 0, h->stream>>>(d_iq, stream_stride, L, nblocks, h->d_sdc_sums);
@@ -1878,6 +1923,33 @@ static int launch_source_dc(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_str
 		h->d_sdc_sums, L, nblocks, nsrc, h->chan_per, h->cfg.rdc_block_const, sin, sout,
 		hist ? h->d_sdc_hist[h->src_hist_cur].get() : nullptr, hist ? h->d_sdc_hist[h->src_hist_cur ^ 1].get() : nullptr, h->d_sdc, h->sdc_stride);
 	return 0;
+}
+
+// Options source_stats / source_health without the pre-pass kernel: the stream readers' launches over the SOURCE rows -
+// k_input_health, which takes the statistics along when both are on, or k_input_stats alone.
+static int launch_source_readers(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks)
+{
+	rtlfm_input_stat *so = source_stats_out(h);
+	rtlfm_input_health *ho = source_health_out(h);
+	const int nsrc = h->nstreams / h->chan_per, rs = h->src_rec_stride ? h->src_rec_stride : nblocks;
+	const bool nt = h->opt.input_stats_nt != 0;
+	if (ho) return ihealth::launch(d_iq, stream_stride, h->cfg.block_len, nblocks, nsrc, ho, rs, nt, h->stream, so);
+	if (so) return istats::launch(d_iq, stream_stride, h->cfg.block_len, nblocks, nsrc, so, rs, nt, h->stream);
+	return 0;
+}
+
+// What a channel run does with its source rows in front of its front end, inside the front end's timed pair: source_dc's
+// pre-pass and the records of options source_stats / source_health, both over the raw bytes (the records are in front of
+// source_dc's subtraction: nothing here changes a byte).  With source_dc and a record option on, ONE read: k_source_prepass
+// (k_rdc_sums_* and the readers behind them, the same results from two reads, lost the A/B of LAB.md at 1024 sources x 4).
+static int launch_source_side(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, const state_t *sin, state_t *sout, bool hist)
+{
+	const bool records = h->opt.source_stats || h->opt.source_health;
+	if (records && ((h->opt.source_stats && !h->d_src_stats) || (h->opt.source_health && !h->d_src_health))) return -EFAULT;  // (views do not allocate)
+	const bool one = records && h->opt.source_dc;
+	int r;
+	if (h->opt.source_dc && (r = launch_source_dc(h, d_iq, stream_stride, nblocks, sin, sout, hist, one)) < 0) return r;
+	return records && !one ? launch_source_readers(h, d_iq, stream_stride, nblocks) : 0;
 }
 
 // ROUTE_STAGED and ROUTE_CHAN_MIX: a kernel per stage through the work buffers.  The timed pair holds the decimator with
@@ -1907,8 +1979,8 @@ static int run_staged(RunFrame &f)
 		                                           h->d_rdc_avg);
 		rdc = h->d_rdc_avg;
 	}
-	if (h->chan_per > 0 && h->opt.source_dc) {  // ... behind option source_dc's pre-pass (no filter, no bank here: no history)
-		if ((r = launch_source_dc(h, d_iq, stream_stride, nblocks, sin, sout, false)) < 0) return r;
+	if (h->chan_per > 0 && (r = launch_source_side(h, d_iq, stream_stride, nblocks, sin, sout, false)) < 0) return r;  // (no filter, no bank here: no history)
+	if (h->chan_per > 0 && h->opt.source_dc) {  // ... behind option source_dc's pre-pass
 		channel::k_channel_mix<true><<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S, h->chan_per,
 		                                                                                  h->d_chan_steps, h->d_chan_table,
 		                                                                                  (uint32_t)h->chan_pos, h->bufA, h->xstride, h->d_sdc,
@@ -2392,8 +2464,7 @@ static int run_channels(RunFrame &f)
 	int r = chan_run_prepare(f, cr);
 	if (r < 0) return r;
 	if ((r = timing_begin(h, f.ev)) < 0) return r;
-	if (h->opt.source_dc && (r = launch_source_dc(h, f.d_iq, f.stream_stride, f.nblocks, cr.sin, cr.sout, route != RTLFM_ROUTE_CHAN_BOXCAR)) < 0)
-		return r;
+	if ((r = launch_source_side(h, f.d_iq, f.stream_stride, f.nblocks, cr.sin, cr.sout, route != RTLFM_ROUTE_CHAN_BOXCAR)) < 0) return r;
 	switch (route) {
 	case RTLFM_ROUTE_CHAN_BOXCAR: r = launch_channel_boxcar(h, cr); break;
 	case RTLFM_ROUTE_CHAN_FIR: r = launch_channel_fir(h, true, cr); break;
@@ -2423,7 +2494,7 @@ extern "C" int rtlfm_gpu_source_dc_prepass(rtlfm_gpu *h, const uint8_t *d_iq, si
 	std::pair<Event, Event> ev;
 	int r = timing_begin(h, ev);
 	if (r < 0) return r;
-	if ((r = launch_source_dc(h, d_iq, stream_stride, nblocks, h->st[h->st_cur], h->st[(h->st_cur + 1) % 3], false)) < 0) return r;
+	if ((r = launch_source_dc(h, d_iq, stream_stride, nblocks, h->st[h->st_cur], h->st[(h->st_cur + 1) % 3], false, false)) < 0) return r;
 	if ((r = timing_end(h, ev)) < 0) return r;
 	HIP_TRY(hipGetLastError());
 	return 0;
@@ -2729,6 +2800,10 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		const int g = ensure_gate(h);
 		if (g < 0) return g;
 	}
+	if (!h->src_rec_stride) {  // (the same)
+		const int e = ensure_source_records(h);
+		if (e < 0) return e;
+	}
 	// the survey: of every run the bank takes while the option is on (both executions of a verified run write the same set:
 	// each stores, neither adds)
 	const bool surveyed = h->opt.bank_survey && h->chan_per > 0 && h->bank_K > 0;
@@ -2752,6 +2827,8 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	h->stats_nblocks = h->opt.input_stats ? nblocks : 0;
 	h->health_nblocks = h->opt.input_health ? nblocks : 0;
 	h->gate_nblocks = h->opt.squelch_gate ? nblocks : 0;
+	h->src_stats_nblocks = h->chan_per > 0 && h->opt.source_stats ? nblocks : 0;
+	h->src_health_nblocks = h->chan_per > 0 && h->opt.source_health ? nblocks : 0;
 	return 0;
 }
 
@@ -2760,9 +2837,11 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 // written even where it does not fit -, then the copy.
 template <class Rec>
 static int fetch_records(rtlfm_gpu *h, DevBuf<Rec> rtlfm_gpu::*recs, int rtlfm_gpu::*count_of, bool (*enabled)(const rtlfm_gpu *),
-                         bool all, int stream, Rec *out, int cap, int *n)
+                         bool all, int stream, Rec *out, int cap, int *n, bool by_source = false)
 {
-	if (!h || !out || !n || (!all && (stream < 0 || stream >= h->nstreams))) return -EINVAL;
+	// (by_source: rows are sources, of a handle whose last run channels took - `enabled` says -ENODATA otherwise)
+	const int rows = !h ? 0 : !by_source ? h->nstreams : h->chan_per > 0 ? h->nstreams / h->chan_per : h->nstreams;
+	if (!h || !out || !n || (!all && (stream < 0 || stream >= rows))) return -EINVAL;
 	if (!enabled(h)) return -ENODATA;
 	const int count = h->*count_of;
 	*n = count;
@@ -2772,7 +2851,7 @@ static int fetch_records(rtlfm_gpu *h, DevBuf<Rec> rtlfm_gpu::*recs, int rtlfm_g
 	if (count <= 0) return 0;
 	const size_t row = (size_t)count * sizeof(Rec);
 	if (all)
-		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(Rec), h->*recs, row, row, (size_t)h->nstreams, hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy2D(out, (size_t)cap * sizeof(Rec), h->*recs, row, row, (size_t)rows, hipMemcpyDeviceToHost));
 	else
 		HIP_TRY(hipMemcpy(out, h->*recs + (size_t)stream * count, row, hipMemcpyDeviceToHost));
 	return 0;
@@ -2817,6 +2896,27 @@ extern "C" int rtlfm_gpu_input_health(rtlfm_gpu *h, int stream, rtlfm_input_heal
 extern "C" int rtlfm_gpu_input_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n)
 {
 	return fetch_records(h, &rtlfm_gpu::d_ihealth, &rtlfm_gpu::health_nblocks, health_on, true, 0, out, cap, n);
+}
+
+// The last run's records per SOURCE (options source_stats / source_health): -ENODATA while the option is off and while the
+// last run was not one that channels took
+static bool source_stats_on(const rtlfm_gpu *h) { return h->opt.source_stats != 0 && h->chan_per > 0 && h->src_stats_nblocks > 0; }
+static bool source_health_on(const rtlfm_gpu *h) { return h->opt.source_health != 0 && h->chan_per > 0 && h->src_health_nblocks > 0; }
+extern "C" int rtlfm_gpu_source_stats(rtlfm_gpu *h, int source, rtlfm_input_stat *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_src_stats, &rtlfm_gpu::src_stats_nblocks, source_stats_on, false, source, out, cap, n, true);
+}
+extern "C" int rtlfm_gpu_source_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_src_stats, &rtlfm_gpu::src_stats_nblocks, source_stats_on, true, 0, out, cap, n, true);
+}
+extern "C" int rtlfm_gpu_source_health(rtlfm_gpu *h, int source, rtlfm_input_health *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_src_health, &rtlfm_gpu::src_health_nblocks, source_health_on, false, source, out, cap, n, true);
+}
+extern "C" int rtlfm_gpu_source_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_src_health, &rtlfm_gpu::src_health_nblocks, source_health_on, true, 0, out, cap, n, true);
 }
 
 // The raw-byte readers as standalone operators on device memory (no handle): tools/input_stats_bench.py times them, and a
@@ -3366,6 +3466,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
 	if (h->opt.squelch_gate && (r = ensure_gate(h)) < 0) return r;
 	if (h->chan_per > 0 && (r = ensure_channel_buffers(h)) < 0) return r;
+	if ((r = ensure_source_records(h)) < 0) return r;
 	OWN_TRY(in->d_tmp.alloc((size_t)S * in->ostride));
 	OWN_TRY(in->d_tmp_len.alloc((size_t)S));
 	// The views run their audio tail on the handle's main stream: the tails of the two previous
@@ -3393,6 +3494,8 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 			rtlfm_gpu v = make_view(h, 0, S, len);
 			v.st_cur = cur;
 			v.step = step;
+			v.src_rec_off = (size_t)j;  // options source_stats / source_health: each buffer's record over its own length, [source][nb]
+			v.src_rec_stride = nb;
 			r = run_device_impl(&v, in->inp.d_in[f] + (size_t)j * h->cfg.block_len, stride, 1, in->d_tmp, in->ostride, in->d_tmp_len);
 			view_done(h, v);
 			if (r < 0) return r;
@@ -3430,6 +3533,8 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	h->stats_nblocks = h->opt.input_stats ? nb : 0;
 	h->health_nblocks = h->opt.input_health ? nb : 0;
 	h->gate_nblocks = h->opt.squelch_gate ? nb : 0;
+	h->src_stats_nblocks = h->chan_per > 0 && h->opt.source_stats ? nb : 0;
+	h->src_health_nblocks = h->chan_per > 0 && h->opt.source_health ? nb : 0;
 	survey_advance(h, -1);  // (a run of short buffers carries no survey: rtlfm_gpu_bank_survey says -ENODATA)
 	HIP_TRY(hipGetLastError());
 	return 0;

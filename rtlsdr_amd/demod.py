@@ -22,7 +22,7 @@ class GpuDemod:
 
     def __init__(self, cfg: RtlfmCfg, nstreams: int = 1, device: int = 0, lib_path: str | None = None,
                  options: dict | None = None, squelch_gate: bool | None = None, conseq_squelch: int | None = None,
-                 source_dc: bool | None = None):
+                 source_dc: bool | None = None, source_stats: bool | None = None, source_health: bool | None = None):
         self.lib = capi.load(lib_path)  # lib_path: another build of the library (A/B measurements)
         self.cfg = cfg
         self.nstreams = nstreams
@@ -42,6 +42,11 @@ class GpuDemod:
         # the raw DC block per source in front of the channel front ends (include/rtlfm_hip.h, option source_dc)
         if source_dc is not None:
             self.set_option("source_dc", int(bool(source_dc)))
+        # the ADC statistics and the input health per source (include/rtlfm_hip.h, options source_stats / source_health)
+        if source_stats is not None:
+            self.set_option("source_stats", int(bool(source_stats)))
+        if source_health is not None:
+            self.set_option("source_health", int(bool(source_health)))
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -219,6 +224,36 @@ class GpuDemod:
         n = C.c_int()
         check(self.lib.rtlfm_gpu_input_health_all(self._h, out.ctypes.data, cap, C.byref(n)), "rtlfm_gpu_input_health_all")
         return out[:, :n.value].copy()
+
+    def _source_records(self, name: str, dtype, source: int | None) -> np.ndarray:
+        cap = max(1, self.cfg.max_blocks)
+        n = C.c_int()
+        if source is None:
+            nsrc = self.nstreams // self._per_source if self._per_source else self.nstreams
+            out = np.zeros((nsrc, cap), dtype=dtype)
+            check(getattr(self.lib, name + "_all")(self._h, out.ctypes.data, cap, C.byref(n)), name + "_all")
+            return out[:, :n.value].copy()
+        out = np.zeros(cap, dtype=dtype)
+        check(getattr(self.lib, name)(self._h, int(source), out.ctypes.data, cap, C.byref(n)), name)
+        return out[:n.value].copy()
+
+    def source_stats(self, source: int = 0) -> np.ndarray:
+        """``input_stats``' records for the raw bytes of SOURCE ``source`` of the last run that channels took: needs
+        channels on and ``set_option("source_stats", 1)`` before the run (``RtlfmError`` with -ENODATA otherwise)."""
+        return self._source_records("rtlfm_gpu_source_stats", capi.INPUT_STAT_DTYPE, source)
+
+    def source_stats_all(self) -> np.ndarray:
+        """The same for every source in one copy: records [sources, buffers of the last run]."""
+        return self._source_records("rtlfm_gpu_source_stats", capi.INPUT_STAT_DTYPE, None)
+
+    def source_health(self, source: int = 0) -> np.ndarray:
+        """``input_health``'s records for the raw bytes of SOURCE ``source`` of the last run that channels took: needs
+        channels on and ``set_option("source_health", 1)`` before the run."""
+        return self._source_records("rtlfm_gpu_source_health", capi.INPUT_HEALTH_DTYPE, source)
+
+    def source_health_all(self) -> np.ndarray:
+        """The same for every source in one copy: records [sources, buffers of the last run]."""
+        return self._source_records("rtlfm_gpu_source_health", capi.INPUT_HEALTH_DTYPE, None)
 
     def gate(self, stream: int | None = None) -> np.ndarray:
         """The squelch gate's records of the last run (``set_option("squelch_gate", 1)`` before it): a record array with
