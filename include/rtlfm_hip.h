@@ -726,6 +726,63 @@ int rtlfm_gpu_source_stats_all(rtlfm_gpu *h, rtlfm_input_stat *out, int cap, int
 int rtlfm_gpu_source_health(rtlfm_gpu *h, int source, rtlfm_input_health *out, int cap, int *n);
 int rtlfm_gpu_source_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n);
 
+/*
+ * The channel lifecycle: snapshot, resume and regroup by SOURCE ("Lifecycle").
+ *
+ * rtlfm_gpu_save / _load / _state_move stay refused while channels are on (-ENOTSUP): a handle with channels on carries
+ * three things no rtlfm_stream_state record holds -
+ *   pos        the handle's one sample counter (rtlfm_gpu_channels_tell);
+ *   history    with a channel filter or a bank set, every source's last 4096 complex samples as raw bytes, which both re-read
+ *              in front of every run: 8192 bytes per source, oldest sample first, bytes 127 where it was cleared or where a
+ *              run shorter than the history shifted silence in;
+ *   biases     with option "source_dc" as well, what was subtracted from each of the history's sixteen 256-sample pieces:
+ *              16 words per source as the kernels keep them (0x007f007f where nothing was) -
+ * and these calls, beside the old ones, move all of it.  With channels off every one of them is -ENOTSUP and nothing differs.
+ *
+ * rtlfm_gpu_channels_history_get: waits for the handle; *sources is written always; [sources][8192] bytes of the history
+ * and, with "source_dc" on, [sources][16] bias words (dc may be NULL while the option is off).  -ENOTSUP with channels off,
+ * -ENODATA when neither a filter nor a bank is set (nothing is carried then), -ENOBUFS when a cap is too small.
+ * rtlfm_gpu_channels_history_set: the inverse, in the role rtlfm_gpu_state_set_all plays for the records.  sources must be
+ * the handle's (-EINVAL); dc == NULL with "source_dc" on means "none subtracted"; -EBUSY while a run is begun, a ring slot
+ * is open or (option source_ring) buffers are queued.  With rtlfm_gpu_state_get_all / _set_all and rtlfm_gpu_channels_tell /
+ * _seek these two are the route between devices.  rtlfm_gpu_channels_seek clears the history: to resume, seek FIRST, then
+ * history_set.
+ *
+ * rtlfm_gpu_channels_move: the regroup, by source and on the device.  For a < nsources (= dst's sources), m = source_map[a]:
+ * source a of dst receives the per_source records of source m of src (channel c from channel c), its history and its biases;
+ * m == -1 gives demod_init()'s records, a history of bytes 127 and no biases - a source that joins from silence.  An entry
+ * may occur several times (a fan-out); dst == src is a permutation in place.  dst takes src's pos: one counter per handle.
+ * Steps, shared or per-source bins, taps and options do not move - the caller sets them on dst, as it must anyway to switch
+ * channels on there, and every call that clears comes before the move:
+ *   rtlfm_gpu_set_channels, rtlfm_gpu_set_channel_filter / _set_channel_bank, option "source_dc", rtlfm_gpu_channels_move,
+ *   rtlfm_gpu_set_channel_bins.
+ * Waits for both handles, then ONE launch (k_source_move, csrc/state_kernel.h) for records, history and biases.
+ *   -EINVAL       NULL, nsources not dst's sources, or an entry outside [-1, src's sources)
+ *   -ENOTSUP      channels off on either handle
+ *   -EXDEV        different devices: go through the accessors above
+ *   -EMEDIUMTYPE  the handles do not carry the same things: a rtlfm_cfg field other than max_blocks / report_levels,
+ *                 per_source, option "source_dc", the filter (ntaps, shift, taps) or the bank (K, ntaps, shift, taps) differs
+ *   -EBUSY        as rtlfm_gpu_channels_history_set, on either handle
+ * Every refusal leaves both handles as they were.
+ *
+ * rtlfm_gpu_channels_save / _load: all of it to / from a file (include/rtlfm_chansnap.h: magic "RTLFMCHN", checksummed,
+ * written through a temporary file and rename).  save = state_get_all + channels_history_get + channels_tell, with the
+ * steps, the taps and the bins as they rule, + rtlfm_chansnap_write (-EBUSY as rtlfm_gpu_channels_history_set: buffers queued in the ring would be missing from the file).  load
+ * checks the whole file first, changes nothing on any failure and says
+ *   -ERANGE       the file holds another number of streams than the handle
+ *   -EMEDIUMTYPE  the comparison of the move, between the file and the handle
+ *   -ENOTSUP      channels are off (RTLFMSNP files and such handles belong to rtlfm_gpu_load)
+ *   -EBUSY        as above
+ *   -EILSEQ       the file is damaged, or an RTLFMSNP file
+ * The file's steps and bins are for the caller: load neither compares nor applies them (a different step after a resume is
+ * a retune, which keeps a stream's state in the reference too).  Set the handle up as for a move, then load.
+ */
+int rtlfm_gpu_channels_history_get(rtlfm_gpu *h, uint8_t *bytes, size_t cap_bytes, uint32_t *dc, size_t cap_dc, int *sources);
+int rtlfm_gpu_channels_history_set(rtlfm_gpu *h, const uint8_t *bytes, const uint32_t *dc, int sources);
+int rtlfm_gpu_channels_move(rtlfm_gpu *dst, rtlfm_gpu *src, const int32_t *source_map, int nsources);
+int rtlfm_gpu_channels_save(rtlfm_gpu *h, const char *path);
+int rtlfm_gpu_channels_load(rtlfm_gpu *h, const char *path);
+
 int rtlfm_gpu_sync(rtlfm_gpu *h);
 /* Launch on a caller-owned hipStream_t (NULL = the handle's own stream).  On a caller-owned stream
  * EVERYTHING the handle launches is ordered on that stream, the audio tail (deemph, DC block,

@@ -381,6 +381,11 @@ _SIGNATURES = [
     ("rtlfm_gpu_state_move", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     ("rtlfm_gpu_save", C.c_int, [C.c_void_p, C.c_char_p]),
     ("rtlfm_gpu_load", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rtlfm_gpu_channels_history_get", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _P(C.c_int)]),
+    ("rtlfm_gpu_channels_history_set", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("rtlfm_gpu_channels_move", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    ("rtlfm_gpu_channels_save", C.c_int, [C.c_void_p, C.c_char_p]),
+    ("rtlfm_gpu_channels_load", C.c_int, [C.c_void_p, C.c_char_p]),
     ("rtlfm_channel_step", C.c_uint32, [C.c_int32, C.c_uint32]),
     ("rtlfm_channel_table", C.c_int, [C.c_void_p]),
     ("rtlfm_gpu_set_channels", C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
@@ -563,6 +568,41 @@ _SNAPSHOT_SIGNATURES = [
 ]
 DECLARED_SNAPSHOT_SYMBOLS = [s[0] for s in _SNAPSHOT_SIGNATURES]
 
+class RtlfmChansnapHdr(C.Structure):
+    """``rtlfm_chansnap_hdr`` — the header fields of a channel snapshot (include/rtlfm_chansnap.h)."""
+
+    _fields_ = [("pos", C.c_uint64), ("nstreams", C.c_uint32), ("per_source", C.c_uint32), ("flags", C.c_uint32),
+                ("fir_ntaps", C.c_uint32), ("fir_shift", C.c_uint32), ("bank_K", C.c_uint32), ("bank_ntaps", C.c_uint32),
+                ("bank_shift", C.c_uint32), ("hist_samples", C.c_uint32), ("dc_pieces", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class RtlfmChansnapParts(C.Structure):
+    """``rtlfm_chansnap_parts`` — the writer's sections."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("cfg", "steps", "fir_taps", "bank_taps", "bins", "states", "hist", "dc")]
+
+
+class RtlfmChansnapBufs(C.Structure):
+    """``rtlfm_chansnap_bufs`` — where the reader puts each section and how many elements fit there."""
+
+    _fields_ = [("cfg", C.c_void_p)] + [f for n in ("steps", "fir_taps", "bank_taps", "bins", "states", "hist", "dc")
+                                        for f in ((n, C.c_void_p), ("cap_" + n, C.c_size_t))]
+
+
+CHANSNAP_HIST, CHANSNAP_DC_PIECES, CHANSNAP_DC_NONE = 4096, 16, 0x007F007F  # RTLFM_CHANSNAP_*
+CHANSNAP_FLAG_SOURCE_DC, CHANSNAP_FLAG_HISTORY = 1, 2
+
+# ... and include/rtlfm_chansnap.h (the file of rtlfm_gpu_channels_save / _load; host code inside the same library)
+_CHANSNAP_SIGNATURES = [
+    ("rtlfm_chansnap_write", C.c_int, [C.c_char_p, _P(RtlfmChansnapHdr), _P(RtlfmChansnapParts)]),
+    ("rtlfm_chansnap_info", C.c_int, [C.c_char_p, _P(RtlfmChansnapHdr), _P(RtlfmCfg)]),
+    ("rtlfm_chansnap_read", C.c_int, [C.c_char_p, _P(RtlfmChansnapHdr), _P(RtlfmChansnapBufs)]),
+]
+DECLARED_CHANSNAP_SYMBOLS = [s[0] for s in _CHANSNAP_SIGNATURES]
+
 DECLARED_SYMBOLS = [s[0] for s in _SIGNATURES]
 DECLARED_FM_SYMBOLS = [s[0] for s in _SIGNATURES if s[0].startswith("rtlfm_")]
 DECLARED_POWER_SYMBOLS = [s[0] for s in _POWER_SIGNATURES]
@@ -597,7 +637,7 @@ def load(path: str | None = None) -> C.CDLL:
         pass
     lib = C.CDLL(p)
     for name, res, args in (_SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES + _SNAPSHOT_SIGNATURES
-                            + _SLOTS_SIGNATURES):
+                            + _SLOTS_SIGNATURES + _CHANSNAP_SIGNATURES):
         if p != LIB_PATH and not hasattr(lib, name):
             continue  # an explicitly named other build (`path` or RTLFM_HIP_LIB: A/B against an earlier revision) may predate a symbol
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
@@ -627,3 +667,66 @@ def snapshot_info(path: str):
     cfg, n = RtlfmCfg(), C.c_int()
     check(load().rtlfm_snapshot_info(os.fsencode(path), C.byref(cfg), C.byref(n)), "rtlfm_snapshot_info")
     return cfg, n.value
+
+
+def chansnap_info(path: str):
+    """rtlfm_chansnap_info: (RtlfmChansnapHdr, RtlfmCfg) of a channel snapshot (include/rtlfm_chansnap.h) that passes every
+    check of its format, the checksum included; RtlfmError otherwise (-EILSEQ for a damaged file or one of the other
+    kind).  Needs no GPU."""
+    hdr, cfg = RtlfmChansnapHdr(), RtlfmCfg()
+    check(load().rtlfm_chansnap_info(os.fsencode(path), C.byref(hdr), C.byref(cfg)), "rtlfm_chansnap_info")
+    return hdr, cfg
+
+
+def chansnap_read(path: str) -> dict:
+    """rtlfm_chansnap_read: the whole file as a dict - ``hdr``, ``cfg``, ``steps`` uint32 [n], ``fir_taps`` / ``bank_taps``
+    int16, ``bins`` int32 [sources, per_source] (empty without a bank), ``states`` (a ctypes array of RtlfmStreamState),
+    ``hist`` uint8 [sources, 8192] and ``dc`` uint32 [sources, 16] (empty where the file holds none).  Needs no GPU."""
+    import numpy as np
+    hdr, cfg = chansnap_info(path)
+    n, nsrc = hdr.nstreams, hdr.nstreams // hdr.per_source
+    hist = bool(hdr.flags & CHANSNAP_FLAG_HISTORY)
+    dc = hist and bool(hdr.flags & CHANSNAP_FLAG_SOURCE_DC)
+    out = dict(cfg=RtlfmCfg(), steps=np.zeros(n, np.uint32), fir_taps=np.zeros(hdr.fir_ntaps, np.int16),
+               bank_taps=np.zeros(hdr.bank_ntaps, np.int16), bins=np.zeros((nsrc if hdr.bank_K else 0, hdr.per_source), np.int32),
+               states=(RtlfmStreamState * n)(), hist=np.zeros((nsrc if hist else 0, 2 * CHANSNAP_HIST), np.uint8),
+               dc=np.zeros((nsrc if dc else 0, CHANSNAP_DC_PIECES), np.uint32))
+    b = RtlfmChansnapBufs(cfg=C.addressof(out["cfg"]), states=C.addressof(out["states"]), cap_states=n)
+    for k in ("steps", "fir_taps", "bank_taps", "bins", "hist", "dc"):
+        setattr(b, k, out[k].ctypes.data)
+        setattr(b, "cap_" + k, out[k].size)
+    h2 = RtlfmChansnapHdr()
+    check(load().rtlfm_chansnap_read(os.fsencode(path), C.byref(h2), C.byref(b)), "rtlfm_chansnap_read")
+    out["hdr"] = h2
+    return out
+
+
+def chansnap_write(path: str, cfg: RtlfmCfg, per_source: int, pos: int, steps, states, fir_taps=None, fir_shift: int = 0, bank_K: int = 0,
+                   bank_taps=None, bank_shift: int = 0, bins=None, hist=None, dc=None, source_dc: bool = False):
+    """rtlfm_chansnap_write: a channel snapshot from its parts (``states``: a ctypes array of RtlfmStreamState; ``hist`` is
+    needed exactly where a filter or a bank is given, ``dc = None`` with ``source_dc`` writes "none subtracted").  The
+    file appears whole or not at all.  Needs no GPU."""
+    import numpy as np
+    st = np.ascontiguousarray(steps, np.uint32)
+    ft = np.ascontiguousarray([] if fir_taps is None else fir_taps, np.int16)
+    bt = np.ascontiguousarray([] if bank_taps is None else bank_taps, np.int16)
+    bn = np.ascontiguousarray([] if bins is None else bins, np.int32)
+    hs = np.ascontiguousarray([] if hist is None else hist, np.uint8)
+    dw = None if dc is None else np.ascontiguousarray(dc, np.uint32)
+    if not isinstance(states, C.Array):
+        states = (RtlfmStreamState * len(states))(*states)
+    n = len(states)
+    has_hist = ft.size > 0 or bank_K > 0
+    nsrc = n // per_source if per_source > 0 else 0
+    if st.size != n or (bank_K and bn.size != n) or (has_hist and hs.size != nsrc * 2 * CHANSNAP_HIST) or \
+            (dw is not None and dw.size != nsrc * CHANSNAP_DC_PIECES):
+        raise ValueError("chansnap_write: a section's size does not follow from the header")
+    hdr = RtlfmChansnapHdr(pos=pos, nstreams=n, per_source=per_source,
+                           flags=(CHANSNAP_FLAG_SOURCE_DC if source_dc else 0) | (CHANSNAP_FLAG_HISTORY if has_hist else 0),
+                           fir_ntaps=ft.size, fir_shift=fir_shift, bank_K=bank_K, bank_ntaps=bt.size if bank_K else 0,
+                           bank_shift=bank_shift if bank_K else 0)
+    parts = RtlfmChansnapParts(cfg=C.addressof(cfg), steps=st.ctypes.data, fir_taps=ft.ctypes.data if ft.size else None,
+                               bank_taps=bt.ctypes.data if bt.size else None, bins=bn.ctypes.data if bn.size else None,
+                               states=C.addressof(states), hist=hs.ctypes.data if hs.size else None,
+                               dc=None if dw is None else dw.ctypes.data)
+    check(load().rtlfm_chansnap_write(os.fsencode(path), C.byref(hdr), C.byref(parts)), "rtlfm_chansnap_write")

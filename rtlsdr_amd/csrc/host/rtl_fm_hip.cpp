@@ -89,6 +89,16 @@
 // fed the full length for a completed short last buffer - the record is over the completed buffer - and nothing for a
 // source that has ended: the bytes 127 it is fed must not ramp its gain.  The PCM files are those of the run without it.
 //
+// -k file / -u file (not reference letters; with -X only): keep / take up, -K / -R for channels.  -k writes, behind the last
+// run, everything the handle carries - every stream's record, the handle's sample counter, every source's history and its
+// bias pieces - to a channel snapshot (rtlfm_gpu_channels_save, include/rtlfm_chansnap.h: its own file kind, magic RTLFMCHN);
+// -u loads such a file in front of the first buffer (rtlfm_gpu_channels_load).  -u's file is checked against what the command
+// line plans before a device is opened: n x K records, K per source, -x's taps and shift, -E srcdc, the configuration;
+// anything else is refused with the library's text, exit status 2.  The PCM of "first half with -k" + "second half with
+// -u" is the PCM of the whole capture, cut at a buffer boundary, for every out_%d.raw.  Not without -X (-K / -R are the
+// letters for independent streams), not with -S, -C or -E srcagc: those engines carry state of their own that the file does
+// not hold.  -X with -K / -R stays refused.
+//
 // Not restated (out of scope): the command file's own hop (its 2 x 3 200 000 byte mute, the DC-filter reset, -B), and
 // -t negative (terminate on squelch).
 //
@@ -124,6 +134,7 @@
 #include "../../../include/rtlfm_monitor.h"
 #include "../../../include/rtlfm_scan.h"
 #include "../../../include/rtlfm_snapshot.h"
+#include "../../../include/rtlfm_chansnap.h"
 #include "../../../include/rtlsdr_file.h"
 #include "wavhdr.h"
 
@@ -157,6 +168,7 @@ struct Settings {
 	bool zero_copy = false;  // -Z: the device layer reads straight into the pinned staging ring
 	const char *filename = "-", *cmd_file = nullptr, *scan_file = nullptr, *keep_file = nullptr, *resume_file = nullptr;
 	const char *chan_file = nullptr, *opt_string = nullptr;
+	const char *chan_keep_file = nullptr, *chan_resume_file = nullptr;  // -k / -u: -K / -R for -X (a channel snapshot)
 	bool source_dc = false;  // -E srcdc: the library's option source_dc (with -X only)
 	bool source_agc = false; // -E srcagc: the software AGC per source (with -X only; not with agc= in -O)
 	int agc = -1;        // -O agc=<n>; -1: not given
@@ -1372,6 +1384,24 @@ void demod_thread_channels(Multi *m)
 	demod_done(m);
 }
 
+// -x's filter: rtlfm_channel_lowpass at the cutoff the benchmarks use, 0.4 of the output rate in cycles per capture sample.
+// (-ERANGE: fewer taps than the gain D needs at shift 14 - a tap beyond an int16, a short filter at a large D.  The same
+// filter at half the scale and one bit less shift has the same DC gain, as long as D stays whole.)  Host arithmetic: -u's
+// check asks it before a device is opened, run_channels when it sets the filter.
+int plan_chan_filter(const rtlfm_cfg &c, int ntaps, int16_t *taps, int *shift, int *gain_out)
+{
+	int gain = c.downsample, less = 0;
+	int r = rtlfm_channel_lowpass(ntaps, 0.4 / c.downsample, gain, taps, shift);
+	while (r == -ERANGE && gain % 2 == 0 && less < 14) {
+		gain /= 2;
+		less++;
+		r = rtlfm_channel_lowpass(ntaps, 0.4 / c.downsample, gain, taps, shift);
+	}
+	*shift -= less;
+	*gain_out = gain;
+	return r;
+}
+
 // everything after option parsing for -X (main has refused what -X does not allow): freqs[i] = source i's -f as given,
 // chan_freqs[i] = its K channel frequencies, each within capture_rate / 2 of freqs[i]
 int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const std::vector<std::vector<uint32_t>> &chan_freqs)
@@ -1422,22 +1452,17 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 			if (r == -ENOTSUP) r = 0;
 		}
 		if (r == 0 && ntaps > 0) {
-			// the cutoff the benchmarks use: 0.4 of the output rate, in cycles per capture sample
 			std::vector<int16_t> taps((size_t)ntaps);
-			int shift = 0;
+			int shift = 0, gain = 0;
 			what = "rtlfm_channel_lowpass";
-			// (-ERANGE: fewer taps than the gain D needs at shift 14 - a tap beyond an int16, a short filter at a large D.  The
-			// same filter at half the scale and one bit less shift has the same DC gain, as long as D stays whole.)
-			int gain = c.downsample, less = 0;
-			r = rtlfm_channel_lowpass(ntaps, 0.4 / c.downsample, gain, taps.data(), &shift);
-			while (r == -ERANGE && gain % 2 == 0 && less < 14) {
-				gain /= 2;
-				less++;
-				r = rtlfm_channel_lowpass(ntaps, 0.4 / c.downsample, gain, taps.data(), &shift);
-			}
-			shift -= less;
-			if (r == 0 && (less || st.verbosity)) fprintf(stderr, "-x %d: gain %d at shift %d\n", ntaps, gain, shift);
+			r = plan_chan_filter(c, ntaps, taps.data(), &shift, &gain);
+			if (r == 0 && (gain != c.downsample || st.verbosity)) fprintf(stderr, "-x %d: gain %d at shift %d\n", ntaps, gain, shift);
 			if (r == 0) { what = "rtlfm_gpu_set_channel_filter"; r = rtlfm_gpu_set_channel_filter(m.gpu, taps.data(), ntaps, shift); }
+		}
+		if (r == 0 && st.chan_resume_file) {  // -u: in front of the first buffer, behind everything that clears
+			what = st.chan_resume_file;
+			r = rtlfm_gpu_channels_load(m.gpu, st.chan_resume_file);
+			if (r < 0) fprintf(stderr, "-u ");
 		}
 		if (r < 0) {
 			fprintf(stderr, "%s: %s\n", what, rtlfm_gpu_strerror(r));
@@ -1453,6 +1478,13 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 		summary(m.out.data(), m.out.size(), in, nullptr, m.failed, st.verbosity > 0);
 		if (m.hl.agc) health_report(&m.hl);
 		if (m.failed) ret = 3;
+		if (!ret && st.chan_keep_file) {  // -k: behind the last run
+			const int r = rtlfm_gpu_channels_save(m.gpu, st.chan_keep_file);
+			if (r < 0) {
+				fprintf(stderr, "-k %s: %s\n", st.chan_keep_file, rtlfm_gpu_strerror(r));
+				ret = 3;
+			}
+		}
 	}
 	if (m.hl.agc) rtlfm_agc_destroy(m.hl.agc);
 	close_all(&m);
@@ -1477,6 +1509,39 @@ int check_resume(const char *path, const rtlfm_cfg &planned, int nstreams)
 	return 2;
 }
 
+// -u: the channel snapshot against what the command line plans, before a device is opened: 0, or the exit status (2) behind
+// the library's text.  The handle makes the same comparison again when it loads the file (rtlfm_gpu_channels_load).
+int check_chan_resume(const char *path, const Settings &st, int nstreams, int K)
+{
+	const rtlfm_cfg &planned = st.cfg;
+	const int ntaps = st.chan_taps > 0 ? st.chan_taps : 0;
+	rtlfm_chansnap_hdr hd;
+	rtlfm_cfg saved;
+	int r = rtlfm_chansnap_info(path, &hd, &saved);
+	if (r == 0 && hd.nstreams != (uint32_t)nstreams) r = -ERANGE;
+	if (r == 0) {
+		saved.max_blocks = planned.max_blocks;        // how much a run takes and what it reports, not what a stream carries
+		saved.report_levels = planned.report_levels;
+		const bool dc = (hd.flags & RTLFM_CHANSNAP_FLAG_SOURCE_DC) != 0;
+		if (memcmp(&saved, &planned, sizeof(saved)) != 0 || hd.per_source != (uint32_t)K || dc != st.source_dc || hd.bank_K != 0 ||
+		    hd.fir_ntaps != (uint32_t)ntaps)
+			r = -EMEDIUMTYPE;
+	}
+	if (r == 0 && ntaps > 0) {
+		std::vector<int16_t> want((size_t)ntaps), got((size_t)ntaps);
+		int shift = 0, gain = 0;
+		rtlfm_chansnap_bufs b{};
+		b.fir_taps = got.data();
+		b.cap_fir_taps = got.size();
+		r = plan_chan_filter(planned, ntaps, want.data(), &shift, &gain);
+		if (r == 0) r = rtlfm_chansnap_read(path, nullptr, &b);
+		if (r == 0 && ((uint32_t)shift != hd.fir_shift || memcmp(want.data(), got.data(), got.size() * sizeof(int16_t)) != 0)) r = -EMEDIUMTYPE;
+	}
+	if (r == 0) return 0;
+	fprintf(stderr, "-u %s: %s\n", path, rtlfm_gpu_strerror(r));
+	return 2;
+}
+
 void usage()
 {
 	fprintf(stderr,
@@ -1493,10 +1558,14 @@ void usage()
 	        "\t       and a:b:step ranges; needs -l; a source whose squelch holds a buffer hops to its next frequency; not with -C]\n"
 	        "\t[-X channel_file  channels: line i of the file is the list of channel frequencies of source i (-N n, or one source), in\n"
 	        "\t       -S's grammar, the same number K on every line; source i's centre frequency is its -f as given and its K channels are mixed\n"
-	        "\t       down on the GPU; stream s = channel s %% K of source s / K writes the file with %%d = s; not with -S -C -K -R -Z,\n"
+	        "\t       down on the GPU; stream s = channel s %% K of source s / K writes the file with %%d = s; not with -S -C -K -R -Z (-k / -u keep and take up),\n"
 	        "\t       -O agc=2 or -E rdc; -E srcdc takes every source's DC spike off in front of the mixers (-q sets its constant);\n"
 	        "\t       -E srcagc is the software AGC for every SOURCE from the GPU's records of its raw bytes (-v prints every change; not with agc= in -O)]\n"
 	        "\t[-x ntaps  with -X: a windowed-sinc channel filter of ntaps taps (cutoff 0.4 of the output rate) in the boxcar's place; not with -F]\n"
+	        "\t[-k file  with -X: keep - write everything the handle carries (every stream's state, the sample counter, every source's\n"
+	        "\t       history) to a channel snapshot at exit;  -u file  with -X: take up - load such a file before the first buffer; it must come\n"
+	        "\t       from the same -N / -X (K) / -x / -E srcdc / -M / -s ... plan, else exit 2; the output continues as if the tool had never\n"
+	        "\t       stopped.  Not without -X (there: -K / -R), not with -S, -C or -E srcagc: those engines carry state the file does not hold]\n"
 	        "\t[-K file  keep: write every stream's carried filter state to file at exit (with -N n: n records, in source order)]\n"
 	        "\t[-R file  resume: load such a file before the first buffer - it must hold as many records as there are sources and\n"
 	        "\t       come from the same -M / -s / -r / -F / -A / -E / -l / -W ... plan, else exit 2; the output continues as if the tool had\n"
@@ -1534,7 +1603,7 @@ int main(int argc, char **argv)
 	c.rate_out = 24000;
 	c.max_blocks = 8;
 	int opt;
-	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:K:R:X:x:")) != -1) {
+	while ((opt = getopt(argc, argv, "d:f:g:s:l:o:t:r:p:E:F:A:M:hm:L:q:c:W:HvZN:C:O:S:K:R:X:x:k:u:")) != -1) {
 		switch (opt) {
 		case 'd': st.dev_index = atoi(optarg); break;
 		case 'f': freq = (uint32_t)atofs(optarg); freqs.push_back(freq); have_freq = true; break;
@@ -1545,6 +1614,8 @@ int main(int argc, char **argv)
 		case 'R': st.resume_file = optarg; break;
 		case 'X': st.chan_file = optarg; break;
 		case 'x': st.chan_taps = atoi(optarg); break;
+		case 'k': st.chan_keep_file = optarg; break;
+		case 'u': st.chan_resume_file = optarg; break;
 		case 'O':
 			st.opt_string = optarg;
 			st.agc = opt_string_agc(optarg);
@@ -1636,6 +1707,21 @@ int main(int argc, char **argv)
 	if (st.chan_taps != -1 && !st.chan_file) {
 		fprintf(stderr, "-x (taps of the channel filter) needs -X (the channel file): the filter acts on channels only.\n");
 		return 1;
+	}
+	if (st.chan_keep_file || st.chan_resume_file) {
+		// before a device is opened - and before -X's own refusals, so that the line names both letters
+		const char *me = st.chan_keep_file ? "-k (keep the channels' carried state)" : "-u (take up the channels' carried state)";
+		if (!st.chan_file) {
+			fprintf(stderr, "%s needs -X (the channel file): a channel snapshot holds what a handle with channels carries; "
+			                "for independent streams the letters are -K / -R.\n", me);
+			return 1;
+		}
+		const char *with = st.scan_file ? "-S (scan lists)" : st.cmd_file ? "-C (command file)" : st.source_agc ? "-E srcagc (software AGC per source)" : nullptr;
+		if (with) {
+			fprintf(stderr, "%s does not go with %s: -k / -u do not go with -S, -C or -E srcagc, those engines carry state of their own "
+			                "that the file does not hold.\n", me, with);
+			return 1;
+		}
 	}
 	if (st.chan_file) {
 		// everything -X refuses for what it is combined with is refused here, before a device is opened or a handle created:
@@ -1769,6 +1855,8 @@ int main(int argc, char **argv)
 					return 1;
 				}
 			}
+		if (st.chan_resume_file)
+			if (const int r = check_chan_resume(st.chan_resume_file, st, (int)total, (int)chan_freqs[0].size())) return r;
 		return run_channels(st, freqs, chan_freqs);
 	}
 	const bool multi = nstreams > 1 || st.cmd_file || st.scan_file;

@@ -39,6 +39,7 @@
 #include "channel_fir_kernel.h"
 #include "channel_bank_kernel.h"
 #include "../../include/rtlfm_snapshot.h"
+#include "../../include/rtlfm_chansnap.h"
 
 using namespace rtlfm;
 using namespace rtlfm::plan;
@@ -1057,6 +1058,241 @@ extern "C" int rtlfm_gpu_channels_tell(rtlfm_gpu *h, uint64_t *pos)
 {
 	if (!h || !pos) return -EINVAL;
 	*pos = h->chan_pos;
+	return 0;
+}
+
+// ---- the channel lifecycle: what a handle with channels on carries beyond the records (include/rtlfm_hip.h) ----
+
+static_assert(statemove::kHistPieces * 16 == channel::kHist * 2 && statemove::kDcWords == channel::kDcHist, "k_source_move moves the history the channel kernels keep");
+static_assert(RTLFM_CHANSNAP_HIST == channel::kHist && RTLFM_CHANSNAP_DC_PIECES == channel::kDcHist && RTLFM_CHANSNAP_DC_NONE == channel::kDcNone,
+              "the file holds the history the channel kernels keep");
+
+// a history is carried: channels on and something set that re-reads it
+static inline bool carries_history(const rtlfm_gpu *h) { return h->chan_per > 0 && (h->fir_ntaps > 0 || h->bank_K > 0); }
+
+// what _channels_move, _channels_history_set and _channels_load must not interrupt
+static bool lifecycle_busy(rtlfm_gpu *h) { return ingest_busy(h) || (h->opt.source_ring && ingest_queued(h)); }
+
+extern "C" int rtlfm_gpu_channels_history_get(rtlfm_gpu *h, uint8_t *bytes, size_t cap_bytes, uint32_t *dc, size_t cap_dc, int *sources)
+{
+	if (!h || !sources) return -EINVAL;
+	*sources = h->chan_per > 0 ? h->nstreams / h->chan_per : 0;
+	if (h->chan_per <= 0) return -ENOTSUP;
+	if (!carries_history(h)) return -ENODATA;
+	if (!bytes || (h->opt.source_dc && !dc)) return -EINVAL;
+	const size_t nsrc = (size_t)*sources;
+	if (cap_bytes < nsrc * channel::kHist * 2 || (h->opt.source_dc && cap_dc < nsrc * channel::kDcHist)) return -ENOBUFS;
+	if (!h->d_src_hist[0] || !h->d_src_hist[1] || (size_t)h->src_hist_srcs < nsrc) return -EFAULT;
+	if (h->opt.source_dc && (!h->d_sdc_hist[0] || !h->d_sdc_hist[1])) return -EFAULT;  // (before anything is written to an output)
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	HIP_TRY(hipMemcpy(bytes, h->d_src_hist[h->src_hist_cur], nsrc * channel::kHist * 2, hipMemcpyDeviceToHost));
+	if (h->opt.source_dc) {
+		HIP_TRY(hipMemcpy(dc, h->d_sdc_hist[h->src_hist_cur], nsrc * channel::kDcHist * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	}
+	return 0;
+}
+
+// A history and its biases into the buffers that are NOT current; the caller changes over (src_hist_cur ^= 1) once everything
+// that belongs together has arrived, so a copy that fails half way leaves the history where it was.  The handle is idle
+// behind sync_all - nothing reads or writes either copy - and the buffers are there: the callers have seen to both.
+static int history_stage(rtlfm_gpu *h, const uint8_t *bytes, const uint32_t *dc, size_t nsrc)
+{
+	const int next = h->src_hist_cur ^ 1;
+	HIP_TRY(hipMemcpy(h->d_src_hist[next], bytes, nsrc * channel::kHist * 2, hipMemcpyHostToDevice));
+	if (!h->opt.source_dc) return 0;
+	if (dc) {
+		HIP_TRY(hipMemcpy(h->d_sdc_hist[next], dc, nsrc * channel::kDcHist * sizeof(uint32_t), hipMemcpyHostToDevice));
+	} else {
+		HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->d_sdc_hist[next].get(), (int)channel::kDcNone, nsrc * channel::kDcHist, h->stream));
+		HIP_TRY(hipStreamSynchronize(h->stream));
+	}
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_channels_history_set(rtlfm_gpu *h, const uint8_t *bytes, const uint32_t *dc, int sources)
+{
+	if (!h || !bytes) return -EINVAL;
+	if (h->chan_per <= 0) return -ENOTSUP;
+	if (sources != h->nstreams / h->chan_per) return -EINVAL;
+	if (!carries_history(h)) return -ENODATA;
+	if (lifecycle_busy(h)) return -EBUSY;
+	const size_t nsrc = (size_t)sources;
+	if (!h->d_src_hist[0] || !h->d_src_hist[1] || (size_t)h->src_hist_srcs < nsrc) return -EFAULT;
+	if (h->opt.source_dc && (!h->d_sdc_hist[0] || !h->d_sdc_hist[1])) return -EFAULT;
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	const int r = history_stage(h, bytes, dc, nsrc);
+	if (r < 0) return r;
+	h->src_hist_cur ^= 1;
+	return 0;
+}
+
+// -EMEDIUMTYPE's comparison, for the move and the load: the carried cfg, per_source, source_dc, the filter and the bank
+static bool same_carried(const rtlfm_cfg &cfg, int per, int source_dc, int fir_ntaps, int fir_shift, const int16_t *fir_taps, int bank_K, int bank_ntaps,
+                         int bank_shift, const int16_t *bank_taps, const rtlfm_gpu *h)
+{
+	if (!same_carried_cfg(cfg, h->cfg) || per != h->chan_per || (source_dc != 0) != (h->opt.source_dc != 0)) return false;
+	if (fir_ntaps != h->fir_ntaps || fir_shift != h->fir_shift) return false;
+	if (fir_ntaps > 0 && memcmp(fir_taps, h->fir_taps.data(), (size_t)fir_ntaps * sizeof(int16_t)) != 0) return false;
+	if (bank_K != h->bank_K) return false;
+	if (bank_K > 0) {
+		if (bank_ntaps != h->bank_ntaps || bank_shift != h->bank_shift) return false;
+		if (memcmp(bank_taps, h->bank_taps.data(), (size_t)bank_ntaps * sizeof(int16_t)) != 0) return false;
+	}
+	return true;
+}
+
+// The regroup by SOURCE, one launch (k_source_move, state_kernel.h).  Ordering as rtlfm_gpu_state_move's, also for dst == src:
+// both handles are idle behind sync_all, the kernel reads src's current state copy and current history and writes dst's NEXT
+// state copy and the history buffers that are NOT current, which nothing reads before st_cur / src_hist_cur have changed
+// over, and they change over - with pos - only behind the synchronisation that follows the launch.  A failure before that
+// leaves the handle where it was.
+extern "C" int rtlfm_gpu_channels_move(rtlfm_gpu *dst, rtlfm_gpu *src, const int32_t *source_map, int nsources)
+{
+	if (!dst || !src || !source_map) return -EINVAL;
+	if (dst->chan_per <= 0 || src->chan_per <= 0) return -ENOTSUP;
+	const int dsrcs = dst->nstreams / dst->chan_per, ssrcs = src->nstreams / src->chan_per;
+	if (nsources != dsrcs) return -EINVAL;
+	for (int a = 0; a < nsources; a++)
+		if (source_map[a] < -1 || source_map[a] >= ssrcs) return -EINVAL;
+	if (dst->device != src->device) return -EXDEV;
+	if (!same_carried(src->cfg, src->chan_per, src->opt.source_dc, src->fir_ntaps, src->fir_shift, src->fir_taps.data(), src->bank_K, src->bank_ntaps,
+	                  src->bank_shift, src->bank_taps.data(), dst))
+		return -EMEDIUMTYPE;
+	if (lifecycle_busy(dst) || (src != dst && lifecycle_busy(src))) return -EBUSY;
+	const bool hist = carries_history(dst), dc = hist && dst->opt.source_dc;
+	if (hist && (!dst->d_src_hist[0] || !dst->d_src_hist[1] || !src->d_src_hist[0] || !src->d_src_hist[1] || dst->src_hist_srcs < dsrcs || src->src_hist_srcs < ssrcs)) return -EFAULT;
+	if (dc && (!dst->d_sdc_hist[0] || !dst->d_sdc_hist[1] || !src->d_sdc_hist[0] || !src->d_sdc_hist[1])) return -EFAULT;
+	HIP_TRY(hipSetDevice(dst->device));
+	OWN_TRY(dst->d_move_map.alloc((size_t)dst->nstreams));  // (nstreams: rtlfm_gpu_state_move shares it once channels are off)
+	HIP_TRY(sync_all(src));
+	if (src != dst) HIP_TRY(sync_all(dst));
+	HIP_TRY(hipMemcpy(dst->d_move_map, source_map, (size_t)nsources * sizeof(int32_t), hipMemcpyHostToDevice));
+	const int next = (dst->st_cur + 1) % 3, hnext = dst->src_hist_cur ^ 1;
+	statemove::SourceMove p{};
+	p.dst_rec = reinterpret_cast<uint32_t *>(dst->st[next].get());
+	p.src_rec = reinterpret_cast<const uint32_t *>(src->st[src->st_cur].get());
+	if (hist) {
+		p.dst_hist = reinterpret_cast<uint4 *>(dst->d_src_hist[hnext].get());
+		p.src_hist = reinterpret_cast<const uint4 *>(src->d_src_hist[src->src_hist_cur].get());
+	}
+	if (dc) {
+		p.dst_dc = dst->d_sdc_hist[hnext].get();
+		p.src_dc = src->d_sdc_hist[src->src_hist_cur].get();
+	}
+	p.map = dst->d_move_map;
+	p.nsrc = (uint32_t)nsources;
+	p.per = (uint32_t)dst->chan_per;
+	p.dc_none = channel::kDcNone;
+	const int r = statemove::launch_source_move(p, dst->stream);
+	if (r < 0) return r;
+	HIP_TRY(hipStreamSynchronize(dst->stream));
+	dst->st_cur = next;
+	if (hist) dst->src_hist_cur = hnext;
+	dst->chan_pos = src->chan_pos;
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_channels_save(rtlfm_gpu *h, const char *path)
+{
+	if (!h || !path) return -EINVAL;
+	if (h->chan_per <= 0) return -ENOTSUP;
+	// (a run begun and not ended: pos and the records are between two states; buffers queued over the source ring: the file
+	// would silently lack them)
+	if (lifecycle_busy(h)) return -EBUSY;
+	const size_t n = (size_t)h->nstreams, nsrc = n / (size_t)h->chan_per;
+	const bool hist = carries_history(h), dc = hist && h->opt.source_dc;
+	std::vector<state_t> st;
+	std::vector<uint32_t> steps, dcw;
+	std::vector<uint8_t> bytes;
+	std::vector<int32_t> bins;
+	try {
+		st.resize(n);
+		steps.resize(n);
+		if (hist) bytes.resize(nsrc * channel::kHist * 2);
+		if (dc) dcw.resize(nsrc * channel::kDcHist);
+		if (h->bank_K > 0) bins.resize(n);
+	} catch (const std::bad_alloc &) {
+		return -ENOMEM;
+	}
+	int got = 0, r;
+	if ((r = rtlfm_gpu_state_get_all(h, st.data(), h->nstreams, &got)) < 0) return r;
+	if (hist && (r = rtlfm_gpu_channels_history_get(h, bytes.data(), bytes.size(), dc ? dcw.data() : nullptr, dcw.size(), &got)) < 0) return r;
+	HIP_TRY(hipMemcpy(steps.data(), h->d_chan_steps, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (h->bank_K > 0 && (r = rtlfm_gpu_get_channel_bins(h, bins.data(), h->nstreams)) < 0) return r;
+	rtlfm_chansnap_hdr hd{};
+	hd.pos = h->chan_pos;
+	hd.nstreams = (uint32_t)h->nstreams;
+	hd.per_source = (uint32_t)h->chan_per;
+	hd.flags = (h->opt.source_dc ? RTLFM_CHANSNAP_FLAG_SOURCE_DC : 0u) | (hist ? RTLFM_CHANSNAP_FLAG_HISTORY : 0u);
+	hd.fir_ntaps = (uint32_t)h->fir_ntaps;
+	hd.fir_shift = (uint32_t)h->fir_shift;
+	hd.bank_K = (uint32_t)h->bank_K;
+	hd.bank_ntaps = h->bank_K > 0 ? (uint32_t)h->bank_ntaps : 0u;
+	hd.bank_shift = h->bank_K > 0 ? (uint32_t)h->bank_shift : 0u;
+	rtlfm_chansnap_parts pt{};
+	pt.cfg = &h->cfg;
+	pt.steps = steps.data();
+	pt.fir_taps = h->fir_taps.data();
+	pt.bank_taps = h->bank_taps.data();
+	pt.bins = bins.data();
+	pt.states = st.data();
+	pt.hist = bytes.data();
+	pt.dc = dc ? dcw.data() : nullptr;
+	return rtlfm_chansnap_write(path, &hd, &pt);
+}
+
+extern "C" int rtlfm_gpu_channels_load(rtlfm_gpu *h, const char *path)
+{
+	if (!h || !path) return -EINVAL;
+	if (h->chan_per <= 0) return -ENOTSUP;
+	rtlfm_chansnap_hdr hd;
+	rtlfm_cfg cfg;
+	int r = rtlfm_chansnap_info(path, &hd, &cfg);  // (checks the whole file, the checksum included)
+	if (r < 0) return r;
+	if (hd.nstreams != (uint32_t)h->nstreams) return -ERANGE;
+	const size_t n = hd.nstreams, nsrc = n / hd.per_source;
+	const bool hist = (hd.flags & RTLFM_CHANSNAP_FLAG_HISTORY) != 0, dc = hist && (hd.flags & RTLFM_CHANSNAP_FLAG_SOURCE_DC);
+	std::vector<state_t> st;
+	std::vector<uint32_t> dcw;
+	std::vector<uint8_t> bytes;
+	std::vector<int16_t> ftaps, btaps;
+	try {
+		st.resize(n);
+		ftaps.resize(hd.fir_ntaps);
+		btaps.resize(hd.bank_ntaps);
+		if (hist) bytes.resize(nsrc * channel::kHist * 2);
+		if (dc) dcw.resize(nsrc * channel::kDcHist);
+	} catch (const std::bad_alloc &) {
+		return -ENOMEM;
+	}
+	rtlfm_chansnap_hdr hd2;
+	rtlfm_chansnap_bufs b{};
+	b.fir_taps = ftaps.data(); b.cap_fir_taps = ftaps.size();
+	b.bank_taps = btaps.data(); b.cap_bank_taps = btaps.size();
+	b.states = st.data(); b.cap_states = st.size();
+	b.hist = hist ? bytes.data() : nullptr; b.cap_hist = bytes.size();
+	b.dc = dc ? dcw.data() : nullptr; b.cap_dc = dcw.size();
+	if ((r = rtlfm_chansnap_read(path, &hd2, &b)) < 0) return r == -ENOBUFS ? -EILSEQ : r;
+	if (memcmp(&hd, &hd2, sizeof(hd)) != 0) return -EILSEQ;  // (the file changed between the two reads)
+	if (!same_carried(cfg, (int)hd.per_source, (hd.flags & RTLFM_CHANSNAP_FLAG_SOURCE_DC) != 0, (int)hd.fir_ntaps, (int)hd.fir_shift, ftaps.data(),
+	                  (int)hd.bank_K, (int)hd.bank_ntaps, (int)hd.bank_shift, btaps.data(), h))
+		return -EMEDIUMTYPE;
+	if (lifecycle_busy(h)) return -EBUSY;
+	if (hist && (!h->d_src_hist[0] || !h->d_src_hist[1] || (size_t)h->src_hist_srcs < nsrc)) return -EFAULT;
+	if (dc && (!h->d_sdc_hist[0] || !h->d_sdc_hist[1])) return -EFAULT;
+	// As rtlfm_gpu_channels_move: the handle idle behind sync_all, the records into the NEXT state copy and the history into the
+	// buffers that are not current, which nothing reads before the change-over; st_cur, src_hist_cur and pos change over
+	// together behind the last copy, so a copy that fails leaves the handle where it was.
+	HIP_TRY(hipSetDevice(h->device));
+	HIP_TRY(sync_all(h));
+	if (hist && (r = history_stage(h, bytes.data(), dc ? dcw.data() : nullptr, nsrc)) < 0) return r;
+	const int next = (h->st_cur + 1) % 3;
+	HIP_TRY(hipMemcpy(h->st[next], st.data(), n * sizeof(state_t), hipMemcpyHostToDevice));
+	h->st_cur = next;
+	if (hist) h->src_hist_cur ^= 1;
+	h->chan_pos = hd.pos;
 	return 0;
 }
 
@@ -4002,14 +4238,20 @@ extern "C" const char *rtlfm_gpu_strerror(int err)
 	case -EAGAIN: return "streams have unequal / zero queued blocks, or a producer still holds an acquired slot";
 	case -EBUSY: return "the stream's previous slot is still open (rtlfm_gpu_acquire without rtlfm_gpu_commit), or rtlfm_gpu_run_device while "
 	                    "a rtlfm_gpu_mute count is pending (it never writes its input), or rtlfm_gpu_state_move while a handle has a run "
-	                    "begun and not ended or a ring slot open, or the options source_ring / pack_results set in such a moment";
-	case -EXDEV: return "rtlfm_gpu_state_move: the handles are on different devices (use rtlfm_gpu_state_get_all / _set_all)";
-	case -ERANGE: return "the snapshot holds another number of streams than the handle";
-	case -EMEDIUMTYPE: return "the snapshot was saved under another configuration (a rtlfm_cfg field other than max_blocks / report_levels differs)";
-	case -EILSEQ: return "the snapshot file is damaged or no snapshot (magic, version, sizes, length or checksum)";
+	                    "begun and not ended or a ring slot open, or the options source_ring / pack_results set in such a moment; "
+	                    "rtlfm_gpu_channels_move / _channels_history_set / _channels_load in such a moment, or (option source_ring) with buffers queued";
+	case -EXDEV: return "rtlfm_gpu_state_move: the handles are on different devices (use rtlfm_gpu_state_get_all / _set_all); rtlfm_gpu_channels_move: "
+	                    "the same (with them rtlfm_gpu_channels_history_get / _set and rtlfm_gpu_channels_tell / _seek)";
+	case -ERANGE: return "the snapshot holds another number of streams than the handle";  // (rtlfm_gpu_load and rtlfm_gpu_channels_load)
+	case -EMEDIUMTYPE: return "the snapshot was saved under another configuration (a rtlfm_cfg field other than max_blocks / report_levels differs); "
+	                          "rtlfm_gpu_channels_load / _channels_move: the two sides do not carry the same things (that, or per_source, the option "
+	                          "source_dc, the channel filter or the channel bank differs)";
+	case -EILSEQ: return "the snapshot file is damaged or no snapshot (magic, version, sizes, length or checksum); a file of the other kind: "
+	                     "RTLFMSNP files belong to rtlfm_gpu_load, RTLFMCHN files to rtlfm_gpu_channels_load";
 	case -ENOTSUP: return "configuration not supported on this path; squelch_gate and pack_results 2: not behind a resampler "
 	                      "(rate_out2 > 0), post_downsample > 1 or a buffer the fifth_order passes do not divide; pack_results 2: "
-	                      "not on a run that holds a short buffer";
+	                      "not on a run that holds a short buffer; rtlfm_gpu_save / _load / _state_move with channels on (use rtlfm_gpu_channels_save / _load / "
+	                      "_move) and rtlfm_gpu_channels_* with channels off (use rtlfm_gpu_save / rtlfm_gpu_load / rtlfm_gpu_state_move)";
 	case -EDOM: return "outside the reference's own domain: a boxcar longer than the buffer (fm_demod reads lowpassed[-2]), low_pass_simple on a "
 	                   "count its step does not divide (src/rtl_fm.c:740), or rate_out2 > rate_out with low_pass_real (division by zero, :769)";
 	case -E2BIG: return "more blocks than cfg.max_blocks; a configuration whose max_blocks buffers exceed 2^31 - 1 complex samples per stream";
@@ -4017,7 +4259,8 @@ extern "C" const char *rtlfm_gpu_strerror(int err)
 	case -EIO: return "HIP runtime error";
 	case -ENODATA: return "no clock stamps recorded (rtlfm_gpu_clock_probe, fused fifth_order path only); no records of this kind "
 	                      "(the option was off); rtlfm_gpu_fetch_packed: that run was not packed (option pack_results was 0); "
-	                      "rtlfm_gpu_bank_survey: that run carried no survey (option bank_survey off, no bank, or no run yet)";
+	                      "rtlfm_gpu_bank_survey: that run carried no survey (option bank_survey off, no bank, or no run yet); "
+	                      "rtlfm_gpu_channels_history_get: neither a channel filter nor a bank is set, so no history is carried";
 	default: return strerror(-err);
 	}
 }

@@ -416,6 +416,50 @@ class GpuDemod:
         report_levels may differ); a file that does not fit or is damaged changes nothing (RtlfmError)."""
         check(self.lib.rtlfm_gpu_load(self._h, os.fsencode(path)), "rtlfm_gpu_load")
 
+    # -- the channel lifecycle: what a handle with channels on carries beyond the records -------------
+    def channels_history(self):
+        """rtlfm_gpu_channels_history_get: ``(bytes uint8 [sources, 8192], dc)`` - every source's last 4096 complex samples
+        as raw bytes, oldest first (bytes 127 where cleared), and with the option ``source_dc`` on the history's bias words,
+        uint32 [sources, 16] (else ``None``).  RtlfmError with -ENODATA when neither a filter nor a bank is set."""
+        nsrc = self.nstreams // self._per_source if self._per_source else 0
+        on = bool(self._per_source and self.get_option("source_dc"))
+        out = np.zeros((nsrc, 2 * capi.CHANSNAP_HIST), dtype=np.uint8)
+        dc = np.zeros((nsrc, capi.CHANSNAP_DC_PIECES), dtype=np.uint32)
+        n = C.c_int()
+        check(self.lib.rtlfm_gpu_channels_history_get(self._h, out.ctypes.data, out.size, dc.ctypes.data, dc.size, C.byref(n)),
+              "rtlfm_gpu_channels_history_get")
+        return out, (dc if on else None)
+
+    def set_channels_history(self, bytes, dc=None):
+        """rtlfm_gpu_channels_history_set: the inverse (``dc = None`` with ``source_dc`` on: none subtracted).  Behind
+        ``channels_seek``, which clears the history - seek first."""
+        b = np.ascontiguousarray(bytes, dtype=np.uint8)
+        if b.ndim != 2 or b.shape[1] != 2 * capi.CHANSNAP_HIST:
+            raise ValueError(f"history: [sources, {2 * capi.CHANSNAP_HIST}] bytes, not {b.shape}")
+        d = None
+        if dc is not None:
+            d = np.ascontiguousarray(dc, dtype=np.uint32)
+            if d.shape != (b.shape[0], capi.CHANSNAP_DC_PIECES):
+                raise ValueError(f"dc: [sources, {capi.CHANSNAP_DC_PIECES}] words, not {d.shape}")
+        check(self.lib.rtlfm_gpu_channels_history_set(self._h, b.ctypes.data, None if d is None else d.ctypes.data, b.shape[0]),
+              "rtlfm_gpu_channels_history_set")
+
+    def channels_move_from(self, src: "GpuDemod", source_map):
+        """rtlfm_gpu_channels_move: source a of this handle takes the records, the history and the biases of source
+        ``source_map[a]`` of ``src`` (-1: a source that joins from silence), and the handle takes ``src``'s pos; ``src`` may
+        be this handle itself.  One kernel launch."""
+        m = np.ascontiguousarray(source_map, dtype=np.int32)
+        check(self.lib.rtlfm_gpu_channels_move(self._h, src._h, m.ctypes.data, m.size), "rtlfm_gpu_channels_move")
+
+    def channels_save(self, path):
+        """rtlfm_gpu_channels_save: records, pos, history and biases into a channel snapshot (include/rtlfm_chansnap.h)."""
+        check(self.lib.rtlfm_gpu_channels_save(self._h, os.fsencode(path)), "rtlfm_gpu_channels_save")
+
+    def channels_load(self, path):
+        """rtlfm_gpu_channels_load: the reverse, into a handle set up alike (stream count, per_source, filter, bank,
+        ``source_dc``, configuration); a file that does not fit or is damaged changes nothing (RtlfmError)."""
+        check(self.lib.rtlfm_gpu_channels_load(self._h, os.fsencode(path)), "rtlfm_gpu_channels_load")
+
     def reset(self):
         check(self.lib.rtlfm_gpu_reset(self._h), "rtlfm_gpu_reset")
 
