@@ -727,6 +727,55 @@ int rtlfm_gpu_source_health(rtlfm_gpu *h, int source, rtlfm_input_health *out, i
 int rtlfm_gpu_source_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n);
 
 /*
+ * Option "source_iq": IQ balance per SOURCE, measured and applied on the device ("Source IQ").
+ *
+ * A wideband source whose I and Q differ in gain or are not in quadrature folds the channel at +f onto the channel at -f:
+ * every one of its K demodulators hears its mirror channel.  rtl_tcp -c (iqBalance, src/rtl_tcp.c:211-233) rewrites its
+ * uint8 buffer; so does this option (0 default / 1), for runs that channels take.  It may be set with channels off.
+ *
+ * records      one rtlfm_iq_sums per (source, buffer) of the run over the RAW bytes I, Q in [0, 255]: n = len / 2, si = sum I,
+ *              sq = sum Q, sii = sum I^2, sqq = sum Q^2, siq = sum I Q; clipped = output BYTES the clamp below changed.
+ *              Integers: any order of summation gives the same bits.
+ * rows         with x = I - 127, y = Q - 127 and the source's four int16 Q14 coefficients (a, b, p, q):
+ *                I' = (a x + b y + 8192) >> 14,  Q' = (p x + q y + 8192) >> 14    (arithmetic shift, int32)
+ *              and each output byte is clamp(v + 127, 0, 255).  The identity (16384, 0, 0, 16384) reproduces every byte.
+ *              The rows go into a buffer of the handle's, [sources][max_blocks * block_len], allocated by the first run that
+ *              needs it, regrown when rtlfm_gpu_set_channels makes the sources more, freed when the option returns to 0.
+ * who reads    everything behind it reads the corrected rows in the caller's place: source_dc's sums, every channel front
+ *              end and cross-check, k_channel_mix, and k_source_history - the history keeps the bytes as they were
+ *              consumed, so a change of coefficients between runs needs no list per piece.  "source_stats" / "source_health"
+ *              describe the ADC and keep reading the RAW rows (k_input_health / k_input_stats as with source_dc off; with
+ *              source_dc on its sums come from k_rdc_sums_* on the corrected rows, and k_source_prepass is not used: one
+ *              more read).  verify_twice: both executions read the same coefficients and leave the same rows and records.
+ * setting      -EINVAL for any value but 0 / 1; -EBUSY while a run is begun, a ring slot is open or, with source_ring,
+ *              buffers are queued; a refused call changes nothing.  Either direction waits for the handle and does NOT
+ *              clear the history.  With the option at 0 no kernel, launch count, allocation or result differs.
+ *
+ * rtlfm_gpu_set_source_iq: coef [sources][4] = (a, b, p, q) per source.  No wait: the copy goes through a rotation of pinned
+ * buffers on the handle's stream (as rtlfm_gpu_set_channel_bins) - runs already queued use the old coefficients, later
+ * runs the new.  -ENOTSUP with channels off, -EINVAL for NULL, -EBUSY in a begun run.  A fresh handle has the identity and
+ * rtlfm_gpu_set_channels resets every source to it.  May be called with the option off; the values rule once it is on.
+ * rtlfm_gpu_get_source_iq: the coefficients as they rule now, [sources][4]; -ENOBUFS when cap (in int16) is too small,
+ * -ENOTSUP with channels off.
+ * rtlfm_gpu_source_iq_sums / _all: the contract of rtlfm_gpu_source_stats / _all: -EINVAL for bad arguments or a source
+ * outside [0, sources); -ENODATA while the option is off, before the first run, after rtlfm_gpu_set_channels and while the
+ * last run was not one that channels took; -ENOBUFS, with *n written, when cap is too small; a ring run that holds short
+ * buffers files each buffer's record over its own length, [source][nb].
+ *
+ * The coefficients belong to the caller: rtlfm_gpu_channels_save / _load / _move and the RTLFMCHN file do not carry them.
+ * Whoever resumes or regroups reads them with rtlfm_gpu_get_source_iq and sets them again, as with the soft AGC's indices.
+ * The policy that turns records into coefficients is host code: include/rtlfm_iq.h.
+ */
+typedef struct rtlfm_iq_sums {
+	uint32_t n, clipped;
+	uint64_t si, sq, sii, sqq, siq;
+} rtlfm_iq_sums;  /* 48 bytes */
+int rtlfm_gpu_set_source_iq(rtlfm_gpu *h, const int16_t *coef /* [sources][4] */);
+int rtlfm_gpu_get_source_iq(rtlfm_gpu *h, int16_t *coef, int cap);
+int rtlfm_gpu_source_iq_sums(rtlfm_gpu *h, int source, rtlfm_iq_sums *out, int cap, int *n);
+int rtlfm_gpu_source_iq_sums_all(rtlfm_gpu *h, rtlfm_iq_sums *out, int cap, int *n);
+
+/*
  * The channel lifecycle: snapshot, resume and regroup by SOURCE ("Lifecycle").
  *
  * rtlfm_gpu_save / _load / _state_move stay refused while channels are on (-ENOTSUP): a handle with channels on carries
@@ -874,6 +923,8 @@ int rtlfm_gpu_release_to(rtlfm_gpu *h, void *consumer_stream);
  *                        of the mixers and the bank (see "source_dc" above)
  *   source_stats         0 (default) / 1: runs that channels take leave the ADC statistics of every source's raw bytes, and
  *   source_health        ... the overload / high-level / continuity records (see "source_stats" above)
+ *   source_iq            0 (default) / 1: runs that channels take measure every source's second moments and rewrite its bytes
+ *                        with the source's IQ-balance coefficients in front of everything else (see "source_iq" above)
  * Read-only (rtlfm_gpu_get_option):
  *   pack_us              device time of the last run's two pack launches in microseconds (waits for them); -1 when that
  *                        run was not packed or rtlfm_gpu_timing_enable was off

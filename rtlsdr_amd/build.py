@@ -14,7 +14,7 @@ OUT = os.path.join(CSRC, "librtlfm_hip.so")
 # entries hold device code; FUSED_UNIT names the one that holds the k_fused instances - today the whole rtl_fm library -
 # for the prefetch lint, which reads that unit's assembly (first: it compiles longest).
 FUSED_UNIT = "rtlfm_hip.hip"
-SOURCES = [FUSED_UNIT, "rtlpower_hip.hip", "rtlfm_place.hip", "monitor.cpp", "agc.cpp", "scan.cpp", "snapshot.cpp", "chansnap.cpp", "slots.cpp"]
+SOURCES = [FUSED_UNIT, "rtlpower_hip.hip", "rtlfm_place.hip", "monitor.cpp", "agc.cpp", "scan.cpp", "snapshot.cpp", "chansnap.cpp", "slots.cpp", "iq.cpp"]
 DEVICE_UNITS = [s for s in SOURCES if s.endswith(".hip")]
 ARCH = "gfx950"
 
@@ -167,7 +167,7 @@ def build_host(force: bool = False, verbose: bool = False) -> tuple[str, str]:
     build_shim(force, verbose)
     cli_src = os.path.join(HOST, "rtl_fm_hip.cpp")
     if stale(CLI_OUT, [cli_src, SHIM_OUT, OUT, os.path.join(inc, "rtlfm_hip.h"), os.path.join(inc, "rtlfm_monitor.h"),
-                       os.path.join(inc, "rtlfm_agc.h"), os.path.join(inc, "rtlfm_scan.h"), os.path.join(inc, "rtlfm_snapshot.h"),
+                       os.path.join(inc, "rtlfm_agc.h"), os.path.join(inc, "rtlfm_iq.h"), os.path.join(inc, "rtlfm_scan.h"), os.path.join(inc, "rtlfm_snapshot.h"),
                        os.path.join(inc, "rtlfm_chansnap.h"),
                        os.path.join(inc, "rtlsdr_file.h")]):
         cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-o", CLI_OUT, cli_src,

@@ -204,6 +204,21 @@ class RtlfmAgcEvent(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RtlfmIqEvent(C.Structure):
+    """``rtlfm_iq_event`` — one decision of the IQ-balance engine (include/rtlfm_iq.h)."""
+
+    _fields_ = [("source", C.c_int32), ("kind", C.c_int32), ("coef", C.c_int16 * 4), ("g_q14", C.c_int32), ("s_q14", C.c_int32),
+                ("window_serial", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {n: (tuple(getattr(self, n)) if n == "coef" else getattr(self, n)) for n, _ in self._fields_}
+
+
+IQ_OK, IQ_WEAK, IQ_REJECTED = range(3)           # rtlfm_iq_compute's verdicts
+IQ_EVENT_CHANGED, IQ_EVENT_REJECTED = range(2)   # rtlfm_iq_event.kind
+# ``rtlfm_iq_sums`` as a numpy dtype (GpuDemod.source_iq_sums / _all return arrays of it)
+IQ_SUMS_DTYPE = [("n", "<u4"), ("clipped", "<u4"), ("si", "<u8"), ("sq", "<u8"), ("sii", "<u8"), ("sqq", "<u8"), ("siq", "<u8")]
+
 MONITOR_AUTO_GAIN = -100
 CRIT_IN, CRIT_OUT, CRIT_LT, CRIT_GT = range(4)
 CRIT_NAMES = ("in", "out", "<", ">")  # aCritStr, src/rtl_fm.c:116
@@ -365,6 +380,10 @@ _SIGNATURES = [
     ("rtlfm_gpu_source_stats_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_source_health", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_source_health_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_set_source_iq", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_gpu_get_source_iq", C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    ("rtlfm_gpu_source_iq_sums", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
+    ("rtlfm_gpu_source_iq_sums_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_gate", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_gate_all", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _P(C.c_int)]),
     ("rtlfm_gpu_mute", C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
@@ -534,6 +553,19 @@ _AGC_SIGNATURES = [
 ]
 DECLARED_AGC_SYMBOLS = [s[0] for s in _AGC_SIGNATURES]
 
+# ... and include/rtlfm_iq.h (IQ balance per source: the policy between k_source_iq's records and its coefficients)
+_IQ_SIGNATURES = [
+    ("rtlfm_iq_compute", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, _P(C.c_int32), _P(C.c_int32)]),
+    ("rtlfm_iq_create", C.c_int, [C.c_int, _P(C.c_void_p)]),
+    ("rtlfm_iq_destroy", C.c_int, [C.c_void_p]),
+    ("rtlfm_iq_feed", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    ("rtlfm_iq_update", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_iq_poll", C.c_int, [C.c_void_p, _P(RtlfmIqEvent), C.c_int, _P(C.c_int)]),
+    ("rtlfm_iq_coeffs", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("rtlfm_iq_set_params", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+]
+DECLARED_IQ_SYMBOLS = [s[0] for s in _IQ_SIGNATURES]
+
 # ... and include/rtlfm_scan.h (the scanner's hop engine; host code inside the same library)
 _SCAN_SIGNATURES = [
     ("rtlfm_scan_create", C.c_int, [C.c_int, C.c_uint32, C.c_int32, _P(C.c_void_p)]),
@@ -636,7 +668,7 @@ def load(path: str | None = None) -> C.CDLL:
     except ImportError:
         pass
     lib = C.CDLL(p)
-    for name, res, args in (_SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _SCAN_SIGNATURES + _SNAPSHOT_SIGNATURES
+    for name, res, args in (_SIGNATURES + _MONITOR_SIGNATURES + _AGC_SIGNATURES + _IQ_SIGNATURES + _SCAN_SIGNATURES + _SNAPSHOT_SIGNATURES
                             + _SLOTS_SIGNATURES + _CHANSNAP_SIGNATURES):
         if p != LIB_PATH and not hasattr(lib, name):
             continue  # an explicitly named other build (`path` or RTLFM_HIP_LIB: A/B against an earlier revision) may predate a symbol

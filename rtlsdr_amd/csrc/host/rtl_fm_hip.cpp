@@ -88,6 +88,11 @@
 // lines of -N -O agc=2 -v with "source %d:" where those say "stream %d:" (under -X a stream is a channel).  The engine is
 // fed the full length for a completed short last buffer - the record is over the completed buffer - and nothing for a
 // source that has ended: the bytes 127 it is fed must not ramp its gain.  The PCM files are those of the run without it.
+// -E srciq (with -X only) is rtl_tcp -c for the SOURCES of -X: the library's option source_iq (every source's second
+// moments measured and its bytes rewritten on the device, in front of everything else), the engine of include/rtlfm_iq.h
+// fed after every run, and its coefficients handed to the handle for the next run (rtlfm_gpu_set_source_iq).  -v prints
+// "source %d: iq a b p q" for every change, "source %d: iq rejected g s" for a window the engine refuses, and every
+// source's coefficients at exit.  A source that has ended is fed bytes 127: weak windows, which change nothing.
 //
 // -k file / -u file (not reference letters; with -X only): keep / take up, -K / -R for channels.  -k writes, behind the last
 // run, everything the handle carries - every stream's record, the handle's sample counter, every source's history and its
@@ -131,6 +136,7 @@
 
 #include "../../../include/rtlfm_hip.h"
 #include "../../../include/rtlfm_agc.h"
+#include "../../../include/rtlfm_iq.h"
 #include "../../../include/rtlfm_monitor.h"
 #include "../../../include/rtlfm_scan.h"
 #include "../../../include/rtlfm_snapshot.h"
@@ -171,6 +177,7 @@ struct Settings {
 	const char *chan_keep_file = nullptr, *chan_resume_file = nullptr;  // -k / -u: -K / -R for -X (a channel snapshot)
 	bool source_dc = false;  // -E srcdc: the library's option source_dc (with -X only)
 	bool source_agc = false; // -E srcagc: the software AGC per source (with -X only; not with agc= in -O)
+	bool source_iq = false;  // -E srciq: IQ balance per source (with -X only)
 	int agc = -1;        // -O agc=<n>; -1: not given
 	int chan_taps = -1;  // -x; -1: not given
 };
@@ -782,6 +789,7 @@ struct Multi {
 	std::vector<pid_t> children;
 	uint64_t events = 0, fired = 0;
 	Health hl;  // -O agc=2
+	rtlfm_iq *iq = nullptr;  // -E srciq: the IQ-balance engine, input i = source i
 	bool use_gate = false;  // -l through the device's squelch gate
 	// -S: the hop engine, list i = source i
 	rtlfm_scan *scan = nullptr;
@@ -1332,6 +1340,32 @@ int run_multi(const Settings &st, const std::vector<uint32_t> &freqs, const std:
 // a source that has ended is fed b buffers of bytes 127, so that every source has one length per buffer index and the
 // handle's one sample counter holds for all.  The streams of an ended source write nothing more and count nothing more.
 // The run ends with the last source.
+// -E srciq after a run: the engine takes every source's records of the run (include/rtlfm_iq.h), says what it decided
+// (-v), and its coefficients go to the handle - no wait: they rule from the next run on.
+int iq_step(Multi *m)
+{
+	int r = rtlfm_iq_update(m->iq, m->gpu);
+	if (r < 0) return r;
+	rtlfm_iq_event ev[16];
+	int n = 0;
+	bool changed = false;
+	do {
+		if ((r = rtlfm_iq_poll(m->iq, ev, 16, &n)) < 0) return r;
+		for (int k = 0; k < n; k++) {
+			if (ev[k].kind == RTLFM_IQ_EVENT_CHANGED) changed = true;
+			if (!m->st.verbosity) continue;
+			if (ev[k].kind == RTLFM_IQ_EVENT_CHANGED)
+				fprintf(stderr, "source %d: iq %d %d %d %d\n", ev[k].source, ev[k].coef[0], ev[k].coef[1], ev[k].coef[2], ev[k].coef[3]);
+			else
+				fprintf(stderr, "source %d: iq rejected %d %d\n", ev[k].source, ev[k].g_q14, ev[k].s_q14);
+		}
+	} while (n == 16);
+	if (!changed) return 0;
+	std::vector<int16_t> coef(m->src.size() * 4);
+	if ((r = rtlfm_iq_coeffs(m->iq, coef.data())) < 0) return r;
+	return rtlfm_gpu_set_source_iq(m->gpu, coef.data());
+}
+
 void demod_thread_channels(Multi *m)
 {
 	const int n = (int)m->src.size(), K = m->chan_per, S = n * K;
@@ -1365,6 +1399,10 @@ void demod_thread_channels(Multi *m)
 				fail(m, "rtlfm_gpu_source_health_all / rtlfm_agc_feed", r);
 				break;
 			}
+		}
+		if (m->iq && (r = iq_step(m)) < 0) {  // -E srciq: this run's records decide the next run's coefficients
+			fail(m, "rtlfm_iq_update / rtlfm_gpu_set_source_iq", r);
+			break;
 		}
 		for (int s = 0; s < S; s++)
 			if (ended[(size_t)(s / K)]) o.lens[(size_t)s] = 0;
@@ -1442,6 +1480,11 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 			m.hl.by_source = true;
 			if (r == 0) { what = "rtlfm_agc_create"; r = health_create(&m.hl, devs, c.max_blocks, st.verbosity); }
 		}
+		if (r == 0 && st.source_iq) {
+			what = "option source_iq";
+			r = rtlfm_gpu_set_option(m.gpu, "source_iq", 1);
+			if (r == 0) { what = "rtlfm_iq_create"; r = rtlfm_iq_create(n, &m.iq); }
+		}
 		if (r == 0 && c.squelch_level) {
 			// -l: demod_thread_fn's rule on the device, and only what it let through comes back.  (-ENOTSUP, behind a
 			// resampler: the rule from the carried state after every run, hold_back.)
@@ -1477,6 +1520,13 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 		for (Source &s : m.src) in += s.blocks_in;
 		summary(m.out.data(), m.out.size(), in, nullptr, m.failed, st.verbosity > 0);
 		if (m.hl.agc) health_report(&m.hl);
+		if (m.iq && st.verbosity) {  // -E srciq: where every source ended up
+			std::vector<int16_t> coef((size_t)n * 4);
+			if (rtlfm_iq_coeffs(m.iq, coef.data()) == 0)
+				for (int i = 0; i < n; i++)
+					fprintf(stderr, "source %d: iq %d %d %d %d at exit\n", i, coef[(size_t)i * 4], coef[(size_t)i * 4 + 1], coef[(size_t)i * 4 + 2],
+					        coef[(size_t)i * 4 + 3]);
+		}
 		if (m.failed) ret = 3;
 		if (!ret && st.chan_keep_file) {  // -k: behind the last run
 			const int r = rtlfm_gpu_channels_save(m.gpu, st.chan_keep_file);
@@ -1487,6 +1537,7 @@ int run_channels(const Settings &st, const std::vector<uint32_t> &freqs, const s
 		}
 	}
 	if (m.hl.agc) rtlfm_agc_destroy(m.hl.agc);
+	if (m.iq) rtlfm_iq_destroy(m.iq);
 	close_all(&m);
 	return ret;
 }
@@ -1560,7 +1611,9 @@ void usage()
 	        "\t       -S's grammar, the same number K on every line; source i's centre frequency is its -f as given and its K channels are mixed\n"
 	        "\t       down on the GPU; stream s = channel s %% K of source s / K writes the file with %%d = s; not with -S -C -K -R -Z (-k / -u keep and take up),\n"
 	        "\t       -O agc=2 or -E rdc; -E srcdc takes every source's DC spike off in front of the mixers (-q sets its constant);\n"
-	        "\t       -E srcagc is the software AGC for every SOURCE from the GPU's records of its raw bytes (-v prints every change; not with agc= in -O)]\n"
+	        "\t       -E srcagc is the software AGC for every SOURCE from the GPU's records of its raw bytes (-v prints every change; not with agc= in -O);\n"
+	        "\t       -E srciq is rtl_tcp -c for every SOURCE: its I/Q gain and phase mismatch measured and corrected on the GPU, so that no channel\n"
+	        "\t       hears its mirror channel (-v prints every change of the four Q14 coefficients)]\n"
 	        "\t[-x ntaps  with -X: a windowed-sinc channel filter of ntaps taps (cutoff 0.4 of the output rate) in the boxcar's place; not with -F]\n"
 	        "\t[-k file  with -X: keep - write everything the handle carries (every stream's state, the sample counter, every source's\n"
 	        "\t       history) to a channel snapshot at exit;  -u file  with -X: take up - load such a file before the first buffer; it must come\n"
@@ -1575,7 +1628,8 @@ void usage()
 	        "\t[-m minimum_capture_rate Hz (default: 1m)]\n"
 	        "\t[-F fir_size (default: off)]  enables the fifth-order low pass; 0 or 9 (9 = droop compensation)\n"
 	        "\t[-A std/fast/lut choose atan math (default: std)]\n"
-	        "\t[-E enable_option]  edge, dc, rdc, deemp, offset, srcdc (with -X only; not with rdc), srcagc (with -X only; not with agc= in -O)\n"
+	        "\t[-E enable_option]  edge, dc, rdc, deemp, offset, srcdc (with -X only; not with rdc), srcagc (with -X only; not with agc= in -O),\n"
+	        "\t                    srciq (with -X only)\n"
 	        "\t[-c de-emphasis_time_constant in us: us (75), eu (50) or a number]\n"
 	        "\t[-o oversampling (default: 1)]  [-l squelch_level]  [-t squelch_delay (default: 10)]  [-q rdc_block_const]\n"
 	        "\t[-L N  prints levels every N calculations (with -N: per stream, as 'stream i: ...')]\n"
@@ -1643,6 +1697,7 @@ int main(int argc, char **argv)
 			if (!strcmp(optarg, "rdc")) c.dc_block_raw = 1;
 			if (!strcmp(optarg, "srcdc")) st.source_dc = true;
 			if (!strcmp(optarg, "srcagc")) st.source_agc = true;
+			if (!strcmp(optarg, "srciq")) st.source_iq = true;
 			if (!strcmp(optarg, "deemp")) c.deemph = 1;
 			if (!strcmp(optarg, "offset")) c.offset_tuning = 1;
 			break;
@@ -1699,6 +1754,11 @@ int main(int argc, char **argv)
 		                "that only a handle with channels takes; without channels -O agc=2 is the software AGC.\n");
 		return 1;
 	}
+	if (st.source_iq && !st.chan_file) {
+		fprintf(stderr, "-E srciq (IQ balance per source) needs -X (the channel file): it measures and rewrites the sources' raw bytes "
+		                "in front of the channels' mixers, which only a handle with channels does.\n");
+		return 1;
+	}
 	if (st.source_agc && st.agc != -1) {
 		fprintf(stderr, "-E srcagc (software AGC per source, gain mode 2 on every device) does not go with agc=%d in -O: one of them "
 		                "sets the devices' gain mode.\n", st.agc);
@@ -1716,9 +1776,10 @@ int main(int argc, char **argv)
 			                "for independent streams the letters are -K / -R.\n", me);
 			return 1;
 		}
-		const char *with = st.scan_file ? "-S (scan lists)" : st.cmd_file ? "-C (command file)" : st.source_agc ? "-E srcagc (software AGC per source)" : nullptr;
+		const char *with = st.scan_file ? "-S (scan lists)" : st.cmd_file ? "-C (command file)" : st.source_agc ? "-E srcagc (software AGC per source)"
+		                   : st.source_iq ? "-E srciq (IQ balance per source)" : nullptr;
 		if (with) {
-			fprintf(stderr, "%s does not go with %s: -k / -u do not go with -S, -C or -E srcagc, those engines carry state of their own "
+			fprintf(stderr, "%s does not go with %s: -k / -u do not go with -S, -C, -E srcagc or -E srciq, those engines carry state of their own "
 			                "that the file does not hold.\n", me, with);
 			return 1;
 		}

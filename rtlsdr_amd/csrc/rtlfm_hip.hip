@@ -32,6 +32,7 @@
 #include "input_stats_kernel.h"
 #include "input_health_kernel.h"
 #include "source_prepass_kernel.h"
+#include "source_iq_kernel.h"
 #include "scan_kernel.h"
 #include "pack_kernel.h"
 #include "state_kernel.h"
@@ -139,6 +140,19 @@ struct rtlfm_gpu {
 	int src_stats_nblocks = 0, src_health_nblocks = 0;  // buffers of the last run that have records; 0: that run left none
 	size_t src_rec_off = 0;                    // a view (run_ragged) files buffer j of the run: [source][src_rec_stride] + j
 	int src_rec_stride = 0;                    // 0: the run's own buffer count
+	// option source_iq (source_iq_kernel.h): the corrected source rows every front end reads in the caller's place and the
+	// records of the raw bytes, allocated by the first run that needs them, regrown with the sources, freed with the option;
+	// the coefficients, identity on a fresh handle and after rtlfm_gpu_set_channels, for as many sources as there are streams
+	DevBuf<uint8_t> d_siq_rows;                // [sources][siq_stride]
+	size_t siq_stride = 0;                     // cap_blocks * cfg.block_len of the HANDLE (a view keeps it)
+	DevBuf<rtlfm_iq_sums> d_siq_sums;          // [sources][cap_blocks], filed as the records above
+	int siq_nblocks = 0;                       // buffers of the last run that have records; 0: that run left none
+	std::vector<int16_t> siq_coef;             // [nstreams][4], what the getter hands back
+	DevBuf<int16_t> d_siq_coef;
+	static constexpr int kIqStages = 4;        // rtlfm_gpu_set_source_iq's rotation, as the bins'
+	PinnedBuf<int16_t> h_siq_stage[kIqStages];
+	Event ev_siq_stage[kIqStages];
+	int siq_stage_next = 0;
 	// the channel filter (channel_fir_kernel.h; rtlfm_gpu_set_channel_filter): acts while channels are on
 	int fir_ntaps = 0, fir_shift = 0;      // 0 taps: none, the boxcar
 	std::vector<int16_t> fir_taps;         // what the getter hands back
@@ -220,6 +234,7 @@ struct rtlfm_gpu {
 		int source_dc = 0;     // 1: runs that channels take subtract every source's smoothed buffer averages in front of the front end (k_source_dc_smooth)
 		int source_stats = 0;  // 1: runs that channels take leave the ADC statistics of every source's raw bytes (rtlfm_gpu_source_stats)
 		int source_health = 0; // 1: ... and the health records (rtlfm_gpu_source_health)
+		int source_iq = 0;     // 1: runs that channels take rewrite every source's bytes with its IQ-balance coefficients first (k_source_iq)
 	} opt;
 	// verify_twice (round 6): shadow rows / lengths / state, and what the comparisons found so far
 	DevBuf<int16_t> vt_out;
@@ -573,6 +588,34 @@ static int ensure_source_records(rtlfm_gpu *h)
 	return 0;
 }
 
+// Option source_iq.  The coefficients on the host, [nstreams][4]: the identity until somebody sets them.
+static void siq_identity(rtlfm_gpu *h)
+{
+	h->siq_coef.assign((size_t)h->nstreams * 4, 0);
+	for (int s = 0; s < h->nstreams; s++) h->siq_coef[(size_t)s * 4] = h->siq_coef[(size_t)s * 4 + 3] = 16384;
+}
+// ... and on the device: allocated by whoever needs them first, with what rules now (a blocking copy: nothing reads them yet)
+static int ensure_source_iq_coef(rtlfm_gpu *h)
+{
+	if (h->d_siq_coef) return 0;
+	if (h->siq_coef.empty()) siq_identity(h);
+	OWN_TRY(h->d_siq_coef.alloc((size_t)h->nstreams * 4));
+	HIP_TRY(hipMemcpy(h->d_siq_coef, h->siq_coef.data(), h->siq_coef.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+	return 0;
+}
+// The corrected rows, [sources][cap_blocks * block_len], and the records, [sources][cap_blocks], for the sources there are now
+// (a view cannot allocate: the handle's run does, before the first view).  Grown - never shrunk - behind the handle's stream;
+// the rows hold nothing a later run needs, and the callers have said what became of the records (siq_nblocks = 0).
+static int ensure_source_iq(rtlfm_gpu *h)
+{
+	if (h->chan_per <= 0 || !h->opt.source_iq) return 0;
+	const size_t nsrc = (size_t)(h->nstreams / h->chan_per);
+	h->siq_stride = (size_t)h->cap_blocks * h->cfg.block_len;  // (a multiple of 512: rows start on 16-byte lines)
+	OWN_TRY(h->d_siq_rows.grow(nsrc * h->siq_stride, h->stream));
+	OWN_TRY(h->d_siq_sums.grow(nsrc * h->cap_blocks, h->stream));
+	return ensure_source_iq_coef(h);
+}
+
 // The source history - every source's carried bytes - back to 127: mixed zeros, m[n < 0] = 0 and x[n < 0] = 0.  On the
 // handle's stream: behind the runs already queued, in front of the next.
 static int history_clear(rtlfm_gpu *h)
@@ -808,9 +851,14 @@ extern "C" int rtlfm_gpu_set_channels(rtlfm_gpu *h, int per_source, const uint32
 	h->bank_K = 0;  // (the bank's bins belong to the old per_source)
 	h->bank_bins_ps.clear();
 	h->src_stats_nblocks = h->src_health_nblocks = 0;  // (options source_stats / source_health: records of the old rows)
+	h->siq_nblocks = 0;                                // (option source_iq: the same, and every source back to the identity)
+	siq_identity(h);
+	if (h->d_siq_coef)
+		HIP_TRY(hipMemcpy(h->d_siq_coef, h->siq_coef.data(), h->siq_coef.size() * sizeof(int16_t), hipMemcpyHostToDevice));
 	int r = ensure_history(h);
 	if (r < 0) return r;
 	if ((r = ensure_source_records(h)) < 0) return r;
+	if ((r = ensure_source_iq(h)) < 0) return r;
 	return ingest_resize(h);  // (option source_ring: the ring's input side for the new number of sources)
 }
 
@@ -1041,6 +1089,43 @@ extern "C" int rtlfm_gpu_get_channel_bins(rtlfm_gpu *h, int32_t *bins, int cap)
 	if (cap < h->nstreams) return -ENOBUFS;
 	for (int s = 0; s < h->nstreams; s++)
 		bins[s] = h->bank_bins_ps.empty() ? h->bank_bins[(size_t)(s % h->chan_per)] : h->bank_bins_ps[(size_t)s];
+	return 0;
+}
+
+// Option source_iq's coefficients, (a, b, p, q) per source: the bins' pattern - nothing is waited for but a staging buffer
+// whose own copy has not left yet, and the copy is ordered on the handle's stream: runs queued before the call read the old
+// coefficients, runs after it the new.
+extern "C" int rtlfm_gpu_set_source_iq(rtlfm_gpu *h, const int16_t *coef)
+{
+	if (!h || !coef) return -EINVAL;
+	if (h->chan_per <= 0) return -ENOTSUP;
+	if (ingest_busy(h)) return -EBUSY;
+	HIP_TRY(hipSetDevice(h->device));
+	const size_t n = (size_t)(h->nstreams / h->chan_per) * 4, cap = (size_t)h->nstreams * 4;
+	int r = ensure_source_iq_coef(h);
+	if (r < 0) return r;
+	for (int k = 0; k < rtlfm_gpu::kIqStages; k++) {
+		OWN_TRY(h->h_siq_stage[k].alloc(cap));  // (the first call: a handle's stream count never changes)
+		OWN_TRY(h->ev_siq_stage[k].create(hipEventDisableTiming));
+	}
+	const int k = h->siq_stage_next;
+	HIP_TRY(hipEventSynchronize(h->ev_siq_stage[k]));  // (an event never recorded is complete)
+	memcpy(h->h_siq_stage[k], coef, n * sizeof(int16_t));
+	HIP_TRY(hipMemcpyAsync(h->d_siq_coef, h->h_siq_stage[k], n * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(hipEventRecord(h->ev_siq_stage[k], h->stream));
+	h->siq_stage_next = (k + 1) % rtlfm_gpu::kIqStages;
+	std::copy(coef, coef + n, h->siq_coef.begin());
+	return 0;
+}
+
+extern "C" int rtlfm_gpu_get_source_iq(rtlfm_gpu *h, int16_t *coef, int cap)
+{
+	if (!h || !coef || cap < 0) return -EINVAL;
+	if (h->chan_per <= 0) return -ENOTSUP;
+	const size_t n = (size_t)(h->nstreams / h->chan_per) * 4;
+	if ((size_t)cap < n) return -ENOBUFS;
+	if (h->siq_coef.empty()) siq_identity(h);
+	memcpy(coef, h->siq_coef.data(), n * sizeof(int16_t));
 	return 0;
 }
 
@@ -1382,6 +1467,7 @@ static int *option_slot(rtlfm_gpu *h, const char *name)
 		{"source_ring", &h->opt.source_ring}, {"pack_results", &h->opt.pack_results}, {"bank_survey", &h->opt.bank_survey},
 		{"source_dc", &h->opt.source_dc},
 		{"source_stats", &h->opt.source_stats}, {"source_health", &h->opt.source_health},
+		{"source_iq", &h->opt.source_iq},
 	};
 	for (auto &t : tab)
 		if (!strcmp(t.n, name)) return t.p;
@@ -1479,6 +1565,21 @@ extern "C" int rtlfm_gpu_set_option(rtlfm_gpu *h, const char *name, long value)
 		if (value != 0 && value != 1) return -EINVAL;
 		if (ingest_busy(h)) return -EBUSY;
 		*slot = (int)value;
+		return 0;
+	}
+	if (!strcmp(name, "source_iq")) {
+		// (include/rtlfm_hip.h: acts only on runs that channels take, free to set with channels off; the history stays)
+		if (value != 0 && value != 1) return -EINVAL;
+		if (ingest_busy(h) || (h->opt.source_ring && ingest_queued(h))) return -EBUSY;
+		HIP_TRY(hipSetDevice(h->device));
+		HIP_TRY(sync_all(h));
+		h->opt.source_iq = (int)value;
+		h->siq_nblocks = 0;
+		if (value == 0) {  // the rows and the records go; the coefficients stay as they rule
+			h->d_siq_rows.reset();
+			h->d_siq_sums.reset();
+			h->siq_stride = 0;
+		}
 		return 0;
 	}
 	if (!strcmp(name, "conseq_squelch") && (value < 0 || value > INT32_MAX - 1)) return -EINVAL;
@@ -2178,14 +2279,41 @@ static int launch_source_readers(rtlfm_gpu *h, const uint8_t *d_iq, size_t strea
 // pre-pass and the records of options source_stats / source_health, both over the raw bytes (the records are in front of
 // source_dc's subtraction: nothing here changes a byte).  With source_dc and a record option on, ONE read: k_source_prepass
 // (k_rdc_sums_* and the readers behind them, the same results from two reads, lost the A/B of LAB.md at 1024 sources x 4).
-static int launch_source_side(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stride, int nblocks, const state_t *sin, state_t *sout, bool hist)
+//
+// Option source_iq comes first: k_source_iq reads the caller's rows (raw) and leaves the corrected rows in the handle's
+// buffer, where source_iq_redirect has pointed the run (d_iq).  The records describe the ADC and stay on the raw rows - the
+// readers' own launches, as with source_dc off -, source_dc's sums come from k_rdc_sums_* on the corrected rows, and
+// k_source_prepass is not used: one more read.
+static int launch_source_side(rtlfm_gpu *h, const uint8_t *raw, size_t raw_stride, const uint8_t *d_iq, size_t stream_stride, int nblocks,
+                              const state_t *sin, state_t *sout, bool hist)
 {
 	const bool records = h->opt.source_stats || h->opt.source_health;
 	if (records && ((h->opt.source_stats && !h->d_src_stats) || (h->opt.source_health && !h->d_src_health))) return -EFAULT;  // (views do not allocate)
-	const bool one = records && h->opt.source_dc;
 	int r;
+	if (h->opt.source_iq) {
+		const int nsrc = h->nstreams / h->chan_per;
+		if (!h->d_siq_rows || !h->d_siq_sums || !h->d_siq_coef || d_iq != h->d_siq_rows.get()) return -EFAULT;
+		if ((size_t)nsrc * h->siq_stride > h->d_siq_rows.capacity() || (size_t)nblocks * h->cfg.block_len > h->siq_stride) return -E2BIG;
+		const int rs = h->src_rec_stride ? h->src_rec_stride : nblocks;
+		if (h->src_rec_off + (size_t)(nsrc - 1) * rs + nblocks > h->d_siq_sums.capacity()) return -E2BIG;
+		if ((r = siq::launch(raw, raw_stride, h->cfg.block_len, nblocks, nsrc, h->d_siq_coef, h->d_siq_rows, h->siq_stride,
+		                     h->d_siq_sums + h->src_rec_off, rs, h->opt.input_stats_nt != 0, h->stream)) < 0)
+			return r;
+	}
+	const bool one = records && h->opt.source_dc && !h->opt.source_iq;
 	if (h->opt.source_dc && (r = launch_source_dc(h, d_iq, stream_stride, nblocks, sin, sout, hist, one)) < 0) return r;
-	return records && !one ? launch_source_readers(h, d_iq, stream_stride, nblocks) : 0;
+	return records && !one ? launch_source_readers(h, raw, raw_stride, nblocks) : 0;
+}
+
+// Option source_iq: from here on the run's source rows are the handle's corrected rows (what the run was handed comes back
+// in raw / raw_stride for launch_source_side).  Before anything takes the frame's pointers.
+static void source_iq_redirect(RunFrame &f, const uint8_t **raw, size_t *raw_stride)
+{
+	*raw = f.d_iq; *raw_stride = f.stream_stride;
+	if (f.h->chan_per > 0 && f.h->opt.source_iq) {
+		f.d_iq = f.h->d_siq_rows;
+		f.stream_stride = f.h->siq_stride;
+	}
 }
 
 // ROUTE_STAGED and ROUTE_CHAN_MIX: a kernel per stage through the work buffers.  The timed pair holds the decimator with
@@ -2198,6 +2326,8 @@ static int run_staged(RunFrame &f)
 	const RunGeom &g = f.pl.g;
 	const int S = h->nstreams, nblocks = f.nblocks;
 	const uint32_t L = c.block_len;
+	const uint8_t *raw; size_t raw_stride;
+	source_iq_redirect(f, &raw, &raw_stride);
 	const uint8_t *d_iq = f.d_iq;
 	const size_t stream_stride = f.stream_stride;
 	hipStream_t q = f.q;
@@ -2215,7 +2345,7 @@ static int run_staged(RunFrame &f)
 		                                           h->d_rdc_avg);
 		rdc = h->d_rdc_avg;
 	}
-	if (h->chan_per > 0 && (r = launch_source_side(h, d_iq, stream_stride, nblocks, sin, sout, false)) < 0) return r;  // (no filter, no bank here: no history)
+	if (h->chan_per > 0 && (r = launch_source_side(h, raw, raw_stride, d_iq, stream_stride, nblocks, sin, sout, false)) < 0) return r;  // (no filter, no bank here: no history)
 	if (h->chan_per > 0 && h->opt.source_dc) {  // ... behind option source_dc's pre-pass
 		channel::k_channel_mix<true><<<grid_for((size_t)S * nblocks * (L / 16)), 256, 0, q>>>(d_iq, stream_stride, L, nblocks, S, h->chan_per,
 		                                                                                  h->d_chan_steps, h->d_chan_table,
@@ -2697,10 +2827,12 @@ static int run_channels(RunFrame &f)
 	rtlfm_gpu *h = f.h;
 	const int route = f.pl.route;
 	ChanRun cr{f.pl.g};
+	const uint8_t *raw; size_t raw_stride;
+	source_iq_redirect(f, &raw, &raw_stride);
 	int r = chan_run_prepare(f, cr);
 	if (r < 0) return r;
 	if ((r = timing_begin(h, f.ev)) < 0) return r;
-	if ((r = launch_source_side(h, f.d_iq, f.stream_stride, f.nblocks, cr.sin, cr.sout, route != RTLFM_ROUTE_CHAN_BOXCAR)) < 0) return r;
+	if ((r = launch_source_side(h, raw, raw_stride, f.d_iq, f.stream_stride, f.nblocks, cr.sin, cr.sout, route != RTLFM_ROUTE_CHAN_BOXCAR)) < 0) return r;
 	switch (route) {
 	case RTLFM_ROUTE_CHAN_BOXCAR: r = launch_channel_boxcar(h, cr); break;
 	case RTLFM_ROUTE_CHAN_FIR: r = launch_channel_fir(h, true, cr); break;
@@ -3037,8 +3169,8 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 		if (g < 0) return g;
 	}
 	if (!h->src_rec_stride) {  // (the same)
-		const int e = ensure_source_records(h);
-		if (e < 0) return e;
+		int e = ensure_source_records(h);
+		if (e < 0 || (e = ensure_source_iq(h)) < 0) return e;
 	}
 	// the survey: of every run the bank takes while the option is on (both executions of a verified run write the same set:
 	// each stores, neither adds)
@@ -3065,6 +3197,7 @@ static int run_device_impl(rtlfm_gpu *h, const uint8_t *d_iq, size_t stream_stri
 	h->gate_nblocks = h->opt.squelch_gate ? nblocks : 0;
 	h->src_stats_nblocks = h->chan_per > 0 && h->opt.source_stats ? nblocks : 0;
 	h->src_health_nblocks = h->chan_per > 0 && h->opt.source_health ? nblocks : 0;
+	h->siq_nblocks = h->chan_per > 0 && h->opt.source_iq ? nblocks : 0;
 	return 0;
 }
 
@@ -3153,6 +3286,17 @@ extern "C" int rtlfm_gpu_source_health(rtlfm_gpu *h, int source, rtlfm_input_hea
 extern "C" int rtlfm_gpu_source_health_all(rtlfm_gpu *h, rtlfm_input_health *out, int cap, int *n)
 {
 	return fetch_records(h, &rtlfm_gpu::d_src_health, &rtlfm_gpu::src_health_nblocks, source_health_on, true, 0, out, cap, n, true);
+}
+
+// The last run's second moments per SOURCE (option source_iq, k_source_iq): the same contract
+static bool source_iq_on(const rtlfm_gpu *h) { return h->opt.source_iq != 0 && h->chan_per > 0 && h->siq_nblocks > 0; }
+extern "C" int rtlfm_gpu_source_iq_sums(rtlfm_gpu *h, int source, rtlfm_iq_sums *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_siq_sums, &rtlfm_gpu::siq_nblocks, source_iq_on, false, source, out, cap, n, true);
+}
+extern "C" int rtlfm_gpu_source_iq_sums_all(rtlfm_gpu *h, rtlfm_iq_sums *out, int cap, int *n)
+{
+	return fetch_records(h, &rtlfm_gpu::d_siq_sums, &rtlfm_gpu::siq_nblocks, source_iq_on, true, 0, out, cap, n, true);
 }
 
 // The raw-byte readers as standalone operators on device memory (no handle): tools/input_stats_bench.py times them, and a
@@ -3702,7 +3846,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	if (h->opt.input_health && (r = ensure_input_health(h)) < 0) return r;
 	if (h->opt.squelch_gate && (r = ensure_gate(h)) < 0) return r;
 	if (h->chan_per > 0 && (r = ensure_channel_buffers(h)) < 0) return r;
-	if ((r = ensure_source_records(h)) < 0) return r;
+	if ((r = ensure_source_records(h)) < 0 || (r = ensure_source_iq(h)) < 0) return r;
 	OWN_TRY(in->d_tmp.alloc((size_t)S * in->ostride));
 	OWN_TRY(in->d_tmp_len.alloc((size_t)S));
 	// The views run their audio tail on the handle's main stream: the tails of the two previous
@@ -3771,6 +3915,7 @@ static int run_ragged(rtlfm_gpu *h, Ingest *in, int f, int nb)
 	h->gate_nblocks = h->opt.squelch_gate ? nb : 0;
 	h->src_stats_nblocks = h->chan_per > 0 && h->opt.source_stats ? nb : 0;
 	h->src_health_nblocks = h->chan_per > 0 && h->opt.source_health ? nb : 0;
+	h->siq_nblocks = h->chan_per > 0 && h->opt.source_iq ? nb : 0;
 	survey_advance(h, -1);  // (a run of short buffers carries no survey: rtlfm_gpu_bank_survey says -ENODATA)
 	HIP_TRY(hipGetLastError());
 	return 0;

@@ -22,7 +22,8 @@ class GpuDemod:
 
     def __init__(self, cfg: RtlfmCfg, nstreams: int = 1, device: int = 0, lib_path: str | None = None,
                  options: dict | None = None, squelch_gate: bool | None = None, conseq_squelch: int | None = None,
-                 source_dc: bool | None = None, source_stats: bool | None = None, source_health: bool | None = None):
+                 source_dc: bool | None = None, source_stats: bool | None = None, source_health: bool | None = None,
+                 source_iq: bool | None = None):
         self.lib = capi.load(lib_path)  # lib_path: another build of the library (A/B measurements)
         self.cfg = cfg
         self.nstreams = nstreams
@@ -47,6 +48,9 @@ class GpuDemod:
             self.set_option("source_stats", int(bool(source_stats)))
         if source_health is not None:
             self.set_option("source_health", int(bool(source_health)))
+        # IQ balance per source, measured and applied on the device (include/rtlfm_hip.h, option source_iq)
+        if source_iq is not None:
+            self.set_option("source_iq", int(bool(source_iq)))
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -254,6 +258,31 @@ class GpuDemod:
     def source_health_all(self) -> np.ndarray:
         """The same for every source in one copy: records [sources, buffers of the last run]."""
         return self._source_records("rtlfm_gpu_source_health", capi.INPUT_HEALTH_DTYPE, None)
+
+    def source_iq_sums(self, source: int = 0) -> np.ndarray:
+        """The second moments of the RAW bytes of SOURCE ``source`` per buffer of the last run that channels took (records of
+        ``capi.IQ_SUMS_DTYPE``): needs channels on and ``set_option("source_iq", 1)`` before the run."""
+        return self._source_records("rtlfm_gpu_source_iq_sums", capi.IQ_SUMS_DTYPE, source)
+
+    def source_iq_sums_all(self) -> np.ndarray:
+        """The same for every source in one copy: records [sources, buffers of the last run]."""
+        return self._source_records("rtlfm_gpu_source_iq_sums", capi.IQ_SUMS_DTYPE, None)
+
+    def set_source_iq(self, coef):
+        """rtlfm_gpu_set_source_iq: the Q14 coefficients (a, b, p, q) of every source, int16 [sources, 4].  No wait: runs
+        already queued use the old coefficients, later runs the new."""
+        c = np.ascontiguousarray(coef, dtype=np.int16)
+        nsrc = self.nstreams // self._per_source if self._per_source else 0
+        if self._per_source and c.size != nsrc * 4:
+            raise ValueError(f"four coefficients per source: {nsrc} sources, not {c.shape}")
+        check(self.lib.rtlfm_gpu_set_source_iq(self._h, c.ctypes.data), "rtlfm_gpu_set_source_iq")
+
+    def get_source_iq(self) -> np.ndarray:
+        """rtlfm_gpu_get_source_iq: the coefficients as they rule now, int16 [sources, 4]."""
+        nsrc = self.nstreams // self._per_source if self._per_source else self.nstreams
+        out = np.zeros((nsrc, 4), dtype=np.int16)
+        check(self.lib.rtlfm_gpu_get_source_iq(self._h, out.ctypes.data, out.size), "rtlfm_gpu_get_source_iq")
+        return out
 
     def gate(self, stream: int | None = None) -> np.ndarray:
         """The squelch gate's records of the last run (``set_option("squelch_gate", 1)`` before it): a record array with
